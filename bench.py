@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the EPI depth scan on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path (K1 edge confidence, compaction, K2 scan, K3
@@ -181,6 +181,36 @@ def rows_cpu_baseline(kind: str, cfg: dict, budget_s: float = 12.0) -> dict:
                           rows, cfg["U"], cfg["S"], cfg["C"], cfg["D"], reps, elapsed)}
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # the arrays of one dump, under 64 MB with their .npy headers
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs DIR: every array the timed path handed back in its last step, as DIR/<name>.npy, float64 kept and
+    everything else (float32, int32 indices, uint8 masks: all exact) as float32.  Over the budget, every array keeps the
+    same seeded sample of its leading axis (scanlines of the pile planes, views of the sweep / fine-to-coarse volumes),
+    so two builds dump the same elements."""
+    import torch
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / total) if total else 1.0
+    if keep < 1.0:
+        for name, a in host.items():
+            n = int(a.shape[0] * keep)
+            if n < 1:
+                raise SystemExit("--dump-outputs: one slice of %s (%s) exceeds the %d-byte budget" % (name, a.shape, DUMP_BUDGET_BYTES))
+            idx = np.sort(np.random.default_rng(20261015).choice(a.shape[0], n, replace=False))
+            host[name] = np.ascontiguousarray(a[idx])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print("dumped %s to %s (%.1f MB%s)" % (", ".join(sorted(host)), out_dir, sum(a.nbytes for a in host.values()) / 1e6,
+                                           "" if keep >= 1.0 else ", a seeded sample of %.0f %% of the leading axis" % (keep * 100)),
+          file=sys.stderr)
+
+
 def apply_bench_hooks(ctx) -> None:
     """RSLF_BENCH_HOOKS="px=0,share=2,groups=8,lds=64": rslf_ctx_set_debug hooks for developer A/B runs (never a result)."""
     if os.environ.get("RSLF_BENCH_HOOKS"):
@@ -227,6 +257,8 @@ def bench_sweep2d(args) -> None:
         comp.run(want_stats=False)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, comp.results())
     roof = rows_roofline(ctx, lambda: (comp.run(want_stats=False), torch.cuda.synchronize()), units, S, C, elapsed / args.steps * 1e3)
     line = {
         "metric": "Mpixel*disparity-hypotheses/s", "value": units / (elapsed / args.steps) / 1e6, "unit": "Mpixel*hyp/s",
@@ -263,17 +295,19 @@ def bench_f2c(args) -> None:
         f.run()
         m, v = f.get_results()
         torch.cuda.synchronize()
-        return f
+        return f, m, v
 
     f = None
     for _ in range(max(args.warmup, 1)):
-        f = once()
+        f = once()[0]
     units = sum(int(c.stats.units) for c in f.m_computers)
     dims = [(c.m_epis.V, c.m_epis.U) for c in f.m_computers]
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        once()
+        last = once()[1:]
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(out_map=last[0], out_validity=last[1]))
     roof = rows_roofline(rs.default_context(), once, units, S, C, elapsed / args.steps * 1e3)
     line = {
         "metric": "Mpixel*disparity-hypotheses/s", "value": units / (elapsed / args.steps) / 1e6, "unit": "Mpixel*hyp/s",
@@ -311,13 +345,15 @@ def bench_e2e(args) -> None:
     m = rs.MultiDevice(devices)
     peer = m.peer_access()
     ts, units = [], 0
-    calls = max(2, args.steps + 1) if host.nbytes <= (4 << 30) else 3
+    calls = args.steps + 1
     for _ in range(calls):
         t0 = time.perf_counter()
         out = m.depth1d_pile(epis, cfg["dmin"], cfg["dmax"], D, epi_scale_factor=1.0)
         ts.append(time.perf_counter() - t0)
     units = int((out["edge_mask"] > 0).sum()) * D
     m.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     t = sorted(ts[1:])[(calls - 1) // 2]
     print(json.dumps({
         "metric": "Mpixel*disparity-hypotheses/s", "value": None, "unit": "Mpixel*hyp/s", "n_gpus": len(devices), "path": "e2e",
@@ -361,7 +397,13 @@ def main() -> None:
     ap.add_argument("--path", default="pile", choices=["pile", "sweep2d", "f2c", "e2e"],
                     help="pile = Depth1DComputer_pile::run (the headline path); sweep2d = Depth2DComputer::run, the 'next' row "
                          "(all views, centre outwards, with propagation), 1 GPU only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     args.config_given = args.config is not None
     args.config = args.config or "c3"
     if args.path == "e2e":      # one process, N devices behind the C-ABI (no ranks)
@@ -463,6 +505,8 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)   # before the stats pass below reuses the planes
 
     # units = mask-selected pixels actually scanned x hypotheses, owned rows only:
     # the scan mask on entry is the edge mask K1 produces (core.hpp:513)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the committed golden fixtures under tests/golden/.
 
-    python tests/golden/make_golden.py          (run in the build container)
+    python tests/golden/make_golden.py [REFERENCE/data/000.tif]
 
 What is pinned and by what
 --------------------------
@@ -14,10 +14,11 @@ GPU tests fixed expected values; they do not pin the oracle to the reference
 ("parity unpinned", DESIGN.md).
 
 Inputs: seeded synthetic volumes, and one data file of the reference:
-/root/reference/data/000.tif (960x540 float32, the input of BASELINE.json
-configs[0]) -- decoded, as data, whole (c1_000tif_960x540_f32.npz) and as a
-24-row crop -- normalised by the max of the WHOLE image as
-Depth1DComputer_pile's constructor would (dc.hpp:442-477).
+data/000.tif (960x540 float32, the input of BASELINE.json configs[0]), given
+on the command line -- decoded, as data, whole (c1_000tif_960x540_f32.npz) and
+as a 24-row crop -- normalised by the max of the WHOLE image as
+Depth1DComputer_pile's constructor would (dc.hpp:442-477).  Without it the
+committed decoded frame and crop are reused.
 """
 from __future__ import annotations
 
@@ -35,7 +36,7 @@ import oracle  # noqa: E402
 from oracle import oracle_np as onp  # noqa: E402
 from remotesensingproject_amd.synth import make_lightfield  # noqa: E402
 
-TIF = "/root/reference/data/000.tif"
+TIF = sys.argv[1] if len(sys.argv) > 1 else ""
 OUT_KEYS = ("edge_confidence", "edge_mask", "disp_confidence", "depth", "rbar", "depth_idx", "score", "depth_raw")
 
 

@@ -216,13 +216,16 @@ def test_c1_anchor_recorded():
     assert abs(a["tif_max"] - 262.72208) < 1e-4
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/000.tif"), reason="reference data file not present on this box")
 def test_c1_anchor_recomputed(oracle_mod):
-    from PIL import Image
-    img = np.array(Image.open("/root/reference/data/000.tif"), dtype=np.float32)
+    """The anchor and the 24-row crop recomputed from the committed decoded frame of data/000.tif."""
+    img = np.load(os.path.join(GOLD, "c1_000tif_960x540_f32.npz"))["image"]
+    a = json.load(open(os.path.join(GOLD, "c1_anchor.json")))
+    assert list(img.shape) == a["tif_shape"] and float(img.max()) == a["tif_max"]
     norm, scale = oracle_mod.normalize_f32(img[:, None, :, None], -1.0)
-    _, m = oracle_mod.edge_confidence_pile(np.ascontiguousarray(norm), 0)
+    assert scale == a["scale_used"]
+    Ce, m = oracle_mod.edge_confidence_pile(np.ascontiguousarray(norm), 0)
     assert int((m > 0).sum()) == 223271
+    assert int((Ce == 0).sum()) == a["shadow_cut_count"]
     crop = np.load(os.path.join(GOLD, "c1_crop_000tif_rows400_424.npy"))
     assert np.array_equal(crop, img[400:424])
 

@@ -1,6 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo" if os.path.exists("/root/repo/tools") else os.getcwd())
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
 from remotesensingproject_amd import depth as rs
