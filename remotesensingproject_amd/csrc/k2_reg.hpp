@@ -33,6 +33,113 @@ namespace rslf {
 constexpr int gather_batch(int c) { return c == 1 ? 8 : 4; }
 constexpr int kPadSlack = 16;     // compiled slot counts step by at most this: only the last kPadSlack slots can be padding
 
+// One mean-shift pass over the samples of a (pixel, hypothesis) unit held in registers: A[c] += R*K, B += K in ascending s
+// (core.hpp:589-606).  KONLY: B alone -- the last pass of a TRIM scan (A is left untouched).
+template <int SPAD, int C, bool PK, bool KONLY>
+__device__ __forceinline__ void mean_shift_pass(const float (&R)[PK ? 1 : C][PK ? 1 : SPAD], const f2 (&R2)[PK ? C : 1][PK ? SPAD / 2 : 1],
+                                                int S, float kq, const float (&rbar)[C], float (&A)[C], float& B)
+{
+    static_assert(!KONLY || (C == 1 && !PK), "the K-only pass is written for the scalar one-channel blocks");
+    if constexpr (PK) {
+        // a pair of samples per step: delta, kq*delta, q, K and R*K as packed instructions on both
+        // samples, then the sums take sample s and sample s+1 in turn (core.hpp:602-603 order)
+        f2 rb2[C];
+        const f2 kq2 = {kq, kq};
+#pragma unroll
+        for (int c = 0; c < C; c++)
+            rb2[c] = f2{rbar[c], rbar[c]};
+        // hand-scheduled blocks of 8 (C = 1) / 4 (C = 3) samples; the slots of a block that lie beyond S are
+        // padding (K = P = +0 exactly), whole blocks beyond S are skipped (wave-uniform)
+        constexpr int kBlk = (C == 1) ? 8 : 4;
+#pragma unroll
+        for (int s0 = 0; s0 < SPAD; s0 += kBlk) {
+            if (!(s0 < SPAD - kPadSlack || s0 < S))
+                continue;
+            if constexpr (C == 1) {
+                f2 P[4], K[4];
+                const f2 r4[4] = {R2[0][s0 / 2], R2[0][s0 / 2 + 1], R2[0][s0 / 2 + 2], R2[0][s0 / 2 + 3]};
+                mean_shift_pk_octet(r4, rb2[0], kq2, P, K);
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    A[0] = A[0] + P[j].x;                // core.hpp:602, ascending s
+                    B = B + K[j].x;                      // core.hpp:603
+                    A[0] = A[0] + P[j].y;
+                    B = B + K[j].y;
+                }
+            } else {
+                f2 Pa[3], Pb[3], Ka, Kb;
+                const f2 ra[3] = {R2[0][s0 / 2], R2[1][s0 / 2], R2[C - 1][s0 / 2]};
+                const f2 rb[3] = {R2[0][s0 / 2 + 1], R2[1][s0 / 2 + 1], R2[C - 1][s0 / 2 + 1]};
+                const f2 m[3] = {rb2[0], rb2[C > 1 ? 1 : 0], rb2[C - 1]};
+                mean_shift_pk_rgb_quad(ra, rb, m, kq2, Pa, Pb, Ka, Kb);
+#pragma unroll
+                for (int c = 0; c < C; c++)
+                    A[c] = A[c] + Pa[c].x;
+                B = B + Ka.x;
+#pragma unroll
+                for (int c = 0; c < C; c++)
+                    A[c] = A[c] + Pa[c].y;
+                B = B + Ka.y;
+#pragma unroll
+                for (int c = 0; c < C; c++)
+                    A[c] = A[c] + Pb[c].x;
+                B = B + Kb.x;
+#pragma unroll
+                for (int c = 0; c < C; c++)
+                    A[c] = A[c] + Pb[c].y;
+                B = B + Kb.y;
+            }
+        }
+    } else if (C == 1) {
+        // hand-scheduled, four samples per block (rslf_device.hpp).  Only the last kPadSlack slots can
+        // be padding: there a wave-uniform test skips what lies beyond S (a padded slot would add +0
+        // to both sums, so skipping it changes nothing but the instruction count).
+#pragma unroll
+        for (int s0 = 0; s0 < SPAD; s0 += 4) {
+            if (s0 + 4 <= SPAD - kPadSlack || s0 + 4 <= S) {
+                if constexpr (KONLY)
+                    mean_shift_group4_k(R[0][s0], R[0][s0 + 1], R[0][s0 + 2], R[0][s0 + 3], rbar[0], kq, B);
+                else
+                    mean_shift_group4(R[0][s0], R[0][s0 + 1], R[0][s0 + 2], R[0][s0 + 3], rbar[0], kq, A[0], B);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; j++)
+                    if (s0 + j < S) {
+                        if constexpr (KONLY)
+                            mean_shift_group1_k(R[0][s0 + j], rbar[0], kq, B);
+                        else
+                            mean_shift_group1(R[0][s0 + j], rbar[0], kq, A[0], B);
+                    }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < SPAD; s++) {
+            if (!(s < SPAD - kPadSlack || s < S))   // wave-uniform: padding slot
+                continue;
+            float q[C];
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                const float delta = R[c][s] - rbar[c];   // core.hpp:591
+                const float tq = kq * delta;             // kernels.cpp:21 / :43
+                q[c] = tq * delta;
+            }
+            float qs = q[0];
+            if (C == 3) {
+                qs = q[0] + q[C - 1];                    // OpenCV 3.x reduceC_: (q0 + q2) + q1
+                qs = qs + q[C > 1 ? 1 : 0];
+            }
+            const float K = kernel_weight(qs);           // kernels.cpp:23-25 / :51-53
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                const float pr = R[c][s] * K;            // core.cpp:28 / :36
+                A[c] = A[c] + pr;                        // core.hpp:602
+            }
+            B = B + K;                                   // core.hpp:603
+        }
+    }
+}
+
 // BORDER:    some sample line of this wave may leave [0, U-1]: test validity per sample.
 // UNIFORM_D: every pixel shares the hypothesis grid (no per-pixel dmin/dmax planes), so the
 //            view offset fl(fl(float(s_hat - s) * D[d]) * slope) is the same for all 64 lanes:
@@ -47,7 +154,10 @@ constexpr int kPadSlack = 16;     // compiled slot counts step by at most this: 
 //            itself, and a hypothesis costs it one memory round trip per batch.
 // LANE_D:    the lanes of the wave own HYPOTHESES of one pixel instead of pixels (k2_scan_reg_px): lane `dlane` scores
 //            d0 + dlane, d0 + dlane + dstep, ... below d1 (a lane past the end repeats d1 - 1 and offers nothing).
-template <int SPAD, int C, bool BORDER, bool UNIFORM_D, bool PK, int GB = 0, class BestT = Best<C>, bool LANE_D = false>
+// TRIM:      the last mean-shift pass sums K alone (the score) and `best` is offered the rbar that ENTERED it; the
+//            kernel's epilogue recomputes the last pass for the winning hypothesis of each pixel (last_pass_rbar).
+template <int SPAD, int C, bool BORDER, bool UNIFORM_D, bool PK, int GB = 0, class BestT = Best<C>, bool LANE_D = false,
+          bool TRIM = false>
 __device__ __forceinline__ void scan_reg_body(const ScanArgs& a, int v, int u, int d0, int d1, BestT& best,
                                               float* __restrict__ otab, int dlane = 0, int dstep = 1)
 {
@@ -222,97 +332,14 @@ __device__ __forceinline__ void scan_reg_body(const ScanArgs& a, int v, int u, i
             for (int c = 0; c < C; c++)
                 A[c] = 0.0f;
             B = 0.0f;
-            if constexpr (PK) {
-                // a pair of samples per step: delta, kq*delta, q, K and R*K as packed instructions on both
-                // samples, then the sums take sample s and sample s+1 in turn (core.hpp:602-603 order)
-                f2 rb2[C];
-                const f2 kq2 = {kq, kq};
-#pragma unroll
-                for (int c = 0; c < C; c++)
-                    rb2[c] = f2{rbar[c], rbar[c]};
-                // hand-scheduled blocks of 8 (C = 1) / 4 (C = 3) samples; the slots of a block that lie beyond S are
-                // padding (K = P = +0 exactly), whole blocks beyond S are skipped (wave-uniform)
-                constexpr int kBlk = (C == 1) ? 8 : 4;
-#pragma unroll
-                for (int s0 = 0; s0 < SPAD; s0 += kBlk) {
-                    if (!(s0 < SPAD - kPadSlack || s0 < S))
-                        continue;
-                    if constexpr (C == 1) {
-                        f2 P[4], K[4];
-                        const f2 r4[4] = {R2[0][s0 / 2], R2[0][s0 / 2 + 1], R2[0][s0 / 2 + 2], R2[0][s0 / 2 + 3]};
-                        mean_shift_pk_octet(r4, rb2[0], kq2, P, K);
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            A[0] = A[0] + P[j].x;                // core.hpp:602, ascending s
-                            B = B + K[j].x;                      // core.hpp:603
-                            A[0] = A[0] + P[j].y;
-                            B = B + K[j].y;
-                        }
-                    } else {
-                        f2 Pa[3], Pb[3], Ka, Kb;
-                        const f2 ra[3] = {R2[0][s0 / 2], R2[1][s0 / 2], R2[C - 1][s0 / 2]};
-                        const f2 rb[3] = {R2[0][s0 / 2 + 1], R2[1][s0 / 2 + 1], R2[C - 1][s0 / 2 + 1]};
-                        const f2 m[3] = {rb2[0], rb2[C > 1 ? 1 : 0], rb2[C - 1]};
-                        mean_shift_pk_rgb_quad(ra, rb, m, kq2, Pa, Pb, Ka, Kb);
-#pragma unroll
-                        for (int c = 0; c < C; c++)
-                            A[c] = A[c] + Pa[c].x;
-                        B = B + Ka.x;
-#pragma unroll
-                        for (int c = 0; c < C; c++)
-                            A[c] = A[c] + Pa[c].y;
-                        B = B + Ka.y;
-#pragma unroll
-                        for (int c = 0; c < C; c++)
-                            A[c] = A[c] + Pb[c].x;
-                        B = B + Kb.x;
-#pragma unroll
-                        for (int c = 0; c < C; c++)
-                            A[c] = A[c] + Pb[c].y;
-                        B = B + Kb.y;
-                    }
-                }
-            } else if (C == 1) {
-                // hand-scheduled, four samples per block (rslf_device.hpp).  Only the last kPadSlack slots can
-                // be padding: there a wave-uniform test skips what lies beyond S (a padded slot would add +0
-                // to both sums, so skipping it changes nothing but the instruction count).
-#pragma unroll
-                for (int s0 = 0; s0 < SPAD; s0 += 4) {
-                    if (s0 + 4 <= SPAD - kPadSlack || s0 + 4 <= S) {
-                        mean_shift_group4(R[0][s0], R[0][s0 + 1], R[0][s0 + 2], R[0][s0 + 3], rbar[0], kq, A[0], B);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 3; j++)
-                            if (s0 + j < S)
-                                mean_shift_group1(R[0][s0 + j], rbar[0], kq, A[0], B);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int s = 0; s < SPAD; s++) {
-                    if (!(s < SPAD - kPadSlack || s < S))   // wave-uniform: padding slot
-                        continue;
-                    float q[C];
-#pragma unroll
-                    for (int c = 0; c < C; c++) {
-                        const float delta = R[c][s] - rbar[c];   // core.hpp:591
-                        const float tq = kq * delta;             // kernels.cpp:21 / :43
-                        q[c] = tq * delta;
-                    }
-                    float qs = q[0];
-                    if (C == 3) {
-                        qs = q[0] + q[C - 1];                    // OpenCV 3.x reduceC_: (q0 + q2) + q1
-                        qs = qs + q[C > 1 ? 1 : 0];
-                    }
-                    const float K = kernel_weight(qs);           // kernels.cpp:23-25 / :51-53
-#pragma unroll
-                    for (int c = 0; c < C; c++) {
-                        const float pr = R[c][s] * K;            // core.cpp:28 / :36
-                        A[c] = A[c] + pr;                        // core.hpp:602
-                    }
-                    B = B + K;                                   // core.hpp:603
+            if constexpr (TRIM) {
+                if (it == a.k.n_iter - 1) {
+                    // the last pass sums K alone, and rbar stays the one that entered it (LastPassRbar)
+                    mean_shift_pass<SPAD, C, PK, true>(R, R2, S, kq, rbar, A, B);
+                    break;
                 }
             }
+            mean_shift_pass<SPAD, C, PK, false>(R, R2, S, kq, rbar, A, B);
 #pragma unroll
             for (int c = 0; c < C; c++) {
                 const float qd = (B != 0.0f) ? (A[c] / B) : 0.0f;   // core.cpp:42 / :50, OpenCV 3.x: /0 -> 0
@@ -326,6 +353,88 @@ __device__ __forceinline__ void scan_reg_body(const ScanArgs& a, int v, int u, i
             best.offer(sc, d, Dd, rbar);
     }
 }
+
+// The last mean-shift pass of ONE (pixel, hypothesis), from the rbar that entered it: what a TRIM scan leaves out for every
+// hypothesis but the winner.  The samples are gathered again with scan_reg_body's per-lane arithmetic (the uniform-D
+// offset table holds the same values: float(s_hat) - float(s) is float(s_hat - s) exactly), out-of-range ones are
+// kSentinel, and the pass is mean_shift_pass's: the K values are those whose sum is the stored score's numerator, added
+// in the same order, so the rbar is bit-identical to the one a full last pass would have left.  n_iter == 0: no pass,
+// rbar stays the centre.
+template <int C>
+struct LastPassRbar {
+    __device__ __forceinline__ void operator()(const ScanArgs& a, long long o, float Dd, float (&rbar)[C]) const
+    {
+        if (a.k.n_iter == 0)
+            return;
+        const VolView& vol = a.vol;
+        const int v = (int)(o / vol.U);
+        const int u = (int)(o - (long long)v * vol.U);
+        const float* epi = vol.row(v, 0);
+        const float uf = (float)u;
+        const unsigned Um1_bits = __float_as_uint((float)(vol.U - 1));
+        const float kq = (C == 1) ? a.k.k1 : a.k.inv_h2;
+        const float Ss0 = (float)a.s_hat;
+        const int S = vol.S;
+        float A[C];
+#pragma unroll
+        for (int c = 0; c < C; c++)
+            A[c] = 0.0f;
+        float B = 0.0f;
+        constexpr int kBatch = 8;   // loads in flight
+#pragma unroll 1
+        for (int s0 = 0; s0 < S; s0 += kBatch) {
+            float R[C][kBatch];
+#pragma unroll
+            for (int j = 0; j < kBatch; j++) {
+                const int s = min(s0 + j, S - 1);   // (past S: a valid address, the sample is not used)
+                float x = (Ss0 - (float)s) * Dd;   // core.hpp:542,550
+                x = x * a.k.slope;                 // core.hpp:551
+                x = x + uf;                        // core.hpp:552
+                const float t = lerp_weight(x);    // interp.hpp:179-181
+                const bool ok = __float_as_uint(x) <= Um1_bits;   // interp.hpp:182 (x is never -0)
+                const int i0 = ok ? floor_to_int(x) : 0;
+                const float* p = epi + (long long)s * vol.stride_s + i0 * C;
+                const float omt = 1.0f - t;
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    const float m0 = omt * p[c];   // interp.hpp:184
+                    const float m1 = t * p[C + c];
+                    const float r = m0 + m1;
+                    R[c][j] = ok ? r : kSentinel;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kBatch; j++) {
+                if (s0 + j >= S)
+                    break;
+                float q[C];
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    const float delta = R[c][j] - rbar[c];   // core.hpp:591
+                    const float tq = kq * delta;             // kernels.cpp:21 / :43
+                    q[c] = tq * delta;
+                }
+                float qs = q[0];
+                if (C == 3) {
+                    qs = q[0] + q[C - 1];                    // OpenCV 3.x reduceC_: (q0 + q2) + q1
+                    qs = qs + q[C > 1 ? 1 : 0];
+                }
+                const float K = kernel_weight(qs);           // kernels.cpp:23-25 / :51-53
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    const float pr = R[c][j] * K;            // core.cpp:28 / :36
+                    A[c] = A[c] + pr;                        // core.hpp:602
+                }
+                B = B + K;                                   // core.hpp:603
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const float qd = (B != 0.0f) ? (A[c] / B) : 0.0f;   // core.cpp:42 / :50, OpenCV 3.x: /0 -> 0
+            rbar[c] = (qd > 0.0f) ? qd : 0.0f;                  // core.hpp:609
+        }
+    }
+};
 
 // Waves per SIMD the register budget allows: C*SPAD sample registers + ~64 working registers
 // (a batch of in-flight samples, the per-pixel state, SGPR overflow lanes), in the hardware's
@@ -365,12 +474,22 @@ constexpr bool scan_reg_best_in_lds(int spad, int c)
 // saturated by scalar instructions and packed ones run at half rate.
 constexpr bool scan_reg_packed_math(int spad, int c) { return scan_reg_waves(spad, c) == 1; }
 
+// The row kernels whose scan is TRIM (one channel, scalar math): not the ones that already run a wave per SIMD more than
+// their registers allow (scan_reg_waves' measured exceptions, which carry scratch by design): the value the split keeps
+// live adds to their spill.  Their last pass stays whole.
+constexpr bool scan_reg_trim(int spad, int c)
+{
+    return c == 1 && !scan_reg_packed_math(spad, c) && spad != 48 && !(spad >= 80 && spad <= 88) && !(spad > 112 && spad <= 144);
+}
+template <int SPAD, int C>
+using ScanRegRbarFix = std::conditional_t<scan_reg_trim(SPAD, C), LastPassRbar<C>, NoRbarFix>;
+
 template <int SPAD, int C, class BestT>
 __device__ __forceinline__ void scan_reg_rows(const ScanArgs& a, int v, int u, int d0, int d1, BestT& best, float* otab)
 {
     constexpr bool PK = scan_reg_packed_math(SPAD, C);
     if (a.dmin_vu) {
-        scan_reg_body<SPAD, C, true, false, PK, 0, BestT>(a, v, u, d0, d1, best, otab);
+        scan_reg_body<SPAD, C, true, false, PK, 0, BestT, false, scan_reg_trim(SPAD, C)>(a, v, u, d0, d1, best, otab);
         return;
     }
     // the validity test is decided per hypothesis, as in the streaming kernel (scan_stream_rows): runs of hypotheses whose
@@ -389,9 +508,9 @@ __device__ __forceinline__ void scan_reg_rows(const ScanArgs& a, int v, int u, i
         while (e < d1 && interior(e) == in)
             e++;
         if (in)
-            scan_reg_body<SPAD, C, false, true, PK, 0, BestT>(a, v, u, d, e, best, otab);
+            scan_reg_body<SPAD, C, false, true, PK, 0, BestT, false, scan_reg_trim(SPAD, C)>(a, v, u, d, e, best, otab);
         else
-            scan_reg_body<SPAD, C, true, true, PK, 0, BestT>(a, v, u, d, e, best, otab);
+            scan_reg_body<SPAD, C, true, true, PK, 0, BestT, false, scan_reg_trim(SPAD, C)>(a, v, u, d, e, best, otab);
         d = e;
     }
 }
@@ -405,12 +524,13 @@ void k2_scan_reg(ScanArgs a)
     constexpr bool kEpiDyn = false;
     float* const epi_lds = nullptr;
     const int epi_stride = 0;
+    using Fix = ScanRegRbarFix<SPAD, C>;
     if constexpr (scan_reg_best_in_lds(SPAD, C)) {
         __shared__ float s_best[kScanWaves][BestLds<C>::kFloats];
         BestLds<C> running(s_best[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
-        RSLF_SCAN_ROW_TILE((running.init(), scan_reg_rows<SPAD, C>(a, v, u, d0, d1, running, otab), running.load(best)))
+        RSLF_SCAN_ROW_TILE_FIX((running.init(), scan_reg_rows<SPAD, C>(a, v, u, d0, d1, running, otab), running.load(best)), Fix{})
     } else {
-        RSLF_SCAN_ROW_TILE((scan_reg_rows<SPAD, C>(a, v, u, d0, d1, best, otab)))
+        RSLF_SCAN_ROW_TILE_FIX((scan_reg_rows<SPAD, C>(a, v, u, d0, d1, best, otab)), Fix{})
     }
 }
 

@@ -260,18 +260,31 @@ __device__ __forceinline__ float hypothesis(float dmin, float range, float denom
     return dmin + quo;
 }
 
+// What the epilogue does to the winner's rbar before it is written: nothing, where the scan offered the final one.  A
+// kernel whose scan offers the rbar that entered the last pass hands in the functor that runs that pass
+// (LastPassRbar, k2_reg.hpp): fix(a, pixel index, disparity, rbar in / out).
+struct NoRbarFix {
+    template <int C>
+    __device__ __forceinline__ void operator()(const ScanArgs&, long long, float, float (&)[C]) const {}
+};
+
 // core.hpp:636-657 for one pixel once every hypothesis is scored.
-template <int C>
+template <int C, class Fix = NoRbarFix>
 __device__ __forceinline__ void write_pixel(const ScanArgs& a, long long o, float best, int best_d, float best_D,
-                                            const float (&best_rbar)[C], double sum)
+                                            const float (&best_rbar)[C], double sum, const Fix& fix = Fix{})
 {
     if ((double)best > (double)a.k.raw_thr) {   // core.hpp:636
         a.depth[o] = best_D;
         const double mean = sum / (double)a.dim_d;
         a.Cd[o] = (float)((double)a.Ce[o] * fabs((double)best - mean));   // core.hpp:641
+        float rb[C];
 #pragma unroll
         for (int c = 0; c < C; c++)
-            a.rbar[o * C + c] = best_rbar[c];
+            rb[c] = best_rbar[c];
+        fix(a, o, best_D, rb);
+#pragma unroll
+        for (int c = 0; c < C; c++)
+            a.rbar[o * C + c] = rb[c];
         if (a.idx)
             a.idx[o] = best_d;
         if (a.score)
@@ -370,8 +383,8 @@ __device__ __forceinline__ unsigned load_coherent(const unsigned* p)
 
 constexpr int kRecordWords = 8;
 
-template <int C>
-__device__ __forceinline__ void combine_tile(const ScanArgs& a, int tile, int v, int u, int lane);
+template <int C, class Fix>
+__device__ __forceinline__ void combine_tile(const ScanArgs& a, int tile, int v, int u, int lane, const Fix& fix);
 
 // Merge the waves' partial results in hypothesis order (first maximum wins, cv::minMaxLoc) and either
 // write the pixel (groups == 1) or leave this group's record -- the last group to finish merges the records.
@@ -389,10 +402,10 @@ struct EpilogueBlock {
         : sum(base), score(reinterpret_cast<float*>(base + 64)), D(score + 64), rbar(D + 64), d(reinterpret_cast<int*>(rbar + C * 64)) {}
 };
 
-template <int C, bool DYN = false>
+template <int C, bool DYN = false, class Fix = NoRbarFix>
 __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, int lb, int v, int u, bool active, const Best<C>& mine,
                                               float* wave_lds = nullptr, int wave_stride = 0, int lane = threadIdx.x & 63,
-                                              int wave = threadIdx.x >> 6)
+                                              int wave = threadIdx.x >> 6, const Fix& fix = Fix{})
 {
     __shared__ double s_static[DYN ? 1 : kScanWaves][DYN ? 1 : EpilogueBlock<C>::kDoubles];
     auto block_of = [&](int w) {
@@ -468,18 +481,18 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, int lb, int v, 
             return;
         asm volatile("" ::: "memory");
         if (active)
-            combine_tile<C>(a, tile, v, u, lane);
+            combine_tile<C>(a, tile, v, u, lane, fix);
         if (lane == 0)
             a.ticket[tile] = 0;   // clean for the next launch (kernel boundary orders it)
         return;
     }
     if (active)
-        write_pixel<C>(a, (long long)v * a.vol.U + u, best, best_d, best_D, best_rbar, sum);
+        write_pixel<C>(a, (long long)v * a.vol.U + u, best, best_d, best_D, best_rbar, sum, fix);
 }
 
 // groups > 1: the wave that drew the tile's last ticket merges the groups' records in hypothesis order and writes the pixels.
-template <int C>
-__device__ __forceinline__ void combine_tile(const ScanArgs& a, int tile, int v, int u, int lane)
+template <int C, class Fix>
+__device__ __forceinline__ void combine_tile(const ScanArgs& a, int tile, int v, int u, int lane, const Fix& fix)
 {
     const unsigned* pr = reinterpret_cast<const unsigned*>(a.partial) + ((long long)tile * a.groups * kRecordWords * 64 + lane);
     float best = -1.0f, best_D = 0.0f;
@@ -520,7 +533,7 @@ __device__ __forceinline__ void combine_tile(const ScanArgs& a, int tile, int v,
             }
         }
     }
-    write_pixel<C>(a, (long long)v * a.vol.U + u, best, best_d, best_D, best_rbar, sum);
+    write_pixel<C>(a, (long long)v * a.vol.U + u, best, best_d, best_D, best_rbar, sum, fix);
 }
 
 // ---------------------------------------------------------------------------
@@ -655,7 +668,8 @@ __device__ __forceinline__ int packed_groups(int groups, int tiles, int adapt)
 // every wave of a workgroup makes the same trips, and the epilogue's second barrier separates one item's
 // merge in LDS from the next item's.
 #define RSLF_SCAN_PACKED_LOOP(PACKED_CALL) RSLF_SCAN_PACKED_LOOP_(scan_chunk, PACKED_CALL)
-#define RSLF_SCAN_ROW_TILE(ROWS_CALL) RSLF_SCAN_ROW_TILE_(scan_chunk, ROWS_CALL)
+#define RSLF_SCAN_ROW_TILE(ROWS_CALL) RSLF_SCAN_ROW_TILE_(scan_chunk, ROWS_CALL, NoRbarFix{})
+#define RSLF_SCAN_ROW_TILE_FIX(ROWS_CALL, FIX) RSLF_SCAN_ROW_TILE_(scan_chunk, ROWS_CALL, FIX)
 #define RSLF_SCAN_PACKED_LOOP_(CHUNK, PACKED_CALL)                                      \
     {                                                                                   \
         const int n = *a.packed_n;                                                      \
@@ -676,7 +690,7 @@ __device__ __forceinline__ int packed_groups(int groups, int tiles, int adapt)
             }                                                                           \
         }                                                                               \
     }
-#define RSLF_SCAN_ROW_TILE_(CHUNK, ROWS_CALL)                                           \
+#define RSLF_SCAN_ROW_TILE_(CHUNK, ROWS_CALL, FIX)                                      \
     {                                                                                   \
         Best<C> best;                                                                   \
         int v, u, d0, d1;                                                               \
@@ -688,14 +702,15 @@ __device__ __forceinline__ int packed_groups(int groups, int tiles, int adapt)
         CHUNK(a, lb % a.groups, d0, d1);                                                \
         best.init();                                                                    \
         ROWS_CALL;                                                                      \
-        scan_epilogue<C, kEpiDyn>(a, lb, v, u, active, best, epi_lds, epi_stride);      \
+        scan_epilogue<C, kEpiDyn>(a, lb, v, u, active, best, epi_lds, epi_stride,       \
+                                  threadIdx.x & 63, threadIdx.x >> 6, FIX);             \
     }
 #define RSLF_SCAN_KERNEL_BODY_(CHUNK, ROWS_CALL, PACKED_CALL)                           \
     if (a.packed) {                                                                     \
         RSLF_SCAN_PACKED_LOOP_(CHUNK, PACKED_CALL)                                      \
         return;                                                                         \
     }                                                                                   \
-    RSLF_SCAN_ROW_TILE_(CHUNK, ROWS_CALL)
+    RSLF_SCAN_ROW_TILE_(CHUNK, ROWS_CALL, NoRbarFix{})
 #define RSLF_SCAN_KERNEL_BODY(ROWS_CALL, PACKED_CALL) RSLF_SCAN_KERNEL_BODY_(scan_chunk, ROWS_CALL, PACKED_CALL)
 
 template <int C>

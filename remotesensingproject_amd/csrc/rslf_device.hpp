@@ -246,6 +246,49 @@ __device__ __forceinline__ void mean_shift_group1(float r0, float rbar, float k1
         : "v"(r0), "v"(rbar), "s"(k1));
 }
 
+// The LAST pass of the register scan needs only B = sum of K: its score is B / card, and the A / B it would give is the
+// rbar of a hypothesis only where that hypothesis wins the pixel, where it is recomputed once (last_pass_rbar, k2_reg.hpp).
+// These are the blocks above without P = R*K and A += P, same K, same order of the adds to B.
+//   delta = R - rbar ; t = k1*delta ; q = t*delta ; K = clamp(1 - q) ; B += K                ( 5 VALU / sample )
+__device__ __forceinline__ void mean_shift_group4_k(float r0, float r1, float r2, float r3, float rbar, float k1, float& B)
+{
+    float t0, t1, t2, t3, u0, u1, u2, u3;
+    asm("v_sub_f32 %1, %9, %13\n\t"
+        "v_sub_f32 %2, %10, %13\n\t"
+        "v_sub_f32 %3, %11, %13\n\t"
+        "v_sub_f32 %4, %12, %13\n\t"
+        "v_mul_f32 %5, %14, %1\n\t"
+        "v_mul_f32 %6, %14, %2\n\t"
+        "v_mul_f32 %7, %14, %3\n\t"
+        "v_mul_f32 %8, %14, %4\n\t"
+        "v_mul_f32 %1, %1, %5\n\t"
+        "v_mul_f32 %2, %2, %6\n\t"
+        "v_mul_f32 %3, %3, %7\n\t"
+        "v_mul_f32 %4, %4, %8\n\t"
+        "v_sub_f32_e64 %1, 1.0, %1 clamp\n\t"
+        "v_sub_f32_e64 %2, 1.0, %2 clamp\n\t"
+        "v_add_f32 %0, %0, %1\n\t"
+        "v_sub_f32_e64 %3, 1.0, %3 clamp\n\t"
+        "v_add_f32 %0, %0, %2\n\t"
+        "v_sub_f32_e64 %4, 1.0, %4 clamp\n\t"
+        "v_add_f32 %0, %0, %3\n\t"
+        "v_add_f32 %0, %0, %4"
+        : "+v"(B), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(u0), "=&v"(u1), "=&v"(u2), "=&v"(u3)
+        : "v"(r0), "v"(r1), "v"(r2), "v"(r3), "v"(rbar), "s"(k1));
+}
+
+__device__ __forceinline__ void mean_shift_group1_k(float r0, float rbar, float k1, float& B)
+{
+    float t0, u0;
+    asm("v_sub_f32 %1, %3, %4\n\t"
+        "v_mul_f32 %2, %5, %1\n\t"
+        "v_mul_f32 %1, %1, %2\n\t"
+        "v_sub_f32_e64 %1, 1.0, %1 clamp\n\t"
+        "v_add_f32 %0, %0, %1"
+        : "+v"(B), "=&v"(t0), "=&v"(u0)
+        : "v"(r0), "v"(rbar), "s"(k1));
+}
+
 // cv::BORDER_REFLECT_101
 __device__ __forceinline__ int reflect101(int p, int len)
 {
