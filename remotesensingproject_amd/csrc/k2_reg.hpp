@@ -20,7 +20,7 @@ namespace rslf {
 // and P = 1e30 * 0 = 0 exactly, so they add +0 to every sum -- bit-identical to the
 // reference's "NaN -> K = 0, R0 = 0" without a second register per sample.
 // Needs R == max(R, 0), hence the non-negative-volume precondition checked by
-// the host (rslf_pile.hip: choose_scan).
+// the host (rslf_plan.hpp: choose_scan_kernel).
 // ---------------------------------------------------------------------------
 // samples whose loads are in flight together (2 registers per sample and channel while they are)
 #ifndef RSLF_REG_GB104

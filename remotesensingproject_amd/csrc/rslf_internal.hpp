@@ -182,10 +182,8 @@ struct rslf_ctx {
     int last_kernel = 0; // RSLF_SCAN_* of the last K2 launch
     int num_cus = 0;           // compute units of the device (how many workgroups a launch needs to fill it)
     bool keep_total = false;   // the 2-D sweep sums the scanned pixels of all its visits
-    int scan_groups = 1;       // hypothesis groups per tile for the next scan launches (the 2-D sweep raises it)
-    bool scan_packed = false;  // next scan launches use one packed pixel list (sparse visits of the 2-D sweep)
     // test / tuning hooks (rslf_ctx_set_debug), per context: 0 / -1 = automatic
-    int force_scan = 0;        // 1 generic kernel, 2 streaming kernel, 3 on-chip kernel
+    int force_scan = 0;        // 1 generic kernel, 2 streaming kernel wherever it can run (never the on-chip one)
     int force_groups = 0;      // hypothesis groups per tile
     int force_packed = -1;     // 0 / 1
     int px_mode = -1;          // pixel-per-wave kernel on packed launches: -1 automatic, 0 never, 1 whenever it can run
@@ -198,12 +196,11 @@ struct rslf_ctx {
     size_t partial_rec_cap = 0;
     int* scan_ticket = nullptr;        // [tile] of the same launches: which group merges the tile (zero between launches)
     size_t ticket_cap = 0;
-    bool packed_n_clean = false;       // the packed list's length is already 0 (the sweep's apply pass resets it)
-    int precompacted = 0;              // the next scan's pixel lists and total are already in place: 1 = per-row lists (K1 +
-                                       // compaction in one launch), 2 = the packed list (a sweep's apply pass made it)
     int sweep_expect = -1;             // the view the sweep visits next (core.hpp:981-990), -1 once all are done
     bool sweep_open = false;           // between rslf_sweep_begin and rslf_sweep_end
     bool sweep_first = true;           // the next visit is the sweep's first (dense) one
+    bool sweep_listed = false;         // the last apply pass listed the next visit's pixels (packed list and length in place);
+                                       // else k34_median_claim left the list's length at 0
     uint8_t* sweep_mask_run = nullptr; // the running masks [S][V][U] of the open sweep
     // 2-D sweep scratch
     int* winner = nullptr;        // [S][V][U]
@@ -303,9 +300,26 @@ extern template int upload_host<float>(rslf_volume*, const float* const*, size_t
 extern template int upload_host<uint8_t>(rslf_volume*, const uint8_t* const*, size_t, bool, float);
 
 // rslf_pile.hip
-bool scan_takes_stream(const rslf_volume* vol);   // would a linear-interpolation scan of this volume run a grouped LDS kernel?
+// What a scan is given besides the arguments of rslf_depth_epi_scan: where its pixel lists come from and the launch shape
+// its caller asks for.  The public entry points pass scan_defaults.
+struct ScanInputs {
+    enum Lists { kCompact = 0, kRowLists = 1, kPackedList = 2 };   // (plan::ScanRequest::precompacted)
+    int lists = kCompact;         // the scan compacts the mask / K1 left per-row lists and the total / a sweep's apply pass
+                                  // left the packed list and its length
+    int groups = 1;               // hypothesis groups per tile (a sweep's sparse visits ask for more)
+    bool packed = false;          // one packed pixel list over all scanlines
+    bool packed_n_zero = false;   // the packed list's length is already 0
+    bool zero_total = true;       // the pixel total starts again
+    bool timed = true;            // ctx->ev0 / ev1 bracket the launches (rslf_last_scan_kernel_ms)
+};
+ScanInputs scan_defaults(const rslf_ctx* ctx);
+int depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
+                   int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu,
+                   const rslf_params* p, uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats,
+                   const ScanInputs& in);
 void fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_stats* stats);
 int scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf_params* p, const int* rows, int n_rows);
+int sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const ScanInputs& sparse);
 
 // rslf_f2c.hip: small elementwise launches the multi-device form shares
 int f2c_u8_to_f32(hipStream_t st, const uint8_t* in, float* out, size_t n);

@@ -161,69 +161,32 @@ static int launch_scan_reg(int spad, int C, const ScanArgs& a, dim3 grid, hipStr
     return fail(RSLF_ERR_UNSUPPORTED, "no register scan kernel with %d slots x %d channels", spad, C);
 }
 
-// Radiances in [0, 1e6] (max(R,0) == R, and the 1e30 sentinel dwarfs them) and an offset table that fits the LDS
-static bool scan_takes_lds_kernel(const rslf_volume* vol)
+// The device headers' numbers for a volume of S views x C channels
+static plan::ScanKernelFacts kernel_facts(int S, int C)
 {
-    return vol->min_value >= 0.0f && vol->max_value <= 1.0e6f && (size_t)kScanWaves * vol->S * sizeof(float) <= (size_t)48 << 10;
+    const int spad = plan::pick_spad(S, C);
+    return plan::ScanKernelFacts{spad ? scan_reg_waves(spad, C) : 0, stream_resident_for(S, C), stream_px_resident_for(S, C)};
 }
 
-bool rslf::scan_takes_stream(const rslf_volume* vol)
+// The request a scan of V x U pixels makes: the caller's inputs, the context's hooks, and the kernel plan::choose_scan_kernel
+// picks (`pixel_ranges`: per-pixel [dmin, dmax] planes, so no one hypothesis grid for all pixels)
+static plan::ScanRequest scan_request(const rslf_ctx* ctx, int V, int U, int S, int C, int dim_d, bool in_range, bool linear,
+                                      bool pixel_ranges, const ScanInputs& in)
 {
-    return scan_takes_lds_kernel(vol) && plan::pick_spad(vol->S, vol->C) == 0;
-}
-
-// Which kernel?  Register variant: S within the compiled slot counts, and radiances in [0, 1e6] so that max(R,0) == R and
-// the 1e30 sentinel dwarfs them.  Streaming variant: same precondition, any S whose offset table fits the LDS.
-// Otherwise the generic kernel.
-struct ScanChoice {
-    int spad;          // register kernel's slot count, 0 = not the register kernel
-    bool stream_ok;    // an LDS kernel could take this volume
-    bool use_stream;
-    bool use_chip;     // the on-chip kernel (k2_chip.hpp) -- only ever set by choose_scan's caller-visible conditions
-};
-
-// `dense_uniform`: a row-tile launch with one hypothesis grid for all pixels (what the on-chip kernel is written for)
-static ScanChoice choose_scan(const rslf_ctx* ctx, int S, int C, bool in_range, int interpolation, bool dense_uniform = false)
-{
-    ScanChoice c;
-    c.spad = in_range ? plan::pick_spad(S, C) : 0;
-    c.stream_ok = in_range && (size_t)kScanWaves * S * sizeof(float) <= (size_t)48 << 10;
-    if (interpolation != RSLF_INTERP_LINEAR) {      // nearest-neighbour sampling: generic kernel only
-        c.spad = 0;
-        c.stream_ok = false;
-    } else if (ctx->force_scan == 1) {              // parity tests exercise every variant on small cases
-        c.spad = 0;
-        c.stream_ok = false;
-    } else if (ctx->force_scan == 2) {
-        c.spad = 0;
-    }
-    c.use_stream = !c.spad && c.stream_ok;
-    // more views than two waves per SIMD hold on chip (RGB, 123 to 220 views: plan::chip_takes): one wave per SIMD with every sample at hand
-    c.use_chip = c.use_stream && dense_uniform && plan::chip_takes(S, C) && ctx->force_scan != 2;
-    if (c.use_chip)
-        c.use_stream = false;
-    return c;
-}
-
-static plan::ScanRequest scan_request(const rslf_ctx* ctx, int V, int U, int S, int C, int dim_d, const ScanChoice& ch, int precompacted)
-{
-    plan::ScanRequest rq;
+    plan::ScanRequest rq = {};
     rq.V = V, rq.U = U, rq.S = S, rq.C = C, rq.dim_d = dim_d;
-    rq.spad = ch.spad;
-    rq.use_stream = ch.use_stream;
-    rq.use_chip = ch.use_chip;
-    rq.chip_wave_floats = ch.use_chip ? plan::chip_wave_floats(S, plan::kChipLadder[plan::chip_rung_for(S)]) : 0;
-    rq.reg_waves = ch.spad ? scan_reg_waves(ch.spad, C) : 0;
     rq.num_cus = ctx->num_cus;
-    rq.ctx_groups = ctx->scan_groups;
-    rq.ctx_packed = ctx->scan_packed;
-    rq.precompacted = precompacted;
+    rq.ctx_groups = in.groups;
+    rq.ctx_packed = in.packed;
+    rq.precompacted = in.lists;
     rq.force_groups = ctx->force_groups;
     rq.force_packed = ctx->force_packed;
     rq.px_mode = ctx->px_mode;
     rq.stream_groups = ctx->stream_groups;
     rq.stream_share = ctx->stream_share;
     rq.stream_lds_bytes = ctx->stream_lds_bytes;
+    const bool dense_uniform = !pixel_ranges && !in.packed && ctx->force_packed != 1 && in.lists != ScanInputs::kPackedList;
+    plan::choose_scan_kernel(&rq, in_range, linear, ctx->force_scan, dense_uniform, kernel_facts(S, C));
     return rq;
 }
 
@@ -232,15 +195,16 @@ static plan::ScanRequest scan_request(const rslf_ctx* ctx, int V, int U, int S, 
 // launches take no records.
 int rslf::scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf_params* p, const int* rows, int n_rows)
 {
-    const ScanChoice ch = choose_scan(ctx, S, C, true, p ? p->interpolation : RSLF_INTERP_LINEAR,
-                                      !ctx->scan_packed && ctx->force_packed != 1);
-    const bool fused = p && p->edge_confidence_opening_size <= 1 && ctx->force_packed != 1 && !ctx->scan_packed;
+    const plan::ScanKernelFacts f = kernel_facts(S, C);
     int max_rows = 0;
     size_t recs = 0, tickets = 0;
     for (int i = 0; i < n_rows; i++) {
         max_rows = std::max(max_rows, rows[i]);
-        const plan::ScanPlan sp = plan::plan_scan(scan_request(ctx, rows[i], U, S, C, dim_d, ch, fused ? 1 : 0),
-                                                  ch.use_stream ? stream_resident_for(S, C) : 0, ch.use_stream ? stream_px_resident_for(S, C) : -1);
+        ScanInputs in;   // what rslf_depth1d_pile_run passes
+        if (p && plan::fuse_k1_compaction(p->edge_confidence_opening_size, ctx->force_packed, (size_t)rows[i] * U))
+            in.lists = ScanInputs::kRowLists;
+        const plan::ScanRequest rq = scan_request(ctx, rows[i], U, S, C, dim_d, true, !p || p->interpolation == RSLF_INTERP_LINEAR, false, in);
+        const plan::ScanPlan sp = plan::plan_scan(rq, f.nres, f.nres_px);
         recs = std::max(recs, sp.records);
         tickets = std::max(tickets, sp.tickets);
     }
@@ -257,6 +221,16 @@ int rslf::scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf
     return rc;
 }
 
+// Size the records of a sweep's sparse visits (`sparse`: what they pass) before its first visit, for linear interpolation
+int rslf::sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const ScanInputs& sparse)
+{
+    const plan::ScanRequest rq = scan_request(ctx, vol->V, vol->U, vol->S, vol->C, dim_d, plan::scan_range_ok(vol->min_value, vol->max_value),
+                                              true, false, sparse);
+    size_t recs = 0, tickets = 0;
+    plan::sweep_reserve(rq, kernel_facts(vol->S, vol->C), ctx->row_split, &recs, &tickets);
+    return recs ? ensure_group_scratch(ctx, recs, tickets) : RSLF_OK;
+}
+
 void rslf::fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_stats* stats)
 {
     stats->pixels_scanned = (int64_t)tot;
@@ -265,13 +239,18 @@ void rslf::fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_sta
     stats->s_pad = ctx->last_spad;
 }
 
-extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
-                                   float dmin, float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu,
-                                   float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu, const rslf_params* p,
-                                   uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats) RSLF_API_TRY
+ScanInputs rslf::scan_defaults(const rslf_ctx* ctx)
 {
-    if (!ctx || !vol || !d_Ce_vu || !d_Ce_mask_vu || !d_Cd_vu || !d_depth_vu || !d_rbar_vu)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    ScanInputs in;
+    in.zero_total = !ctx->keep_total;                   // an open sweep sums its visits' pixels ...
+    in.timed = !ctx->sweep_open || ctx->sweep_first;    // ... and times its first visit only
+    return in;
+}
+
+// The arguments every scan of the hypothesis grid takes (K2, the K columns)
+static int check_scan_args(const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat,
+                           const rslf_params* p)
+{
     int rc = check_params(p);
     if (rc)
         return rc;
@@ -283,8 +262,106 @@ extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const 
         return fail(RSLF_ERR_INVALID_ARG, "s_hat=%d outside [0,%d)", s_hat, vol->S);
     if (!vol->filled)
         return fail(RSLF_ERR_INVALID_ARG, "volume has not been filled");
+    return RSLF_OK;
+}
+
+// The launch shape's part of the scan's arguments
+static void apply_plan(ScanArgs& a, const plan::ScanPlan& p, const rslf_ctx* ctx)
+{
+    a.groups = p.groups;
+    a.tile_w = p.tile_w;   // the streaming kernel's row tiles leave lane 63 to its neighbour's right tap (DENSE)
+    a.tiles_per_row = p.tiles_per_row;
+    a.packed = p.packed ? 1 : 0;
+    a.packed_adapt = p.packed_adapt ? 1 : 0;
+    a.px_waves = p.px_waves;
+    a.stream_park = p.stream_park;
+    a.stream_wave_floats = p.stream_wave_floats;
+    // grouped launches leave one 32-byte record per (tile, group, lane) for the tile's last group to merge (k2_scan.hpp)
+    a.partial = p.groups > 1 ? ctx->scan_partial : nullptr;
+    a.ticket = p.groups > 1 ? ctx->scan_ticket : nullptr;
+}
+
+// One launch of the kernel the plan names: its template instantiation for the slot count / resident prefix / channels
+// (RSLF_SPAD_LIST_* in rslf_plan.hpp; k2_stream.hpp; the on-chip rungs in rslf_chip_a.hip)
+static int enqueue_scan(const plan::ScanPlan& p, const ScanArgs& a, unsigned grid_x, size_t stream_lds_bytes, hipStream_t st)
+{
+    const dim3 grid(grid_x), block(64 * kScanWaves);
+    const int C = a.vol.C;
+    hipError_t attr = hipSuccess;
+    auto stream = [&](auto kernel) {   // (more than the 64 KiB a kernel gets without asking: set on every launch)
+        attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stream_lds_bytes);
+        if (attr == hipSuccess)
+            hipLaunchKernelGGL(kernel, grid, block, p.lds_bytes, st, a);
+    };
+    int rc = RSLF_OK;
+    switch (p.kind) {
+    case RSLF_SCAN_REG:
+    case RSLF_SCAN_REG_PX:
+        rc = launch_scan_reg(p.spad, C, a, grid, st);
+        break;
+    case RSLF_SCAN_CHIP:
+        rc = launch_scan_chip(a, grid, p.lds_bytes, st);   // rslf_chip_a.hip: the rung that holds this view count
+        break;
+    case RSLF_SCAN_STREAM_PX:
+        if (C == 1)
+            stream_px_kernel_for<1>(p.stream_nres, stream);
+        else
+            stream_px_kernel_for<3>(p.stream_nres, stream);
+        break;
+    case RSLF_SCAN_STREAM:
+        if (p.packed && C == 1)
+            stream_kernel_for<1, true>(p.stream_nres, stream);
+        else if (p.packed)
+            stream_kernel_for<3, true>(p.stream_nres, stream);
+        else if (C == 1)
+            stream_kernel_for<1, false>(p.stream_nres, stream);
+        else
+            stream_kernel_for<3, false>(p.stream_nres, stream);
+        break;
+    default:
+        if (C == 1)
+            hipLaunchKernelGGL(k2_scan_generic<1>, grid, block, 0, st, a);
+        else
+            hipLaunchKernelGGL(k2_scan_generic<3>, grid, block, 0, st, a);
+    }
+    if (rc)
+        return rc;
+    HIP_TRY(attr);
+    HIP_TRY(hipGetLastError());   // grouped launches merge their records themselves (scan_epilogue): no combine launch
+    return RSLF_OK;
+}
+
+int rslf::depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin,
+                         float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                         float* d_rbar_vu, const rslf_params* p, uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu,
+                         rslf_stats* stats, const ScanInputs& in)
+{
+    if (!ctx || !vol || !d_Ce_vu || !d_Ce_mask_vu || !d_Cd_vu || !d_depth_vu || !d_rbar_vu)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    int rc = check_scan_args(vol, d_dmin_vu, d_dmax_vu, dim_d, s_hat, p);
+    if (rc)
+        return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     rc = ensure_plane_scratch(ctx, vol->V, vol->U);
+    if (rc)
+        return rc;
+
+    // Kernel and launch shape (rslf_plan.hpp): which kernel, hypothesis groups per tile, packed or row tiles, 63- or 64-entry
+    // tiles, row blocks and records of grouped launches, the streaming kernel's LDS split, the grids -- pure host logic,
+    // unit-tested on the CPU.  Everything that can fail on the host fails here, before anything is queued.
+    const plan::ScanRequest rq = scan_request(ctx, vol->V, vol->U, vol->S, vol->C, dim_d, plan::scan_range_ok(vol->min_value, vol->max_value),
+                                              p->interpolation == RSLF_INTERP_LINEAR, d_dmin_vu != nullptr, in);
+    const plan::ScanKernelFacts f = kernel_facts(vol->S, vol->C);
+    const plan::ScanPlan sp = plan::plan_scan(rq, f.nres, f.nres_px);
+    const int row_min = plan::row_split_min(rq, sp, ctx->row_split);
+    const plan::ScanPlan spr = row_min ? plan::plan_scan(plan::row_split_request(rq), f.nres) : sp;
+    std::vector<plan::ScanLaunch> row_launches, launches;
+    long long tiles = 0;
+    if (row_min && !plan::scan_launches(vol->V, vol->U, spr, &row_launches, &tiles))
+        return fail(RSLF_ERR_UNSUPPORTED, "%lld tiles x %d groups exceeds the grid limit", tiles, spr.groups);
+    if (!plan::scan_launches(vol->V, vol->U, sp, &launches, &tiles))
+        return fail(RSLF_ERR_UNSUPPORTED, "%lld tiles x %d groups exceeds the grid limit", tiles, sp.groups);
+    rc = ensure_group_scratch(ctx, std::max(sp.records, spr.records), std::max(sp.tickets, spr.tickets));
     if (rc)
         return rc;
 
@@ -294,29 +371,13 @@ extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const 
         HIP_TRY(hipMemsetAsync(d_idx_vu, 0xFF, n * sizeof(int32_t), st));   // -1
     if (d_score_vu)
         HIP_TRY(hipMemsetAsync(d_score_vu, 0, n * sizeof(float), st));
-    const int precompacted = ctx->precompacted;   // 1: rslf_depth1d_pile_run's K1 left row lists and total; 2: packed list (sweep)
-    ctx->precompacted = 0;
-    if (!ctx->keep_total && !precompacted)
+    if (in.zero_total && in.lists == ScanInputs::kCompact)
         HIP_TRY(hipMemsetAsync(ctx->total, 0, sizeof(unsigned long long), st));
-
-    const bool dense_uniform = !d_dmin_vu && !ctx->scan_packed && ctx->force_packed != 1 && precompacted != 2;
-    const ScanChoice ch = choose_scan(ctx, vol->S, vol->C, vol->min_value >= 0.0f && vol->max_value <= 1.0e6f, p->interpolation,
-                                      dense_uniform);
-    const int spad = ch.spad;
-    const bool stream_ok = ch.stream_ok, use_stream = ch.use_stream, use_chip = ch.use_chip;
-    // Launch shape (rslf_plan.hpp, plan_scan): hypothesis groups per tile, packed or row tiles, 63- or 64-entry tiles, row
-    // blocks and records of grouped launches, the streaming kernel's LDS split -- pure host logic, unit-tested on the CPU.
-    const plan::ScanRequest rq = scan_request(ctx, vol->V, vol->U, vol->S, vol->C, dim_d, ch, precompacted);
-    const plan::ScanPlan sp = plan::plan_scan(rq, use_stream ? stream_resident_for(vol->S, vol->C) : 0,
-                                              use_stream ? stream_px_resident_for(vol->S, vol->C) : -1);
-    const int groups = sp.groups;
-    const bool packed = sp.packed;
-
     int* packed_n = reinterpret_cast<int*>(ctx->total + 1);
-    if (precompacted) {
+    if (in.lists != ScanInputs::kCompact) {
         // nothing to compact
-    } else if (packed) {
-        if (!ctx->packed_n_clean)
+    } else if (sp.packed) {
+        if (!in.packed_n_zero)
             HIP_TRY(hipMemsetAsync(packed_n, 0, sizeof(int), st));
         hipLaunchKernelGGL(k_compact_mask_packed, dim3(vol->V), dim3(256), 0, st, d_Ce_mask_vu, d_mask_vu, vol->U, ctx->list,
                            ctx->count, ctx->total, packed_n, ctx->count + ctx->count_cap);
@@ -326,7 +387,7 @@ extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const 
     }
     HIP_TRY(hipGetLastError());
 
-    ScanArgs a;
+    ScanArgs a = {};
     a.vol = view_of(vol);
     a.list = ctx->list;
     a.count = ctx->count;
@@ -344,179 +405,58 @@ extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const 
     a.rbar = d_rbar_vu;
     a.idx = d_idx_vu;
     a.score = d_score_vu;
-    a.tile_w = sp.tile_w;                 // the streaming kernel's row tiles leave lane 63 to its neighbour's right tap (DENSE)
-    a.tiles_per_row = sp.tiles_per_row;
     a.stream_frac_max = plan::stream_frac_max(vol->U);
-    a.packed = packed ? 1 : 0;
     a.packed_n = packed_n;
-    a.packed_adapt = sp.packed_adapt ? 1 : 0;
-    a.px_waves = sp.px_waves;
-    a.stream_park = sp.stream_park;
-    a.stream_wave_floats = sp.stream_wave_floats;
-    a.partial = nullptr;
-    a.ticket = nullptr;
-    a.v0 = 0;
-    a.groups = groups;
-    a.rowbase = nullptr;
-    a.row_min = 0;
-    // Row split (sparse visits of stream-class volumes): the rows of the packed list that hold many pixels go as ROW tiles --
-    // the streaming kernel's dense form, reading its tiles straight from the packed list -- and the pixel-per-wave launch
-    // takes the rest.  Both are queued; which rows each scans is settled on the device, from the rows' counts.
-    const bool row_split = packed && use_stream && sp.px_waves > 0 && ctx->row_split != 0 && precompacted != 1;
-    plan::ScanPlan spr = sp;
-    if (row_split) {
-        plan::ScanRequest rr = rq;
-        rr.ctx_packed = false;
-        rr.ctx_groups = 1;
-        rr.precompacted = 1;      // the lists are in place
-        rr.force_packed = 0;
-        if (rr.stream_groups <= 0)
-            rr.stream_groups = plan::kStreamGroups;   // (sparse rows: the groups are the launch's parallelism, not the dense rule's few)
-        spr = plan::plan_scan(rr, stream_resident_for(vol->S, vol->C));
-        a.row_min = ctx->row_split > 1 ? ctx->row_split : plan::kRowSplitMin;   // (hook: 1 = the default threshold, larger = that many pixels)
-    }
-    // Grouped launches leave one 32-byte record per (tile, group, lane) for the tile's last group to merge (k2_scan.hpp)
-    const int rows_per_launch = sp.rows_per_launch;
-    if (groups > 1) {
-        rc = ensure_group_scratch(ctx, sp.records, sp.tickets);
-        if (rc)
-            return rc;
-        a.partial = ctx->scan_partial;
-        a.ticket = ctx->scan_ticket;
-    }
-    if (row_split && spr.groups > 1) {
-        rc = ensure_group_scratch(ctx, spr.records, spr.tickets);
-        if (rc)
-            return rc;
-    }
-    const size_t lds = sp.lds_bytes;
-    // (more than the 64 KiB a kernel gets without asking: set on the instantiation about to be launched, below)
+    a.row_min = row_min;
+    ScanArgs ar = a;   // the row split's row tiles of the packed list
+    apply_plan(a, sp, ctx);
+    apply_plan(ar, spr, ctx);
+    ar.rowbase = ctx->count + ctx->count_cap;
+    ctx->last_spad = sp.spad;
+    ctx->last_kernel = sp.kind;
     HIP_TRY(hipGetLastError());   // anything an earlier enqueue left behind is not this launch's fault
-    ctx->last_spad = spad;
-    ctx->last_kernel = spad ? (sp.px_waves ? RSLF_SCAN_REG_PX : RSLF_SCAN_REG)
-                       : use_chip ? RSLF_SCAN_CHIP
-                       : stream_ok ? (sp.px_waves ? RSLF_SCAN_STREAM_PX : RSLF_SCAN_STREAM) : RSLF_SCAN_GENERIC;
+
     // The events that time K2 are marker packets of their own: ~5.6 us each before the next kernel starts (measured,
-    // tools/probe_gaps.py) -- nothing beside a 66 ms scan, a tenth of a sweep's sparse visit.  A sweep times its first
-    // (dense) visit only.
-    const bool timed = !ctx->sweep_open || ctx->sweep_first;
-    hipEvent_t pool0 = nullptr, pool1 = nullptr;
-    if (ctx->time_all && ctx->ev_used + 2 <= ((size_t)1 << 16)) {   // every launch sequence gets a pair of its own (rslf_scan_time_total_ms;
-                                                                      // 32 768 untimed-for launches are the pool's end: later ones go untimed)
-        while (ctx->ev_pool.size() < ctx->ev_used + 2) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            ctx->ev_pool.push_back(e);
+    // tools/probe_gaps.py) -- nothing beside a 66 ms scan, a tenth of a sweep's sparse visit.  time_all: every launch
+    // sequence gets a pair of its own from the pool (rslf_scan_time_total_ms; 32 768 untimed-for launches are the pool's
+    // end: later ones go untimed), handed back if the sequence fails to queue.
+    const bool pooled = ctx->time_all && ctx->ev_used + 2 <= ((size_t)1 << 16);
+    while (pooled && ctx->ev_pool.size() < ctx->ev_used + 2) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        ctx->ev_pool.push_back(e);
+    }
+    auto enqueue_all = [&]() -> int {
+        if (pooled)
+            HIP_TRY(hipEventRecord(ctx->ev_pool[ctx->ev_used - 2], st));
+        if (in.timed)
+            HIP_TRY(hipEventRecord(ctx->ev0, st));
+        for (const plan::ScanLaunch& l : row_launches) {   // the rows with many pixels first
+            ar.v0 = l.v0, ar.logical_blocks = l.logical_blocks, ar.per_xcd = l.per_xcd;
+            if (int e = enqueue_scan(spr, ar, l.grid, ctx->stream_lds_bytes, st))
+                return e;
         }
-        pool0 = ctx->ev_pool[ctx->ev_used];
-        pool1 = ctx->ev_pool[ctx->ev_used + 1];
+        for (const plan::ScanLaunch& l : launches) {
+            a.v0 = l.v0, a.logical_blocks = l.logical_blocks, a.per_xcd = l.per_xcd;
+            if (int e = enqueue_scan(sp, a, l.grid, ctx->stream_lds_bytes, st))
+                return e;
+        }
+        if (in.timed) {
+            HIP_TRY(hipEventRecord(ctx->ev1, st));
+            ctx->ev_valid = true;
+        }
+        if (pooled)
+            HIP_TRY(hipEventRecord(ctx->ev_pool[ctx->ev_used - 1], st));
+        return RSLF_OK;
+    };
+    if (pooled)
         ctx->ev_used += 2;
-        HIP_TRY(hipEventRecord(pool0, st));
+    rc = enqueue_all();
+    if (rc) {
+        if (pooled)
+            ctx->ev_used -= 2;
+        return rc;
     }
-    if (timed)
-        HIP_TRY(hipEventRecord(ctx->ev0, st));
-    if (row_split) {   // the rows with many pixels, as row tiles of the packed list
-        ScanArgs ar = a;
-        ar.packed = 0;
-        ar.px_waves = 0;
-        ar.packed_adapt = 0;
-        ar.rowbase = ctx->count + ctx->count_cap;
-        ar.groups = spr.groups;
-        ar.tile_w = spr.tile_w;
-        ar.tiles_per_row = spr.tiles_per_row;
-        ar.stream_park = spr.stream_park;
-        ar.stream_wave_floats = spr.stream_wave_floats;
-        ar.partial = spr.groups > 1 ? ctx->scan_partial : nullptr;
-        ar.ticket = spr.groups > 1 ? ctx->scan_ticket : nullptr;
-        for (int v0 = 0; v0 < vol->V; v0 += spr.rows_per_launch) {
-            const int rows = std::min(spr.rows_per_launch, vol->V - v0);
-            const long long tiles = (long long)rows * ar.tiles_per_row;
-            if (tiles * ar.groups > (long long)1 << 30)
-                return fail(RSLF_ERR_UNSUPPORTED, "%lld tiles x %d groups exceeds the grid limit", tiles, ar.groups);
-            ar.v0 = v0;
-            ar.logical_blocks = (int)(tiles * ar.groups);
-            ar.per_xcd = ((rows + 7) / 8) * ar.tiles_per_row * ar.groups;
-            const dim3 rgrid((unsigned)(ar.per_xcd * 8));
-            hipError_t rattr = hipSuccess;
-            auto launch_rows = [&](auto kernel) {
-                rattr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)ctx->stream_lds_bytes);
-                if (rattr == hipSuccess)
-                    hipLaunchKernelGGL(kernel, rgrid, dim3(64 * kScanWaves), spr.lds_bytes, st, ar);
-            };
-            if (vol->C == 1)
-                stream_kernel_for<1, false>(spr.stream_nres, launch_rows);
-            else
-                stream_kernel_for<3, false>(spr.stream_nres, launch_rows);
-            HIP_TRY(rattr);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    for (int v0 = 0; v0 < vol->V; v0 += rows_per_launch) {
-        const int rows = std::min(rows_per_launch, vol->V - v0);
-        // row tiles: ceil(U/64) per scanline; packed tiles: at most ceil(V*U/64), the device knows how many
-        const long long tiles = packed ? (long long)((n + 63) / 64) : (long long)rows * a.tiles_per_row;
-        if (tiles * groups > (long long)1 << 30)
-            return fail(RSLF_ERR_UNSUPPORTED, "%lld tiles x %d groups exceeds the grid limit", tiles, groups);
-        a.v0 = v0;
-        a.logical_blocks = (int)(tiles * groups);   // `groups` workgroups per tile, their waves split the hypotheses
-        // (row tiles: the scanlines are dealt to the XCDs in turn, every XCD ceil(rows / 8) of them: xcd_logical_block_rows)
-        a.per_xcd = packed ? (a.logical_blocks + 7) / 8 : ((rows + 7) / 8) * a.tiles_per_row * groups;
-        // packed: a fixed grid strides over the items (k2_scan.hpp); ~4 workgroups per CU cover any occupancy
-        // (the pixel-per-wave kernel's items are 4 / px_waves pixels each)
-        const long long px_items = sp.px_waves ? ((long long)n * sp.px_waves + kScanWaves - 1) / kScanWaves : 0;
-        const dim3 grid(sp.px_waves ? (unsigned)std::min<long long>(px_items, 2048)
-                        : packed    ? (unsigned)std::min<long long>(tiles * groups, 1024)
-                                    : (unsigned)(a.per_xcd * 8));
-        if (spad) {
-            rc = launch_scan_reg(spad, vol->C, a, grid, st);
-            if (rc)
-                return rc;
-        } else if (use_chip) {
-            rc = launch_scan_chip(a, grid, lds, st);   // rslf_chip_a.hip: the rung that holds this view count
-            if (rc)
-                return rc;
-        } else if (use_stream) {
-            // one instantiation per channel count, resident-prefix length and launch form (k2_stream.hpp)
-            hipError_t attr = hipSuccess;
-            auto launch = [&](auto kernel) {
-                attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)ctx->stream_lds_bytes);   // (more than the 64 KiB a kernel gets without asking)
-                if (attr == hipSuccess)
-                    hipLaunchKernelGGL(kernel, grid, dim3(64 * kScanWaves), lds, st, a);
-            };
-            if (sp.px_waves) {
-                if (vol->C == 1)
-                    stream_px_kernel_for<1>(sp.stream_nres, launch);
-                else
-                    stream_px_kernel_for<3>(sp.stream_nres, launch);
-            } else if (packed) {
-                if (vol->C == 1)
-                    stream_kernel_for<1, true>(sp.stream_nres, launch);
-                else
-                    stream_kernel_for<3, true>(sp.stream_nres, launch);
-            } else {
-                if (vol->C == 1)
-                    stream_kernel_for<1, false>(sp.stream_nres, launch);
-                else
-                    stream_kernel_for<3, false>(sp.stream_nres, launch);
-            }
-            HIP_TRY(attr);
-        } else if (vol->C == 1) {
-            hipLaunchKernelGGL(k2_scan_generic<1>, grid, dim3(64 * kScanWaves), 0, st, a);
-        } else {
-            hipLaunchKernelGGL(k2_scan_generic<3>, grid, dim3(64 * kScanWaves), 0, st, a);
-        }
-        HIP_TRY(hipGetLastError());   // grouped launches merge their records themselves (scan_epilogue): no combine launch
-        if (packed)
-            break;   // one launch covers the packed list
-    }
-    if (timed) {
-        HIP_TRY(hipEventRecord(ctx->ev1, st));
-        ctx->ev_valid = true;
-    }
-    if (pool1)
-        HIP_TRY(hipEventRecord(pool1, st));
 
     if (stats) {
         unsigned long long tot = 0;
@@ -526,6 +466,17 @@ extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const 
     }
     return RSLF_OK;
 }
+
+extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                                   float dmin, float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu,
+                                   float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu, const rslf_params* p,
+                                   uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats) RSLF_API_TRY
+{
+    if (!ctx)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    return depth_epi_scan(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,
+                          d_rbar_vu, p, d_mask_vu, d_idx_vu, d_score_vu, stats, scan_defaults(ctx));
+}
 RSLF_API_CATCH
 
 extern "C" int rslf_kernel_columns_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
@@ -534,17 +485,9 @@ extern "C" int rslf_kernel_columns_pile(rslf_ctx* ctx, const rslf_volume* vol, c
 {
     if (!ctx || !vol || !d_idx_vu || !d_K_vsu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    int rc = check_params(p);
+    int rc = check_scan_args(vol, d_dmin_vu, d_dmax_vu, dim_d, s_hat, p);
     if (rc)
         return rc;
-    if ((d_dmin_vu == nullptr) != (d_dmax_vu == nullptr))
-        return fail(RSLF_ERR_INVALID_ARG, "d_dmin_vu and d_dmax_vu must both be given or both be NULL");
-    if (dim_d < 2)
-        return fail(RSLF_ERR_INVALID_ARG, "dim_d=%d: the hypothesis grid divides by dim_d-1 (core.hpp:548)", dim_d);
-    if (s_hat < 0 || s_hat >= vol->S)
-        return fail(RSLF_ERR_INVALID_ARG, "s_hat=%d outside [0,%d)", s_hat, vol->S);
-    if (!vol->filled)
-        return fail(RSLF_ERR_INVALID_ARG, "volume has not been filled");
     HIP_TRY(hipSetDevice(ctx->device));
     ScanArgs a = {};
     a.vol = view_of(vol);
@@ -566,11 +509,10 @@ extern "C" int rslf_kernel_columns_pile(rslf_ctx* ctx, const rslf_volume* vol, c
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
-                                   float dmin, float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu,
-                                   float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu, const rslf_params* p,
-                                   uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, float* d_depth_raw_vu,
-                                   rslf_stats* stats) RSLF_API_TRY
+static int depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin,
+                          float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                          float* d_rbar_vu, const rslf_params* p, uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu,
+                          float* d_depth_raw_vu, rslf_stats* stats, const ScanInputs& in)
 {
     if (!ctx || !vol || !d_depth_vu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -590,8 +532,8 @@ extern "C" int rslf_depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const 
         HIP_TRY(hipMemcpyAsync(raw, d_depth_vu, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     else if (d_depth_raw_vu)
         HIP_TRY(hipMemsetAsync(d_depth_raw_vu, 0, n * sizeof(float), st));
-    rc = rslf_depth_epi_scan(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, raw,
-                             d_rbar_vu, p, d_mask_vu, d_idx_vu, d_score_vu, nullptr);
+    rc = depth_epi_scan(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, raw, d_rbar_vu,
+                        p, d_mask_vu, d_idx_vu, d_score_vu, nullptr, in);
     if (rc)
         return rc;
     // ... then core.hpp:881-892: median over the EDGE mask, result replaces best_depth -- written straight into the
@@ -607,6 +549,18 @@ extern "C" int rslf_depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const 
         fill_stats(ctx, tot, dim_d, stats);
     }
     return RSLF_OK;
+}
+
+extern "C" int rslf_depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                                   float dmin, float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu,
+                                   float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu, const rslf_params* p,
+                                   uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, float* d_depth_raw_vu,
+                                   rslf_stats* stats) RSLF_API_TRY
+{
+    if (!ctx)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    return depth_epi_pile(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,
+                          d_rbar_vu, p, d_mask_vu, d_idx_vu, d_score_vu, d_depth_raw_vu, stats, scan_defaults(ctx));
 }
 RSLF_API_CATCH
 
@@ -630,11 +584,10 @@ extern "C" int rslf_depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, floa
     if (rc)
         return rc;
     // dc.hpp:538 + the findNonZero of dc.hpp:547's callee (core.hpp:513-516) in ONE launch when nothing sits between
-    // them: no opening of the mask (core.hpp:759-768) and row tiles.  A pile step is then three launches -- edge
-    // confidence + compaction, scan, selective median -- and no plane is copied.
-    const bool fuse = p->edge_confidence_opening_size <= 1 && ctx->force_packed != 1 && !ctx->scan_packed && vol->filled &&
-                      (size_t)vol->V * vol->U <= (size_t)INT32_MAX;
-    if (fuse) {
+    // them (plan::fuse_k1_compaction).  A pile step is then three launches -- edge confidence + compaction, scan, selective
+    // median -- and no plane is copied.
+    ScanInputs in = scan_defaults(ctx);
+    if (vol->filled && plan::fuse_k1_compaction(p->edge_confidence_opening_size, ctx->force_packed, n)) {
         rc = ensure_plane_scratch(ctx, vol->V, vol->U);
         if (rc)
             return rc;
@@ -643,7 +596,7 @@ extern "C" int rslf_depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, floa
         ec.cut_shadows = p->cut_shadows;
         ec.shadow_level = p->shadow_level;
         ec.edge_thr = p->edge_score_threshold;
-        if (!ctx->keep_total)
+        if (in.zero_total)
             HIP_TRY(hipMemsetAsync(ctx->total, 0, sizeof(unsigned long long), st));
         if (vol->C == 1)
             hipLaunchKernelGGL(k1_edge_confidence_compact<1>, dim3(vol->V), dim3(256), 0, st, view_of(vol), s_hat, ec, d_Ce_vu,
@@ -652,16 +605,14 @@ extern "C" int rslf_depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, floa
             hipLaunchKernelGGL(k1_edge_confidence_compact<3>, dim3(vol->V), dim3(256), 0, st, view_of(vol), s_hat, ec, d_Ce_vu,
                                d_Ce_mask_vu, ctx->list, ctx->count, ctx->total);
         HIP_TRY(hipGetLastError());
-        ctx->precompacted = 1;
+        in.lists = ScanInputs::kRowLists;
     } else {
         rc = rslf_edge_confidence_pile(ctx, vol, s_hat, p, d_Ce_vu, d_Ce_mask_vu);   // dc.hpp:538
         if (rc)
             return rc;
     }
-    rc = rslf_depth_epi_pile(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu,   // dc.hpp:547
-                             d_depth_vu, d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, d_depth_raw_vu, stats);
-    ctx->precompacted = 0;
-    return rc;
+    return depth_epi_pile(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,   // dc.hpp:547
+                          d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, d_depth_raw_vu, stats, in);
 }
 RSLF_API_CATCH
 
@@ -683,8 +634,8 @@ extern "C" int rslf_depth1d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmi
     int rc = rslf_edge_confidence_pile(ctx, vol, s_hat, p, d_Ce_vu, d_Ce_mask_vu);   // dc.hpp:347
     if (rc)
         return rc;
-    return rslf_depth_epi_scan(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu,   // dc.hpp:356
-                               d_depth_vu, d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, stats);
+    return depth_epi_scan(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,   // dc.hpp:356
+                          d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, stats, scan_defaults(ctx));
 }
 RSLF_API_CATCH
 
@@ -735,12 +686,8 @@ extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol,
     }
     if (rc == RSLF_OK && stats) {
         unsigned long long tot = 0;
-        if (hipMemcpy(&tot, ctx->total, sizeof(tot), hipMemcpyDeviceToHost) == hipSuccess) {
-            stats->pixels_scanned = (int64_t)tot;
-            stats->units = (int64_t)tot * dim_d;
-            stats->scan_kernel = ctx->last_kernel;
-            stats->s_pad = ctx->last_spad;
-        }
+        if (hipMemcpy(&tot, ctx->total, sizeof(tot), hipMemcpyDeviceToHost) == hipSuccess)
+            fill_stats(ctx, tot, dim_d, stats);
     }
     (void)hipFree(blk);
     return rc;

@@ -18,6 +18,8 @@
 #include <cmath>
 #include <vector>
 
+#include "../../include/rslf_hip.h"   // RSLF_SCAN_*
+
 namespace rslf {
 
 // cv::getStructuringElement result as one bit row per kernel row (k <= 31); the device side is k1_morph_pass
@@ -38,6 +40,7 @@ constexpr int kPackedItemTarget = 2048;                            // packed lau
 constexpr int kSweepGroups = 32;                                   // workgroups sharing a packed tile on a sweep's sparse visits
 constexpr int kStreamGroups = 16;                                  // dense launches of the streaming kernel: workgroups per tile
 constexpr size_t kStreamSmallEpiBytes = (size_t)2 << 20;           // ... 2 or 3 where a scanline's EPI is at most this (half an XCD's L2)
+constexpr size_t kScanOffsetTableBytes = (size_t)48 << 10;        // LDS kernels: the waves' view-offset tables fit this
 constexpr int kRowSplitMin = 64;                                   // packed launches of stream-class volumes: rows with at least this many pixels go as row tiles
 constexpr int kChipGroups = 8;                                     // ... of the on-chip kernel: half the records, same speed (profiles/r03_k2_variants.md)
 constexpr size_t kStreamLdsBytes = (size_t)80 << 10;               // dynamic LDS of one streaming workgroup (two per CU)
@@ -519,6 +522,7 @@ inline int px_waves(int dim_d)
 
 struct ScanRequest {
     int V, U, S, C, dim_d;
+    // the kernel (choose_scan_kernel)
     int spad;              // register kernel's slot count, 0 = none
     bool use_stream;       // streaming kernel
     bool use_chip;         // on-chip kernel (k2_chip.hpp): one workgroup per CU, row tiles as the streaming kernel's, never packed
@@ -537,6 +541,8 @@ struct ScanRequest {
 };
 
 struct ScanPlan {
+    int kind;              // RSLF_SCAN_*: the kernel that runs
+    int spad;              // ... the register kernel's slot count, 0 = another kernel
     int groups;            // workgroups sharing one tile's hypotheses
     bool packed;           // one packed list over all scanlines
     bool packed_adapt;     // the device settles the group count from the list length
@@ -554,6 +560,32 @@ struct ScanPlan {
 };
 
 inline int stream_resident_hi(int C, int nres_1ch, int nres_rgb) { return C == 1 ? nres_1ch : nres_rgb; }
+
+// What the device headers fix for a volume of S views x C channels, passed in so that this header stays host-only
+struct ScanKernelFacts {
+    int reg_waves;   // scan_reg_waves(pick_spad(S, C), C) (k2_reg.hpp), 0 where no register kernel has the slots
+    int nres;        // stream_resident_for(S, C) (k2_stream.hpp): the streaming kernel's resident prefix
+    int nres_px;     // stream_px_resident_for(S, C): ... of its pixel-per-wave form
+};
+
+// LDS kernels take radiances in [0, 1e6]: max(R, 0) == R, and the 1e30 sentinel dwarfs them
+inline bool scan_range_ok(float min_value, float max_value) { return min_value >= 0.0f && max_value <= 1.0e6f; }
+
+// Which kernel scans r's volume (S views x C channels): fills r's kernel fields.  The register kernel where S is within its
+// compiled slot counts; the streaming kernel for any S whose offset table fits the LDS; both need radiances in range and
+// linear interpolation.  Instead of the streaming kernel, the on-chip one for the RGB view counts it has a rung for
+// (chip_takes: more views than two waves per SIMD hold on chip), on a row-tile launch with one hypothesis grid for all
+// pixels (`dense_uniform`, what it is written for).  Otherwise the generic kernel.  `force_scan` (debug hook, the parity
+// tests exercise every variant on small cases): 1 the generic kernel, 2 the streaming kernel wherever it can run.
+inline void choose_scan_kernel(ScanRequest* r, bool in_range, bool linear, int force_scan, bool dense_uniform, const ScanKernelFacts& f)
+{
+    const bool lds_ok = in_range && linear && force_scan != 1 && (size_t)kScanWavesPerTile * r->S * sizeof(float) <= kScanOffsetTableBytes;
+    r->spad = lds_ok && force_scan == 0 ? pick_spad(r->S, r->C) : 0;
+    r->use_chip = lds_ok && r->spad == 0 && dense_uniform && force_scan != 2 && chip_takes(r->S, r->C);
+    r->use_stream = lds_ok && r->spad == 0 && !r->use_chip;
+    r->chip_wave_floats = r->use_chip ? chip_wave_floats(r->S, kChipLadder[chip_rung_for(r->S)]) : 0;
+    r->reg_waves = r->spad ? f.reg_waves : 0;
+}
 
 // The streaming kernel's LDS per wave: the S view offsets (rounded up to 4) and as many batches of parked samples as the
 // workgroup's share leaves room for (never past the end of the views).  Returns the parked samples per lane.
@@ -654,6 +686,10 @@ inline ScanPlan plan_scan(const ScanRequest& r, int nres, int nres_px = -1)
         while (groups > 1 && ((n + 63) / 64) * groups * 64 * kPartialRecordBytes > kPartialBudget)
             groups /= 2;
     p.px_waves = px_w;
+    p.spad = r.spad;
+    p.kind = r.spad ? (px_w ? RSLF_SCAN_REG_PX : RSLF_SCAN_REG)
+             : r.use_chip ? RSLF_SCAN_CHIP
+             : r.use_stream ? (px_w ? RSLF_SCAN_STREAM_PX : RSLF_SCAN_STREAM) : RSLF_SCAN_GENERIC;
     if (px_w) {
         groups = 1;
         p.packed_adapt = false;
@@ -689,26 +725,84 @@ inline ScanPlan plan_scan(const ScanRequest& r, int nres, int nres_px = -1)
     return p;
 }
 
-// The records a sweep's sparse visits will need, sized before the first visit (no allocation in the middle of the sequence)
-inline void sweep_record_plan(size_t n_pixels, int dim_d, bool stream, size_t* records, size_t* tickets)
+// Row split (sparse visits of stream-class volumes): the rows of the packed list that hold at least this many pixels go as
+// ROW tiles -- the streaming kernel's dense form, reading its tiles straight from the packed list -- and the pixel-per-wave
+// launch takes the rest; which rows each scans is settled on the device, from the rows' counts.  `hook` = the row_split
+// debug key: 0 off, 1 the default threshold, larger = that many pixels.  0: the launch is not split.
+inline int row_split_min(const ScanRequest& r, const ScanPlan& p, int hook)
 {
-    int g = kSweepGroups;
-    while (g > 1 && dim_d < 2 * kScanWavesPerTile * g)
-        g /= 2;
-    const size_t tiles_all = (n_pixels + 63) / 64;
-    if (stream)
-        while (g > 1 && tiles_all * g * 64 * kPartialRecordBytes > kPartialBudget)
-            g /= 2;
-    *records = 0;
-    *tickets = 0;
-    if (g > 1 && n_pixels <= (size_t)INT32_MAX) {
-        if (stream) {
-            *records = tiles_all * g * 64;
-            *tickets = tiles_all;
-        } else {
-            *records = std::min<size_t>(tiles_all * g, kPackedItemTarget) * 64;
-            *tickets = std::min<size_t>(tiles_all, kPackedItemTarget / 2);
+    return r.use_stream && p.px_waves > 0 && hook != 0 ? (hook > 1 ? hook : kRowSplitMin) : 0;
+}
+
+// ... the request of its row-tile launches: the lists are in place, and the groups are the launch's parallelism (sparse
+// rows), not the dense rule's few
+inline ScanRequest row_split_request(ScanRequest r)
+{
+    r.ctx_packed = false;
+    r.ctx_groups = 1;
+    r.precompacted = 1;
+    r.force_packed = 0;
+    if (r.stream_groups <= 0)
+        r.stream_groups = kStreamGroups;
+    return r;
+}
+
+struct ScanLaunch {
+    int v0;               // first scanline of the launch's row tiles (0 for a packed list)
+    int logical_blocks;   // (tile, group) items: `groups` workgroups per tile, their waves split the hypotheses
+    int per_xcd;          // ... dealt to each XCD
+    unsigned grid;        // workgroups launched
+};
+
+// The launches of a scan of V x U pixels, in order.  Row tiles: one launch per block of rows_per_launch scanlines, the
+// scanlines dealt to the XCDs in turn, every XCD ceil(rows / 8) of them (xcd_logical_block_rows).  A packed list: one launch
+// of at most ceil(V*U/64) tiles -- the device knows how many -- whose fixed grid strides over the items (k2_scan.hpp): ~4
+// workgroups per CU cover any occupancy (the pixel-per-wave kernel's items are 4 / px_waves pixels each).  False when a
+// launch would have more than 2^30 items; *bad_tiles is then its tile count.
+inline bool scan_launches(int V, int U, const ScanPlan& p, std::vector<ScanLaunch>* out, long long* bad_tiles)
+{
+    out->clear();
+    const size_t n = (size_t)V * U;
+    for (int v0 = 0; v0 < V; v0 += p.rows_per_launch) {
+        const int rows = std::min(p.rows_per_launch, V - v0);
+        const long long tiles = p.packed ? (long long)((n + 63) / 64) : (long long)rows * p.tiles_per_row;
+        if (tiles * p.groups > (long long)1 << 30) {
+            *bad_tiles = tiles;
+            return false;
         }
+        ScanLaunch l;
+        l.v0 = v0;
+        l.logical_blocks = (int)(tiles * p.groups);
+        l.per_xcd = p.packed ? (l.logical_blocks + 7) / 8 : ((rows + 7) / 8) * p.tiles_per_row * p.groups;
+        const long long px_items = ((long long)n * p.px_waves + kScanWavesPerTile - 1) / kScanWavesPerTile;
+        l.grid = p.px_waves ? (unsigned)std::min<long long>(px_items, 2048)
+                 : p.packed ? (unsigned)std::min<long long>(tiles * p.groups, 1024)
+                            : (unsigned)(l.per_xcd * 8);
+        out->push_back(l);
+        if (p.packed)
+            break;
+    }
+    return true;
+}
+
+// rslf_depth1d_pile_run computes edge confidence and compacts the mask into row lists in ONE launch when nothing sits
+// between them: no opening of the mask (core.hpp:759-768), row tiles, entry counts that fit an int
+inline bool fuse_k1_compaction(int opening_size, int force_packed, size_t n_pixels)
+{
+    return opening_size <= 1 && force_packed != 1 && n_pixels <= (size_t)INT32_MAX;
+}
+
+// The records and tickets a sweep reserves before its first visit, so that none allocates in the middle of the sequence:
+// what its sparse visits ask for (`sparse`: their request) and the row tiles of their row split
+inline void sweep_reserve(const ScanRequest& sparse, const ScanKernelFacts& f, int row_split_hook, size_t* records, size_t* tickets)
+{
+    const ScanPlan p = plan_scan(sparse, f.nres, f.nres_px);
+    *records = p.records;
+    *tickets = p.tickets;
+    if (row_split_min(sparse, p, row_split_hook)) {
+        const ScanPlan q = plan_scan(row_split_request(sparse), f.nres);
+        *records = std::max(*records, q.records);
+        *tickets = std::max(*tickets, q.tickets);
     }
 }
 

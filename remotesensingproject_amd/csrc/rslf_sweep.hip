@@ -53,23 +53,36 @@ static int ensure_sweep_scratch(rslf_ctx* ctx, const rslf_volume* vol)
     return RSLF_OK;
 }
 
-// The sweep one visit at a time (rslf_sweep_*), and rslf_depth_epi_2d on top of it.  The launch shape of the visits
-// (hypothesis groups, packed tiles, running total) is context state the scan reads: rslf_sweep_end restores it, and after
-// an error the winners are refilled on the next sweep (a claim pass whose apply never ran leaves them set).
+// The sweep one visit at a time (rslf_sweep_*), and rslf_depth_epi_2d on top of it.  rslf_sweep_end closes it; after an
+// error the winners are refilled on the next sweep (a claim pass whose apply never ran leaves them set).
 // The order of the visits (core.hpp:981-990): plan::sweep_order.
 static void sweep_close(rslf_ctx* ctx, bool ok)
 {
     ctx->keep_total = false;
-    ctx->scan_groups = 1;
-    ctx->scan_packed = false;
-    ctx->packed_n_clean = false;
-    ctx->precompacted = 0;
+    ctx->sweep_listed = false;
     ctx->sweep_expect = -1;
     if (!ok) {
         ctx->sweep_cap = 0;   // claims without their apply pass may be left behind: fresh winners and flags next time
         ctx->dirty_cap = 0;
     }
     ctx->sweep_open = false;
+}
+
+// What a visit's scan is given.  After the centre view, propagation has explained most pixels: a visit scans a few per
+// scanline.  They go in one packed list -- the one the previous visit's apply pass made, if it made one -- and each tile's
+// hypotheses are shared out over up to kSweepGroups workgroups (k2_scan.hpp).  The visits sum their pixels; the first is timed.
+static ScanInputs visit_inputs(bool first, bool listed)
+{
+    ScanInputs in;
+    in.zero_total = false;
+    in.timed = first;
+    if (!first) {
+        in.groups = plan::kSweepGroups;
+        in.packed = true;
+        in.lists = listed ? ScanInputs::kPackedList : ScanInputs::kCompact;
+        in.packed_n_zero = !listed;   // k34_median_claim zeroed the length; a listing apply pass set it again
+    }
+    return in;
 }
 
 extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uint8_t* d_Ce_mask_svu, uint8_t* d_scan_mask_svu,
@@ -105,30 +118,17 @@ extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uin
         hipLaunchKernelGGL(k4_count_segments, dim3((unsigned)items), dim3(256), 0, st, mask_svu, rows, U, ctx->remain);
         HIP_TRY(hipGetLastError());
     }
-    {   // the sparse visits' records, sized before the first visit (no allocation in the middle of the sequence).
-        // (The same choice of kernel as rslf_depth_epi_scan makes for linear interpolation without debug hooks; should it
-        // differ, that call sizes the records itself.)
-        size_t recs = 0, tickets = 0;
-        plan::sweep_record_plan(n, dim_d, scan_takes_stream(vol), &recs, &tickets);
-        if (scan_takes_stream(vol)) {   // the row split of the sparse visits: row tiles of the streaming kernel's dense form, in row blocks
-            const size_t tiles_per_row = (size_t)std::max(1, (U + 61) / 63);
-            const size_t per_row = tiles_per_row * plan::kStreamGroups * 64;
-            const size_t rows = std::min<size_t>((size_t)V, std::max<size_t>(1, plan::kPartialBudget / (per_row * plan::kPartialRecordBytes)));
-            recs = std::max(recs, rows * per_row);
-            tickets = std::max(tickets, rows * tiles_per_row);
-        }
-        if (recs) {
-            rc = ensure_group_scratch(ctx, recs, tickets);
-            if (rc)
-                return rc;
-        }
-    }
+    // the sparse visits' records, sized before the first visit (no allocation in the middle of the sequence; should a
+    // visit ask for more -- nearest-neighbour interpolation -- it sizes them itself)
+    rc = sweep_scan_presize(ctx, vol, dim_d, visit_inputs(false, true));
+    if (rc)
+        return rc;
     ctx->keep_total = true;
     ctx->sweep_open = true;
     ctx->sweep_first = true;
+    ctx->sweep_listed = false;
     ctx->sweep_mask_run = mask_svu;
     ctx->sweep_expect = plan::sweep_order(S)[0];
-    ctx->precompacted = 0;
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -148,19 +148,15 @@ extern "C" int rslf_sweep_visit_scan(rslf_ctx* ctx, const rslf_volume* vol, cons
     if (s_hat != ctx->sweep_expect)   // the previous visit has already listed this view's pixels (k4_propagate_apply)
         return fail(RSLF_ERR_INVALID_ARG, "the sweep visits view %d next (core.hpp:981-990), not %d", ctx->sweep_expect, s_hat);
     const size_t n = (size_t)vol->V * vol->U;
-    // After the centre view, propagation has explained most pixels: a visit scans a few per scanline.
-    // Pack them into one list and share each tile's hypotheses out over up to kSweepGroups workgroups (k2_scan.hpp).
-    ctx->scan_groups = ctx->sweep_first ? 1 : plan::kSweepGroups;
-    ctx->scan_packed = !ctx->sweep_first;
     // core.hpp:1012-1028: the pile call is the scan of every EPI followed by the selective median.  In the
     // reference the stored plane keeps the RAW depths and only the local header is rebound to the median
     // (core.hpp:892), which the propagation then paints from: so the scan writes the view's depth plane and the median
     // goes to ctx->filtered (rslf_sweep_visit_finish) -- no plane copies.
-    return rslf_depth_epi_scan(ctx, vol, d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr,
-                               d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr, dmin, dmax, dim_d, s_hat,
-                               d_Ce_svu + (size_t)s_hat * n, d_Ce_mask_svu + (size_t)s_hat * n, d_Cd_svu + (size_t)s_hat * n,
-                               d_depth_svu + (size_t)s_hat * n, d_rbar_svu + (size_t)s_hat * n * vol->C, p,
-                               ctx->sweep_mask_run + (size_t)s_hat * n, nullptr, nullptr, nullptr);
+    return depth_epi_scan(ctx, vol, d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr,
+                          d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr, dmin, dmax, dim_d, s_hat, d_Ce_svu + (size_t)s_hat * n,
+                          d_Ce_mask_svu + (size_t)s_hat * n, d_Cd_svu + (size_t)s_hat * n, d_depth_svu + (size_t)s_hat * n,
+                          d_rbar_svu + (size_t)s_hat * n * vol->C, p, ctx->sweep_mask_run + (size_t)s_hat * n, nullptr, nullptr,
+                          nullptr, visit_inputs(ctx->sweep_first, ctx->sweep_listed));
 }
 RSLF_API_CATCH
 
@@ -222,8 +218,7 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
                        d_Cd_svu, mask_svu, ctx->winner, ctx->dirty, s_next, s_next >= 0 ? d_Ce_mask_svu + (size_t)s_next * n : nullptr, ctx->list,
                        ctx->count, ctx->total, packed_n, ctx->remain, ctx->count + ctx->count_cap);
     HIP_TRY(hipGetLastError());
-    ctx->packed_n_clean = s_next < 0;       // k34_median_claim zeroed the packed list's length; a listing apply pass set it again
-    ctx->precompacted = s_next >= 0 ? 2 : 0;
+    ctx->sweep_listed = s_next >= 0;
     ctx->sweep_expect = s_after;
     ctx->sweep_first = false;
     return RSLF_OK;

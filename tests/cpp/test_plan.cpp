@@ -383,21 +383,6 @@ static void test_scan_plans()
         }
         const int nres = r.use_stream ? (C == 1 ? (r.S >= 192 ? 192 : 0) : (r.S >= 68 ? 68 : r.S >= 48 ? 48 : 0)) : 0;
         check_plan(r, plan_scan(r, nres));
-        size_t recs, tickets;
-        sweep_record_plan((size_t)r.V * r.U, r.dim_d, r.use_stream, &recs, &tickets);
-        if (recs)
-            CHECK(tickets > 0 && (r.use_stream ? recs * kPartialRecordBytes <= kPartialBudget || true : recs <= (size_t)kPackedItemTarget * 64));
-    }
-    // what the sweep sizes in advance is what its sparse visits ask for
-    for (int D : {8, 16, 64, 128, 256, 512}) {
-        ScanRequest r = request(512, 512, 33, 1, D);
-        r.ctx_groups = kSweepGroups;
-        r.ctx_packed = true;
-        r.precompacted = 2;
-        const ScanPlan q = plan_scan(r, 0);
-        size_t recs, tickets;
-        sweep_record_plan((size_t)512 * 512, D, false, &recs, &tickets);
-        CHECK(q.groups == 1 ? recs == 0 || recs >= q.records : (recs == q.records && tickets == q.tickets));
     }
     for (int U : {1, 2, 63, 64, 65, 1920, 4096, 1 << 20, (1 << 24) - 3}) {
         const float f = stream_frac_max(U);
@@ -406,6 +391,228 @@ static void test_scan_plans()
         const float x = (float)(U + 1) + f;
         CHECK(x < (float)(U + 2) || (float)(U + 1) + 1.0f == (float)(U + 1));
     }
+}
+
+// k2_stream.hpp's resident prefixes and a register kernel's waves, as the library passes them in (kernel_facts)
+static ScanKernelFacts facts(int S, int C, int reg_waves = 3)
+{
+    const int nres = C == 1 ? (S >= 192 ? 192 : 0) : (S >= 68 ? 68 : S >= 48 ? 48 : 0);
+    return ScanKernelFacts{pick_spad(S, C) ? reg_waves : 0, nres, C == 3 ? (S >= 48 ? 48 : 0) : nres};
+}
+
+static void test_scan_kernel_choice()
+{
+    // The rule as rslf_pile.hip applied it before it moved here, as a table: channels, views, radiances in range, linear
+    // interpolation, force_scan, dense uniform launch -> slot count and kernel
+    struct Case {
+        int C, S;
+        bool in_range, linear;
+        int force;
+        bool dense;
+        int spad, kind;
+    };
+    const Case cases[] = {
+        {1, 101, true, true, 0, true, 104, RSLF_SCAN_REG},     {1, 101, true, true, 0, false, 104, RSLF_SCAN_REG},
+        {1, 192, true, true, 0, true, 192, RSLF_SCAN_REG},     {1, 193, true, true, 0, true, 0, RSLF_SCAN_STREAM},
+        {1, 193, true, true, 0, false, 0, RSLF_SCAN_STREAM},   {3, 48, true, true, 0, true, 48, RSLF_SCAN_REG},
+        {3, 49, true, true, 0, true, 0, RSLF_SCAN_STREAM},     {3, 122, true, true, 0, true, 0, RSLF_SCAN_STREAM},
+        {3, 123, true, true, 0, true, 0, RSLF_SCAN_CHIP},      {3, 123, true, true, 0, false, 0, RSLF_SCAN_STREAM},
+        {3, 201, true, true, 0, true, 0, RSLF_SCAN_CHIP},      {3, 201, true, true, 0, false, 0, RSLF_SCAN_STREAM},
+        {3, 220, true, true, 0, true, 0, RSLF_SCAN_CHIP},      {3, 221, true, true, 0, true, 0, RSLF_SCAN_STREAM},
+        // nearest-neighbour sampling, radiances out of range: the generic kernel only
+        {1, 101, true, false, 0, true, 0, RSLF_SCAN_GENERIC},  {3, 201, true, false, 0, true, 0, RSLF_SCAN_GENERIC},
+        {3, 48, true, false, 2, false, 0, RSLF_SCAN_GENERIC},  {1, 101, false, true, 0, true, 0, RSLF_SCAN_GENERIC},
+        {3, 201, false, true, 0, true, 0, RSLF_SCAN_GENERIC},  {3, 49, false, true, 2, false, 0, RSLF_SCAN_GENERIC},
+        // force_scan 1: generic; 2: streaming wherever it can run, never on chip
+        {1, 101, true, true, 1, true, 0, RSLF_SCAN_GENERIC},   {3, 201, true, true, 1, true, 0, RSLF_SCAN_GENERIC},
+        {1, 101, true, true, 2, true, 0, RSLF_SCAN_STREAM},    {3, 48, true, true, 2, false, 0, RSLF_SCAN_STREAM},
+        {3, 201, true, true, 2, true, 0, RSLF_SCAN_STREAM},    {3, 123, true, true, 2, true, 0, RSLF_SCAN_STREAM},
+        // the waves' offset tables must fit 48 KiB of LDS: 3072 views do, 3073 do not
+        {1, 3072, true, true, 0, true, 0, RSLF_SCAN_STREAM},   {1, 3073, true, true, 0, true, 0, RSLF_SCAN_GENERIC},
+        {3, 3073, true, true, 2, true, 0, RSLF_SCAN_GENERIC},
+    };
+    for (const Case& c : cases) {
+        ScanRequest r = request(64, 512, c.S, c.C, 64);
+        choose_scan_kernel(&r, c.in_range, c.linear, c.force, c.dense, facts(c.S, c.C, 5));
+        const int kind = r.spad ? RSLF_SCAN_REG : r.use_chip ? RSLF_SCAN_CHIP : r.use_stream ? RSLF_SCAN_STREAM : RSLF_SCAN_GENERIC;
+        CHECK(r.spad == c.spad && kind == c.kind && !(r.use_stream && r.use_chip) && !(r.spad && (r.use_stream || r.use_chip)));
+        CHECK(r.reg_waves == (r.spad ? 5 : 0));
+        CHECK(r.chip_wave_floats == (r.use_chip ? chip_wave_floats(c.S, kChipLadder[chip_rung_for(c.S)]) : 0));
+        const ScanKernelFacts f = facts(c.S, c.C);
+        const ScanPlan p = plan_scan(r, f.nres, f.nres_px);   // row tiles: the kind the plan reports is the kernel's row form
+        CHECK(p.kind == c.kind && p.spad == c.spad);
+        r.ctx_packed = true;                                    // packed, 64 hypotheses: the pixel-per-wave forms
+        r.use_chip = false;
+        r.use_stream = c.kind == RSLF_SCAN_STREAM || c.kind == RSLF_SCAN_CHIP;
+        const int px = plan_scan(r, f.nres, f.nres_px).kind;
+        CHECK(px == (c.kind == RSLF_SCAN_REG ? RSLF_SCAN_REG_PX : c.kind == RSLF_SCAN_GENERIC ? RSLF_SCAN_GENERIC : RSLF_SCAN_STREAM_PX));
+    }
+    // K1 and the compaction in one launch: no opening, row tiles, entry counts that fit an int
+    CHECK(fuse_k1_compaction(1, -1, 1080 * 1920) && fuse_k1_compaction(0, 0, 1) && !fuse_k1_compaction(3, -1, 1));
+    CHECK(!fuse_k1_compaction(1, 1, 1) && !fuse_k1_compaction(1, -1, (size_t)INT32_MAX + 1) && fuse_k1_compaction(1, -1, INT32_MAX));
+}
+
+static void check_launches(int V, int U, const ScanPlan& p, const std::vector<ScanLaunch>& ls)
+{
+    // row tiles: consecutive blocks of rows_per_launch scanlines over [0, V); packed: one launch
+    CHECK(!ls.empty() && ls[0].v0 == 0 && (!p.packed || ls.size() == 1));
+    for (size_t i = 0; i < ls.size(); i++) {
+        const ScanLaunch& l = ls[i];
+        CHECK(l.logical_blocks > 0 && l.per_xcd > 0 && l.grid > 0);
+        if (!p.packed) {
+            const int rows = std::min(p.rows_per_launch, V - l.v0);
+            CHECK(l.v0 == (int)i * p.rows_per_launch && rows >= 1);
+            CHECK(l.logical_blocks == rows * p.tiles_per_row * p.groups && l.grid == (unsigned)l.per_xcd * 8);
+            CHECK((long long)l.per_xcd * 8 >= l.logical_blocks);   // every XCD's share holds its scanlines' blocks
+        } else {
+            CHECK(l.logical_blocks == (int)(((size_t)V * U + 63) / 64) * p.groups && l.grid <= (p.px_waves ? 2048u : 1024u));
+        }
+    }
+    CHECK(p.packed || ls.back().v0 + p.rows_per_launch >= V);
+}
+
+static void test_scan_launches()
+{
+    std::vector<ScanLaunch> ls;
+    long long bad = 0;
+    // c3: one launch of 1080 x 30 row tiles, 135 scanlines per XCD
+    ScanPlan p = plan_scan(request(1080, 1920, 101, 1, 256), 0);
+    CHECK(scan_launches(1080, 1920, p, &ls, &bad) && ls.size() == 1);
+    CHECK(ls[0].v0 == 0 && ls[0].logical_blocks == 32400 && ls[0].per_xcd == 135 * 30 && ls[0].grid == 32400);
+    check_launches(1080, 1920, p, ls);
+    // c5, streaming kernel: 16 groups of 63-pixel tiles in blocks of 126 scanlines -- 18 launches, the last of 18 scanlines
+    p = plan_scan(request(2160, 4096, 201, 3, 512), 68);
+    CHECK(scan_launches(2160, 4096, p, &ls, &bad) && ls.size() == 18);
+    CHECK(ls[0].logical_blocks == 126 * 65 * 16 && ls[0].per_xcd == 16 * 65 * 16 && ls[0].grid == 16 * 65 * 16 * 8);
+    CHECK(ls[17].v0 == 2142 && ls[17].logical_blocks == 18 * 65 * 16 && ls[17].per_xcd == 3 * 65 * 16 && ls[17].grid == 3 * 65 * 16 * 8);
+    check_launches(2160, 4096, p, ls);
+    {   // ... on chip: 8 groups, blocks of 252 scanlines
+        ScanRequest chip = request(2160, 4096, 201, 3, 512);
+        choose_scan_kernel(&chip, true, true, 0, true, facts(201, 3));
+        CHECK(chip.use_chip);
+        p = plan_scan(chip, 68);
+        CHECK(scan_launches(2160, 4096, p, &ls, &bad) && ls.size() == 9 && ls[8].v0 == 2016 && ls[8].logical_blocks == 144 * 65 * 8);
+        check_launches(2160, 4096, p, ls);
+    }
+    // a sweep's sparse visit, packed: the pixel-per-wave kernel's strided grid of at most 2048 workgroups ...
+    ScanRequest sparse = request(512, 512, 33, 1, 128);
+    sparse.ctx_groups = kSweepGroups;
+    sparse.ctx_packed = true;
+    sparse.precompacted = 2;
+    p = plan_scan(sparse, 0);
+    CHECK(p.kind == RSLF_SCAN_REG_PX && scan_launches(512, 512, p, &ls, &bad) && ls.size() == 1);
+    CHECK(ls[0].logical_blocks == 4096 && ls[0].per_xcd == 512 && ls[0].grid == 2048);
+    check_launches(512, 512, p, ls);
+    sparse.V = 4;   // (fewer items: 2048 pixels x 2 waves / 4 waves per workgroup)
+    CHECK(scan_launches(4, 512, plan_scan(sparse, 0), &ls, &bad) && ls[0].grid == 1024 && ls[0].logical_blocks == 32);
+    sparse.V = 512;
+    sparse.px_mode = 0;   // ... or the pixel-per-lane kernel's: 16 groups, at most 1024 workgroups
+    p = plan_scan(sparse, 0);
+    CHECK(p.kind == RSLF_SCAN_REG && p.packed && scan_launches(512, 512, p, &ls, &bad) && ls.size() == 1);
+    CHECK(ls[0].logical_blocks == 4096 * 16 && ls[0].per_xcd == 8192 && ls[0].grid == 1024);
+    check_launches(512, 512, p, ls);
+    {   // MansionLR-like sparse visit (720 x 1146, 100 views RGB): the pixel-per-wave launch and its row split, whose row tiles
+        // are the streaming kernel's dense form: kStreamGroups groups, halved to 8 so that 120 hypotheses keep two per wave
+        ScanRequest m = request(720, 1146, 100, 3, 120);
+        m.ctx_groups = kSweepGroups;
+        m.ctx_packed = true;
+        m.precompacted = 2;
+        choose_scan_kernel(&m, true, true, 0, false, facts(100, 3));
+        p = plan_scan(m, 68, 48);
+        CHECK(p.kind == RSLF_SCAN_STREAM_PX && p.stream_nres == 48 && row_split_min(m, p, 1) == kRowSplitMin);
+        CHECK(row_split_min(m, p, 0) == 0 && row_split_min(m, p, 200) == 200);
+        CHECK(scan_launches(720, 1146, p, &ls, &bad) && ls.size() == 1 && ls[0].logical_blocks == 12893 && ls[0].grid == 2048);
+        const ScanPlan r = plan_scan(row_split_request(m), 68);
+        CHECK(r.kind == RSLF_SCAN_STREAM && !r.packed && r.groups == 8 && r.stream_nres == 68 && r.tile_w == 64);
+        CHECK(r.tiles_per_row == 18 && r.rows_per_launch == 720 && r.records == (size_t)720 * 18 * 8 * 64);
+        CHECK(scan_launches(720, 1146, r, &ls, &bad) && ls.size() == 1);
+        CHECK(ls[0].logical_blocks == 720 * 18 * 8 && ls[0].per_xcd == 90 * 18 * 8 && ls[0].grid == 90 * 18 * 8 * 8);
+        check_launches(720, 1146, r, ls);
+        m.dim_d = 256;   // enough hypotheses for all 16 groups: blocks of 455 scanlines under the record budget
+        const ScanPlan r16 = plan_scan(row_split_request(m), 68);
+        CHECK(r16.groups == kStreamGroups && r16.rows_per_launch == 455);
+        CHECK(scan_launches(720, 1146, r16, &ls, &bad) && ls.size() == 2 && ls[1].v0 == 455);
+        CHECK(ls[0].logical_blocks == 455 * 18 * 16 && ls[0].per_xcd == 57 * 18 * 16 && ls[1].logical_blocks == 265 * 18 * 16);
+        check_launches(720, 1146, r16, ls);
+        m.dim_d = 120;
+        // no split on row tiles, nor for the register kernels
+        CHECK(row_split_min(m, r, 1) == 0 && row_split_min(sparse, plan_scan(sparse, 0), 1) == 0);
+    }
+    // the grid limit: more than 2^30 (tile, group) items in one launch is refused, with the tile count
+    ScanRequest wide = request(40000, 2000000, 33, 1, 128);
+    wide.spad = 0;   // generic kernel: no groups, every scanline in one launch
+    p = plan_scan(wide, 0);
+    CHECK(p.groups == 1 && p.rows_per_launch == 40000 && !scan_launches(40000, 2000000, p, &ls, &bad) && bad == 40000LL * 31250);
+    wide.V = 20000;
+    CHECK(scan_launches(20000, 2000000, plan_scan(wide, 0), &ls, &bad));
+    ScanRequest big = request(46340, 46340, 33, 1, 512);   // a packed list just under 2^31 entries, 64 groups forced
+    big.spad = 0;
+    big.ctx_packed = true;
+    big.force_groups = 64;
+    p = plan_scan(big, 0);
+    CHECK(p.packed && p.groups == 64 && !scan_launches(46340, 46340, p, &ls, &bad) && bad == (long long)((46340LL * 46340 + 63) / 64));
+}
+
+static void test_sweep_reserve()
+{
+    // What a sweep reserves before its first visit covers what every sparse visit asks for -- the packed launch (whether
+    // the previous apply pass listed its pixels or not) and its row split -- for any shape, without debug hooks
+    std::mt19937 rng(11);
+    for (int it = 0; it < 20000; it++) {
+        const int C = (rng() & 1) ? 1 : 3;
+        const int V = 1 + (int)(rng() % 2200), U = 1 + (int)(rng() % 4200), S = 1 + (int)(rng() % 300), D = 2 + (int)(rng() % 600);
+        const ScanKernelFacts f = facts(S, C, 1 + (int)(rng() % 8));
+        ScanRequest sparse = request(V, U, S, C, D);
+        sparse.num_cus = (rng() % 8 == 0) ? 0 : 256;
+        sparse.ctx_groups = kSweepGroups;
+        sparse.ctx_packed = true;
+        sparse.precompacted = 2;
+        choose_scan_kernel(&sparse, rng() % 5 != 0, true, 0, false, f);
+        size_t recs = 0, tickets = 0;
+        sweep_reserve(sparse, f, 1, &recs, &tickets);
+        CHECK(!recs || tickets > 0);
+        CHECK(sparse.use_stream || recs <= (size_t)kPackedItemTarget * 64);   // the packed launches of the other kernels adapt
+        for (int lists : {0, 2}) {
+            ScanRequest visit = sparse;
+            visit.precompacted = lists;
+            const ScanPlan p = plan_scan(visit, f.nres, f.nres_px);
+            CHECK(p.packed && recs >= p.records && tickets >= p.tickets);
+            if (row_split_min(visit, p, 1)) {
+                const ScanPlan q = plan_scan(row_split_request(visit), f.nres);
+                CHECK(recs >= q.records && tickets >= q.tickets && q.records > 0);
+            }
+        }
+    }
+    // what the sweep sizes in advance is exactly what its sparse visits ask for, with and without the pixel-per-wave kernel
+    size_t recs = 0, tickets = 0;
+    for (int D : {8, 16, 64, 128, 256, 512})
+        for (int px : {-1, 0}) {
+            ScanRequest r = request(512, 512, 33, 1, D);
+            r.ctx_groups = kSweepGroups;
+            r.ctx_packed = true;
+            r.precompacted = 2;
+            r.px_mode = px;
+            choose_scan_kernel(&r, true, true, 0, false, facts(33, 1));
+            const ScanPlan q = plan_scan(r, 0);
+            sweep_reserve(r, facts(33, 1), 1, &recs, &tickets);
+            CHECK(recs == q.records && tickets == q.tickets && (q.groups == 1) == (recs == 0));
+        }
+    // the shapes: c3-like sparse visits take the pixel-per-wave kernel (no records); MansionLR's row split takes 720 x 18
+    // tiles x 8 groups
+    ScanRequest r = request(1080, 1920, 101, 1, 256);
+    r.ctx_groups = kSweepGroups;
+    r.ctx_packed = true;
+    r.precompacted = 2;
+    sweep_reserve(r, facts(101, 1), 1, &recs, &tickets);
+    CHECK(recs == 0 && tickets == 0);
+    ScanRequest m = request(720, 1146, 100, 3, 120);
+    m.ctx_groups = kSweepGroups;
+    m.ctx_packed = true;
+    m.precompacted = 2;
+    sweep_reserve(m, facts(100, 3), 1, &recs, &tickets);
+    CHECK(recs == (size_t)720 * 18 * 8 * 64 && tickets == (size_t)720 * 18);
+    sweep_reserve(m, facts(100, 3), 0, &recs, &tickets);   // row split off (debug key): nothing to reserve
+    CHECK(recs == 0 && tickets == 0);
 }
 
 static void test_chip_ladder()
@@ -595,6 +802,9 @@ int main()
     test_host_copies();
     test_plane_layout();
     test_scan_plans();
+    test_scan_kernel_choice();
+    test_scan_launches();
+    test_sweep_reserve();
     test_chip_ladder();
     test_visit_schedule();
     std::printf("plan tests ok: %d checks\n", g_checks);
