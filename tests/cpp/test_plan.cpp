@@ -553,6 +553,65 @@ static void test_scan_launches()
     CHECK(p.packed && p.groups == 64 && !scan_launches(46340, 46340, p, &ls, &bad) && bad == (long long)((46340LL * 46340 + 63) / 64));
 }
 
+// The shapes of tests/test_gpu_sweep_views.py, as its sweeps and fine-to-coarse levels ask for them (visit_inputs,
+// scan_request): what each visit runs there is what this says.
+static void test_sweep_view_plans()
+{
+    struct Vol {
+        int C, S, V, U, D;
+        int first_kind;
+    };
+    const Vol vols[] = {{3, 100, 6, 230, 120, RSLF_SCAN_STREAM}, {3, 151, 6, 210, 48, RSLF_SCAN_CHIP}, {1, 224, 8, 250, 64, RSLF_SCAN_STREAM},
+                        {1, 101, 6, 300, 256, RSLF_SCAN_REG}};
+    for (const Vol& v : vols) {
+        const ScanKernelFacts f = facts(v.S, v.C);
+        // the first visit: dense, one hypothesis grid for all pixels
+        ScanRequest first = request(v.V, v.U, v.S, v.C, v.D);
+        choose_scan_kernel(&first, true, true, 0, true, f);
+        const ScanPlan p = plan_scan(first, f.nres, f.nres_px);
+        CHECK(p.kind == v.first_kind && !p.packed && p.px_waves == 0);
+        // a sparse visit over the packed list the previous visit's apply pass left: pixel-per-wave, and for the
+        // stream-class volumes the row split of the list's long rows
+        ScanRequest sparse = request(v.V, v.U, v.S, v.C, v.D);
+        sparse.ctx_groups = kSweepGroups;
+        sparse.ctx_packed = true;
+        sparse.precompacted = 2;
+        choose_scan_kernel(&sparse, true, true, 0, false, f);
+        const ScanPlan q = plan_scan(sparse, f.nres, f.nres_px);
+        CHECK(q.packed && q.px_waves > 0 && q.groups == 1);
+        if (v.first_kind == RSLF_SCAN_REG) {
+            CHECK(q.kind == RSLF_SCAN_REG_PX && row_split_min(sparse, q, 1) == 0);
+        } else {
+            CHECK(q.kind == RSLF_SCAN_STREAM_PX && q.stream_nres == f.nres_px && row_split_min(sparse, q, 1) == kRowSplitMin);
+            CHECK(row_split_min(sparse, q, 0) == 0);
+            const ScanPlan r = plan_scan(row_split_request(sparse), f.nres);
+            CHECK(r.kind == RSLF_SCAN_STREAM && !r.packed && r.stream_nres == f.nres);
+        }
+        // ... without the pixel-per-wave kernel (the px hook 0): the packed list goes to the pixel-per-lane forms, no split
+        sparse.px_mode = 0;
+        const ScanPlan n = plan_scan(sparse, f.nres, f.nres_px);
+        CHECK(n.packed && n.px_waves == 0 && n.kind == (v.first_kind == RSLF_SCAN_REG ? RSLF_SCAN_REG : RSLF_SCAN_STREAM));
+        CHECK(row_split_min(sparse, n, 1) == 0);
+    }
+    // the resident prefixes at these view counts: 68 (row) and 48 (pixel-per-wave) at 100 views RGB, 192 for 224 views
+    CHECK(facts(100, 3).nres == 68 && facts(100, 3).nres_px == 48 && facts(224, 1).nres == 192 && facts(224, 1).nres_px == 192);
+    // MansionLR's own first visit (720 x 1146): the streaming kernel's few groups, three as 120 hypotheses divide over 12 waves
+    {
+        ScanRequest m = request(720, 1146, 100, 3, 120);
+        choose_scan_kernel(&m, true, true, 0, true, facts(100, 3));
+        const ScanPlan p = plan_scan(m, 68, 48);
+        CHECK(p.kind == RSLF_SCAN_STREAM && p.groups == 3 && p.stream_nres == 68);
+    }
+    // a fine-to-coarse level (per-pixel hypothesis ranges): never the on-chip kernel, whatever the view count
+    for (int S : {100, 123, 151, 201, 220}) {
+        ScanRequest r = request(32, 64, S, 3, 32);
+        choose_scan_kernel(&r, true, true, 0, false, facts(S, 3));
+        CHECK(!r.use_chip && r.use_stream && plan_scan(r, facts(S, 3).nres, facts(S, 3).nres_px).kind == RSLF_SCAN_STREAM);
+        choose_scan_kernel(&r, true, true, 0, true, facts(S, 3));
+        CHECK(r.use_chip == (S >= kChipMinS));
+    }
+}
+
 static void test_sweep_reserve()
 {
     // What a sweep reserves before its first visit covers what every sparse visit asks for -- the packed launch (whether
@@ -804,6 +863,7 @@ int main()
     test_scan_plans();
     test_scan_kernel_choice();
     test_scan_launches();
+    test_sweep_view_plans();
     test_sweep_reserve();
     test_chip_ladder();
     test_visit_schedule();

@@ -1,0 +1,181 @@
+"""Every compiled instantiation of the depth scan (K2) against the CPU oracle, one table row per (instantiation, launch form).
+
+The scan is a family of template instantiations: the register kernels per slot count and channel count (k2_scan_reg,
+k2_scan_reg_packed, k2_scan_reg_px; RSLF_SPAD_LIST_* in rslf_plan.hpp), each with its own waves per SIMD, running best in
+LDS or not, trimmed last pass or not and packed gather unit (k2_reg.hpp); the streaming kernels per channel count and
+resident prefix, in row, packed and pixel-per-wave form (k2_stream.hpp); the on-chip kernel per rung of kChipLadder,
+plus the top rung's exact and ragged-tail forms (rslf_chip_a/b/c.hip); and the generic kernel.  The tables below name
+one volume for every cell; tests/test_scan_coverage_cpu.py checks, from the same headers the library is built from,
+that no compiled cell is missing.  They are plain data, importable without torch or a GPU.
+
+Every volume has hypothesis lines that leave the EPI at both borders and lines that stay inside it, a row length that is
+not a multiple of 64, a hypothesis count that does not split evenly over a tile's waves, a dark band (gaps in the pixel
+lists), and a scanline whose views other than the centre one hold one constant radiance: there every hypothesis whose line
+stays inside the EPI reads the same samples, so its pixels tie across all hypotheses -- across lanes, waves, hypothesis
+groups and records -- and the first maximum must win.  tests/test_scan_coverage_cpu.py checks that, for every volume, an
+oracle that takes the LAST maximum gives other indices.  Bit-exact against the oracle, C_d within 1e-5 (tests/util.py).
+
+On the GPU a row asserts the kernel kind (stats.scan_kernel) and slot count (stats.s_pad) that ran.  Which resident prefix,
+rung, group count or packing ran is not reported by the library: those rest on the plan mapping that
+tests/test_scan_coverage_cpu.py checks with the plan's own functions."""
+from collections import namedtuple
+
+import numpy as np
+import pytest
+
+from tests.util import assert_pile_parity
+
+pytestmark = pytest.mark.gpu
+
+# RSLF_SCAN_* (include/rslf_hip.h)
+GENERIC, REG, STREAM, CHIP, REG_PX, STREAM_PX = 0, 1, 2, 3, 4, 5
+
+# ---- the register kernels: (channels, views, slot count the plan picks) --------------------------------------------
+# Each slot count once with padded slots live (views strictly between the slot count below and this one) and once exact.
+REGISTER = [
+    (1, 5, 8), (1, 8, 8),            # 7 waves
+    (1, 13, 16), (1, 16, 16),        # 7 waves, best in LDS
+    (1, 21, 24), (1, 24, 24),
+    (1, 29, 32), (1, 32, 32),
+    (1, 37, 40), (1, 40, 40),        # 5 waves, best in LDS
+    (1, 45, 48), (1, 48, 48),        # 5 waves, best in LDS, last pass whole
+    (1, 53, 56), (1, 56, 56),
+    (1, 61, 64), (1, 64, 64),
+    (1, 69, 72), (1, 72, 72),
+    (1, 77, 80), (1, 80, 80),        # 4 waves, best in LDS, last pass whole; packed: long gather unit
+    (1, 85, 88), (1, 88, 88),        # ... the same
+    (1, 93, 96), (1, 96, 96),        # packed: long gather unit
+    (1, 101, 104), (1, 104, 104),    # 3 waves, best in LDS, trimmed
+    (1, 109, 112), (1, 112, 112),    # 3 waves, best in LDS, trimmed
+    (1, 117, 120), (1, 120, 120),    # 3 waves, best in LDS, last pass whole
+    (1, 125, 128), (1, 128, 128),
+    (1, 141, 144), (1, 144, 144),
+    (1, 157, 160), (1, 160, 160),
+    (1, 173, 176), (1, 176, 176),
+    (1, 189, 192), (1, 192, 192),
+    (3, 5, 8), (3, 8, 8),
+    (3, 13, 16), (3, 16, 16),
+    (3, 21, 24), (3, 24, 24),        # 4 waves, best in LDS
+    (3, 29, 32), (3, 32, 32),
+    (3, 37, 40), (3, 40, 40),        # 3 waves, best in LDS
+    (3, 45, 48), (3, 48, 48),
+]
+# row tiles; row tiles shared by hypothesis groups (the records' merge, then the trimmed kernels' LastPassRbar); one packed
+# pixel list (k2_scan_reg_packed); pixel-per-wave (k2_scan_reg_px)
+REG_FORMS = {
+    "row": (dict(force_groups=1), REG),
+    "groups": (dict(force_groups=4), REG),
+    "packed": (dict(force_packed=1, px=0), REG),
+    "px": (dict(force_packed=1, px=1), REG_PX),
+}
+
+# ---- the streaming kernels: (channels, views, resident prefix of the row / packed form, of the pixel-per-wave form) ---
+# (force_scan="stream" on every row: below the resident prefixes' view counts only the hook selects them)
+STREAM_PREFIXES = [
+    (1, 33, 0, 0),
+    (1, 200, 192, 192),
+    (3, 21, 0, 0),
+    (3, 57, 48, 48),
+    (3, 100, 68, 48),
+]
+STREAM_FORMS = {
+    "row_share0": (dict(force_scan="stream", stream_share=0), STREAM),      # 64-pixel row tiles
+    "row_share2": (dict(force_scan="stream", stream_share=2), STREAM),      # 63-pixel row tiles, shared right taps
+    "packed_groups": (dict(force_scan="stream", force_packed=1, px=0, force_groups=4), STREAM),
+    "px": (dict(force_scan="stream", force_packed=1, px=1), STREAM_PX),
+}
+
+# ---- the on-chip kernel (RGB): (views, views of the rung that runs, hypothesis groups: 0 one, else forced) --------------
+# Every rung exact and padded (above the rung below it, at most kChipPadMax views short), one workgroup per tile (the pixel
+# written directly, no records); the top rung exact and with a ragged tail; and hypothesis groups once per translation
+# unit's list (RSLF_CHIP_LADDER_C / _B / _A), four of them -- what the automatic rule settles on at 37 hypotheses.
+CHIP_RUNGS = [
+    (124, 127, 0), (127, 127, 0),
+    (132, 135, 0), (135, 135, 0), (135, 135, 4),
+    (140, 143, 0), (143, 143, 0),
+    (148, 151, 0), (151, 151, 0),
+    (156, 159, 0), (159, 159, 0),
+    (164, 167, 0), (167, 167, 0), (164, 167, 4),
+    (172, 175, 0), (175, 175, 0),
+    (180, 183, 0), (183, 183, 0),
+    (188, 191, 0), (191, 191, 0), (191, 191, 4),
+    (196, 201, 0), (201, 201, 0),    # the top rung padded (its own instantiation) and exact (another)
+    (211, 201, 0),                   # ... and its ragged tail
+]
+
+# ---- the generic kernel: (channels, views) ----------------------------------------------------------------------------
+GENERIC_VOLUMES = [(1, 33), (3, 17)]
+
+Case = namedtuple("Case", "id family C S form hooks kernel slots")
+
+
+def _cases():
+    out = []
+    for C, S, slots in REGISTER:
+        for form, (h, k) in REG_FORMS.items():
+            out.append(Case("reg-c%d-s%d-%s" % (C, S, form), "reg", C, S, form, h, k, slots))
+    for C, S, nres, nres_px in STREAM_PREFIXES:
+        for form, (h, k) in STREAM_FORMS.items():
+            out.append(Case("stream-c%d-s%d-%s" % (C, S, form), "stream", C, S, form, h, k, 0))
+    for S, rung, groups in CHIP_RUNGS:
+        form = "groups" if groups else "single"
+        h = dict(force_groups=groups) if groups else dict(stream_groups=1)
+        out.append(Case("chip-s%d-%s" % (S, form), "chip", 3, S, form, h, CHIP, 0))
+    for C, S in GENERIC_VOLUMES:
+        out.append(Case("generic-c%d-s%d" % (C, S), "generic", C, S, "plain", dict(force_scan="generic"), GENERIC, 0))
+    return out
+
+
+CASES = _cases()
+
+
+def volume(C, S):
+    """The volume of every row with C channels and S views: (vol [V, S, U, C], dmin, dmax, D)."""
+    U = 70 + (37 * S + 11 * C) % 131
+    if U % 64 == 0:
+        U += 1
+    V = 2 if S >= 100 else 3
+    D = 37                                   # 37 hypotheses: no even split over 4 waves, 4 groups still take 2 per wave
+    reach = U / (2.0 * S)                    # the extreme hypotheses' lines reach ~U/4 pixels from the centre view
+    dmin = float(np.float32(-reach))
+    dmax = float(np.float32(0.75 * reach))
+    rng = np.random.default_rng(7000 + 10 * S + C)
+    vol = rng.uniform(0.0, 1.0, size=(V, S, U, C)).astype(np.float32)
+    vol[:, :, U // 3: U // 3 + 5] *= np.float32(0.05)   # a dark band: the shadow cut leaves gaps in the pixel lists
+    vol[1] = np.float32(0.5)                             # ties: every view but the centre one constant, so every line that
+    vol[1, S // 2] = vol[0, S // 2]                      # stays inside the EPI reads the same samples (s_hat = S // 2)
+    return np.ascontiguousarray(vol), dmin, dmax, D
+
+
+@pytest.fixture(scope="module")
+def rs():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    from remotesensingproject_amd import depth
+    return depth
+
+
+@pytest.fixture(scope="module")
+def oracle_for(oracle_mod):
+    """The oracle's pile run of each volume, computed once and compared with every launch form of it."""
+    cache = {}
+
+    def get(C, S):
+        if (C, S) not in cache:
+            vol, dmin, dmax, D = volume(C, S)
+            cache[(C, S)] = oracle_mod.depth1d_pile_run(vol, dmin, dmax, D)
+        return cache[(C, S)]
+    return get
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_scan_instantiation_against_the_oracle(rs, oracle_for, hooks, case):
+    vol, dmin, dmax, D = volume(case.C, case.S)
+    ref = oracle_for(case.C, case.S)
+    if case.hooks:
+        hooks(**case.hooks)
+    comp = rs.Depth1DComputer_pile(vol, dmin, dmax, D, -1, 1.0)   # (already in [0, 1): no rescale)
+    comp.run()
+    st = comp.stats
+    assert (st.scan_kernel, st.s_pad) == (case.kernel, case.slots), case.id
+    assert_pile_parity(comp.results(), ref, label=case.id)
