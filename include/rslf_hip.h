@@ -174,16 +174,23 @@ int rslf_volume_describe(const rslf_volume* vol, rslf_volume_desc* out);
 /* Host EPIs as the reference holds them: h_epis[v] -> S rows of U*C values,
  * row_stride_bytes apart (cv::Mat::step).  u8: x * float(1/255) (dc.hpp:470).
  * f32: x * float(1/double(scale)); scale < 0 => the max over all EPIs
- * (dc.hpp:442-460, :474).  scale_used is nullable. */
+ * (dc.hpp:442-460, :474).  scale_used is nullable.
+ * u16 (CV_16U): the reference's rule for every depth other than 8U, the f32 one
+ * applied to float(x) (exact for ushort): the slab and scale_used are
+ * bit-identical to the f32 upload of the same values with the same factor. */
 int rslf_volume_upload_epis_f32(rslf_volume* vol, const float* const* h_epis, size_t row_stride_bytes,
                                 float epi_scale_factor, float* scale_used);
 int rslf_volume_upload_epis_u8(rslf_volume* vol, const uint8_t* const* h_epis, size_t row_stride_bytes);
+int rslf_volume_upload_epis_u16(rslf_volume* vol, const uint16_t* const* h_epis, size_t row_stride_bytes,
+                                float epi_scale_factor, float* scale_used);
 /* Host image stack as read from disk, h_imgs[s] -> V rows of U*C values: the
  * input of rslf::build_epis_from_imgs (src/rslf_io.cpp:194-227); the
  * [s][v][u] -> [v][s][u] transposition happens on the device. */
 int rslf_volume_upload_images_f32(rslf_volume* vol, const float* const* h_imgs, size_t row_stride_bytes,
                                   float epi_scale_factor, float* scale_used);
 int rslf_volume_upload_images_u8(rslf_volume* vol, const uint8_t* const* h_imgs, size_t row_stride_bytes);
+int rslf_volume_upload_images_u16(rslf_volume* vol, const uint16_t* const* h_imgs, size_t row_stride_bytes,
+                                  float epi_scale_factor, float* scale_used);
 /* The same with the two per-EPI options of rslf::build_epis_from_imgs (src/rslf_io.cpp:194-227, arguments `transpose`,
  * `rotate_180`): the EPI of scanline v is E[i][x] = h_imgs[i](v, x); transpose stores E^T -- the volume then has
  * S = image columns and U = number of images, h_imgs holds vol->U images of V rows x vol->S columns -- and
@@ -192,6 +199,8 @@ int rslf_volume_upload_images_xf_f32(rslf_volume* vol, const float* const* h_img
                                      float epi_scale_factor, float* scale_used, int transpose, int rotate_180);
 int rslf_volume_upload_images_xf_u8(rslf_volume* vol, const uint8_t* const* h_imgs, size_t row_stride_bytes,
                                     int transpose, int rotate_180);
+int rslf_volume_upload_images_xf_u16(rslf_volume* vol, const uint16_t* const* h_imgs, size_t row_stride_bytes,
+                                     float epi_scale_factor, float* scale_used, int transpose, int rotate_180);
 /* Device-resident dense [V][S][U][C] float32 (already on this GPU). */
 int rslf_volume_pack_device_f32(rslf_volume* vol, const float* d_vsuc, float epi_scale_factor, float* scale_used);
 
@@ -320,6 +329,12 @@ int rslf_multi_depth1d_pile_u8(rslf_multi* m, const uint8_t* const* h_epis, size
                                float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
                                float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu, float* h_rbar_vu,
                                int32_t* h_idx_vu, float* h_score_vu, float* h_depth_raw_vu, rslf_stats* stats);
+/* CV_16U EPIs: arguments as rslf_multi_depth1d_pile_f32 (the scale rule of rslf_volume_upload_epis_u16); results
+ * bit-identical to the f32 form on the same values. */
+int rslf_multi_depth1d_pile_u16(rslf_multi* m, const uint16_t* const* h_epis, size_t row_stride_bytes, int V, int S, int U, int C,
+                                float epi_scale_factor, float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
+                                float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu, float* h_rbar_vu,
+                                int32_t* h_idx_vu, float* h_score_vu, float* h_depth_raw_vu, rslf_stats* stats, float* scale_used);
 
 /* ---- "next" row: the 2-D sweep over all views ------ */
 /* Planes here are [S][V][U] (the reference's Vec<Mat> indexed by s, dc.hpp:208-215),
@@ -385,6 +400,11 @@ int rslf_downsample_epis_f32(rslf_ctx* ctx, const float* d_in_vsuc, int V, int S
  * exact in 8 fractional bits) rounded half up once -- the result of both 8U paths of OpenCV 3.4 (<= 3.4.0 8-bit
  * fixed-point filter, >= 3.4.1 ufixedpoint16); resize = INTER_AREA's (sum + 2) >> 2. */
 int rslf_downsample_epis_u8(rslf_ctx* ctx, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc);
+/* The same for CV_16U light fields (ushort levels 0..65535 as float32), as OpenCV 3.4 runs it without IPP: GaussianBlur =
+ * sepFilter2D with the float kernel and a float buffer -- the row pass of rslf_downsample_epis_f32 (exact on ushort), its
+ * column pass (centre tap, then k[j] * (S[y+j] + S[y-j])) rounded by saturate_cast<ushort> (cvRound, ties to even,
+ * clamped to [0, 65535]); resize = INTER_AREA's (sum + 2) >> 2, cvRound((float)sum / count) at an odd border. */
+int rslf_downsample_epis_u16(rslf_ctx* ctx, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc);
 /* max over a device buffer: the per-level epi_scale_factor of Depth2DComputer's constructor
  * (include/rslf_depth_computation.hpp:671-690).  Synchronises. */
 int rslf_device_max_f32(rslf_ctx* ctx, const float* d_values, size_t n, float* h_max);   /* returns the value: waits */
@@ -414,6 +434,12 @@ int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_epis, int i
                                  size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                  const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                  float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats);
+/* The same from CV_16U EPIs: the pyramid keeps ushort levels (rslf_downsample_epis_u16) and every level is normalised by
+ * its own max, or by epi_scale_factor when that is >= 0 (dc.hpp:671-705). */
+int rslf_fine_to_coarse_run_host_u16(rslf_ctx* ctx, const uint16_t* const* h_epis, int V, int S, int U, int C,
+                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                     float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats);
 
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit
@@ -428,6 +454,11 @@ int rslf_multi_depth2d_run_u8(rslf_multi* m, const uint8_t* const* h_epis, size_
                               float dmin, float dmax, int dim_d, const rslf_params* p, float* h_Ce_svu,
                               uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
                               uint8_t* h_scan_mask_svu, rslf_stats* stats);
+/* CV_16U EPIs: arguments as rslf_multi_depth2d_run_f32, bit-identical to it on the same values. */
+int rslf_multi_depth2d_run_u16(rslf_multi* m, const uint16_t* const* h_epis, size_t row_stride_bytes, int V, int S, int U, int C,
+                               float epi_scale_factor, float dmin, float dmax, int dim_d, const rslf_params* p,
+                               float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                               float* h_rbar_svu, uint8_t* h_scan_mask_svu, rslf_stats* stats, float* scale_used);
 
 /* FineToCoarse<T>'s constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) over the context's devices:
  * every level's 2-D sweep runs sharded as in rslf_multi_depth2d_run_* (with the level's tightened per-pixel ranges); the
@@ -438,6 +469,10 @@ int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* const* h_epis,
                                        size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                        const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                        float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats);
+int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint16_t* const* h_epis, int V, int S, int U, int C,
+                                           size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                           const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                           float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats);
 
 /* ---- measurement ------------------------------------------------------ */
 /* Duration in milliseconds of the last scan-kernel launch (K2) of this

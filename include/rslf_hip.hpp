@@ -116,6 +116,83 @@ struct Depth1DParameters {
     }
 };
 
+// The element type of a host light field: the cv::Mat depths the reference's constructors take (CV_32F, CV_8U and, as every
+// depth other than 8U, CV_16U: dc.hpp:269-288, :442-475, :671-705).  U8 is normalised by 1/255; F32 and U16 by the max over
+// all values, or by epi_scale_factor when it is >= 0 -- a U16 field gives the slab of the same values given as float.
+enum class InputType { F32, U8, U16 };
+
+namespace detail {
+
+// the constructor's copy (dc.hpp:425-477) into vol; returns the epi_scale_factor used
+inline float upload_epis(rslf_volume* vol, InputType type, const void* const* epis, size_t row_stride_bytes, float epi_scale_factor)
+{
+    float used = 255.f;
+    switch (type) {
+    case InputType::U8:
+        check(rslf_volume_upload_epis_u8(vol, (const uint8_t* const*)epis, row_stride_bytes), "rslf_volume_upload_epis_u8");
+        break;
+    case InputType::U16:
+        check(rslf_volume_upload_epis_u16(vol, (const uint16_t* const*)epis, row_stride_bytes, epi_scale_factor, &used),
+              "rslf_volume_upload_epis_u16");
+        break;
+    default:
+        check(rslf_volume_upload_epis_f32(vol, (const float* const*)epis, row_stride_bytes, epi_scale_factor, &used),
+              "rslf_volume_upload_epis_f32");
+    }
+    return used;
+}
+
+#ifdef RSLFX_HAVE_OPENCV
+// The data pointers of a Vec<Mat> of EPIs and their element type; one shape, one type, `channels` channels.  CV_16U is
+// accepted where the OpenCV in use defines it (a macro in every OpenCV release).
+inline std::vector<const void*> mat_pointers(const std::vector<cv::Mat>& epis, int channels, InputType& type, const char* who)
+{
+    if (epis.empty())
+        throw std::invalid_argument(std::string(who) + ": no EPIs");
+    if (epis[0].channels() != channels)
+        throw std::invalid_argument(std::string(who) + ": channel count does not match the instantiation");
+    std::vector<const void*> ptrs(epis.size());
+    for (size_t v = 0; v < epis.size(); v++) {
+        if (epis[v].rows != epis[0].rows || epis[v].cols != epis[0].cols || epis[v].type() != epis[0].type())
+            throw std::invalid_argument(std::string(who) + ": EPIs differ in size or type");
+        ptrs[v] = epis[v].data;
+    }
+    const int depth = epis[0].depth();
+    if (depth == CV_8U)
+        type = InputType::U8;
+    else if (depth == CV_32F)
+        type = InputType::F32;
+#ifdef CV_16U
+    else if (depth == CV_16U)
+        type = InputType::U16;
+    else
+        throw std::invalid_argument(std::string(who) + ": EPIs must be CV_8U, CV_16U or CV_32F");
+#else
+    else
+        throw std::invalid_argument(std::string(who) + ": EPIs must be CV_8U or CV_32F");
+#endif
+    return ptrs;
+}
+
+// A Vec<Mat> as the pointer constructors take it
+struct MatInput {
+    std::vector<const void*> ptrs;
+    InputType type;
+    int V, S, U;
+    size_t stride;
+    MatInput(const std::vector<cv::Mat>& epis, int channels, const char* who) : type(InputType::F32)
+    {
+        ptrs = mat_pointers(epis, channels, type, who);
+        V = (int)epis.size();
+        S = epis[0].rows;
+        U = epis[0].cols;
+        stride = epis[0].step[0];
+    }
+};
+#endif
+
+}  // namespace detail
+
 // RAII handles
 class Context {
 public:
@@ -172,7 +249,16 @@ public:
                          float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default())
         : ctx_(&ctx), multi_(nullptr), vol_(nullptr), m_parameters(parameters)
     {
-        init(epis, is_u8, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d, s_hat, epi_scale_factor);
+        init(epis, is_u8 ? InputType::U8 : InputType::F32, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d, s_hat,
+             epi_scale_factor);
+    }
+    // The same with the element type named (InputType::U16: CV_16U EPIs, normalised like float).
+    Depth1DComputer_pile(Context& ctx, const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u,
+                         size_t row_stride_bytes, float dmin, float dmax, int dim_d, int s_hat = -1,
+                         float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default())
+        : ctx_(&ctx), multi_(nullptr), vol_(nullptr), m_parameters(parameters)
+    {
+        init(epis, type, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d, s_hat, epi_scale_factor);
     }
 
     // The same on a MultiContext: the scanlines are shared out over its devices and the host copies overlap the kernels.
@@ -183,7 +269,15 @@ public:
                          float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default())
         : ctx_(nullptr), multi_(&multi), vol_(nullptr), m_parameters(parameters)
     {
-        init_multi(epis, is_u8, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d, s_hat, epi_scale_factor);
+        init_multi(epis, is_u8 ? InputType::U8 : InputType::F32, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d, s_hat,
+                   epi_scale_factor);
+    }
+    Depth1DComputer_pile(MultiContext& multi, const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u,
+                         size_t row_stride_bytes, float dmin, float dmax, int dim_d, int s_hat = -1,
+                         float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default())
+        : ctx_(nullptr), multi_(&multi), vol_(nullptr), m_parameters(parameters)
+    {
+        init_multi(epis, type, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d, s_hat, epi_scale_factor);
     }
 
 #ifdef RSLFX_HAVE_OPENCV
@@ -191,9 +285,9 @@ public:
                          float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default())
         : ctx_(nullptr), multi_(&multi), vol_(nullptr), m_parameters(parameters)
     {
-        bool is_u8 = false;
-        const std::vector<const void*> ptrs = mat_pointers(epis, is_u8);
-        init_multi(ptrs.data(), is_u8, (int)epis.size(), epis[0].rows, epis[0].cols, epis[0].step[0], dmin, dmax, dim_d, s_hat,
+        InputType type = InputType::F32;
+        const std::vector<const void*> ptrs = mat_pointers(epis, type);
+        init_multi(ptrs.data(), type, (int)epis.size(), epis[0].rows, epis[0].cols, epis[0].step[0], dmin, dmax, dim_d, s_hat,
                    epi_scale_factor);
     }
     // Exactly the reference's signature: Vec<Mat> in (dc.hpp:97-106).
@@ -201,26 +295,23 @@ public:
                          float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default())
         : ctx_(&ctx), multi_(nullptr), vol_(nullptr), m_parameters(parameters)
     {
-        bool is_u8 = false;
-        const std::vector<const void*> ptrs = mat_pointers(epis, is_u8);
-        init(ptrs.data(), is_u8, (int)epis.size(), epis[0].rows, epis[0].cols, epis[0].step[0], dmin, dmax, dim_d, s_hat,
+        InputType type = InputType::F32;
+        const std::vector<const void*> ptrs = mat_pointers(epis, type);
+        init(ptrs.data(), type, (int)epis.size(), epis[0].rows, epis[0].cols, epis[0].step[0], dmin, dmax, dim_d, s_hat,
              epi_scale_factor);
     }
+    static std::vector<const void*> mat_pointers(const std::vector<cv::Mat>& epis, InputType& type)
+    {
+        return detail::mat_pointers(epis, CHANNELS, type, "Depth1DComputer_pile");
+    }
+    // (the two-type form: CV_8U or CV_32F)
     static std::vector<const void*> mat_pointers(const std::vector<cv::Mat>& epis, bool& is_u8)
     {
-        if (epis.empty())
-            throw std::invalid_argument("Depth1DComputer_pile: no EPIs");
-        if (epis[0].channels() != CHANNELS)
-            throw std::invalid_argument("Depth1DComputer_pile: channel count does not match the instantiation");
-        std::vector<const void*> ptrs(epis.size());
-        for (size_t v = 0; v < epis.size(); v++) {
-            if (epis[v].rows != epis[0].rows || epis[v].cols != epis[0].cols || epis[v].type() != epis[0].type())
-                throw std::invalid_argument("Depth1DComputer_pile: EPIs differ in size or type");
-            ptrs[v] = epis[v].data;
-        }
-        is_u8 = epis[0].depth() == CV_8U;
-        if (!is_u8 && epis[0].depth() != CV_32F)
-            throw std::invalid_argument("Depth1DComputer_pile: EPIs must be CV_8U or CV_32F");
+        InputType type = InputType::F32;
+        std::vector<const void*> ptrs = mat_pointers(epis, type);
+        if (type == InputType::U16)
+            throw std::invalid_argument("Depth1DComputer_pile: CV_16U EPIs need the InputType form of mat_pointers");
+        is_u8 = type == InputType::U8;
         return ptrs;
     }
     cv::Mat get_edge_confidence() const { return cv::Mat(dim_v_, dim_u_, CV_32FC1, (void*)m_edge_confidence_v_u.data()).clone(); }
@@ -248,13 +339,20 @@ public:
         m_score_v_u.assign(n, 0.f);
         const rslf_params p = m_parameters.to_c();
         if (multi_) {
-            if (is_u8_)
+            if (type_ == InputType::U8)
                 check(rslf_multi_depth1d_pile_u8(multi_->get(), (const uint8_t* const*)epis_.data(), row_stride_bytes_, dim_v_, dim_s_,
                                                  dim_u_, CHANNELS, m_dmin, m_dmax, m_dim_d, m_s_hat, &p, m_edge_confidence_v_u.data(),
                                                  m_edge_confidence_mask_v_u.data(), m_disp_confidence_v_u.data(),
                                                  m_best_depth_v_u.data(), m_rbar_v_u.data(), m_depth_idx_v_u.data(),
                                                  m_score_v_u.data(), nullptr, &stats),
                       "rslf_multi_depth1d_pile_u8");
+            else if (type_ == InputType::U16)
+                check(rslf_multi_depth1d_pile_u16(multi_->get(), (const uint16_t* const*)epis_.data(), row_stride_bytes_, dim_v_, dim_s_,
+                                                  dim_u_, CHANNELS, epi_scale_arg_, m_dmin, m_dmax, m_dim_d, m_s_hat, &p,
+                                                  m_edge_confidence_v_u.data(), m_edge_confidence_mask_v_u.data(),
+                                                  m_disp_confidence_v_u.data(), m_best_depth_v_u.data(), m_rbar_v_u.data(),
+                                                  m_depth_idx_v_u.data(), m_score_v_u.data(), nullptr, &stats, &scale_used_),
+                      "rslf_multi_depth1d_pile_u16");
             else
                 check(rslf_multi_depth1d_pile_f32(multi_->get(), (const float* const*)epis_.data(), row_stride_bytes_, dim_v_, dim_s_,
                                                   dim_u_, CHANNELS, epi_scale_arg_, m_dmin, m_dmax, m_dim_d, m_s_hat, &p,
@@ -287,7 +385,7 @@ public:
     rslf_stats stats;
 
 private:
-    void init(const void* const* epis, bool is_u8, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes, float dmin,
+    void init(const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes, float dmin,
               float dmax, int dim_d, int s_hat, float epi_scale_factor)
     {
         dim_v_ = dim_v;
@@ -300,14 +398,10 @@ private:
         m_s_hat = (s_hat < 0 || s_hat > dim_s - 1) ? (int)std::floor((0.0 + dim_s) / 2) : s_hat;
         stats = rslf_stats();
         check(rslf_volume_create(ctx_->get(), dim_v, dim_s, dim_u, CHANNELS, &vol_), "rslf_volume_create");
-        scale_used_ = 255.f;
-        if (is_u8)
-            check(rslf_volume_upload_epis_u8(vol_, (const uint8_t* const*)epis, row_stride_bytes), "rslf_volume_upload_epis_u8");
-        else
-            check(rslf_volume_upload_epis_f32(vol_, (const float* const*)epis, row_stride_bytes, epi_scale_factor, &scale_used_),
-                  "rslf_volume_upload_epis_f32");
+        type_ = type;
+        scale_used_ = detail::upload_epis(vol_, type, epis, row_stride_bytes, epi_scale_factor);
     }
-    void init_multi(const void* const* epis, bool is_u8, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes, float dmin,
+    void init_multi(const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes, float dmin,
                     float dmax, int dim_d, int s_hat, float epi_scale_factor)
     {
         dim_v_ = dim_v;
@@ -319,7 +413,7 @@ private:
         m_s_hat = (s_hat < 0 || s_hat > dim_s - 1) ? (int)std::floor((0.0 + dim_s) / 2) : s_hat;   // dc.hpp:490-498
         stats = rslf_stats();
         epis_.assign(epis, epis + dim_v);
-        is_u8_ = is_u8;
+        type_ = type;
         row_stride_bytes_ = row_stride_bytes;
         epi_scale_arg_ = epi_scale_factor;
         scale_used_ = 255.f;
@@ -328,7 +422,7 @@ private:
     Context* ctx_;
     MultiContext* multi_;
     std::vector<const void*> epis_;   // multi path: the caller's buffers, read by run()
-    bool is_u8_;
+    InputType type_;
     size_t row_stride_bytes_;
     float epi_scale_arg_;
     rslf_volume* vol_;
@@ -348,28 +442,51 @@ public:
     Depth2DComputer(Context& ctx, const void* const* epis, bool is_u8, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes,
                     float dmin, float dmax, int dim_d, float epi_scale_factor = -1,
                     const Depth1DParameters& parameters = Depth1DParameters::get_default())
-        : ctx_(&ctx), multi_(nullptr), vol_(nullptr), is_u8_(is_u8), stride_(row_stride_bytes), scale_(epi_scale_factor), dim_v_(dim_v),
+        : Depth2DComputer(ctx, epis, is_u8 ? InputType::U8 : InputType::F32, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d,
+                          epi_scale_factor, parameters)
+    {
+    }
+    Depth2DComputer(Context& ctx, const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes,
+                    float dmin, float dmax, int dim_d, float epi_scale_factor = -1,
+                    const Depth1DParameters& parameters = Depth1DParameters::get_default())
+        : ctx_(&ctx), multi_(nullptr), vol_(nullptr), type_(type), stride_(row_stride_bytes), scale_(epi_scale_factor), dim_v_(dim_v),
           dim_s_(dim_s), dim_u_(dim_u), m_dim_d(dim_d), m_dmin(dmin), m_dmax(dmax), m_parameters(parameters)
     {
         stats = rslf_stats();
         check(rslf_volume_create(ctx_->get(), dim_v, dim_s, dim_u, CHANNELS, &vol_), "rslf_volume_create");
-        if (is_u8)
-            check(rslf_volume_upload_epis_u8(vol_, (const uint8_t* const*)epis, row_stride_bytes), "rslf_volume_upload_epis_u8");
-        else
-            check(rslf_volume_upload_epis_f32(vol_, (const float* const*)epis, row_stride_bytes, epi_scale_factor, nullptr),
-                  "rslf_volume_upload_epis_f32");
+        detail::upload_epis(vol_, type, epis, row_stride_bytes, epi_scale_factor);
     }
     // The same on a MultiContext: the sweep is cut into one block of scanlines per device, the neighbours' boundary rows
     // exchanged by peer copy on every visit (rslf_multi_depth2d_run_*).  The EPIs are read by run(): they must outlive it.
     Depth2DComputer(MultiContext& multi, const void* const* epis, bool is_u8, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes,
                     float dmin, float dmax, int dim_d, float epi_scale_factor = -1,
                     const Depth1DParameters& parameters = Depth1DParameters::get_default())
-        : ctx_(nullptr), multi_(&multi), vol_(nullptr), epis_(epis, epis + dim_v), is_u8_(is_u8), stride_(row_stride_bytes),
+        : Depth2DComputer(multi, epis, is_u8 ? InputType::U8 : InputType::F32, dim_v, dim_s, dim_u, row_stride_bytes, dmin, dmax, dim_d,
+                          epi_scale_factor, parameters)
+    {
+    }
+    Depth2DComputer(MultiContext& multi, const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u,
+                    size_t row_stride_bytes, float dmin, float dmax, int dim_d, float epi_scale_factor = -1,
+                    const Depth1DParameters& parameters = Depth1DParameters::get_default())
+        : ctx_(nullptr), multi_(&multi), vol_(nullptr), epis_(epis, epis + dim_v), type_(type), stride_(row_stride_bytes),
           scale_(epi_scale_factor), dim_v_(dim_v), dim_s_(dim_s), dim_u_(dim_u), m_dim_d(dim_d), m_dmin(dmin), m_dmax(dmax),
           m_parameters(parameters)
     {
         stats = rslf_stats();
     }
+#ifdef RSLFX_HAVE_OPENCV
+    // The reference's signature: Vec<Mat> in (dc.hpp:183-190), CV_8U, CV_16U or CV_32F.
+    Depth2DComputer(Context& ctx, const std::vector<cv::Mat>& epis, float dmin, float dmax, int dim_d, float epi_scale_factor = -1,
+                    const Depth1DParameters& parameters = Depth1DParameters::get_default())
+        : Depth2DComputer(ctx, detail::MatInput(epis, CHANNELS, "Depth2DComputer"), dmin, dmax, dim_d, epi_scale_factor, parameters)
+    {
+    }
+    Depth2DComputer(MultiContext& multi, const std::vector<cv::Mat>& epis, float dmin, float dmax, int dim_d,
+                    float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default())
+        : Depth2DComputer(multi, detail::MatInput(epis, CHANNELS, "Depth2DComputer"), dmin, dmax, dim_d, epi_scale_factor, parameters)
+    {
+    }
+#endif
     ~Depth2DComputer() { rslf_volume_destroy(vol_); }
     Depth2DComputer(const Depth2DComputer&) = delete;
     Depth2DComputer& operator=(const Depth2DComputer&) = delete;
@@ -384,12 +501,18 @@ public:
         m_rbar_s_v_u.assign(n * CHANNELS, 0.f);
         const rslf_params p = m_parameters.to_c();
         if (multi_) {
-            if (is_u8_)
+            if (type_ == InputType::U8)
                 check(rslf_multi_depth2d_run_u8(multi_->get(), (const uint8_t* const*)epis_.data(), stride_, dim_v_, dim_s_, dim_u_, CHANNELS,
                                                 m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
                                                 m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
                                                 m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), nullptr, &stats),
                       "rslf_multi_depth2d_run_u8");
+            else if (type_ == InputType::U16)
+                check(rslf_multi_depth2d_run_u16(multi_->get(), (const uint16_t* const*)epis_.data(), stride_, dim_v_, dim_s_, dim_u_,
+                                                 CHANNELS, scale_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
+                                                 m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
+                                                 m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), nullptr, &stats, nullptr),
+                      "rslf_multi_depth2d_run_u16");
             else
                 check(rslf_multi_depth2d_run_f32(multi_->get(), (const float* const*)epis_.data(), stride_, dim_v_, dim_s_, dim_u_, CHANNELS,
                                                  scale_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
@@ -413,11 +536,19 @@ public:
     rslf_stats stats;
 
 private:
+#ifdef RSLFX_HAVE_OPENCV
+    template <typename Ctx>
+    Depth2DComputer(Ctx& ctx, const detail::MatInput& in, float dmin, float dmax, int dim_d, float epi_scale_factor,
+                    const Depth1DParameters& parameters)
+        : Depth2DComputer(ctx, in.ptrs.data(), in.type, in.V, in.S, in.U, in.stride, dmin, dmax, dim_d, epi_scale_factor, parameters)
+    {
+    }
+#endif
     Context* ctx_;
     MultiContext* multi_;
     rslf_volume* vol_;
     std::vector<const void*> epis_;
-    bool is_u8_;
+    InputType type_;
     size_t stride_;
     float scale_;
     int dim_v_, dim_s_, dim_u_, m_dim_d;
@@ -434,37 +565,83 @@ public:
                  float d_min, float d_max, int dim_d, float epi_scale_factor = -1,
                  const Depth1DParameters& parameters = Depth1DParameters::get_default(), int max_pyr_depth = -1,
                  bool accept_all_last_scale = true)
-        : ctx_(&ctx), multi_(nullptr), epis_(epis, epis + dim_v), is_u8_(is_u8), dim_v_(dim_v), dim_s_(dim_s), dim_u_(dim_u),
-          stride_(row_stride_bytes), d_min_(d_min), d_max_(d_max), dim_d_(dim_d), scale_(epi_scale_factor),
-          m_parameters(parameters), max_pyr_depth_(max_pyr_depth), accept_all_(accept_all_last_scale), n_levels_(0)
+        : FineToCoarse(&ctx, nullptr, epis, is_u8 ? InputType::U8 : InputType::F32, dim_v, dim_s, dim_u, row_stride_bytes, d_min, d_max,
+                       dim_d, epi_scale_factor, parameters, max_pyr_depth, accept_all_last_scale)
     {
-        stats = rslf_stats();
+    }
+    // The same with the element type named: InputType::U16 keeps ushort arithmetic through the pyramid, as the reference's
+    // CV_16U Mats do (rslf_fine_to_coarse_run_host_u16).
+    FineToCoarse(Context& ctx, const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes,
+                 float d_min, float d_max, int dim_d, float epi_scale_factor = -1,
+                 const Depth1DParameters& parameters = Depth1DParameters::get_default(), int max_pyr_depth = -1,
+                 bool accept_all_last_scale = true)
+        : FineToCoarse(&ctx, nullptr, epis, type, dim_v, dim_s, dim_u, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor,
+                       parameters, max_pyr_depth, accept_all_last_scale)
+    {
     }
     // The same over a MultiContext's devices: every level's sweep sharded by scanline (rslf_multi_fine_to_coarse_run_host).
     FineToCoarse(MultiContext& multi, const void* const* epis, bool is_u8, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes,
                  float d_min, float d_max, int dim_d, float epi_scale_factor = -1,
                  const Depth1DParameters& parameters = Depth1DParameters::get_default(), int max_pyr_depth = -1,
                  bool accept_all_last_scale = true)
-        : ctx_(nullptr), multi_(&multi), epis_(epis, epis + dim_v), is_u8_(is_u8), dim_v_(dim_v), dim_s_(dim_s), dim_u_(dim_u),
-          stride_(row_stride_bytes), d_min_(d_min), d_max_(d_max), dim_d_(dim_d), scale_(epi_scale_factor),
-          m_parameters(parameters), max_pyr_depth_(max_pyr_depth), accept_all_(accept_all_last_scale), n_levels_(0)
+        : FineToCoarse(nullptr, &multi, epis, is_u8 ? InputType::U8 : InputType::F32, dim_v, dim_s, dim_u, row_stride_bytes, d_min,
+                       d_max, dim_d, epi_scale_factor, parameters, max_pyr_depth, accept_all_last_scale)
     {
-        stats = rslf_stats();
     }
+    FineToCoarse(MultiContext& multi, const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u, size_t row_stride_bytes,
+                 float d_min, float d_max, int dim_d, float epi_scale_factor = -1,
+                 const Depth1DParameters& parameters = Depth1DParameters::get_default(), int max_pyr_depth = -1,
+                 bool accept_all_last_scale = true)
+        : FineToCoarse(nullptr, &multi, epis, type, dim_v, dim_s, dim_u, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor,
+                       parameters, max_pyr_depth, accept_all_last_scale)
+    {
+    }
+#ifdef RSLFX_HAVE_OPENCV
+    // The reference's signature: Vec<Mat> in (rslf_fine_to_coarse.hpp:103-110), CV_8U, CV_16U or CV_32F.
+    FineToCoarse(Context& ctx, const std::vector<cv::Mat>& epis, float d_min, float d_max, int dim_d, float epi_scale_factor = -1,
+                 const Depth1DParameters& parameters = Depth1DParameters::get_default(), int max_pyr_depth = -1,
+                 bool accept_all_last_scale = true)
+        : FineToCoarse(&ctx, nullptr, detail::MatInput(epis, CHANNELS, "FineToCoarse"), d_min, d_max, dim_d, epi_scale_factor,
+                       parameters, max_pyr_depth, accept_all_last_scale)
+    {
+    }
+    FineToCoarse(MultiContext& multi, const std::vector<cv::Mat>& epis, float d_min, float d_max, int dim_d,
+                 float epi_scale_factor = -1, const Depth1DParameters& parameters = Depth1DParameters::get_default(),
+                 int max_pyr_depth = -1, bool accept_all_last_scale = true)
+        : FineToCoarse(nullptr, &multi, detail::MatInput(epis, CHANNELS, "FineToCoarse"), d_min, d_max, dim_d, epi_scale_factor,
+                       parameters, max_pyr_depth, accept_all_last_scale)
+    {
+    }
+#endif
     void run()
     {
         const size_t n = (size_t)dim_s_ * dim_v_ * dim_u_;
         out_map_s_v_u_.assign(n, 0.f);
         out_validity_s_v_u_.assign(n, 0);
         const rslf_params p = m_parameters.to_c();
+        if (type_ == InputType::U16) {   // ushort arithmetic through the pyramid
+            const uint16_t* const* e = (const uint16_t* const*)epis_.data();
+            if (multi_)
+                check(rslf_multi_fine_to_coarse_run_host_u16(multi_->get(), e, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+                                                             dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
+                                                             out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats),
+                      "rslf_multi_fine_to_coarse_run_host_u16");
+            else
+                check(rslf_fine_to_coarse_run_host_u16(ctx_->get(), e, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
+                                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
+                                                       out_validity_s_v_u_.data(), &n_levels_, &stats),
+                      "rslf_fine_to_coarse_run_host_u16");
+            return;
+        }
+        const int is_u8 = type_ == InputType::U8 ? 1 : 0;
         if (multi_) {
-            check(rslf_multi_fine_to_coarse_run_host(multi_->get(), epis_.data(), is_u8_ ? 1 : 0, dim_v_, dim_s_, dim_u_, CHANNELS, stride_,
+            check(rslf_multi_fine_to_coarse_run_host(multi_->get(), epis_.data(), is_u8, dim_v_, dim_s_, dim_u_, CHANNELS, stride_,
                                                      d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
                                                      out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats),
                   "rslf_multi_fine_to_coarse_run_host");
             return;
         }
-        check(rslf_fine_to_coarse_run_host(ctx_->get(), epis_.data(), is_u8_ ? 1 : 0, dim_v_, dim_s_, dim_u_, CHANNELS, stride_,
+        check(rslf_fine_to_coarse_run_host(ctx_->get(), epis_.data(), is_u8, dim_v_, dim_s_, dim_u_, CHANNELS, stride_,
                                            d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
                                            out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats),
               "rslf_fine_to_coarse_run_host");
@@ -478,10 +655,27 @@ public:
     rslf_stats stats;
 
 private:
+    FineToCoarse(Context* ctx, MultiContext* multi, const void* const* epis, InputType type, int dim_v, int dim_s, int dim_u,
+                 size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor, const Depth1DParameters& parameters,
+                 int max_pyr_depth, bool accept_all_last_scale)
+        : ctx_(ctx), multi_(multi), epis_(epis, epis + dim_v), type_(type), dim_v_(dim_v), dim_s_(dim_s), dim_u_(dim_u),
+          stride_(row_stride_bytes), d_min_(d_min), d_max_(d_max), dim_d_(dim_d), scale_(epi_scale_factor),
+          m_parameters(parameters), max_pyr_depth_(max_pyr_depth), accept_all_(accept_all_last_scale), n_levels_(0)
+    {
+        stats = rslf_stats();
+    }
+#ifdef RSLFX_HAVE_OPENCV
+    FineToCoarse(Context* ctx, MultiContext* multi, const detail::MatInput& in, float d_min, float d_max, int dim_d,
+                 float epi_scale_factor, const Depth1DParameters& parameters, int max_pyr_depth, bool accept_all_last_scale)
+        : FineToCoarse(ctx, multi, in.ptrs.data(), in.type, in.V, in.S, in.U, in.stride, d_min, d_max, dim_d, epi_scale_factor,
+                       parameters, max_pyr_depth, accept_all_last_scale)
+    {
+    }
+#endif
     Context* ctx_;
     MultiContext* multi_;
     std::vector<const void*> epis_;
-    bool is_u8_;
+    InputType type_;
     int dim_v_, dim_s_, dim_u_;
     size_t stride_;
     float d_min_, d_max_;

@@ -31,6 +31,10 @@ SYMBOLS = [
     "rslf_depth_epi_scan", "rslf_depth1d_run",
     "rslf_f2c_level_dims", "rslf_downsample_epis_f32", "rslf_downsample_epis_u8", "rslf_device_max_f32", "rslf_f2c_tighten_bounds", "rslf_f2c_fuse",
     "rslf_depth2d_run_host", "rslf_fine_to_coarse_run_host", "rslf_kernel_columns_pile", "rslf_volume_upload_images_xf_f32", "rslf_volume_upload_images_xf_u8",
+    # CV_16U light fields
+    "rslf_volume_upload_epis_u16", "rslf_volume_upload_images_u16", "rslf_volume_upload_images_xf_u16", "rslf_downsample_epis_u16",
+    "rslf_multi_depth1d_pile_u16", "rslf_multi_depth2d_run_u16", "rslf_fine_to_coarse_run_host_u16",
+    "rslf_multi_fine_to_coarse_run_host_u16",
 ]
 
 
@@ -132,6 +136,9 @@ def lib():
     L.rslf_volume_upload_images_u8.argtypes = [vp, C.POINTER(vp), C.c_size_t]
     L.rslf_volume_upload_images_xf_f32.argtypes = [vp, C.POINTER(vp), C.c_size_t, cf, C.POINTER(cf), ci, ci]
     L.rslf_volume_upload_images_xf_u8.argtypes = [vp, C.POINTER(vp), C.c_size_t, ci, ci]
+    L.rslf_volume_upload_epis_u16.argtypes = L.rslf_volume_upload_epis_f32.argtypes
+    L.rslf_volume_upload_images_u16.argtypes = L.rslf_volume_upload_images_f32.argtypes
+    L.rslf_volume_upload_images_xf_u16.argtypes = L.rslf_volume_upload_images_xf_f32.argtypes
     L.rslf_volume_pack_device_f32.argtypes = [vp, vp, cf, C.POINTER(cf)]
     L.rslf_edge_confidence_pile.argtypes = [vp, vp, ci, C.POINTER(RslfParams), vp, vp]
     L.rslf_depth_epi_pile.argtypes = [vp, vp, vp, vp, cf, cf, ci, ci, vp, vp, vp, vp, vp, C.POINTER(RslfParams),
@@ -164,17 +171,23 @@ def lib():
                                              vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RslfStats)]
     L.rslf_multi_depth2d_run_f32.argtypes = [vp, C.POINTER(vp), C.c_size_t, ci, ci, ci, ci, cf, cf, cf, ci, C.POINTER(RslfParams),
                                              vp, vp, vp, vp, vp, vp, C.POINTER(RslfStats), C.POINTER(cf)]
+    L.rslf_multi_depth1d_pile_u16.argtypes = L.rslf_multi_depth1d_pile_f32.argtypes
+    L.rslf_multi_depth2d_run_u16.argtypes = L.rslf_multi_depth2d_run_f32.argtypes
     L.rslf_multi_depth2d_run_u8.argtypes = [vp, C.POINTER(vp), C.c_size_t, ci, ci, ci, ci, cf, cf, ci, C.POINTER(RslfParams),
                                             vp, vp, vp, vp, vp, vp, C.POINTER(RslfStats)]
     L.rslf_multi_fine_to_coarse_run_host.argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.c_size_t, cf, cf, ci, cf, C.POINTER(RslfParams),
                                                      ci, ci, vp, vp, C.POINTER(ci), C.POINTER(RslfStats)]
+    L.rslf_multi_fine_to_coarse_run_host_u16.argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.c_size_t, cf, cf, ci, cf,
+                                                         C.POINTER(RslfParams), ci, ci, vp, vp, C.POINTER(ci), C.POINTER(RslfStats)]
     L.rslf_kernel_columns_pile.argtypes = [vp, vp, vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, vp]
     L.rslf_depth2d_run_host.argtypes = [vp, vp, cf, cf, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, C.POINTER(RslfStats)]
     L.rslf_fine_to_coarse_run_host.argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.c_size_t, cf, cf, ci, cf, C.POINTER(RslfParams),
                                                ci, ci, vp, vp, C.POINTER(ci), C.POINTER(RslfStats)]
+    L.rslf_fine_to_coarse_run_host_u16.argtypes = L.rslf_multi_fine_to_coarse_run_host_u16.argtypes
     L.rslf_f2c_level_dims.argtypes = [ci, ci, C.POINTER(ci), C.POINTER(ci)]
     L.rslf_downsample_epis_f32.argtypes = [vp, vp, ci, ci, ci, ci, vp]
     L.rslf_downsample_epis_u8.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+    L.rslf_downsample_epis_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp]
     L.rslf_device_max_f32.argtypes = [vp, vp, C.c_size_t, C.POINTER(cf)]
     L.rslf_f2c_tighten_bounds.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, ci, ci]
     L.rslf_f2c_fuse.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), ci, ci, vp, vp]

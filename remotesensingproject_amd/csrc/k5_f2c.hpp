@@ -154,6 +154,43 @@ __global__ __launch_bounds__(256) void k5_gauss_cols_halve_u8(const int* __restr
     out[(((long long)y * S + s) * U2 + x) * C + c] = (float)r;
 }
 
+// ---- the same on CV_16U Mats (ushort levels carried in float arrays) ---------------------------------------
+// OpenCV 3.4 without IPP blurs a 16U Mat with sepFilter2D, the float kernel small_gaussian_tab and a CV_32F buffer:
+// the row pass RowFilter<ushort, float> is k5_gauss_rows (exact on ushort: every product and partial sum fits in 24 bits);
+// the column pass SymmColumnFilter<Cast<float, ushort>> is gauss_col followed by saturate_cast<ushort> = cvRound (ties to
+// even) clamped to [0, 65535].  resize(0.5, INTER_LINEAR) is INTER_AREA's fast path, (S00 + S01 + S10 + S11 + 2) >> 2 in
+// int; at an odd border cvRound((float)sum / count), as on 8U.
+__device__ __forceinline__ int gauss_col_u16(const float* __restrict__ tmp, int y, int s, int x, int c, int V, int S, int U, int C)
+{
+    return (int)fminf(fmaxf(rintf(gauss_col(tmp, y, s, x, c, V, S, U, C)), 0.0f), 65535.0f);
+}
+
+__global__ __launch_bounds__(256) void k5_gauss_cols_halve_u16(const float* __restrict__ tmp, float* __restrict__ out, int V, int S, int U,
+                                                              int C, int V2, int U2)
+{
+    const int xc = blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y, y = blockIdx.z;
+    if (xc >= U2 * C)
+        return;
+    const int x = xc / C, c = xc - x * C;
+    const int y0 = 2 * y, x0 = 2 * x;
+    int r;
+    if (y0 + 1 < V && x0 + 1 < U) {
+        r = (gauss_col_u16(tmp, y0, s, x0, c, V, S, U, C) + gauss_col_u16(tmp, y0, s, x0 + 1, c, V, S, U, C) +
+             gauss_col_u16(tmp, y0 + 1, s, x0, c, V, S, U, C) + gauss_col_u16(tmp, y0 + 1, s, x0 + 1, c, V, S, U, C) + 2) >> 2;
+    } else {
+        int sum = 0, cnt = 0;
+        for (int sy = 0; sy < 2; sy++)
+            for (int sx = 0; sx < 2; sx++)
+                if (y0 + sy < V && x0 + sx < U) {
+                    sum += gauss_col_u16(tmp, y0 + sy, s, x0 + sx, c, V, S, U, C);
+                    cnt++;
+                }
+        r = cnt ? (int)rintf((float)sum / (float)cnt) : 0;   // cvRound: ties to even
+    }
+    out[(((long long)y * S + s) * U2 + x) * C + c] = (float)r;
+}
+
 // max over a dense float buffer (per-level epi_scale_factor, dc.hpp:671-690)
 __global__ __launch_bounds__(256) void k5_max_partial(const float* __restrict__ in, long long n, float* __restrict__ partial)
 {

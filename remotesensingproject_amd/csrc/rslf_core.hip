@@ -583,7 +583,8 @@ static int upload_images_xf(rslf_volume* vol, const SrcT* const* h_imgs, size_t 
 }
 
 // dc.hpp:442-460: epi_scale_factor = max over every value of every EPI
-float rslf::host_max_f32(const float* const* h_ptrs, int n_ptrs, int rows, size_t row_stride_bytes, size_t row_elems, float start)
+template <>
+float rslf::host_max<float>(const float* const* h_ptrs, int n_ptrs, int rows, size_t row_stride_bytes, size_t row_elems, float start)
 {
     float m = start;
     for (int i = 0; i < n_ptrs; i++) {
@@ -596,75 +597,180 @@ float rslf::host_max_f32(const float* const* h_ptrs, int n_ptrs, int rows, size_
     }
     return m;
 }
+// ushort: the max taken in integers (a vectorised pass), then widened -- float(max x) == max float(x), the conversion
+// being exact and monotone
+template <>
+float rslf::host_max<uint16_t>(const uint16_t* const* h_ptrs, int n_ptrs, int rows, size_t row_stride_bytes, size_t row_elems,
+                               float start)
+{
+    uint16_t mx = 0;
+    for (int i = 0; i < n_ptrs; i++) {
+        for (int r = 0; r < rows; r++) {
+            const uint16_t* p = (const uint16_t*)((const char*)h_ptrs[i] + (size_t)r * row_stride_bytes);
+            uint16_t rm = 0;
+            for (size_t k = 0; k < row_elems; k++)
+                rm = p[k] > rm ? p[k] : rm;
+            mx = rm > mx ? rm : mx;
+        }
+    }
+    const bool any = n_ptrs > 0 && rows > 0 && row_elems > 0;
+    return any && (float)mx > start ? (float)mx : start;
+}
 
-extern "C" int rslf_volume_upload_epis_f32(rslf_volume* vol, const float* const* h_epis, size_t row_stride_bytes,
-                                           float epi_scale_factor, float* scale_used) RSLF_API_TRY
+float rslf::resolve_scale_factor(Elem e, const void* const* h_ptrs, int n_ptrs, int rows, size_t row_stride_bytes, size_t row_elems,
+                                 float epi_scale_factor, bool parallel)
+{
+    if (e == Elem::U8)
+        return 255.0f;   // dc.hpp:470
+    if (!(epi_scale_factor < 0))
+        return epi_scale_factor;
+    if (e == Elem::F32)
+        return parallel ? host_max_parallel((const float* const*)h_ptrs, n_ptrs, rows, row_stride_bytes, row_elems, epi_scale_factor)
+                        : host_max((const float* const*)h_ptrs, n_ptrs, rows, row_stride_bytes, row_elems, epi_scale_factor);
+    return parallel ? host_max_parallel((const uint16_t* const*)h_ptrs, n_ptrs, rows, row_stride_bytes, row_elems, epi_scale_factor)
+                    : host_max((const uint16_t* const*)h_ptrs, n_ptrs, rows, row_stride_bytes, row_elems, epi_scale_factor);
+}
+
+int rslf::upload_host_elem(rslf_volume* vol, Elem e, const void* const* h_ptrs, size_t row_stride_bytes, bool image_major, float scale)
+{
+    switch (e) {
+    case Elem::U8:
+        return upload_host<uint8_t>(vol, (const uint8_t* const*)h_ptrs, row_stride_bytes, image_major, scale);
+    case Elem::U16:
+        return upload_host<uint16_t>(vol, (const uint16_t* const*)h_ptrs, row_stride_bytes, image_major, scale);
+    default:
+        return upload_host<float>(vol, (const float* const*)h_ptrs, row_stride_bytes, image_major, scale);
+    }
+}
+
+// The three host uploads for one element type.  n_ptrs pointers of `rows` rows each, of row_elems values: EPIs
+// (V x S), images (S x V), or the images of the transposing form.  The scale rule is resolve_scale_factor's.
+static int upload_epis_elem(rslf_volume* vol, Elem e, const void* const* h_epis, size_t row_stride_bytes, float epi_scale_factor,
+                            float* scale_used)
 {
     if (!vol || !h_epis)
         return fail(RSLF_ERR_INVALID_ARG, "vol/h_epis is NULL");
     const size_t row_elems = (size_t)vol->U * vol->C;
-    const size_t stride = row_stride_bytes ? row_stride_bytes : row_elems * sizeof(float);
-    if (epi_scale_factor < 0)
-        epi_scale_factor = host_max_f32(h_epis, vol->V, vol->S, stride, row_elems, epi_scale_factor);
+    const size_t row_bytes = row_elems * elem_bytes(e);
+    const size_t stride = row_stride_bytes ? row_stride_bytes : row_bytes;
+    if (stride < row_bytes)
+        return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", stride, row_bytes);
+    for (int v = 0; v < vol->V; v++)
+        if (!h_epis[v])
+            return fail(RSLF_ERR_INVALID_ARG, "h_epis[%d] is NULL", v);
+    epi_scale_factor = resolve_scale_factor(e, h_epis, vol->V, vol->S, stride, row_elems, epi_scale_factor, false);
     if (scale_used)
         *scale_used = epi_scale_factor;
-    return upload_host<float>(vol, h_epis, stride, false, scale_of(epi_scale_factor));
+    return upload_host_elem(vol, e, h_epis, stride, false, scale_of(epi_scale_factor));
+}
+
+static int upload_images_elem(rslf_volume* vol, Elem e, const void* const* h_imgs, size_t row_stride_bytes, float epi_scale_factor,
+                              float* scale_used)
+{
+    if (!vol || !h_imgs)
+        return fail(RSLF_ERR_INVALID_ARG, "vol/h_imgs is NULL");
+    const size_t row_elems = (size_t)vol->U * vol->C;
+    const size_t row_bytes = row_elems * elem_bytes(e);
+    const size_t stride = row_stride_bytes ? row_stride_bytes : row_bytes;
+    if (stride < row_bytes)
+        return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", stride, row_bytes);
+    for (int s = 0; s < vol->S; s++)
+        if (!h_imgs[s])
+            return fail(RSLF_ERR_INVALID_ARG, "h_imgs[%d] is NULL", s);
+    epi_scale_factor = resolve_scale_factor(e, h_imgs, vol->S, vol->V, stride, row_elems, epi_scale_factor, false);
+    if (scale_used)
+        *scale_used = epi_scale_factor;
+    return upload_host_elem(vol, e, h_imgs, stride, true, scale_of(epi_scale_factor));
+}
+
+static int upload_images_xf_elem(rslf_volume* vol, Elem e, const void* const* h_imgs, size_t row_stride_bytes, float epi_scale_factor,
+                                 float* scale_used, int transpose, int rotate_180)
+{
+    if (!vol || !h_imgs)
+        return fail(RSLF_ERR_INVALID_ARG, "vol/h_imgs is NULL");
+    const int n_imgs = transpose ? vol->U : vol->S;
+    const size_t row_elems = (size_t)(transpose ? vol->S : vol->U) * vol->C;
+    const size_t row_bytes = row_elems * elem_bytes(e);
+    const size_t stride = row_stride_bytes ? row_stride_bytes : row_bytes;
+    if (stride < row_bytes)
+        return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", stride, row_bytes);
+    for (int i = 0; i < n_imgs; i++)
+        if (!h_imgs[i])
+            return fail(RSLF_ERR_INVALID_ARG, "h_imgs[%d] is NULL", i);
+    epi_scale_factor = resolve_scale_factor(e, h_imgs, n_imgs, vol->V, stride, row_elems, epi_scale_factor, false);
+    if (scale_used)
+        *scale_used = epi_scale_factor;
+    const float scale = scale_of(epi_scale_factor);
+    switch (e) {
+    case Elem::U8:
+        return upload_images_xf<uint8_t>(vol, (const uint8_t* const*)h_imgs, stride, scale, transpose != 0, rotate_180 != 0);
+    case Elem::U16:
+        return upload_images_xf<uint16_t>(vol, (const uint16_t* const*)h_imgs, stride, scale, transpose != 0, rotate_180 != 0);
+    default:
+        return upload_images_xf<float>(vol, (const float* const*)h_imgs, stride, scale, transpose != 0, rotate_180 != 0);
+    }
+}
+
+extern "C" int rslf_volume_upload_epis_f32(rslf_volume* vol, const float* const* h_epis, size_t row_stride_bytes,
+                                           float epi_scale_factor, float* scale_used) RSLF_API_TRY
+{
+    return upload_epis_elem(vol, Elem::F32, (const void* const*)h_epis, row_stride_bytes, epi_scale_factor, scale_used);
 }
 RSLF_API_CATCH
 
 extern "C" int rslf_volume_upload_epis_u8(rslf_volume* vol, const uint8_t* const* h_epis, size_t row_stride_bytes) RSLF_API_TRY
 {
-    if (!vol || !h_epis)
-        return fail(RSLF_ERR_INVALID_ARG, "vol/h_epis is NULL");
-    return upload_host<uint8_t>(vol, h_epis, row_stride_bytes, false, (float)(1.0 / 255.0));   // dc.hpp:470
+    return upload_epis_elem(vol, Elem::U8, (const void* const*)h_epis, row_stride_bytes, -1.0f, nullptr);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_volume_upload_epis_u16(rslf_volume* vol, const uint16_t* const* h_epis, size_t row_stride_bytes,
+                                           float epi_scale_factor, float* scale_used) RSLF_API_TRY
+{
+    return upload_epis_elem(vol, Elem::U16, (const void* const*)h_epis, row_stride_bytes, epi_scale_factor, scale_used);
 }
 RSLF_API_CATCH
 
 extern "C" int rslf_volume_upload_images_f32(rslf_volume* vol, const float* const* h_imgs, size_t row_stride_bytes,
                                              float epi_scale_factor, float* scale_used) RSLF_API_TRY
 {
-    if (!vol || !h_imgs)
-        return fail(RSLF_ERR_INVALID_ARG, "vol/h_imgs is NULL");
-    const size_t row_elems = (size_t)vol->U * vol->C;
-    const size_t stride = row_stride_bytes ? row_stride_bytes : row_elems * sizeof(float);
-    if (epi_scale_factor < 0)
-        epi_scale_factor = host_max_f32(h_imgs, vol->S, vol->V, stride, row_elems, epi_scale_factor);
-    if (scale_used)
-        *scale_used = epi_scale_factor;
-    return upload_host<float>(vol, h_imgs, stride, true, scale_of(epi_scale_factor));
+    return upload_images_elem(vol, Elem::F32, (const void* const*)h_imgs, row_stride_bytes, epi_scale_factor, scale_used);
 }
 RSLF_API_CATCH
 
 extern "C" int rslf_volume_upload_images_u8(rslf_volume* vol, const uint8_t* const* h_imgs, size_t row_stride_bytes) RSLF_API_TRY
 {
-    if (!vol || !h_imgs)
-        return fail(RSLF_ERR_INVALID_ARG, "vol/h_imgs is NULL");
-    return upload_host<uint8_t>(vol, h_imgs, row_stride_bytes, true, (float)(1.0 / 255.0));
+    return upload_images_elem(vol, Elem::U8, (const void* const*)h_imgs, row_stride_bytes, -1.0f, nullptr);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_volume_upload_images_u16(rslf_volume* vol, const uint16_t* const* h_imgs, size_t row_stride_bytes,
+                                             float epi_scale_factor, float* scale_used) RSLF_API_TRY
+{
+    return upload_images_elem(vol, Elem::U16, (const void* const*)h_imgs, row_stride_bytes, epi_scale_factor, scale_used);
 }
 RSLF_API_CATCH
 
 extern "C" int rslf_volume_upload_images_xf_f32(rslf_volume* vol, const float* const* h_imgs, size_t row_stride_bytes,
                                                 float epi_scale_factor, float* scale_used, int transpose, int rotate_180) RSLF_API_TRY
 {
-    if (!vol || !h_imgs)
-        return fail(RSLF_ERR_INVALID_ARG, "vol/h_imgs is NULL");
-    const int n_imgs = transpose ? vol->U : vol->S;
-    const size_t row_elems = (size_t)(transpose ? vol->S : vol->U) * vol->C;
-    const size_t stride = row_stride_bytes ? row_stride_bytes : row_elems * sizeof(float);
-    if (epi_scale_factor < 0)
-        epi_scale_factor = host_max_f32(h_imgs, n_imgs, vol->V, stride, row_elems, epi_scale_factor);
-    if (scale_used)
-        *scale_used = epi_scale_factor;
-    return upload_images_xf<float>(vol, h_imgs, stride, scale_of(epi_scale_factor), transpose != 0, rotate_180 != 0);
+    return upload_images_xf_elem(vol, Elem::F32, (const void* const*)h_imgs, row_stride_bytes, epi_scale_factor, scale_used, transpose,
+                                 rotate_180);
 }
 RSLF_API_CATCH
 
 extern "C" int rslf_volume_upload_images_xf_u8(rslf_volume* vol, const uint8_t* const* h_imgs, size_t row_stride_bytes, int transpose,
                                                int rotate_180) RSLF_API_TRY
 {
-    if (!vol || !h_imgs)
-        return fail(RSLF_ERR_INVALID_ARG, "vol/h_imgs is NULL");
-    return upload_images_xf<uint8_t>(vol, h_imgs, row_stride_bytes, (float)(1.0 / 255.0), transpose != 0, rotate_180 != 0);
+    return upload_images_xf_elem(vol, Elem::U8, (const void* const*)h_imgs, row_stride_bytes, -1.0f, nullptr, transpose, rotate_180);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_volume_upload_images_xf_u16(rslf_volume* vol, const uint16_t* const* h_imgs, size_t row_stride_bytes,
+                                                float epi_scale_factor, float* scale_used, int transpose, int rotate_180) RSLF_API_TRY
+{
+    return upload_images_xf_elem(vol, Elem::U16, (const void* const*)h_imgs, row_stride_bytes, epi_scale_factor, scale_used, transpose,
+                                 rotate_180);
 }
 RSLF_API_CATCH
 
@@ -690,9 +796,11 @@ RSLF_API_CATCH
 
 template int rslf::upload_host<float>(rslf_volume*, const float* const*, size_t, bool, float);
 template int rslf::upload_host<uint8_t>(rslf_volume*, const uint8_t* const*, size_t, bool, float);
+template int rslf::upload_host<uint16_t>(rslf_volume*, const uint16_t* const*, size_t, bool, float);
 
 // dc.hpp:442-460 over all EPIs, by up to eight host threads
-float rslf::host_max_f32_parallel(const float* const* h_epis, int V, int S, size_t stride, size_t row_elems, float start)
+template <typename T>
+float rslf::host_max_parallel(const T* const* h_epis, int V, int S, size_t stride, size_t row_elems, float start)
 {
     const int nt = std::max(1, std::min<int>(8, std::min<int>((int)std::thread::hardware_concurrency(), V / 8)));
     std::vector<float> part((size_t)nt, start);
@@ -702,7 +810,7 @@ float rslf::host_max_f32_parallel(const float* const* h_epis, int V, int S, size
             pool.run([&, t] {
                 int v0, v1;
                 plan::split_range(V, t, nt, &v0, &v1);
-                part[(size_t)t] = host_max_f32(h_epis + v0, v1 - v0, S, stride, row_elems, start);
+                part[(size_t)t] = host_max(h_epis + v0, v1 - v0, S, stride, row_elems, start);
             });
     }
     float m = start;
@@ -710,3 +818,5 @@ float rslf::host_max_f32_parallel(const float* const* h_epis, int V, int S, size
         m = std::max(m, part[(size_t)t]);
     return m;
 }
+template float rslf::host_max_parallel<float>(const float* const*, int, int, size_t, size_t, float);
+template float rslf::host_max_parallel<uint16_t>(const uint16_t* const*, int, int, size_t, size_t, float);

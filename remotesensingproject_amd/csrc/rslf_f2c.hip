@@ -74,6 +74,32 @@ extern "C" int rslf_downsample_epis_u8(rslf_ctx* ctx, const float* d_in_vsuc, in
 }
 RSLF_API_CATCH
 
+extern "C" int rslf_downsample_epis_u16(rslf_ctx* ctx, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc) RSLF_API_TRY
+{
+    if (!ctx || !d_in_vsuc || !d_out_vsuc || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
+        return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    HIP_TRY(hipSetDevice(ctx->device));
+    int V2, U2;
+    rslf_f2c_level_dims(V, U, &V2, &U2);
+    if (V2 < 1 || U2 < 1)
+        return fail(RSLF_ERR_INVALID_ARG, "level too small to halve");
+    void* tmp_p = nullptr;
+    int rc = helper_scratch(ctx, 0, (size_t)V * S * U * C * sizeof(float), &tmp_p);
+    if (rc)
+        return rc;
+    hipStream_t st = ctx->stream;
+    const long long row_blocks = (long long)V * S * ((U * C + 255) / 256);
+    if (row_blocks > (1ll << 31) - 1)
+        return fail(RSLF_ERR_UNSUPPORTED, "volume too large for one downsampling launch");
+    hipLaunchKernelGGL(k5_gauss_rows, dim3((unsigned)row_blocks), dim3(256), 0, st, d_in_vsuc, (float*)tmp_p, (long long)V * S, U, C);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k5_gauss_cols_halve_u16, dim3((U2 * C + 255) / 256, S, V2), dim3(256), 0, st, (const float*)tmp_p, d_out_vsuc,
+                       V, S, U, C, V2, U2);
+    HIP_TRY(hipGetLastError());
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
 extern "C" int rslf_device_max_f32(rslf_ctx* ctx, const float* d_values, size_t n, float* h_max) RSLF_API_TRY
 {
     if (!ctx || !d_values || !h_max || n == 0)
@@ -205,7 +231,8 @@ struct F2cLevel {
     ~F2cLevel() { rslf_volume_destroy(vol); }
 };
 
-__global__ __launch_bounds__(256) void k_u8_to_f32(const uint8_t* __restrict__ in, float* __restrict__ out, long long n)
+template <typename T>
+__global__ __launch_bounds__(256) void k_to_f32(const T* __restrict__ in, float* __restrict__ out, long long n)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         out[i] = (float)in[i];
@@ -224,11 +251,62 @@ __global__ __launch_bounds__(256) void k_valid_mask(const float* __restrict__ Ce
 inline unsigned stream_blocks(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 8192); }
 }  // namespace
 
-int rslf::f2c_u8_to_f32(hipStream_t st, const uint8_t* in, float* out, size_t n)
+int rslf::f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float* d_raw)
 {
-    hipLaunchKernelGGL(k_u8_to_f32, dim3(stream_blocks(n)), dim3(256), 0, st, in, out, (long long)n);
+    hipStream_t st = ctx->stream;
+    const size_t row_bytes = (size_t)U * C * elem_bytes(e);
+    if (row_stride_bytes == 0)
+        row_stride_bytes = row_bytes;
+    if (row_stride_bytes < row_bytes)
+        return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", row_stride_bytes, row_bytes);
+    for (int v = 0; v < V; v++)
+        if (!h_epis[v])
+            return fail(RSLF_ERR_INVALID_ARG, "h_epis[%d] is NULL", v);
+    DevBuf stage;   // integer EPIs go up as they are and are widened on the device
+    void* dst = d_raw;
+    if (e != Elem::F32) {
+        HIP_TRY(stage.alloc((size_t)V * S * row_bytes));
+        dst = stage.p;
+    }
+    for (int v = 0; v < V; v++) {
+        if (row_stride_bytes == row_bytes)   // dense rows: one run of bytes per EPI (upload_host)
+            HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)v * S * row_bytes, h_epis[v], (size_t)S * row_bytes, hipMemcpyHostToDevice, st));
+        else
+            HIP_TRY(hipMemcpy2DAsync((char*)dst + (size_t)v * S * row_bytes, row_bytes, h_epis[v], row_stride_bytes, row_bytes, S,
+                                     hipMemcpyHostToDevice, st));
+    }
+    const size_t n = (size_t)V * S * U * C;
+    if (e == Elem::U8)
+        hipLaunchKernelGGL(k_to_f32<uint8_t>, dim3(stream_blocks(n)), dim3(256), 0, st, (const uint8_t*)stage.p, d_raw, (long long)n);
+    else if (e == Elem::U16)
+        hipLaunchKernelGGL(k_to_f32<uint16_t>, dim3(stream_blocks(n)), dim3(256), 0, st, (const uint16_t*)stage.p, d_raw, (long long)n);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the staging buffer is freed on return)
     return RSLF_OK;
+}
+int rslf::f2c_level_scale(rslf_ctx* ctx, Elem e, const float* d_raw, size_t n, float epi_scale_factor, float* scale)
+{
+    if (e == Elem::U8) {   // dc.hpp:696-699 (uchar)
+        *scale = 255.0f;
+        return RSLF_OK;
+    }
+    *scale = epi_scale_factor;
+    if (*scale < 0)        // dc.hpp:671-690: this level's own max
+        return rslf_device_max_f32(ctx, d_raw, n, scale);
+    return RSLF_OK;
+}
+int rslf::f2c_downsample(rslf_ctx* ctx, Elem e, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc)
+{
+    // integer EPIs go down in their own arithmetic, as the reference's Mats do (fine_to_coarse_core.cpp:22-41)
+    switch (e) {
+    case Elem::U8:
+        return rslf_downsample_epis_u8(ctx, d_in_vsuc, V, S, U, C, d_out_vsuc);
+    case Elem::U16:
+        return rslf_downsample_epis_u16(ctx, d_in_vsuc, V, S, U, C, d_out_vsuc);
+    default:
+        return rslf_downsample_epis_f32(ctx, d_in_vsuc, V, S, U, C, d_out_vsuc);
+    }
 }
 int rslf::f2c_fill_f32(hipStream_t st, float* out, size_t n, float value)
 {
@@ -243,10 +321,10 @@ int rslf::f2c_valid_mask(hipStream_t st, const float* Ce, uint8_t* out, size_t n
     return RSLF_OK;
 }
 
-extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
-                                            size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
-                                            const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
-                                            float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C,
+                                   size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                   const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
+                                   uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats)
 {
     if (!ctx || !h_epis || !h_out_map_svu || !h_out_valid_svu || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
@@ -255,38 +333,13 @@ extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t elem = is_u8 ? 1 : 4;
-    const size_t row_bytes = (size_t)U * C * elem;
-    if (row_stride_bytes == 0)
-        row_stride_bytes = row_bytes;
 
     // the raw (un-normalised) finest level as a dense float volume [V][S][U][C]
     DevBuf raw;
     HIP_TRY(raw.alloc((size_t)V * S * U * C * sizeof(float)));
-    {
-        DevBuf stage;
-        void* dst = raw.p;
-        if (is_u8) {
-            HIP_TRY(stage.alloc((size_t)V * S * row_bytes));
-            dst = stage.p;
-        }
-        for (int v = 0; v < V; v++) {
-            if (!h_epis[v])
-                return fail(RSLF_ERR_INVALID_ARG, "h_epis[%d] is NULL", v);
-            if (row_stride_bytes == row_bytes)   // dense rows: one run of bytes per EPI (upload_host)
-                HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)v * S * row_bytes, h_epis[v], (size_t)S * row_bytes, hipMemcpyHostToDevice, st));
-            else
-                HIP_TRY(hipMemcpy2DAsync((char*)dst + (size_t)v * S * row_bytes, row_bytes, h_epis[v], row_stride_bytes, row_bytes, S,
-                                         hipMemcpyHostToDevice, st));
-        }
-        if (is_u8) {
-            const size_t n = (size_t)V * S * U * C;
-            hipLaunchKernelGGL(k_u8_to_f32, dim3(stream_blocks(n)), dim3(256), 0, st, (const uint8_t*)stage.p, (float*)raw.p,
-                               (long long)n);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, (float*)raw.p);
+    if (rc)
+        return rc;
 
     // constructor: rslf_fine_to_coarse.hpp:103-159 -- the level sizes are plan::f2c_pyramid
     const std::vector<plan::LevelDims> dims = plan::f2c_pyramid(V, U, max_pyr_depth);
@@ -301,15 +354,10 @@ extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_
         lv->U = dim_u;
         lv->params = *p;
         lv->params.slope_factor = (float)((0.0 + dim_u) / U);             // f2c.hpp:139
-        float scale = 255.0f;                                              // dc.hpp:696-699 (uchar)
-        if (!is_u8) {
-            scale = epi_scale_factor;
-            if (scale < 0) {                                               // dc.hpp:671-690: this level's own max
-                rc = rslf_device_max_f32(ctx, cur_p, (size_t)dim_v * S * dim_u * C, &scale);
-                if (rc)
-                    return rc;
-            }
-        }
+        float scale;
+        rc = f2c_level_scale(ctx, elem, cur_p, (size_t)dim_v * S * dim_u * C, epi_scale_factor, &scale);
+        if (rc)
+            return rc;
         rc = rslf_volume_create(ctx, dim_v, S, dim_u, C, &lv->vol);
         if (rc)
             return rc;
@@ -321,9 +369,7 @@ extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_
         const int v2 = dims[l + 1].V, u2 = dims[l + 1].U;
         DevBuf next;                                                       // f2c.hpp:145-147: the RAW EPIs go down
         HIP_TRY(next.alloc((size_t)v2 * S * u2 * C * sizeof(float)));
-        // uchar EPIs go down in uchar arithmetic, as the reference's CV_8U Mats do (fine_to_coarse_core.cpp:22-41)
-        rc = is_u8 ? rslf_downsample_epis_u8(ctx, cur_p, dim_v, S, dim_u, C, (float*)next.p)
-                   : rslf_downsample_epis_f32(ctx, cur_p, dim_v, S, dim_u, C, (float*)next.p);
+        rc = f2c_downsample(ctx, elem, cur_p, dim_v, S, dim_u, C, (float*)next.p);
         if (rc)
             return rc;
         std::swap(cur.p, next.p);   // `next` now frees the previous level's raw copy
@@ -408,5 +454,26 @@ extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_
         stats->units = pixels * dim_d;
     }
     return RSLF_OK;
+}
+
+extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
+                                            size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                            const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                            float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+{
+    return fine_to_coarse_run_host(ctx, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
+                                   stats);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_fine_to_coarse_run_host_u16(rslf_ctx* ctx, const uint16_t* const* h_epis, int V, int S, int U, int C,
+                                                size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                                const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+{
+    return fine_to_coarse_run_host(ctx, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
+                                   stats);
 }
 RSLF_API_CATCH

@@ -292,12 +292,28 @@ int ensure_plane_scratch(rslf_ctx* ctx, int V, int U);
 int ensure_group_scratch(rslf_ctx* ctx, size_t recs, size_t tiles);
 int ensure_staging(rslf_ctx* ctx, size_t bytes);
 int helper_scratch(rslf_ctx* ctx, int slot, size_t bytes, void** out);
-float host_max_f32(const float* const* h_ptrs, int n_ptrs, int rows, size_t row_stride_bytes, size_t row_elems, float start);
-float host_max_f32_parallel(const float* const* h_epis, int V, int S, size_t stride, size_t row_elems, float start);
+// The element type of a host light field (the cv::Mat depths the reference's constructors take, dc.hpp:269-288,
+// :442-475, :671-705): CV_32F, CV_8U, CV_16U.  Chosen once at the C-ABI entry point; everything below it dispatches on it.
+enum class Elem { F32, U8, U16 };
+inline size_t elem_bytes(Elem e) { return e == Elem::F32 ? sizeof(float) : e == Elem::U8 ? 1 : sizeof(uint16_t); }
+// dc.hpp:442-460 over host rows: max(start, every value as float) -- exact for ushort, so a u16 field's max equals the
+// max of the same values given as float
+template <typename T>
+float host_max(const T* const* h_ptrs, int n_ptrs, int rows, size_t row_stride_bytes, size_t row_elems, float start);
+template <typename T>
+float host_max_parallel(const T* const* h_epis, int V, int S, size_t stride, size_t row_elems, float start);
+// The constructor's epi_scale_factor for element type e: CV_8U -> 255 (the factor is ignored, dc.hpp:470); every other
+// depth -> the given factor, or when it is < 0 the max over every value of the n_ptrs x rows host rows (dc.hpp:442-475).
+// The stored value is then x * scale_of(factor) for every type (scale_of(255) == float(1/255)).
+float resolve_scale_factor(Elem e, const void* const* h_ptrs, int n_ptrs, int rows, size_t row_stride_bytes, size_t row_elems,
+                           float epi_scale_factor, bool parallel);
 template <typename SrcT>
 int upload_host(rslf_volume* vol, const SrcT* const* h_ptrs, size_t row_stride_bytes, bool image_major, float scale);
 extern template int upload_host<float>(rslf_volume*, const float* const*, size_t, bool, float);
 extern template int upload_host<uint8_t>(rslf_volume*, const uint8_t* const*, size_t, bool, float);
+extern template int upload_host<uint16_t>(rslf_volume*, const uint16_t* const*, size_t, bool, float);
+// upload_host for a field of element type e
+int upload_host_elem(rslf_volume* vol, Elem e, const void* const* h_ptrs, size_t row_stride_bytes, bool image_major, float scale);
 
 // rslf_pile.hip
 // What a scan is given besides the arguments of rslf_depth_epi_scan: where its pixel lists come from and the launch shape
@@ -321,8 +337,16 @@ void fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_stats* st
 int scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf_params* p, const int* rows, int n_rows);
 int sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const ScanInputs& sparse);
 
-// rslf_f2c.hip: small elementwise launches the multi-device form shares
-int f2c_u8_to_f32(hipStream_t st, const uint8_t* in, float* out, size_t n);
+// rslf_f2c.hip: the per-type steps and small elementwise launches the multi-device form shares
+// The finest level's raw values from host EPIs of element type e into the dense float volume d_raw [V][S][U][C]
+// (integer types widened on the device); synchronises.
+int f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
+                   float* d_raw);
+// The level rule of FineToCoarse on element type e: the level's epi_scale_factor (CV_8U: 255; otherwise the given factor
+// or, when < 0, the level's own max -- dc.hpp:671-705) and the halving that keeps the Mats' type
+// (fine_to_coarse_core.cpp:22-41: rslf_downsample_epis_u8 / _u16 / _f32).
+int f2c_level_scale(rslf_ctx* ctx, Elem e, const float* d_raw, size_t n, float epi_scale_factor, float* scale);
+int f2c_downsample(rslf_ctx* ctx, Elem e, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc);
 int f2c_fill_f32(hipStream_t st, float* out, size_t n, float value);
 int f2c_valid_mask(hipStream_t st, const float* Ce, uint8_t* out, size_t n, float thr);
 

@@ -161,10 +161,10 @@ namespace {
 
 struct MultiJob {
     const void* const* h_epis;
-    bool is_u8;
+    Elem elem;
     size_t row_stride_bytes;
     int V, S, U, C;
-    float scale_arg;      // f32: the divisor (already resolved, > 0 or as given); u8: unused
+    float scale_arg;      // the divisor, already resolved (resolve_scale_factor)
     float dmin, dmax;
     int dim_d, s_hat;
     const rslf_params* p;
@@ -226,7 +226,7 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
     rslf_ctx* ctx = d.ctx;
     MW_HIP(hipSetDevice(ctx->device));
     // Do the EPIs follow one another in host memory (a stacked array) or are they scattered over the heap (a Vec<Mat>)?
-    const size_t in_row_bytes = (size_t)j.U * j.C * (j.is_u8 ? 1 : sizeof(float));
+    const size_t in_row_bytes = (size_t)j.U * j.C * elem_bytes(j.elem);
     const size_t in_epi_bytes = in_row_bytes * j.S;
     const bool scattered = plan::epis_scattered(j.h_epis, r0, r1, j.row_stride_bytes ? j.row_stride_bytes : in_row_bytes,
                                                 in_row_bytes, in_epi_bytes);
@@ -308,8 +308,7 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
         // EPIs scattered over the heap (a Vec<Mat>) would be one pageable copy each, and the runtime stages those through
         // its own bounce buffer on the calling thread at ~10 GB/s -- slower than the kernels consume them.  They are
         // gathered into a pinned buffer by a few host threads first (dense rows; ~25 GB/s per thread) and go up from there.
-        const size_t esz = j.is_u8 ? 1 : sizeof(float);
-        const size_t row_bytes = (size_t)j.U * j.C * esz;
+        const size_t row_bytes = (size_t)j.U * j.C * elem_bytes(j.elem);
         const size_t stride = j.row_stride_bytes ? j.row_stride_bytes : row_bytes;
         const size_t epi_bytes = row_bytes * j.S;
         const int rows = c.hi - c.lo;
@@ -348,11 +347,7 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
             src = staged.data();
             src_stride = row_bytes;
         }
-        int rc;
-        if (j.is_u8)
-            rc = upload_host<uint8_t>(vol, (const uint8_t* const*)src, src_stride, false, (float)(1.0 / 255.0));
-        else
-            rc = upload_host<float>(vol, (const float* const*)src, src_stride, false, scale_of(j.scale_arg));
+        const int rc = upload_host_elem(vol, j.elem, src, src_stride, false, scale_of(j.scale_arg));
         return rc;   // upload_host ends with a synchronisation of its stream (minmax_end): the pinned buffer is free again
     };
     auto compute = [&](int k) -> int {
@@ -510,24 +505,27 @@ int multi_run(rslf_multi* m, MultiJob j, rslf_stats* stats)
 
 }  // namespace
 
-static int multi_pile_f32(rslf_multi* m, const float* const* h_epis, size_t row_stride_bytes, int V, int S, int U, int C,
-                          float epi_scale_factor, float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p, int out_device,
-                          float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu,
-                          float* h_score_vu, float* h_depth_raw_vu, rslf_stats* stats, float* scale_used)
+// Depth1DComputer_pile from host EPIs of element type e: the default scale (epi_scale_factor < 0: the maximum over ALL EPIs,
+// dc.hpp:442-460) is taken once here, never per block; CV_8U's is 1/255 (resolve_scale_factor).
+static int multi_pile(rslf_multi* m, Elem e, const void* const* h_epis, size_t row_stride_bytes, int V, int S, int U, int C,
+                      float epi_scale_factor, float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p, int out_device,
+                      float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu,
+                      float* h_score_vu, float* h_depth_raw_vu, rslf_stats* stats, float* scale_used)
 {
-    if (!m || !h_epis || V < 1)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (!m || !h_epis || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument or bad dimensions V=%d S=%d U=%d C=%d", V, S, U, C);
     const size_t row_elems = (size_t)U * C;
-    const size_t stride = row_stride_bytes ? row_stride_bytes : row_elems * sizeof(float);
+    const size_t row_bytes = row_elems * elem_bytes(e);
+    const size_t stride = row_stride_bytes ? row_stride_bytes : row_bytes;
+    if (stride < row_bytes)
+        return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", stride, row_bytes);
     for (int v = 0; v < V; v++)
         if (!h_epis[v])
             return fail(RSLF_ERR_INVALID_ARG, "h_epis[%d] is NULL", v);
-    // dc.hpp:442-460: the default scale is the maximum over ALL EPIs -- taken once here, never per block
-    if (epi_scale_factor < 0)
-        epi_scale_factor = host_max_f32_parallel(h_epis, V, S, stride, row_elems, epi_scale_factor);
+    epi_scale_factor = resolve_scale_factor(e, h_epis, V, S, stride, row_elems, epi_scale_factor, true);
     if (scale_used)
         *scale_used = epi_scale_factor;
-    MultiJob j = {(const void* const*)h_epis, false, stride, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat, p,
+    MultiJob j = {h_epis, e, stride, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat, p,
                   h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, 0, out_device};
     return multi_run(m, j, stats);
 }
@@ -538,8 +536,8 @@ extern "C" int rslf_multi_depth1d_pile_f32(rslf_multi* m, const float* const* h_
                                            float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu,
                                            float* h_depth_raw_vu, rslf_stats* stats, float* scale_used) RSLF_API_TRY
 {
-    return multi_pile_f32(m, h_epis, row_stride_bytes, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat, p, -1, h_Ce_vu,
-                          h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, stats, scale_used);
+    return multi_pile(m, Elem::F32, (const void* const*)h_epis, row_stride_bytes, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat,
+                      p, -1, h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, stats, scale_used);
 }
 RSLF_API_CATCH
 
@@ -551,8 +549,9 @@ extern "C" int rslf_multi_depth1d_pile_f32_dev(rslf_multi* m, const float* const
 {
     if (out_device < 0)
         return fail(RSLF_ERR_INVALID_ARG, "out_device %d", out_device);
-    return multi_pile_f32(m, h_epis, row_stride_bytes, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat, p, out_device, d_Ce_vu,
-                          d_Ce_mask_vu, d_Cd_vu, d_depth_vu, d_rbar_vu, d_idx_vu, d_score_vu, d_depth_raw_vu, stats, scale_used);
+    return multi_pile(m, Elem::F32, (const void* const*)h_epis, row_stride_bytes, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat,
+                      p, out_device, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu, d_rbar_vu, d_idx_vu, d_score_vu, d_depth_raw_vu, stats,
+                      scale_used);
 }
 RSLF_API_CATCH
 
@@ -561,8 +560,19 @@ extern "C" int rslf_multi_depth1d_pile_u8(rslf_multi* m, const uint8_t* const* h
                                           uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu,
                                           float* h_score_vu, float* h_depth_raw_vu, rslf_stats* stats) RSLF_API_TRY
 {
-    MultiJob j = {(const void* const*)h_epis, true, row_stride_bytes, V, S, U, C, 255.0f, dmin, dmax, dim_d, s_hat, p,
+    MultiJob j = {(const void* const*)h_epis, Elem::U8, row_stride_bytes, V, S, U, C, 255.0f, dmin, dmax, dim_d, s_hat, p,
                   h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, 0, -1};
     return multi_run(m, j, stats);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_multi_depth1d_pile_u16(rslf_multi* m, const uint16_t* const* h_epis, size_t row_stride_bytes, int V, int S, int U,
+                                           int C, float epi_scale_factor, float dmin, float dmax, int dim_d, int s_hat,
+                                           const rslf_params* p, float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu,
+                                           float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu,
+                                           float* h_depth_raw_vu, rslf_stats* stats, float* scale_used) RSLF_API_TRY
+{
+    return multi_pile(m, Elem::U16, (const void* const*)h_epis, row_stride_bytes, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat,
+                      p, -1, h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, stats, scale_used);
 }
 RSLF_API_CATCH

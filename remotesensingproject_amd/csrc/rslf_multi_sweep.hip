@@ -61,7 +61,7 @@ struct FirstDevicePlanes {
     float* depth_svu = nullptr;
 };
 
-int multi_depth2d(rslf_multi* m, const void* const* h_epis, bool is_u8, size_t row_stride_bytes, int V, int S, int U, int C, float scale_arg,
+int multi_depth2d(rslf_multi* m, const void* const* h_epis, Elem elem, size_t row_stride_bytes, int V, int S, int U, int C, float scale_arg,
                   float dmin, float dmax, int dim_d, const rslf_params* p, float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu,
                   float* h_depth_svu, float* h_rbar_svu, uint8_t* h_scan_mask_svu, rslf_stats* stats,
                   const FirstDevicePlanes* first = nullptr)
@@ -129,10 +129,8 @@ int multi_depth2d(rslf_multi* m, const void* const* h_epis, bool is_u8, size_t r
                 src = (const float*)ctx->staging;
             }
             S2_TRY(rslf_volume_pack_device_f32(d.vol, src, scale_arg, nullptr));
-        } else if (is_u8) {
-            S2_TRY(upload_host<uint8_t>(d.vol, (const uint8_t* const*)h_epis + d.lo, row_stride_bytes, false, (float)(1.0 / 255.0)));
         } else {
-            S2_TRY(upload_host<float>(d.vol, (const float* const*)h_epis + d.lo, row_stride_bytes, false, scale_of(scale_arg)));
+            S2_TRY(upload_host_elem(d.vol, elem, h_epis + d.lo, row_stride_bytes, false, scale_of(scale_arg)));
         }
         {   // planes: one allocation per device, grown when a larger field comes (allocation calls synchronise the device)
             rslf_multi::Dev& md = m->devs[(size_t)i];
@@ -271,10 +269,10 @@ int multi_depth2d(rslf_multi* m, const void* const* h_epis, bool is_u8, size_t r
 // and the fusion, cheap whole-image passes with non-local footprints, run on the first device, where every level's raw
 // volume, ranges, disparities and confidences stay: the devices take their rows from there and leave their results there
 // by peer copies (FirstDevicePlanes).  The host sees the EPIs going up once and the fused map coming down.
-extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
-                                                  size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
-                                                  const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
-                                                  float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+static int multi_fine_to_coarse(rslf_multi* m, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
+                                float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                                int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
+                                rslf_stats* stats)
 {
     if (!m || !h_epis || !h_out_map_svu || !h_out_valid_svu || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
@@ -284,10 +282,6 @@ extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* con
     rslf_ctx* ctx = m->devs[0].ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t elem = is_u8 ? 1 : 4;
-    const size_t row_bytes = (size_t)U * C * elem;
-    if (row_stride_bytes == 0)
-        row_stride_bytes = row_bytes;
 
     struct Level {
         int V = 0, U = 0;
@@ -304,27 +298,9 @@ extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* con
     {
         Level& l0 = levels.front();
         HIP_TRY(l0.raw.alloc((size_t)V * S * U * C * sizeof(float)));
-        DevBuf stage;
-        void* dst = l0.raw.p;
-        if (is_u8) {
-            HIP_TRY(stage.alloc((size_t)V * S * row_bytes));
-            dst = stage.p;
-        }
-        for (int v = 0; v < V; v++) {
-            if (!h_epis[v])
-                return fail(RSLF_ERR_INVALID_ARG, "h_epis[%d] is NULL", v);
-            if (row_stride_bytes == row_bytes)
-                HIP_TRY(hipMemcpyAsync((char*)dst + (size_t)v * S * row_bytes, h_epis[v], (size_t)S * row_bytes, hipMemcpyHostToDevice, st));
-            else
-                HIP_TRY(hipMemcpy2DAsync((char*)dst + (size_t)v * S * row_bytes, row_bytes, h_epis[v], row_stride_bytes, row_bytes, S,
-                                         hipMemcpyHostToDevice, st));
-        }
-        if (is_u8) {
-            rc = f2c_u8_to_f32(st, (const uint8_t*)stage.p, (float*)l0.raw.p, (size_t)V * S * U * C);
-            if (rc)
-                return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(st));
+        rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, (float*)l0.raw.p);
+        if (rc)
+            return rc;
     }
     for (size_t l = 0; l < dims.size(); l++) {
         Level& lv = levels[l];
@@ -333,21 +309,14 @@ extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* con
         lv.U = dim_u;
         lv.params = *p;
         lv.params.slope_factor = (float)((0.0 + dim_u) / U);              // f2c.hpp:139
-        lv.scale = 255.0f;                                                // dc.hpp:696-699 (uchar)
-        if (!is_u8) {
-            lv.scale = epi_scale_factor;
-            if (lv.scale < 0) {                                           // dc.hpp:671-690: this level's own max
-                rc = rslf_device_max_f32(ctx, (const float*)lv.raw.p, (size_t)dim_v * S * dim_u * C, &lv.scale);
-                if (rc)
-                    return rc;
-            }
-        }
+        rc = f2c_level_scale(ctx, elem, (const float*)lv.raw.p, (size_t)dim_v * S * dim_u * C, epi_scale_factor, &lv.scale);
+        if (rc)
+            return rc;
         if (l + 1 == dims.size())
             break;
         Level& nx = levels[l + 1];
         HIP_TRY(nx.raw.alloc((size_t)dims[l + 1].V * S * dims[l + 1].U * C * sizeof(float)));   // f2c.hpp:145-147: the RAW EPIs go down
-        rc = is_u8 ? rslf_downsample_epis_u8(ctx, (const float*)lv.raw.p, dim_v, S, dim_u, C, (float*)nx.raw.p)
-                   : rslf_downsample_epis_f32(ctx, (const float*)lv.raw.p, dim_v, S, dim_u, C, (float*)nx.raw.p);
+        rc = f2c_downsample(ctx, elem, (const float*)lv.raw.p, dim_v, S, dim_u, C, (float*)nx.raw.p);
         if (rc)
             return rc;
     }
@@ -386,7 +355,7 @@ extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* con
             first.dmax_svu = (const float*)d_hi.p;
         }
         HIP_TRY(hipStreamSynchronize(st));   // what the other devices' streams are about to read is complete
-        rc = multi_depth2d(m, nullptr, false, 0, lv.V, S, lv.U, C, lv.scale, d_min, d_max, dim_d, &lv.params, nullptr, nullptr, nullptr,
+        rc = multi_depth2d(m, nullptr, Elem::F32, 0, lv.V, S, lv.U, C, lv.scale, d_min, d_max, dim_d, &lv.params, nullptr, nullptr, nullptr,
                            nullptr, nullptr, nullptr, &st1, &first);
         if (rc)
             return rc;
@@ -429,26 +398,59 @@ extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* con
     }
     return RSLF_OK;
 }
+
+extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
+                                                  size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                                  const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                                  float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+{
+    return multi_fine_to_coarse(m, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats);
+}
 RSLF_API_CATCH
+
+extern "C" int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint16_t* const* h_epis, int V, int S, int U, int C,
+                                                      size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                                      const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                                      float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
+                                                      rslf_stats* stats) RSLF_API_TRY
+{
+    return multi_fine_to_coarse(m, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats);
+}
+RSLF_API_CATCH
+
+// Depth2DComputer from host EPIs of element type e; the default scale is the maximum over ALL EPIs, taken once
+// (dc.hpp:671-705, resolve_scale_factor).
+static int multi_depth2d_host(rslf_multi* m, Elem e, const void* const* h_epis, size_t row_stride_bytes, int V, int S, int U, int C,
+                              float epi_scale_factor, float dmin, float dmax, int dim_d, const rslf_params* p, float* h_Ce_svu,
+                              uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu, uint8_t* h_scan_mask_svu,
+                              rslf_stats* stats, float* scale_used)
+{
+    if (!m || !h_epis || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument or bad dimensions V=%d S=%d U=%d C=%d", V, S, U, C);
+    const size_t row_elems = (size_t)U * C;
+    const size_t row_bytes = row_elems * elem_bytes(e);
+    const size_t stride = row_stride_bytes ? row_stride_bytes : row_bytes;
+    if (stride < row_bytes)
+        return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", stride, row_bytes);
+    for (int v = 0; v < V; v++)
+        if (!h_epis[v])
+            return fail(RSLF_ERR_INVALID_ARG, "h_epis[%d] is NULL", v);
+    epi_scale_factor = resolve_scale_factor(e, h_epis, V, S, stride, row_elems, epi_scale_factor, true);
+    if (scale_used)
+        *scale_used = epi_scale_factor;
+    return multi_depth2d(m, h_epis, e, stride, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu,
+                         h_depth_svu, h_rbar_svu, h_scan_mask_svu, stats);
+}
 
 extern "C" int rslf_multi_depth2d_run_f32(rslf_multi* m, const float* const* h_epis, size_t row_stride_bytes, int V, int S, int U, int C,
                                           float epi_scale_factor, float dmin, float dmax, int dim_d, const rslf_params* p,
                                           float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
                                           float* h_rbar_svu, uint8_t* h_scan_mask_svu, rslf_stats* stats, float* scale_used) RSLF_API_TRY
 {
-    if (!m || !h_epis || V < 1 || S < 1 || U < 1)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    const size_t row_elems = (size_t)U * C;
-    const size_t stride = row_stride_bytes ? row_stride_bytes : row_elems * sizeof(float);
-    for (int v = 0; v < V; v++)
-        if (!h_epis[v])
-            return fail(RSLF_ERR_INVALID_ARG, "h_epis[%d] is NULL", v);
-    if (epi_scale_factor < 0)   // dc.hpp:671-705: the maximum over ALL EPIs, taken once
-        epi_scale_factor = host_max_f32_parallel(h_epis, V, S, stride, row_elems, epi_scale_factor);
-    if (scale_used)
-        *scale_used = epi_scale_factor;
-    return multi_depth2d(m, (const void* const*)h_epis, false, stride, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, p, h_Ce_svu,
-                         h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, h_scan_mask_svu, stats);
+    return multi_depth2d_host(m, Elem::F32, (const void* const*)h_epis, row_stride_bytes, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d,
+                              p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, h_scan_mask_svu, stats, scale_used);
 }
 RSLF_API_CATCH
 
@@ -457,7 +459,17 @@ extern "C" int rslf_multi_depth2d_run_u8(rslf_multi* m, const uint8_t* const* h_
                                          uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
                                          uint8_t* h_scan_mask_svu, rslf_stats* stats) RSLF_API_TRY
 {
-    return multi_depth2d(m, (const void* const*)h_epis, true, row_stride_bytes, V, S, U, C, 255.0f, dmin, dmax, dim_d, p, h_Ce_svu,
+    return multi_depth2d(m, (const void* const*)h_epis, Elem::U8, row_stride_bytes, V, S, U, C, 255.0f, dmin, dmax, dim_d, p, h_Ce_svu,
                          h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, h_scan_mask_svu, stats);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_multi_depth2d_run_u16(rslf_multi* m, const uint16_t* const* h_epis, size_t row_stride_bytes, int V, int S, int U, int C,
+                                          float epi_scale_factor, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                          float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                                          float* h_rbar_svu, uint8_t* h_scan_mask_svu, rslf_stats* stats, float* scale_used) RSLF_API_TRY
+{
+    return multi_depth2d_host(m, Elem::U16, (const void* const*)h_epis, row_stride_bytes, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d,
+                              p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, h_scan_mask_svu, stats, scale_used);
 }
 RSLF_API_CATCH

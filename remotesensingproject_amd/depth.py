@@ -161,6 +161,17 @@ def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+# The element types of a host light field (the reference's CV_8U, CV_16U and CV_32F Mats) and their C-ABI suffixes.
+_SUFFIX = {np.dtype(np.uint8): "u8", np.dtype(np.uint16): "u16", np.dtype(np.float32): "f32"}
+
+
+def field_dtype(dtype) -> np.dtype:
+    """The element type a host light field of `dtype` is sent as: uint8 and uint16 as they are, anything else as float32
+    (the reference's constructors normalise every depth other than 8U by the max, dc.hpp:269-288, :442-475, :671-705)."""
+    dt = np.dtype(dtype)
+    return dt if dt in (np.uint8, np.uint16) else np.dtype(np.float32)
+
+
 class Volume:
     """The light-field slab in HBM, [V][S][pitch][C] float32 (rslf_volume)."""
 
@@ -176,26 +187,27 @@ class Volume:
     @staticmethod
     def from_epis(epis: Sequence[np.ndarray], epi_scale_factor: float = -1.0, ctx: Context | None = None) -> "Volume":
         """The reference's constructor input: a Vec<Mat> of V EPIs, each [S,U] or
-        [S,U,3], uint8 or float32 (dc.hpp:425-477)."""
+        [S,U,3], uint8, uint16 or float32 (dc.hpp:425-477).  uint16 goes up as it is (no host cast) and is
+        normalised like float: by the max over all values unless a factor is given."""
         ctx = ctx or default_context()
         e0 = np.asarray(epis[0])
         S, U = e0.shape[:2]
         C_ = 1 if e0.ndim == 2 else e0.shape[2]
         vol = Volume(ctx, len(epis), S, U, C_)
-        is_u8 = e0.dtype == np.uint8
-        arrs = [np.ascontiguousarray(e, dtype=np.uint8 if is_u8 else np.float32) for e in epis]
+        dt = field_dtype(e0.dtype)
+        arrs = [np.ascontiguousarray(e, dtype=dt) for e in epis]
         for a in arrs:
             if a.shape != arrs[0].shape:
                 raise ValueError("all EPIs must have the same shape")
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         L = _lib.lib()
-        if is_u8:
+        if dt == np.uint8:
             check(L.rslf_volume_upload_epis_u8(vol._h, ptrs, 0), "rslf_volume_upload_epis_u8")
             vol.scale_used = 255.0
         else:
+            name = "rslf_volume_upload_epis_" + _SUFFIX[dt]
             su = C.c_float()
-            check(L.rslf_volume_upload_epis_f32(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su)),
-                  "rslf_volume_upload_epis_f32")
+            check(getattr(L, name)(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su)), name)
             vol.scale_used = float(su.value)
         return vol
 
@@ -211,12 +223,12 @@ class Volume:
         C_ = 1 if i0.ndim == 2 else i0.shape[2]
         S, U = (cols, len(imgs)) if transpose else (len(imgs), cols)
         vol = Volume(ctx, V, S, U, C_)
-        is_u8 = i0.dtype == np.uint8
-        arrs = [np.ascontiguousarray(e, dtype=np.uint8 if is_u8 else np.float32) for e in imgs]
+        dt = field_dtype(i0.dtype)
+        arrs = [np.ascontiguousarray(e, dtype=dt) for e in imgs]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         L = _lib.lib()
         plain = not (transpose or rotate_180)
-        if is_u8:
+        if dt == np.uint8:
             if plain:
                 check(L.rslf_volume_upload_images_u8(vol._h, ptrs, 0), "rslf_volume_upload_images_u8")
             else:
@@ -226,11 +238,11 @@ class Volume:
         else:
             su = C.c_float()
             if plain:
-                check(L.rslf_volume_upload_images_f32(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su)),
-                      "rslf_volume_upload_images_f32")
+                name = "rslf_volume_upload_images_" + _SUFFIX[dt]
+                check(getattr(L, name)(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su)), name)
             else:
-                check(L.rslf_volume_upload_images_xf_f32(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su), int(transpose),
-                                                         int(rotate_180)), "rslf_volume_upload_images_xf_f32")
+                name = "rslf_volume_upload_images_xf_" + _SUFFIX[dt]
+                check(getattr(L, name)(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su), int(transpose), int(rotate_180)), name)
             vol.scale_used = float(su.value)
         return vol
 
@@ -429,11 +441,11 @@ class MultiDevice:
 
     def depth1d_pile(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, s_hat: int = -1,
                      epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None) -> dict:
-        """epis: the reference's Vec<Mat> -- V arrays [S,U] or [S,U,3], all uint8 or all float32."""
+        """epis: the reference's Vec<Mat> -- V arrays [S,U] or [S,U,3], all uint8, all uint16 or all float32."""
         first = np.asarray(epis[0])
         dt = first.dtype
-        if dt not in (np.uint8, np.float32):
-            raise TypeError("EPIs must be uint8 or float32 (dc.hpp:149-154)")
+        if dt not in (np.uint8, np.uint16, np.float32):
+            raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
         # keeps the buffers alive over the call; a thousand EPIs: no per-array conversions or ctypes objects where none are needed
         keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
         V = len(keep)
@@ -457,9 +469,9 @@ class MultiDevice:
             self.scale_used = 255.0
         else:
             su = C.c_float()
-            check(L.rslf_multi_depth1d_pile_f32(self._h, ptrs, 0, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
-                                                int(dim_d), int(s_hat), C.byref(p), *hp, C.byref(st), C.byref(su)),
-                  "rslf_multi_depth1d_pile_f32")
+            name = "rslf_multi_depth1d_pile_" + _SUFFIX[dt]
+            check(getattr(L, name)(self._h, ptrs, 0, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
+                                   int(dim_d), int(s_hat), C.byref(p), *hp, C.byref(st), C.byref(su)), name)
             self.scale_used = float(su.value)
         self.stats = st
         return out
@@ -468,11 +480,11 @@ class MultiDevice:
                 parameters: Depth1DParameters | None = None) -> dict:
         """Depth2DComputer (constructor + run + getters) over this object's devices: the 2-D sweep cut into one block of
         scanlines per device, the neighbours' boundary rows exchanged by peer copy on every visit
-        (rslf_multi_depth2d_run_f32 / _u8).  Host EPIs in, numpy planes [S, V, U] out."""
+        (rslf_multi_depth2d_run_f32 / _u8 / _u16).  Host EPIs in, numpy planes [S, V, U] out."""
         first = np.asarray(epis[0])
         dt = first.dtype
-        if dt not in (np.uint8, np.float32):
-            raise TypeError("EPIs must be uint8 or float32 (dc.hpp:149-154)")
+        if dt not in (np.uint8, np.uint16, np.float32):
+            raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
         keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
         V = len(keep)
         S, U = keep[0].shape[0], keep[0].shape[1]
@@ -493,8 +505,9 @@ class MultiDevice:
             self.scale_used = 255.0
         else:
             su = C.c_float()
-            check(L.rslf_multi_depth2d_run_f32(self._h, ptrs, 0, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
-                                               int(dim_d), C.byref(p), *hp, C.byref(st), C.byref(su)), "rslf_multi_depth2d_run_f32")
+            name = "rslf_multi_depth2d_run_" + _SUFFIX[dt]
+            check(getattr(L, name)(self._h, ptrs, 0, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
+                                   int(dim_d), C.byref(p), *hp, C.byref(st), C.byref(su)), name)
             self.scale_used = float(su.value)
         self.stats = st
         return out
@@ -505,8 +518,8 @@ class MultiDevice:
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         first = np.asarray(epis[0])
         dt = first.dtype
-        if dt not in (np.uint8, np.float32):
-            raise TypeError("EPIs must be uint8 or float32 (dc.hpp:149-154)")
+        if dt not in (np.uint8, np.uint16, np.float32):
+            raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
         keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
         V = len(keep)
         S, U = keep[0].shape[0], keep[0].shape[1]
@@ -516,11 +529,14 @@ class MultiDevice:
         out_valid = np.empty((S, V, U), np.uint8)
         p = (parameters or Depth1DParameters()).to_c()
         st, nl = RslfStats(), C.c_int()
-        check(_lib.lib().rslf_multi_fine_to_coarse_run_host(self._h, ptrs, 1 if dt == np.uint8 else 0, V, S, U, C_, 0, float(d_min), float(d_max),
-                                                            int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
-                                                            1 if accept_all_last_scale else 0, out_map.ctypes.data_as(C.c_void_p),
-                                                            out_valid.ctypes.data_as(C.c_void_p), C.byref(nl), C.byref(st)),
-              "rslf_multi_fine_to_coarse_run_host")
+        rest = (V, S, U, C_, 0, float(d_min), float(d_max), int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
+                1 if accept_all_last_scale else 0, out_map.ctypes.data_as(C.c_void_p), out_valid.ctypes.data_as(C.c_void_p),
+                C.byref(nl), C.byref(st))
+        if dt == np.uint16:   # ushort arithmetic through the pyramid
+            check(_lib.lib().rslf_multi_fine_to_coarse_run_host_u16(self._h, ptrs, *rest), "rslf_multi_fine_to_coarse_run_host_u16")
+        else:
+            check(_lib.lib().rslf_multi_fine_to_coarse_run_host(self._h, ptrs, 1 if dt == np.uint8 else 0, *rest),
+                  "rslf_multi_fine_to_coarse_run_host")
         self.stats = st
         return out_map, out_valid, int(nl.value)
 
@@ -726,10 +742,13 @@ class Depth1DComputer:
 _MIN_SPATIAL_DIM = 10   # rslf_fine_to_coarse.hpp:8
 
 
-def downsample_EPIs(raw_vsuc: torch.Tensor, ctx: Context | None = None, is_u8: bool = False) -> torch.Tensor:
+def downsample_EPIs(raw_vsuc: torch.Tensor, ctx: Context | None = None, is_u8: bool = False, dtype=None) -> torch.Tensor:
     """rslf::downsample_EPIs (src/rslf_fine_to_coarse_core.cpp:14-60) on a dense RAW float32 CUDA volume
-    [V,S,U,C] -> [V2,S,U2,C].  is_u8: the values are uchar levels (a CV_8U light field) and the blur and the halving
-    run in uchar arithmetic, as the reference's Mats of the input's own type do."""
+    [V,S,U,C] -> [V2,S,U2,C].  `dtype` is the light field's element type: np.uint8 (or is_u8=True) -- the values are
+    uchar levels of a CV_8U field and the blur and the halving run in uchar arithmetic; np.uint16 -- ushort levels of a
+    CV_16U field, each blurred level rounded back to ushort before the halving; float32 (the default) -- float arithmetic.
+    The reference's Mats keep the input's own type through the pyramid."""
+    dt = np.dtype(np.uint8) if (dtype is None and is_u8) else field_dtype(np.float32 if dtype is None else dtype)
     ctx = ctx or default_context(raw_vsuc.device)
     t = raw_vsuc.contiguous()
     V, S, U, C_ = t.shape
@@ -737,11 +756,27 @@ def downsample_EPIs(raw_vsuc: torch.Tensor, ctx: Context | None = None, is_u8: b
     check(_lib.lib().rslf_f2c_level_dims(V, U, C.byref(v2), C.byref(u2)), "rslf_f2c_level_dims")
     out = torch.empty((v2.value, S, u2.value, C_), dtype=torch.float32, device=t.device)
     ctx.use_current_stream()
-    if is_u8:
-        check(_lib.lib().rslf_downsample_epis_u8(ctx._h, _ptr(t), V, S, U, C_, _ptr(out)), "rslf_downsample_epis_u8")
-    else:
-        check(_lib.lib().rslf_downsample_epis_f32(ctx._h, _ptr(t), V, S, U, C_, _ptr(out)), "rslf_downsample_epis_f32")
+    name = "rslf_downsample_epis_" + _SUFFIX[dt]
+    check(getattr(_lib.lib(), name)(ctx._h, _ptr(t), V, S, U, C_, _ptr(out)), name)
     return out
+
+
+def f2c_level(raw_vsuc: torch.Tensor, dtype, epi_scale_factor: float, ctx: Context) -> tuple[float, torch.Tensor]:
+    """The per-level rule of FineToCoarse for a light field of element type `dtype` (FineToCoarse and
+    sharding.ShardedFineToCoarse): the level's epi_scale_factor -- Depth2DComputer's constructor normalises ITS input,
+    uchar by 1/255, any other depth by the level's own max unless a factor was given (dc.hpp:671-705) -- and the next
+    level, downsampled in the field's own arithmetic (f2c.hpp:145-147).  Returns (scale, next raw level)."""
+    dt = field_dtype(dtype)
+    if dt == np.uint8:
+        scale = 255.0
+    elif epi_scale_factor < 0:
+        mx = C.c_float()
+        ctx.use_current_stream()
+        check(_lib.lib().rslf_device_max_f32(ctx._h, _ptr(raw_vsuc), raw_vsuc.numel(), C.byref(mx)), "rslf_device_max_f32")
+        scale = float(mx.value)
+    else:
+        scale = float(epi_scale_factor)
+    return scale, downsample_EPIs(raw_vsuc, ctx, dtype=dt)
 
 
 class FineToCoarse:
@@ -750,7 +785,8 @@ class FineToCoarse:
     tightened from the finer level, and a coarse-to-fine fusion of the disparity maps.
 
     `epis`: the reference's Vec<Mat> (list of V arrays [S,U] / [S,U,3]) or a dense array [V,S,U(,C)],
-    float32 or uint8.  A uint8 light field keeps uchar arithmetic through the pyramid, as the reference's CV_8U Mats do."""
+    float32, uint8 or uint16.  An integer light field keeps its own arithmetic through the pyramid, as the reference's
+    CV_8U / CV_16U Mats do."""
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
@@ -762,7 +798,7 @@ class FineToCoarse:
         a = np.stack([np.asarray(e) for e in epis]) if isinstance(epis, (list, tuple)) else np.asarray(epis)
         if a.ndim == 3:
             a = a[..., None]
-        self._is_u8 = a.dtype == np.uint8
+        self._dtype = field_dtype(a.dtype)
         raw = torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
         start_dim_u = raw.shape[2]
         if max_pyr_depth < 1:
@@ -770,26 +806,15 @@ class FineToCoarse:
         self.m_computers: list[Depth2DComputer] = []
         self.m_parameter_instances: list[Depth1DParameters] = []
         dim_v, dim_u, counter = raw.shape[0], raw.shape[2], 0
-        L = _lib.lib()
         while dim_v > _MIN_SPATIAL_DIM and dim_u > _MIN_SPATIAL_DIM and counter < max_pyr_depth:   # f2c.hpp:130
             counter += 1
             new_parameters = copy.copy(self.m_parameters)
             new_parameters.par_slope_factor = float(np.float32((0.0 + dim_u) / start_dim_u))       # f2c.hpp:139
-            # Depth2DComputer's constructor normalises ITS input: uchar by 1/255, float by the level's own max
-            # unless a scale factor was given (dc.hpp:671-705)
-            if self._is_u8:
-                scale = 255.0
-            elif epi_scale_factor < 0:
-                mx = C.c_float()
-                ctx.use_current_stream()
-                check(L.rslf_device_max_f32(ctx._h, _ptr(raw), raw.numel(), C.byref(mx)), "rslf_device_max_f32")
-                scale = float(mx.value)
-            else:
-                scale = float(epi_scale_factor)
+            scale, nxt = f2c_level(raw, self._dtype, epi_scale_factor, ctx)
             vol = Volume.from_dense(raw, scale, ctx)
             self.m_computers.append(Depth2DComputer(vol, d_min, d_max, dim_d, parameters=new_parameters))
             self.m_parameter_instances.append(new_parameters)
-            raw = downsample_EPIs(raw, ctx, self._is_u8)                                           # f2c.hpp:145-147
+            raw = nxt                                                                              # f2c.hpp:145-147
             dim_v, dim_u = raw.shape[0], raw.shape[2]
         if not self.m_computers:
             raise ValueError("light field smaller than _MIN_SPATIAL_DIM: no pyramid level")

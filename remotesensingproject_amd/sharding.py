@@ -455,7 +455,6 @@ class ShardedFineToCoarse:
                  parameters=None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True, ctx=None, group=None):
         import copy
         from . import depth as rs
-        from . import _lib
         self.rs, self.rank, self.world, self.group = rs, int(rank), int(world), group
         self.m_parameters = parameters or rs.Depth1DParameters.get_default()
         self.ctx = ctx or rs.default_context()
@@ -463,27 +462,19 @@ class ShardedFineToCoarse:
         a = np.stack([np.asarray(e) for e in epis]) if isinstance(epis, (list, tuple)) else np.asarray(epis)
         if a.ndim == 3:
             a = a[..., None]
-        is_u8 = a.dtype == np.uint8
+        dtype = rs.field_dtype(a.dtype)
         raw = torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
         start_dim_u = raw.shape[2]
         if max_pyr_depth < 1:
             max_pyr_depth = 1 << 30
         self.levels: List[dict] = []
         dim_v, dim_u, counter = raw.shape[0], raw.shape[2], 0
-        L = _lib.lib()
         while dim_v > rs._MIN_SPATIAL_DIM and dim_u > rs._MIN_SPATIAL_DIM and counter < max_pyr_depth:   # f2c.hpp:130
             counter += 1
             par = copy.copy(self.m_parameters)
             par.par_slope_factor = float(np.float32((0.0 + dim_u) / start_dim_u))                          # f2c.hpp:139
-            if is_u8:
-                scale = 255.0
-            elif epi_scale_factor < 0:      # the level's own maximum (dc.hpp:671-705) -- of the WHOLE level
-                mx = C.c_float()
-                self.ctx.use_current_stream()
-                _lib.check(L.rslf_device_max_f32(self.ctx._h, C.c_void_p(raw.data_ptr()), raw.numel(), C.byref(mx)), "rslf_device_max_f32")
-                scale = float(mx.value)
-            else:
-                scale = float(epi_scale_factor)
+            # the level's scale (by default the own maximum of the WHOLE level, dc.hpp:671-705) and the next level
+            scale, nxt = rs.f2c_level(raw, dtype, epi_scale_factor, self.ctx)
             # a coarse level whose blocks would be thinner than the halo they must fill is small enough to run whole
             # on every rank
             replicated = self.world == 1 or dim_v // self.world < max(1, halo_rows(par.par_median_filter_size, par.par_edge_confidence_opening_size))
@@ -492,7 +483,7 @@ class ShardedFineToCoarse:
             vol = rs.Volume.from_dense(raw[shard.rows].contiguous(), scale, self.ctx)
             self.levels.append(dict(V=dim_v, U=dim_u, par=par, shard=shard, vol=vol, sweep=None, depth=None, valid=None, accept_all=False,
                                     replicated=replicated))
-            raw = rs.downsample_EPIs(raw, self.ctx, is_u8)                                                 # f2c.hpp:145-147
+            raw = nxt                                                                                      # f2c.hpp:145-147
             dim_v, dim_u = raw.shape[0], raw.shape[2]
         if not self.levels:
             raise ValueError("light field smaller than _MIN_SPATIAL_DIM: no pyramid level")
