@@ -1,11 +1,10 @@
 // librslf_hip.so, unit 7 of 9: fine-to-coarse (rslf_fine_to_coarse.hpp:103-324, rslf_fine_to_coarse_core.cpp:14-135) --
-// the pyramid (Gaussian blur + halving), the bound tightening, the fusion (K5), the host-pointer form of the 2-D sweep and
-// the native level loop.  C-ABI: include/rslf_hip.h.
+// the pyramid (Gaussian blur + halving), the bound tightening, the fusion (K5) and the native level loop, whose one-context
+// form is here and whose multi-device form is in rslf_multi_sweep.hip.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <memory>
 
 #include "k5_f2c.hpp"
 
@@ -190,47 +189,7 @@ extern "C" int rslf_f2c_fuse(rslf_ctx* ctx, const float* const* d_disp, const ui
 }
 RSLF_API_CATCH
 
-// ---- host-pointer forms of the rows around the path -----------------------------
-
-extern "C" int rslf_depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
-                                     float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
-                                     float* h_rbar_svu, rslf_stats* stats) RSLF_API_TRY
-{
-    if (!ctx || !vol)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = (size_t)vol->S * vol->V * vol->U;
-    DevBuf Ce, Cd, depth, rbar, mask;
-    HIP_TRY(Ce.alloc(n * 4));
-    HIP_TRY(Cd.alloc(n * 4));
-    HIP_TRY(depth.alloc(n * 4));
-    HIP_TRY(rbar.alloc(n * 4 * vol->C));
-    HIP_TRY(mask.alloc(n));
-    int rc = rslf_depth2d_run(ctx, vol, dmin, dmax, dim_d, p, (float*)Ce.p, (uint8_t*)mask.p, (float*)Cd.p, (float*)depth.p,
-                              (float*)rbar.p, nullptr, stats);
-    if (rc)
-        return rc;
-    hipStream_t st = ctx->stream;
-    if (h_Ce_svu) HIP_TRY(hipMemcpyAsync(h_Ce_svu, Ce.p, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_Ce_mask_svu) HIP_TRY(hipMemcpyAsync(h_Ce_mask_svu, mask.p, n, hipMemcpyDeviceToHost, st));
-    if (h_Cd_svu) HIP_TRY(hipMemcpyAsync(h_Cd_svu, Cd.p, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_depth_svu) HIP_TRY(hipMemcpyAsync(h_depth_svu, depth.p, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_rbar_svu) HIP_TRY(hipMemcpyAsync(h_rbar_svu, rbar.p, n * 4 * vol->C, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RSLF_OK;
-}
-RSLF_API_CATCH
-
 namespace {
-// One pyramid level of rslf::FineToCoarse: its Depth2DComputer's volume and result planes.
-struct F2cLevel {
-    rslf_volume* vol = nullptr;
-    int V = 0, U = 0;
-    DevBuf Ce, Cd, depth, rbar, mask, valid, dmin, dmax;
-    rslf_params params;
-    ~F2cLevel() { rslf_volume_destroy(vol); }
-};
-
 template <typename T>
 __global__ __launch_bounds__(256) void k_to_f32(const T* __restrict__ in, float* __restrict__ out, long long n)
 {
@@ -251,8 +210,10 @@ __global__ __launch_bounds__(256) void k_valid_mask(const float* __restrict__ Ce
 inline unsigned stream_blocks(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 8192); }
 }  // namespace
 
-int rslf::f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
-                         float* d_raw)
+// The finest level's raw values from host EPIs of element type e into the dense float volume d_raw [V][S][U][C] (integer
+// types widened on the device); synchronises.
+static int f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
+                          float* d_raw)
 {
     hipStream_t st = ctx->stream;
     const size_t row_bytes = (size_t)U * C * elem_bytes(e);
@@ -285,7 +246,9 @@ int rslf::f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int V
     HIP_TRY(hipStreamSynchronize(st));   // (the staging buffer is freed on return)
     return RSLF_OK;
 }
-int rslf::f2c_level_scale(rslf_ctx* ctx, Elem e, const float* d_raw, size_t n, float epi_scale_factor, float* scale)
+// The level rule of FineToCoarse on element type e: the level's epi_scale_factor (CV_8U: 255; otherwise the given factor or,
+// when < 0, the level's own max -- dc.hpp:671-705) and the halving that keeps the Mats' type (f2c_downsample).
+static int f2c_level_scale(rslf_ctx* ctx, Elem e, const float* d_raw, size_t n, float epi_scale_factor, float* scale)
 {
     if (e == Elem::U8) {   // dc.hpp:696-699 (uchar)
         *scale = 255.0f;
@@ -296,7 +259,7 @@ int rslf::f2c_level_scale(rslf_ctx* ctx, Elem e, const float* d_raw, size_t n, f
         return rslf_device_max_f32(ctx, d_raw, n, scale);
     return RSLF_OK;
 }
-int rslf::f2c_downsample(rslf_ctx* ctx, Elem e, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc)
+static int f2c_downsample(rslf_ctx* ctx, Elem e, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc)
 {
     // integer EPIs go down in their own arithmetic, as the reference's Mats do (fine_to_coarse_core.cpp:22-41)
     switch (e) {
@@ -308,23 +271,23 @@ int rslf::f2c_downsample(rslf_ctx* ctx, Elem e, const float* d_in_vsuc, int V, i
         return rslf_downsample_epis_f32(ctx, d_in_vsuc, V, S, U, C, d_out_vsuc);
     }
 }
-int rslf::f2c_fill_f32(hipStream_t st, float* out, size_t n, float value)
+static int f2c_fill_f32(hipStream_t st, float* out, size_t n, float value)
 {
     hipLaunchKernelGGL(k_fill_f32, dim3(stream_blocks(n)), dim3(256), 0, st, out, (long long)n, value);
     HIP_TRY(hipGetLastError());
     return RSLF_OK;
 }
-int rslf::f2c_valid_mask(hipStream_t st, const float* Ce, uint8_t* out, size_t n, float thr)
+static int f2c_valid_mask(hipStream_t st, const float* Ce, uint8_t* out, size_t n, float thr)
 {
     hipLaunchKernelGGL(k_valid_mask, dim3(stream_blocks(n)), dim3(256), 0, st, Ce, out, (long long)n, thr);
     HIP_TRY(hipGetLastError());
     return RSLF_OK;
 }
 
-static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C,
-                                   size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
-                                   const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
-                                   uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats)
+int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                         int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                         const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep)
 {
     if (!ctx || !h_epis || !h_out_map_svu || !h_out_valid_svu || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
@@ -333,97 +296,72 @@ static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* 
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-
-    // the raw (un-normalised) finest level as a dense float volume [V][S][U][C]
-    DevBuf raw;
+    // constructor: rslf_fine_to_coarse.hpp:103-159 -- the level sizes are plan::f2c_pyramid
+    const std::vector<plan::LevelDims> dims = plan::f2c_pyramid(V, U, max_pyr_depth);
+    if (dims.empty())
+        return fail(RSLF_ERR_INVALID_ARG, "light field %dx%d is not larger than _MIN_SPATIAL_DIM: no pyramid level", V, U);
+    const int P = (int)dims.size();
+    DevBuf raw;   // the raw (un-normalised) values of the level at hand, [V][S][U][C]
     HIP_TRY(raw.alloc((size_t)V * S * U * C * sizeof(float)));
     rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, (float*)raw.p);
     if (rc)
         return rc;
 
-    // constructor: rslf_fine_to_coarse.hpp:103-159 -- the level sizes are plan::f2c_pyramid
-    const std::vector<plan::LevelDims> dims = plan::f2c_pyramid(V, U, max_pyr_depth);
-    std::vector<std::unique_ptr<F2cLevel>> levels;
-    DevBuf cur;           // raw volume of the level being built (level 0 borrows `raw`)
-    float* cur_p = (float*)raw.p;
-    for (size_t l = 0; l < dims.size(); l++) {
-        const int dim_v = dims[l].V, dim_u = dims[l].U;
-        levels.emplace_back(new F2cLevel());
-        F2cLevel* lv = levels.back().get();
-        lv->V = dim_v;
-        lv->U = dim_u;
-        lv->params = *p;
-        lv->params.slope_factor = (float)((0.0 + dim_u) / U);             // f2c.hpp:139
-        float scale;
-        rc = f2c_level_scale(ctx, elem, cur_p, (size_t)dim_v * S * dim_u * C, epi_scale_factor, &scale);
-        if (rc)
-            return rc;
-        rc = rslf_volume_create(ctx, dim_v, S, dim_u, C, &lv->vol);
-        if (rc)
-            return rc;
-        rc = rslf_volume_pack_device_f32(lv->vol, cur_p, scale, nullptr);
-        if (rc)
-            return rc;
-        if (l + 1 == dims.size())
-            break;
-        const int v2 = dims[l + 1].V, u2 = dims[l + 1].U;
-        DevBuf next;                                                       // f2c.hpp:145-147: the RAW EPIs go down
-        HIP_TRY(next.alloc((size_t)v2 * S * u2 * C * sizeof(float)));
-        rc = f2c_downsample(ctx, elem, cur_p, dim_v, S, dim_u, C, (float*)next.p);
-        if (rc)
-            return rc;
-        std::swap(cur.p, next.p);   // `next` now frees the previous level's raw copy
-        cur_p = (float*)cur.p;
-    }
-    if (levels.empty())
-        return fail(RSLF_ERR_INVALID_ARG, "light field %dx%d is not larger than _MIN_SPATIAL_DIM: no pyramid level", V, U);
-    const int P = (int)levels.size();
-
-    // run(): rslf_fine_to_coarse.hpp:171-299
+    // run(): rslf_fine_to_coarse.hpp:171-299, each level built just before its sweep; every level keeps its disparities
+    // and validity for the fusion
+    std::vector<DevBuf> depth(P), valid(P);
     int64_t pixels = 0;
     rslf_stats st1;
+    memset(&st1, 0, sizeof(st1));
     for (int l = 0; l < P; l++) {
-        F2cLevel& lv = *levels[l];
+        F2cLevel lv;
+        lv.V = dims[l].V;
+        lv.U = dims[l].U;
+        lv.params = *p;
+        lv.params.slope_factor = (float)((0.0 + lv.U) / U);              // f2c.hpp:139
         const size_t n = (size_t)S * lv.V * lv.U;
-        HIP_TRY(lv.Ce.alloc(n * 4));
-        HIP_TRY(lv.Cd.alloc(n * 4));
-        HIP_TRY(lv.depth.alloc(n * 4));
-        HIP_TRY(lv.rbar.alloc(n * 4 * C));
-        HIP_TRY(lv.mask.alloc(n));
-        HIP_TRY(lv.valid.alloc(n));
-        if (l == 0) {
-            rc = rslf_depth2d_run(ctx, lv.vol, d_min, d_max, dim_d, &lv.params, (float*)lv.Ce.p, (uint8_t*)lv.mask.p, (float*)lv.Cd.p,
-                                  (float*)lv.depth.p, (float*)lv.rbar.p, nullptr, &st1);
-        } else {
-            F2cLevel& up = *levels[l - 1];
-            HIP_TRY(lv.dmin.alloc(n * 4));
-            HIP_TRY(lv.dmax.alloc(n * 4));
-            hipLaunchKernelGGL(k_fill_f32, dim3(stream_blocks(n)), dim3(256), 0, st, (float*)lv.dmin.p, (long long)n, d_min);
-            hipLaunchKernelGGL(k_fill_f32, dim3(stream_blocks(n)), dim3(256), 0, st, (float*)lv.dmax.p, (long long)n, d_max);
-            HIP_TRY(hipGetLastError());
-            rc = rslf_f2c_tighten_bounds(ctx, (const float*)up.depth.p, (const uint8_t*)up.valid.p, S, up.V, up.U, (float*)lv.dmin.p,
-                                         (float*)lv.dmax.p, lv.V, lv.U);
+        rc = f2c_level_scale(ctx, elem, (const float*)raw.p, n * C, epi_scale_factor, &lv.scale);
+        if (rc)
+            return rc;
+        DevBuf next;                                                       // f2c.hpp:145-147: the RAW EPIs go down
+        if (l + 1 < P) {
+            HIP_TRY(next.alloc((size_t)dims[l + 1].V * S * dims[l + 1].U * C * sizeof(float)));
+            rc = f2c_downsample(ctx, elem, (const float*)raw.p, lv.V, S, lv.U, C, (float*)next.p);
             if (rc)
                 return rc;
-            HIP_TRY(hipMemsetAsync(lv.Ce.p, 0, n * 4, st));
-            HIP_TRY(hipMemsetAsync(lv.Cd.p, 0, n * 4, st));
-            HIP_TRY(hipMemsetAsync(lv.depth.p, 0, n * 4, st));
-            HIP_TRY(hipMemsetAsync(lv.rbar.p, 0, n * 4 * C, st));
-            rc = rslf_edge_confidence_2d(ctx, lv.vol, &lv.params, (float*)lv.Ce.p, (uint8_t*)lv.mask.p);
-            if (rc)
-                return rc;
-            rc = rslf_depth_epi_2d(ctx, lv.vol, (const float*)lv.dmin.p, (const float*)lv.dmax.p, d_min, d_max, dim_d,
-                                   (float*)lv.Ce.p, (uint8_t*)lv.mask.p, (float*)lv.Cd.p, (float*)lv.depth.p, (float*)lv.rbar.p,
-                                   &lv.params, nullptr, &st1);
         }
+        DevBuf Ce, dmin, dmax;
+        HIP_TRY(Ce.alloc(n * 4));
+        HIP_TRY(depth[l].alloc(n * 4));
+        HIP_TRY(valid[l].alloc(n));
+        if (l > 0) {
+            HIP_TRY(dmin.alloc(n * 4));
+            HIP_TRY(dmax.alloc(n * 4));
+            rc = f2c_fill_f32(st, (float*)dmin.p, n, d_min);
+            if (!rc)
+                rc = f2c_fill_f32(st, (float*)dmax.p, n, d_max);
+            if (!rc)
+                rc = rslf_f2c_tighten_bounds(ctx, (const float*)depth[l - 1].p, (const uint8_t*)valid[l - 1].p, S, dims[l - 1].V,
+                                             dims[l - 1].U, (float*)dmin.p, (float*)dmax.p, lv.V, lv.U);
+            if (rc)
+                return rc;
+        }
+        lv.raw_vsuc = (const float*)raw.p;
+        lv.dmin_svu = (const float*)dmin.p;
+        lv.dmax_svu = (const float*)dmax.p;
+        lv.Ce_svu = (float*)Ce.p;
+        lv.depth_svu = (float*)depth[l].p;
+        rc = sweep(lv, &st1);
         if (rc)
             return rc;
         pixels += st1.pixels_scanned;
-        // get_valid_depths_mask_s_v_u: the last level accepts everything when asked to (f2c.hpp:157-158)
+        // get_valid_depths_mask_s_v_u (dc.hpp:893-915): C_e > threshold; the last level accepts everything when asked to
+        // (f2c.hpp:157-158)
         const bool all = accept_all_last_scale && l == P - 1;
-        hipLaunchKernelGGL(k_valid_mask, dim3(stream_blocks(n)), dim3(256), 0, st, (const float*)lv.Ce.p, (uint8_t*)lv.valid.p,
-                           (long long)n, all ? -1.0f : p->edge_score_threshold);
-        HIP_TRY(hipGetLastError());
+        rc = f2c_valid_mask(st, (const float*)Ce.p, (uint8_t*)valid[l].p, n, all ? -1.0f : p->edge_score_threshold);
+        if (rc)
+            return rc;
+        std::swap(raw.p, next.p);   // `next` now frees this level's raw volume
     }
 
     // get_results(): rslf_fine_to_coarse.hpp:302-324
@@ -431,10 +369,10 @@ static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* 
     std::vector<const uint8_t*> vp(P);
     std::vector<int> Vp(P), Up(P);
     for (int l = 0; l < P; l++) {
-        dp[l] = (const float*)levels[l]->depth.p;
-        vp[l] = (const uint8_t*)levels[l]->valid.p;
-        Vp[l] = levels[l]->V;
-        Up[l] = levels[l]->U;
+        dp[l] = (const float*)depth[l].p;
+        vp[l] = (const uint8_t*)valid[l].p;
+        Vp[l] = dims[l].V;
+        Up[l] = dims[l].U;
     }
     const size_t n0 = (size_t)S * V * U;
     DevBuf omap, ovalid;
@@ -454,6 +392,32 @@ static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* 
         stats->units = pixels * dim_d;
     }
     return RSLF_OK;
+}
+
+// FineToCoarse on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run.
+static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C,
+                                   size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                   const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
+                                   uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats)
+{
+    auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
+        const size_t n = (size_t)S * lv.V * lv.U;
+        DevBuf Cd, rbar, mask;
+        HIP_TRY(Cd.alloc(n * 4));
+        HIP_TRY(rbar.alloc(n * 4 * C));
+        HIP_TRY(mask.alloc(n));
+        rslf_volume* vol = nullptr;
+        int rc = rslf_volume_create(ctx, lv.V, S, lv.U, C, &vol);
+        if (!rc)
+            rc = rslf_volume_pack_device_f32(vol, lv.raw_vsuc, lv.scale, nullptr);
+        if (!rc)
+            rc = depth2d_run(ctx, vol, lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, (uint8_t*)mask.p,
+                             (float*)Cd.p, lv.depth_svu, (float*)rbar.p, nullptr, level_stats);
+        rslf_volume_destroy(vol);
+        return rc;
+    };
+    return fine_to_coarse(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, sweep);
 }
 
 extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,

@@ -5,10 +5,10 @@
 //   rslf_core.hip         errors, contexts, volumes, host upload / device pack (K0)
 //   rslf_pile.hip         the hot path: edge confidence (K1), scan (K2), selective median (K3), Depth1DComputer(_pile)
 //   rslf_chip_a/b/c.hip   the on-chip scan kernel's instantiations, one per rung of its ladder (launched by rslf_pile.hip)
-//   rslf_sweep.hip        the 2-D sweep and its propagation (K4)
-//   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the native level loop
+//   rslf_sweep.hip        the 2-D sweep and its propagation (K4), Depth2DComputer::run
+//   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the one native level loop
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
-//   rslf_multi_sweep.hip  the sharded sweep and fine-to-coarse behind the C-ABI
+//   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
 #pragma once
 
@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <new>
 #include <string>
 #include <thread>
@@ -337,18 +338,32 @@ void fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_stats* st
 int scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf_params* p, const int* rows, int n_rows);
 int sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const ScanInputs& sparse);
 
-// rslf_f2c.hip: the per-type steps and small elementwise launches the multi-device form shares
-// The finest level's raw values from host EPIs of element type e into the dense float volume d_raw [V][S][U][C]
-// (integer types widened on the device); synchronises.
-int f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
-                   float* d_raw);
-// The level rule of FineToCoarse on element type e: the level's epi_scale_factor (CV_8U: 255; otherwise the given factor
-// or, when < 0, the level's own max -- dc.hpp:671-705) and the halving that keeps the Mats' type
-// (fine_to_coarse_core.cpp:22-41: rslf_downsample_epis_u8 / _u16 / _f32).
-int f2c_level_scale(rslf_ctx* ctx, Elem e, const float* d_raw, size_t n, float epi_scale_factor, float* scale);
-int f2c_downsample(rslf_ctx* ctx, Elem e, const float* d_in_vsuc, int V, int S, int U, int C, float* d_out_vsuc);
-int f2c_fill_f32(hipStream_t st, float* out, size_t n, float value);
-int f2c_valid_mask(hipStream_t st, const float* Ce, uint8_t* out, size_t n, float thr);
+// rslf_sweep.hip
+// Depth2DComputer::run (dc.hpp:748-805) on device planes; d_dmin_svu / d_dmax_svu: per-pixel ranges (a fine-to-coarse
+// level, dc.hpp:201-203), or both NULL for the scalar range.
+int depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
+                int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats);
+
+// rslf_f2c.hip
+// One level of FineToCoarse as its sweep sees it, every pointer on the context's device.
+struct F2cLevel {
+    int V = 0, U = 0;
+    rslf_params params;                 // slope_factor set (f2c.hpp:139)
+    float scale = 1.0f;                 // the level's epi_scale_factor (dc.hpp:671-705)
+    const float* raw_vsuc = nullptr;    // [V][S][U][C] raw values of the level
+    const float* dmin_svu = nullptr;    // [S][V][U] ranges tightened from the level above; NULL on level 0
+    const float* dmax_svu = nullptr;
+    float* Ce_svu = nullptr;            // [S][V][U] results the sweep fills: edge confidence, disparities
+    float* depth_svu = nullptr;
+};
+// FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from host EPIs of element type elem
+// into host planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which
+// reports the level's stats.
+int fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
+                   float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                   int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                   const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep);
 
 // rslf_multi.hip
 void multi_free_dev(rslf_multi::Dev& d);

@@ -1,10 +1,10 @@
-// librslf_hip.so, unit 9 of 9: the 2-D sweep and fine-to-coarse sharded by scanline over the devices of one process, behind
-// the C-ABI -- one neighbour exchange of boundary rows per visit (the path's one real exchange step).  C-ABI: include/rslf_hip.h.
+// librslf_hip.so, unit 9 of 9: the 2-D sweep sharded by scanline over the devices of one process, behind the C-ABI -- one
+// neighbour exchange of boundary rows per visit (the path's one real exchange step) -- and fine-to-coarse with every level
+// swept so (the level loop itself is rslf_f2c.hip's).  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <deque>
 
 using namespace rslf;
 
@@ -264,139 +264,30 @@ int multi_depth2d(rslf_multi* m, const void* const* h_epis, Elem elem, size_t ro
 
 }  // namespace
 
-// FineToCoarse<T> (rslf_fine_to_coarse.hpp:103-324) over the context's devices.  Where the time goes -- every level's 2-D
-// sweep -- runs sharded (multi_depth2d, with the level's tightened per-pixel ranges); the pyramid, the bound tightening
-// and the fusion, cheap whole-image passes with non-local footprints, run on the first device, where every level's raw
-// volume, ranges, disparities and confidences stay: the devices take their rows from there and leave their results there
-// by peer copies (FirstDevicePlanes).  The host sees the EPIs going up once and the fused map coming down.
+// FineToCoarse<T> (rslf_fine_to_coarse.hpp:103-324) over the object's devices: the level loop of rslf_f2c.hip on the first
+// device, where each level's raw volume, ranges, disparities and confidences live; each level's 2-D sweep -- where the
+// time goes -- runs sharded (multi_depth2d), the devices taking their rows from there and leaving their results there by
+// peer copies (FirstDevicePlanes).  The host sees the EPIs going up once and the fused map coming down.
 static int multi_fine_to_coarse(rslf_multi* m, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
                                 float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                 int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
                                 rslf_stats* stats)
 {
-    if (!m || !h_epis || !h_out_map_svu || !h_out_valid_svu || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
+    if (!m)
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
-    int rc = check_params(p);
-    if (rc)
-        return rc;
     rslf_ctx* ctx = m->devs[0].ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
-    struct Level {
-        int V = 0, U = 0;
-        float scale = 1.0f;
-        rslf_params params;
-        DevBuf raw;                 // [V][S][U][C] raw values, on the first device
-        DevBuf Ce, depth, valid;    // [S][V][U], on the first device
+    auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
+        const FirstDevicePlanes first{lv.raw_vsuc, lv.dmin_svu, lv.dmax_svu, lv.Ce_svu, lv.depth_svu};
+        HIP_TRY(hipStreamSynchronize(ctx->stream));   // what the other devices' streams are about to read is complete
+        int rc = multi_depth2d(m, nullptr, Elem::F32, 0, lv.V, S, lv.U, C, lv.scale, d_min, d_max, dim_d, &lv.params, nullptr, nullptr,
+                               nullptr, nullptr, nullptr, nullptr, level_stats, &first);
+        if (rc)
+            return rc;
+        HIP_TRY(hipSetDevice(ctx->device));
+        return RSLF_OK;
     };
-    // constructor (f2c.hpp:103-159): the pyramid (plan::f2c_pyramid) on the first device, every level's RAW volume kept there
-    const std::vector<plan::LevelDims> dims = plan::f2c_pyramid(V, U, max_pyr_depth);
-    if (dims.empty())
-        return fail(RSLF_ERR_INVALID_ARG, "light field %dx%d is not larger than _MIN_SPATIAL_DIM: no pyramid level", V, U);
-    std::deque<Level> levels(dims.size());   // (a deque: the levels own device buffers and must not move)
-    {
-        Level& l0 = levels.front();
-        HIP_TRY(l0.raw.alloc((size_t)V * S * U * C * sizeof(float)));
-        rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, (float*)l0.raw.p);
-        if (rc)
-            return rc;
-    }
-    for (size_t l = 0; l < dims.size(); l++) {
-        Level& lv = levels[l];
-        const int dim_v = dims[l].V, dim_u = dims[l].U;
-        lv.V = dim_v;
-        lv.U = dim_u;
-        lv.params = *p;
-        lv.params.slope_factor = (float)((0.0 + dim_u) / U);              // f2c.hpp:139
-        rc = f2c_level_scale(ctx, elem, (const float*)lv.raw.p, (size_t)dim_v * S * dim_u * C, epi_scale_factor, &lv.scale);
-        if (rc)
-            return rc;
-        if (l + 1 == dims.size())
-            break;
-        Level& nx = levels[l + 1];
-        HIP_TRY(nx.raw.alloc((size_t)dims[l + 1].V * S * dims[l + 1].U * C * sizeof(float)));   // f2c.hpp:145-147: the RAW EPIs go down
-        rc = f2c_downsample(ctx, elem, (const float*)lv.raw.p, dim_v, S, dim_u, C, (float*)nx.raw.p);
-        if (rc)
-            return rc;
-    }
-    const int P = (int)levels.size();
-
-    // run(): f2c.hpp:171-299 -- the sweeps over all devices, the tightening on the first
-    int64_t pixels = 0;
-    rslf_stats st1;
-    memset(&st1, 0, sizeof(st1));
-    for (int l = 0; l < P; l++) {
-        Level& lv = levels[(size_t)l];
-        const size_t n = (size_t)S * lv.V * lv.U;
-        HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(lv.Ce.alloc(n * 4));
-        HIP_TRY(lv.depth.alloc(n * 4));
-        HIP_TRY(lv.valid.alloc(n));
-        DevBuf d_lo, d_hi;
-        FirstDevicePlanes first;
-        first.raw_vsuc = (const float*)lv.raw.p;
-        first.Ce_svu = (float*)lv.Ce.p;
-        first.depth_svu = (float*)lv.depth.p;
-        if (l > 0) {
-            Level& up = levels[(size_t)l - 1];
-            HIP_TRY(d_lo.alloc(n * 4));
-            HIP_TRY(d_hi.alloc(n * 4));
-            rc = f2c_fill_f32(st, (float*)d_lo.p, n, d_min);
-            if (!rc)
-                rc = f2c_fill_f32(st, (float*)d_hi.p, n, d_max);
-            if (rc)
-                return rc;
-            rc = rslf_f2c_tighten_bounds(ctx, (const float*)up.depth.p, (const uint8_t*)up.valid.p, S, up.V, up.U, (float*)d_lo.p,
-                                         (float*)d_hi.p, lv.V, lv.U);
-            if (rc)
-                return rc;
-            first.dmin_svu = (const float*)d_lo.p;
-            first.dmax_svu = (const float*)d_hi.p;
-        }
-        HIP_TRY(hipStreamSynchronize(st));   // what the other devices' streams are about to read is complete
-        rc = multi_depth2d(m, nullptr, Elem::F32, 0, lv.V, S, lv.U, C, lv.scale, d_min, d_max, dim_d, &lv.params, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, &st1, &first);
-        if (rc)
-            return rc;
-        pixels += st1.pixels_scanned;
-        // get_valid_depths_mask_s_v_u (dc.hpp:893-915): C_e > threshold; the last level accepts everything when asked to
-        HIP_TRY(hipSetDevice(ctx->device));
-        const bool all = accept_all_last_scale && l == P - 1;
-        rc = f2c_valid_mask(st, (const float*)lv.Ce.p, (uint8_t*)lv.valid.p, n, all ? -1.0f : p->edge_score_threshold);
-        if (rc)
-            return rc;
-        lv.raw.release();   // the level's raw volume has been taken by every device
-    }
-
-    // get_results(): f2c.hpp:302-324 on the first device
-    std::vector<const float*> dp((size_t)P);
-    std::vector<const uint8_t*> vp((size_t)P);
-    std::vector<int> Vp((size_t)P), Up((size_t)P);
-    for (int l = 0; l < P; l++) {
-        dp[(size_t)l] = (const float*)levels[(size_t)l].depth.p;
-        vp[(size_t)l] = (const uint8_t*)levels[(size_t)l].valid.p;
-        Vp[(size_t)l] = levels[(size_t)l].V;
-        Up[(size_t)l] = levels[(size_t)l].U;
-    }
-    const size_t n0 = (size_t)S * V * U;
-    DevBuf omap, ovalid;
-    HIP_TRY(omap.alloc(n0 * 4));
-    HIP_TRY(ovalid.alloc(n0));
-    rc = rslf_f2c_fuse(ctx, dp.data(), vp.data(), Vp.data(), Up.data(), P, S, (float*)omap.p, (uint8_t*)ovalid.p);
-    if (rc)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.p, n0 * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_out_valid_svu, ovalid.p, n0, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (n_levels)
-        *n_levels = P;
-    if (stats) {
-        *stats = st1;
-        stats->pixels_scanned = pixels;
-        stats->units = pixels * dim_d;
-    }
-    return RSLF_OK;
+    return fine_to_coarse(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, sweep);
 }
 
 extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* const* h_epis, int is_u8, int V, int S, int U, int C,

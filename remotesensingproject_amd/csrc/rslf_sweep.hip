@@ -273,9 +273,9 @@ extern "C" int rslf_depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const fl
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
-                                float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
-                                uint8_t* d_scan_mask_svu, rslf_stats* stats) RSLF_API_TRY
+int rslf::depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
+                      int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                      float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -290,7 +290,44 @@ extern "C" int rslf_depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmi
     int rc = rslf_edge_confidence_2d(ctx, vol, p, d_Ce_svu, d_Ce_mask_svu);   // dc.hpp:772
     if (rc)
         return rc;
-    return rslf_depth_epi_2d(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
+    return rslf_depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
                              d_rbar_svu, p, d_scan_mask_svu, stats);
+}
+
+extern "C" int rslf_depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
+                                uint8_t* d_scan_mask_svu, rslf_stats* stats) RSLF_API_TRY
+{
+    return depth2d_run(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                       d_scan_mask_svu, stats);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                     float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                                     float* h_rbar_svu, rslf_stats* stats) RSLF_API_TRY
+{
+    if (!ctx || !vol)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = (size_t)vol->S * vol->V * vol->U;
+    DevBuf Ce, Cd, depth, rbar, mask;
+    HIP_TRY(Ce.alloc(n * 4));
+    HIP_TRY(Cd.alloc(n * 4));
+    HIP_TRY(depth.alloc(n * 4));
+    HIP_TRY(rbar.alloc(n * 4 * vol->C));
+    HIP_TRY(mask.alloc(n));
+    int rc = rslf_depth2d_run(ctx, vol, dmin, dmax, dim_d, p, (float*)Ce.p, (uint8_t*)mask.p, (float*)Cd.p, (float*)depth.p,
+                              (float*)rbar.p, nullptr, stats);
+    if (rc)
+        return rc;
+    hipStream_t st = ctx->stream;
+    if (h_Ce_svu) HIP_TRY(hipMemcpyAsync(h_Ce_svu, Ce.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_Ce_mask_svu) HIP_TRY(hipMemcpyAsync(h_Ce_mask_svu, mask.p, n, hipMemcpyDeviceToHost, st));
+    if (h_Cd_svu) HIP_TRY(hipMemcpyAsync(h_Cd_svu, Cd.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_depth_svu) HIP_TRY(hipMemcpyAsync(h_depth_svu, depth.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_rbar_svu) HIP_TRY(hipMemcpyAsync(h_rbar_svu, rbar.p, n * 4 * vol->C, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RSLF_OK;
 }
 RSLF_API_CATCH

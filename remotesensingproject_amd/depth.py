@@ -14,6 +14,7 @@ of include/rslf_hip.h.  No CPU path exists here.
 from __future__ import annotations
 
 import atexit
+import copy
 import ctypes as C
 import sys
 from dataclasses import dataclass
@@ -415,6 +416,23 @@ class Depth1DComputer_pile:
         )
 
 
+def host_epis(epis: Sequence[np.ndarray], dtype=None):
+    """A host EPI list (the reference's Vec<Mat>: V arrays [S,U] or [S,U,3]) as the C-ABI takes it: (the arrays, to be
+    kept alive over the call; their pointers; their element type; V, S, U, C).  Every EPI goes as `dtype`, by default
+    the first one's, and must have the first one's shape."""
+    dt = np.asarray(epis[0]).dtype if dtype is None else np.dtype(dtype)
+    if dt not in (np.uint8, np.uint16, np.float32):
+        raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
+    # a thousand EPIs: no per-array conversions or ctypes objects where none are needed
+    keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
+    S, U = keep[0].shape[0], keep[0].shape[1]
+    C_ = 1 if keep[0].ndim == 2 else keep[0].shape[2]
+    if any(e.shape != keep[0].shape for e in keep):
+        raise ValueError("every EPI must have the shape of the first, %s" % (keep[0].shape,))
+    ptrs = (C.c_void_p * len(keep))(*[e.__array_interface__["data"][0] for e in keep])
+    return keep, ptrs, dt, len(keep), S, U, C_
+
+
 class MultiDevice:
     """rslf_multi: Depth1DComputer_pile's constructor + run() + result Mats in one call on HOST arrays, the scanlines cut
     into one block per device (and every block into chunks whose upload, kernels and download overlap).  Host planes
@@ -442,18 +460,7 @@ class MultiDevice:
     def depth1d_pile(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, s_hat: int = -1,
                      epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None) -> dict:
         """epis: the reference's Vec<Mat> -- V arrays [S,U] or [S,U,3], all uint8, all uint16 or all float32."""
-        first = np.asarray(epis[0])
-        dt = first.dtype
-        if dt not in (np.uint8, np.uint16, np.float32):
-            raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
-        # keeps the buffers alive over the call; a thousand EPIs: no per-array conversions or ctypes objects where none are needed
-        keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
-        V = len(keep)
-        S, U = keep[0].shape[0], keep[0].shape[1]
-        C_ = 1 if keep[0].ndim == 2 else keep[0].shape[2]
-        if any(e.shape != keep[0].shape for e in keep):
-            raise ValueError("every EPI must have the shape of the first, %s" % (keep[0].shape,))
-        ptrs = (C.c_void_p * V)(*[e.__array_interface__["data"][0] for e in keep])
+        keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
         out = dict(edge_confidence=np.empty((V, U), np.float32), edge_mask=np.empty((V, U), np.uint8),
                    disp_confidence=np.empty((V, U), np.float32), depth=np.empty((V, U), np.float32),
                    rbar=np.empty((V, U, C_), np.float32), depth_idx=np.empty((V, U), np.int32),
@@ -481,17 +488,7 @@ class MultiDevice:
         """Depth2DComputer (constructor + run + getters) over this object's devices: the 2-D sweep cut into one block of
         scanlines per device, the neighbours' boundary rows exchanged by peer copy on every visit
         (rslf_multi_depth2d_run_f32 / _u8 / _u16).  Host EPIs in, numpy planes [S, V, U] out."""
-        first = np.asarray(epis[0])
-        dt = first.dtype
-        if dt not in (np.uint8, np.uint16, np.float32):
-            raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
-        keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
-        V = len(keep)
-        S, U = keep[0].shape[0], keep[0].shape[1]
-        C_ = 1 if keep[0].ndim == 2 else keep[0].shape[2]
-        if any(e.shape != keep[0].shape for e in keep):
-            raise ValueError("every EPI must have the shape of the first, %s" % (keep[0].shape,))
-        ptrs = (C.c_void_p * V)(*[e.__array_interface__["data"][0] for e in keep])
+        keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
         out = dict(edge_confidence=np.empty((S, V, U), np.float32), edge_mask=np.empty((S, V, U), np.uint8),
                    disp_confidence=np.empty((S, V, U), np.float32), depth=np.empty((S, V, U), np.float32),
                    rbar=np.empty((S, V, U, C_), np.float32), scan_mask=np.empty((S, V, U), np.uint8))
@@ -516,15 +513,7 @@ class MultiDevice:
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
-        first = np.asarray(epis[0])
-        dt = first.dtype
-        if dt not in (np.uint8, np.uint16, np.float32):
-            raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
-        keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
-        V = len(keep)
-        S, U = keep[0].shape[0], keep[0].shape[1]
-        C_ = 1 if keep[0].ndim == 2 else keep[0].shape[2]
-        ptrs = (C.c_void_p * V)(*[e.__array_interface__["data"][0] for e in keep])
+        keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
         p = (parameters or Depth1DParameters()).to_c()
@@ -544,11 +533,7 @@ class MultiDevice:
                                 s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None) -> dict:
         """The same with the result planes left on `out_device` as CUDA tensors (float32 EPIs): every worker copies its
         rows there with a peer copy (rslf_multi_depth1d_pile_f32_dev)."""
-        keep = [np.ascontiguousarray(e, dtype=np.float32) for e in epis]
-        V = len(keep)
-        S, U = keep[0].shape[0], keep[0].shape[1]
-        C_ = 1 if keep[0].ndim == 2 else keep[0].shape[2]
-        ptrs = (C.c_void_p * V)(*[e.ctypes.data for e in keep])
+        keep, ptrs, _, V, S, U, C_ = host_epis(epis, np.float32)
         dev = torch.device("cuda", out_device)
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         out = dict(edge_confidence=mk((V, U), torch.float32), edge_mask=mk((V, U), torch.uint8), disp_confidence=mk((V, U), torch.float32),
@@ -762,8 +747,7 @@ def downsample_EPIs(raw_vsuc: torch.Tensor, ctx: Context | None = None, is_u8: b
 
 
 def f2c_level(raw_vsuc: torch.Tensor, dtype, epi_scale_factor: float, ctx: Context) -> tuple[float, torch.Tensor]:
-    """The per-level rule of FineToCoarse for a light field of element type `dtype` (FineToCoarse and
-    sharding.ShardedFineToCoarse): the level's epi_scale_factor -- Depth2DComputer's constructor normalises ITS input,
+    """The per-level rule of FineToCoarse for a light field of element type `dtype` (f2c_pyramid): the level's epi_scale_factor -- Depth2DComputer's constructor normalises ITS input,
     uchar by 1/255, any other depth by the level's own max unless a factor was given (dc.hpp:671-705) -- and the next
     level, downsampled in the field's own arithmetic (f2c.hpp:145-147).  Returns (scale, next raw level)."""
     dt = field_dtype(dtype)
@@ -779,6 +763,62 @@ def f2c_level(raw_vsuc: torch.Tensor, dtype, epi_scale_factor: float, ctx: Conte
     return scale, downsample_EPIs(raw_vsuc, ctx, dtype=dt)
 
 
+def f2c_input(epis, ctx: Context) -> tuple[torch.Tensor, np.dtype]:
+    """FineToCoarse's input -- a list of V arrays [S,U] / [S,U,3] or a dense array [V,S,U(,C)] -- as the raw float32 volume
+    [V,S,U,C] on the context's device, and the element type its pyramid keeps (field_dtype)."""
+    a = np.stack([np.asarray(e) for e in epis]) if isinstance(epis, (list, tuple)) else np.asarray(epis)
+    if a.ndim == 3:
+        a = a[..., None]
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(ctx.device), field_dtype(a.dtype)
+
+
+def f2c_pyramid(raw: torch.Tensor, dtype, epi_scale_factor: float, parameters: Depth1DParameters, max_pyr_depth: int, ctx: Context):
+    """The levels of FineToCoarse's constructor (f2c.hpp:103-159), finest first, each built as it is asked for:
+    (V, U, the parameters with the level's slope factor, the level's scale, its raw volume [V,S,U,C])."""
+    start_dim_u = raw.shape[2]
+    if max_pyr_depth < 1:
+        max_pyr_depth = 1 << 30
+    counter = 0
+    while raw.shape[0] > _MIN_SPATIAL_DIM and raw.shape[2] > _MIN_SPATIAL_DIM and counter < max_pyr_depth:   # f2c.hpp:130
+        counter += 1
+        par = copy.copy(parameters)
+        par.par_slope_factor = float(np.float32((0.0 + raw.shape[2]) / start_dim_u))                     # f2c.hpp:139
+        scale, nxt = f2c_level(raw, dtype, epi_scale_factor, ctx)
+        yield raw.shape[0], raw.shape[2], par, scale, raw
+        raw = nxt                                                                                       # f2c.hpp:145-147
+    if counter == 0:
+        raise ValueError("light field smaller than _MIN_SPATIAL_DIM: no pyramid level")
+
+
+def f2c_ranges(ctx: Context, depth_up: torch.Tensor, valid_up: torch.Tensor, V: int, U: int, d_min: float,
+               d_max: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """The per-pixel hypothesis ranges [S,V,U] of a level below the finest: [d_min, d_max] tightened around the valid
+    disparities of the level above, depth_up / valid_up [S,V_up,U_up] (f2c.hpp:202-294)."""
+    S, V_up, U_up = depth_up.shape
+    lo = torch.full((S, V, U), d_min, dtype=torch.float32, device=ctx.device)
+    hi = torch.full((S, V, U), d_max, dtype=torch.float32, device=ctx.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_f2c_tighten_bounds(ctx._h, _ptr(depth_up), _ptr(valid_up), S, V_up, U_up, _ptr(lo), _ptr(hi), V, U),
+          "rslf_f2c_tighten_bounds")
+    return lo, hi
+
+
+def f2c_fuse(ctx: Context, depths: Sequence[torch.Tensor], valids: Sequence[torch.Tensor]) -> tuple[torch.Tensor, torch.Tensor]:
+    """get_results() (f2c.hpp:302-324): the levels' disparities and validity masks [S,V_p,U_p], finest first, fused from
+    coarse to fine -> (out_map_s_v_u [S,V,U] f32, out_validity_s_v_u [S,V,U] u8) at the finest scale."""
+    P = len(depths)
+    S, V, U = depths[0].shape
+    dp = (C.c_void_p * P)(*[t.data_ptr() for t in depths])
+    vp = (C.c_void_p * P)(*[t.data_ptr() for t in valids])
+    Vp = (C.c_int * P)(*[t.shape[1] for t in depths])
+    Up = (C.c_int * P)(*[t.shape[2] for t in depths])
+    out_map = torch.empty((S, V, U), dtype=torch.float32, device=ctx.device)
+    out_valid = torch.empty((S, V, U), dtype=torch.uint8, device=ctx.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_f2c_fuse(ctx._h, dp, vp, Vp, Up, P, S, _ptr(out_map), _ptr(out_valid)), "rslf_f2c_fuse")
+    return out_map, out_valid
+
+
 class FineToCoarse:
     """rslf::FineToCoarse<T> (include/rslf_fine_to_coarse.hpp:26-81, :103-324): a pyramid of Depth2DComputers,
     each level halving (v, u) -- never s --, with slope_factor = U_p / U_0, per-pixel hypothesis ranges
@@ -791,78 +831,38 @@ class FineToCoarse:
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                  ctx: Context | None = None):
-        import copy
         self.m_parameters = parameters or Depth1DParameters.get_default()
         ctx = ctx or default_context()
-        dev = ctx.device
-        a = np.stack([np.asarray(e) for e in epis]) if isinstance(epis, (list, tuple)) else np.asarray(epis)
-        if a.ndim == 3:
-            a = a[..., None]
-        self._dtype = field_dtype(a.dtype)
-        raw = torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
-        start_dim_u = raw.shape[2]
-        if max_pyr_depth < 1:
-            max_pyr_depth = 1 << 30
         self.m_computers: list[Depth2DComputer] = []
         self.m_parameter_instances: list[Depth1DParameters] = []
-        dim_v, dim_u, counter = raw.shape[0], raw.shape[2], 0
-        while dim_v > _MIN_SPATIAL_DIM and dim_u > _MIN_SPATIAL_DIM and counter < max_pyr_depth:   # f2c.hpp:130
-            counter += 1
-            new_parameters = copy.copy(self.m_parameters)
-            new_parameters.par_slope_factor = float(np.float32((0.0 + dim_u) / start_dim_u))       # f2c.hpp:139
-            scale, nxt = f2c_level(raw, self._dtype, epi_scale_factor, ctx)
+        for _, _, par, scale, raw in f2c_pyramid(*f2c_input(epis, ctx), epi_scale_factor, self.m_parameters, max_pyr_depth, ctx):
             vol = Volume.from_dense(raw, scale, ctx)
-            self.m_computers.append(Depth2DComputer(vol, d_min, d_max, dim_d, parameters=new_parameters))
-            self.m_parameter_instances.append(new_parameters)
-            raw = nxt                                                                              # f2c.hpp:145-147
-            dim_v, dim_u = raw.shape[0], raw.shape[2]
-        if not self.m_computers:
-            raise ValueError("light field smaller than _MIN_SPATIAL_DIM: no pyramid level")
+            self.m_computers.append(Depth2DComputer(vol, d_min, d_max, dim_d, parameters=par))
+            self.m_parameter_instances.append(par)
         if accept_all_last_scale:
             self.m_computers[-1].set_accept_all(True)                                              # f2c.hpp:157-158
         self._dmin, self._dmax = float(d_min), float(d_max)
 
     def run(self) -> None:
         """f2c.hpp:171-299."""
-        L = _lib.lib()
         for p, comp in enumerate(self.m_computers):
-            vol = comp.m_epis
-            S, V, U = vol.S, vol.V, vol.U
             if p == 0:
                 comp.run(want_stats=True)
-            else:
-                up = self.m_computers[p - 1]
-                dev = vol.ctx.device
-                dmin = torch.full((S, V, U), self._dmin, dtype=torch.float32, device=dev)
-                dmax = torch.full((S, V, U), self._dmax, dtype=torch.float32, device=dev)
-                mask_up = up.get_valid_depths_mask_s_v_u()
-                vol.ctx.use_current_stream()
-                check(L.rslf_f2c_tighten_bounds(vol.ctx._h, _ptr(up.m_best_depth_s_v_u), _ptr(mask_up), S, up.m_epis.V, up.m_epis.U,
-                                                _ptr(dmin), _ptr(dmax), V, U), "rslf_f2c_tighten_bounds")
-                comp.m_dmin_s_v_u, comp.m_dmax_s_v_u = dmin, dmax
-                # Depth2DComputer::run with per-pixel ranges (edit_dmin / edit_dmax, dc.hpp:201-203)
-                for t in (comp.m_edge_confidence_s_v_u, comp.m_disp_confidence_s_v_u, comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u):
-                    t.zero_()
-                comp.m_edge_confidence_mask_s_v_u = compute_2D_edge_confidence(vol, comp.m_edge_confidence_s_v_u, comp.m_parameters)
-                comp.stats = compute_2D_depth_epi(vol, dmin, dmax, comp.m_dim_d, comp.m_edge_confidence_s_v_u,
-                                                  comp.m_edge_confidence_mask_s_v_u, comp.m_disp_confidence_s_v_u,
-                                                  comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u, comp.m_parameters,
-                                                  scan_mask_s_v_u=comp.m_scan_mask_s_v_u, want_stats=True)
+                continue
+            vol, up = comp.m_epis, self.m_computers[p - 1]
+            dmin, dmax = f2c_ranges(vol.ctx, up.m_best_depth_s_v_u, up.get_valid_depths_mask_s_v_u(), vol.V, vol.U, self._dmin, self._dmax)
+            comp.m_dmin_s_v_u, comp.m_dmax_s_v_u = dmin, dmax
+            # Depth2DComputer::run with per-pixel ranges (edit_dmin / edit_dmax, dc.hpp:201-203)
+            for t in (comp.m_edge_confidence_s_v_u, comp.m_disp_confidence_s_v_u, comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u):
+                t.zero_()
+            comp.m_edge_confidence_mask_s_v_u = compute_2D_edge_confidence(vol, comp.m_edge_confidence_s_v_u, comp.m_parameters)
+            comp.stats = compute_2D_depth_epi(vol, dmin, dmax, comp.m_dim_d, comp.m_edge_confidence_s_v_u,
+                                              comp.m_edge_confidence_mask_s_v_u, comp.m_disp_confidence_s_v_u,
+                                              comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u, comp.m_parameters,
+                                              scan_mask_s_v_u=comp.m_scan_mask_s_v_u, want_stats=True)
 
     def get_results(self):
         """f2c.hpp:302-324 -> (out_map_s_v_u [S,V,U] f32, out_validity_s_v_u [S,V,U] u8) at the finest scale."""
         comps = self.m_computers
-        P, S = len(comps), comps[0].m_epis.S
-        disp = [c.m_best_depth_s_v_u.contiguous() for c in comps]
-        valid = [c.get_valid_depths_mask_s_v_u().contiguous() for c in comps]
-        dp = (C.c_void_p * P)(*[t.data_ptr() for t in disp])
-        vp = (C.c_void_p * P)(*[t.data_ptr() for t in valid])
-        Vp = (C.c_int * P)(*[c.m_epis.V for c in comps])
-        Up = (C.c_int * P)(*[c.m_epis.U for c in comps])
-        dev = comps[0].m_epis.ctx.device
-        out_map = torch.empty((S, comps[0].m_epis.V, comps[0].m_epis.U), dtype=torch.float32, device=dev)
-        out_valid = torch.empty((S, comps[0].m_epis.V, comps[0].m_epis.U), dtype=torch.uint8, device=dev)
-        ctx = comps[0].m_epis.ctx
-        ctx.use_current_stream()
-        check(_lib.lib().rslf_f2c_fuse(ctx._h, dp, vp, Vp, Up, P, S, _ptr(out_map), _ptr(out_valid)), "rslf_f2c_fuse")
-        return out_map, out_valid
+        return f2c_fuse(comps[0].m_epis.ctx, [c.m_best_depth_s_v_u.contiguous() for c in comps],
+                        [c.get_valid_depths_mask_s_v_u().contiguous() for c in comps])

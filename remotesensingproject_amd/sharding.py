@@ -453,28 +453,14 @@ class ShardedFineToCoarse:
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, rank: int, world: int, epi_scale_factor: float = -1.0,
                  parameters=None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True, ctx=None, group=None):
-        import copy
         from . import depth as rs
         self.rs, self.rank, self.world, self.group = rs, int(rank), int(world), group
         self.m_parameters = parameters or rs.Depth1DParameters.get_default()
         self.ctx = ctx or rs.default_context()
-        dev = self.ctx.device
-        a = np.stack([np.asarray(e) for e in epis]) if isinstance(epis, (list, tuple)) else np.asarray(epis)
-        if a.ndim == 3:
-            a = a[..., None]
-        dtype = rs.field_dtype(a.dtype)
-        raw = torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
-        start_dim_u = raw.shape[2]
-        if max_pyr_depth < 1:
-            max_pyr_depth = 1 << 30
         self.levels: List[dict] = []
-        dim_v, dim_u, counter = raw.shape[0], raw.shape[2], 0
-        while dim_v > rs._MIN_SPATIAL_DIM and dim_u > rs._MIN_SPATIAL_DIM and counter < max_pyr_depth:   # f2c.hpp:130
-            counter += 1
-            par = copy.copy(self.m_parameters)
-            par.par_slope_factor = float(np.float32((0.0 + dim_u) / start_dim_u))                          # f2c.hpp:139
-            # the level's scale (by default the own maximum of the WHOLE level, dc.hpp:671-705) and the next level
-            scale, nxt = rs.f2c_level(raw, dtype, epi_scale_factor, self.ctx)
+        # every level's scale is by default the own maximum of the WHOLE level (dc.hpp:671-705)
+        for dim_v, dim_u, par, scale, raw in rs.f2c_pyramid(*rs.f2c_input(epis, self.ctx), epi_scale_factor, self.m_parameters,
+                                                            max_pyr_depth, self.ctx):
             # a coarse level whose blocks would be thinner than the halo they must fill is small enough to run whole
             # on every rank
             replicated = self.world == 1 or dim_v // self.world < max(1, halo_rows(par.par_median_filter_size, par.par_edge_confidence_opening_size))
@@ -483,20 +469,14 @@ class ShardedFineToCoarse:
             vol = rs.Volume.from_dense(raw[shard.rows].contiguous(), scale, self.ctx)
             self.levels.append(dict(V=dim_v, U=dim_u, par=par, shard=shard, vol=vol, sweep=None, depth=None, valid=None, accept_all=False,
                                     replicated=replicated))
-            raw = nxt                                                                                      # f2c.hpp:145-147
-            dim_v, dim_u = raw.shape[0], raw.shape[2]
-        if not self.levels:
-            raise ValueError("light field smaller than _MIN_SPATIAL_DIM: no pyramid level")
         if accept_all_last_scale:
             self.levels[-1]["accept_all"] = True                                                           # f2c.hpp:157-158
         self._dmin, self._dmax, self._dim_d = float(d_min), float(d_max), int(dim_d)
-        self.S = self.levels[0]["vol"].S
 
     # -- steps (a lock-step harness drives them for several ranks in one process) ---------------------------------------
     def begin_level(self, p: int) -> ShardedDepth2D:
         """The sweep of level p over this rank's rows; levels below the finest take their per-pixel ranges from the
         gathered planes of level p - 1 (f2c.hpp:202-294)."""
-        from . import _lib
         lv = self.levels[p]
         if p == 0:
             lo, hi = self._dmin, self._dmax
@@ -504,13 +484,7 @@ class ShardedFineToCoarse:
             up = self.levels[p - 1]
             if up["depth"] is None:
                 raise RuntimeError("level %d needs the gathered planes of level %d" % (p, p - 1))
-            dev = self.ctx.device
-            lo = torch.full((self.S, lv["V"], lv["U"]), self._dmin, dtype=torch.float32, device=dev)
-            hi = torch.full((self.S, lv["V"], lv["U"]), self._dmax, dtype=torch.float32, device=dev)
-            self.ctx.use_current_stream()
-            vp = C.c_void_p
-            _lib.check(_lib.lib().rslf_f2c_tighten_bounds(self.ctx._h, vp(up["depth"].data_ptr()), vp(up["valid"].data_ptr()), self.S, up["V"],
-                                                          up["U"], vp(lo.data_ptr()), vp(hi.data_ptr()), lv["V"], lv["U"]), "rslf_f2c_tighten_bounds")
+            lo, hi = self.rs.f2c_ranges(self.ctx, up["depth"], up["valid"], lv["V"], lv["U"], self._dmin, self._dmax)
             rows = lv["shard"].rows
             lo, hi = lo[:, rows].contiguous(), hi[:, rows].contiguous()
         lv["sweep"] = ShardedDepth2D(lv["vol"], lv["shard"], lo, hi, self._dim_d, lv["par"], self.group)
@@ -539,19 +513,7 @@ class ShardedFineToCoarse:
 
     def get_results(self):
         """f2c.hpp:302-324 on the gathered planes -> (out_map_s_v_u, out_validity_s_v_u) at the finest scale."""
-        from . import _lib
-        P = len(self.levels)
-        dp = (C.c_void_p * P)(*[lv["depth"].data_ptr() for lv in self.levels])
-        vp = (C.c_void_p * P)(*[lv["valid"].data_ptr() for lv in self.levels])
-        Vp = (C.c_int * P)(*[lv["V"] for lv in self.levels])
-        Up = (C.c_int * P)(*[lv["U"] for lv in self.levels])
-        dev = self.ctx.device
-        out_map = torch.empty((self.S, self.levels[0]["V"], self.levels[0]["U"]), dtype=torch.float32, device=dev)
-        out_valid = torch.empty((self.S, self.levels[0]["V"], self.levels[0]["U"]), dtype=torch.uint8, device=dev)
-        self.ctx.use_current_stream()
-        _lib.check(_lib.lib().rslf_f2c_fuse(self.ctx._h, dp, vp, Vp, Up, P, self.S, C.c_void_p(out_map.data_ptr()),
-                                            C.c_void_p(out_valid.data_ptr())), "rslf_f2c_fuse")
-        return out_map, out_valid
+        return self.rs.f2c_fuse(self.ctx, [lv["depth"] for lv in self.levels], [lv["valid"] for lv in self.levels])
 
     @property
     def pixels_scanned(self) -> int:

@@ -115,6 +115,27 @@ def test_no_device_is_an_error_not_a_fallback(L):
     assert L.rslf_ctx_synchronize(None) == -1
 
 
+def test_host_epi_lists_reach_the_library_checked_and_converted():
+    """MultiDevice's four methods (depth1d_pile, depth2d, fine_to_coarse, depth1d_pile_device_out) hand their EPI lists to
+    the library through depth.host_epis; MultiDevice() itself needs a device.  An EPI shorter than the first is refused
+    before the library could read past its end; every EPI goes as the first one's element type, or as float32 where the
+    method takes float32 only (depth1d_pile_device_out)."""
+    import numpy as np
+    from remotesensingproject_amd import depth as rs
+    short = [np.zeros((5, 7), np.float32) for _ in range(4)]
+    short[2] = np.zeros((5, 6), np.float32)
+    with pytest.raises(ValueError):
+        rs.host_epis(short)
+    mixed = [np.full((5, 7), 3, np.uint16), np.full((5, 7), 2.0, np.float64), np.full((5, 7), 1, np.uint8)]
+    keep, ptrs, dt, V, S, U, C_ = rs.host_epis(mixed)
+    assert dt == np.uint16 and [a.dtype for a in keep] == [np.uint16] * 3
+    assert (V, S, U, C_) == (3, 5, 7, 1) and [int(a[0, 0]) for a in keep] == [3, 2, 1]
+    assert keep[0] is mixed[0] and list(ptrs) == [a.ctypes.data for a in keep]
+    keep, _, dt, V, S, U, C_ = rs.host_epis(mixed, np.float32)
+    assert dt == np.float32 and all(a.dtype == np.float32 for a in keep)
+    assert rs.host_epis([np.zeros((2, 4, 3), np.uint8)] * 2)[3:] == (2, 2, 4, 3)
+
+
 def test_product_does_not_import_the_oracle():
     """oracle/ is test infrastructure: nothing under the package or include/ may reference it."""
     bad = []

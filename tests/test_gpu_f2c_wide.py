@@ -6,7 +6,7 @@ Every K5 launch runs one thread per column or value in 256-wide blocks; the suit
 directly (the entry points tests/test_gpu_f2c.py uses), then the whole pyramid at skysat_lr's and mansion_lr's widths --
 levels (44, 960) -> (22, 480) -> (11, 240), and (46, 1146) -> (23, 573) -> (12, 286) where the last width rounds half to
 even -- and with max_pyr_depth and accept_all_last_scale=False, through the Python level loop (FineToCoarse) and the
-native one (MultiDevice.fine_to_coarse).  Everything bit-exact; C_d within 1e-5."""
+native one (both of its C-ABI entries).  Everything bit-exact; C_d within 1e-5."""
 import ctypes as C
 
 import numpy as np
@@ -246,9 +246,11 @@ def test_fine_to_coarse_wide(pyramids, oracle_mod, name, opt):
 
 @pytest.mark.parametrize("name,opt", RUNS_F2C)
 def test_native_fine_to_coarse_wide(pyramids, oracle_mod, name, opt):
-    """The native level loop behind the C ABI (rslf_multi_fine_to_coarse_run_host) on one device.  Only the fused output
+    """The native level loop behind the C ABI, through both of its entries on one device: the multi-device one
+    (rslf_multi_fine_to_coarse_run_host) and the one-context one (rslf_fine_to_coarse_run_host).  Only the fused output
     comes back, so the scene must make every level count in it (check_coarse_levels_decide)."""
     from remotesensingproject_amd import depth as rs
+    from tests.util import native_fine_to_coarse
     C_, u8, V, S, U, D, dmin, dmax, dims = PYRAMIDS[name]
     depth, accept = OPTIONS[opt]
     raw, ref = pyramids(name, opt)
@@ -256,9 +258,11 @@ def test_native_fine_to_coarse_wide(pyramids, oracle_mod, name, opt):
     epis = [np.ascontiguousarray(raw[v, :, :, 0] if C_ == 1 else raw[v]) for v in range(V)]
     md = rs.MultiDevice([0])
     try:
-        out_map, out_valid, n_levels = md.fine_to_coarse(epis, dmin, dmax, D, max_pyr_depth=depth, accept_all_last_scale=accept)
+        multi = md.fine_to_coarse(epis, dmin, dmax, D, max_pyr_depth=depth, accept_all_last_scale=accept)
     finally:
         md.close()
-    assert n_levels == len(ref["dims"])
-    assert np.array_equal(out_map, ref["fused_map"])
-    assert np.array_equal(out_valid, ref["fused_valid"])
+    one = native_fine_to_coarse(epis, dmin, dmax, D, max_pyr_depth=depth, accept_all_last_scale=accept)[:3]
+    for entry, (out_map, out_valid, n_levels) in (("multi", multi), ("one context", one)):
+        assert n_levels == len(ref["dims"]), entry
+        assert np.array_equal(out_map, ref["fused_map"]), entry
+        assert np.array_equal(out_valid, ref["fused_valid"]), entry

@@ -169,8 +169,10 @@ def test_multi_depth2d_equals_single_volume(rs, devices, C_, dtype, V):
 def test_multi_fine_to_coarse_equals_single_device(rs, devices, C_, dtype, V):
     """FineToCoarse behind the C-ABI over several devices: every level's sweep sharded by scanline (the coarsest levels fall
     back to fewer blocks by themselves), pyramid, tightening and fusion on the first device -- the fused map and its
-    validity equal the single-context run bit for bit, and so does the count of scanned pixels."""
+    validity equal the single-context run bit for bit, and so does the count of scanned pixels.  So do those of the
+    one-context entry (rslf_fine_to_coarse_run_host)."""
     from remotesensingproject_amd.synth import make_lightfield
+    from tests.util import native_fine_to_coarse
     S, U, D = 5, 64, 9
     vol, _ = make_lightfield(U, V, S, C_, seed=2, dmin=-1, dmax=1, band=8)
     if dtype == "u8":
@@ -193,6 +195,11 @@ def test_multi_fine_to_coarse_equals_single_device(rs, devices, C_, dtype, V):
     assert np.array_equal(got_valid, want_valid.cpu().numpy())
     assert m.stats.pixels_scanned == sum(int(c.stats.pixels_scanned) for c in f.m_computers)
     m.close()
+    one_map, one_valid, one_levels, one_stats = native_fine_to_coarse(epis, -1.0, 1.0, D, epi_scale_factor=scale)
+    assert one_levels == len(f.m_computers)
+    assert np.array_equal(one_map, want_map.cpu().numpy())
+    assert np.array_equal(one_valid, want_valid.cpu().numpy())
+    assert one_stats.pixels_scanned == sum(int(c.stats.pixels_scanned) for c in f.m_computers)
 
 
 def _need_devices(n):
