@@ -474,6 +474,65 @@ int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint16_t* const*
                                            const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                            float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats);
 
+/* ---- rendering: the getters' pictures (K6) ------------------------------- */
+/* What the reference's getters do between run() and imshow: scale a plane to 8 bits, map it through a colour table,
+ * black out what the masks reject.  cv::applyColorMap lives in OpenCV, not in the reference, so the library knows no
+ * colour map by name: every render entry takes `lut_bgr`, a HOST table of 256 x 3 bytes (copied to the device once per
+ * call), and level i becomes lut_bgr[3 i .. 3 i + 2].  Pictures are uint8 BGR like the reference's CV_8UC3, dense.
+ * Planes, masks and pictures are device pointers; strides are in elements.  A NaN in a plane (cv::sort and minMaxLoc
+ * are undefined on one) neither faults nor hangs; what comes back for it is unspecified. */
+#define RSLF_FIT_MINMAX    0   /* cv::minMaxLoc, as copy_and_scale_uchar takes them -- src/rslf_plot.cpp:52-53 */
+#define RSLF_FIT_QUANTILE  1   /* ImageConverter_uchar::fit(img, true), :70-84: elements floor(0.02 N) and floor(0.98 N) of the
+                                  ascending sort, N = rows * cols -- here an exact radix select, no sort */
+#define RSLF_FIT_MEANSTD   2   /* fit(img, false), :85-95: min = true min, max = min(mean + 12 std, true max), double sums */
+#define RSLF_RENDER_SHIFT  0   /* copy_and_scale_uchar, :41-63: (x - (float)min) * (float)(255.0 / (max - min)) */
+#define RSLF_RENDER_AFFINE 1   /* ImageConverter_uchar::copy_and_scale, :100-107: x * alpha + beta, alpha = (float)(255.0 / (max - min)),
+                                  beta = (float)(-(double)alpha * min) */
+#define RSLF_MASK_BLACK      0 /* the pixel goes black after the look-up where the mask byte is 0
+                                  (setTo(0, validity == 0), include/rslf_fine_to_coarse.hpp:356, :514; cv::add under a mask,
+                                  include/rslf_depth_computation.hpp:638) */
+#define RSLF_MASK_ZERO_VALUE 1 /* the VALUE counts as 0.0f before the level is taken: the pixel gets the colour of level(0), not
+                                  black (get_coloured_epi_pyr, include/rslf_fine_to_coarse.hpp:458-459 before :465-466) */
+#define RSLF_SLICE_VIEW    0   /* plane k is view s = index + k of the volume, its rows are scanlines v */
+#define RSLF_SLICE_EPI     1   /* the one plane is scanline v = index, its rows are views s */
+
+/* The two numbers a converter holds (ImageConverter_uchar::min / max, include/rslf_plot.hpp:63-64; the min / max of
+ * copy_and_scale_uchar) for a plane of rows x cols floats, `row_stride` elements from row to row -- so row v of an
+ * [S][V][U] stack is fitted as an S x U plane.  d_valid (nullable, same strides): a pixel whose byte is 0 counts as
+ * 0.0f (include/rslf_fine_to_coarse.hpp:458-459).  mode: RSLF_FIT_*.  Integer counts and fixed-order double sums: the
+ * same bits on every run. */
+int rslf_render_fit(rslf_ctx* ctx, const float* d_plane, int rows, int cols, size_t row_stride, const uint8_t* d_valid, int mode,
+                    double* h_min, double* h_max);   /* returns the values: waits */
+/* Level -> table -> mask -> shadow cut for n_planes planes in one launch (the loops of get_disparity_map,
+ * get_coloured_epi of Depth2DComputer, get_coloured_depth_maps, get_coloured_depth_pyr, get_coloured_epi_pyr --
+ * include/rslf_depth_computation.hpp:619-643, :808-891, include/rslf_fine_to_coarse.hpp:325-378, :432-519).
+ * Plane k starts plane_stride elements after plane k - 1.  formula: RSLF_RENDER_*, then cvRound (nearest even) and
+ * saturate_cast<uchar>.  d_valid (nullable, same strides) acts as mask_mode (RSLF_MASK_*) says.  vol (nullable): the
+ * shadow cut, applied last -- a pixel goes black when the norm of the volume's radiance at its (v, s, u) is below
+ * shadow_level (include/rslf_fine_to_coarse.hpp:360-372, :466-481); slice_kind / index (RSLF_SLICE_*) say where the
+ * planes lie in the volume.  d_bgr_out: [n_planes][rows][cols][3]. */
+int rslf_render_planes(rslf_ctx* ctx, const float* d_planes, int n_planes, size_t plane_stride, int rows, int cols, size_t row_stride,
+                       double min, double max, int formula, const uint8_t* lut_bgr, const uint8_t* d_valid, int mask_mode,
+                       const rslf_volume* vol, int slice_kind, int index, float shadow_level, uint8_t* d_bgr_out);
+/* Depth1DComputer_pile::get_coloured_epi and Depth1DComputer::get_coloured_epi --
+ * include/rslf_depth_computation.hpp:568-617, :374-416 -- for scanlines v_first .. v_first + n_rows - 1 of the planes
+ * [V][U]: every masked column u draws, in view s, the column u + (int)std::round(depth * (float)(s_hat - s)) (columns
+ * > -1, the pile's test) in the colour of its depth, scaled by RSLF_RENDER_SHIFT over the min and max of the scanline's
+ * U depths, masked or not (:587).  A target keeps the source with the greatest depth, of equal depths the smallest u:
+ * the loop's sequential meaning (under OpenMP the reference's loop races).  Pixels no line reaches stay black; a NaN depth
+ * draws nothing.  d_bgr_out: [n_rows][S][U][3]. */
+int rslf_render_epi_lines(rslf_ctx* ctx, const float* d_depth_vu, const uint8_t* d_mask_vu, int V, int S, int U, int s_hat, int v_first,
+                          int n_rows, const uint8_t* lut_bgr, uint8_t* d_bgr_out);
+/* The getters' two index rules, which both run off the end in the reference (it then reads out of bounds); these
+ * return RSLF_ERR_INVALID_ARG there and say why.  std::round: halves away from zero.
+ * (int)std::round(n / 2.0): the plane FineToCoarse fits on and shows -- include/rslf_fine_to_coarse.hpp:344, :497;
+ * n itself for n = 1. */
+int rslf_render_centre_index(int n, int* index);
+/* (int)std::round(1.0 * v * dim_v / dim_v_orig): the scanline of a pyramid level that get_coloured_epi_pyr shows for
+ * scanline v of the finest -- include/rslf_fine_to_coarse.hpp:451; dim_v itself for v = dim_v_orig - 1 where
+ * dim_v = dim_v_orig / 2 (the getter's default v, round(dim_v_orig / 2.0), is out of range for dim_v_orig = 1). */
+int rslf_render_scaled_row(int v, int dim_v, int dim_v_orig, int* row);
+
 /* ---- measurement ------------------------------------------------------ */
 /* Duration in milliseconds of the last scan-kernel launch (K2) of this
  * context, from HIP events recorded on the context's stream around that

@@ -35,6 +35,8 @@ SYMBOLS = [
     "rslf_volume_upload_epis_u16", "rslf_volume_upload_images_u16", "rslf_volume_upload_images_xf_u16", "rslf_downsample_epis_u16",
     "rslf_multi_depth1d_pile_u16", "rslf_multi_depth2d_run_u16", "rslf_fine_to_coarse_run_host_u16",
     "rslf_multi_fine_to_coarse_run_host_u16",
+    # rendering (K6)
+    "rslf_render_fit", "rslf_render_planes", "rslf_render_epi_lines", "rslf_render_centre_index", "rslf_render_scaled_row",
 ]
 
 
@@ -191,6 +193,11 @@ def lib():
     L.rslf_device_max_f32.argtypes = [vp, vp, C.c_size_t, C.POINTER(cf)]
     L.rslf_f2c_tighten_bounds.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, ci, ci]
     L.rslf_f2c_fuse.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), ci, ci, vp, vp]
+    L.rslf_render_fit.argtypes = [vp, vp, ci, ci, C.c_size_t, vp, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rslf_render_planes.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, C.c_size_t, C.c_double, C.c_double, ci, vp, vp, ci, vp, ci, ci, cf, vp]
+    L.rslf_render_epi_lines.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.rslf_render_centre_index.argtypes = [ci, C.POINTER(ci)]
+    L.rslf_render_scaled_row.argtypes = [ci, ci, ci, C.POINTER(ci)]
     L.rslf_edge_confidence_2d.argtypes = [vp, vp, C.POINTER(RslfParams), vp, vp]
     L.rslf_depth_epi_2d.argtypes = [vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp, vp, C.POINTER(RslfParams), vp, C.POINTER(RslfStats)]
     L.rslf_depth2d_run.argtypes = [vp, vp, cf, cf, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, vp, C.POINTER(RslfStats)]

@@ -851,5 +851,129 @@ inline void fetch_rows(const RowBlock& bd, const RowBlock& bo, int side, int h, 
     *src_row = side == 0 ? (bo.b - bo.lo) - h : (bo.a - bo.lo);
 }
 
+// ---- K6, the renderers (k6_render.hpp, rslf_render.hip) -----------------------------------------------------------
+// The reference's getters (get_coloured_epi, get_disparity_map, get_coloured_depth_maps, ..._pyr) and the converter
+// they share (rslf_plot.cpp:41-110).  The functions a kernel calls as well are constexpr: hipcc compiles those for
+// both sides, so the kernel and the CPU tests run one definition.
+
+constexpr int kRadixBits = 8;                       // one digit of the radix select
+constexpr int kRadixBins = 1 << kRadixBits;
+constexpr int kRadixPasses = 32 / kRadixBits;       // histogram passes over the plane, most significant digit first
+constexpr int kFitBlock = 256;                      // threads of a fit workgroup, four adjacent pixels per thread and step
+constexpr int kFitMaxBlocks = 1024;                 // the fit kernels stride over the plane with at most this many workgroups
+constexpr int kRenderBlock = 256;                   // threads of a plane-render workgroup, four adjacent pixels each
+constexpr int kEpiLinesBlock = 256;                 // threads of the EPI line painter's workgroup (one (v, s) row)
+constexpr int kEpiLinesMaxU = 8000;                 // its z-buffer, one 64-bit key per column, stays below 64 KiB of LDS
+
+// A float's bits as a key whose UNSIGNED order is the float order (negative: all bits flipped; else the sign bit set).
+// -0.0f lands directly below +0.0f; NaNs land beyond the infinities on the side of their sign.
+constexpr uint32_t radix_key(uint32_t float_bits)
+{
+    return (float_bits & 0x80000000u) ? ~float_bits : (float_bits | 0x80000000u);
+}
+constexpr uint32_t radix_key_inverse(uint32_t key)
+{
+    return (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+}
+// The digit of `key` that pass `pass` (0 = most significant) counts, and the digits above it.
+constexpr uint32_t radix_digit(uint32_t key, int pass)
+{
+    return (key >> (32 - kRadixBits * (pass + 1))) & (uint32_t)(kRadixBins - 1);
+}
+constexpr uint32_t radix_prefix(uint32_t key, int pass)
+{
+    return pass == 0 ? 0u : key >> (32 - kRadixBits * pass);
+}
+// How a rank narrows to a bin: the keys that share the prefix found so far were counted per digit; `before` of them lie
+// in lower bins.  The bin with `count` keys holds the key of rank `rank` (0-based among the counted keys) iff this is
+// true, and the rank among that bin's keys is then rank - before.  Exactly one bin holds a rank below the total.
+constexpr bool radix_bin_holds(uint32_t before, uint32_t count, uint32_t rank)
+{
+    return rank >= before && rank - before < count;
+}
+// The same over a whole histogram (what the narrowing kernel's 256 threads do together): the bin, and the rank within it.
+inline int radix_narrow(const uint32_t* hist, uint32_t rank, uint32_t* rank_within)
+{
+    uint32_t before = 0;
+    for (int b = 0; b < kRadixBins; b++) {
+        if (radix_bin_holds(before, hist[b], rank)) {
+            *rank_within = rank - before;
+            return b;
+        }
+        before += hist[b];
+    }
+    return -1;   // rank >= number of keys counted
+}
+// ImageConverter_uchar::fit(img, true), rslf_plot.cpp:75-79: (int)std::floor(q * N), the product in double
+inline int quantile_index(double q, int n)
+{
+    return (int)std::floor(q * n);
+}
+// ... fit(img, false), :85-95: max = min(mean + 12 * std, true_max) with cv::meanStdDev's mean = sum * (1 / N) and
+// std = sqrt(max(sumsq * (1 / N) - mean * mean, 0)), all in double
+inline double meanstd_max(double sum, double sumsq, int n, double true_max)
+{
+    const double scale = 1.0 / n;
+    const double mean = sum * scale;
+    const double sd = std::sqrt(std::max(sumsq * scale - mean * mean, 0.0));
+    return std::min(mean + 12 * sd, true_max);
+}
+inline int fit_blocks(long long n)   // workgroups of a fit launch over n pixels
+{
+    const long long quads = (n + 3) / 4;
+    return (int)std::max<long long>(1, std::min<long long>((quads + kFitBlock - 1) / kFitBlock, kFitMaxBlocks));
+}
+
+// The two float constants a render formula applies per pixel (include/rslf_hip.h: RSLF_RENDER_*): level from
+// (x - a) * b for SHIFT (copy_and_scale_uchar, rslf_plot.cpp:52-56: `res -= min` subtracts (float)min, convertTo scales by
+// (float)(255.0 / (max - min))), from x * a + b for AFFINE (ImageConverter_uchar::copy_and_scale, :106-107:
+// float alpha = 255.0 / (max - min); convertTo(..., alpha, -alpha * min) with the product in double).
+struct RenderConsts {
+    float a, b;
+};
+inline RenderConsts render_consts(int affine, double min, double max)
+{
+    const float alpha = (float)(255.0 / (max - min));
+    if (!affine)
+        return RenderConsts{(float)min, alpha};
+    return RenderConsts{alpha, (float)(-(double)alpha * min)};
+}
+// cvRound + saturate_cast<uchar> of a level: nearest even, clamped to [0, 255]; a NaN, an infinity or anything beyond
+// the int range converts to INT_MIN (cvtss2si) and so saturates to 0.  `rounded` is rintf(y).
+constexpr int render_level(float rounded)
+{
+    return !(rounded > -2147483648.0f && rounded < 2147483648.0f) ? 0 : rounded <= 0.0f ? 0 : rounded >= 255.0f ? 255 : (int)rounded;
+}
+// Four adjacent pixels per lane as 16-byte loads and three output dwords: every row start must keep the alignment.
+inline bool render_vec4_ok(int cols, long long row_stride, long long plane_stride, const void* planes, const void* valid, const void* out)
+{
+    return cols % 4 == 0 && row_stride % 4 == 0 && plane_stride % 4 == 0 && (uintptr_t)planes % 16 == 0 && (uintptr_t)valid % 4 == 0 &&
+           (uintptr_t)out % 4 == 0;
+}
+inline long long render_quads(int rows, int cols)   // lanes of one plane: four adjacent pixels of a row each
+{
+    return (long long)rows * ((cols + 3) / 4);
+}
+inline size_t epi_lines_lds_bytes(int U)   // the z-buffer, 16 floats for the scanline's range, the table as 256 dwords
+{
+    return (size_t)U * 8 + 16 * 4 + 256 * 4;
+}
+// Index rules of the getters.  Both run off the end in the reference (which then reads out of bounds); here the
+// caller gets -1 and refuses.  std::round: halves away from zero.
+// FineToCoarse::get_coloured_depth_maps / _pyr, rslf_fine_to_coarse.hpp:344, :497: (int)std::round(dim_s / 2.0)
+inline int centre_plane_index(int n)
+{
+    const int i = (int)std::round(n / 2.0);
+    return (n < 1 || i >= n) ? -1 : i;   // n == 1: round(0.5) == 1 == n
+}
+// get_coloured_epi_pyr, :451: (int)std::round(1.0 * v * dim_v / m_dim_v_orig_)
+inline int scaled_row_index(int v, int dim_v, int dim_v_orig)
+{
+    if (v < 0 || dim_v < 1 || dim_v_orig < 1 || v >= dim_v_orig)
+        return -1;
+    const int i = (int)std::round(1.0 * v * dim_v / dim_v_orig);
+    return i >= dim_v ? -1 : i;
+}
+
 }  // namespace plan
 }  // namespace rslf

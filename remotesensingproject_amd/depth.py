@@ -289,6 +289,125 @@ class Volume:
             pass
 
 
+# ---- rendering: the getters' pictures (include/rslf_hip.h, "rendering"; csrc/k6_render.hpp) ----------------------
+
+FIT_MINMAX, FIT_QUANTILE, FIT_MEANSTD = 0, 1, 2      # RSLF_FIT_*
+RENDER_SHIFT, RENDER_AFFINE = 0, 1                   # RSLF_RENDER_*
+MASK_BLACK, MASK_ZERO_VALUE = 0, 1                   # RSLF_MASK_*
+SLICE_VIEW, SLICE_EPI = 0, 1                         # RSLF_SLICE_*
+
+
+def colormap_jet() -> np.ndarray:
+    """A jet table [256, 3] uint8, BGR, for the getters' `lut_bgr`.  Restated from memory of OpenCV 3.4, unpinned: the
+    library knows no colour map by name (cv::applyColorMap lives in OpenCV, not in the reference), no test compares
+    this table with OpenCV's COLORMAP_JET, and none may rest on it.  Any [256, 3] uint8 table serves instead."""
+    x = np.arange(256, dtype=np.float64) / 255.0
+    r = np.clip(1.5 - np.abs(4.0 * x - 3.0), 0.0, 1.0)
+    g = np.clip(1.5 - np.abs(4.0 * x - 2.0), 0.0, 1.0)
+    b = np.clip(1.5 - np.abs(4.0 * x - 1.0), 0.0, 1.0)
+    return np.rint(np.stack([b, g, r], axis=1) * 255.0).astype(np.uint8)
+
+
+def _table(lut_bgr) -> np.ndarray:
+    t = colormap_jet() if lut_bgr is None else np.ascontiguousarray(lut_bgr)
+    if t.dtype != np.uint8 or t.shape != (256, 3):
+        raise ValueError("lut_bgr must be a [256, 3] uint8 array (level i -> lut_bgr[i], BGR)")
+    return t
+
+
+def _strided(t: torch.Tensor, like: torch.Tensor | None = None) -> tuple:
+    """Strides in elements of a plane stack whose rows are contiguous (views of larger stacks are taken as they are)."""
+    if not t.is_cuda or t.stride(-1) != 1 and t.shape[-1] > 1:
+        raise ValueError("planes must be CUDA tensors with contiguous rows")
+    if like is not None and (t.shape != like.shape or t.stride() != like.stride()):
+        raise ValueError("the mask must have the planes' shape and strides")
+    return t.stride()
+
+
+def _index_rule(name: str, *args) -> int:
+    """The getters' two index rules (rslf_render_centre_index / rslf_render_scaled_row): ValueError where the
+    reference's own index runs off the end."""
+    out = C.c_int()
+    st = getattr(_lib.lib(), name)(*args, C.byref(out))
+    if st == -1:
+        raise ValueError(_lib.lib().rslf_last_error().decode(errors="replace"))
+    check(st, name)
+    return int(out.value)
+
+
+def render_fit(ctx: Context, plane: torch.Tensor, valid: torch.Tensor | None = None, mode: int = FIT_MINMAX) -> tuple[float, float]:
+    """rslf_render_fit: the (min, max) a converter holds for a [rows, cols] float32 plane (a strided slice of a stack
+    is fine).  mode FIT_MINMAX: cv::minMaxLoc; FIT_QUANTILE: ImageConverter_uchar::fit(img, true), elements
+    floor(0.02 N) and floor(0.98 N) of the sort; FIT_MEANSTD: fit(img, false).  `valid` (uint8, same shape and strides): a
+    pixel whose byte is 0 counts as 0.  Waits for the result.  What a NaN in the plane gives is unspecified."""
+    if plane.dim() != 2 or plane.dtype != torch.float32 or (valid is not None and valid.dtype != torch.uint8):
+        raise ValueError("render_fit takes a 2-D float32 plane and a uint8 mask")
+    stride = _strided(plane)
+    if valid is not None:
+        _strided(valid, plane)
+    rows, cols = plane.shape
+    lo, hi = C.c_double(), C.c_double()
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_render_fit(ctx._h, _ptr(plane), rows, cols, stride[0] if rows > 1 else cols, _ptr(valid), int(mode),
+                                     C.byref(lo), C.byref(hi)), "rslf_render_fit")
+    return float(lo.value), float(hi.value)
+
+
+def render_planes(ctx: Context, planes: torch.Tensor, vmin: float, vmax: float, formula: int, lut_bgr, valid: torch.Tensor | None = None,
+                  mask_mode: int = MASK_BLACK, vol: "Volume | None" = None, slice_kind: int = SLICE_VIEW, index: int = 0,
+                  shadow_level: float = 0.0) -> torch.Tensor:
+    """rslf_render_planes: [n, rows, cols] float32 planes (strided slices are fine) -> [n, rows, cols, 3] uint8 BGR in one
+    launch.  Level by `formula` (RENDER_SHIFT: copy_and_scale_uchar; RENDER_AFFINE: ImageConverter_uchar::copy_and_scale)
+    from (vmin, vmax), then lut_bgr, then `valid` by `mask_mode` (MASK_BLACK: black where the byte is 0; MASK_ZERO_VALUE:
+    the value counts as 0 before the level is taken), then with `vol` the shadow cut: black where the norm of the
+    volume's radiance is below shadow_level (SLICE_VIEW: plane k is view index + k; SLICE_EPI: the one plane is scanline
+    `index`, its rows are views).  What a NaN in a plane renders as is unspecified."""
+    if planes.dim() != 3 or planes.dtype != torch.float32 or (valid is not None and valid.dtype != torch.uint8):
+        raise ValueError("render_planes takes 3-D float32 planes and a uint8 mask")
+    stride = _strided(planes)
+    if valid is not None:
+        _strided(valid, planes)
+    n, rows, cols = planes.shape
+    table = _table(lut_bgr)
+    out = torch.empty((n, rows, cols, 3), dtype=torch.uint8, device=planes.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_render_planes(
+        ctx._h, _ptr(planes), n, stride[0] if n > 1 else 0, rows, cols, stride[1] if rows > 1 else cols, float(vmin), float(vmax),
+        int(formula), table.ctypes.data_as(C.c_void_p), _ptr(valid), int(mask_mode), vol._h if vol is not None else None,
+        int(slice_kind), int(index), float(shadow_level), _ptr(out)), "rslf_render_planes")
+    return out
+
+
+def render_epi_lines(ctx: Context, depth_v_u: torch.Tensor, mask_v_u: torch.Tensor, S: int, s_hat: int, v_first: int, n_rows: int,
+                     lut_bgr) -> torch.Tensor:
+    """rslf_render_epi_lines: the z-buffered EPI lines of get_coloured_epi for scanlines v_first .. v_first + n_rows - 1 of
+    the [V, U] planes -> [n_rows, S, U, 3] uint8 BGR.  A NaN depth draws nothing."""
+    if depth_v_u.dim() != 2 or depth_v_u.dtype != torch.float32 or mask_v_u.dtype != torch.uint8 or mask_v_u.shape != depth_v_u.shape:
+        raise ValueError("render_epi_lines takes [V, U] float32 depths and a uint8 mask of the same shape")
+    depth_v_u, mask_v_u = depth_v_u.contiguous(), mask_v_u.contiguous()
+    V, U = depth_v_u.shape
+    table = _table(lut_bgr)
+    out = torch.empty((n_rows, S, U, 3), dtype=torch.uint8, device=depth_v_u.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_render_epi_lines(ctx._h, _ptr(depth_v_u), _ptr(mask_v_u), V, int(S), U, int(s_hat), int(v_first), int(n_rows),
+                                           table.ctypes.data_as(C.c_void_p), _ptr(out)), "rslf_render_epi_lines")
+    return out
+
+
+def _coloured_epi_rows(ctx: Context, depth_v_u, mask_v_u, S: int, s_hat: int, a_v, lut_bgr) -> torch.Tensor:
+    """get_coloured_epi's scanline argument: an int (< 0: floor(V / 2.0), dc.hpp:576-577) -> [S, U, 3]; a range of step 1 ->
+    [len, S, U, 3], the same scanlines in one call."""
+    V = depth_v_u.shape[0]
+    if isinstance(a_v, range):
+        if a_v.step != 1 or len(a_v) < 1 or a_v.start < 0 or a_v.stop > V:
+            raise ValueError("a_v must be a non-empty range of step 1 within the %d scanlines" % V)
+        return render_epi_lines(ctx, depth_v_u, mask_v_u, S, s_hat, a_v.start, len(a_v), lut_bgr)
+    a_v = int(np.floor(V / 2.0)) if a_v < 0 else int(a_v)
+    if a_v >= V:
+        raise ValueError("scanline %d of %d" % (a_v, V))
+    return render_epi_lines(ctx, depth_v_u, mask_v_u, S, s_hat, a_v, 1, lut_bgr)[0]
+
+
 # ---- the reference's free functions -------------------------------------
 
 def compute_1D_edge_confidence_pile(vol: Volume, a_s: int, a_edge_confidence_v_u: torch.Tensor,
@@ -400,6 +519,23 @@ class Depth1DComputer_pile:
 
     def get_s_hat(self) -> int:
         return self.m_s_hat
+
+    def get_coloured_epi(self, a_v=-1, lut_bgr=None) -> torch.Tensor:
+        """dc.hpp:568-617: the EPI of scanline a_v (< 0: floor(V / 2.0)) with every confident pixel's line drawn in the
+        colour of its disparity, nearer lines over farther ones -> [S, U, 3] uint8 BGR on the device.  a_v may be a
+        range: [len, S, U, 3] in one call.  lut_bgr ([256, 3] uint8) stands where the reference takes a_cv_colormap (None:
+        colormap_jet()).  The reference's loop races under OpenMP; this is its sequential meaning (a target keeps the
+        greatest depth, of equal depths the smallest u).  A NaN depth draws nothing."""
+        vol = self.m_epis
+        return _coloured_epi_rows(vol.ctx, self.m_best_depth_v_u, self.m_edge_confidence_mask_v_u, vol.S, self.m_s_hat, a_v, lut_bgr)
+
+    def get_disparity_map(self, lut_bgr=None) -> torch.Tensor:
+        """dc.hpp:619-643: the disparities scaled over their min / max (every pixel, confident or not), colour-mapped,
+        black outside m_edge_confidence_mask_v_u -> [V, U, 3] uint8 BGR.  What a NaN disparity gives is unspecified."""
+        ctx = self.m_epis.ctx
+        lo, hi = render_fit(ctx, self.m_best_depth_v_u, None, FIT_MINMAX)
+        return render_planes(ctx, self.m_best_depth_v_u.unsqueeze(0), lo, hi, RENDER_SHIFT, lut_bgr,
+                             self.m_edge_confidence_mask_v_u.unsqueeze(0), MASK_BLACK)[0]
 
     def results(self) -> dict:
         """Host copies of every output plane."""
@@ -643,6 +779,36 @@ class Depth2DComputer:
     def set_accept_all(self, b: bool) -> None:
         self.m_accept_all = bool(b)
 
+    def _confidence_mask_s_v_u(self) -> torch.Tensor:
+        """The mask the two getters paint under: m_edge_confidence_mask_s_v_u in the default build (dc.hpp:840-842,
+        :885-887); with par_use_disp_confidence_score, C_d > (float)par_disp_score_threshold (:832-834, :875-878)."""
+        if not self.m_parameters.par_use_disp_confidence_score:
+            return self.m_edge_confidence_mask_s_v_u
+        return (self.m_disp_confidence_s_v_u > float(np.float32(self.m_parameters.par_disp_score_threshold))).to(torch.uint8) * 255
+
+    def get_coloured_epi(self, a_v=-1, lut_bgr=None) -> torch.Tensor:
+        """dc.hpp:808-856: the S x U slice of the disparities at scanline a_v (< 0: floor(V / 2.0)), scaled over its own
+        min / max, colour-mapped, black outside the mask; no line drawing -> [S, U, 3] uint8 BGR.  The slice is read in
+        place through its row stride.  What a NaN disparity gives is unspecified."""
+        vol = self.m_epis
+        a_v = int(np.floor(vol.V / 2.0)) if a_v < 0 else int(a_v)
+        if a_v >= vol.V:
+            raise ValueError("scanline %d of %d" % (a_v, vol.V))
+        plane, mask = self.m_best_depth_s_v_u[:, a_v, :], self._confidence_mask_s_v_u()[:, a_v, :]
+        lo, hi = render_fit(vol.ctx, plane, None, FIT_MINMAX)
+        return render_planes(vol.ctx, plane.unsqueeze(0), lo, hi, RENDER_SHIFT, lut_bgr, mask.unsqueeze(0), MASK_BLACK)[0]
+
+    def get_disparity_map(self, a_s=-1, lut_bgr=None) -> torch.Tensor:
+        """dc.hpp:858-891: view a_s (< 0: floor(S / 2.0)) scaled over its min / max (every pixel), colour-mapped, black
+        outside the mask -> [V, U, 3] uint8 BGR.  What a NaN disparity gives is unspecified."""
+        vol = self.m_epis
+        a_s = int(np.floor(vol.S / 2.0)) if a_s < 0 else int(a_s)
+        if a_s >= vol.S:
+            raise ValueError("view %d of %d" % (a_s, vol.S))
+        plane, mask = self.m_best_depth_s_v_u[a_s], self._confidence_mask_s_v_u()[a_s]
+        lo, hi = render_fit(vol.ctx, plane, None, FIT_MINMAX)
+        return render_planes(vol.ctx, plane.unsqueeze(0), lo, hi, RENDER_SHIFT, lut_bgr, mask.unsqueeze(0), MASK_BLACK)[0]
+
     def get_valid_depths_mask_s_v_u(self) -> torch.Tensor:
         """dc.hpp:893-915, default build: C_e > edge threshold (or everything > -1 with accept_all)."""
         thr = -1.0 if self.m_accept_all else float(np.float32(self.m_parameters.par_edge_score_threshold))
@@ -713,6 +879,15 @@ class Depth1DComputer:
             _ptr(self.m_best_depth_u), _ptr(self.m_rbar_u), _ptr(self.m_depth_idx_u), _ptr(self.m_score_u), C.byref(st)),
             "rslf_depth1d_run")
         self.stats = st
+
+    def get_coloured_epi(self, lut_bgr=None) -> torch.Tensor:
+        """dc.hpp:374-416: as Depth1DComputer_pile.get_coloured_epi for the one EPI -> [S, U, 3] uint8 BGR.  This class
+        tests `requested_index > 0` where the pile tests `> -1` (:401 against :601): column 0 is never painted, and no
+        other column depends on it, so it is the pile's picture with column 0 black."""
+        vol = self.m_epi
+        out = _coloured_epi_rows(vol.ctx, self.m_best_depth_u, self.m_edge_confidence_mask_u, vol.S, self.m_s_hat, 0, lut_bgr)
+        out[:, 0, :] = 0
+        return out
 
     def results(self) -> dict:
         torch.cuda.synchronize(self.m_epi.ctx.device)
@@ -866,3 +1041,65 @@ class FineToCoarse:
         comps = self.m_computers
         return f2c_fuse(comps[0].m_epis.ctx, [c.m_best_depth_s_v_u.contiguous() for c in comps],
                         [c.get_valid_depths_mask_s_v_u().contiguous() for c in comps])
+
+    def _fit_mode(self, saturate: bool) -> int:
+        return FIT_QUANTILE if saturate else FIT_MEANSTD   # ImageConverter_uchar::fit(img, saturate), rslf_plot.cpp:65-98
+
+    def _shadow_volume(self, level: int):
+        """The volume and level of the getters' shadow cut (f2c.hpp:360-372, :466-481), or (None, 0) without
+        par_cut_shadows.  The reference compares against _SHADOW_NORMALIZED_LEVEL; here it is par_shadow_level, whose
+        default is that constant."""
+        if not self.m_parameters.par_cut_shadows:
+            return None, 0.0
+        return self.m_computers[level].m_epis, float(self.m_parameters.par_shadow_level)
+
+    def get_coloured_depth_maps(self, lut_bgr=None, saturate: bool = True) -> torch.Tensor:
+        """f2c.hpp:325-378: the fused disparities of every view through ONE converter, fitted on the fused plane
+        (int)std::round(S / 2.0) (saturate: 2 % / 98 % quantiles, else min and mean + 12 std), colour-mapped, black where the
+        fused validity is 0 and, with par_cut_shadows, where the finest level's radiance is in shadow -> [S, V, U, 3] uint8
+        BGR.  S = 1 raises ValueError: the reference's index is then S itself.  NaN disparities: unspecified."""
+        ctx = self.m_computers[0].m_epis.ctx
+        mid = _index_rule("rslf_render_centre_index", self.m_computers[0].m_epis.S)
+        out_map, out_valid = self.get_results()
+        lo, hi = render_fit(ctx, out_map[mid], None, self._fit_mode(saturate))
+        vol, level = self._shadow_volume(0)
+        return render_planes(ctx, out_map, lo, hi, RENDER_AFFINE, lut_bgr, out_valid, MASK_BLACK, vol, SLICE_VIEW, 0, level)
+
+    def get_coloured_depth_pyr(self, s: int = -1, lut_bgr=None, saturate: bool = True) -> list:
+        """f2c.hpp:491-519: view s (-1: (int)std::round(S / 2.0)) of every level, finest first, through the converter fitted
+        on level 0's plane before any masking; black outside each level's validity; no shadow cut -> a list of
+        [V_p, U_p, 3] uint8 BGR.  ValueError where the reference's index runs off the end (S = 1)."""
+        comps = self.m_computers
+        S = comps[0].m_epis.S
+        s = _index_rule("rslf_render_centre_index", S) if s == -1 else int(s)
+        if not 0 <= s < S:
+            raise ValueError("view %d of %d" % (s, S))
+        out, lo, hi = [], 0.0, 0.0
+        for p, comp in enumerate(comps):
+            ctx, plane = comp.m_epis.ctx, comp.m_best_depth_s_v_u[s]
+            if p == 0:
+                lo, hi = render_fit(ctx, plane, None, self._fit_mode(saturate))
+            valid = comp.get_valid_depths_mask_s_v_u()[s]
+            out.append(render_planes(ctx, plane.unsqueeze(0), lo, hi, RENDER_AFFINE, lut_bgr, valid.unsqueeze(0), MASK_BLACK)[0])
+        return out
+
+    def get_coloured_epi_pyr(self, v: int = -1, lut_bgr=None, saturate: bool = True) -> list:
+        """f2c.hpp:432-488: the S x U_p slice of every level at scanline (int)std::round(1.0 * v * V_p / V_0) (v = -1:
+        (int)std::round(V_0 / 2.0)), finest first.  Invalid pixels count as 0 in the fit (level 0 only) and in the render, so
+        they get the colour of level(0), not black; then, with par_cut_shadows, the shadow cut against the level's own
+        volume -> a list of [S, U_p, 3] uint8 BGR.  ValueError where the reference's row index reaches V_p (V_0 = 1, or
+        v = V_0 - 1 with V_p = V_0 / 2)."""
+        comps = self.m_computers
+        V0 = comps[0].m_epis.V
+        v = _index_rule("rslf_render_centre_index", V0) if v == -1 else int(v)
+        out, lo, hi = [], 0.0, 0.0
+        for p, comp in enumerate(comps):
+            ctx = comp.m_epis.ctx
+            row = _index_rule("rslf_render_scaled_row", v, comp.m_epis.V, V0)
+            plane, valid = comp.m_best_depth_s_v_u[:, row, :], comp.get_valid_depths_mask_s_v_u()[:, row, :]
+            if p == 0:
+                lo, hi = render_fit(ctx, plane, valid, self._fit_mode(saturate))
+            vol, level = self._shadow_volume(p)
+            out.append(render_planes(ctx, plane.unsqueeze(0), lo, hi, RENDER_AFFINE, lut_bgr, valid.unsqueeze(0), MASK_ZERO_VALUE,
+                                     vol, SLICE_EPI, row, level)[0])
+        return out
