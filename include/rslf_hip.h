@@ -479,7 +479,7 @@ int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint16_t* const*
  * black out what the masks reject.  cv::applyColorMap lives in OpenCV, not in the reference, so the library knows no
  * colour map by name: every render entry takes `lut_bgr`, a HOST table of 256 x 3 bytes (copied to the device once per
  * call), and level i becomes lut_bgr[3 i .. 3 i + 2].  Pictures are uint8 BGR like the reference's CV_8UC3, dense.
- * Planes, masks and pictures are device pointers; strides are in elements.  A NaN in a plane (cv::sort and minMaxLoc
+ * Planes, masks and pictures are device pointers (host pointers in the *_host forms); strides are in elements.  A NaN in a plane (cv::sort and minMaxLoc
  * are undefined on one) neither faults nor hangs; what comes back for it is unspecified. */
 #define RSLF_FIT_MINMAX    0   /* cv::minMaxLoc, as copy_and_scale_uchar takes them -- src/rslf_plot.cpp:52-53 */
 #define RSLF_FIT_QUANTILE  1   /* ImageConverter_uchar::fit(img, true), :70-84: elements floor(0.02 N) and floor(0.98 N) of the
@@ -494,7 +494,8 @@ int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint16_t* const*
 #define RSLF_MASK_ZERO_VALUE 1 /* the VALUE counts as 0.0f before the level is taken: the pixel gets the colour of level(0), not
                                   black (get_coloured_epi_pyr, include/rslf_fine_to_coarse.hpp:458-459 before :465-466) */
 #define RSLF_SLICE_VIEW    0   /* plane k is view s = index + k of the volume, its rows are scanlines v */
-#define RSLF_SLICE_EPI     1   /* the one plane is scanline v = index, its rows are views s */
+#define RSLF_SLICE_EPI     1   /* the plane is scanline v = index, its rows are views s (rslf_render_planes_each and
+                                  rslf_render_planes_host: plane k is scanline index + k) */
 
 /* The two numbers a converter holds (ImageConverter_uchar::min / max, include/rslf_plot.hpp:63-64; the min / max of
  * copy_and_scale_uchar) for a plane of rows x cols floats, `row_stride` elements from row to row -- so row v of an
@@ -503,6 +504,13 @@ int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint16_t* const*
  * same bits on every run. */
 int rslf_render_fit(rslf_ctx* ctx, const float* d_plane, int rows, int cols, size_t row_stride, const uint8_t* d_valid, int mode,
                     double* h_min, double* h_max);   /* returns the values: waits */
+/* The same for n_planes planes (1 .. 65535) of one stack, plane k starting plane_stride elements after plane k - 1, in
+ * launches whose number does not depend on n_planes, one copy to the host and one wait: h_minmax [n_planes][2] gets
+ * (min, max) of every plane, bit for bit what rslf_render_fit returns for that plane alone.  Every view of an [S][V][U]
+ * stack: n_planes = S, plane_stride = V * U, rows = V, row_stride = U; every EPI slice of it: n_planes = V,
+ * plane_stride = U, rows = S, row_stride = V * U.  d_valid (nullable): same strides. */
+int rslf_render_fit_many(rslf_ctx* ctx, const float* d_planes, int n_planes, size_t plane_stride, int rows, int cols, size_t row_stride,
+                         const uint8_t* d_valid, int mode, double* h_minmax);   /* returns the values: waits */
 /* Level -> table -> mask -> shadow cut for n_planes planes in one launch (the loops of get_disparity_map,
  * get_coloured_epi of Depth2DComputer, get_coloured_depth_maps, get_coloured_depth_pyr, get_coloured_epi_pyr --
  * include/rslf_depth_computation.hpp:619-643, :808-891, include/rslf_fine_to_coarse.hpp:325-378, :432-519).
@@ -514,6 +522,23 @@ int rslf_render_fit(rslf_ctx* ctx, const float* d_plane, int rows, int cols, siz
 int rslf_render_planes(rslf_ctx* ctx, const float* d_planes, int n_planes, size_t plane_stride, int rows, int cols, size_t row_stride,
                        double min, double max, int formula, const uint8_t* lut_bgr, const uint8_t* d_valid, int mask_mode,
                        const rslf_volume* vol, int slice_kind, int index, float shadow_level, uint8_t* d_bgr_out);
+/* rslf_render_planes with a range per plane: plane k goes through h_minmax[k][0 .. 1] (HOST, [n_planes][2], as
+ * rslf_render_fit_many fills it).  With RSLF_SLICE_EPI the batch may hold several planes: plane k is scanline index + k,
+ * index + n_planes <= V.  Enqueued, not awaited, like rslf_render_planes. */
+int rslf_render_planes_each(rslf_ctx* ctx, const float* d_planes, int n_planes, size_t plane_stride, int rows, int cols, size_t row_stride,
+                            const double* h_minmax, int formula, const uint8_t* lut_bgr, const uint8_t* d_valid, int mask_mode,
+                            const rslf_volume* vol, int slice_kind, int index, float shadow_level, uint8_t* d_bgr_out);
+/* Fit and render with planes, validity and pictures on the HOST (what the classes of rslf_hip.hpp hold): uploads the
+ * stack, fits (fit_mode: RSLF_FIT_*; fit_plane = -1: every plane through its own range, by rslf_render_fit_many;
+ * fit_plane = k >= 0: every plane through plane k's range, as FineToCoarse::get_coloured_depth_maps does; fit_masked != 0:
+ * the fit sees h_valid, as rslf_render_fit's d_valid), renders as rslf_render_planes_each / rslf_render_planes do, downloads
+ * and waits.  h_valid: nullable.  vol (nullable) is a device volume of this context.  h_bgr_out: [n_planes][rows][cols][3].
+ * h_minmax (nullable): [n_planes][2], the ranges used.  Staging is the context's grow-only scratch: a second call of the
+ * same size allocates nothing. */
+int rslf_render_planes_host(rslf_ctx* ctx, const float* h_planes, int n_planes, size_t plane_stride, int rows, int cols, size_t row_stride,
+                            const uint8_t* h_valid, int fit_mode, int fit_plane, int fit_masked, int formula, const uint8_t* lut_bgr,
+                            int mask_mode, const rslf_volume* vol, int slice_kind, int index, float shadow_level, uint8_t* h_bgr_out,
+                            double* h_minmax);
 /* Depth1DComputer_pile::get_coloured_epi and Depth1DComputer::get_coloured_epi --
  * include/rslf_depth_computation.hpp:568-617, :374-416 -- for scanlines v_first .. v_first + n_rows - 1 of the planes
  * [V][U]: every masked column u draws, in view s, the column u + (int)std::round(depth * (float)(s_hat - s)) (columns
@@ -523,6 +548,9 @@ int rslf_render_planes(rslf_ctx* ctx, const float* d_planes, int n_planes, size_
  * draws nothing.  d_bgr_out: [n_rows][S][U][3]. */
 int rslf_render_epi_lines(rslf_ctx* ctx, const float* d_depth_vu, const uint8_t* d_mask_vu, int V, int S, int U, int s_hat, int v_first,
                           int n_rows, const uint8_t* lut_bgr, uint8_t* d_bgr_out);
+/* The same with depths, mask and picture on the host: uploads the n_rows scanlines, paints, downloads and waits. */
+int rslf_render_epi_lines_host(rslf_ctx* ctx, const float* h_depth_vu, const uint8_t* h_mask_vu, int V, int S, int U, int s_hat, int v_first,
+                               int n_rows, const uint8_t* lut_bgr, uint8_t* h_bgr_out);
 /* The getters' two index rules, which both run off the end in the reference (it then reads out of bounds); these
  * return RSLF_ERR_INVALID_ARG there and say why.  std::round: halves away from zero.
  * (int)std::round(n / 2.0): the plane FineToCoarse fits on and shows -- include/rslf_fine_to_coarse.hpp:344, :497;

@@ -5,7 +5,8 @@
 // rslf::Depth1DParameters<DataType> (rslf_depth_computation_core.hpp:66-142) so
 // the class drops into the reference's demos (tests/test_depth_computation_pile.cpp:49-51)
 // in place of the OpenMP path.  Everything below the class goes through the
-// C-ABI of rslf_hip.h; nothing here computes.
+// C-ABI of rslf_hip.h; nothing here computes.  The reference's picture getters (get_coloured_epi, get_disparity_map,
+// get_coloured_depth_maps) are here too, on byte vectors and a caller's colour table: see "the getters' pictures".
 //
 // OpenCV is optional: when <opencv2/core/core.hpp> is on the include path
 // (the reference's own build, CMakeLists.txt:29) the cv::Mat constructor and
@@ -142,6 +143,37 @@ inline float upload_epis(rslf_volume* vol, InputType type, const void* const* ep
     return used;
 }
 
+// ---- the getters' pictures ------------------------------------------------------------------------------------------
+// The classes below hold their results on the host, so their getters go through the host-pointer forms of the renderers
+// (rslf_render_planes_host, rslf_render_epi_lines_host).  Pictures are dense uint8 BGR vectors; `lut_bgr` is the caller's
+// table of 256 x 3 bytes (level i -> lut_bgr[3 i .. 3 i + 2]), which stands where the reference takes a cv colormap id.
+// The rules (index defaults, masks, fits, formulas) are those of remotesensingproject_amd/depth.py's getters, which cite
+// the reference line by line; where the reference's own index runs past the end, the getter throws
+// Error(RSLF_ERR_INVALID_ARG).  Each getter has a form whose first argument is the Context to render on: an object
+// built on a MultiContext has no context of its own (rendering OVER several devices is not built).
+
+inline void require(bool ok, const char* what)
+{
+    if (!ok) {
+        rslf_render_centre_index(0, nullptr);   // sets the library's error text to "bad arguments"
+        throw Error(RSLF_ERR_INVALID_ARG, what);
+    }
+}
+
+// fit (fit_plane = -1: every plane its own range; k: plane k's range for all) + render of host planes -> [n][rows][cols][3]
+inline std::vector<uint8_t> render_planes(rslf_ctx* ctx, const std::vector<float>& planes, size_t offset, const uint8_t* valid, int n,
+                                          size_t plane_stride, int rows, int cols, size_t row_stride, int fit_mode, int fit_plane,
+                                          int formula, const uint8_t* lut_bgr, const rslf_volume* vol = nullptr, float shadow_level = 0.f)
+{
+    require(!planes.empty(), "the getters show the results of run(): call it first");
+    std::vector<uint8_t> out((size_t)n * rows * cols * 3);
+    check(rslf_render_planes_host(ctx, planes.data() + offset, n, plane_stride, rows, cols, row_stride, valid ? valid + offset : nullptr,
+                                  fit_mode, fit_plane, 0, formula, lut_bgr, RSLF_MASK_BLACK, vol, RSLF_SLICE_VIEW, 0, shadow_level,
+                                  out.data(), nullptr),
+          "rslf_render_planes_host");
+    return out;
+}
+
 #ifdef RSLFX_HAVE_OPENCV
 // The data pointers of a Vec<Mat> of EPIs and their element type; one shape, one type, `channels` channels.  CV_16U is
 // accepted where the OpenCV in use defines it (a macro in every OpenCV release).
@@ -213,6 +245,15 @@ public:
 private:
     rslf_ctx* h_;
 };
+
+namespace detail {
+inline Context& own(Context* ctx)   // the context an object was built on
+{
+    if (!ctx)
+        throw std::invalid_argument("this object was built on a MultiContext: pass the Context to render on");
+    return *ctx;
+}
+}  // namespace detail
 
 // Several devices (or several workers on one device) behind one handle: the pile path then cuts the scanlines into one
 // block per device and overlaps upload, kernels and download chunk by chunk (rslf_hip.h, rslf_multi_*).
@@ -370,6 +411,32 @@ public:
     }
 
     int get_s_hat() const { return m_s_hat; }
+
+    // dc.hpp:568-617: the EPI of scanline a_v (< 0: floor(V / 2.0)) with every confident pixel's line drawn in the colour
+    // of its disparity, nearer lines over farther ones -> [S][U][3].  The loop's sequential meaning (under OpenMP the
+    // reference's loop races).
+    std::vector<uint8_t> get_coloured_epi(Context& on, int a_v, const uint8_t* lut_bgr) const
+    {
+        detail::require(!m_best_depth_v_u.empty(), "the getters show the results of run(): call it first");
+        if (a_v < 0)
+            a_v = (int)std::floor(dim_v_ / 2.0);   // :576-577
+        detail::require(a_v < dim_v_, "get_coloured_epi: the scanline is not below dim_v");
+        std::vector<uint8_t> out((size_t)dim_s_ * dim_u_ * 3);
+        check(rslf_render_epi_lines_host(on.get(), m_best_depth_v_u.data(), m_edge_confidence_mask_v_u.data(), dim_v_, dim_s_, dim_u_, m_s_hat,
+                                         a_v, 1, lut_bgr, out.data()),
+              "rslf_render_epi_lines_host");
+        return out;
+    }
+    std::vector<uint8_t> get_coloured_epi(int a_v, const uint8_t* lut_bgr) const { return get_coloured_epi(detail::own(ctx_), a_v, lut_bgr); }
+    // dc.hpp:619-643: the disparities scaled over their min / max (every pixel, confident or not), colour-mapped, black
+    // outside m_edge_confidence_mask_v_u -> [V][U][3]
+    std::vector<uint8_t> get_disparity_map(Context& on, const uint8_t* lut_bgr) const
+    {
+        return detail::render_planes(on.get(), m_best_depth_v_u, 0, m_edge_confidence_mask_v_u.data(), 1, 0, dim_v_, dim_u_, (size_t)dim_u_,
+                                     RSLF_FIT_MINMAX, -1, RSLF_RENDER_SHIFT, lut_bgr);
+    }
+    std::vector<uint8_t> get_disparity_map(const uint8_t* lut_bgr) const { return get_disparity_map(detail::own(ctx_), lut_bgr); }
+
     int rows() const { return dim_v_; }
     int cols() const { return dim_u_; }
     float epi_scale_factor() const { return scale_used_; }
@@ -528,6 +595,40 @@ public:
     }
     const std::vector<float>& get_depths_s_v_u() const { return m_best_depth_s_v_u; }
 
+    // dc.hpp:808-856: the S x U slice of the disparities at scanline a_v (< 0: floor(V / 2.0)) over its own min / max,
+    // colour-mapped, black outside the mask; no line drawing -> [S][U][3].  The slice is read through its row stride.
+    std::vector<uint8_t> get_coloured_epi(Context& on, int a_v, const uint8_t* lut_bgr) const
+    {
+        if (a_v < 0)
+            a_v = (int)std::floor(dim_v_ / 2.0);
+        detail::require(a_v < dim_v_, "get_coloured_epi: the scanline is not below dim_v");
+        return slices(on, (size_t)a_v * dim_u_, 1, 0, dim_s_, (size_t)dim_v_ * dim_u_, lut_bgr);
+    }
+    std::vector<uint8_t> get_coloured_epi(int a_v, const uint8_t* lut_bgr) const { return get_coloured_epi(detail::own(ctx_), a_v, lut_bgr); }
+    // dc.hpp:858-891: view a_s (< 0: floor(S / 2.0)) over its min / max (every pixel), colour-mapped, black outside the
+    // mask -> [V][U][3]
+    std::vector<uint8_t> get_disparity_map(Context& on, int a_s, const uint8_t* lut_bgr) const
+    {
+        if (a_s < 0)
+            a_s = (int)std::floor(dim_s_ / 2.0);
+        detail::require(a_s < dim_s_, "get_disparity_map: the view is not below dim_s");
+        return slices(on, (size_t)a_s * dim_v_ * dim_u_, 1, 0, dim_v_, (size_t)dim_u_, lut_bgr);
+    }
+    std::vector<uint8_t> get_disparity_map(int a_s, const uint8_t* lut_bgr) const { return get_disparity_map(detail::own(ctx_), a_s, lut_bgr); }
+    // get_disparity_map(a_s) for every view (the loop of the reference's demo, tests/test_depth_computation_2d.cpp:77)
+    // -> [S][V][U][3], and get_coloured_epi(a_v) for every scanline -> [V][S][U][3]: one upload, one batch of fits, one
+    // render launch, each plane over its own min / max.
+    std::vector<uint8_t> get_disparity_maps(Context& on, const uint8_t* lut_bgr) const
+    {
+        return slices(on, 0, dim_s_, (size_t)dim_v_ * dim_u_, dim_v_, (size_t)dim_u_, lut_bgr);
+    }
+    std::vector<uint8_t> get_disparity_maps(const uint8_t* lut_bgr) const { return get_disparity_maps(detail::own(ctx_), lut_bgr); }
+    std::vector<uint8_t> get_coloured_epis(Context& on, const uint8_t* lut_bgr) const
+    {
+        return slices(on, 0, dim_v_, (size_t)dim_u_, dim_s_, (size_t)dim_v_ * dim_u_, lut_bgr);
+    }
+    std::vector<uint8_t> get_coloured_epis(const uint8_t* lut_bgr) const { return get_coloured_epis(detail::own(ctx_), lut_bgr); }
+
     std::vector<float> m_edge_confidence_s_v_u;
     std::vector<uint8_t> m_edge_confidence_mask_s_v_u;
     std::vector<float> m_disp_confidence_s_v_u;
@@ -544,6 +645,22 @@ private:
     {
     }
 #endif
+    // n planes of rows x dim_u out of the [S][V][U] results, under the mask the getters paint with: the edge mask in the
+    // default build (dc.hpp:840-842, :885-887); with par_use_disp_confidence_score, C_d > (float)par_disp_score_threshold
+    // (:832-834, :875-878)
+    std::vector<uint8_t> slices(Context& on, size_t offset, int n, size_t plane_stride, int rows, size_t row_stride, const uint8_t* lut_bgr) const
+    {
+        std::vector<uint8_t> by_score;
+        if (m_parameters.par_use_disp_confidence_score) {
+            by_score.resize(m_disp_confidence_s_v_u.size());
+            for (size_t i = 0; i < by_score.size(); i++)
+                by_score[i] = m_disp_confidence_s_v_u[i] > m_parameters.par_disp_score_threshold ? 255 : 0;
+        }
+        const std::vector<uint8_t>& mask = m_parameters.par_use_disp_confidence_score ? by_score : m_edge_confidence_mask_s_v_u;
+        return detail::render_planes(on.get(), m_best_depth_s_v_u, offset, mask.data(), n, plane_stride, rows, dim_u_, row_stride,
+                                     RSLF_FIT_MINMAX, -1, RSLF_RENDER_SHIFT, lut_bgr);
+    }
+
     Context* ctx_;
     MultiContext* multi_;
     rslf_volume* vol_;
@@ -650,6 +767,33 @@ public:
     {
         out_map_s_v_u = out_map_s_v_u_;
         out_validity_s_v_u = out_validity_s_v_u_;
+    }
+    // rslf_fine_to_coarse.hpp:325-378: the fused disparities of every view through ONE converter, fitted on the fused plane
+    // (int)std::round(S / 2.0) (saturate: 2 % / 98 % quantiles, else min and mean + 12 std), colour-mapped, black where the
+    // fused validity is 0 and, with par_cut_shadows, where the finest level's radiance is in shadow -> [S][V][U][3].
+    // S = 1 throws: the reference's index is then S itself.  The shadow cut reads the EPIs the constructor was given
+    // (into a volume of its own, as the constructor's copy would): their buffers must outlive this call.
+    std::vector<uint8_t> get_coloured_depth_maps(Context& on, const uint8_t* lut_bgr, bool saturate = true) const
+    {
+        int mid = 0;
+        check(rslf_render_centre_index(dim_s_, &mid), "get_coloured_depth_maps");
+        detail::require(!out_map_s_v_u_.empty(), "the getters show the results of run(): call it first");
+        struct Shadow {   // the finest level's radiance on the device, for the time of the call
+            rslf_volume* vol;
+            Shadow() : vol(nullptr) {}
+            ~Shadow() { rslf_volume_destroy(vol); }
+        } shadow;
+        if (m_parameters.par_cut_shadows) {
+            check(rslf_volume_create(on.get(), dim_v_, dim_s_, dim_u_, CHANNELS, &shadow.vol), "rslf_volume_create");
+            detail::upload_epis(shadow.vol, type_, epis_.data(), stride_, scale_);
+        }
+        return detail::render_planes(on.get(), out_map_s_v_u_, 0, out_validity_s_v_u_.data(), dim_s_, (size_t)dim_v_ * dim_u_, dim_v_, dim_u_,
+                                     (size_t)dim_u_, saturate ? RSLF_FIT_QUANTILE : RSLF_FIT_MEANSTD, mid, RSLF_RENDER_AFFINE, lut_bgr,
+                                     shadow.vol, m_parameters.par_shadow_level);
+    }
+    std::vector<uint8_t> get_coloured_depth_maps(const uint8_t* lut_bgr, bool saturate = true) const
+    {
+        return get_coloured_depth_maps(detail::own(ctx_), lut_bgr, saturate);
     }
     int pyramid_depth() const { return n_levels_; }
     rslf_stats stats;

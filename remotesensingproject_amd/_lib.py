@@ -37,6 +37,7 @@ SYMBOLS = [
     "rslf_multi_fine_to_coarse_run_host_u16",
     # rendering (K6)
     "rslf_render_fit", "rslf_render_planes", "rslf_render_epi_lines", "rslf_render_centre_index", "rslf_render_scaled_row",
+    "rslf_render_fit_many", "rslf_render_planes_each", "rslf_render_planes_host", "rslf_render_epi_lines_host",
 ]
 
 
@@ -196,6 +197,11 @@ def lib():
     L.rslf_render_fit.argtypes = [vp, vp, ci, ci, C.c_size_t, vp, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rslf_render_planes.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, C.c_size_t, C.c_double, C.c_double, ci, vp, vp, ci, vp, ci, ci, cf, vp]
     L.rslf_render_epi_lines.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.rslf_render_epi_lines_host.argtypes = L.rslf_render_epi_lines.argtypes
+    L.rslf_render_fit_many.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, C.c_size_t, vp, ci, C.POINTER(C.c_double)]
+    L.rslf_render_planes_each.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, C.c_size_t, C.POINTER(C.c_double), ci, vp, vp, ci, vp, ci, ci, cf, vp]
+    L.rslf_render_planes_host.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, C.c_size_t, vp, ci, ci, ci, ci, vp, ci, vp, ci, ci, cf, vp,
+                                          C.POINTER(C.c_double)]
     L.rslf_render_centre_index.argtypes = [ci, C.POINTER(ci)]
     L.rslf_render_scaled_row.argtypes = [ci, ci, ci, C.POINTER(ci)]
     L.rslf_edge_confidence_2d.argtypes = [vp, vp, C.POINTER(RslfParams), vp, vp]

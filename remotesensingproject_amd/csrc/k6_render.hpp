@@ -5,7 +5,9 @@
 //   fit      the two numbers an ImageConverter_uchar holds: min / max, double sums for mean / std, or two order statistics
 //            by an exact radix select over order-preserving keys (integer counts: the result does not depend on the
 //            order in which workgroups arrive)
-//   planes   level -> table -> mask -> shadow cut for a stack of planes in one launch, four adjacent pixels per lane
+//            -- for a whole stack of planes in the same launches: the plane is blockIdx.y, every plane has its own state
+//   planes   level -> table -> mask -> shadow cut for a stack of planes in one launch, four adjacent pixels per lane,
+//            through one range for all planes or one per plane
 //   lines    the z-buffered EPI lines of get_coloured_epi, one workgroup per (scanline, view) row
 //
 // All three are bandwidth-bound; none uses a float atomic.  Float formulas are single IEEE operations in the reference's
@@ -14,18 +16,28 @@
 
 #include "rslf_device.hpp"
 #include "rslf_plan.hpp"
+#include "rslf_plan_render.hpp"
 
 namespace rslf {
 
 // A plane of rows x cols floats, `row_stride` elements between rows (row v of an [S][V][U] stack is an S x U plane), and
-// its validity bytes with the same strides (nullable): a pixel whose byte is 0 counts as 0.0f.
+// its validity bytes with the same strides (nullable): a pixel whose byte is 0 counts as 0.0f.  In a batch plane k
+// starts `plane_stride` elements after plane k - 1.
 struct PlaneView {
     const float* p;
     const uint8_t* valid;
     int rows, cols;
-    long long row_stride;
-    int vec;   // cols and row_stride multiples of 4, p 16-byte and valid 4-byte aligned: a quad is one 16-byte load
+    long long row_stride, plane_stride;
+    int vec;   // cols and both strides multiples of 4, p 16-byte and valid 4-byte aligned: a quad is one 16-byte load
 };
+
+__device__ __forceinline__ PlaneView plane_of(PlaneView pv, int k)   // plane k of the batch
+{
+    pv.p += (long long)k * pv.plane_stride;
+    if (pv.valid)
+        pv.valid += (long long)k * pv.plane_stride;
+    return pv;
+}
 
 // Pixels 4q .. 4q + 3 of the plane's row-major order (n = rows * cols of them); returns how many exist.
 __device__ __forceinline__ int load_quad(const PlaneView& pv, int q, int n, float (&x)[4])
@@ -60,8 +72,10 @@ __device__ __forceinline__ int load_quad(const PlaneView& pv, int q, int n, floa
 
 // ---- fit: min / max / double sums -----------------------------------------------------------------------------------
 // cv::minMaxLoc and cv::meanStdDev's sums (rslf_plot.cpp:52-53, :88-91).  Every thread sums its pixels in double in a
-// fixed order, the workgroup adds its threads in a fixed tree, and k6_fit_reduce adds the workgroups' partials of the
-// slab in a fixed order: the same bits on every run (no atomics).
+// fixed order, the workgroup adds its threads in a fixed tree, and k6_fit_reduce adds the partials of the slab in a
+// fixed order: the same bits on every run (no atomics).  The unit of that order is the SUM BLOCK: a plane of n pixels
+// has `blocks` = plan::fit_blocks(n) of them, whatever the launch; the workgroups of plane blockIdx.y (gridDim.x of
+// them, plan::fit_batch_groups) share its sum blocks, so a plane's sums do not depend on the batch it is fitted in.
 struct FitPartial {
     double sum, sumsq;
     float mn, mx;
@@ -93,32 +107,38 @@ __device__ __forceinline__ void fit_block_reduce(FitPartial acc, FitPartial* __r
         *dst = sh[0];
 }
 
-__global__ __launch_bounds__(plan::kFitBlock) void k6_fit_stats(PlaneView pv, int n, FitPartial* __restrict__ slab)
+__global__ __launch_bounds__(plan::kFitBlock) void k6_fit_stats(PlaneView batch, int n, int blocks, FitPartial* __restrict__ slab)
 {
+    const PlaneView pv = plane_of(batch, blockIdx.y);
     const int quads = (n + 3) / 4;
-    FitPartial acc{0.0, 0.0, INFINITY, -INFINITY};
-    for (int q = blockIdx.x * plan::kFitBlock + threadIdx.x; q < quads; q += gridDim.x * plan::kFitBlock) {
-        float x[4];
-        const int cnt = load_quad(pv, q, n, x);
+    for (int b = blockIdx.x; b < blocks; b += gridDim.x) {   // the same for the whole workgroup
+        FitPartial acc{0.0, 0.0, INFINITY, -INFINITY};
+        for (int q = b * plan::kFitBlock + threadIdx.x; q < quads; q += blocks * plan::kFitBlock) {
+            float x[4];
+            const int cnt = load_quad(pv, q, n, x);
 #pragma unroll
-        for (int j = 0; j < 4; j++)
-            if (j < cnt) {
-                const double d = (double)x[j];
-                acc.sum += d;
-                acc.sumsq += d * d;
-                acc.mn = fminf(acc.mn, x[j]);
-                acc.mx = fmaxf(acc.mx, x[j]);
-            }
+            for (int j = 0; j < 4; j++)
+                if (j < cnt) {
+                    const double d = (double)x[j];
+                    acc.sum += d;
+                    acc.sumsq += d * d;
+                    acc.mn = fminf(acc.mn, x[j]);
+                    acc.mx = fmaxf(acc.mx, x[j]);
+                }
+        }
+        fit_block_reduce(acc, slab + (long long)blockIdx.y * blocks + b);
+        __syncthreads();   // the tree's LDS is free again
     }
-    fit_block_reduce(acc, slab + blockIdx.x);
 }
 
+// One workgroup per plane: slab [plane][blocks] -> out [plane]
 __global__ __launch_bounds__(plan::kFitBlock) void k6_fit_reduce(const FitPartial* __restrict__ slab, int blocks, FitPartial* __restrict__ out)
 {
+    const FitPartial* mine = slab + (long long)blockIdx.x * blocks;
     FitPartial acc{0.0, 0.0, INFINITY, -INFINITY};
     for (int i = threadIdx.x; i < blocks; i += plan::kFitBlock)
-        fit_combine(acc, slab[i]);
-    fit_block_reduce(acc, out);
+        fit_combine(acc, mine[i]);
+    fit_block_reduce(acc, out + blockIdx.x);
 }
 
 // ---- fit: two order statistics by radix select ------------------------------------------------------------------------
@@ -128,22 +148,24 @@ __global__ __launch_bounds__(plan::kFitBlock) void k6_fit_reduce(const FitPartia
 // in LDS, merged with one integer atomic per non-empty bin), k6_select_narrow picks each rank's bin
 // (plan::radix_bin_holds), extends its prefix, and zeroes the histograms for the next pass.  After plan::kRadixPasses
 // passes the prefixes are the keys.  While both ranks share a prefix one histogram serves both.
+// A batch keeps one state per plane (st[plane]); k6_select_count has the plane on blockIdx.y, the two one-workgroup
+// kernels run one workgroup per plane.  The keys come out as out[plane][2].
 struct SelectState {
     uint32_t hist[2][plan::kRadixBins];
     uint32_t prefix[2];
     uint32_t rank[2];
-    float out[2];
 };
+static_assert(sizeof(SelectState) == plan::kSelectStateBytes && sizeof(FitPartial) == plan::kFitPartialBytes, "rslf_plan_render.hpp sizes the scratch");
 
 __global__ __launch_bounds__(plan::kRadixBins) void k6_select_init(SelectState* st, uint32_t rank_lo, uint32_t rank_hi)
 {
     const int t = threadIdx.x;
+    st += blockIdx.x;
     st->hist[0][t] = 0;
     st->hist[1][t] = 0;
     if (t < 2) {
         st->prefix[t] = 0;
         st->rank[t] = t ? rank_hi : rank_lo;
-        st->out[t] = 0.0f;
     }
 }
 
@@ -169,10 +191,12 @@ __device__ __forceinline__ void hist_add(uint32_t* h, bool on, uint32_t d)
         atomicAdd(&h[d], 1u);
 }
 
-__global__ __launch_bounds__(plan::kFitBlock) void k6_select_count(PlaneView pv, int n, int pass, SelectState* st)
+__global__ __launch_bounds__(plan::kFitBlock) void k6_select_count(PlaneView batch, int n, int pass, SelectState* st)
 {
     __shared__ uint32_t h[2][plan::kRadixBins];
     const int t = threadIdx.x;
+    const PlaneView pv = plane_of(batch, blockIdx.y);
+    st += blockIdx.y;
     static_assert(plan::kFitBlock == plan::kRadixBins, "one thread per bin");
     h[0][t] = 0;
     h[1][t] = 0;
@@ -200,10 +224,11 @@ __global__ __launch_bounds__(plan::kFitBlock) void k6_select_count(PlaneView pv,
         atomicAdd(&st->hist[1][t], h[1][t]);
 }
 
-__global__ __launch_bounds__(plan::kRadixBins) void k6_select_narrow(SelectState* st, int pass)
+__global__ __launch_bounds__(plan::kRadixBins) void k6_select_narrow(SelectState* st, int pass, float* __restrict__ out)
 {
     __shared__ uint32_t scan[plan::kRadixBins];
     const int t = threadIdx.x;
+    st += blockIdx.x;
     const uint32_t p[2] = {st->prefix[0], st->prefix[1]}, rk[2] = {st->rank[0], st->rank[1]};
     const bool same = p[0] == p[1];
     uint32_t c[2];
@@ -227,7 +252,7 @@ __global__ __launch_bounds__(plan::kRadixBins) void k6_select_narrow(SelectState
             st->prefix[r] = np;
             st->rank[r] = rk[r] - before;
             if (pass == plan::kRadixPasses - 1)
-                st->out[r] = __uint_as_float(plan::radix_key_inverse(np));
+                out[2 * blockIdx.x + r] = __uint_as_float(plan::radix_key_inverse(np));
         }
         __syncthreads();
     }
@@ -280,10 +305,11 @@ struct RenderArgs {
     long long plane_stride, row_stride;
     int rows, cols, quads_per_row;
     float a, b;             // plan::render_consts
+    const float2* ab;       // nullable: plan::render_consts of every plane, (a, b)[n_planes], in place of a, b
     int affine;             // RSLF_RENDER_AFFINE
     int zero_value;         // RSLF_MASK_ZERO_VALUE (else RSLF_MASK_BLACK)
     VolView vol;            // the shadow cut's volume (C > 0)
-    int slice_epi, index;   // RSLF_SLICE_*
+    int slice_epi, index;   // RSLF_SLICE_*: plane k is view index + k, or scanline index + k
     float shadow_level;
 };
 
@@ -303,6 +329,7 @@ __global__ __launch_bounds__(plan::kRenderBlock) void k6_render_planes(RenderArg
     const int r = (int)(q / A.quads_per_row), u0 = (int)(q - (long long)r * A.quads_per_row) * 4;
     const int cnt = min(4, A.cols - u0);
     const long long o = (long long)k * A.plane_stride + (long long)r * A.row_stride + u0;
+    const float a = A.ab ? A.ab[k].x : A.a, b = A.ab ? A.ab[k].y : A.b;
     float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     uint32_t m = 0xffffffffu;   // a byte per pixel
     if (VEC) {
@@ -324,12 +351,12 @@ __global__ __launch_bounds__(plan::kRenderBlock) void k6_render_planes(RenderArg
     for (int j = 0; j < 4; j++) {
         const bool ok = ((m >> (8 * j)) & 255u) != 0;
         const float xv = (!ok && A.zero_value) ? 0.0f : x[j];   // rslf_fine_to_coarse.hpp:458-459: before the level is taken
-        e[j] = lut[level_of(xv, A.a, A.b, A.affine)];
+        e[j] = lut[level_of(xv, a, b, A.affine)];
         if (!ok && !A.zero_value)                                // :356, :514: black after the look-up
             e[j] = 0;
     }
     if (C > 0) {   // :360-372, :466-481, applied last
-        const int s = A.slice_epi ? r : A.index + k, v = A.slice_epi ? A.index : r;
+        const int s = A.slice_epi ? r : A.index + k, v = A.slice_epi ? A.index + k : r;
         const float4* rad = reinterpret_cast<const float4*>(A.vol.row(v, s) + (long long)u0 * C);
         float f[4 * (C > 0 ? C : 1)];
 #pragma unroll

@@ -213,11 +213,12 @@ struct rslf_ctx {
     float* filtered = nullptr;    // [V][U] median of the visited view, the propagation's source
     size_t sweep_cap = 0;         // entries winner / sweep_mask can hold (S*V*U)
     size_t sweep_plane_cap = 0;   // floats `filtered` can hold (V*U)
-    // grow-only scratch of the once-per-level helpers (pyramid, tightening, fusion): reused across calls, so
-    // these helpers neither allocate nor free -- and so never force a device-wide synchronisation
-    static constexpr int kHelperSlots = 4;
-    void* helper[kHelperSlots] = {nullptr, nullptr, nullptr, nullptr};
-    size_t helper_cap[kHelperSlots] = {0, 0, 0, 0};
+    // grow-only scratch of the once-per-level helpers (pyramid, tightening, fusion) and of the renderers (slots 4 .. 6: the
+    // staging of their host-pointer forms): reused across calls, so these helpers neither allocate nor free -- and so
+    // never force a device-wide synchronisation
+    static constexpr int kHelperSlots = 7;
+    void* helper[kHelperSlots] = {};
+    size_t helper_cap[kHelperSlots] = {};
 };
 
 struct rslf_volume {

@@ -378,6 +378,49 @@ def render_planes(ctx: Context, planes: torch.Tensor, vmin: float, vmax: float, 
     return out
 
 
+def _stack_args(planes: torch.Tensor, valid: torch.Tensor | None, who: str) -> tuple:
+    """(n, plane_stride, rows, cols, row_stride) of a [n, rows, cols] float32 stack read in place, as the C entries take it."""
+    if planes.dim() != 3 or planes.dtype != torch.float32 or (valid is not None and valid.dtype != torch.uint8):
+        raise ValueError("%s takes 3-D float32 planes and a uint8 mask" % who)
+    stride = _strided(planes)
+    if valid is not None:
+        _strided(valid, planes)
+    n, rows, cols = planes.shape
+    return n, stride[0] if n > 1 else 0, rows, cols, stride[1] if rows > 1 else cols
+
+
+def render_fit_many(ctx: Context, planes: torch.Tensor, valid: torch.Tensor | None = None, mode: int = FIT_MINMAX) -> list:
+    """rslf_render_fit_many: render_fit for every plane of a [n, rows, cols] float32 stack (n <= 65535) -> a list of n
+    (min, max), each bit for bit render_fit's for that plane alone, in launches whose number does not depend on n, one
+    copy and one wait.  The stack is read in place through its strides: depth_s_v_u for every view,
+    depth_s_v_u.permute(1, 0, 2) for every EPI slice.  `valid`: uint8, same shape and strides."""
+    n, plane_stride, rows, cols, row_stride = _stack_args(planes, valid, "render_fit_many")
+    out = (C.c_double * (2 * max(n, 1)))()
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_render_fit_many(ctx._h, _ptr(planes), n, plane_stride, rows, cols, row_stride, _ptr(valid), int(mode), out),
+          "rslf_render_fit_many")
+    return [(float(out[2 * k]), float(out[2 * k + 1])) for k in range(n)]
+
+
+def render_planes_each(ctx: Context, planes: torch.Tensor, minmax, formula: int, lut_bgr, valid: torch.Tensor | None = None,
+                       mask_mode: int = MASK_BLACK, vol: "Volume | None" = None, slice_kind: int = SLICE_VIEW, index: int = 0,
+                       shadow_level: float = 0.0) -> torch.Tensor:
+    """rslf_render_planes_each: render_planes with plane k scaled over minmax[k] = (min, max) (as render_fit_many returns
+    them) -> [n, rows, cols, 3] uint8 BGR in one launch.  With SLICE_EPI plane k is scanline index + k of `vol`."""
+    n, plane_stride, rows, cols, row_stride = _stack_args(planes, valid, "render_planes_each")
+    mm = np.ascontiguousarray(minmax, dtype=np.float64)
+    if mm.shape != (n, 2):
+        raise ValueError("minmax must hold one (min, max) per plane")
+    table = _table(lut_bgr)
+    out = torch.empty((n, rows, cols, 3), dtype=torch.uint8, device=planes.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_render_planes_each(
+        ctx._h, _ptr(planes), n, plane_stride, rows, cols, row_stride, mm.ctypes.data_as(C.POINTER(C.c_double)), int(formula),
+        table.ctypes.data_as(C.c_void_p), _ptr(valid), int(mask_mode), vol._h if vol is not None else None, int(slice_kind), int(index),
+        float(shadow_level), _ptr(out)), "rslf_render_planes_each")
+    return out
+
+
 def render_epi_lines(ctx: Context, depth_v_u: torch.Tensor, mask_v_u: torch.Tensor, S: int, s_hat: int, v_first: int, n_rows: int,
                      lut_bgr) -> torch.Tensor:
     """rslf_render_epi_lines: the z-buffered EPI lines of get_coloured_epi for scanlines v_first .. v_first + n_rows - 1 of
@@ -808,6 +851,20 @@ class Depth2DComputer:
         plane, mask = self.m_best_depth_s_v_u[a_s], self._confidence_mask_s_v_u()[a_s]
         lo, hi = render_fit(vol.ctx, plane, None, FIT_MINMAX)
         return render_planes(vol.ctx, plane.unsqueeze(0), lo, hi, RENDER_SHIFT, lut_bgr, mask.unsqueeze(0), MASK_BLACK)[0]
+
+    def _coloured_stack(self, planes: torch.Tensor, mask: torch.Tensor, lut_bgr) -> torch.Tensor:
+        ctx = self.m_epis.ctx
+        return render_planes_each(ctx, planes, render_fit_many(ctx, planes, None, FIT_MINMAX), RENDER_SHIFT, lut_bgr, mask, MASK_BLACK)
+
+    def get_disparity_maps(self, lut_bgr=None) -> torch.Tensor:
+        """get_disparity_map(a_s) for every view a_s (the loop of the reference's demo, tests/test_depth_computation_2d.cpp:77)
+        -> [S, V, U, 3] uint8 BGR: one batch of fits and one render launch, each view over its own min / max."""
+        return self._coloured_stack(self.m_best_depth_s_v_u, self._confidence_mask_s_v_u(), lut_bgr)
+
+    def get_coloured_epis(self, lut_bgr=None) -> torch.Tensor:
+        """get_coloured_epi(a_v) for every scanline a_v -> [V, S, U, 3] uint8 BGR: one batch of fits and one render launch.
+        The S x U slices are read in place through their strides; the volume is not copied."""
+        return self._coloured_stack(self.m_best_depth_s_v_u.permute(1, 0, 2), self._confidence_mask_s_v_u().permute(1, 0, 2), lut_bgr)
 
     def get_valid_depths_mask_s_v_u(self) -> torch.Tensor:
         """dc.hpp:893-915, default build: C_e > edge threshold (or everything > -1 with accept_all)."""

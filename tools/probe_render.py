@@ -8,7 +8,15 @@ context's stream after a warm-up:
         moves in all, half of them read and half written,
 and, as the yardstick, what a user had to do before these entries existed: the same planes, masks and radiances copied to
 the host and pushed through tests/render_ref.py's vectorised numpy path on 16 threads.  Medians over --runs runs.
-    python tools/probe_render.py [--runs 5] [--planes 101] [--no-cpu] [--channels 1,3]"""
+    python tools/probe_render.py [--runs 5] [--planes 101] [--no-cpu] [--channels 1,3]
+
+With --batch CONFIGS (names of remotesensingproject_amd.synth.CONFIGS, e.g. c2,c3) it times instead, on the result of one
+Depth2DComputer run per config, every view's disparity map and every scanline's coloured EPI
+  (a) through the batch getters (get_disparity_maps / get_coloured_epis: one batch of fits, one wait, one render launch),
+  (b) through a loop of the single getters (get_disparity_map(s) / get_coloured_epi(v): a fit, a wait and a render per plane),
+as host wall time from the call to the end of torch.cuda.synchronize() (the fits wait on the host, so the waits are what
+is being measured), medians over --runs runs after a warm-up, and checks that both give the same bytes.
+    python tools/probe_render.py --batch c2,c3 [--runs 5]"""
 import argparse
 import json
 import os
@@ -31,6 +39,7 @@ ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--planes", type=int, default=101)
 ap.add_argument("--channels", default="1,3")
 ap.add_argument("--no-cpu", action="store_true")
+ap.add_argument("--batch", default="", help="configs whose sweep shape the batch getters are timed on against a loop of the single ones")
 args = ap.parse_args()
 
 V, U, S = 1080, 1920, args.planes
@@ -64,7 +73,59 @@ def clocks():
         return ["rocm-smi not available: %s" % e]
 
 
+def wall(fn, runs):
+    """Median milliseconds of host wall time of fn() up to the end of a device synchronise, after one warm-up."""
+    out = []
+    for i in range(runs + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        keep = fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+        if i < runs:
+            del keep
+    return statistics.median(out[1:]), out[1:], keep
+
+
+def probe_batch(names):
+    from remotesensingproject_amd.synth import CONFIGS, make_lightfield
+    result = {"runs": args.runs}
+    for name in names:
+        cfg = CONFIGS[name]
+        U_, V_, S_, C_, D_ = cfg["U"], cfg["V"], cfg["S"], cfg["C"], cfg["D"]
+        field, _ = make_lightfield(U_, V_, S_, C_, seed=cfg["seed"], dmin=cfg["dmin"], dmax=cfg["dmax"])
+        comp = rs.Depth2DComputer(rs.Volume.from_dense(torch.from_numpy(field).cuda(), 1.0, ctx), cfg["dmin"], cfg["dmax"], D_)
+        del field
+        comp.run(want_stats=False)
+        torch.cuda.synchronize()
+        row = {"shape": [S_, V_, U_]}
+        for what, n, batch, loop in (
+                ("disparity_maps", S_, lambda: comp.get_disparity_maps(lut), lambda: [comp.get_disparity_map(s, lut) for s in range(S_)]),
+                ("coloured_epis", V_, lambda: comp.get_coloured_epis(lut), lambda: [comp.get_coloured_epi(v, lut) for v in range(V_)])):
+            b_ms, b_all, b_out = wall(batch, args.runs)
+            l_ms, l_all, l_out = wall(loop, args.runs)
+            same = all(torch.equal(b_out[k], l_out[k]) for k in range(n))
+            del b_out, l_out
+            one = rs.FIT_MINMAX   # the getters' fit: two launches, a copy and a wait
+            f_ms, _, _ = wall(lambda: rs.render_fit(ctx, comp.m_best_depth_s_v_u[0] if what == "disparity_maps" else
+                                                    comp.m_best_depth_s_v_u[:, 0, :], None, one), args.runs)
+            n_bytes = S_ * V_ * U_ * (4 + 4 + 1 + 3)   # fit: 4 B read; render: 4 B + 1 B mask read, 3 B written
+            print("%s %s: %d planes of %s -- batch median %.3f ms %s | loop median %.3f ms %s | loop / batch %.1f | one fit alone %.3f ms | "
+                  "%.1f MB algorithmic, batch at %.1f GB/s | same bytes: %s" % (
+                      name, what, n, "%d x %d" % ((V_, U_) if what == "disparity_maps" else (S_, U_)), b_ms, ["%.3f" % m for m in b_all],
+                      l_ms, ["%.3f" % m for m in l_all], l_ms / b_ms, f_ms, n_bytes / 1e6, n_bytes / b_ms / 1e6, same), flush=True)
+            row[what] = {"planes": n, "batch_ms": b_ms, "loop_ms": l_ms, "one_fit_ms": f_ms, "bytes": n_bytes, "equal": bool(same)}
+        result[name] = row
+        del comp
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
 print("clock state before:", *clocks(), sep="\n  ")
+if args.batch:
+    probe_batch(args.batch.split(","))
+    print("clock state after:", *clocks(), sep="\n  ")
+    sys.exit(0)
 gen = torch.Generator(device=dev).manual_seed(5)
 # disparity-like planes: a grid of 256 hypotheses in [-2, 5.97], a third of the pixels exact zeros
 planes = (torch.randint(0, 256, (S, V, U), device=dev, generator=gen).to(torch.float32) * 0.03125 - 2.0)
