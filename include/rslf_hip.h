@@ -56,7 +56,7 @@ typedef enum rslf_status {
  * and the kernel is BandwidthKernel(h) (src/rslf_kernels.cpp:16-54), h = kernel_bandwidth. */
 typedef struct rslf_params {
     float edge_score_threshold;         /* 0.02 */
-    float line_score_threshold;         /* 0.02  (unused by this path, kept for 1:1 layout) */
+    float line_score_threshold;         /* 0.02  (the gate of RSLF_LINE_CONF_GATE sweeps) */
     float disp_score_threshold;         /* 0.01  (only with use_disp_confidence_score) */
     float raw_score_threshold;          /* 0 */
     float mean_shift_max_iter;          /* 10; a float in the reference (:115) */
@@ -382,6 +382,57 @@ int rslf_sweep_end(rslf_ctx* ctx, int ok, int dim_d, rslf_stats* stats);
 int rslf_depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                      float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                      float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats);
+
+/* ---- the line confidence C_l of the 2-D sweep (K7) ------------------------ */
+/* The reference's third criterion, C_l = sum_s C_e(s) K(r_s - rbar) / sum_s K(r_s - rbar) along a pixel's EPI line
+ * (report/rs_report.tex:700-704), as compute_2D_depth_epi computes it under -D_USE_LINE_CONFIDENCE_SCORE
+ * (core.hpp:1032-1081) and carries it along the propagation (:1122-1124).  The places that would GATE on it
+ * (core.hpp:1099, dc.hpp:841, :881, :903) sit behind an `#elseif` typo inside a skipped group and are never compiled:
+ * OFF       the default build: no line confidence, exactly the launches of rslf_depth_epi_2d.
+ * AS_BUILT  what the macro compiles to: the planes are computed and carried, the gate stays the edge mask, every other
+ *           plane is bit for bit the OFF result.
+ * GATE      what the `#elseif` branches say: a pixel is a source of the propagation iff C_l > (float)line_score_threshold
+ *           (no edge-mask test, as core.hpp:1100 has none).
+ * With use_disp_confidence_score the #ifdef chain gives C_d the gate in every mode; C_l is still computed and carried. */
+#define RSLF_LINE_CONF_OFF       0
+#define RSLF_LINE_CONF_AS_BUILT  1
+#define RSLF_LINE_CONF_GATE      2
+
+/* core.hpp:1054-1079 for one visited view on caller planes: for every pixel of d_Ce_mask_vu ([V][U]),
+ *   I = (float)((double)(s_hat - s) * (double)depth + (double)u)  (:1058, one gemm; no slope_factor, as written)
+ *   E = max(lerp of d_Ce_svu[s][v][.] at I, 0), NaN outside [0, U-1] -> 0  (:1069-1071, interp.hpp:155-193)
+ *   d_Cl_vu = sum_s E K / sum_s K, float sums with s ascending, x / 0 -> 0  (:1074-1079)
+ * with K = d_K_vsu [V][S][U].  d_Ce_svu is [S][V][U], d_depth_vu [V][U].  Pixels outside the mask keep what d_Cl_vu held.
+ * A disparity that is NaN or sends I beyond the int range neither faults nor hangs; what it gives is unspecified. */
+int rslf_line_confidence_pile(rslf_ctx* ctx, int V, int S, int U, int s_hat, const float* d_Ce_svu, const float* d_K_vsu,
+                              const float* d_depth_vu, const uint8_t* d_Ce_mask_vu, float* d_Cl_vu);
+
+/* Line confidence is state of an open sweep: valid between rslf_sweep_begin and the first visit, cleared by
+ * rslf_sweep_end.  mode: RSLF_LINE_CONF_*; d_Cl_svu: the [S][V][U] plane the visits fill and the propagation paints
+ * (a_line_confidence_s_v_u, core.hpp:345; dc.hpp:737 leaves it uninitialised: pass zeros), required for mode >= 1.
+ * Sizes the sweep-long K(r - rbar) columns [V][S][U] (core.hpp:975-979; zero-filled here, uninitialised there) and the
+ * visits' arg-max plane in the context's grow-only scratch: no visit allocates.  A visit is then
+ *   AS_BUILT  scan -> median + claims -> K7 -> apply
+ *   GATE      scan -> median -> K7 -> median + claims gated by C_l -> apply  (with use_disp_confidence_score, where C_d
+ *             gates: the AS_BUILT order)
+ * RSLF_ERR_INVALID_ARG: a mode outside 0..2, a NULL plane with mode >= 1, a call outside that window. */
+int rslf_sweep_line_confidence(rslf_ctx* ctx, const rslf_volume* vol, int mode, float* d_Cl_svu);
+
+/* rslf_depth_epi_2d, rslf_depth2d_run and rslf_depth2d_run_host with the reference's extra argument
+ * a_line_confidence_s_v_u (core.hpp:345, handed over at dc.hpp:791-792; allocated at dc.hpp:721-738): the existing
+ * signature plus line_mode (RSLF_LINE_CONF_*) and the [S][V][U] plane (NULL allowed with mode 0, which is the plain
+ * entry).  rslf_depth2d_run_lc also zero-fills d_Cl_svu (dc.hpp:737 leaves it uninitialised). */
+int rslf_depth_epi_2d_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                         float dmin, float dmax, int dim_d,
+                         float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                         float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats,
+                         int line_mode, float* d_Cl_svu);
+int rslf_depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                        float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                        float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu);
+int rslf_depth2d_run_host_lc(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                             float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                             float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu);
 
 /* ---- "next" row: fine-to-coarse ---------------------- */
 /* rslf::FineToCoarse<T> (include/rslf_fine_to_coarse.hpp:26-81) is a host-side loop over pyramid

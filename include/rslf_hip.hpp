@@ -63,6 +63,10 @@ struct Depth1DParameters {
     float par_kernel_bandwidth;   // BandwidthKernel(_BANDWIDTH_KERNEL_PARAMETER), core.hpp:78
     int par_interpolation_class;  // RSLF_INTERP_*: stands for the Interpolation1DClass* of core.hpp:108 (default Linear, :76)
     bool par_use_disp_confidence_score;   // the reference's build switch _USE_DISP_CONFIDENCE_SCORE (core.hpp:35), off by default
+    // the reference's build switch _USE_LINE_CONFIDENCE_SCORE (core.hpp:1032-1081) as a mode of Depth2DComputer:
+    // RSLF_LINE_CONF_OFF (default) | _AS_BUILT (C_l computed and carried, the gate stays the edge mask) | _GATE (propagation
+    // and getters under C_l > par_line_score_threshold).  Host side only: no member of rslf_params.
+    int par_line_confidence_mode;
 
     Depth1DParameters()
     {
@@ -85,6 +89,7 @@ struct Depth1DParameters {
         par_kernel_bandwidth = p.kernel_bandwidth;
         par_interpolation_class = p.interpolation;
         par_use_disp_confidence_score = p.use_disp_confidence_score != 0;
+        par_line_confidence_mode = RSLF_LINE_CONF_OFF;
     }
 
     static Depth1DParameters& get_default()
@@ -567,6 +572,8 @@ public:
         m_best_depth_s_v_u.assign(n, 0.f);
         m_rbar_s_v_u.assign(n * CHANNELS, 0.f);
         const rslf_params p = m_parameters.to_c();
+        const int line_mode = m_parameters.par_line_confidence_mode;
+        detail::require(!multi_ || line_mode == RSLF_LINE_CONF_OFF, "Depth2DComputer: line confidence runs on one device");
         if (multi_) {
             if (type_ == InputType::U8)
                 check(rslf_multi_depth2d_run_u8(multi_->get(), (const uint8_t* const*)epis_.data(), stride_, dim_v_, dim_s_, dim_u_, CHANNELS,
@@ -586,6 +593,15 @@ public:
                                                  m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
                                                  m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), nullptr, &stats, nullptr),
                       "rslf_multi_depth2d_run_f32");
+            return;
+        }
+        if (line_mode != RSLF_LINE_CONF_OFF) {   // dc.hpp:721-738, :791-792
+            m_line_confidence_s_v_u.assign(n, 0.f);
+            check(rslf_depth2d_run_host_lc(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
+                                           m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
+                                           m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
+                                           m_line_confidence_s_v_u.data()),
+                  "rslf_depth2d_run_host_lc");
             return;
         }
         check(rslf_depth2d_run_host(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
@@ -632,6 +648,7 @@ public:
     std::vector<float> m_edge_confidence_s_v_u;
     std::vector<uint8_t> m_edge_confidence_mask_s_v_u;
     std::vector<float> m_disp_confidence_s_v_u;
+    std::vector<float> m_line_confidence_s_v_u;   // filled with par_line_confidence_mode >= 1 (dc.hpp:737), else empty
     std::vector<float> m_rbar_s_v_u;
     std::vector<float> m_best_depth_s_v_u;
     rslf_stats stats;
@@ -647,7 +664,7 @@ private:
 #endif
     // n planes of rows x dim_u out of the [S][V][U] results, under the mask the getters paint with: the edge mask in the
     // default build (dc.hpp:840-842, :885-887); with par_use_disp_confidence_score, C_d > (float)par_disp_score_threshold
-    // (:832-834, :875-878)
+    // (:832-834, :875-878); else with RSLF_LINE_CONF_GATE, C_l > (float)par_line_score_threshold (:842, :883)
     std::vector<uint8_t> slices(Context& on, size_t offset, int n, size_t plane_stride, int rows, size_t row_stride, const uint8_t* lut_bgr) const
     {
         std::vector<uint8_t> by_score;
@@ -656,7 +673,14 @@ private:
             for (size_t i = 0; i < by_score.size(); i++)
                 by_score[i] = m_disp_confidence_s_v_u[i] > m_parameters.par_disp_score_threshold ? 255 : 0;
         }
-        const std::vector<uint8_t>& mask = m_parameters.par_use_disp_confidence_score ? by_score : m_edge_confidence_mask_s_v_u;
+        const bool by_line = !m_parameters.par_use_disp_confidence_score && m_parameters.par_line_confidence_mode == RSLF_LINE_CONF_GATE;
+        if (by_line) {
+            detail::require(m_line_confidence_s_v_u.size() == m_best_depth_s_v_u.size(), "the line confidence is filled by run()");
+            by_score.resize(m_line_confidence_s_v_u.size());
+            for (size_t i = 0; i < by_score.size(); i++)
+                by_score[i] = m_line_confidence_s_v_u[i] > m_parameters.par_line_score_threshold ? 255 : 0;
+        }
+        const std::vector<uint8_t>& mask = (m_parameters.par_use_disp_confidence_score || by_line) ? by_score : m_edge_confidence_mask_s_v_u;
         return detail::render_planes(on.get(), m_best_depth_s_v_u, offset, mask.data(), n, plane_stride, rows, dim_u_, row_stride,
                                      RSLF_FIT_MINMAX, -1, RSLF_RENDER_SHIFT, lut_bgr);
     }

@@ -38,6 +38,8 @@ SYMBOLS = [
     # rendering (K6)
     "rslf_render_fit", "rslf_render_planes", "rslf_render_epi_lines", "rslf_render_centre_index", "rslf_render_scaled_row",
     "rslf_render_fit_many", "rslf_render_planes_each", "rslf_render_planes_host", "rslf_render_epi_lines_host",
+    # line confidence of the 2-D sweep (K7)
+    "rslf_line_confidence_pile", "rslf_sweep_line_confidence", "rslf_depth_epi_2d_lc", "rslf_depth2d_run_lc", "rslf_depth2d_run_host_lc",
 ]
 
 
@@ -207,6 +209,11 @@ def lib():
     L.rslf_edge_confidence_2d.argtypes = [vp, vp, C.POINTER(RslfParams), vp, vp]
     L.rslf_depth_epi_2d.argtypes = [vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp, vp, C.POINTER(RslfParams), vp, C.POINTER(RslfStats)]
     L.rslf_depth2d_run.argtypes = [vp, vp, cf, cf, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, vp, C.POINTER(RslfStats)]
+    L.rslf_line_confidence_pile.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.rslf_sweep_line_confidence.argtypes = [vp, vp, ci, vp]
+    L.rslf_depth_epi_2d_lc.argtypes = L.rslf_depth_epi_2d.argtypes + [ci, vp]
+    L.rslf_depth2d_run_lc.argtypes = L.rslf_depth2d_run.argtypes + [ci, vp]
+    L.rslf_depth2d_run_host_lc.argtypes = L.rslf_depth2d_run_host.argtypes + [ci, vp]
     for name in SYMBOLS:
         f = getattr(L, name)   # AttributeError here = the library does not export the ABI
         if f.restype is C.c_int and name not in ("rslf_abi_version", "rslf_device_count"):

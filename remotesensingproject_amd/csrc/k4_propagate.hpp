@@ -195,7 +195,8 @@ __global__ __launch_bounds__(256) void k34_median_claim(VolView vol, int s_hat, 
 __device__ __forceinline__ void apply_segment(long long r, int seg, int V, int U, const float* __restrict__ filtered_vu,
                                               const float* __restrict__ Cd_hat_vu, float* __restrict__ depth_svu,
                                               float* __restrict__ Cd_svu, uint8_t* mask_svu, int* __restrict__ winner_svu,
-                                              int* __restrict__ remain)
+                                              int* __restrict__ remain, const float* __restrict__ Cl_hat_vu,
+                                              float* __restrict__ Cl_svu)
 {
     const int u = (seg << 8) + threadIdx.x;
     const long long t = r * U + (u < U ? u : U - 1);
@@ -210,6 +211,8 @@ __device__ __forceinline__ void apply_segment(long long r, int seg, int V, int U
     // s == s_hat: w == u, both assignments are self-assignments (core.hpp:1119-1121)
     depth_svu[t] = filtered_vu[src];
     Cd_svu[t] = Cd_hat_vu[src];
+    if (Cl_svu)   // core.hpp:1122-1124: the line confidence travels with the disparity (both NULL: not kept)
+        Cl_svu[t] = Cl_hat_vu[src];
     mask_svu[t] = 0;
     winner_svu[t] = kNoWinner;
 }
@@ -245,7 +248,8 @@ __global__ __launch_bounds__(256) void k4_propagate_apply(int S, int V, int U, i
                                                          uint8_t* __restrict__ dirty, int s_next, const uint8_t* __restrict__ edge_mask_next_vu,
                                                          int* __restrict__ list, int* __restrict__ count,
                                                          unsigned long long* __restrict__ total, int* __restrict__ packed_n,
-                                                         int* __restrict__ remain, int* __restrict__ rowbase)
+                                                         int* __restrict__ remain, int* __restrict__ rowbase,
+                                                         const float* __restrict__ Cl_hat_vu, float* __restrict__ Cl_svu)
 {
     __shared__ uint8_t s_flags[kApplyFlagSlots];
     const int nseg = (U + 255) >> 8;
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(256) void k4_propagate_apply(int S, int V, int U, i
         uint8_t* flags = dirty + r * nseg;
         for (int seg = 0; seg < nseg; seg++)
             if (flags[seg])   // the same byte for the whole workgroup
-                apply_segment(r, seg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain);
+                apply_segment(r, seg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain, Cl_hat_vu, Cl_svu);
         __syncthreads();      // every thread has read the flags, and this row's mask writes are the workgroup's own
         if ((int)threadIdx.x < nseg)
             flags[threadIdx.x] = 0;
@@ -282,7 +286,7 @@ __global__ __launch_bounds__(256) void k4_propagate_apply(int S, int V, int U, i
     __syncthreads();
     for (int i = 0; i < nfl; i++)
         if (s_flags[i])
-            apply_segment(r0 + i / nseg, i % nseg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain);
+            apply_segment(r0 + i / nseg, i % nseg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain, Cl_hat_vu, Cl_svu);
 }
 
 }  // namespace rslf

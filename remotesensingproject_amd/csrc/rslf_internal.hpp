@@ -201,6 +201,7 @@ struct rslf_ctx {
     int sweep_expect = -1;             // the view the sweep visits next (core.hpp:981-990), -1 once all are done
     bool sweep_open = false;           // between rslf_sweep_begin and rslf_sweep_end
     bool sweep_first = true;           // the next visit is the sweep's first (dense) one
+    bool sweep_scanned = false;        // a visit of the open sweep has scanned (rslf_sweep_line_confidence comes before)
     bool sweep_listed = false;         // the last apply pass listed the next visit's pixels (packed list and length in place);
                                        // else k34_median_claim left the list's length at 0
     uint8_t* sweep_mask_run = nullptr; // the running masks [S][V][U] of the open sweep
@@ -213,10 +214,24 @@ struct rslf_ctx {
     float* filtered = nullptr;    // [V][U] median of the visited view, the propagation's source
     size_t sweep_cap = 0;         // entries winner / sweep_mask can hold (S*V*U)
     size_t sweep_plane_cap = 0;   // floats `filtered` can hold (V*U)
+    // line confidence of the open sweep (rslf_sweep_line_confidence; k7_line_conf.hpp).  The K columns and the visit's arg-max
+    // plane are helper slots kLineConfColumns / kLineConfArgmax, sized when the mode is set, never inside a visit.
+    int lc_mode = 0;                   // RSLF_LINE_CONF_*; rslf_sweep_end puts it back to 0
+    float* lc_Cl_svu = nullptr;        // the caller's [S][V][U] plane
+    float* lc_K_vsu = nullptr;         // [V][S][U] K(r - rbar) columns, kept from visit to visit (core.hpp:975-979)
+    int32_t* lc_idx_vu = nullptr;      // [V][U] arg-max indices of the visit's scan, -1 where it accepted nothing
+    // what rslf_sweep_visit_scan was given and K7 needs to re-run a winning hypothesis (rslf_sweep_visit_finish is not told)
+    const float* lc_Ce_svu = nullptr;
+    const float* lc_dmin_vu = nullptr;
+    const float* lc_dmax_vu = nullptr;
+    float lc_dmin = 0.0f, lc_dmax = 0.0f;
+    int lc_dim_d = 0;
+    rslf::ScanConsts lc_consts = {};
     // grow-only scratch of the once-per-level helpers (pyramid, tightening, fusion) and of the renderers (slots 4 .. 6: the
     // staging of their host-pointer forms): reused across calls, so these helpers neither allocate nor free -- and so
     // never force a device-wide synchronisation
-    static constexpr int kHelperSlots = 7;
+    static constexpr int kHelperSlots = 9;
+    static constexpr int kLineConfColumns = 7, kLineConfArgmax = 8;   // slots 7, 8: the line confidence of a sweep
     void* helper[kHelperSlots] = {};
     size_t helper_cap[kHelperSlots] = {};
 };

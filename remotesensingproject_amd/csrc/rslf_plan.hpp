@@ -185,6 +185,56 @@ inline int sweep_view_after(int S, int s_hat)
     return -1;
 }
 
+// ---- the line confidence of a sweep (k7_line_conf.hpp; core.hpp:1032-1081 under _USE_LINE_CONFIDENCE_SCORE) ----------
+// 0: not computed (the default build); 1: computed and carried, the gate stays the edge mask (what the macro compiles
+// to: the gating branches sit behind an `#elseif` typo, core.hpp:1099); 2: computed, carried and gating (what those
+// branches say).
+constexpr int kLineConfOff = 0, kLineConfAsBuilt = 1, kLineConfGate = 2;
+
+inline bool line_conf_mode_ok(int mode) { return mode >= kLineConfOff && mode <= kLineConfGate; }
+
+// Which plane gates the propagation of a visit (core.hpp:1097-1103): the #ifdef chain gives C_d the gate whenever
+// use_disp_confidence_score is set; C_l has it in mode 2 alone; else the edge mask.
+enum SweepGate { kGateEdgeMask = 0, kGateDispConf = 1, kGateLineConf = 2 };
+inline SweepGate sweep_gate(bool use_disp_confidence_score, int line_mode)
+{
+    if (use_disp_confidence_score)
+        return kGateDispConf;
+    return line_mode == kLineConfGate ? kGateLineConf : kGateEdgeMask;
+}
+
+// K7 runs before the claims only where the claims gate on its plane; it then needs the filtered plane first, from a median
+// pass of its own.  Where C_d or the edge mask gates, K7 follows median + claims (which leaves the filtered plane).
+inline bool line_conf_before_claims(bool use_disp_confidence_score, int mode)
+{
+    return sweep_gate(use_disp_confidence_score, mode) == kGateLineConf;
+}
+
+// Launches rslf_sweep_visit_finish queues.  Off: median + claims, apply.  K7 after the claims: one more.  K7 before them: the
+// median alone, K7, median + claims, apply.
+inline int line_conf_finish_launches(bool use_disp_confidence_score, int mode)
+{
+    if (mode == kLineConfOff)
+        return 2;
+    return line_conf_before_claims(use_disp_confidence_score, mode) ? 4 : 3;
+}
+
+// Bytes of the sweep-long K(r - rbar) columns [V][S][U] (core.hpp:975-979) and of a visit's arg-max plane [V][U]; 0 when off
+// or when a dimension is not positive.
+inline size_t line_conf_columns_bytes(int mode, int V, int S, int U)
+{
+    if (mode == kLineConfOff || V < 1 || S < 1 || U < 1)
+        return 0;
+    return (size_t)V * (size_t)S * (size_t)U * sizeof(float);
+}
+
+inline size_t line_conf_argmax_bytes(int mode, int V, int U)
+{
+    if (mode == kLineConfOff || V < 1 || U < 1)
+        return 0;
+    return (size_t)V * (size_t)U * sizeof(int32_t);
+}
+
 // cv::getStructuringElement(shape, Size(k, k)) with the default anchor, as OpenCV 3.x builds it (imgproc/src/morph.cpp):
 // RECT every column; CROSS the anchor row entirely, elsewhere the anchor column; ELLIPSE the columns
 // [c - dx, c + dx + 1), dx = cvRound(c * sqrt((r*r - dy*dy) / (r*r))), r = c = k/2, dy = i - r.

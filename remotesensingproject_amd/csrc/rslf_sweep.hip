@@ -1,5 +1,6 @@
 // librslf_hip.so, unit 6 of 9: the 2-D sweep (Depth2DComputer::run, core.hpp:901-1133) -- one visit per view, scan (unit 2),
-// selective median + claims, apply + the next visit's compaction (K4).  C-ABI: include/rslf_hip.h.
+// selective median + claims, apply + the next visit's compaction (K4), and the sweep's line confidence (K7).  C-ABI:
+// include/rslf_hip.h.
 #include "rslf_internal.hpp"
 
 #include <algorithm>
@@ -7,6 +8,7 @@
 
 #include "k3_median.hpp"
 #include "k4_propagate.hpp"
+#include "k7_line_conf.hpp"
 
 using namespace rslf;
 
@@ -61,6 +63,8 @@ static void sweep_close(rslf_ctx* ctx, bool ok)
     ctx->keep_total = false;
     ctx->sweep_listed = false;
     ctx->sweep_expect = -1;
+    ctx->lc_mode = RSLF_LINE_CONF_OFF;   // line confidence is state of ONE sweep (rslf_sweep_line_confidence)
+    ctx->lc_Cl_svu = nullptr;
     if (!ok) {
         ctx->sweep_cap = 0;   // claims without their apply pass may be left behind: fresh winners and flags next time
         ctx->dirty_cap = 0;
@@ -126,9 +130,84 @@ extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uin
     ctx->keep_total = true;
     ctx->sweep_open = true;
     ctx->sweep_first = true;
+    ctx->sweep_scanned = false;
     ctx->sweep_listed = false;
+    ctx->lc_mode = RSLF_LINE_CONF_OFF;
+    ctx->lc_Cl_svu = nullptr;
     ctx->sweep_mask_run = mask_svu;
     ctx->sweep_expect = plan::sweep_order(S)[0];
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+// ---- line confidence (K7; core.hpp:1032-1081 under _USE_LINE_CONFIDENCE_SCORE) ---------------------------------------
+
+// One K7 launch.  idx_vu (nullable): the visit's arg-max plane, with which `a` holds the scan's arguments and C its channels.
+static int launch_line_confidence(rslf_ctx* ctx, const LineConfArgs& q, const ScanArgs& a, const int32_t* idx_vu, int C)
+{
+    if (q.V > 65535 || q.U > (1 << 24))
+        return fail(RSLF_ERR_UNSUPPORTED, "%d scanlines x %d columns: too large for one line-confidence launch", q.V, q.U);
+    const dim3 grid((q.U + 255) / 256, q.V);
+    if (C == 3)
+        hipLaunchKernelGGL(k7_line_confidence<3>, grid, dim3(256), 0, ctx->stream, q, a, idx_vu);
+    else
+        hipLaunchKernelGGL(k7_line_confidence<1>, grid, dim3(256), 0, ctx->stream, q, a, idx_vu);
+    HIP_TRY(hipGetLastError());
+    return RSLF_OK;
+}
+
+// core.hpp:1054-1079 on caller planes (include/rslf_hip.h)
+extern "C" int rslf_line_confidence_pile(rslf_ctx* ctx, int V, int S, int U, int s_hat, const float* d_Ce_svu, const float* d_K_vsu,
+                                         const float* d_depth_vu, const uint8_t* d_Ce_mask_vu, float* d_Cl_vu) RSLF_API_TRY
+{
+    if (!ctx || !d_Ce_svu || !d_K_vsu || !d_depth_vu || !d_Ce_mask_vu || !d_Cl_vu)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (V < 1 || S < 1 || U < 1)
+        return fail(RSLF_ERR_INVALID_ARG, "V=%d S=%d U=%d: every dimension must be positive", V, S, U);
+    if (s_hat < 0 || s_hat >= S)
+        return fail(RSLF_ERR_INVALID_ARG, "s_hat=%d outside [0,%d)", s_hat, S);
+    HIP_TRY(hipSetDevice(ctx->device));
+    LineConfArgs q = {};
+    q.V = V, q.S = S, q.U = U, q.s_hat = s_hat;
+    q.Ce_svu = d_Ce_svu;
+    q.K_vsu = const_cast<float*>(d_K_vsu);   // written only with an arg-max plane: there is none here
+    q.depth_vu = d_depth_vu;
+    q.mask_vu = d_Ce_mask_vu;
+    q.Cl_vu = d_Cl_vu;
+    return launch_line_confidence(ctx, q, ScanArgs{}, nullptr, 1);
+}
+RSLF_API_CATCH
+
+// dc.hpp:721-738, :791-792 and core.hpp:975-979: the planes a sweep with line confidence keeps (include/rslf_hip.h)
+extern "C" int rslf_sweep_line_confidence(rslf_ctx* ctx, const rslf_volume* vol, int mode, float* d_Cl_svu) RSLF_API_TRY
+{
+    if (!ctx || !vol)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (!plan::line_conf_mode_ok(mode))
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", mode);
+    if (mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", mode);
+    if (!ctx->sweep_open || ctx->sweep_scanned || !ctx->sweep_first)
+        return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_line_confidence belongs between rslf_sweep_begin and the first visit");
+    HIP_TRY(hipSetDevice(ctx->device));
+    ctx->lc_mode = RSLF_LINE_CONF_OFF;
+    ctx->lc_Cl_svu = nullptr;
+    if (mode == RSLF_LINE_CONF_OFF)
+        return RSLF_OK;
+    const size_t kb = plan::line_conf_columns_bytes(mode, vol->V, vol->S, vol->U);
+    void *K = nullptr, *idx = nullptr;
+    int rc = helper_scratch(ctx, rslf_ctx::kLineConfColumns, kb, &K);
+    if (!rc)
+        rc = helper_scratch(ctx, rslf_ctx::kLineConfArgmax, plan::line_conf_argmax_bytes(mode, vol->V, vol->U), &idx);
+    if (rc)
+        return rc;
+    // core.hpp:975-979 leaves K uninitialised; here a column nobody has written reads as zeros.  The arg-max
+    // plane is refilled with -1 by every scan.
+    HIP_TRY(hipMemsetAsync(K, 0, kb, ctx->stream));
+    ctx->lc_K_vsu = static_cast<float*>(K);
+    ctx->lc_idx_vu = static_cast<int32_t*>(idx);
+    ctx->lc_Cl_svu = d_Cl_svu;
+    ctx->lc_mode = mode;
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -152,11 +231,21 @@ extern "C" int rslf_sweep_visit_scan(rslf_ctx* ctx, const rslf_volume* vol, cons
     // reference the stored plane keeps the RAW depths and only the local header is rebound to the median
     // (core.hpp:892), which the propagation then paints from: so the scan writes the view's depth plane and the median
     // goes to ctx->filtered (rslf_sweep_visit_finish) -- no plane copies.
-    return depth_epi_scan(ctx, vol, d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr,
-                          d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr, dmin, dmax, dim_d, s_hat, d_Ce_svu + (size_t)s_hat * n,
-                          d_Ce_mask_svu + (size_t)s_hat * n, d_Cd_svu + (size_t)s_hat * n, d_depth_svu + (size_t)s_hat * n,
-                          d_rbar_svu + (size_t)s_hat * n * vol->C, p, ctx->sweep_mask_run + (size_t)s_hat * n, nullptr, nullptr,
-                          nullptr, visit_inputs(ctx->sweep_first, ctx->sweep_listed));
+    ctx->sweep_scanned = true;
+    const bool lc = ctx->lc_mode != RSLF_LINE_CONF_OFF;   // K7 re-runs the winners: the scan keeps its arg-max indices
+    const int rc = depth_epi_scan(ctx, vol, d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr,
+                                  d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr, dmin, dmax, dim_d, s_hat, d_Ce_svu + (size_t)s_hat * n,
+                                  d_Ce_mask_svu + (size_t)s_hat * n, d_Cd_svu + (size_t)s_hat * n, d_depth_svu + (size_t)s_hat * n,
+                                  d_rbar_svu + (size_t)s_hat * n * vol->C, p, ctx->sweep_mask_run + (size_t)s_hat * n,
+                                  lc ? ctx->lc_idx_vu : nullptr, nullptr, nullptr, visit_inputs(ctx->sweep_first, ctx->sweep_listed));
+    if (rc || !lc)
+        return rc;
+    ctx->lc_Ce_svu = d_Ce_svu;
+    ctx->lc_dmin_vu = d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr;
+    ctx->lc_dmax_vu = d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr;
+    ctx->lc_dmin = dmin, ctx->lc_dmax = dmax, ctx->lc_dim_d = dim_d;
+    ctx->lc_consts = make_scan_consts(p);
+    return RSLF_OK;
 }
 RSLF_API_CATCH
 
@@ -195,7 +284,53 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
     const int s_after = s_next;
     if (ctx->force_packed == 0 || n > (size_t)INT32_MAX)
         s_next = -1;   // that scan will not take a packed list: it compacts for itself
+    // Line confidence (core.hpp:1032-1081): K7 needs the FILTERED plane (:892) and, in mode 2, the claims need K7's plane.
+    const int lc_mode = ctx->lc_mode;
+    float* Cl = lc_mode ? ctx->lc_Cl_svu + (size_t)s_hat * n : nullptr;
+    auto line_confidence = [&]() -> int {
+        LineConfArgs q = {};
+        q.V = V, q.S = S, q.U = U, q.s_hat = s_hat;
+        q.Ce_svu = ctx->lc_Ce_svu;
+        q.K_vsu = ctx->lc_K_vsu;
+        q.depth_vu = ctx->filtered;
+        q.mask_vu = cem;
+        q.Cl_vu = Cl;
+        ScanArgs a = {};
+        a.vol = view_of(vol);
+        a.dmin_vu = ctx->lc_dmin_vu, a.dmax_vu = ctx->lc_dmax_vu;
+        a.dmin = ctx->lc_dmin, a.dmax = ctx->lc_dmax;
+        a.dim_d = ctx->lc_dim_d;
+        a.s_hat = s_hat;
+        a.k = ctx->lc_consts;
+        a.groups = 1;
+        return launch_line_confidence(ctx, q, a, ctx->lc_idx_vu, C);
+    };
+    // core.hpp:1097-1103: C_d gates whenever use_disp_confidence_score is set, C_l in mode 2, else the edge mask
+    const plan::SweepGate gate = plan::sweep_gate(p->use_disp_confidence_score != 0, lc_mode);
+    const bool k7_first = plan::line_conf_before_claims(p->use_disp_confidence_score != 0, lc_mode);
     bool launched = false;
+    if (k7_first) {   // the claims wait for C_l: the median alone first; k34_median_claim repeats it (tens of microseconds a plane)
+#define RSLF_K3_CASE(CC, MODE)                                                                                                    \
+    if (!launched && C == CC && mp.mode == MODE) {                                                                                \
+        if (mp.lds_bytes > ((size_t)64 << 10))                                                                                    \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k3_selective_median<CC, MODE>),                           \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds_bytes));                         \
+        hipLaunchKernelGGL((k3_selective_median<CC, MODE>), grid_vu, dim3(kMedianBlock), mp.lds_bytes, st, view_of(vol), depth,   \
+                           ctx->filtered, cem, s_hat, mp.w, median_thr);                                                          \
+        launched = true;                                                                                                          \
+    }
+        RSLF_MEDIAN_MODES(RSLF_K3_CASE, 1)
+        RSLF_MEDIAN_MODES(RSLF_K3_CASE, 3)
+#undef RSLF_K3_CASE
+        if (!launched)
+            return fail(RSLF_ERR_INTERNAL, "no selective-median kernel for %d channels, mode %d", C, mp.mode);
+        HIP_TRY(hipGetLastError());
+        if (int rc = line_confidence())
+            return rc;
+        launched = false;
+    }
+    const float* gate_vu = gate == plan::kGateDispConf ? Cd : gate == plan::kGateLineConf ? Cl : nullptr;
+    const float gate_thr = gate == plan::kGateLineConf ? p->line_score_threshold : p->disp_score_threshold;
 #define RSLF_K34_CASE(CC, MODE)                                                                                                  \
     if (!launched && C == CC && mp.mode == MODE) {                                                                                \
         if (mp.lds_bytes > ((size_t)64 << 10))                                                                                    \
@@ -203,7 +338,7 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds_bytes));                         \
         hipLaunchKernelGGL((k34_median_claim<CC, MODE>), grid_vu, dim3(256), mp.lds_bytes, st, view_of(vol), s_hat, depth, ctx->filtered, \
                            cem, mp.w, median_thr, rbar, mask_svu, ctx->winner, ctx->dirty, p->slope_factor, prop_thr,             \
-                           p->use_disp_confidence_score ? Cd : nullptr, p->disp_score_threshold, packed_n,                       \
+                           gate_vu, gate_thr, packed_n,                                                                           \
                            ctx->claim_skip ? ctx->remain : nullptr);                                                             \
         launched = true;                                                                                                          \
     }
@@ -213,10 +348,13 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
     if (!launched)
         return fail(RSLF_ERR_INTERNAL, "no median + claims kernel for %d channels, mode %d", C, mp.mode);
     HIP_TRY(hipGetLastError());
+    if (lc_mode != RSLF_LINE_CONF_OFF && !k7_first)
+        if (int rc = line_confidence())
+            return rc;
     const unsigned apply_blocks = (unsigned)((s_next >= 0 ? V : 0) + ((long long)S * V + kApplyRowsPerBlock - 1) / kApplyRowsPerBlock);
     hipLaunchKernelGGL(k4_propagate_apply, dim3(apply_blocks), dim3(256), 0, st, S, V, U, s_hat, ctx->filtered, Cd, d_depth_svu,
                        d_Cd_svu, mask_svu, ctx->winner, ctx->dirty, s_next, s_next >= 0 ? d_Ce_mask_svu + (size_t)s_next * n : nullptr, ctx->list,
-                       ctx->count, ctx->total, packed_n, ctx->remain, ctx->count + ctx->count_cap);
+                       ctx->count, ctx->total, packed_n, ctx->remain, ctx->count + ctx->count_cap, Cl, lc_mode ? ctx->lc_Cl_svu : nullptr);
     HIP_TRY(hipGetLastError());
     ctx->sweep_listed = s_next >= 0;
     ctx->sweep_expect = s_after;
@@ -245,22 +383,31 @@ extern "C" int rslf_sweep_end(rslf_ctx* ctx, int ok, int dim_d, rslf_stats* stat
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
-                                 float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
-                                 float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
-                                 rslf_stats* stats) RSLF_API_TRY
+// compute_2D_depth_epi (core.hpp:933-1133) as begin + (scan, finish) per view + end; line_mode / d_Cl_svu: the extra argument
+// a_line_confidence_s_v_u of the -D_USE_LINE_CONFIDENCE_SCORE build (core.hpp:345), RSLF_LINE_CONF_OFF / NULL without it
+static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
+                        float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                        float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
+                        float* d_Cl_svu)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (!plan::line_conf_mode_ok(line_mode))
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
+    if (line_mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
     int rc = check_params(p);
     if (rc)
         return rc;
     rc = rslf_sweep_begin(ctx, vol, d_Ce_mask_svu, d_scan_mask_svu, dim_d, 0, vol->V);
     if (rc)
         return rc;
+    if (line_mode != RSLF_LINE_CONF_OFF)
+        rc = rslf_sweep_line_confidence(ctx, vol, line_mode, d_Cl_svu);
     for (int s_hat : plan::sweep_order(vol->S)) {   // core.hpp:981-990
-        rc = rslf_sweep_visit_scan(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, s_hat, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu,
-                                   d_depth_svu, d_rbar_svu, p);
+        if (!rc)
+            rc = rslf_sweep_visit_scan(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, s_hat, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu,
+                                       d_depth_svu, d_rbar_svu, p);
         if (!rc)
             rc = rslf_sweep_visit_finish(ctx, vol, s_hat, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, p);
         if (rc) {
@@ -271,27 +418,62 @@ extern "C" int rslf_depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const fl
     }
     return rslf_sweep_end(ctx, 1, dim_d, stats);
 }
+
+extern "C" int rslf_depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                                 float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
+                                 float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
+                                 rslf_stats* stats) RSLF_API_TRY
+{
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                        p, d_scan_mask_svu, stats, RSLF_LINE_CONF_OFF, nullptr);
+}
 RSLF_API_CATCH
+
+// core.hpp:336-351 with a_line_confidence_s_v_u (:345)
+extern "C" int rslf_depth_epi_2d_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                                    float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
+                                    float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
+                                    rslf_stats* stats, int line_mode, float* d_Cl_svu) RSLF_API_TRY
+{
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu);
+}
+RSLF_API_CATCH
+
+static int depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
+                          float dmax, int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
+                          float* d_depth_svu, float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
+                          float* d_Cl_svu)
+{
+    if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (!plan::line_conf_mode_ok(line_mode))
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
+    if (line_mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = (size_t)vol->S * vol->V * vol->U;
+    hipStream_t st = ctx->stream;
+    // dc.hpp:733-750 (C_e, C_d and C_l are uninitialised there; zero is the intended start)
+    HIP_TRY(hipMemsetAsync(d_Ce_svu, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(d_Cd_svu, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(d_depth_svu, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(d_rbar_svu, 0, n * vol->C * sizeof(float), st));
+    if (line_mode != RSLF_LINE_CONF_OFF)
+        HIP_TRY(hipMemsetAsync(d_Cl_svu, 0, n * sizeof(float), st));   // dc.hpp:737
+    int rc = rslf_edge_confidence_2d(ctx, vol, p, d_Ce_svu, d_Ce_mask_svu);   // dc.hpp:772
+    if (rc)
+        return rc;
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
+                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu);
+}
 
 int rslf::depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
                       int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                       float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats)
 {
-    if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = (size_t)vol->S * vol->V * vol->U;
-    hipStream_t st = ctx->stream;
-    // dc.hpp:733-750 (C_e and C_d are uninitialised there; zero is the intended start)
-    HIP_TRY(hipMemsetAsync(d_Ce_svu, 0, n * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(d_Cd_svu, 0, n * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(d_depth_svu, 0, n * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(d_rbar_svu, 0, n * vol->C * sizeof(float), st));
-    int rc = rslf_edge_confidence_2d(ctx, vol, p, d_Ce_svu, d_Ce_mask_svu);   // dc.hpp:772
-    if (rc)
-        return rc;
-    return rslf_depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
-                             d_rbar_svu, p, d_scan_mask_svu, stats);
+    return depth2d_run_lc(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,
+                          d_rbar_svu, d_scan_mask_svu, stats, RSLF_LINE_CONF_OFF, nullptr);
 }
 
 extern "C" int rslf_depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
@@ -303,22 +485,38 @@ extern "C" int rslf_depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmi
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
-                                     float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
-                                     float* h_rbar_svu, rslf_stats* stats) RSLF_API_TRY
+// dc.hpp:748-805 with the line-confidence planes of dc.hpp:721-738, :791-792
+extern "C" int rslf_depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                   float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
+                                   uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu) RSLF_API_TRY
+{
+    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                          d_scan_mask_svu, stats, line_mode, d_Cl_svu);
+}
+RSLF_API_CATCH
+
+static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                            float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
+                            rslf_stats* stats, int line_mode, float* h_Cl_svu)
 {
     if (!ctx || !vol)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (!plan::line_conf_mode_ok(line_mode))
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
+    if (line_mode != RSLF_LINE_CONF_OFF && !h_Cl_svu)
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n = (size_t)vol->S * vol->V * vol->U;
-    DevBuf Ce, Cd, depth, rbar, mask;
+    DevBuf Ce, Cd, depth, rbar, mask, Cl;
     HIP_TRY(Ce.alloc(n * 4));
     HIP_TRY(Cd.alloc(n * 4));
     HIP_TRY(depth.alloc(n * 4));
     HIP_TRY(rbar.alloc(n * 4 * vol->C));
     HIP_TRY(mask.alloc(n));
-    int rc = rslf_depth2d_run(ctx, vol, dmin, dmax, dim_d, p, (float*)Ce.p, (uint8_t*)mask.p, (float*)Cd.p, (float*)depth.p,
-                              (float*)rbar.p, nullptr, stats);
+    if (line_mode != RSLF_LINE_CONF_OFF)
+        HIP_TRY(Cl.alloc(n * 4));
+    int rc = depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, (float*)Ce.p, (uint8_t*)mask.p, (float*)Cd.p,
+                            (float*)depth.p, (float*)rbar.p, nullptr, stats, line_mode, (float*)Cl.p);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
@@ -327,7 +525,25 @@ extern "C" int rslf_depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, floa
     if (h_Cd_svu) HIP_TRY(hipMemcpyAsync(h_Cd_svu, Cd.p, n * 4, hipMemcpyDeviceToHost, st));
     if (h_depth_svu) HIP_TRY(hipMemcpyAsync(h_depth_svu, depth.p, n * 4, hipMemcpyDeviceToHost, st));
     if (h_rbar_svu) HIP_TRY(hipMemcpyAsync(h_rbar_svu, rbar.p, n * 4 * vol->C, hipMemcpyDeviceToHost, st));
+    if (line_mode != RSLF_LINE_CONF_OFF) HIP_TRY(hipMemcpyAsync(h_Cl_svu, Cl.p, n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RSLF_OK;
+}
+
+extern "C" int rslf_depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                     float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                                     float* h_rbar_svu, rslf_stats* stats) RSLF_API_TRY
+{
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
+                            RSLF_LINE_CONF_OFF, nullptr);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_depth2d_run_host_lc(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                        float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                                        float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu) RSLF_API_TRY
+{
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
+                            line_mode, h_Cl_svu);
 }
 RSLF_API_CATCH

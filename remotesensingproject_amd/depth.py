@@ -66,6 +66,11 @@ class Depth1DParameters:
     # the reference's commented-out build switch _USE_DISP_CONFIDENCE_SCORE (core.hpp:35): propagation gated by
     # C_d > par_disp_score_threshold instead of the edge mask
     par_use_disp_confidence_score: bool = False
+    # the reference's build switch _USE_LINE_CONFIDENCE_SCORE (core.hpp:1032-1081), a LINE_CONF_* mode of the 2-D sweep:
+    # 0 off; 1 as built (C_l computed and carried, the gate stays the edge mask: the gating branches sit behind an
+    # `#elseif` typo); 2 gate (propagation, getters and validity under C_l > par_line_score_threshold, what those branches
+    # say).  Host-side only: it is an argument of the *_lc entry points, not a member of rslf_params.
+    par_line_confidence_mode: int = 0
 
     @staticmethod
     def get_default() -> "Depth1DParameters":
@@ -80,6 +85,17 @@ class Depth1DParameters:
             v = getattr(self, "par_" + f)
             setattr(p, f, int(v) if isinstance(getattr(p, f), int) else float(v))
         return p
+
+
+LINE_CONF_OFF, LINE_CONF_AS_BUILT, LINE_CONF_GATE = 0, 1, 2   # RSLF_LINE_CONF_*
+
+
+def require_no_line_confidence(parameters, who: str) -> None:
+    """The line confidence is built for the one-device Depth2DComputer alone (DESIGN.md 3 "K7"): every other path that
+    takes parameters refuses a mode other than 0 instead of ignoring it or running it untested."""
+    if parameters is not None and int(parameters.par_line_confidence_mode) != LINE_CONF_OFF:
+        raise ValueError("%s: par_line_confidence_mode=%d is not built here (one-device Depth2DComputer only)"
+                         % (who, int(parameters.par_line_confidence_mode)))
 
 
 class Context:
@@ -672,6 +688,7 @@ class MultiDevice:
                    disp_confidence=np.empty((S, V, U), np.float32), depth=np.empty((S, V, U), np.float32),
                    rbar=np.empty((S, V, U, C_), np.float32), scan_mask=np.empty((S, V, U), np.uint8))
         hp = [out[k].ctypes.data_as(C.c_void_p) for k in ("edge_confidence", "edge_mask", "disp_confidence", "depth", "rbar", "scan_mask")]
+        require_no_line_confidence(parameters, "MultiDevice.depth2d")
         p = (parameters or Depth1DParameters()).to_c()
         st = RslfStats()
         L = _lib.lib()
@@ -695,6 +712,7 @@ class MultiDevice:
         keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
+        require_no_line_confidence(parameters, "MultiDevice.fine_to_coarse")
         p = (parameters or Depth1DParameters()).to_c()
         st, nl = RslfStats(), C.c_int()
         rest = (V, S, U, C_, 0, float(d_min), float(d_max), int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
@@ -754,23 +772,47 @@ def compute_2D_edge_confidence(vol: Volume, a_edge_confidence_s_v_u: torch.Tenso
     return mask
 
 
+def line_confidence_pile(ctx: Context, a_s_hat: int, a_edge_confidence_s_v_u: torch.Tensor, a_K_r_m_rbar_v_s_u: torch.Tensor,
+                         a_best_depth_v_u: torch.Tensor, a_edge_confidence_mask_v_u: torch.Tensor,
+                         a_line_confidence_v_u: torch.Tensor) -> None:
+    """core.hpp:1054-1079 for one visited view on caller planes: C_l = sum_s E K / sum_s K with E the edge confidence
+    [S,V,U] interpolated along each pixel's line (slope a_best_depth_v_u [V,U], no slope factor) and K [V,S,U]; written
+    into a_line_confidence_v_u [V,U] where a_edge_confidence_mask_v_u is set, left alone elsewhere."""
+    S, V, U = a_edge_confidence_s_v_u.shape
+    if tuple(a_K_r_m_rbar_v_s_u.shape) != (V, S, U) or tuple(a_best_depth_v_u.shape) != (V, U) \
+            or tuple(a_edge_confidence_mask_v_u.shape) != (V, U) or tuple(a_line_confidence_v_u.shape) != (V, U):
+        raise ValueError("line_confidence_pile: C_e is [S,V,U], K [V,S,U], the other planes [V,U]")
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_line_confidence_pile(ctx._h, V, S, U, int(a_s_hat), _ptr(a_edge_confidence_s_v_u), _ptr(a_K_r_m_rbar_v_s_u),
+                                               _ptr(a_best_depth_v_u), _ptr(a_edge_confidence_mask_v_u), _ptr(a_line_confidence_v_u)),
+          "rslf_line_confidence_pile")
+
+
 def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, a_edge_confidence_s_v_u: torch.Tensor,
                          a_edge_confidence_mask_s_v_u: torch.Tensor, a_disp_confidence_s_v_u: torch.Tensor,
                          a_best_depth_s_v_u: torch.Tensor, a_rbar_s_v_u: torch.Tensor,
                          a_parameters: Depth1DParameters | None = None, *, scan_mask_s_v_u: torch.Tensor | None = None,
-                         want_stats: bool = False) -> RslfStats | None:
-    """core.hpp:336-351 (the line-confidence argument does not exist in the default build).
+                         want_stats: bool = False, a_line_confidence_s_v_u: torch.Tensor | None = None) -> RslfStats | None:
+    """core.hpp:336-351.  a_line_confidence_s_v_u ([S,V,U] f32, pass zeros) is the argument of the
+    _USE_LINE_CONFIDENCE_SCORE build (:345): with it the call goes through rslf_depth_epi_2d_lc in
+    a_parameters.par_line_confidence_mode -- mode 0 is then the default build and leaves the plane untouched; modes 1 and 2
+    need the plane (without it the library returns RSLF_ERR_INVALID_ARG).
     a_dmin_s_v_u / a_dmax_s_v_u: [S,V,U] f32 CUDA tensors or Python floats."""
-    p = (a_parameters or Depth1DParameters()).to_c()
+    par = a_parameters or Depth1DParameters()
+    p = par.to_c()
     planes = isinstance(a_dmin_s_v_u, torch.Tensor)
     st = RslfStats() if want_stats else None
     vol.ctx.use_current_stream()
-    check(_lib.lib().rslf_depth_epi_2d(
-        vol.ctx._h, vol._h, _ptr(a_dmin_s_v_u if planes else None), _ptr(a_dmax_s_v_u if planes else None),
-        0.0 if planes else float(a_dmin_s_v_u), 0.0 if planes else float(a_dmax_s_v_u), a_dim_d,
-        _ptr(a_edge_confidence_s_v_u), _ptr(a_edge_confidence_mask_s_v_u), _ptr(a_disp_confidence_s_v_u),
-        _ptr(a_best_depth_s_v_u), _ptr(a_rbar_s_v_u), C.byref(p), _ptr(scan_mask_s_v_u),
-        C.byref(st) if st is not None else None), "rslf_depth_epi_2d")
+    args = (vol.ctx._h, vol._h, _ptr(a_dmin_s_v_u if planes else None), _ptr(a_dmax_s_v_u if planes else None),
+            0.0 if planes else float(a_dmin_s_v_u), 0.0 if planes else float(a_dmax_s_v_u), a_dim_d,
+            _ptr(a_edge_confidence_s_v_u), _ptr(a_edge_confidence_mask_s_v_u), _ptr(a_disp_confidence_s_v_u),
+            _ptr(a_best_depth_s_v_u), _ptr(a_rbar_s_v_u), C.byref(p), _ptr(scan_mask_s_v_u),
+            C.byref(st) if st is not None else None)
+    mode = int(par.par_line_confidence_mode)
+    if a_line_confidence_s_v_u is None and mode == LINE_CONF_OFF:
+        check(_lib.lib().rslf_depth_epi_2d(*args), "rslf_depth_epi_2d")
+    else:
+        check(_lib.lib().rslf_depth_epi_2d_lc(*args, mode, _ptr(a_line_confidence_s_v_u)), "rslf_depth_epi_2d_lc")
     return st
 
 
@@ -801,7 +843,16 @@ class Depth2DComputer:
         self.m_best_depth_s_v_u = torch.empty((S, V, U), dtype=torch.float32, device=dev)
         self.m_rbar_s_v_u = torch.empty((S, V, U, C_), dtype=torch.float32, device=dev)
         self.m_scan_mask_s_v_u = torch.empty((S, V, U), dtype=torch.uint8, device=dev)
+        # dc.hpp:721-738: allocated in the _USE_LINE_CONFIDENCE_SCORE build only
+        self.m_line_confidence_s_v_u = (torch.empty((S, V, U), dtype=torch.float32, device=dev)
+                                        if self._line_mode() != LINE_CONF_OFF else None)
         self.stats: RslfStats | None = None
+
+    def _line_mode(self) -> int:
+        mode = int(self.m_parameters.par_line_confidence_mode)
+        if mode not in (LINE_CONF_OFF, LINE_CONF_AS_BUILT, LINE_CONF_GATE):
+            raise ValueError("par_line_confidence_mode=%d: 0 (off), 1 (as built) or 2 (gate)" % mode)
+        return mode
 
     def run(self, want_stats: bool = True) -> None:
         """dc.hpp:748-805."""
@@ -809,12 +860,21 @@ class Depth2DComputer:
         p = self.m_parameters.to_c()
         st = RslfStats() if want_stats else None
         vol.ctx.use_current_stream()
-        check(_lib.lib().rslf_depth2d_run(
-            vol.ctx._h, vol._h, self.m_dmin, self.m_dmax, self.m_dim_d, C.byref(p), _ptr(self.m_edge_confidence_s_v_u),
-            _ptr(self.m_edge_confidence_mask_s_v_u), _ptr(self.m_disp_confidence_s_v_u), _ptr(self.m_best_depth_s_v_u),
-            _ptr(self.m_rbar_s_v_u), _ptr(self.m_scan_mask_s_v_u), C.byref(st) if st is not None else None),
-            "rslf_depth2d_run")
+        args = (vol.ctx._h, vol._h, self.m_dmin, self.m_dmax, self.m_dim_d, C.byref(p), _ptr(self.m_edge_confidence_s_v_u),
+                _ptr(self.m_edge_confidence_mask_s_v_u), _ptr(self.m_disp_confidence_s_v_u), _ptr(self.m_best_depth_s_v_u),
+                _ptr(self.m_rbar_s_v_u), _ptr(self.m_scan_mask_s_v_u), C.byref(st) if st is not None else None)
+        mode = self._line_mode()
+        if mode == LINE_CONF_OFF:
+            check(_lib.lib().rslf_depth2d_run(*args), "rslf_depth2d_run")
+        else:
+            if self.m_line_confidence_s_v_u is None:   # the mode was set after the constructor ran
+                self.m_line_confidence_s_v_u = torch.empty_like(self.m_edge_confidence_s_v_u)
+            check(_lib.lib().rslf_depth2d_run_lc(*args, mode, _ptr(self.m_line_confidence_s_v_u)), "rslf_depth2d_run_lc")
         self.stats = st
+
+    def _line_gates(self) -> bool:
+        """The #ifdef chain (dc.hpp:838-847, :877-888, :901-907): C_d first, then C_l where the `#elseif` branches are taken."""
+        return self._line_mode() == LINE_CONF_GATE and not self.m_parameters.par_use_disp_confidence_score
 
     def get_depths_s_v_u(self) -> torch.Tensor:
         return self.m_best_depth_s_v_u
@@ -825,6 +885,8 @@ class Depth2DComputer:
     def _confidence_mask_s_v_u(self) -> torch.Tensor:
         """The mask the two getters paint under: m_edge_confidence_mask_s_v_u in the default build (dc.hpp:840-842,
         :885-887); with par_use_disp_confidence_score, C_d > (float)par_disp_score_threshold (:832-834, :875-878)."""
+        if self._line_gates():   # dc.hpp:842, :883: C_l > (float)par_line_score_threshold, one comparison on the device
+            return (self.m_line_confidence_s_v_u > float(np.float32(self.m_parameters.par_line_score_threshold))).to(torch.uint8) * 255
         if not self.m_parameters.par_use_disp_confidence_score:
             return self.m_edge_confidence_mask_s_v_u
         return (self.m_disp_confidence_s_v_u > float(np.float32(self.m_parameters.par_disp_score_threshold))).to(torch.uint8) * 255
@@ -868,16 +930,21 @@ class Depth2DComputer:
 
     def get_valid_depths_mask_s_v_u(self) -> torch.Tensor:
         """dc.hpp:893-915, default build: C_e > edge threshold (or everything > -1 with accept_all)."""
+        if self._line_gates() and not self.m_accept_all:   # dc.hpp:904
+            return (self.m_line_confidence_s_v_u > float(np.float32(self.m_parameters.par_line_score_threshold))).to(torch.uint8) * 255
         thr = -1.0 if self.m_accept_all else float(np.float32(self.m_parameters.par_edge_score_threshold))
         return (self.m_edge_confidence_s_v_u > thr).to(torch.uint8) * 255
 
     def results(self) -> dict:
         torch.cuda.synchronize(self.m_epis.ctx.device)
-        return dict(edge_confidence=self.m_edge_confidence_s_v_u.cpu().numpy(),
-                    edge_mask=self.m_edge_confidence_mask_s_v_u.cpu().numpy(),
-                    disp_confidence=self.m_disp_confidence_s_v_u.cpu().numpy(),
-                    depth=self.m_best_depth_s_v_u.cpu().numpy(), rbar=self.m_rbar_s_v_u.cpu().numpy(),
-                    scan_mask=self.m_scan_mask_s_v_u.cpu().numpy())
+        out = dict(edge_confidence=self.m_edge_confidence_s_v_u.cpu().numpy(),
+                   edge_mask=self.m_edge_confidence_mask_s_v_u.cpu().numpy(),
+                   disp_confidence=self.m_disp_confidence_s_v_u.cpu().numpy(),
+                   depth=self.m_best_depth_s_v_u.cpu().numpy(), rbar=self.m_rbar_s_v_u.cpu().numpy(),
+                   scan_mask=self.m_scan_mask_s_v_u.cpu().numpy())
+        if self.m_line_confidence_s_v_u is not None:
+            out["line_confidence"] = self.m_line_confidence_s_v_u.cpu().numpy()
+        return out
 
 
 # ---- "next" row: the single-EPI class (SURVEY.md 8f rank 4) -------------------
@@ -1007,6 +1074,7 @@ def f2c_input(epis, ctx: Context) -> tuple[torch.Tensor, np.dtype]:
 def f2c_pyramid(raw: torch.Tensor, dtype, epi_scale_factor: float, parameters: Depth1DParameters, max_pyr_depth: int, ctx: Context):
     """The levels of FineToCoarse's constructor (f2c.hpp:103-159), finest first, each built as it is asked for:
     (V, U, the parameters with the level's slope factor, the level's scale, its raw volume [V,S,U,C])."""
+    require_no_line_confidence(parameters, "FineToCoarse")   # validity by C_l across the pyramid is not built
     start_dim_u = raw.shape[2]
     if max_pyr_depth < 1:
         max_pyr_depth = 1 << 30
@@ -1064,6 +1132,7 @@ class FineToCoarse:
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                  ctx: Context | None = None):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        require_no_line_confidence(self.m_parameters, "FineToCoarse")
         ctx = ctx or default_context()
         self.m_computers: list[Depth2DComputer] = []
         self.m_parameter_instances: list[Depth1DParameters] = []

@@ -297,6 +297,7 @@ class ShardedDepth2D:
         self.rs, self.vol, self.shard, self.group = rs, vol, shard, group
         self.bounds = (dmin, dmax) if isinstance(dmin, torch.Tensor) else None
         self.p = parameters or rs.Depth1DParameters()
+        rs.require_no_line_confidence(self.p, "ShardedDepth2D")   # C_l is local to a scanline; not carried over shards yet
         self.dmin, self.dmax = (0.0, 0.0) if self.bounds else (float(dmin), float(dmax))
         self.dim_d = int(dim_d)
         self.h = halo_rows(int(self.p.par_median_filter_size), 1)         # rows the median reads either side
@@ -456,6 +457,7 @@ class ShardedFineToCoarse:
         from . import depth as rs
         self.rs, self.rank, self.world, self.group = rs, int(rank), int(world), group
         self.m_parameters = parameters or rs.Depth1DParameters.get_default()
+        rs.require_no_line_confidence(self.m_parameters, "ShardedFineToCoarse")
         self.ctx = ctx or rs.default_context()
         self.levels: List[dict] = []
         # every level's scale is by default the own maximum of the WHOLE level (dc.hpp:671-705)
