@@ -492,6 +492,42 @@ int rslf_fine_to_coarse_run_host_u16(rslf_ctx* ctx, const uint16_t* const* h_epi
                                      const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                      float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats);
 
+/* Fine-to-coarse with the line confidence (the -D_USE_LINE_CONFIDENCE_SCORE build of FineToCoarse<T>): every level's
+ * sweep runs in line_mode (RSLF_LINE_CONF_*) with a zero-filled [S][V_p][U_p] C_l plane of its own, and each level's
+ * validity -- which tightens the next level's ranges (rslf_fine_to_coarse.hpp:185-186) and feeds the fusion (:312) -- is
+ * get_valid_depths_mask_s_v_u (dc.hpp:893-915):
+ *   accept_all (the last level, when asked to)              everything (C_e > -1)
+ *   RSLF_LINE_CONF_GATE without use_disp_confidence_score   C_l > (float)line_score_threshold  (:903-904)
+ *   otherwise                                               C_e > (float)edge_score_threshold
+ * (validity by C_d under use_disp_confidence_score, :902, is not built).  AS_BUILT changes nothing but the existence of the
+ * C_l planes.  OFF with levels_out NULL queues exactly the launches of rslf_fine_to_coarse_run_host, which is that call.
+ *
+ * levels_out (nullable): host copies of every level's planes, finest first.  Each member is NULL (not wanted) or an array
+ * of `capacity` host pointers, entry l NULL or room for [S][Vp[l]][Up[l]] values; the level sizes come from
+ * rslf_f2c_pyramid_dims.  h_Cl_svu is filled in modes AS_BUILT and GATE only.
+ * RSLF_ERR_INVALID_ARG, before anything is queued: a mode outside 0..2, a capacity below the pyramid depth. */
+typedef struct rslf_f2c_levels_out {
+    int capacity;            /* entries of each array below */
+    float** h_depth_svu;     /* the level's disparities */
+    uint8_t** h_valid_svu;   /* its validity mask, 0 / 255 */
+    float** h_Cl_svu;        /* its line confidence */
+    float** h_Ce_svu;        /* its edge confidence */
+} rslf_f2c_levels_out;
+/* The level sizes FineToCoarse's constructor builds (rslf_fine_to_coarse.hpp:130-154), finest first, into Vp / Up
+ * [capacity], and their count into n_levels (0: the field is not larger than _MIN_SPATIAL_DIM).  capacity 0 (Vp / Up may
+ * be NULL) asks for the count alone; a capacity in between is RSLF_ERR_INVALID_ARG. */
+int rslf_f2c_pyramid_dims(int V, int U, int max_pyr_depth, int* Vp, int* Up, int capacity, int* n_levels);
+int rslf_fine_to_coarse_run_host_lc(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                    float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                    int line_mode, const rslf_f2c_levels_out* levels_out);
+int rslf_fine_to_coarse_run_host_u16_lc(rslf_ctx* ctx, const uint16_t* const* h_epis, int V, int S, int U, int C,
+                                        size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                        const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                        float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                        int line_mode, const rslf_f2c_levels_out* levels_out);
+
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit
  * exchanges the neighbours' boundary rows (median reach) of the visited view's raw disparities and edge mask by peer
@@ -536,6 +572,8 @@ int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint16_t* const*
 #define RSLF_FIT_QUANTILE  1   /* ImageConverter_uchar::fit(img, true), :70-84: elements floor(0.02 N) and floor(0.98 N) of the
                                   ascending sort, N = rows * cols -- here an exact radix select, no sort */
 #define RSLF_FIT_MEANSTD   2   /* fit(img, false), :85-95: min = true min, max = min(mean + 12 std, true max), double sums */
+#define RSLF_FIT_GIVEN     3   /* rslf_render_planes_host alone: no fit, plane k goes through h_minmax[k][0 .. 1], which is then an
+                                  input -- a level of a pyramid through the converter fitted on another level */
 #define RSLF_RENDER_SHIFT  0   /* copy_and_scale_uchar, :41-63: (x - (float)min) * (float)(255.0 / (max - min)) */
 #define RSLF_RENDER_AFFINE 1   /* ImageConverter_uchar::copy_and_scale, :100-107: x * alpha + beta, alpha = (float)(255.0 / (max - min)),
                                   beta = (float)(-(double)alpha * min) */

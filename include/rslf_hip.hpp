@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rslf_hip.h"
@@ -754,12 +755,26 @@ public:
     {
     }
 #endif
+    // The -D_USE_LINE_CONFIDENCE_SCORE build of the pyramid, to be called before run(): every level's sweep runs in `mode`
+    // (RSLF_LINE_CONF_*) with a C_l plane of its own, and with RSLF_LINE_CONF_GATE (without par_use_disp_confidence_score)
+    // each level's validity is C_l > par_line_score_threshold (dc.hpp:903-904).  run() then also keeps every level's
+    // disparities, validity and line confidence for the per-level getters.  One device only.
+    void set_line_confidence_mode(int mode)
+    {
+        detail::require(!multi_, "FineToCoarse: line confidence runs on one device");
+        detail::require(mode >= RSLF_LINE_CONF_OFF && mode <= RSLF_LINE_CONF_GATE, "line confidence mode: RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE");
+        line_mode_ = mode;
+    }
     void run()
     {
         const size_t n = (size_t)dim_s_ * dim_v_ * dim_u_;
         out_map_s_v_u_.assign(n, 0.f);
         out_validity_s_v_u_.assign(n, 0);
         const rslf_params p = m_parameters.to_c();
+        if (line_mode_ >= 0) {
+            run_levels(p);
+            return;
+        }
         if (type_ == InputType::U16) {   // ushort arithmetic through the pyramid
             const uint16_t* const* e = (const uint16_t* const*)epis_.data();
             if (multi_)
@@ -820,6 +835,38 @@ public:
         return get_coloured_depth_maps(detail::own(ctx_), lut_bgr, saturate);
     }
     int pyramid_depth() const { return n_levels_; }
+    // After a run() that followed set_line_confidence_mode: the level sizes (V_p, U_p), finest first, and every level's
+    // [S][V_p][U_p] disparities, validity mask and line confidence (empty planes with RSLF_LINE_CONF_OFF).
+    const std::vector<std::pair<int, int> >& pyramid_dims() const { return dims_; }
+    const std::vector<std::vector<float> >& get_depths_pyr() const { return depths_pyr_; }
+    const std::vector<std::vector<uint8_t> >& get_validity_pyr() const { return validity_pyr_; }
+    const std::vector<std::vector<float> >& get_line_confidence_pyr() const { return line_confidence_pyr_; }
+    // rslf_fine_to_coarse.hpp:491-519: view s (-1: (int)std::round(S / 2.0)) of every level, finest first, through the
+    // converter fitted on level 0's plane before any masking; black outside each level's validity; no shadow cut ->
+    // one [V_p][U_p][3] picture per level.  Throws where the reference's index runs off the end (S = 1).
+    std::vector<std::vector<uint8_t> > get_coloured_depth_pyr(Context& on, int s, const uint8_t* lut_bgr, bool saturate = true) const
+    {
+        detail::require(!depths_pyr_.empty(), "get_coloured_depth_pyr shows the levels of a run() after set_line_confidence_mode");
+        if (s == -1)
+            check(rslf_render_centre_index(dim_s_, &s), "get_coloured_depth_pyr");
+        detail::require(s >= 0 && s < dim_s_, "get_coloured_depth_pyr: the view is not below dim_s");
+        std::vector<std::vector<uint8_t> > out(dims_.size());
+        double mm[2] = {0.0, 0.0};
+        for (size_t l = 0; l < dims_.size(); l++) {
+            const int rows = dims_[l].first, cols = dims_[l].second;
+            const size_t o = (size_t)s * rows * cols;
+            out[l].resize((size_t)rows * cols * 3);
+            check(rslf_render_planes_host(on.get(), depths_pyr_[l].data() + o, 1, 0, rows, cols, (size_t)cols, validity_pyr_[l].data() + o,
+                                          l == 0 ? (saturate ? RSLF_FIT_QUANTILE : RSLF_FIT_MEANSTD) : RSLF_FIT_GIVEN, -1, 0,
+                                          RSLF_RENDER_AFFINE, lut_bgr, RSLF_MASK_BLACK, nullptr, RSLF_SLICE_VIEW, 0, 0.f, out[l].data(), mm),
+                  "rslf_render_planes_host");
+        }
+        return out;
+    }
+    std::vector<std::vector<uint8_t> > get_coloured_depth_pyr(int s, const uint8_t* lut_bgr, bool saturate = true) const
+    {
+        return get_coloured_depth_pyr(detail::own(ctx_), s, lut_bgr, saturate);
+    }
     rslf_stats stats;
 
 private:
@@ -828,9 +875,50 @@ private:
                  int max_pyr_depth, bool accept_all_last_scale)
         : ctx_(ctx), multi_(multi), epis_(epis, epis + dim_v), type_(type), dim_v_(dim_v), dim_s_(dim_s), dim_u_(dim_u),
           stride_(row_stride_bytes), d_min_(d_min), d_max_(d_max), dim_d_(dim_d), scale_(epi_scale_factor),
-          m_parameters(parameters), max_pyr_depth_(max_pyr_depth), accept_all_(accept_all_last_scale), n_levels_(0)
+          m_parameters(parameters), max_pyr_depth_(max_pyr_depth), accept_all_(accept_all_last_scale), n_levels_(0), line_mode_(-1)
     {
         stats = rslf_stats();
+    }
+    // run() through rslf_fine_to_coarse_run_host_lc / _u16_lc, every level's planes kept
+    void run_levels(const rslf_params& p)
+    {
+        int P = 0;
+        check(rslf_f2c_pyramid_dims(dim_v_, dim_u_, max_pyr_depth_, nullptr, nullptr, 0, &P), "rslf_f2c_pyramid_dims");
+        std::vector<int> Vp(P), Up(P);
+        check(rslf_f2c_pyramid_dims(dim_v_, dim_u_, max_pyr_depth_, Vp.data(), Up.data(), P, &P), "rslf_f2c_pyramid_dims");
+        dims_.clear();
+        depths_pyr_.assign(P, std::vector<float>());
+        validity_pyr_.assign(P, std::vector<uint8_t>());
+        line_confidence_pyr_.assign(P, std::vector<float>());
+        std::vector<float*> hd(P), hl(P);
+        std::vector<uint8_t*> hv(P);
+        for (int l = 0; l < P; l++) {
+            const size_t nl = (size_t)dim_s_ * Vp[l] * Up[l];
+            dims_.push_back(std::make_pair(Vp[l], Up[l]));
+            depths_pyr_[l].assign(nl, 0.f);
+            validity_pyr_[l].assign(nl, 0);
+            if (line_mode_ != RSLF_LINE_CONF_OFF)
+                line_confidence_pyr_[l].assign(nl, 0.f);
+            hd[l] = depths_pyr_[l].data();
+            hv[l] = validity_pyr_[l].data();
+            hl[l] = line_mode_ != RSLF_LINE_CONF_OFF ? line_confidence_pyr_[l].data() : nullptr;
+        }
+        rslf_f2c_levels_out lo;
+        lo.capacity = P;
+        lo.h_depth_svu = hd.data();
+        lo.h_valid_svu = hv.data();
+        lo.h_Cl_svu = hl.data();
+        lo.h_Ce_svu = nullptr;
+        if (type_ == InputType::U16)
+            check(rslf_fine_to_coarse_run_host_u16_lc(ctx_->get(), (const uint16_t* const*)epis_.data(), dim_v_, dim_s_, dim_u_, CHANNELS,
+                                                      stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
+                                                      out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, line_mode_, &lo),
+                  "rslf_fine_to_coarse_run_host_u16_lc");
+        else
+            check(rslf_fine_to_coarse_run_host_lc(ctx_->get(), epis_.data(), type_ == InputType::U8 ? 1 : 0, dim_v_, dim_s_, dim_u_, CHANNELS,
+                                                  stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
+                                                  out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, line_mode_, &lo),
+                  "rslf_fine_to_coarse_run_host_lc");
     }
 #ifdef RSLFX_HAVE_OPENCV
     FineToCoarse(Context* ctx, MultiContext* multi, const detail::MatInput& in, float d_min, float d_max, int dim_d,
@@ -853,8 +941,12 @@ private:
     int max_pyr_depth_;
     bool accept_all_;
     int n_levels_;
+    int line_mode_;   // -1: set_line_confidence_mode was not called
     std::vector<float> out_map_s_v_u_;
     std::vector<uint8_t> out_validity_s_v_u_;
+    std::vector<std::pair<int, int> > dims_;
+    std::vector<std::vector<float> > depths_pyr_, line_confidence_pyr_;
+    std::vector<std::vector<uint8_t> > validity_pyr_;
 };
 
 typedef Depth1DComputer_pile<1> Depth1DComputer_pile_1ch;   // dc.hpp:149

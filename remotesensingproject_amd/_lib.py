@@ -40,6 +40,8 @@ SYMBOLS = [
     "rslf_render_fit_many", "rslf_render_planes_each", "rslf_render_planes_host", "rslf_render_epi_lines_host",
     # line confidence of the 2-D sweep (K7)
     "rslf_line_confidence_pile", "rslf_sweep_line_confidence", "rslf_depth_epi_2d_lc", "rslf_depth2d_run_lc", "rslf_depth2d_run_host_lc",
+    # fine-to-coarse with the line confidence
+    "rslf_f2c_pyramid_dims", "rslf_fine_to_coarse_run_host_lc", "rslf_fine_to_coarse_run_host_u16_lc",
 ]
 
 
@@ -84,6 +86,18 @@ class RslfStats(C.Structure):
         ("units", C.c_int64),
         ("scan_kernel", C.c_int),
         ("s_pad", C.c_int),
+    ]
+
+
+class RslfF2cLevelsOut(C.Structure):
+    """rslf_f2c_levels_out: per level, host pointers for the planes the caller wants."""
+
+    _fields_ = [
+        ("capacity", C.c_int),
+        ("h_depth_svu", C.POINTER(C.c_void_p)),
+        ("h_valid_svu", C.POINTER(C.c_void_p)),
+        ("h_Cl_svu", C.POINTER(C.c_void_p)),
+        ("h_Ce_svu", C.POINTER(C.c_void_p)),
     ]
 
 
@@ -189,6 +203,9 @@ def lib():
     L.rslf_fine_to_coarse_run_host.argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.c_size_t, cf, cf, ci, cf, C.POINTER(RslfParams),
                                                ci, ci, vp, vp, C.POINTER(ci), C.POINTER(RslfStats)]
     L.rslf_fine_to_coarse_run_host_u16.argtypes = L.rslf_multi_fine_to_coarse_run_host_u16.argtypes
+    L.rslf_f2c_pyramid_dims.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(ci)]
+    L.rslf_fine_to_coarse_run_host_lc.argtypes = L.rslf_fine_to_coarse_run_host.argtypes + [ci, C.POINTER(RslfF2cLevelsOut)]
+    L.rslf_fine_to_coarse_run_host_u16_lc.argtypes = L.rslf_fine_to_coarse_run_host_u16.argtypes + [ci, C.POINTER(RslfF2cLevelsOut)]
     L.rslf_f2c_level_dims.argtypes = [ci, ci, C.POINTER(ci), C.POINTER(ci)]
     L.rslf_downsample_epis_f32.argtypes = [vp, vp, ci, ci, ci, ci, vp]
     L.rslf_downsample_epis_u8.argtypes = [vp, vp, ci, ci, ci, ci, vp]

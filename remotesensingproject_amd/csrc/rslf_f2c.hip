@@ -201,11 +201,12 @@ __global__ __launch_bounds__(256) void k_fill_f32(float* __restrict__ out, long 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         out[i] = value;
 }
-// get_valid_depths_mask_s_v_u (dc.hpp:893-915, default build): C_e > thr, or everything with accept_all
-__global__ __launch_bounds__(256) void k_valid_mask(const float* __restrict__ Ce, uint8_t* __restrict__ out, long long n, float thr)
+// get_valid_depths_mask_s_v_u (dc.hpp:893-915): a confidence plane > thr -- C_e, or C_l where plan::f2c_validity says so;
+// everything (C_e > -1) with accept_all
+__global__ __launch_bounds__(256) void k_valid_mask(const float* __restrict__ conf, uint8_t* __restrict__ out, long long n, float thr)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        out[i] = (Ce[i] > thr) ? 255 : 0;
+        out[i] = (conf[i] > thr) ? 255 : 0;
 }
 inline unsigned stream_blocks(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 8192); }
 }  // namespace
@@ -277,9 +278,9 @@ static int f2c_fill_f32(hipStream_t st, float* out, size_t n, float value)
     HIP_TRY(hipGetLastError());
     return RSLF_OK;
 }
-static int f2c_valid_mask(hipStream_t st, const float* Ce, uint8_t* out, size_t n, float thr)
+static int f2c_valid_mask(hipStream_t st, const float* conf, uint8_t* out, size_t n, float thr)
 {
-    hipLaunchKernelGGL(k_valid_mask, dim3(stream_blocks(n)), dim3(256), 0, st, Ce, out, (long long)n, thr);
+    hipLaunchKernelGGL(k_valid_mask, dim3(stream_blocks(n)), dim3(256), 0, st, conf, out, (long long)n, thr);
     HIP_TRY(hipGetLastError());
     return RSLF_OK;
 }
@@ -287,10 +288,13 @@ static int f2c_valid_mask(hipStream_t st, const float* Ce, uint8_t* out, size_t 
 int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
                          float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                          int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                         int line_mode, const rslf_f2c_levels_out* levels_out,
                          const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep)
 {
     if (!ctx || !h_epis || !h_out_map_svu || !h_out_valid_svu || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    if (!plan::line_conf_mode_ok(line_mode))
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
     int rc = check_params(p);
     if (rc)
         return rc;
@@ -301,6 +305,8 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     if (dims.empty())
         return fail(RSLF_ERR_INVALID_ARG, "light field %dx%d is not larger than _MIN_SPATIAL_DIM: no pyramid level", V, U);
     const int P = (int)dims.size();
+    if (levels_out && levels_out->capacity < P)
+        return fail(RSLF_ERR_INVALID_ARG, "levels out: capacity %d < pyramid depth %d", levels_out->capacity, P);
     DevBuf raw;   // the raw (un-normalised) values of the level at hand, [V][S][U][C]
     HIP_TRY(raw.alloc((size_t)V * S * U * C * sizeof(float)));
     rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, (float*)raw.p);
@@ -330,8 +336,10 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             if (rc)
                 return rc;
         }
-        DevBuf Ce, dmin, dmax;
+        DevBuf Ce, Cl, dmin, dmax;
         HIP_TRY(Ce.alloc(n * 4));
+        if (line_mode != RSLF_LINE_CONF_OFF)
+            HIP_TRY(Cl.alloc(n * 4));   // dc.hpp:721-738: every level's computer has a plane of its own
         HIP_TRY(depth[l].alloc(n * 4));
         HIP_TRY(valid[l].alloc(n));
         if (l > 0) {
@@ -351,16 +359,37 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         lv.dmax_svu = (const float*)dmax.p;
         lv.Ce_svu = (float*)Ce.p;
         lv.depth_svu = (float*)depth[l].p;
+        lv.line_mode = line_mode;
+        lv.Cl_svu = (float*)Cl.p;
         rc = sweep(lv, &st1);
         if (rc)
             return rc;
         pixels += st1.pixels_scanned;
-        // get_valid_depths_mask_s_v_u (dc.hpp:893-915): C_e > threshold; the last level accepts everything when asked to
-        // (f2c.hpp:157-158)
-        const bool all = accept_all_last_scale && l == P - 1;
-        rc = f2c_valid_mask(st, (const float*)Ce.p, (uint8_t*)valid[l].p, n, all ? -1.0f : p->edge_score_threshold);
+        // get_valid_depths_mask_s_v_u (dc.hpp:893-915), asked for by the next level's bounds (f2c.hpp:185-186) and by the
+        // fusion (:312): the last level accepts everything when asked to (f2c.hpp:157-158)
+        switch (plan::f2c_validity(accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0, line_mode)) {
+        case plan::kValidAll:
+            rc = f2c_valid_mask(st, (const float*)Ce.p, (uint8_t*)valid[l].p, n, -1.0f);
+            break;
+        case plan::kValidLineConf:
+            rc = f2c_valid_mask(st, (const float*)Cl.p, (uint8_t*)valid[l].p, n, p->line_score_threshold);
+            break;
+        case plan::kValidEdgeConf:
+            rc = f2c_valid_mask(st, (const float*)Ce.p, (uint8_t*)valid[l].p, n, p->edge_score_threshold);
+            break;
+        }
         if (rc)
             return rc;
+        if (levels_out) {   // host copies of the level's planes; C_e and C_l leave the device with this iteration
+            const auto out = [&](void* const* hp, const void* d, size_t bytes) -> hipError_t {
+                return (hp && hp[l] && d) ? hipMemcpyAsync(hp[l], d, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+            };
+            HIP_TRY(out((void* const*)levels_out->h_depth_svu, depth[l].p, n * 4));
+            HIP_TRY(out((void* const*)levels_out->h_valid_svu, valid[l].p, n));
+            HIP_TRY(out((void* const*)levels_out->h_Cl_svu, Cl.p, n * 4));
+            HIP_TRY(out((void* const*)levels_out->h_Ce_svu, Ce.p, n * 4));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
         std::swap(raw.p, next.p);   // `next` now frees this level's raw volume
     }
 
@@ -394,11 +423,12 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     return RSLF_OK;
 }
 
-// FineToCoarse on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run.
+// FineToCoarse on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run_lc.
 static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C,
                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
-                                   uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats)
+                                   uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats, int line_mode,
+                                   const rslf_f2c_levels_out* levels_out)
 {
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
         const size_t n = (size_t)S * lv.V * lv.U;
@@ -411,23 +441,64 @@ static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* 
         if (!rc)
             rc = rslf_volume_pack_device_f32(vol, lv.raw_vsuc, lv.scale, nullptr);
         if (!rc)
-            rc = depth2d_run(ctx, vol, lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, (uint8_t*)mask.p,
-                             (float*)Cd.p, lv.depth_svu, (float*)rbar.p, nullptr, level_stats);
+            rc = depth2d_run_lc(ctx, vol, lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, (uint8_t*)mask.p,
+                                (float*)Cd.p, lv.depth_svu, (float*)rbar.p, nullptr, level_stats, lv.line_mode, lv.Cl_svu);
         rslf_volume_destroy(vol);
         return rc;
     };
     return fine_to_coarse(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, sweep);
+                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, line_mode, levels_out, sweep);
 }
+
+extern "C" int rslf_f2c_pyramid_dims(int V, int U, int max_pyr_depth, int* Vp, int* Up, int capacity, int* n_levels) RSLF_API_TRY
+{
+    if (!n_levels || V < 1 || U < 1 || capacity < 0 || (capacity > 0 && (!Vp || !Up)))
+        return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    const std::vector<plan::LevelDims> dims = plan::f2c_pyramid(V, U, max_pyr_depth);
+    *n_levels = (int)dims.size();
+    if (capacity < *n_levels)
+        return capacity == 0 ? RSLF_OK : fail(RSLF_ERR_INVALID_ARG, "capacity %d < pyramid depth %d", capacity, *n_levels);
+    for (int l = 0; l < *n_levels; l++) {
+        Vp[l] = dims[l].V;
+        Up[l] = dims[l].U;
+    }
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_fine_to_coarse_run_host_lc(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
+                                               size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                               const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                               float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                               int line_mode, const rslf_f2c_levels_out* levels_out) RSLF_API_TRY
+{
+    return fine_to_coarse_run_host(ctx, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
+                                   stats, line_mode, levels_out);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_fine_to_coarse_run_host_u16_lc(rslf_ctx* ctx, const uint16_t* const* h_epis, int V, int S, int U, int C,
+                                                   size_t row_stride_bytes, float d_min, float d_max, int dim_d,
+                                                   float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                                                   int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu,
+                                                   int* n_levels, rslf_stats* stats, int line_mode,
+                                                   const rslf_f2c_levels_out* levels_out) RSLF_API_TRY
+{
+    return fine_to_coarse_run_host(ctx, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
+                                   stats, line_mode, levels_out);
+}
+RSLF_API_CATCH
 
 extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
                                             size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                             const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                             float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
 {
-    return fine_to_coarse_run_host(ctx, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
-                                   stats);
+    return rslf_fine_to_coarse_run_host_lc(ctx, h_epis, is_u8, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                                           max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats,
+                                           RSLF_LINE_CONF_OFF, nullptr);
 }
 RSLF_API_CATCH
 
@@ -436,8 +507,8 @@ extern "C" int rslf_fine_to_coarse_run_host_u16(rslf_ctx* ctx, const uint16_t* c
                                                 const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                                 float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
 {
-    return fine_to_coarse_run_host(ctx, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
-                                   stats);
+    return rslf_fine_to_coarse_run_host_u16_lc(ctx, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                                               max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats,
+                                               RSLF_LINE_CONF_OFF, nullptr);
 }
 RSLF_API_CATCH

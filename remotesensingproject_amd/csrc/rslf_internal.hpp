@@ -361,6 +361,11 @@ int sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const S
 int depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
                 int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                 float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats);
+// The same with the line-confidence plane of dc.hpp:721-738, :791-792: line_mode RSLF_LINE_CONF_*, d_Cl_svu [S][V][U]
+// (zero-filled here; NULL with RSLF_LINE_CONF_OFF, which queues exactly the launches of depth2d_run).
+int depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
+                   int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                   float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu);
 
 // rslf_f2c.hip
 // One level of FineToCoarse as its sweep sees it, every pointer on the context's device.
@@ -373,13 +378,17 @@ struct F2cLevel {
     const float* dmax_svu = nullptr;
     float* Ce_svu = nullptr;            // [S][V][U] results the sweep fills: edge confidence, disparities
     float* depth_svu = nullptr;
+    int line_mode = RSLF_LINE_CONF_OFF; // the mode of the level's sweep and its zero-filled [S][V][U] C_l plane (NULL when off)
+    float* Cl_svu = nullptr;
 };
 // FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from host EPIs of element type elem
 // into host planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which
-// reports the level's stats.
+// reports the level's stats.  line_mode: every level's sweep mode, and through plan::f2c_validity the plane its validity is
+// read from; levels_out (nullable): host copies of every level's planes.
 int fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
                    float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                    int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                   int line_mode, const rslf_f2c_levels_out* levels_out,
                    const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep);
 
 // rslf_multi.hip

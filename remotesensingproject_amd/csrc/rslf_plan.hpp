@@ -203,6 +203,18 @@ inline SweepGate sweep_gate(bool use_disp_confidence_score, int line_mode)
     return line_mode == kLineConfGate ? kGateLineConf : kGateEdgeMask;
 }
 
+// Which plane a level of the pyramid reads its validity from (get_valid_depths_mask_s_v_u, dc.hpp:893-915, asked for by the
+// next level's bounds, f2c.hpp:185-186, and by the fusion, :312): everything (C_e > -1) with accept_all; C_l > the line
+// threshold where the line confidence gates (mode 2, and C_d does not come first in the #ifdef chain); else C_e > the edge
+// threshold.  Validity by C_d under use_disp_confidence_score (:902) is not built: that case reads C_e.
+enum F2cValidity { kValidAll = 0, kValidLineConf = 1, kValidEdgeConf = 2 };
+inline F2cValidity f2c_validity(bool accept_all, bool use_disp_confidence_score, int line_mode)
+{
+    if (accept_all)
+        return kValidAll;
+    return sweep_gate(use_disp_confidence_score, line_mode) == kGateLineConf ? kValidLineConf : kValidEdgeConf;
+}
+
 // K7 runs before the claims only where the claims gate on its plane; it then needs the filtered plane first, from a median
 // pass of its own.  Where C_d or the edge mask gates, K7 follows median + claims (which leaves the filtered plane).
 inline bool line_conf_before_claims(bool use_disp_confidence_score, int mode)

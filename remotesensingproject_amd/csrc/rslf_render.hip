@@ -298,9 +298,12 @@ extern "C" int rslf_render_planes_host(rslf_ctx* ctx, const float* h_planes, int
                                        const uint8_t* lut_bgr, int mask_mode, const rslf_volume* vol, int slice_kind, int index,
                                        float shadow_level, uint8_t* h_bgr_out, double* h_minmax) RSLF_API_TRY
 {
-    int rc = check_fit_args(ctx, h_planes, h_bgr_out, n_planes, rows, cols, row_stride, fit_mode);
+    const bool given = fit_mode == RSLF_FIT_GIVEN;   // no fit: the ranges come in through h_minmax
+    int rc = check_fit_args(ctx, h_planes, h_bgr_out, n_planes, rows, cols, row_stride, given ? RSLF_FIT_MINMAX : fit_mode);
     if (rc)
         return rc;
+    if (given && !h_minmax)
+        return fail(RSLF_ERR_INVALID_ARG, "RSLF_FIT_GIVEN needs h_minmax");
     if (!lut_bgr || fit_plane < -1 || fit_plane >= n_planes || (fit_masked && !h_valid) || (n_planes > 1 && plane_stride == 0))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -321,7 +324,9 @@ extern "C" int rslf_render_planes_host(rslf_ctx* ctx, const float* h_planes, int
     const float* planes = (const float*)d_planes;
     const uint8_t* valid = (const uint8_t*)d_valid;
     std::vector<double> mm(2 * (size_t)n_planes);
-    if (fit_plane < 0) {   // every plane through its own range
+    if (given) {
+        std::copy(h_minmax, h_minmax + mm.size(), mm.begin());
+    } else if (fit_plane < 0) {   // every plane through its own range
         rc = fit_many(ctx, planes, n_planes, plane_stride, rows, cols, row_stride, fit_masked ? valid : nullptr, fit_mode, mm.data());
     } else {               // every plane through plane fit_plane's range
         const size_t o = (size_t)fit_plane * plane_stride;
@@ -330,13 +335,13 @@ extern "C" int rslf_render_planes_host(rslf_ctx* ctx, const float* h_planes, int
             mm[2 * k] = mm[0], mm[2 * k + 1] = mm[1];
     }
     if (!rc)
-        rc = render_planes(ctx, planes, n_planes, plane_stride, rows, cols, row_stride, mm.data(), fit_plane < 0, formula, lut_bgr, valid, mask_mode,
+        rc = render_planes(ctx, planes, n_planes, plane_stride, rows, cols, row_stride, mm.data(), given || fit_plane < 0, formula, lut_bgr, valid, mask_mode,
                            vol, slice_kind, index, shadow_level, (uint8_t*)d_out);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(h_bgr_out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_minmax)
+    if (h_minmax && !given)
         std::copy(mm.begin(), mm.end(), h_minmax);
     return RSLF_OK;
 }

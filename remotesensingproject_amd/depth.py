@@ -1071,10 +1071,26 @@ def f2c_input(epis, ctx: Context) -> tuple[torch.Tensor, np.dtype]:
     return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(ctx.device), field_dtype(a.dtype)
 
 
-def f2c_pyramid(raw: torch.Tensor, dtype, epi_scale_factor: float, parameters: Depth1DParameters, max_pyr_depth: int, ctx: Context):
+def f2c_line_mode(parameters: Depth1DParameters, line_confidence_mode: int | None, who: str) -> int:
+    """The line mode of a pyramid.  None: no line confidence, and parameters that ask for one are refused (the paths that
+    do not carry C_l).  0 / 1 / 2: that mode on every level; parameters.par_line_confidence_mode must be 0 or equal to it."""
+    if line_confidence_mode is None:
+        require_no_line_confidence(parameters, who)
+        return LINE_CONF_OFF
+    mode = int(line_confidence_mode)
+    if mode not in (LINE_CONF_OFF, LINE_CONF_AS_BUILT, LINE_CONF_GATE):
+        raise ValueError("%s: line_confidence_mode=%d: 0 (off), 1 (as built) or 2 (gate)" % (who, mode))
+    if int(parameters.par_line_confidence_mode) not in (LINE_CONF_OFF, mode):
+        raise ValueError("%s: par_line_confidence_mode=%d disagrees with line_confidence_mode=%d"
+                         % (who, int(parameters.par_line_confidence_mode), mode))
+    return mode
+
+
+def f2c_pyramid(raw: torch.Tensor, dtype, epi_scale_factor: float, parameters: Depth1DParameters, max_pyr_depth: int, ctx: Context,
+                line_confidence_mode: int | None = None):
     """The levels of FineToCoarse's constructor (f2c.hpp:103-159), finest first, each built as it is asked for:
-    (V, U, the parameters with the level's slope factor, the level's scale, its raw volume [V,S,U,C])."""
-    require_no_line_confidence(parameters, "FineToCoarse")   # validity by C_l across the pyramid is not built
+    (V, U, the parameters with the level's slope factor and line mode, the level's scale, its raw volume [V,S,U,C])."""
+    mode = f2c_line_mode(parameters, line_confidence_mode, "FineToCoarse")
     start_dim_u = raw.shape[2]
     if max_pyr_depth < 1:
         max_pyr_depth = 1 << 30
@@ -1083,6 +1099,7 @@ def f2c_pyramid(raw: torch.Tensor, dtype, epi_scale_factor: float, parameters: D
         counter += 1
         par = copy.copy(parameters)
         par.par_slope_factor = float(np.float32((0.0 + raw.shape[2]) / start_dim_u))                     # f2c.hpp:139
+        par.par_line_confidence_mode = mode
         scale, nxt = f2c_level(raw, dtype, epi_scale_factor, ctx)
         yield raw.shape[0], raw.shape[2], par, scale, raw
         raw = nxt                                                                                       # f2c.hpp:145-147
@@ -1119,6 +1136,46 @@ def f2c_fuse(ctx: Context, depths: Sequence[torch.Tensor], valids: Sequence[torc
     return out_map, out_valid
 
 
+def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
+                            parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
+                            ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False) -> dict:
+    """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
+    [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
+    and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
+    (line_confidence is None in mode 0)."""
+    ctx = ctx or default_context()
+    keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
+    L = _lib.lib()
+    out_map, out_valid = np.empty((S, V, U), np.float32), np.empty((S, V, U), np.uint8)
+    p = (parameters or Depth1DParameters()).to_c()
+    st, nl = RslfStats(), C.c_int()
+    levels, lo = [], None
+    if want_levels:
+        check(L.rslf_f2c_pyramid_dims(V, U, int(max_pyr_depth), None, None, 0, C.byref(nl)), "rslf_f2c_pyramid_dims")
+        P = nl.value
+        Vp, Up = (C.c_int * P)(), (C.c_int * P)()
+        check(L.rslf_f2c_pyramid_dims(V, U, int(max_pyr_depth), Vp, Up, P, C.byref(nl)), "rslf_f2c_pyramid_dims")
+        for l in range(P):
+            shape = (S, Vp[l], Up[l])
+            levels.append(dict(depth=np.empty(shape, np.float32), valid=np.empty(shape, np.uint8),
+                               line_confidence=np.empty(shape, np.float32) if line_mode != LINE_CONF_OFF else None,
+                               edge_confidence=np.empty(shape, np.float32)))
+        arr = lambda k: (C.c_void_p * P)(*[None if lv[k] is None else lv[k].ctypes.data for lv in levels])
+        lo = _lib.RslfF2cLevelsOut(P, arr("depth"), arr("valid"), arr("line_confidence"), arr("edge_confidence"))
+    rest = (V, S, U, C_, 0, float(d_min), float(d_max), int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
+            1 if accept_all_last_scale else 0, out_map.ctypes.data_as(C.c_void_p), out_valid.ctypes.data_as(C.c_void_p),
+            C.byref(nl), C.byref(st), int(line_mode), C.byref(lo) if lo is not None else None)
+    ctx.use_current_stream()
+    if dt == np.uint16:
+        check(L.rslf_fine_to_coarse_run_host_u16_lc(ctx._h, ptrs, *rest), "rslf_fine_to_coarse_run_host_u16_lc")
+    else:
+        check(L.rslf_fine_to_coarse_run_host_lc(ctx._h, ptrs, 1 if dt == np.uint8 else 0, *rest), "rslf_fine_to_coarse_run_host_lc")
+    out = dict(out_map=out_map, out_valid=out_valid, n_levels=int(nl.value), stats=st)
+    if want_levels:
+        out["levels"] = levels
+    return out
+
+
 class FineToCoarse:
     """rslf::FineToCoarse<T> (include/rslf_fine_to_coarse.hpp:26-81, :103-324): a pyramid of Depth2DComputers,
     each level halving (v, u) -- never s --, with slope_factor = U_p / U_0, per-pixel hypothesis ranges
@@ -1126,17 +1183,23 @@ class FineToCoarse:
 
     `epis`: the reference's Vec<Mat> (list of V arrays [S,U] / [S,U,3]) or a dense array [V,S,U(,C)],
     float32, uint8 or uint16.  An integer light field keeps its own arithmetic through the pyramid, as the reference's
-    CV_8U / CV_16U Mats do."""
+    CV_8U / CV_16U Mats do.
+
+    `line_confidence_mode` (None, 0, 1 or 2) is the -D_USE_LINE_CONFIDENCE_SCORE build of the pyramid: every level's
+    computer runs in that mode with a C_l plane of its own, and in mode 2 (without par_use_disp_confidence_score) each
+    level's validity -- the next level's bounds and the fusion -- is C_l > par_line_score_threshold (dc.hpp:903-904).
+    None is the default build; parameters whose par_line_confidence_mode is set are then refused."""
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                 ctx: Context | None = None):
+                 ctx: Context | None = None, line_confidence_mode: int | None = None):
         self.m_parameters = parameters or Depth1DParameters.get_default()
-        require_no_line_confidence(self.m_parameters, "FineToCoarse")
+        f2c_line_mode(self.m_parameters, line_confidence_mode, "FineToCoarse")
         ctx = ctx or default_context()
         self.m_computers: list[Depth2DComputer] = []
         self.m_parameter_instances: list[Depth1DParameters] = []
-        for _, _, par, scale, raw in f2c_pyramid(*f2c_input(epis, ctx), epi_scale_factor, self.m_parameters, max_pyr_depth, ctx):
+        for _, _, par, scale, raw in f2c_pyramid(*f2c_input(epis, ctx), epi_scale_factor, self.m_parameters, max_pyr_depth, ctx,
+                                                 line_confidence_mode):
             vol = Volume.from_dense(raw, scale, ctx)
             self.m_computers.append(Depth2DComputer(vol, d_min, d_max, dim_d, parameters=par))
             self.m_parameter_instances.append(par)
@@ -1154,13 +1217,16 @@ class FineToCoarse:
             dmin, dmax = f2c_ranges(vol.ctx, up.m_best_depth_s_v_u, up.get_valid_depths_mask_s_v_u(), vol.V, vol.U, self._dmin, self._dmax)
             comp.m_dmin_s_v_u, comp.m_dmax_s_v_u = dmin, dmax
             # Depth2DComputer::run with per-pixel ranges (edit_dmin / edit_dmax, dc.hpp:201-203)
-            for t in (comp.m_edge_confidence_s_v_u, comp.m_disp_confidence_s_v_u, comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u):
-                t.zero_()
+            for t in (comp.m_edge_confidence_s_v_u, comp.m_disp_confidence_s_v_u, comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u,
+                      comp.m_line_confidence_s_v_u):
+                if t is not None:
+                    t.zero_()
             comp.m_edge_confidence_mask_s_v_u = compute_2D_edge_confidence(vol, comp.m_edge_confidence_s_v_u, comp.m_parameters)
             comp.stats = compute_2D_depth_epi(vol, dmin, dmax, comp.m_dim_d, comp.m_edge_confidence_s_v_u,
                                               comp.m_edge_confidence_mask_s_v_u, comp.m_disp_confidence_s_v_u,
                                               comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u, comp.m_parameters,
-                                              scan_mask_s_v_u=comp.m_scan_mask_s_v_u, want_stats=True)
+                                              scan_mask_s_v_u=comp.m_scan_mask_s_v_u, want_stats=True,
+                                              a_line_confidence_s_v_u=comp.m_line_confidence_s_v_u)
 
     def get_results(self):
         """f2c.hpp:302-324 -> (out_map_s_v_u [S,V,U] f32, out_validity_s_v_u [S,V,U] u8) at the finest scale."""

@@ -17,6 +17,13 @@ it).  K7's own time comes from a kernel trace of this tool:
 
 and --k7-stats OUT/.../*_kernel_stats.csv turns the trace's k7_line_confidence row into time per visit and bytes per second.
 Prints one JSON line per mode and one for the copy.
+
+    python tools/probe_line_conf.py --f2c [--config skysat_lr] [--modes 0,1,2] [--reps 3] [--threshold T] [--k7-stats stats.csv]
+
+is the same for fine-to-coarse: bench.py --path f2c's step (FineToCoarse constructor + run + get_results on the raw field, host
+upload included) with line_confidence_mode = the mode, the modes alternating.  Mode 2 takes the median of mode 1's C_l over
+the masked pixels of the finest level unless --threshold is given, and every mode reports each level's share of valid pixels.
+--k7-stats here gives K7's share of the kernel time of the traced run (the trace's Percentage column).
 """
 from __future__ import annotations
 
@@ -42,15 +49,89 @@ def k7_row(path: str):
     return calls, total
 
 
+def kernel_share(path: str, needle: str):
+    """(calls, total ns, share of all kernel time) of the rows of a rocprofv3 kernel_stats.csv whose name holds `needle`."""
+    calls, total, everything = 0, 0.0, 0.0
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            everything += float(row["TotalDurationNs"])
+            if needle in row.get("Name", ""):
+                calls += int(row["Calls"])
+                total += float(row["TotalDurationNs"])
+    return calls, total, (total / everything if everything else 0.0)
+
+
+def f2c(args) -> None:
+    import numpy as np
+    import torch
+    from remotesensingproject_amd import depth as rs
+    from remotesensingproject_amd.synth import CONFIGS, make_lightfield
+
+    cfg = dict(CONFIGS[args.config])
+    U, V, S, C, D = cfg["U"], cfg["V"], cfg["S"], cfg["C"], cfg["D"]
+    modes = [int(m) for m in args.modes.split(",")]
+    torch.cuda.set_device(0)
+    host, _ = make_lightfield(U, V, S, C, seed=cfg["seed"], dmin=cfg["dmin"], dmax=cfg["dmax"])
+    raw = (host * 200.0 + 3.0).astype(np.float32)
+
+    def once(mode: int, thr: float):
+        f = rs.FineToCoarse(raw, cfg["dmin"], cfg["dmax"], D, parameters=rs.Depth1DParameters(par_line_score_threshold=thr),
+                            line_confidence_mode=mode)
+        f.run()
+        f.get_results()
+        torch.cuda.synchronize()
+        return f
+
+    thr = 0.02
+    if args.threshold is not None:
+        thr = args.threshold
+    elif 2 in modes:
+        c0 = once(1, thr).m_computers[0]
+        m = c0.m_edge_confidence_mask_s_v_u != 0
+        thr = float(c0.m_line_confidence_s_v_u[m].median()) if bool(m.any()) else 0.02
+        del c0
+    last = {mode: once(mode, thr) for mode in modes}   # warm-up: scratch sized, clocks up
+    times = {mode: [] for mode in modes}
+    for _ in range(args.reps):
+        for mode in modes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[mode] = once(mode, thr)
+            times[mode].append((time.perf_counter() - t0) * 1e3)
+    for mode in modes:
+        comps = last[mode].m_computers
+        line = {"path": "f2c", "config": args.config, "mode": mode, "ms_median": statistics.median(times[mode]),
+                "ms_runs": [round(t, 3) for t in times[mode]], "levels": [(c.m_epis.V, c.m_epis.U) for c in comps],
+                "pixels_scanned": [int(c.stats.pixels_scanned) for c in comps],
+                "valid_share": [round(float((c.get_valid_depths_mask_s_v_u() != 0).float().mean()), 4) for c in comps]}
+        if mode:
+            # K7 per visit: 4 S + 4 bytes per masked pixel, 4 S per scanned pixel, the S rows of C_e once per scanline
+            masked = [int((c.m_edge_confidence_mask_s_v_u != 0).sum()) for c in comps]
+            line.update(k7_masked_pixels=masked, line_score_threshold=thr,
+                        k7_algorithmic_bytes=sum(m * (4 * S + 4) + int(c.stats.pixels_scanned) * 4 * S + S * (c.m_epis.V * S * c.m_epis.U * 4)
+                                                 for m, c in zip(masked, comps)))
+            if args.k7_stats:
+                calls, ns, share = kernel_share(args.k7_stats, "k7_line_confidence")
+                line.update(k7_calls=calls, k7_ms_total=ns / 1e6, k7_share_of_kernel_time=share)
+        print(json.dumps(line), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="c2", choices=["c2", "c3"])
+    ap.add_argument("--f2c", action="store_true", help="fine-to-coarse (bench.py --path f2c's step) instead of one 2-D sweep")
+    ap.add_argument("--config", default=None, help="c2 / c3 (the sweep; default c2), or with --f2c any config of synth.CONFIGS (default skysat_lr)")
     ap.add_argument("--modes", default="0,1,2")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-copy", action="store_true")
     ap.add_argument("--threshold", type=float, default=None, help="par_line_score_threshold of the mode-2 runs (default: measured)")
     ap.add_argument("--k7-stats", default="", help="rocprofv3 kernel_stats.csv of a run of this tool with ONE timed mode-1 or mode-2 run")
     args = ap.parse_args()
+    if args.f2c:
+        args.config = args.config or "skysat_lr"
+        return f2c(args)
+    args.config = args.config or "c2"
+    if args.config not in ("c2", "c3"):
+        ap.error("the sweep form takes --config c2 or c3")
     import numpy as np
     import torch
     from remotesensingproject_amd import depth as rs
