@@ -47,50 +47,30 @@ extern "C" int rslf_debug_inject(const char* site, int count) RSLF_API_TRY
 }
 RSLF_API_CATCH
 
+// Pixel lists and the raw-disparity plane of V x U pixels, per-scanline counts and row bases of V scanlines
 int rslf::ensure_plane_scratch(rslf_ctx* ctx, int V, int U)
 {
+    Scratch& sc = ctx->scratch;
     const size_t n = (size_t)V * U;
-    if (n > ctx->plane_cap) {
-        if (ctx->list)
-            HIP_TRY(hipFree(ctx->list));
-        if (ctx->depth_tmp)
-            HIP_TRY(hipFree(ctx->depth_tmp));
-        ctx->list = nullptr;
-        ctx->depth_tmp = nullptr;
-        ctx->plane_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->list, n * sizeof(int)));
-        HIP_TRY(hipMalloc(&ctx->depth_tmp, n * sizeof(float)));
-        ctx->plane_cap = n;
-    }
-    if (V > ctx->count_cap) {
-        if (ctx->count)
-            HIP_TRY(hipFree(ctx->count));
-        ctx->count = nullptr;
-        ctx->count_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->count, (size_t)2 * V * sizeof(int)));   // [count_cap] entries per row, then [count_cap] row bases of packed lists
-        ctx->count_cap = V;
-    }
+    HIP_TRY(hip_err(sc.list.reserve(n * sizeof(int))));
+    HIP_TRY(hip_err(sc.depth_tmp.reserve(n * sizeof(float))));
+    HIP_TRY(hip_err(sc.count.reserve((size_t)V * sizeof(int))));
+    HIP_TRY(hip_err(sc.rowbase.reserve((size_t)V * sizeof(int))));
     return RSLF_OK;
 }
 
 // Records and tickets of grouped scan launches (k2_scan.hpp): grow-only, so a context allocates them once.
-int rslf::ensure_group_scratch(rslf_ctx* ctx, size_t recs, size_t tiles)
+// tickets_fresh (nullable): new tickets were made, and their zeros are queued on the context's stream.
+int rslf::ensure_group_scratch(rslf_ctx* ctx, size_t recs, size_t tiles, bool* tickets_fresh)
 {
-    if (recs > ctx->partial_rec_cap) {
-        HIP_TRY(hipFree(ctx->scan_partial));
-        ctx->scan_partial = nullptr;
-        ctx->partial_rec_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->scan_partial, recs * plan::kPartialRecordBytes));
-        ctx->partial_rec_cap = recs;
-    }
-    if (tiles > ctx->ticket_cap) {
-        HIP_TRY(hipFree(ctx->scan_ticket));
-        ctx->scan_ticket = nullptr;
-        ctx->ticket_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->scan_ticket, tiles * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(ctx->scan_ticket, 0, tiles * sizeof(int), ctx->stream));   // the kernels leave it at zero
-        ctx->ticket_cap = tiles;
-    }
+    Scratch& sc = ctx->scratch;
+    HIP_TRY(hip_err(sc.scan_partial.reserve(recs * plan::kPartialRecordBytes)));
+    const Reserved t = sc.scan_ticket.reserve(tiles * sizeof(int));
+    HIP_TRY(hip_err(t));
+    if (t.fresh)   // the kernels leave it at zero
+        HIP_TRY(hipMemsetAsync(sc.scan_ticket.get(), 0, sc.scan_ticket.capacity(), ctx->stream));
+    if (tickets_fresh)
+        *tickets_fresh = t.fresh;
     return RSLF_OK;
 }
 
@@ -211,15 +191,15 @@ extern "C" int rslf_ctx_create(int device, rslf_ctx** out) RSLF_API_TRY
         return fail(RSLF_ERR_ALLOC, "out of host memory");
     ctx->device = device;
     (void)hipDeviceGetAttribute(&ctx->num_cus, hipDeviceAttributeMultiprocessorCount, device);
-    hipError_t e = hipMalloc(&ctx->total, 2 * sizeof(unsigned long long));   // [0] scanned pixels, [1] packed-list length (int)
+    hipError_t e = hip_err(ctx->scratch.total.reserve(2 * sizeof(unsigned long long)));   // Scratch::pixel_total, packed_len
     if (e == hipSuccess)
-        e = hipMalloc(&ctx->minmax, 2 * sizeof(float));
+        e = hip_err(ctx->scratch.minmax.reserve(2 * sizeof(float)));
     if (e == hipSuccess)
         e = hipEventCreate(&ctx->ev0);
     if (e == hipSuccess)
         e = hipEventCreate(&ctx->ev1);
     if (e != hipSuccess) {
-        (void)rslf_ctx_destroy(ctx);   // frees whatever of total / minmax / the events was made
+        (void)rslf_ctx_destroy(ctx);   // whatever of total / minmax / the events was made goes with it
         return fail(RSLF_ERR_HIP, "context setup failed: %s", hipGetErrorString(e));
     }
     *out = ctx;
@@ -233,29 +213,13 @@ extern "C" int rslf_ctx_destroy(rslf_ctx* ctx) RSLF_API_TRY
         return RSLF_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(ctx->list);
-    (void)hipFree(ctx->count);
-    (void)hipFree(ctx->depth_tmp);
-    (void)hipFree(ctx->total);
-    (void)hipFree(ctx->partial);
-    (void)hipFree(ctx->minmax);
-    (void)hipFree(ctx->staging);
-    (void)hipFree(ctx->scan_partial);
-    (void)hipFree(ctx->scan_ticket);
-    for (int i = 0; i < rslf_ctx::kHelperSlots; i++)
-        (void)hipFree(ctx->helper[i]);
-    (void)hipFree(ctx->winner);
-    (void)hipFree(ctx->dirty);
-    (void)hipFree(ctx->remain);
-    (void)hipFree(ctx->sweep_mask);
-    (void)hipFree(ctx->filtered);
     for (hipEvent_t e : ctx->ev_pool)
         (void)hipEventDestroy(e);
     if (ctx->ev0)
         (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1)
         (void)hipEventDestroy(ctx->ev1);
-    delete ctx;
+    delete ctx;   // every buffer of ctx->scratch is freed by its destructor
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -380,43 +344,24 @@ RSLF_API_CATCH
 
 static int ensure_partial(rslf_ctx* ctx, size_t rows)
 {
-    if (rows > ctx->partial_cap) {
-        if (ctx->partial)
-            HIP_TRY(hipFree(ctx->partial));
-        ctx->partial = nullptr;
-        ctx->partial_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->partial, rows * 2 * sizeof(float)));
-        ctx->partial_cap = rows;
-    }
+    HIP_TRY(hip_err(ctx->scratch.partial.reserve(rows * 2 * sizeof(float))));
     return RSLF_OK;
 }
 
 int rslf::ensure_staging(rslf_ctx* ctx, size_t bytes)
 {
-    if (bytes > ctx->staging_cap) {
-        if (ctx->staging)
-            HIP_TRY(hipFree(ctx->staging));
-        ctx->staging = nullptr;
-        ctx->staging_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->staging, bytes));
-        ctx->staging_cap = bytes;
-    }
+    HIP_TRY(hip_err(ctx->scratch.staging.reserve(bytes)));
     return RSLF_OK;
 }
 
-// Helper scratch slot `slot`, at least `bytes` large.  Growing it frees the old buffer, which waits for the
-// device; after the first call of a given size nothing is allocated any more.
-int rslf::helper_scratch(rslf_ctx* ctx, int slot, size_t bytes, void** out)
+// Shared buffer `which` (SharedBuf in rslf_internal.hpp: who shares it and why that is safe), at least `bytes` large.
+// Growing it frees the old buffer, which waits for the device; after the first call of a given size nothing is allocated
+// any more.
+int rslf::helper_scratch(rslf_ctx* ctx, SharedBuf which, size_t bytes, void** out)
 {
-    if (bytes > ctx->helper_cap[slot]) {
-        if (ctx->helper[slot])
-            HIP_TRY(hipFree(ctx->helper[slot]));
-        ctx->helper[slot] = nullptr;
-        ctx->helper_cap[slot] = 0;
-        HIP_TRY(hipMalloc(&ctx->helper[slot], bytes));
-        ctx->helper_cap[slot] = bytes;
-    }
-    *out = ctx->helper[slot];
+    DeviceBuf& b = ctx->scratch.shared[which];
+    HIP_TRY(hip_err(b.reserve(bytes)));
+    *out = b.get();
     return RSLF_OK;
 }
 
@@ -428,7 +373,7 @@ __global__ void k_init_minmax(float* minmax)
 
 static int minmax_begin(rslf_ctx* ctx)
 {
-    hipLaunchKernelGGL(k_init_minmax, dim3(1), dim3(1), 0, ctx->stream, ctx->minmax);
+    hipLaunchKernelGGL(k_init_minmax, dim3(1), dim3(1), 0, ctx->stream, ctx->scratch.minmax.as<float>());
     HIP_TRY(hipGetLastError());
     return RSLF_OK;
 }
@@ -437,7 +382,7 @@ static int minmax_end(rslf_volume* vol)
 {
     rslf_ctx* ctx = vol->ctx;
     float mm[2];
-    HIP_TRY(hipMemcpyAsync(mm, ctx->minmax, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(mm, ctx->scratch.minmax.get(), sizeof(mm), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     vol->min_value = mm[0];
     vol->max_value = mm[1];
@@ -456,12 +401,13 @@ static int pack_chunk(rslf_volume* vol, const SrcT* d_src, int V0, int Vn, bool 
         return rc;
     if (image_major)
         hipLaunchKernelGGL((k0_pack<SrcT, true>), dim3((unsigned)rows), dim3(256), 0, ctx->stream, d_src, vol->base, V0, Vn, Vn,
-                           vol->S, vol->U, vol->C, vol->pitch, scale, ctx->partial);
+                           vol->S, vol->U, vol->C, vol->pitch, scale, ctx->scratch.partial.as<float>());
     else
         hipLaunchKernelGGL((k0_pack<SrcT, false>), dim3((unsigned)rows), dim3(256), 0, ctx->stream, d_src, vol->base, V0, Vn, Vn,
-                           vol->S, vol->U, vol->C, vol->pitch, scale, ctx->partial);
+                           vol->S, vol->U, vol->C, vol->pitch, scale, ctx->scratch.partial.as<float>());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k0_minmax_final, dim3(1), dim3(256), 0, ctx->stream, ctx->partial, (int)rows, ctx->minmax);
+    hipLaunchKernelGGL(k0_minmax_final, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch.partial.as<float>(), (int)rows,
+                       ctx->scratch.minmax.as<float>());
     HIP_TRY(hipGetLastError());
     return RSLF_OK;
 }
@@ -482,6 +428,7 @@ int rslf::upload_host(rslf_volume* vol, const SrcT* const* h_ptrs, size_t row_st
     int rc = ensure_staging(ctx, (size_t)chunk * epi_bytes);
     if (rc)
         return rc;
+    char* const staging = ctx->scratch.staging.as<char>();
     rc = minmax_begin(ctx);
     if (rc)
         return rc;
@@ -497,7 +444,7 @@ int rslf::upload_host(rslf_volume* vol, const SrcT* const* h_ptrs, size_t row_st
             // (57 GB/s measured, tools/probe_h2d.py) where the 2-D form with its 8 KB rows reached about 10.
             for (int i = 0; i < vn;) {
                 if (row_stride_bytes != row_bytes) {
-                    HIP_TRY(hipMemcpy2DAsync((char*)ctx->staging + (size_t)i * epi_bytes, row_bytes, h_ptrs[v0 + i], row_stride_bytes,
+                    HIP_TRY(hipMemcpy2DAsync(staging + (size_t)i * epi_bytes, row_bytes, h_ptrs[v0 + i], row_stride_bytes,
                                              row_bytes, vol->S, hipMemcpyHostToDevice, ctx->stream));
                     i++;
                     continue;
@@ -505,7 +452,7 @@ int rslf::upload_host(rslf_volume* vol, const SrcT* const* h_ptrs, size_t row_st
                 int n = 1;
                 while (i + n < vn && (const char*)h_ptrs[v0 + i + n] == (const char*)h_ptrs[v0 + i] + (size_t)n * epi_bytes)
                     n++;
-                HIP_TRY(hipMemcpyAsync((char*)ctx->staging + (size_t)i * epi_bytes, h_ptrs[v0 + i], (size_t)n * epi_bytes,
+                HIP_TRY(hipMemcpyAsync(staging + (size_t)i * epi_bytes, h_ptrs[v0 + i], (size_t)n * epi_bytes,
                                        hipMemcpyHostToDevice, ctx->stream));
                 i += n;
             }
@@ -515,15 +462,15 @@ int rslf::upload_host(rslf_volume* vol, const SrcT* const* h_ptrs, size_t row_st
                 if (!h_ptrs[s])
                     return fail(RSLF_ERR_INVALID_ARG, "h_imgs[%d] is NULL", s);
                 if (row_stride_bytes == row_bytes)   // dense rows: one run of bytes (see above)
-                    HIP_TRY(hipMemcpyAsync((char*)ctx->staging + (size_t)s * vn * row_bytes, (const char*)h_ptrs[s] + (size_t)v0 * row_bytes,
+                    HIP_TRY(hipMemcpyAsync(staging + (size_t)s * vn * row_bytes, (const char*)h_ptrs[s] + (size_t)v0 * row_bytes,
                                            (size_t)vn * row_bytes, hipMemcpyHostToDevice, ctx->stream));
                 else
-                    HIP_TRY(hipMemcpy2DAsync((char*)ctx->staging + (size_t)s * vn * row_bytes, row_bytes,
+                    HIP_TRY(hipMemcpy2DAsync(staging + (size_t)s * vn * row_bytes, row_bytes,
                                              (const char*)h_ptrs[s] + (size_t)v0 * row_stride_bytes, row_stride_bytes, row_bytes, vn,
                                              hipMemcpyHostToDevice, ctx->stream));
             }
         }
-        rc = pack_chunk<SrcT>(vol, (const SrcT*)ctx->staging, v0, vn, image_major, scale);
+        rc = pack_chunk<SrcT>(vol, (const SrcT*)staging, v0, vn, image_major, scale);
         if (rc)
             return rc;
         // the staging buffer is reused by the next chunk
@@ -551,6 +498,7 @@ static int upload_images_xf(rslf_volume* vol, const SrcT* const* h_imgs, size_t 
     int rc = ensure_staging(ctx, (size_t)chunk * epi_bytes);
     if (rc)
         return rc;
+    char* const staging = ctx->scratch.staging.as<char>();
     rc = minmax_begin(ctx);
     if (rc)
         return rc;
@@ -560,10 +508,10 @@ static int upload_images_xf(rslf_volume* vol, const SrcT* const* h_imgs, size_t 
             if (!h_imgs[i])
                 return fail(RSLF_ERR_INVALID_ARG, "h_imgs[%d] is NULL", i);
             if (row_stride_bytes == row_bytes)
-                HIP_TRY(hipMemcpyAsync((char*)ctx->staging + (size_t)i * vn * row_bytes, (const char*)h_imgs[i] + (size_t)v0 * row_bytes,
+                HIP_TRY(hipMemcpyAsync(staging + (size_t)i * vn * row_bytes, (const char*)h_imgs[i] + (size_t)v0 * row_bytes,
                                        (size_t)vn * row_bytes, hipMemcpyHostToDevice, ctx->stream));
             else
-                HIP_TRY(hipMemcpy2DAsync((char*)ctx->staging + (size_t)i * vn * row_bytes, row_bytes,
+                HIP_TRY(hipMemcpy2DAsync(staging + (size_t)i * vn * row_bytes, row_bytes,
                                          (const char*)h_imgs[i] + (size_t)v0 * row_stride_bytes, row_stride_bytes, row_bytes, vn,
                                          hipMemcpyHostToDevice, ctx->stream));
         }
@@ -571,11 +519,12 @@ static int upload_images_xf(rslf_volume* vol, const SrcT* const* h_imgs, size_t 
         rc = ensure_partial(ctx, rows);
         if (rc)
             return rc;
-        hipLaunchKernelGGL((k0_pack_images_xf<SrcT>), dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const SrcT*)ctx->staging,
+        float* const partial = ctx->scratch.partial.as<float>();
+        hipLaunchKernelGGL((k0_pack_images_xf<SrcT>), dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const SrcT*)staging,
                            vol->base, v0, vn, n_imgs, cols, vol->S, vol->U, vol->C, vol->pitch, scale, transpose, rotate_180,
-                           ctx->partial);
+                           partial);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k0_minmax_final, dim3(1), dim3(256), 0, ctx->stream, ctx->partial, (int)rows, ctx->minmax);
+        hipLaunchKernelGGL(k0_minmax_final, dim3(1), dim3(256), 0, ctx->stream, partial, (int)rows, ctx->scratch.minmax.as<float>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));   // the staging buffer is reused by the next chunk
     }

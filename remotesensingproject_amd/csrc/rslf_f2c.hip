@@ -31,7 +31,7 @@ extern "C" int rslf_downsample_epis_f32(rslf_ctx* ctx, const float* d_in_vsuc, i
     if (V2 < 1 || U2 < 1)
         return fail(RSLF_ERR_INVALID_ARG, "level too small to halve");
     void* tmp_p = nullptr;
-    int rc = helper_scratch(ctx, 0, (size_t)V * S * U * C * sizeof(float), &tmp_p);
+    int rc = helper_scratch(ctx, kSharedLevel, (size_t)V * S * U * C * sizeof(float), &tmp_p);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
@@ -57,7 +57,7 @@ extern "C" int rslf_downsample_epis_u8(rslf_ctx* ctx, const float* d_in_vsuc, in
     if (V2 < 1 || U2 < 1)
         return fail(RSLF_ERR_INVALID_ARG, "level too small to halve");
     void* tmp_p = nullptr;
-    int rc = helper_scratch(ctx, 0, (size_t)V * S * U * C * sizeof(int), &tmp_p);
+    int rc = helper_scratch(ctx, kSharedLevel, (size_t)V * S * U * C * sizeof(int), &tmp_p);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
@@ -83,7 +83,7 @@ extern "C" int rslf_downsample_epis_u16(rslf_ctx* ctx, const float* d_in_vsuc, i
     if (V2 < 1 || U2 < 1)
         return fail(RSLF_ERR_INVALID_ARG, "level too small to halve");
     void* tmp_p = nullptr;
-    int rc = helper_scratch(ctx, 0, (size_t)V * S * U * C * sizeof(float), &tmp_p);
+    int rc = helper_scratch(ctx, kSharedLevel, (size_t)V * S * U * C * sizeof(float), &tmp_p);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
@@ -104,12 +104,10 @@ extern "C" int rslf_device_max_f32(rslf_ctx* ctx, const float* d_values, size_t 
     if (!ctx || !d_values || !h_max || n == 0)
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int blocks = (int)std::min<size_t>((n + 255) / 256, 2048);
-    void* part_p = nullptr;
-    int rc = helper_scratch(ctx, 1, (size_t)2048 * sizeof(float), &part_p);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(k5_max_partial, dim3(blocks), dim3(256), 0, ctx->stream, d_values, (long long)n, (float*)part_p);
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, Scratch::kMaxPartials);
+    HIP_TRY(hip_err(ctx->scratch.max_partial.reserve(Scratch::kMaxPartials * sizeof(float))));   // 8 KiB of its own
+    float* const part_p = ctx->scratch.max_partial.as<float>();
+    hipLaunchKernelGGL(k5_max_partial, dim3(blocks), dim3(256), 0, ctx->stream, d_values, (long long)n, part_p);
     HIP_TRY(hipGetLastError());
     std::vector<float> h(blocks);
     HIP_TRY(hipMemcpyAsync(h.data(), part_p, (size_t)blocks * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -131,9 +129,9 @@ extern "C" int rslf_f2c_tighten_bounds(rslf_ctx* ctx, const float* d_depth_up_sv
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n_up = (size_t)S * V_up * U_up;
     void *left_p = nullptr, *right_p = nullptr;
-    int rc = helper_scratch(ctx, 2, n_up * sizeof(int), &left_p);
+    int rc = helper_scratch(ctx, kSharedLeft, n_up * sizeof(int), &left_p);
     if (!rc)
-        rc = helper_scratch(ctx, 3, n_up * sizeof(int), &right_p);
+        rc = helper_scratch(ctx, kSharedRight, n_up * sizeof(int), &right_p);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
@@ -158,13 +156,13 @@ extern "C" int rslf_f2c_fuse(rslf_ctx* ctx, const float* const* d_disp, const ui
     const size_t n0 = (size_t)S * Vp[0] * Up[0];
     // two ping-pong buffers at the finest size hold the running map / mask of every step
     void *mapA = nullptr, *mapB = nullptr, *mskA = nullptr, *mskB = nullptr;
-    int rc = helper_scratch(ctx, 0, n0 * sizeof(float), &mapA);
+    int rc = helper_scratch(ctx, kSharedLevel, n0 * sizeof(float), &mapA);
     if (!rc)
-        rc = helper_scratch(ctx, 2, n0 * sizeof(float), &mapB);
+        rc = helper_scratch(ctx, kSharedLeft, n0 * sizeof(float), &mapB);
     if (!rc)
-        rc = helper_scratch(ctx, 1, std::max<size_t>(n0, 2048 * sizeof(float)), &mskA);
+        rc = helper_scratch(ctx, kSharedTable, n0, &mskA);
     if (!rc)
-        rc = helper_scratch(ctx, 3, n0, &mskB);
+        rc = helper_scratch(ctx, kSharedRight, n0, &mskB);
     if (rc)
         return rc;
     float* map_down = (float*)mapA;
@@ -229,7 +227,7 @@ static int f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int 
     void* dst = d_raw;
     if (e != Elem::F32) {
         HIP_TRY(stage.alloc((size_t)V * S * row_bytes));
-        dst = stage.p;
+        dst = stage.get();
     }
     for (int v = 0; v < V; v++) {
         if (row_stride_bytes == row_bytes)   // dense rows: one run of bytes per EPI (upload_host)
@@ -240,9 +238,9 @@ static int f2c_upload_raw(rslf_ctx* ctx, Elem e, const void* const* h_epis, int 
     }
     const size_t n = (size_t)V * S * U * C;
     if (e == Elem::U8)
-        hipLaunchKernelGGL(k_to_f32<uint8_t>, dim3(stream_blocks(n)), dim3(256), 0, st, (const uint8_t*)stage.p, d_raw, (long long)n);
+        hipLaunchKernelGGL(k_to_f32<uint8_t>, dim3(stream_blocks(n)), dim3(256), 0, st, stage.as<const uint8_t>(), d_raw, (long long)n);
     else if (e == Elem::U16)
-        hipLaunchKernelGGL(k_to_f32<uint16_t>, dim3(stream_blocks(n)), dim3(256), 0, st, (const uint16_t*)stage.p, d_raw, (long long)n);
+        hipLaunchKernelGGL(k_to_f32<uint16_t>, dim3(stream_blocks(n)), dim3(256), 0, st, stage.as<const uint16_t>(), d_raw, (long long)n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));   // (the staging buffer is freed on return)
     return RSLF_OK;
@@ -309,7 +307,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         return fail(RSLF_ERR_INVALID_ARG, "levels out: capacity %d < pyramid depth %d", levels_out->capacity, P);
     DevBuf raw;   // the raw (un-normalised) values of the level at hand, [V][S][U][C]
     HIP_TRY(raw.alloc((size_t)V * S * U * C * sizeof(float)));
-    rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, (float*)raw.p);
+    rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, raw.as<float>());
     if (rc)
         return rc;
 
@@ -326,13 +324,13 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         lv.params = *p;
         lv.params.slope_factor = (float)((0.0 + lv.U) / U);              // f2c.hpp:139
         const size_t n = (size_t)S * lv.V * lv.U;
-        rc = f2c_level_scale(ctx, elem, (const float*)raw.p, n * C, epi_scale_factor, &lv.scale);
+        rc = f2c_level_scale(ctx, elem, raw.as<const float>(), n * C, epi_scale_factor, &lv.scale);
         if (rc)
             return rc;
         DevBuf next;                                                       // f2c.hpp:145-147: the RAW EPIs go down
         if (l + 1 < P) {
             HIP_TRY(next.alloc((size_t)dims[l + 1].V * S * dims[l + 1].U * C * sizeof(float)));
-            rc = f2c_downsample(ctx, elem, (const float*)raw.p, lv.V, S, lv.U, C, (float*)next.p);
+            rc = f2c_downsample(ctx, elem, raw.as<const float>(), lv.V, S, lv.U, C, next.as<float>());
             if (rc)
                 return rc;
         }
@@ -345,22 +343,22 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         if (l > 0) {
             HIP_TRY(dmin.alloc(n * 4));
             HIP_TRY(dmax.alloc(n * 4));
-            rc = f2c_fill_f32(st, (float*)dmin.p, n, d_min);
+            rc = f2c_fill_f32(st, dmin.as<float>(), n, d_min);
             if (!rc)
-                rc = f2c_fill_f32(st, (float*)dmax.p, n, d_max);
+                rc = f2c_fill_f32(st, dmax.as<float>(), n, d_max);
             if (!rc)
-                rc = rslf_f2c_tighten_bounds(ctx, (const float*)depth[l - 1].p, (const uint8_t*)valid[l - 1].p, S, dims[l - 1].V,
-                                             dims[l - 1].U, (float*)dmin.p, (float*)dmax.p, lv.V, lv.U);
+                rc = rslf_f2c_tighten_bounds(ctx, depth[l - 1].as<const float>(), valid[l - 1].as<const uint8_t>(), S, dims[l - 1].V,
+                                             dims[l - 1].U, dmin.as<float>(), dmax.as<float>(), lv.V, lv.U);
             if (rc)
                 return rc;
         }
-        lv.raw_vsuc = (const float*)raw.p;
-        lv.dmin_svu = (const float*)dmin.p;
-        lv.dmax_svu = (const float*)dmax.p;
-        lv.Ce_svu = (float*)Ce.p;
-        lv.depth_svu = (float*)depth[l].p;
+        lv.raw_vsuc = raw.as<const float>();
+        lv.dmin_svu = dmin.as<const float>();
+        lv.dmax_svu = dmax.as<const float>();
+        lv.Ce_svu = Ce.as<float>();
+        lv.depth_svu = depth[l].as<float>();
         lv.line_mode = line_mode;
-        lv.Cl_svu = (float*)Cl.p;
+        lv.Cl_svu = Cl.as<float>();
         rc = sweep(lv, &st1);
         if (rc)
             return rc;
@@ -369,13 +367,13 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         // fusion (:312): the last level accepts everything when asked to (f2c.hpp:157-158)
         switch (plan::f2c_validity(accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0, line_mode)) {
         case plan::kValidAll:
-            rc = f2c_valid_mask(st, (const float*)Ce.p, (uint8_t*)valid[l].p, n, -1.0f);
+            rc = f2c_valid_mask(st, Ce.as<const float>(), valid[l].as<uint8_t>(), n, -1.0f);
             break;
         case plan::kValidLineConf:
-            rc = f2c_valid_mask(st, (const float*)Cl.p, (uint8_t*)valid[l].p, n, p->line_score_threshold);
+            rc = f2c_valid_mask(st, Cl.as<const float>(), valid[l].as<uint8_t>(), n, p->line_score_threshold);
             break;
         case plan::kValidEdgeConf:
-            rc = f2c_valid_mask(st, (const float*)Ce.p, (uint8_t*)valid[l].p, n, p->edge_score_threshold);
+            rc = f2c_valid_mask(st, Ce.as<const float>(), valid[l].as<uint8_t>(), n, p->edge_score_threshold);
             break;
         }
         if (rc)
@@ -384,13 +382,13 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             const auto out = [&](void* const* hp, const void* d, size_t bytes) -> hipError_t {
                 return (hp && hp[l] && d) ? hipMemcpyAsync(hp[l], d, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
             };
-            HIP_TRY(out((void* const*)levels_out->h_depth_svu, depth[l].p, n * 4));
-            HIP_TRY(out((void* const*)levels_out->h_valid_svu, valid[l].p, n));
-            HIP_TRY(out((void* const*)levels_out->h_Cl_svu, Cl.p, n * 4));
-            HIP_TRY(out((void* const*)levels_out->h_Ce_svu, Ce.p, n * 4));
+            HIP_TRY(out((void* const*)levels_out->h_depth_svu, depth[l].get(), n * 4));
+            HIP_TRY(out((void* const*)levels_out->h_valid_svu, valid[l].get(), n));
+            HIP_TRY(out((void* const*)levels_out->h_Cl_svu, Cl.get(), n * 4));
+            HIP_TRY(out((void* const*)levels_out->h_Ce_svu, Ce.get(), n * 4));
             HIP_TRY(hipStreamSynchronize(st));
         }
-        std::swap(raw.p, next.p);   // `next` now frees this level's raw volume
+        std::swap(raw, next);   // `next` now frees this level's raw volume
     }
 
     // get_results(): rslf_fine_to_coarse.hpp:302-324
@@ -398,8 +396,8 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     std::vector<const uint8_t*> vp(P);
     std::vector<int> Vp(P), Up(P);
     for (int l = 0; l < P; l++) {
-        dp[l] = (const float*)depth[l].p;
-        vp[l] = (const uint8_t*)valid[l].p;
+        dp[l] = depth[l].as<const float>();
+        vp[l] = valid[l].as<const uint8_t>();
         Vp[l] = dims[l].V;
         Up[l] = dims[l].U;
     }
@@ -407,11 +405,11 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     DevBuf omap, ovalid;
     HIP_TRY(omap.alloc(n0 * 4));
     HIP_TRY(ovalid.alloc(n0));
-    rc = rslf_f2c_fuse(ctx, dp.data(), vp.data(), Vp.data(), Up.data(), P, S, (float*)omap.p, (uint8_t*)ovalid.p);
+    rc = rslf_f2c_fuse(ctx, dp.data(), vp.data(), Vp.data(), Up.data(), P, S, omap.as<float>(), ovalid.as<uint8_t>());
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.p, n0 * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_out_valid_svu, ovalid.p, n0, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.get(), n0 * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_out_valid_svu, ovalid.get(), n0, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n_levels)
         *n_levels = P;
@@ -441,8 +439,8 @@ static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* 
         if (!rc)
             rc = rslf_volume_pack_device_f32(vol, lv.raw_vsuc, lv.scale, nullptr);
         if (!rc)
-            rc = depth2d_run_lc(ctx, vol, lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, (uint8_t*)mask.p,
-                                (float*)Cd.p, lv.depth_svu, (float*)rbar.p, nullptr, level_stats, lv.line_mode, lv.Cl_svu);
+            rc = depth2d_run_lc(ctx, vol, lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, mask.as<uint8_t>(),
+                                Cd.as<float>(), lv.depth_svu, rbar.as<float>(), nullptr, level_stats, lv.line_mode, lv.Cl_svu);
         rslf_volume_destroy(vol);
         return rc;
     };

@@ -11,6 +11,7 @@
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
+//   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
 #pragma once
 
 #include "../../include/rslf_hip.h"
@@ -30,6 +31,7 @@
 
 #include "rslf_device.hpp"
 #include "rslf_plan.hpp"
+#include "rslf_scratch.hpp"
 
 // ---- errors ---------------------------------------------------------------
 
@@ -154,24 +156,102 @@ int guarded_status(F f, std::string* err)
 // ---- objects --------------------------------------------------------------
 
 namespace rslf {
-struct Partial;   // k2_scan.hpp: one lane's merged result over one group's hypotheses (32 bytes)
-}
+
+// The allocators of GrowBuf (rslf_scratch.hpp): device memory and pinned host memory.  Their frees wait for the device's
+// outstanding work; no other code of the library frees (a volume's slab apart, rslf_volume_destroy).
+struct DeviceAlloc {
+    static int alloc(size_t bytes, void** out) { return (int)hipMalloc(out, bytes); }
+    static int free(void* p) { return (int)hipFree(p); }
+};
+struct PinnedAlloc {
+    static int alloc(size_t bytes, void** out) { return (int)hipHostMalloc(out, bytes, hipHostMallocDefault); }
+    static int free(void* p) { return (int)hipHostFree(p); }
+};
+using DeviceBuf = GrowBuf<DeviceAlloc>;
+using PinnedBuf = GrowBuf<PinnedAlloc>;
+
+// The one error convention of a regrow: HIP_TRY(hip_err(buf.reserve(bytes))) -- a failed free or allocation is RSLF_ERR_HIP
+// with HIP_TRY's message.
+inline hipError_t hip_err(Reserved r) { return (hipError_t)r.err; }
+
+// The buffers that several entry points share (Scratch::shared, handed out by helper_scratch): the once-per-level helpers of
+// fine-to-coarse and the renderers, whose largest users are as large as a pyramid level -- sharing them is what keeps a
+// context's footprint at one set.  Sharing is safe because every entry point queues all its work on the context's stream,
+// in order, and none keeps a pointer to a shared buffer past its return: the next user's launches run after the previous
+// user's.  (A buffer that IS held across calls -- the line-confidence columns of an open sweep -- is a member of its own.)
+enum SharedBuf {
+    kSharedLevel = 0,    // rslf_downsample_epis_*: the row pass over a whole raw level [V][S][U][C]; rslf_f2c_fuse: running map A
+    kSharedTable,        // rslf_f2c_fuse: running mask A; the renderers: colour table and the planes' (a, b) (upload_table)
+    kSharedLeft,         // rslf_f2c_tighten_bounds: nearest valid pixel to the left, [S][V][U] ints; rslf_f2c_fuse: running map B; the renderers' fit: its state
+    kSharedRight,        // rslf_f2c_tighten_bounds: ... to the right; rslf_f2c_fuse: running mask B; the fit: its slab
+    kSharedStagePlanes,  // the renderers' host-pointer forms: the planes / the depth rows on the device,
+    kSharedStageMask,    // ... their validity / mask bytes,
+    kSharedStageOut,     // ... and the pictures before they go back
+    kSharedBufs
+};
+
+// Every piece of device memory a context owns.  Each buffer has a capacity of its own (a capacity shared by buffers of
+// different shapes once let a later volume overrun the smaller one: tools/fuzz_sweep.py), grows on demand -- never inside a
+// timed launch sequence after the first call -- and is freed by its destructor.
+struct Scratch {
+    DeviceBuf total;        // 2 x u64, made with the context: [0] scanned pixels, [1] the packed list's length (packed_len)
+    DeviceBuf minmax;       // float [2], made with the context: a volume's value range while it is packed
+    DeviceBuf list;         // int [V*U]: the pixels a scan visits, per scanline or as one packed list
+    DeviceBuf depth_tmp;    // float [V*U]: the raw disparities of a pile step; a byte plane for the opening (morph_tmp)
+    DeviceBuf count;        // int [V]: pixels per scanline
+    DeviceBuf rowbase;      // int [V]: where each scanline's pixels start in the packed list
+    DeviceBuf partial;      // float [rows][2]: min / max partials of the pack kernels
+    DeviceBuf staging;      // host uploads pass through here in chunks
+    DeviceBuf scan_partial; // rslf::Partial [tile][group][64]: records of grouped scan launches
+    DeviceBuf scan_ticket;  // int [tile] of the same launches: which group merges the tile (zero between launches)
+    DeviceBuf max_partial;  // float [kMaxPartials]: block maxima of rslf_device_max_f32
+    // 2-D sweep
+    DeviceBuf winner;       // int [S][V][U]: the claims (0x7F7F7F7F between visits)
+    DeviceBuf sweep_mask;   // u8 [S][V][U]: the running masks, unless the caller gives the plane
+    DeviceBuf dirty;        // u8 [S][V][ceil(U/256)]: segments of the winner rows that hold a claim (all 0 between visits)
+    DeviceBuf remain;       // int [S][V][ceil(U/256)]: pixels left in the running mask per segment (lets the claims skip views)
+    DeviceBuf filtered;     // float [V][U]: median of the visited view, the propagation's source
+    DeviceBuf lc_columns;   // float [V][S][U]: K(r - rbar) columns of a sweep with line confidence, kept from visit to visit
+    DeviceBuf lc_argmax;    // int32 [V][U]: arg-max indices of the visit's scan, -1 where it accepted nothing
+    DeviceBuf shared[kSharedBufs];
+
+    static constexpr size_t kMaxPartials = 2048;
+    unsigned long long* pixel_total() const { return total.as<unsigned long long>(); }
+    int* packed_len() const { return reinterpret_cast<int*>(pixel_total() + 1); }   // an int in the second u64 of `total`
+    uint8_t* morph_tmp() const { return depth_tmp.as<uint8_t>(); }                   // V*U floats: room for a byte plane
+};
+
+// An open 2-D sweep (rslf_sweep_begin .. rslf_sweep_end).  The defaults are "no sweep open": sweep_close assigns them.
+struct SweepState {
+    bool open = false;          // between rslf_sweep_begin and rslf_sweep_end
+    bool keep_total = false;    // the sweep sums the scanned pixels of all its visits
+    bool first = true;          // the next visit is the sweep's first (dense) one; true outside a sweep: scan_defaults times every scan then
+    bool scanned = false;       // a visit of the open sweep has scanned (rslf_sweep_line_confidence comes before)
+    bool listed = false;        // the last apply pass listed the next visit's pixels (packed list and length in place); else k34_median_claim left the list's length at 0
+    int expect = -1;            // the view the sweep visits next (core.hpp:981-990), -1 once all are done
+    uint8_t* mask_run = nullptr;   // the running masks [S][V][U]
+    // line confidence (rslf_sweep_line_confidence; k7_line_conf.hpp): state of ONE sweep.  The K columns and the visit's
+    // arg-max plane are Scratch::lc_columns / lc_argmax, sized when the mode is set, never inside a visit.
+    int lc_mode = RSLF_LINE_CONF_OFF;
+    float* lc_Cl_svu = nullptr;        // the caller's [S][V][U] plane
+    float* lc_K_vsu = nullptr;         // (core.hpp:975-979)
+    int32_t* lc_idx_vu = nullptr;
+    // what rslf_sweep_visit_scan was given and K7 needs to re-run a winning hypothesis (rslf_sweep_visit_finish is not told)
+    const float* lc_Ce_svu = nullptr;
+    const float* lc_dmin_vu = nullptr;
+    const float* lc_dmax_vu = nullptr;
+    float lc_dmin = 0.0f, lc_dmax = 0.0f;
+    int lc_dim_d = 0;
+    ScanConsts lc_consts = {};
+};
+
+}  // namespace rslf
 
 struct rslf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    // scratch, grown on demand (never inside a timed launch sequence after the first call)
-    int* list = nullptr;
-    int* count = nullptr;
-    float* depth_tmp = nullptr;
-    size_t plane_cap = 0;   // pixels list/depth_tmp can hold
-    int count_cap = 0;
-    unsigned long long* total = nullptr;   // device counter
-    float* partial = nullptr;              // pack min/max partials
-    size_t partial_cap = 0;
-    float* minmax = nullptr;               // device [2]
-    void* staging = nullptr;
-    size_t staging_cap = 0;
+    rslf::Scratch scratch;
+    rslf::SweepState sweep;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
     // "time_all" (rslf_ctx_set_debug): every scan launch sequence is bracketed by its own pair of events from this pool --
@@ -183,7 +263,6 @@ struct rslf_ctx {
     int last_spad = 0;   // register-scan slot count of the last K2 launch, 0 = none
     int last_kernel = 0; // RSLF_SCAN_* of the last K2 launch
     int num_cus = 0;           // compute units of the device (how many workgroups a launch needs to fill it)
-    bool keep_total = false;   // the 2-D sweep sums the scanned pixels of all its visits
     // test / tuning hooks (rslf_ctx_set_debug), per context: 0 / -1 = automatic
     int force_scan = 0;        // 1 generic kernel, 2 streaming kernel wherever it can run (never the on-chip one)
     int force_groups = 0;      // hypothesis groups per tile
@@ -194,46 +273,6 @@ struct rslf_ctx {
     size_t stream_lds_bytes = rslf::plan::kStreamLdsBytes;   // dynamic LDS of one streaming workgroup
     int row_split = 1;         // packed launches of stream-class volumes: rows with many pixels as row tiles of the list (0: off; A/B and tests)
     int claim_skip = 1;        // 2-D sweep: the claims skip views with nothing left to paint within reach (0: off, A/B and tests)
-    rslf::Partial* scan_partial = nullptr;   // [tile][group][64] records of grouped scan launches
-    size_t partial_rec_cap = 0;
-    int* scan_ticket = nullptr;        // [tile] of the same launches: which group merges the tile (zero between launches)
-    size_t ticket_cap = 0;
-    int sweep_expect = -1;             // the view the sweep visits next (core.hpp:981-990), -1 once all are done
-    bool sweep_open = false;           // between rslf_sweep_begin and rslf_sweep_end
-    bool sweep_first = true;           // the next visit is the sweep's first (dense) one
-    bool sweep_scanned = false;        // a visit of the open sweep has scanned (rslf_sweep_line_confidence comes before)
-    bool sweep_listed = false;         // the last apply pass listed the next visit's pixels (packed list and length in place);
-                                       // else k34_median_claim left the list's length at 0
-    uint8_t* sweep_mask_run = nullptr; // the running masks [S][V][U] of the open sweep
-    // 2-D sweep scratch
-    int* winner = nullptr;        // [S][V][U]
-    uint8_t* dirty = nullptr;     // [S][V][ceil(U/256)]: segments of the winner rows that hold a claim (all 0 between visits)
-    int* remain = nullptr;        // [S][V][ceil(U/256)]: pixels left in the running mask per segment (lets the claims skip views)
-    size_t dirty_cap = 0;
-    uint8_t* sweep_mask = nullptr;
-    float* filtered = nullptr;    // [V][U] median of the visited view, the propagation's source
-    size_t sweep_cap = 0;         // entries winner / sweep_mask can hold (S*V*U)
-    size_t sweep_plane_cap = 0;   // floats `filtered` can hold (V*U)
-    // line confidence of the open sweep (rslf_sweep_line_confidence; k7_line_conf.hpp).  The K columns and the visit's arg-max
-    // plane are helper slots kLineConfColumns / kLineConfArgmax, sized when the mode is set, never inside a visit.
-    int lc_mode = 0;                   // RSLF_LINE_CONF_*; rslf_sweep_end puts it back to 0
-    float* lc_Cl_svu = nullptr;        // the caller's [S][V][U] plane
-    float* lc_K_vsu = nullptr;         // [V][S][U] K(r - rbar) columns, kept from visit to visit (core.hpp:975-979)
-    int32_t* lc_idx_vu = nullptr;      // [V][U] arg-max indices of the visit's scan, -1 where it accepted nothing
-    // what rslf_sweep_visit_scan was given and K7 needs to re-run a winning hypothesis (rslf_sweep_visit_finish is not told)
-    const float* lc_Ce_svu = nullptr;
-    const float* lc_dmin_vu = nullptr;
-    const float* lc_dmax_vu = nullptr;
-    float lc_dmin = 0.0f, lc_dmax = 0.0f;
-    int lc_dim_d = 0;
-    rslf::ScanConsts lc_consts = {};
-    // grow-only scratch of the once-per-level helpers (pyramid, tightening, fusion) and of the renderers (slots 4 .. 6: the
-    // staging of their host-pointer forms): reused across calls, so these helpers neither allocate nor free -- and so
-    // never force a device-wide synchronisation
-    static constexpr int kHelperSlots = 9;
-    static constexpr int kLineConfColumns = 7, kLineConfArgmax = 8;   // slots 7, 8: the line confidence of a sweep
-    void* helper[kHelperSlots] = {};
-    size_t helper_cap[kHelperSlots] = {};
 };
 
 struct rslf_volume {
@@ -253,12 +292,9 @@ struct rslf_multi {
         hipEvent_t done[2] = {nullptr, nullptr};
         rslf_volume* vol[2] = {nullptr, nullptr};
         int vol_rows[2] = {0, 0}, vol_S = 0, vol_U = 0, vol_C = 0;
-        char* planes[2] = {nullptr, nullptr};
-        size_t planes_cap = 0;
-        char* pin[2] = {nullptr, nullptr};   // pinned host staging for EPIs scattered over the heap (Vec<Mat>)
-        size_t pin_cap = 0;
-        char* arena = nullptr;               // the sweep forms' planes, kept from call to call (and from level to level)
-        size_t arena_cap = 0;
+        rslf::DeviceBuf planes[2];           // result planes of the chunk being computed and of the one being collected
+        rslf::PinnedBuf pin[2];              // pinned host staging for EPIs scattered over the heap (Vec<Mat>)
+        rslf::DeviceBuf arena;               // the sweep forms' planes, kept from call to call (and from level to level)
     };
     std::vector<Dev> devs;
     int chunk_rows = 0;   // 0 = automatic
@@ -288,28 +324,19 @@ inline float scale_of(float epi_scale_factor)
     return (float)(1.0 / (double)epi_scale_factor);   // dc.hpp:474 through cvtScale's float scale
 }
 
-// scoped device scratch for the once-per-call helpers
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    void release()
-    {
-        (void)hipFree(p);
-        p = nullptr;
-    }
+// scoped device memory of the once-per-call helpers: the same owning type, allocated once.  A 0-byte request becomes a
+// 1-byte one, so an empty plane still has an address.
+struct DevBuf : DeviceBuf {
+    hipError_t alloc(size_t bytes) { return hip_err(reserve(bytes ? bytes : 1)); }
 };
 
 // rslf_core.hip
 int check_params(const rslf_params* p);
 ScanConsts make_scan_consts(const rslf_params* p);
 int ensure_plane_scratch(rslf_ctx* ctx, int V, int U);
-int ensure_group_scratch(rslf_ctx* ctx, size_t recs, size_t tiles);
+int ensure_group_scratch(rslf_ctx* ctx, size_t recs, size_t tiles, bool* tickets_fresh = nullptr);
 int ensure_staging(rslf_ctx* ctx, size_t bytes);
-int helper_scratch(rslf_ctx* ctx, int slot, size_t bytes, void** out);
+int helper_scratch(rslf_ctx* ctx, SharedBuf which, size_t bytes, void** out);
 // The element type of a host light field (the cv::Mat depths the reference's constructors take, dc.hpp:269-288,
 // :442-475, :671-705): CV_32F, CV_8U, CV_16U.  Chosen once at the C-ABI entry point; everything below it dispatches on it.
 enum class Elem { F32, U8, U16 };
@@ -352,6 +379,7 @@ int depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu
                    const rslf_params* p, uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats,
                    const ScanInputs& in);
 void fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_stats* stats);
+int read_stats(rslf_ctx* ctx, int dim_d, rslf_stats* stats);
 int scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf_params* p, const int* rows, int n_rows);
 int sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const ScanInputs& sparse);
 

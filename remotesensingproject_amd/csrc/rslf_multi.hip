@@ -26,10 +26,6 @@ void rslf::multi_free_dev(rslf_multi::Dev& d)
     for (int i = 0; i < 2; i++) {
         if (d.vol[i])
             (void)rslf_volume_destroy(d.vol[i]);
-        (void)hipFree(d.planes[i]);
-        (void)hipHostFree(d.pin[i]);
-        if (i == 0)
-            (void)hipFree(d.arena);
         if (d.done[i])
             (void)hipEventDestroy(d.done[i]);
     }
@@ -40,7 +36,7 @@ void rslf::multi_free_dev(rslf_multi::Dev& d)
     if (d.s_down)
         (void)hipStreamDestroy(d.s_down);
     (void)rslf_ctx_destroy(d.ctx);
-    d = rslf_multi::Dev();
+    d = rslf_multi::Dev();   // (planes, pinned staging and the arena are freed here, by their destructors)
 }
 
 extern "C" int rslf_multi_destroy(rslf_multi* m) RSLF_API_TRY
@@ -258,16 +254,8 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
     // rewritten by the next chunk's kernels, which are already queued when this chunk is collected)
     const plan::PlaneLayout lay = plan::plane_layout(n_max, j.C, max_rows);
     const size_t plane_bytes = lay.counts, bytes = lay.bytes;
-    if (bytes > d.planes_cap) {
-        for (int k = 0; k < 2; k++) {
-            (void)hipFree(d.planes[k]);
-            d.planes[k] = nullptr;
-        }
-        d.planes_cap = 0;
-        for (int k = 0; k < 2; k++)
-            MW_HIP(hipMalloc(&d.planes[k], bytes));
-        d.planes_cap = bytes;
-    }
+    for (int k = 0; k < 2; k++)
+        MW_HIP(hip_err(d.planes[k].reserve(bytes)));
     std::vector<int> counts((size_t)max_rows);
     // The scan's scratch -- pixel lists, and the records of grouped launches, whose count differs from chunk to chunk (a
     // short first chunk takes more hypothesis groups than the large ones) -- sized ONCE for every chunk of the plan before
@@ -283,19 +271,8 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
     }
     // pinned staging for scattered EPIs
     const int pin_threads = std::max(1, std::min(8, (int)std::thread::hardware_concurrency() / 2));
-    {
-        const size_t need = (size_t)max_rows * in_epi_bytes;
-        if (scattered && need > d.pin_cap) {
-            for (int k = 0; k < 2; k++) {
-                (void)hipHostFree(d.pin[k]);
-                d.pin[k] = nullptr;
-            }
-            d.pin_cap = 0;
-            for (int k = 0; k < 2; k++)
-                MW_HIP(hipHostMalloc((void**)&d.pin[k], need, hipHostMallocDefault));
-            d.pin_cap = need;
-        }
-    }
+    for (int k = 0; scattered && k < 2; k++)
+        MW_HIP(hip_err(d.pin[k].reserve((size_t)max_rows * in_epi_bytes)));
 
     // a volume object of the chunk's height over the (larger or equal) allocation: rows beyond are simply unused
     auto upload = [&](int k) -> int {
@@ -318,8 +295,8 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
         size_t src_stride = j.row_stride_bytes;
         // (the pinned buffer is sized from the scattered-ness of the device's OWN rows; a chunk's halo rows can add breaks
         // of their own, so the buffer must also be seen to hold this chunk -- else the direct per-run copies below)
-        if (plan::use_pinned_gather(runs, rows, epi_bytes, d.pin[k & 1] ? d.pin_cap : 0)) {
-            char* pin = d.pin[k & 1];
+        if (plan::use_pinned_gather(runs, rows, epi_bytes, d.pin[k & 1].capacity())) {
+            char* pin = d.pin[k & 1].as<char>();
             const int nt = std::max(1, std::min(rows, pin_threads));
             for (int i = 0; i < rows; i++)
                 if (j.h_epis[c.lo + i] == nullptr)
@@ -353,7 +330,7 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
     auto compute = [&](int k) -> int {
         const Chunk& c = chunks[k];
         const size_t n = (size_t)(c.hi - c.lo) * j.U;
-        const PlanePtrs q = carve(d.planes[k & 1], n, j.C);
+        const PlanePtrs q = carve(d.planes[k & 1].as<char>(), n, j.C);
         ctx->stream = d.s_comp;
         int rc = rslf_depth1d_pile_run(ctx, d.vol[k & 1], j.dmin, j.dmax, j.dim_d, j.s_hat, j.p, q.Ce, q.mask, q.Cd, q.depth, q.rbar,
                                        q.idx, q.score, q.raw, nullptr);
@@ -361,7 +338,7 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
             return rc;
         *kernel = ctx->last_kernel;
         *spad = ctx->last_spad;
-        hipError_t e = hipMemcpyAsync(d.planes[k & 1] + plane_bytes, ctx->count, (size_t)(c.hi - c.lo) * sizeof(int),
+        hipError_t e = hipMemcpyAsync(d.planes[k & 1].as<char>() + plane_bytes, ctx->scratch.count.get(), (size_t)(c.hi - c.lo) * sizeof(int),
                                       hipMemcpyDeviceToDevice, d.s_comp);
         if (e == hipSuccess)
             e = hipEventRecord(d.done[k & 1], d.s_comp);
@@ -371,7 +348,7 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
         const Chunk& c = chunks[k];
         const int rows = c.hi - c.lo;
         const size_t n = (size_t)rows * j.U;
-        const PlanePtrs q = carve(d.planes[k & 1], n, j.C);
+        const PlanePtrs q = carve(d.planes[k & 1].as<char>(), n, j.C);
         const size_t off = (size_t)(c.a - c.lo) * j.U, cnt = (size_t)(c.b - c.a) * j.U, dst = (size_t)c.a * j.U;
         hipError_t e = hipStreamWaitEvent(d.s_down, d.done[k & 1], 0);
         auto pull = [&](void* h, const void* dv, size_t esz, size_t mult) {
@@ -394,7 +371,7 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
         pull(j.h_raw, q.raw, 4, 1);
         // pixels scanned on the owned rows: the per-scanline counts of the scan's pixel lists
         if (e == hipSuccess)
-            e = hipMemcpyAsync(counts.data(), d.planes[k & 1] + plane_bytes, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, d.s_down);
+            e = hipMemcpyAsync(counts.data(), d.planes[k & 1].as<char>() + plane_bytes, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, d.s_down);
         if (e == hipSuccess)
             e = hipStreamSynchronize(d.s_down);
         if (e != hipSuccess)

@@ -125,8 +125,8 @@ int multi_depth2d(rslf_multi* m, const void* const* h_epis, Elem elem, size_t ro
             const float* src = first->raw_vsuc + (size_t)d.lo * row_floats;
             if (ctx->device != dev0) {
                 S2_TRY(ensure_staging(ctx, (size_t)rows * row_floats * sizeof(float)));
-                S2_HIP(copy01(ctx->staging, ctx->device, src, dev0, (size_t)rows * row_floats * sizeof(float)));
-                src = (const float*)ctx->staging;
+                S2_HIP(copy01(ctx->scratch.staging.get(), ctx->device, src, dev0, (size_t)rows * row_floats * sizeof(float)));
+                src = ctx->scratch.staging.as<const float>();
             }
             S2_TRY(rslf_volume_pack_device_f32(d.vol, src, scale_arg, nullptr));
         } else {
@@ -136,14 +136,8 @@ int multi_depth2d(rslf_multi* m, const void* const* h_epis, Elem elem, size_t ro
             rslf_multi::Dev& md = m->devs[(size_t)i];
             const size_t nf = (n + 63) & ~(size_t)63;   // floats per plane, 256-byte aligned
             const size_t need = nf * sizeof(float) * (3 + (size_t)C + (ranges ? 2 : 0)) + 2 * nf;
-            if (need > md.arena_cap) {
-                (void)hipFree(md.arena);
-                md.arena = nullptr;
-                md.arena_cap = 0;
-                S2_HIP(hipMalloc(&md.arena, need));
-                md.arena_cap = need;
-            }
-            float* f = reinterpret_cast<float*>(md.arena);
+            S2_HIP(hip_err(md.arena.reserve(need)));
+            float* f = md.arena.as<float>();
             d.Ce = f, f += nf;
             d.Cd = f, f += nf;
             d.depth = f, f += nf;

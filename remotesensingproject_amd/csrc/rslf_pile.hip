@@ -47,7 +47,7 @@ extern "C" int rslf_edge_confidence_pile(rslf_ctx* ctx, const rslf_volume* vol, 
         if (rc)
             return rc;
         const MorphElement el = plan::structuring_element(p->edge_confidence_opening_type, p->edge_confidence_opening_size);
-        uint8_t* tmp = reinterpret_cast<uint8_t*>(ctx->depth_tmp);   // V*U floats: room for a byte plane
+        uint8_t* tmp = ctx->scratch.morph_tmp();
         hipLaunchKernelGGL(k1_morph_pass, grid, dim3(256), 0, ctx->stream, d_Ce_mask_vu, tmp, vol->V, vol->U, el, 0);   // erode
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k1_morph_pass, grid, dim3(256), 0, ctx->stream, tmp, d_Ce_mask_vu, vol->V, vol->U, el, 1);   // dilate
@@ -211,12 +211,12 @@ int rslf::scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf
     if (max_rows < 1)
         return RSLF_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t ticket_cap = ctx->ticket_cap;
+    bool tickets_fresh = false;
     int rc = ensure_plane_scratch(ctx, max_rows, U);
     if (rc == RSLF_OK && recs)
-        rc = ensure_group_scratch(ctx, recs, tickets);
+        rc = ensure_group_scratch(ctx, recs, tickets, &tickets_fresh);
     // fresh tickets are zeroed on the context's CURRENT stream; the caller's launches may go to another one
-    if (rc == RSLF_OK && ctx->ticket_cap != ticket_cap)
+    if (rc == RSLF_OK && tickets_fresh)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     return rc;
 }
@@ -239,11 +239,21 @@ void rslf::fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_sta
     stats->s_pad = ctx->last_spad;
 }
 
+// The stats of what the context's stream has been given so far: waits for it and reads the pixel total
+int rslf::read_stats(rslf_ctx* ctx, int dim_d, rslf_stats* stats)
+{
+    unsigned long long tot = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, ctx->scratch.pixel_total(), sizeof(tot), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    fill_stats(ctx, tot, dim_d, stats);
+    return RSLF_OK;
+}
+
 ScanInputs rslf::scan_defaults(const rslf_ctx* ctx)
 {
     ScanInputs in;
-    in.zero_total = !ctx->keep_total;                   // an open sweep sums its visits' pixels ...
-    in.timed = !ctx->sweep_open || ctx->sweep_first;    // ... and times its first visit only
+    in.zero_total = !ctx->sweep.keep_total;             // an open sweep sums its visits' pixels ...
+    in.timed = !ctx->sweep.open || ctx->sweep.first;    // ... and times its first visit only
     return in;
 }
 
@@ -277,8 +287,8 @@ static void apply_plan(ScanArgs& a, const plan::ScanPlan& p, const rslf_ctx* ctx
     a.stream_park = p.stream_park;
     a.stream_wave_floats = p.stream_wave_floats;
     // grouped launches leave one 32-byte record per (tile, group, lane) for the tile's last group to merge (k2_scan.hpp)
-    a.partial = p.groups > 1 ? ctx->scan_partial : nullptr;
-    a.ticket = p.groups > 1 ? ctx->scan_ticket : nullptr;
+    a.partial = p.groups > 1 ? ctx->scratch.scan_partial.as<Partial>() : nullptr;
+    a.ticket = p.groups > 1 ? ctx->scratch.scan_ticket.as<int>() : nullptr;
 }
 
 // One launch of the kernel the plan names: its template instantiation for the slot count / resident prefix / channels
@@ -367,30 +377,31 @@ int rslf::depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
 
     const size_t n = (size_t)vol->V * vol->U;
     hipStream_t st = ctx->stream;
+    const Scratch& sc = ctx->scratch;
     if (d_idx_vu)
         HIP_TRY(hipMemsetAsync(d_idx_vu, 0xFF, n * sizeof(int32_t), st));   // -1
     if (d_score_vu)
         HIP_TRY(hipMemsetAsync(d_score_vu, 0, n * sizeof(float), st));
     if (in.zero_total && in.lists == ScanInputs::kCompact)
-        HIP_TRY(hipMemsetAsync(ctx->total, 0, sizeof(unsigned long long), st));
-    int* packed_n = reinterpret_cast<int*>(ctx->total + 1);
+        HIP_TRY(hipMemsetAsync(sc.pixel_total(), 0, sizeof(unsigned long long), st));
+    int* packed_n = sc.packed_len();
     if (in.lists != ScanInputs::kCompact) {
         // nothing to compact
     } else if (sp.packed) {
         if (!in.packed_n_zero)
             HIP_TRY(hipMemsetAsync(packed_n, 0, sizeof(int), st));
-        hipLaunchKernelGGL(k_compact_mask_packed, dim3(vol->V), dim3(256), 0, st, d_Ce_mask_vu, d_mask_vu, vol->U, ctx->list,
-                           ctx->count, ctx->total, packed_n, ctx->count + ctx->count_cap);
+        hipLaunchKernelGGL(k_compact_mask_packed, dim3(vol->V), dim3(256), 0, st, d_Ce_mask_vu, d_mask_vu, vol->U, sc.list.as<int>(),
+                           sc.count.as<int>(), sc.pixel_total(), packed_n, sc.rowbase.as<int>());
     } else {
-        hipLaunchKernelGGL(k_compact_mask, dim3(vol->V), dim3(256), 0, st, d_Ce_mask_vu, d_mask_vu, vol->U, ctx->list,
-                           ctx->count, ctx->total);
+        hipLaunchKernelGGL(k_compact_mask, dim3(vol->V), dim3(256), 0, st, d_Ce_mask_vu, d_mask_vu, vol->U, sc.list.as<int>(),
+                           sc.count.as<int>(), sc.pixel_total());
     }
     HIP_TRY(hipGetLastError());
 
     ScanArgs a = {};
     a.vol = view_of(vol);
-    a.list = ctx->list;
-    a.count = ctx->count;
+    a.list = sc.list.as<int>();
+    a.count = sc.count.as<int>();
     a.dmin_vu = d_dmin_vu;
     a.dmax_vu = d_dmax_vu;
     a.dmin = dmin;
@@ -411,7 +422,7 @@ int rslf::depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
     ScanArgs ar = a;   // the row split's row tiles of the packed list
     apply_plan(a, sp, ctx);
     apply_plan(ar, spr, ctx);
-    ar.rowbase = ctx->count + ctx->count_cap;
+    ar.rowbase = sc.rowbase.as<int>();
     ctx->last_spad = sp.spad;
     ctx->last_kernel = sp.kind;
     HIP_TRY(hipGetLastError());   // anything an earlier enqueue left behind is not this launch's fault
@@ -457,14 +468,7 @@ int rslf::depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
             ctx->ev_used -= 2;
         return rc;
     }
-
-    if (stats) {
-        unsigned long long tot = 0;
-        HIP_TRY(hipMemcpyAsync(&tot, ctx->total, sizeof(tot), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        fill_stats(ctx, tot, dim_d, stats);
-    }
-    return RSLF_OK;
+    return stats ? read_stats(ctx, dim_d, stats) : RSLF_OK;
 }
 
 extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
@@ -527,7 +531,7 @@ static int depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_
     // the median reads the raw plane at mask pixels only, and every mask pixel has been written by the scan ...
     // With a caller's scan mask, mask pixels that are NOT scanned now keep the disparity the plane came in with
     // (a_best_depth_v_u is in/out, core.hpp:305), and the median reads them: the raw plane then starts as a copy.
-    float* raw = d_depth_raw_vu ? d_depth_raw_vu : ctx->depth_tmp;
+    float* raw = d_depth_raw_vu ? d_depth_raw_vu : ctx->scratch.depth_tmp.as<float>();
     if (d_mask_vu)
         HIP_TRY(hipMemcpyAsync(raw, d_depth_vu, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     else if (d_depth_raw_vu)
@@ -541,14 +545,7 @@ static int depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_
     rc = rslf_selective_median(ctx, vol, raw, d_depth_vu, s_hat, p->median_filter_size, d_Ce_mask_vu, p->median_filter_epsilon);
     if (rc)
         return rc;
-
-    if (stats) {
-        unsigned long long tot = 0;
-        HIP_TRY(hipMemcpyAsync(&tot, ctx->total, sizeof(tot), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        fill_stats(ctx, tot, dim_d, stats);
-    }
-    return RSLF_OK;
+    return stats ? read_stats(ctx, dim_d, stats) : RSLF_OK;
 }
 
 extern "C" int rslf_depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
@@ -591,19 +588,20 @@ extern "C" int rslf_depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, floa
         rc = ensure_plane_scratch(ctx, vol->V, vol->U);
         if (rc)
             return rc;
+        const Scratch& sc = ctx->scratch;
         EdgeConsts ec;
         ec.filter_size = p->edge_confidence_filter_size;
         ec.cut_shadows = p->cut_shadows;
         ec.shadow_level = p->shadow_level;
         ec.edge_thr = p->edge_score_threshold;
         if (in.zero_total)
-            HIP_TRY(hipMemsetAsync(ctx->total, 0, sizeof(unsigned long long), st));
+            HIP_TRY(hipMemsetAsync(sc.pixel_total(), 0, sizeof(unsigned long long), st));
         if (vol->C == 1)
             hipLaunchKernelGGL(k1_edge_confidence_compact<1>, dim3(vol->V), dim3(256), 0, st, view_of(vol), s_hat, ec, d_Ce_vu,
-                               d_Ce_mask_vu, ctx->list, ctx->count, ctx->total);
+                               d_Ce_mask_vu, sc.list.as<int>(), sc.count.as<int>(), sc.pixel_total());
         else
             hipLaunchKernelGGL(k1_edge_confidence_compact<3>, dim3(vol->V), dim3(256), 0, st, view_of(vol), s_hat, ec, d_Ce_vu,
-                               d_Ce_mask_vu, ctx->list, ctx->count, ctx->total);
+                               d_Ce_mask_vu, sc.list.as<int>(), sc.count.as<int>(), sc.pixel_total());
         HIP_TRY(hipGetLastError());
         in.lists = ScanInputs::kRowLists;
     } else {
@@ -651,11 +649,11 @@ extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol,
     // one device block: Ce, Cd, depth, raw, score | rbar (n*C) | idx | mask
     const size_t f_planes = 5 + (size_t)vol->C;
     const size_t bytes = n * (f_planes * sizeof(float) + sizeof(int32_t) + 1);
-    char* blk = nullptr;
-    hipError_t e = hipMalloc(&blk, bytes);
+    DevBuf blk;   // (freed when the call returns, however it returns)
+    hipError_t e = blk.alloc(bytes);
     if (e != hipSuccess)
         return fail(RSLF_ERR_ALLOC, "hipMalloc(%zu) for result planes failed: %s", bytes, hipGetErrorString(e));
-    float* d_Ce = (float*)blk;
+    float* d_Ce = blk.as<float>();
     float* d_Cd = d_Ce + n;
     float* d_depth = d_Cd + n;
     float* d_raw = d_depth + n;
@@ -686,10 +684,9 @@ extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol,
     }
     if (rc == RSLF_OK && stats) {
         unsigned long long tot = 0;
-        if (hipMemcpy(&tot, ctx->total, sizeof(tot), hipMemcpyDeviceToHost) == hipSuccess)
+        if (hipMemcpy(&tot, ctx->scratch.pixel_total(), sizeof(tot), hipMemcpyDeviceToHost) == hipSuccess)
             fill_stats(ctx, tot, dim_d, stats);
     }
-    (void)hipFree(blk);
     return rc;
 }
 RSLF_API_CATCH

@@ -1,8 +1,8 @@
 // K6, the renderers: colour-mapped disparity maps and coloured EPIs (include/rslf_hip.h, "rendering").  The kernels are
 // k6_render.hpp; every host-side decision is plan:: (rslf_plan.hpp, rslf_plan_render.hpp).  Scratch comes from the
-// context's helper slots (1: the colour table and the per-plane render constants, 2: the select states and the fits'
-// results, 3: the slab of partial sums; the host-pointer forms stage in 4: planes, 5: validity, 6: pictures), grow-only: a
-// second call of the same size allocates nothing.
+// context's shared buffers (SharedBuf in rslf_internal.hpp: kSharedTable, the colour table and the per-plane render constants;
+// kSharedLeft, the select states and the fits' results; kSharedRight, the slab of partial sums; the host-pointer forms stage
+// in kSharedStagePlanes / Mask / Out), grow-only: a second call of the same size allocates nothing.
 #include "rslf_internal.hpp"
 
 #include "k6_render.hpp"
@@ -16,7 +16,7 @@ int upload_table(rslf_ctx* ctx, const uint8_t* lut_bgr, const uint8_t** d_lut, c
                  int affine = 0, const float2** d_ab = nullptr)
 {
     void* p = nullptr;
-    int rc = helper_scratch(ctx, 1, plan::render_table_bytes(n_planes), &p);
+    int rc = helper_scratch(ctx, kSharedTable, plan::render_table_bytes(n_planes), &p);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(p, lut_bgr, plan::kRenderTableBytes, hipMemcpyHostToDevice, ctx->stream));
@@ -68,9 +68,9 @@ int fit_many(rslf_ctx* ctx, const float* d_planes, int n_planes, size_t plane_st
     pv.plane_stride = n_planes > 1 ? (long long)plane_stride : 0;
     pv.vec = plan::fit_vec4_ok(cols, pv.row_stride, pv.plane_stride, n_planes, d_planes, d_valid) ? 1 : 0;
     void *state_p = nullptr, *slab_p = nullptr;
-    int rc = helper_scratch(ctx, 2, plan::fit_state_bytes(n_planes), &state_p);
+    int rc = helper_scratch(ctx, kSharedLeft, plan::fit_state_bytes(n_planes), &state_p);
     if (!rc)
-        rc = helper_scratch(ctx, 3, plan::fit_slab_bytes(n_planes, n), &slab_p);
+        rc = helper_scratch(ctx, kSharedRight, plan::fit_slab_bytes(n_planes, n), &slab_p);
     if (rc)
         return rc;
     void* result_p = (char*)state_p + plan::fit_result_offset(n_planes);
@@ -311,11 +311,11 @@ extern "C" int rslf_render_planes_host(rslf_ctx* ctx, const float* h_planes, int
     const size_t extent = plan::planes_extent(n_planes, plane_stride, rows, cols, row_stride);
     const size_t out_bytes = (size_t)n_planes * rows * cols * 3;
     void *d_planes = nullptr, *d_valid = nullptr, *d_out = nullptr;
-    rc = helper_scratch(ctx, 4, extent * sizeof(float), &d_planes);
+    rc = helper_scratch(ctx, kSharedStagePlanes, extent * sizeof(float), &d_planes);
     if (!rc && h_valid)
-        rc = helper_scratch(ctx, 5, extent, &d_valid);
+        rc = helper_scratch(ctx, kSharedStageMask, extent, &d_valid);
     if (!rc)
-        rc = helper_scratch(ctx, 6, out_bytes, &d_out);
+        rc = helper_scratch(ctx, kSharedStageOut, out_bytes, &d_out);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(d_planes, h_planes, extent * sizeof(float), hipMemcpyHostToDevice, st));
@@ -357,11 +357,11 @@ extern "C" int rslf_render_epi_lines_host(rslf_ctx* ctx, const float* h_depth_vu
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)n_rows * U, out_bytes = (size_t)n_rows * S * U * 3;   // the scanlines asked for, no others
     void *d_depth = nullptr, *d_mask = nullptr, *d_out = nullptr;
-    rc = helper_scratch(ctx, 4, n * sizeof(float), &d_depth);
+    rc = helper_scratch(ctx, kSharedStagePlanes, n * sizeof(float), &d_depth);
     if (!rc)
-        rc = helper_scratch(ctx, 5, n, &d_mask);
+        rc = helper_scratch(ctx, kSharedStageMask, n, &d_mask);
     if (!rc)
-        rc = helper_scratch(ctx, 6, out_bytes, &d_out);
+        rc = helper_scratch(ctx, kSharedStageOut, out_bytes, &d_out);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(d_depth, h_depth_vu + (size_t)v_first * U, n * sizeof(float), hipMemcpyHostToDevice, st));

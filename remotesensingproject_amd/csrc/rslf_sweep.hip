@@ -14,44 +14,25 @@ using namespace rslf;
 
 // ---- "next" row: the 2-D sweep ----------------------------------------------
 
-// Two capacities: winner / running mask hold S*V*U entries, the median plane V*U.  (A single S*V*U
-// capacity once let a later volume with fewer views but larger planes overrun the plane: found by
+// Every buffer has its own capacity: winner / running mask hold S*V*U entries, the flags S*V*ceil(U/256), the median plane
+// V*U.  (A single S*V*U capacity once let a later volume with fewer views but larger planes overrun the plane: found by
 // tools/fuzz_sweep.py.)
 static int ensure_sweep_scratch(rslf_ctx* ctx, const rslf_volume* vol)
 {
+    Scratch& sc = ctx->scratch;
     const size_t n = (size_t)vol->S * vol->V * vol->U;
-    if (n > ctx->sweep_cap) {
-        (void)hipFree(ctx->winner);
-        (void)hipFree(ctx->sweep_mask);
-        ctx->winner = nullptr;
-        ctx->sweep_mask = nullptr;
-        ctx->sweep_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->winner, n * sizeof(int)));
-        HIP_TRY(hipMalloc(&ctx->sweep_mask, n));
-        ctx->sweep_cap = n;
-        // every claim pass is undone by its apply pass, so one fill lasts
-        HIP_TRY(hipMemsetAsync(ctx->winner, 0x7F, n * sizeof(int), ctx->stream));
-    }
+    const Reserved w = sc.winner.reserve(n * sizeof(int));
+    HIP_TRY(hip_err(w));
+    if (w.fresh)   // every claim pass is undone by its apply pass, so one fill lasts
+        HIP_TRY(hipMemsetAsync(sc.winner.get(), 0x7F, sc.winner.capacity(), ctx->stream));
+    HIP_TRY(hip_err(sc.sweep_mask.reserve(n)));
     const size_t flags = (size_t)vol->S * vol->V * ((vol->U + 255) / 256);
-    if (flags > ctx->dirty_cap) {
-        (void)hipFree(ctx->dirty);
-        (void)hipFree(ctx->remain);
-        ctx->dirty = nullptr;
-        ctx->remain = nullptr;
-        ctx->dirty_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->remain, flags * sizeof(int)));
-        HIP_TRY(hipMalloc(&ctx->dirty, flags));
-        ctx->dirty_cap = flags;
-        HIP_TRY(hipMemsetAsync(ctx->dirty, 0, flags, ctx->stream));   // every apply pass leaves them at 0 again
-    }
-    const size_t plane = (size_t)vol->V * vol->U;
-    if (plane > ctx->sweep_plane_cap) {
-        (void)hipFree(ctx->filtered);
-        ctx->filtered = nullptr;
-        ctx->sweep_plane_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->filtered, plane * sizeof(float)));
-        ctx->sweep_plane_cap = plane;
-    }
+    HIP_TRY(hip_err(sc.remain.reserve(flags * sizeof(int))));
+    const Reserved d = sc.dirty.reserve(flags);
+    HIP_TRY(hip_err(d));
+    if (d.fresh)   // every apply pass leaves them at 0 again
+        HIP_TRY(hipMemsetAsync(sc.dirty.get(), 0, sc.dirty.capacity(), ctx->stream));
+    HIP_TRY(hip_err(sc.filtered.reserve((size_t)vol->V * vol->U * sizeof(float))));
     return RSLF_OK;
 }
 
@@ -60,16 +41,11 @@ static int ensure_sweep_scratch(rslf_ctx* ctx, const rslf_volume* vol)
 // The order of the visits (core.hpp:981-990): plan::sweep_order.
 static void sweep_close(rslf_ctx* ctx, bool ok)
 {
-    ctx->keep_total = false;
-    ctx->sweep_listed = false;
-    ctx->sweep_expect = -1;
-    ctx->lc_mode = RSLF_LINE_CONF_OFF;   // line confidence is state of ONE sweep (rslf_sweep_line_confidence)
-    ctx->lc_Cl_svu = nullptr;
+    ctx->sweep = SweepState();   // line confidence too is state of ONE sweep (rslf_sweep_line_confidence)
     if (!ok) {
-        ctx->sweep_cap = 0;   // claims without their apply pass may be left behind: fresh winners and flags next time
-        ctx->dirty_cap = 0;
+        ctx->scratch.winner.mark_stale();   // claims without their apply pass may be left behind: fresh winners and flags next time
+        ctx->scratch.dirty.mark_stale();
     }
-    ctx->sweep_open = false;
 }
 
 // What a visit's scan is given.  After the centre view, propagation has explained most pixels: a visit scans a few per
@@ -97,7 +73,7 @@ extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uin
     if (v_lo < 0 || v_hi > vol->V || v_lo >= v_hi)
         return fail(RSLF_ERR_INVALID_ARG, "active scanlines [%d, %d) outside the volume's %d", v_lo, v_hi, vol->V);
     HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->sweep_open)
+    if (ctx->sweep.open)
         sweep_close(ctx, false);   // a sweep left open by a caller's error path
     int rc = ensure_sweep_scratch(ctx, vol);
     if (rc)
@@ -105,7 +81,7 @@ extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uin
     const int S = vol->S, V = vol->V, U = vol->U;
     const size_t n = (size_t)V * U;
     hipStream_t st = ctx->stream;
-    uint8_t* mask_svu = d_scan_mask_svu ? d_scan_mask_svu : ctx->sweep_mask;
+    uint8_t* mask_svu = d_scan_mask_svu ? d_scan_mask_svu : ctx->scratch.sweep_mask.as<uint8_t>();
     // core.hpp:958-965: running masks start as clones of the edge masks ...
     HIP_TRY(hipMemcpyAsync(mask_svu, d_Ce_mask_svu, (size_t)S * n, hipMemcpyDeviceToDevice, st));
     // ... except on halo scanlines (a sharded sweep): never scanned, never painted here -- their owner does both
@@ -113,13 +89,13 @@ extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uin
         HIP_TRY(hipMemset2DAsync(mask_svu, n, 0, (size_t)v_lo * U, S, st));
     if (v_hi < V)
         HIP_TRY(hipMemset2DAsync(mask_svu + (size_t)v_hi * U, n, 0, (size_t)(V - v_hi) * U, S, st));
-    HIP_TRY(hipMemsetAsync(ctx->total, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(ctx->scratch.pixel_total(), 0, sizeof(unsigned long long), st));
     {   // pixels of the running masks per 256-column segment: what lets the claims of the later visits skip most views
         const long long rows = (long long)S * V;
         const long long items = rows * ((U + 255) / 256);
         if (items > (1ll << 31) - 1)
             return fail(RSLF_ERR_UNSUPPORTED, "%d views x %d scanlines x %d columns: too large for one counting launch", S, V, U);
-        hipLaunchKernelGGL(k4_count_segments, dim3((unsigned)items), dim3(256), 0, st, mask_svu, rows, U, ctx->remain);
+        hipLaunchKernelGGL(k4_count_segments, dim3((unsigned)items), dim3(256), 0, st, mask_svu, rows, U, ctx->scratch.remain.as<int>());
         HIP_TRY(hipGetLastError());
     }
     // the sparse visits' records, sized before the first visit (no allocation in the middle of the sequence; should a
@@ -127,15 +103,12 @@ extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uin
     rc = sweep_scan_presize(ctx, vol, dim_d, visit_inputs(false, true));
     if (rc)
         return rc;
-    ctx->keep_total = true;
-    ctx->sweep_open = true;
-    ctx->sweep_first = true;
-    ctx->sweep_scanned = false;
-    ctx->sweep_listed = false;
-    ctx->lc_mode = RSLF_LINE_CONF_OFF;
-    ctx->lc_Cl_svu = nullptr;
-    ctx->sweep_mask_run = mask_svu;
-    ctx->sweep_expect = plan::sweep_order(S)[0];
+    SweepState sw;   // first visit next, nothing scanned or listed, no line confidence
+    sw.open = true;
+    sw.keep_total = true;
+    sw.mask_run = mask_svu;
+    sw.expect = plan::sweep_order(S)[0];
+    ctx->sweep = sw;
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -187,27 +160,26 @@ extern "C" int rslf_sweep_line_confidence(rslf_ctx* ctx, const rslf_volume* vol,
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", mode);
     if (mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", mode);
-    if (!ctx->sweep_open || ctx->sweep_scanned || !ctx->sweep_first)
+    SweepState& sw = ctx->sweep;
+    if (!sw.open || sw.scanned || !sw.first)
         return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_line_confidence belongs between rslf_sweep_begin and the first visit");
     HIP_TRY(hipSetDevice(ctx->device));
-    ctx->lc_mode = RSLF_LINE_CONF_OFF;
-    ctx->lc_Cl_svu = nullptr;
+    sw.lc_mode = RSLF_LINE_CONF_OFF;
+    sw.lc_Cl_svu = nullptr;
     if (mode == RSLF_LINE_CONF_OFF)
         return RSLF_OK;
+    // buffers of their own, not shared ones: they are held until rslf_sweep_end
+    Scratch& sc = ctx->scratch;
     const size_t kb = plan::line_conf_columns_bytes(mode, vol->V, vol->S, vol->U);
-    void *K = nullptr, *idx = nullptr;
-    int rc = helper_scratch(ctx, rslf_ctx::kLineConfColumns, kb, &K);
-    if (!rc)
-        rc = helper_scratch(ctx, rslf_ctx::kLineConfArgmax, plan::line_conf_argmax_bytes(mode, vol->V, vol->U), &idx);
-    if (rc)
-        return rc;
+    HIP_TRY(hip_err(sc.lc_columns.reserve(kb)));
+    HIP_TRY(hip_err(sc.lc_argmax.reserve(plan::line_conf_argmax_bytes(mode, vol->V, vol->U))));
     // core.hpp:975-979 leaves K uninitialised; here a column nobody has written reads as zeros.  The arg-max
     // plane is refilled with -1 by every scan.
-    HIP_TRY(hipMemsetAsync(K, 0, kb, ctx->stream));
-    ctx->lc_K_vsu = static_cast<float*>(K);
-    ctx->lc_idx_vu = static_cast<int32_t*>(idx);
-    ctx->lc_Cl_svu = d_Cl_svu;
-    ctx->lc_mode = mode;
+    HIP_TRY(hipMemsetAsync(sc.lc_columns.get(), 0, kb, ctx->stream));
+    sw.lc_K_vsu = sc.lc_columns.as<float>();
+    sw.lc_idx_vu = sc.lc_argmax.as<int32_t>();
+    sw.lc_Cl_svu = d_Cl_svu;
+    sw.lc_mode = mode;
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -218,33 +190,33 @@ extern "C" int rslf_sweep_visit_scan(rslf_ctx* ctx, const rslf_volume* vol, cons
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (!ctx->sweep_open)
+    if (!ctx->sweep.open)
         return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_visit_scan without rslf_sweep_begin");
     if ((d_dmin_svu == nullptr) != (d_dmax_svu == nullptr))
         return fail(RSLF_ERR_INVALID_ARG, "d_dmin_svu and d_dmax_svu must both be given or both be NULL");
     if (s_hat < 0 || s_hat >= vol->S)
         return fail(RSLF_ERR_INVALID_ARG, "s_hat=%d outside [0,%d)", s_hat, vol->S);
-    if (s_hat != ctx->sweep_expect)   // the previous visit has already listed this view's pixels (k4_propagate_apply)
-        return fail(RSLF_ERR_INVALID_ARG, "the sweep visits view %d next (core.hpp:981-990), not %d", ctx->sweep_expect, s_hat);
+    if (s_hat != ctx->sweep.expect)   // the previous visit has already listed this view's pixels (k4_propagate_apply)
+        return fail(RSLF_ERR_INVALID_ARG, "the sweep visits view %d next (core.hpp:981-990), not %d", ctx->sweep.expect, s_hat);
     const size_t n = (size_t)vol->V * vol->U;
     // core.hpp:1012-1028: the pile call is the scan of every EPI followed by the selective median.  In the
     // reference the stored plane keeps the RAW depths and only the local header is rebound to the median
     // (core.hpp:892), which the propagation then paints from: so the scan writes the view's depth plane and the median
-    // goes to ctx->filtered (rslf_sweep_visit_finish) -- no plane copies.
-    ctx->sweep_scanned = true;
-    const bool lc = ctx->lc_mode != RSLF_LINE_CONF_OFF;   // K7 re-runs the winners: the scan keeps its arg-max indices
+    // goes to Scratch::filtered (rslf_sweep_visit_finish) -- no plane copies.
+    ctx->sweep.scanned = true;
+    const bool lc = ctx->sweep.lc_mode != RSLF_LINE_CONF_OFF;   // K7 re-runs the winners: the scan keeps its arg-max indices
     const int rc = depth_epi_scan(ctx, vol, d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr,
                                   d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr, dmin, dmax, dim_d, s_hat, d_Ce_svu + (size_t)s_hat * n,
                                   d_Ce_mask_svu + (size_t)s_hat * n, d_Cd_svu + (size_t)s_hat * n, d_depth_svu + (size_t)s_hat * n,
-                                  d_rbar_svu + (size_t)s_hat * n * vol->C, p, ctx->sweep_mask_run + (size_t)s_hat * n,
-                                  lc ? ctx->lc_idx_vu : nullptr, nullptr, nullptr, visit_inputs(ctx->sweep_first, ctx->sweep_listed));
+                                  d_rbar_svu + (size_t)s_hat * n * vol->C, p, ctx->sweep.mask_run + (size_t)s_hat * n,
+                                  lc ? ctx->sweep.lc_idx_vu : nullptr, nullptr, nullptr, visit_inputs(ctx->sweep.first, ctx->sweep.listed));
     if (rc || !lc)
         return rc;
-    ctx->lc_Ce_svu = d_Ce_svu;
-    ctx->lc_dmin_vu = d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr;
-    ctx->lc_dmax_vu = d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr;
-    ctx->lc_dmin = dmin, ctx->lc_dmax = dmax, ctx->lc_dim_d = dim_d;
-    ctx->lc_consts = make_scan_consts(p);
+    ctx->sweep.lc_Ce_svu = d_Ce_svu;
+    ctx->sweep.lc_dmin_vu = d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr;
+    ctx->sweep.lc_dmax_vu = d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr;
+    ctx->sweep.lc_dmin = dmin, ctx->sweep.lc_dmax = dmax, ctx->sweep.lc_dim_d = dim_d;
+    ctx->sweep.lc_consts = make_scan_consts(p);
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -254,24 +226,29 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
 {
     if (!ctx || !vol || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu || !p)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (!ctx->sweep_open)
+    if (!ctx->sweep.open)
         return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_visit_finish without rslf_sweep_begin");
-    if (s_hat != ctx->sweep_expect)
-        return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_visit_finish(%d): the open visit is view %d", s_hat, ctx->sweep_expect);
+    if (s_hat != ctx->sweep.expect)
+        return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_visit_finish(%d): the open visit is view %d", s_hat, ctx->sweep.expect);
     if (p->median_filter_size < 0 || p->median_filter_size > plan::kMedianMaxSize)
         return fail(RSLF_ERR_INVALID_ARG, "median_filter_size=%d: must be in [0, %d]", p->median_filter_size, plan::kMedianMaxSize);
     HIP_TRY(hipSetDevice(ctx->device));
     const int S = vol->S, V = vol->V, U = vol->U, C = vol->C;
     const size_t n = (size_t)V * U;
     hipStream_t st = ctx->stream;
-    uint8_t* mask_svu = ctx->sweep_mask_run;
+    uint8_t* mask_svu = ctx->sweep.mask_run;
     const dim3 grid_vu((U + 255) / 256, V);
     if ((long long)S * V > (1ll << 31) - 1 || U > 65536)
         return fail(RSLF_ERR_UNSUPPORTED, "%d views x %d scanlines x %d columns: too large for one apply launch", S, V, U);
     const plan::MedianPlan mp = plan::median_plan(p->median_filter_size, C);   // window tile in LDS (k3_median.hpp)
     const plan::NormThreshold median_thr = plan::norm_threshold(p->median_filter_epsilon);
     const plan::NormThreshold prop_thr = plan::norm_threshold(p->propagation_epsilon);
-    int* packed_n = reinterpret_cast<int*>(ctx->total + 1);
+    const Scratch& sc = ctx->scratch;
+    float* const filtered = sc.filtered.as<float>();
+    int* const winner = sc.winner.as<int>();
+    uint8_t* const dirty = sc.dirty.as<uint8_t>();
+    int* const remain = sc.remain.as<int>();
+    int* packed_n = sc.packed_len();
     float* depth = d_depth_svu + (size_t)s_hat * n;
     float* Cd = d_Cd_svu + (size_t)s_hat * n;
     float* rbar = d_rbar_svu + (size_t)s_hat * n * C;
@@ -285,25 +262,25 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
     if (ctx->force_packed == 0 || n > (size_t)INT32_MAX)
         s_next = -1;   // that scan will not take a packed list: it compacts for itself
     // Line confidence (core.hpp:1032-1081): K7 needs the FILTERED plane (:892) and, in mode 2, the claims need K7's plane.
-    const int lc_mode = ctx->lc_mode;
-    float* Cl = lc_mode ? ctx->lc_Cl_svu + (size_t)s_hat * n : nullptr;
+    const int lc_mode = ctx->sweep.lc_mode;
+    float* Cl = lc_mode ? ctx->sweep.lc_Cl_svu + (size_t)s_hat * n : nullptr;
     auto line_confidence = [&]() -> int {
         LineConfArgs q = {};
         q.V = V, q.S = S, q.U = U, q.s_hat = s_hat;
-        q.Ce_svu = ctx->lc_Ce_svu;
-        q.K_vsu = ctx->lc_K_vsu;
-        q.depth_vu = ctx->filtered;
+        q.Ce_svu = ctx->sweep.lc_Ce_svu;
+        q.K_vsu = ctx->sweep.lc_K_vsu;
+        q.depth_vu = filtered;
         q.mask_vu = cem;
         q.Cl_vu = Cl;
         ScanArgs a = {};
         a.vol = view_of(vol);
-        a.dmin_vu = ctx->lc_dmin_vu, a.dmax_vu = ctx->lc_dmax_vu;
-        a.dmin = ctx->lc_dmin, a.dmax = ctx->lc_dmax;
-        a.dim_d = ctx->lc_dim_d;
+        a.dmin_vu = ctx->sweep.lc_dmin_vu, a.dmax_vu = ctx->sweep.lc_dmax_vu;
+        a.dmin = ctx->sweep.lc_dmin, a.dmax = ctx->sweep.lc_dmax;
+        a.dim_d = ctx->sweep.lc_dim_d;
         a.s_hat = s_hat;
-        a.k = ctx->lc_consts;
+        a.k = ctx->sweep.lc_consts;
         a.groups = 1;
-        return launch_line_confidence(ctx, q, a, ctx->lc_idx_vu, C);
+        return launch_line_confidence(ctx, q, a, ctx->sweep.lc_idx_vu, C);
     };
     // core.hpp:1097-1103: C_d gates whenever use_disp_confidence_score is set, C_l in mode 2, else the edge mask
     const plan::SweepGate gate = plan::sweep_gate(p->use_disp_confidence_score != 0, lc_mode);
@@ -316,7 +293,7 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k3_selective_median<CC, MODE>),                           \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds_bytes));                         \
         hipLaunchKernelGGL((k3_selective_median<CC, MODE>), grid_vu, dim3(kMedianBlock), mp.lds_bytes, st, view_of(vol), depth,   \
-                           ctx->filtered, cem, s_hat, mp.w, median_thr);                                                          \
+                           filtered, cem, s_hat, mp.w, median_thr);                                                               \
         launched = true;                                                                                                          \
     }
         RSLF_MEDIAN_MODES(RSLF_K3_CASE, 1)
@@ -336,10 +313,10 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
         if (mp.lds_bytes > ((size_t)64 << 10))                                                                                    \
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k34_median_claim<CC, MODE>),                              \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds_bytes));                         \
-        hipLaunchKernelGGL((k34_median_claim<CC, MODE>), grid_vu, dim3(256), mp.lds_bytes, st, view_of(vol), s_hat, depth, ctx->filtered, \
-                           cem, mp.w, median_thr, rbar, mask_svu, ctx->winner, ctx->dirty, p->slope_factor, prop_thr,             \
+        hipLaunchKernelGGL((k34_median_claim<CC, MODE>), grid_vu, dim3(256), mp.lds_bytes, st, view_of(vol), s_hat, depth, filtered, \
+                           cem, mp.w, median_thr, rbar, mask_svu, winner, dirty, p->slope_factor, prop_thr,                       \
                            gate_vu, gate_thr, packed_n,                                                                           \
-                           ctx->claim_skip ? ctx->remain : nullptr);                                                             \
+                           ctx->claim_skip ? remain : nullptr);                                                                   \
         launched = true;                                                                                                          \
     }
     RSLF_MEDIAN_MODES(RSLF_K34_CASE, 1)
@@ -352,13 +329,13 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
         if (int rc = line_confidence())
             return rc;
     const unsigned apply_blocks = (unsigned)((s_next >= 0 ? V : 0) + ((long long)S * V + kApplyRowsPerBlock - 1) / kApplyRowsPerBlock);
-    hipLaunchKernelGGL(k4_propagate_apply, dim3(apply_blocks), dim3(256), 0, st, S, V, U, s_hat, ctx->filtered, Cd, d_depth_svu,
-                       d_Cd_svu, mask_svu, ctx->winner, ctx->dirty, s_next, s_next >= 0 ? d_Ce_mask_svu + (size_t)s_next * n : nullptr, ctx->list,
-                       ctx->count, ctx->total, packed_n, ctx->remain, ctx->count + ctx->count_cap, Cl, lc_mode ? ctx->lc_Cl_svu : nullptr);
+    hipLaunchKernelGGL(k4_propagate_apply, dim3(apply_blocks), dim3(256), 0, st, S, V, U, s_hat, filtered, Cd, d_depth_svu,
+                       d_Cd_svu, mask_svu, winner, dirty, s_next, s_next >= 0 ? d_Ce_mask_svu + (size_t)s_next * n : nullptr, sc.list.as<int>(),
+                       sc.count.as<int>(), sc.pixel_total(), packed_n, remain, sc.rowbase.as<int>(), Cl, lc_mode ? ctx->sweep.lc_Cl_svu : nullptr);
     HIP_TRY(hipGetLastError());
-    ctx->sweep_listed = s_next >= 0;
-    ctx->sweep_expect = s_after;
-    ctx->sweep_first = false;
+    ctx->sweep.listed = s_next >= 0;
+    ctx->sweep.expect = s_after;
+    ctx->sweep.first = false;
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -367,17 +344,11 @@ extern "C" int rslf_sweep_end(rslf_ctx* ctx, int ok, int dim_d, rslf_stats* stat
 {
     if (!ctx)
         return fail(RSLF_ERR_INVALID_ARG, "ctx is NULL");
-    const bool was_open = ctx->sweep_open;
+    const bool was_open = ctx->sweep.open;
     sweep_close(ctx, ok != 0 && was_open);
     if (ok && was_open && stats) {
-        unsigned long long tot = 0;
         HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(hipMemcpyAsync(&tot, ctx->total, sizeof(tot), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        stats->pixels_scanned = (int64_t)tot;
-        stats->units = (int64_t)tot * dim_d;
-        stats->scan_kernel = ctx->last_kernel;
-        stats->s_pad = ctx->last_spad;
+        return read_stats(ctx, dim_d, stats);
     }
     return RSLF_OK;
 }
@@ -515,17 +486,17 @@ static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, f
     HIP_TRY(mask.alloc(n));
     if (line_mode != RSLF_LINE_CONF_OFF)
         HIP_TRY(Cl.alloc(n * 4));
-    int rc = depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, (float*)Ce.p, (uint8_t*)mask.p, (float*)Cd.p,
-                            (float*)depth.p, (float*)rbar.p, nullptr, stats, line_mode, (float*)Cl.p);
+    int rc = depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, Ce.as<float>(), mask.as<uint8_t>(), Cd.as<float>(),
+                            depth.as<float>(), rbar.as<float>(), nullptr, stats, line_mode, Cl.as<float>());
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
-    if (h_Ce_svu) HIP_TRY(hipMemcpyAsync(h_Ce_svu, Ce.p, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_Ce_mask_svu) HIP_TRY(hipMemcpyAsync(h_Ce_mask_svu, mask.p, n, hipMemcpyDeviceToHost, st));
-    if (h_Cd_svu) HIP_TRY(hipMemcpyAsync(h_Cd_svu, Cd.p, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_depth_svu) HIP_TRY(hipMemcpyAsync(h_depth_svu, depth.p, n * 4, hipMemcpyDeviceToHost, st));
-    if (h_rbar_svu) HIP_TRY(hipMemcpyAsync(h_rbar_svu, rbar.p, n * 4 * vol->C, hipMemcpyDeviceToHost, st));
-    if (line_mode != RSLF_LINE_CONF_OFF) HIP_TRY(hipMemcpyAsync(h_Cl_svu, Cl.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_Ce_svu) HIP_TRY(hipMemcpyAsync(h_Ce_svu, Ce.get(), n * 4, hipMemcpyDeviceToHost, st));
+    if (h_Ce_mask_svu) HIP_TRY(hipMemcpyAsync(h_Ce_mask_svu, mask.get(), n, hipMemcpyDeviceToHost, st));
+    if (h_Cd_svu) HIP_TRY(hipMemcpyAsync(h_Cd_svu, Cd.get(), n * 4, hipMemcpyDeviceToHost, st));
+    if (h_depth_svu) HIP_TRY(hipMemcpyAsync(h_depth_svu, depth.get(), n * 4, hipMemcpyDeviceToHost, st));
+    if (h_rbar_svu) HIP_TRY(hipMemcpyAsync(h_rbar_svu, rbar.get(), n * 4 * vol->C, hipMemcpyDeviceToHost, st));
+    if (line_mode != RSLF_LINE_CONF_OFF) HIP_TRY(hipMemcpyAsync(h_Cl_svu, Cl.get(), n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RSLF_OK;
 }

@@ -20,10 +20,23 @@ def test_plan_unit_tests_under_sanitizers(tmp_path):
     assert "plan tests ok" in r.stdout
 
 
+def test_scratch_unit_tests_under_sanitizers(tmp_path):
+    """GrowBuf (rslf_scratch.hpp), the one owning buffer type, with a counting allocator: grow-only, free before allocate,
+    the state after a failed allocation, `fresh`, moves, no leak and no double free."""
+    exe = tmp_path / "test_scratch"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+                    "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "test_scratch.cpp"), "-o", str(exe)], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "scratch tests ok" in r.stdout
+
+
 def test_plan_header_is_host_only():
-    """rslf_plan.hpp must stay compilable by g++ alone: no HIP include, no device qualifier."""
-    txt = open(os.path.join(CSRC, "rslf_plan.hpp")).read()
-    assert "hip/hip_runtime" not in txt and "__device__" not in txt and "__global__" not in txt
+    """rslf_plan.hpp and rslf_scratch.hpp must stay compilable by g++ alone: no HIP include, no device qualifier."""
+    for name in ("rslf_plan.hpp", "rslf_scratch.hpp"):
+        txt = open(os.path.join(CSRC, name)).read()
+        assert "hip/hip_runtime" not in txt and "__device__" not in txt and "__global__" not in txt, name
 
 
 def _units():
