@@ -146,6 +146,8 @@ int rslf_ctx_synchronize(rslf_ctx* ctx);
  *   "stream_lds_kib" dynamic LDS of one streaming workgroup, KiB (default 80)
  *   "time_all"       0 (default) | 1: every scan launch is bracketed by its own pair of HIP events, summed and reset by
  *                    rslf_scan_time_total_ms (the K2 time of a whole sweep or pyramid; each event costs ~5.6 us in the queue)
+ *   "staging_kib"    0 (default) the host uploads of a volume walk it in passes through 256 MiB of device staging | 1..262144:
+ *                    that budget in KiB (a pass holds at least one scanline), so that a small volume takes several passes
  * Results do not depend on these (the parity tests drive every combination; "claim_skip" on / off is compared plane by
  * plane in tests/test_gpu_sweep2d.py); speed does.  One qualification: the disparity confidence C_d = C_e * |max - mean of
  * the scores| takes the mean through a double sum whose ORDER differs between launch shapes (per wave in the row kernels,

@@ -181,7 +181,8 @@ inline std::vector<uint8_t> render_planes(rslf_ctx* ctx, const std::vector<float
 }
 
 #ifdef RSLFX_HAVE_OPENCV
-// The data pointers of a Vec<Mat> of EPIs and their element type; one shape, one type, `channels` channels.  CV_16U is
+// The data pointers of a Vec<Mat> of EPIs and their element type; one shape, one row step (the library takes ONE
+// row_stride_bytes for all: a clone among ROI Mats is refused, not misread), one type, `channels` channels.  CV_16U is
 // accepted where the OpenCV in use defines it (a macro in every OpenCV release).
 inline std::vector<const void*> mat_pointers(const std::vector<cv::Mat>& epis, int channels, InputType& type, const char* who)
 {
@@ -193,6 +194,8 @@ inline std::vector<const void*> mat_pointers(const std::vector<cv::Mat>& epis, i
     for (size_t v = 0; v < epis.size(); v++) {
         if (epis[v].rows != epis[0].rows || epis[v].cols != epis[0].cols || epis[v].type() != epis[0].type())
             throw std::invalid_argument(std::string(who) + ": EPIs differ in size or type");
+        if (epis[v].step[0] != epis[0].step[0])
+            throw std::invalid_argument(std::string(who) + ": EPIs differ in their row step (clone() the ROI Mats, or none)");
         ptrs[v] = epis[v].data;
     }
     const int depth = epis[0].depth();

@@ -258,7 +258,9 @@ extern "C" int rslf_ctx_set_debug(rslf_ctx* ctx, const char* key, int value) RSL
         ctx->stream_groups = value;
     else if (strcmp(key, "stream_lds_kib") == 0 && value >= 16 && value <= 152) {
         ctx->stream_lds_bytes = (size_t)value << 10;
-    } else
+    } else if (strcmp(key, "staging_kib") == 0 && value >= 0 && value <= 262144)
+        ctx->staging_kib = value;
+    else
         return fail(RSLF_ERR_INVALID_ARG, "rslf_ctx_set_debug: unknown key or value out of range: %s = %d", key, value);
     return RSLF_OK;
 }
@@ -412,6 +414,12 @@ static int pack_chunk(rslf_volume* vol, const SrcT* d_src, int V0, int Vn, bool 
     return RSLF_OK;
 }
 
+// Bytes of device staging one pass of a chunked host upload may take: plan::kStagingBudget, or the "staging_kib" hook.
+static size_t staging_budget(const rslf_ctx* ctx)
+{
+    return ctx->staging_kib > 0 ? (size_t)ctx->staging_kib << 10 : plan::kStagingBudget;
+}
+
 // Host upload in scanline chunks through a bounded device staging buffer.
 template <typename SrcT>
 int rslf::upload_host(rslf_volume* vol, const SrcT* const* h_ptrs, size_t row_stride_bytes, bool image_major, float scale)
@@ -424,7 +432,7 @@ int rslf::upload_host(rslf_volume* vol, const SrcT* const* h_ptrs, size_t row_st
     if (row_stride_bytes < row_bytes)
         return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", row_stride_bytes, row_bytes);
     const size_t epi_bytes = row_bytes * vol->S;
-    const int chunk = plan::staging_chunk_rows(epi_bytes, vol->V);
+    const int chunk = plan::staging_chunk_rows(epi_bytes, vol->V, staging_budget(ctx));
     int rc = ensure_staging(ctx, (size_t)chunk * epi_bytes);
     if (rc)
         return rc;
@@ -494,7 +502,7 @@ static int upload_images_xf(rslf_volume* vol, const SrcT* const* h_imgs, size_t 
     if (row_stride_bytes < row_bytes)
         return fail(RSLF_ERR_INVALID_ARG, "row_stride_bytes %zu < row size %zu", row_stride_bytes, row_bytes);
     const size_t epi_bytes = row_bytes * n_imgs;
-    const int chunk = plan::staging_chunk_rows(epi_bytes, vol->V);
+    const int chunk = plan::staging_chunk_rows(epi_bytes, vol->V, staging_budget(ctx));
     int rc = ensure_staging(ctx, (size_t)chunk * epi_bytes);
     if (rc)
         return rc;

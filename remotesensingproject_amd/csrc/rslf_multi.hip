@@ -537,9 +537,9 @@ extern "C" int rslf_multi_depth1d_pile_u8(rslf_multi* m, const uint8_t* const* h
                                           uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu,
                                           float* h_score_vu, float* h_depth_raw_vu, rslf_stats* stats) RSLF_API_TRY
 {
-    MultiJob j = {(const void* const*)h_epis, Elem::U8, row_stride_bytes, V, S, U, C, 255.0f, dmin, dmax, dim_d, s_hat, p,
-                  h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, 0, -1};
-    return multi_run(m, j, stats);
+    // (the argument checks, the stride's among them, are multi_pile's; its scale for CV_8U is 255)
+    return multi_pile(m, Elem::U8, (const void* const*)h_epis, row_stride_bytes, V, S, U, C, -1.0f, dmin, dmax, dim_d, s_hat, p, -1,
+                      h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, stats, nullptr);
 }
 RSLF_API_CATCH
 

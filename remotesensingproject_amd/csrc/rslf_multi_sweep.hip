@@ -344,8 +344,9 @@ extern "C" int rslf_multi_depth2d_run_u8(rslf_multi* m, const uint8_t* const* h_
                                          uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
                                          uint8_t* h_scan_mask_svu, rslf_stats* stats) RSLF_API_TRY
 {
-    return multi_depth2d(m, (const void* const*)h_epis, Elem::U8, row_stride_bytes, V, S, U, C, 255.0f, dmin, dmax, dim_d, p, h_Ce_svu,
-                         h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, h_scan_mask_svu, stats);
+    // (the argument checks, the stride's among them, are multi_depth2d_host's; its scale for CV_8U is 255)
+    return multi_depth2d_host(m, Elem::U8, (const void* const*)h_epis, row_stride_bytes, V, S, U, C, -1.0f, dmin, dmax, dim_d, p,
+                              h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, h_scan_mask_svu, stats, nullptr);
 }
 RSLF_API_CATCH
 

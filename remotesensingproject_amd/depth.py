@@ -118,7 +118,7 @@ class Context:
         check(_lib.lib().rslf_ctx_synchronize(self._h), "rslf_ctx_synchronize")
 
     _DEBUG_DEFAULTS = dict(force_scan=0, force_groups=0, force_packed=-1, px=-1, stream_share=1, stream_groups=0, stream_lds_kib=80,
-                           claim_skip=1, time_all=0, row_split=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
+                           claim_skip=1, time_all=0, row_split=1, staging_kib=0)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
     _FORCE_SCAN = {None: 0, "auto": 0, "generic": 1, "stream": 2}
 
     def set_debug(self, **hooks) -> None:
@@ -212,19 +212,15 @@ class Volume:
         C_ = 1 if e0.ndim == 2 else e0.shape[2]
         vol = Volume(ctx, len(epis), S, U, C_)
         dt = field_dtype(e0.dtype)
-        arrs = [np.ascontiguousarray(e, dtype=dt) for e in epis]
-        for a in arrs:
-            if a.shape != arrs[0].shape:
-                raise ValueError("all EPIs must have the same shape")
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        arrs, ptrs, stride = host_rows(epis, dt)   # (arrs: alive over the calls below)
         L = _lib.lib()
         if dt == np.uint8:
-            check(L.rslf_volume_upload_epis_u8(vol._h, ptrs, 0), "rslf_volume_upload_epis_u8")
+            check(L.rslf_volume_upload_epis_u8(vol._h, ptrs, stride), "rslf_volume_upload_epis_u8")
             vol.scale_used = 255.0
         else:
             name = "rslf_volume_upload_epis_" + _SUFFIX[dt]
             su = C.c_float()
-            check(getattr(L, name)(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su)), name)
+            check(getattr(L, name)(vol._h, ptrs, stride, float(epi_scale_factor), C.byref(su)), name)
             vol.scale_used = float(su.value)
         return vol
 
@@ -241,25 +237,24 @@ class Volume:
         S, U = (cols, len(imgs)) if transpose else (len(imgs), cols)
         vol = Volume(ctx, V, S, U, C_)
         dt = field_dtype(i0.dtype)
-        arrs = [np.ascontiguousarray(e, dtype=dt) for e in imgs]
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        arrs, ptrs, stride = host_rows(imgs, dt)   # (arrs: alive over the calls below)
         L = _lib.lib()
         plain = not (transpose or rotate_180)
         if dt == np.uint8:
             if plain:
-                check(L.rslf_volume_upload_images_u8(vol._h, ptrs, 0), "rslf_volume_upload_images_u8")
+                check(L.rslf_volume_upload_images_u8(vol._h, ptrs, stride), "rslf_volume_upload_images_u8")
             else:
-                check(L.rslf_volume_upload_images_xf_u8(vol._h, ptrs, 0, int(transpose), int(rotate_180)),
+                check(L.rslf_volume_upload_images_xf_u8(vol._h, ptrs, stride, int(transpose), int(rotate_180)),
                       "rslf_volume_upload_images_xf_u8")
             vol.scale_used = 255.0
         else:
             su = C.c_float()
             if plain:
                 name = "rslf_volume_upload_images_" + _SUFFIX[dt]
-                check(getattr(L, name)(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su)), name)
+                check(getattr(L, name)(vol._h, ptrs, stride, float(epi_scale_factor), C.byref(su)), name)
             else:
                 name = "rslf_volume_upload_images_xf_" + _SUFFIX[dt]
-                check(getattr(L, name)(vol._h, ptrs, 0, float(epi_scale_factor), C.byref(su), int(transpose), int(rotate_180)), name)
+                check(getattr(L, name)(vol._h, ptrs, stride, float(epi_scale_factor), C.byref(su), int(transpose), int(rotate_180)), name)
             vol.scale_used = float(su.value)
         return vol
 
@@ -611,21 +606,58 @@ class Depth1DComputer_pile:
         )
 
 
-def host_epis(epis: Sequence[np.ndarray], dtype=None):
+def host_rows(arrays: Sequence[np.ndarray], dtype, in_place: bool = True):
+    """Host arrays of one shape ([rows, U] or [rows, U, C]: EPIs or images) as the C-ABI's host-pointer entries take them:
+    (the arrays, to be kept alive over the call; their pointers; row_stride_bytes).  Rows with padding between them -- a window
+    `parent[:, a:b]` of a wider array, the reference's ROI Mat with its cv::Mat::step -- go up where they lie: an array is
+    taken in place when it is a numpy.ndarray of `dtype` whose rows are dense (the strides of a C-contiguous [U] / [U, C]
+    row) and lie a positive stride of at least one row apart.  When every array is, and all share that stride, it is the
+    row_stride_bytes; otherwise every array goes as a dense copy (an array that is dense already as it is) and the stride is
+    0, as it is for a list of dense arrays.  `in_place=False`: always the dense form."""
+    dt = np.dtype(dtype)
+
+    def stride_in_place(a) -> int:
+        """The row stride `a` can be read with where it lies, or -1."""
+        if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim not in (2, 3):
+            return -1
+        row_bytes, inner = dt.itemsize, a.ndim - 1
+        for k in range(inner, 0, -1):          # dense within a row (an axis of one element has no stride to speak of)
+            if a.shape[k] != 1 and a.strides[k] != row_bytes:
+                return -1
+            row_bytes *= a.shape[k]
+        if a.shape[0] == 1:
+            return row_bytes
+        return a.strides[0] if a.strides[0] >= row_bytes else -1
+
+    # a thousand EPIs: no per-array conversions or ctypes objects where none are needed
+    strides = [stride_in_place(a) for a in arrays] if in_place else []
+    if strides and strides[0] > 0 and all(st == strides[0] for st in strides):
+        keep, stride = list(arrays), strides[0]
+    else:
+        keep = [a if (type(a) is np.ndarray and a.dtype == dt and a.flags.c_contiguous) else np.ascontiguousarray(a, dtype=dt)
+                for a in arrays]
+        stride = 0
+    if any(a.shape != keep[0].shape for a in keep):
+        raise ValueError("every array must have the shape of the first, %s" % (keep[0].shape,))
+    if stride and stride == int(np.prod(keep[0].shape[1:])) * dt.itemsize:
+        stride = 0                             # dense rows
+    ptrs = (C.c_void_p * len(keep))(*[a.__array_interface__["data"][0] for a in keep])
+    return keep, ptrs, stride
+
+
+def host_epis(epis: Sequence[np.ndarray], dtype=None, stride: bool = False):
     """A host EPI list (the reference's Vec<Mat>: V arrays [S,U] or [S,U,3]) as the C-ABI takes it: (the arrays, to be
     kept alive over the call; their pointers; their element type; V, S, U, C).  Every EPI goes as `dtype`, by default
-    the first one's, and must have the first one's shape."""
+    the first one's, and must have the first one's shape.  With `stride=True` the row_stride_bytes to pass is returned as an
+    eighth value and padded rows go up in place (host_rows); without it every EPI is dense, for callers that pass stride 0."""
     dt = np.asarray(epis[0]).dtype if dtype is None else np.dtype(dtype)
     if dt not in (np.uint8, np.uint16, np.float32):
         raise TypeError("EPIs must be uint8, uint16 or float32 (dc.hpp:149-154)")
-    # a thousand EPIs: no per-array conversions or ctypes objects where none are needed
-    keep = [e if (type(e) is np.ndarray and e.dtype == dt and e.flags.c_contiguous) else np.ascontiguousarray(e, dtype=dt) for e in epis]
+    keep, ptrs, row_stride = host_rows(epis, dt, in_place=stride)
     S, U = keep[0].shape[0], keep[0].shape[1]
     C_ = 1 if keep[0].ndim == 2 else keep[0].shape[2]
-    if any(e.shape != keep[0].shape for e in keep):
-        raise ValueError("every EPI must have the shape of the first, %s" % (keep[0].shape,))
-    ptrs = (C.c_void_p * len(keep))(*[e.__array_interface__["data"][0] for e in keep])
-    return keep, ptrs, dt, len(keep), S, U, C_
+    out = (keep, ptrs, dt, len(keep), S, U, C_)
+    return out + (row_stride,) if stride else out
 
 
 class MultiDevice:
@@ -655,7 +687,7 @@ class MultiDevice:
     def depth1d_pile(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, s_hat: int = -1,
                      epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None) -> dict:
         """epis: the reference's Vec<Mat> -- V arrays [S,U] or [S,U,3], all uint8, all uint16 or all float32."""
-        keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
+        keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((V, U), np.float32), edge_mask=np.empty((V, U), np.uint8),
                    disp_confidence=np.empty((V, U), np.float32), depth=np.empty((V, U), np.float32),
                    rbar=np.empty((V, U, C_), np.float32), depth_idx=np.empty((V, U), np.int32),
@@ -666,13 +698,13 @@ class MultiDevice:
         st = RslfStats()
         L = _lib.lib()
         if dt == np.uint8:
-            check(L.rslf_multi_depth1d_pile_u8(self._h, ptrs, 0, V, S, U, C_, float(dmin), float(dmax), int(dim_d), int(s_hat),
+            check(L.rslf_multi_depth1d_pile_u8(self._h, ptrs, stride, V, S, U, C_, float(dmin), float(dmax), int(dim_d), int(s_hat),
                                                C.byref(p), *hp, C.byref(st)), "rslf_multi_depth1d_pile_u8")
             self.scale_used = 255.0
         else:
             su = C.c_float()
             name = "rslf_multi_depth1d_pile_" + _SUFFIX[dt]
-            check(getattr(L, name)(self._h, ptrs, 0, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
+            check(getattr(L, name)(self._h, ptrs, stride, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
                                    int(dim_d), int(s_hat), C.byref(p), *hp, C.byref(st), C.byref(su)), name)
             self.scale_used = float(su.value)
         self.stats = st
@@ -683,7 +715,7 @@ class MultiDevice:
         """Depth2DComputer (constructor + run + getters) over this object's devices: the 2-D sweep cut into one block of
         scanlines per device, the neighbours' boundary rows exchanged by peer copy on every visit
         (rslf_multi_depth2d_run_f32 / _u8 / _u16).  Host EPIs in, numpy planes [S, V, U] out."""
-        keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
+        keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((S, V, U), np.float32), edge_mask=np.empty((S, V, U), np.uint8),
                    disp_confidence=np.empty((S, V, U), np.float32), depth=np.empty((S, V, U), np.float32),
                    rbar=np.empty((S, V, U, C_), np.float32), scan_mask=np.empty((S, V, U), np.uint8))
@@ -693,13 +725,13 @@ class MultiDevice:
         st = RslfStats()
         L = _lib.lib()
         if dt == np.uint8:
-            check(L.rslf_multi_depth2d_run_u8(self._h, ptrs, 0, V, S, U, C_, float(dmin), float(dmax), int(dim_d), C.byref(p), *hp,
+            check(L.rslf_multi_depth2d_run_u8(self._h, ptrs, stride, V, S, U, C_, float(dmin), float(dmax), int(dim_d), C.byref(p), *hp,
                                               C.byref(st)), "rslf_multi_depth2d_run_u8")
             self.scale_used = 255.0
         else:
             su = C.c_float()
             name = "rslf_multi_depth2d_run_" + _SUFFIX[dt]
-            check(getattr(L, name)(self._h, ptrs, 0, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
+            check(getattr(L, name)(self._h, ptrs, stride, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
                                    int(dim_d), C.byref(p), *hp, C.byref(st), C.byref(su)), name)
             self.scale_used = float(su.value)
         self.stats = st
@@ -709,13 +741,13 @@ class MultiDevice:
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
-        keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
+        keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
         require_no_line_confidence(parameters, "MultiDevice.fine_to_coarse")
         p = (parameters or Depth1DParameters()).to_c()
         st, nl = RslfStats(), C.c_int()
-        rest = (V, S, U, C_, 0, float(d_min), float(d_max), int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
+        rest = (V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
                 1 if accept_all_last_scale else 0, out_map.ctypes.data_as(C.c_void_p), out_valid.ctypes.data_as(C.c_void_p),
                 C.byref(nl), C.byref(st))
         if dt == np.uint16:   # ushort arithmetic through the pyramid
@@ -730,7 +762,7 @@ class MultiDevice:
                                 s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None) -> dict:
         """The same with the result planes left on `out_device` as CUDA tensors (float32 EPIs): every worker copies its
         rows there with a peer copy (rslf_multi_depth1d_pile_f32_dev)."""
-        keep, ptrs, _, V, S, U, C_ = host_epis(epis, np.float32)
+        keep, ptrs, _, V, S, U, C_, stride = host_epis(epis, np.float32, stride=True)
         dev = torch.device("cuda", out_device)
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         out = dict(edge_confidence=mk((V, U), torch.float32), edge_mask=mk((V, U), torch.uint8), disp_confidence=mk((V, U), torch.float32),
@@ -740,7 +772,7 @@ class MultiDevice:
         hp = [_ptr(out[k]) for k in ("edge_confidence", "edge_mask", "disp_confidence", "depth", "rbar", "depth_idx", "score", "depth_raw")]
         p = (parameters or Depth1DParameters()).to_c()
         st, su = RslfStats(), C.c_float()
-        check(_lib.lib().rslf_multi_depth1d_pile_f32_dev(self._h, ptrs, 0, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
+        check(_lib.lib().rslf_multi_depth1d_pile_f32_dev(self._h, ptrs, stride, V, S, U, C_, float(epi_scale_factor), float(dmin), float(dmax),
                                                          int(dim_d), int(s_hat), C.byref(p), int(out_device), *hp, C.byref(st), C.byref(su)),
               "rslf_multi_depth1d_pile_f32_dev")
         self.stats, self.scale_used = st, float(su.value)
@@ -1144,7 +1176,7 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
     (line_confidence is None in mode 0)."""
     ctx = ctx or default_context()
-    keep, ptrs, dt, V, S, U, C_ = host_epis(epis)
+    keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
     L = _lib.lib()
     out_map, out_valid = np.empty((S, V, U), np.float32), np.empty((S, V, U), np.uint8)
     p = (parameters or Depth1DParameters()).to_c()
@@ -1162,7 +1194,7 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                                edge_confidence=np.empty(shape, np.float32)))
         arr = lambda k: (C.c_void_p * P)(*[None if lv[k] is None else lv[k].ctypes.data for lv in levels])
         lo = _lib.RslfF2cLevelsOut(P, arr("depth"), arr("valid"), arr("line_confidence"), arr("edge_confidence"))
-    rest = (V, S, U, C_, 0, float(d_min), float(d_max), int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
+    rest = (V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d), float(epi_scale_factor), C.byref(p), int(max_pyr_depth),
             1 if accept_all_last_scale else 0, out_map.ctypes.data_as(C.c_void_p), out_valid.ctypes.data_as(C.c_void_p),
             C.byref(nl), C.byref(st), int(line_mode), C.byref(lo) if lo is not None else None)
     ctx.use_current_stream()

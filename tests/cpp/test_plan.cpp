@@ -188,6 +188,17 @@ static void test_host_copies()
           !use_pinned_gather(100, 10, 100, 0));
     CHECK(staging_chunk_rows(1 << 20, 1080) == 256 && staging_chunk_rows((size_t)1 << 30, 1080) == 1 && staging_chunk_rows(100, 7) == 7);
     CHECK(staging_chunk_rows(0, 7) == 7);
+    // a budget of the caller's (the "staging_kib" hook): below one EPI a pass still holds one scanline; a field that the
+    // chunk does not divide ends on a short pass (23 scanlines, 5 a pass: four passes of 5 and one of 3)
+    CHECK(staging_chunk_rows(2520, 23, 1024) == 1 && staging_chunk_rows(2520, 23, 2519) == 1 && staging_chunk_rows(2520, 23, 2520) == 1);
+    CHECK(staging_chunk_rows(2520, 23, 13 << 10) == 5 && staging_chunk_rows(3 * 2520, 23, 37 << 10) == 5);
+    {
+        const int chunk = staging_chunk_rows(2520, 23, 13 << 10);
+        int passes = 0, last = 0;
+        for (int v0 = 0; v0 < 23; v0 += chunk, passes++)
+            last = std::min(chunk, 23 - v0);
+        CHECK(passes == 5 && last == 3 && 23 % chunk != 0);
+    }
 }
 
 static void test_plane_layout()

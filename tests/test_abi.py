@@ -136,6 +136,58 @@ def test_host_epi_lists_reach_the_library_checked_and_converted():
     assert rs.host_epis([np.zeros((2, 4, 3), np.uint8)] * 2)[3:] == (2, 2, 4, 3)
 
 
+def test_host_rows_takes_padded_rows_in_place_and_copies_what_it_cannot():
+    """depth.host_rows, the one place where a host array becomes (pointer, row_stride_bytes): dense arrays go as stride 0 (as
+    they always did), a window of a wider parent goes up where it lies with the parent's stride, and whatever one stride
+    cannot describe -- mixed strides, a channel slice, a reversed or transposed view, another dtype -- goes as a dense copy."""
+    import numpy as np
+    from remotesensingproject_amd import depth as rs
+    for dt, C_ in ((np.float32, 1), (np.uint8, 3), (np.uint16, 1)):
+        shape = (5, 20) if C_ == 1 else (5, 20, C_)
+        parents = [np.arange(np.prod(shape), dtype=np.int64).reshape(shape).astype(dt) for _ in range(3)]
+        row_bytes = 7 * C_ * np.dtype(dt).itemsize
+        # dense in: stride 0, the arrays themselves
+        dense = [np.ascontiguousarray(p[:, 3:10]) for p in parents]
+        keep, ptrs, stride = rs.host_rows(dense, dt)
+        assert stride == 0 and all(k is d for k, d in zip(keep, dense)) and list(ptrs) == [d.ctypes.data for d in dense]
+        # a padded window: the same pointer, the parent's stride
+        views = [p[:, 3:10] for p in parents]
+        keep, ptrs, stride = rs.host_rows(views, dt)
+        assert stride == parents[0].strides[0] != row_bytes
+        assert list(ptrs) == [v.ctypes.data for v in views] and all(k is v for k, v in zip(keep, views))
+        # host_epis hands the same on
+        out = rs.host_epis(views, stride=True)
+        assert out[2] == dt and out[3:] == (3, 5, 7, C_, parents[0].strides[0]) and list(out[1]) == list(ptrs)
+        # ... and without the stride, to a caller that passes 0, dense copies
+        out = rs.host_epis(views)
+        assert len(out) == 7 and all(k.flags.c_contiguous and np.array_equal(k, v) for k, v in zip(out[0], views))
+        assert list(out[1]) == [k.ctypes.data for k in out[0]] and rs.host_epis(dense, stride=True)[7] == 0
+        # a window as wide as its parent is dense
+        assert rs.host_rows([p[:, :] for p in parents], dt)[2] == 0
+        # mixed strides (a clone among windows): everything dense, values kept
+        mixed = [views[0], dense[1], views[2]]
+        keep, ptrs, stride = rs.host_rows(mixed, dt)
+        assert stride == 0 and all(k.flags.c_contiguous for k in keep) and keep[1] is dense[1]
+        assert all(np.array_equal(k, m) for k, m in zip(keep, mixed)) and list(ptrs) == [k.ctypes.data for k in keep]
+        wider = np.zeros((5, 31) + shape[2:], dt)
+        assert rs.host_rows([views[0], wider[:, 3:10]], dt)[2] == 0
+        # views one stride cannot describe, and another dtype
+        for odd in ([v[:, ::-1] for v in views], [v[::-1] for v in views], [v[:, ::2] for v in views],
+                    [v.astype(np.float64) for v in views]):
+            keep, ptrs, stride = rs.host_rows(odd, dt)
+            assert stride == 0 and all(k.flags.c_contiguous and k.dtype == dt for k in keep)
+            assert all(np.array_equal(k, o) for k, o in zip(keep, odd))
+    rgb = [np.arange(5 * 20 * 3, dtype=np.float32).reshape(5, 20, 3) for _ in range(2)]
+    for sliced in ([p[:, 3:10, 1] for p in rgb], [p[:, 3:10, :1] for p in rgb], [p[:, 3:10, :2] for p in rgb]):   # channel slices
+        keep, ptrs, stride = rs.host_rows(sliced, np.float32)
+        assert stride == 0 and all(k.flags.c_contiguous for k in keep) and all(np.array_equal(k, s) for k, s in zip(keep, sliced))
+    # one row: no stride to speak of; lists (not arrays) are converted
+    assert rs.host_rows([p[:1, 3:10] for p in rgb], np.float32)[2] == 0
+    assert rs.host_rows([[[1, 2], [3, 4]]], np.uint8)[2] == 0
+    with pytest.raises(ValueError):
+        rs.host_rows([rgb[0][:, 3:10], rgb[1][:, 3:9]], np.float32)
+
+
 def test_product_does_not_import_the_oracle():
     """oracle/ is test infrastructure: nothing under the package or include/ may reference it."""
     bad = []

@@ -47,17 +47,17 @@ def assert_pile_parity(got: dict, ref, *, exact_float: bool = True, label: str =
 def native_fine_to_coarse(epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0, max_pyr_depth: int = -1,
                           accept_all_last_scale: bool = True):
     """The one-context native level loop (rslf_fine_to_coarse_run_host) on the default context of cuda:0, from a list of
-    float32 or uint8 host EPIs: (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels, rslf_stats)."""
+    float32 or uint8 host EPIs (padded rows go up in place, depth.host_rows): (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels, rslf_stats)."""
     import ctypes as C
     from remotesensingproject_amd import _lib
     from remotesensingproject_amd import depth as rs
-    keep, ptrs, dt, V, S, U, C_ = rs.host_epis(epis)
+    keep, ptrs, dt, V, S, U, C_, stride = rs.host_epis(epis, stride=True)
     assert dt in (np.float32, np.uint8), dt
     out_map, out_valid = np.empty((S, V, U), np.float32), np.empty((S, V, U), np.uint8)
     p = rs.Depth1DParameters().to_c()
     st, nl = _lib.RslfStats(), C.c_int()
     _lib.check(_lib.lib().rslf_fine_to_coarse_run_host(
-        rs.default_context(0)._h, ptrs, int(dt == np.uint8), V, S, U, C_, 0, float(d_min), float(d_max), int(dim_d),
+        rs.default_context(0)._h, ptrs, int(dt == np.uint8), V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
         float(epi_scale_factor), C.byref(p), int(max_pyr_depth), int(accept_all_last_scale), out_map.ctypes.data_as(C.c_void_p),
         out_valid.ctypes.data_as(C.c_void_p), C.byref(nl), C.byref(st)), "rslf_fine_to_coarse_run_host")
     return out_map, out_valid, int(nl.value), st
