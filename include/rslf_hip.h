@@ -158,7 +158,8 @@ int rslf_ctx_synchronize(rslf_ctx* ctx);
 int rslf_ctx_set_debug(rslf_ctx* ctx, const char* key, int value);
 /* Fault injection for the tests of the error paths (process-wide, off unless armed): the next `count` visits of `site`
  * fail as if the runtime had -- "worker": a device worker of rslf_multi_* throws std::runtime_error; "thread_create":
- * std::thread cannot be started (the work then runs on the calling thread); "alloc": std::bad_alloc in a worker.
+ * std::thread cannot be started (the work then runs on the calling thread); "alloc": std::bad_alloc in a worker; "sweep":
+ * rslf_multi_depth2d_run_* throws std::runtime_error once every device's sweep is open, before the first visit is queued.
  * The entry point reports a status; nothing is left running, nothing leaks.  count = 0 disarms. */
 int rslf_debug_inject(const char* site, int count);
 

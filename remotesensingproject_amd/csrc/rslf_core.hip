@@ -37,7 +37,7 @@ extern "C" int rslf_debug_inject(const char* site, int count) RSLF_API_TRY
 {
     if (!site || count < 0)
         return fail(RSLF_ERR_INVALID_ARG, "rslf_debug_inject: bad argument");
-    static const char* const names[kInjectSites] = {"worker", "thread_create", "alloc"};
+    static const char* const names[kInjectSites] = {"worker", "thread_create", "alloc", "sweep"};
     for (int i = 0; i < kInjectSites; i++)
         if (strcmp(site, names[i]) == 0) {
             g_inject[i].store(count, std::memory_order_relaxed);

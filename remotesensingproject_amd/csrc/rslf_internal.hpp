@@ -12,6 +12,10 @@
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
 //   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
+//
+// Two rules of the multi-device paths: they never write into a rslf_volume they did not create (a chunk of another height
+// is a local non-owning copy of the volume object, rslf_multi.hip's Worker::view), and a context's stream is changed only
+// through StreamScope (below), which puts it back when its scope ends.
 #pragma once
 
 #include "../../include/rslf_hip.h"
@@ -50,7 +54,7 @@ inline int fail(int code, const char* fmt, ...)
 
 // Testing hook (rslf_debug_inject, include/rslf_hip.h): the named site throws / fails the next `count` times it is
 // reached.  One relaxed atomic load per site visit; sites sit on host control paths only, never in a launch loop.
-enum InjectSite { kInjectWorker = 0, kInjectThreadCreate = 1, kInjectAlloc = 2, kInjectSites = 3 };
+enum InjectSite { kInjectWorker = 0, kInjectThreadCreate = 1, kInjectAlloc = 2, kInjectSweep = 3, kInjectSites = 4 };
 bool inject_hit(InjectSite site);   // true (and one count consumed) when the site should fail now
 
 }  // namespace rslf
@@ -291,8 +295,7 @@ struct rslf_multi {
         rslf_ctx* ctx = nullptr;
         hipStream_t s_up = nullptr, s_comp = nullptr, s_down = nullptr;
         hipEvent_t done[2] = {nullptr, nullptr};
-        rslf_volume* vol[2] = {nullptr, nullptr};
-        int vol_rows[2] = {0, 0}, vol_S = 0, vol_U = 0, vol_C = 0;
+        rslf_volume* vol[2] = {nullptr, nullptr};   // as tall as the tallest chunk so far; never written once made
         rslf::DeviceBuf planes[2];           // result planes of the chunk being computed and of the one being collected
         rslf::PinnedBuf pin[2];              // pinned host staging for EPIs scattered over the heap (Vec<Mat>)
         rslf::DeviceBuf arena;               // the sweep forms' planes, kept from call to call (and from level to level)
@@ -305,6 +308,17 @@ struct rslf_multi {
 };
 
 namespace rslf {
+
+// The one way the library changes a context's stream (rslf_ctx_set_stream is the caller's): for a scope, put back when it
+// ends, however it ends.
+struct StreamScope {
+    StreamScope(rslf_ctx* ctx_, hipStream_t stream) : ctx(ctx_), saved(ctx_->stream) { ctx->stream = stream; }
+    ~StreamScope() { ctx->stream = saved; }
+    StreamScope(const StreamScope&) = delete;
+    StreamScope& operator=(const StreamScope&) = delete;
+    rslf_ctx* const ctx;
+    const hipStream_t saved;
+};
 
 inline VolView view_of(const rslf_volume* vol)
 {

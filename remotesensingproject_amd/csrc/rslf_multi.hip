@@ -164,237 +164,185 @@ struct MultiJob {
     float dmin, dmax;
     int dim_d, s_hat;
     const rslf_params* p;
-    float* h_Ce;
-    uint8_t* h_mask;
-    float* h_Cd;
-    float* h_depth;
-    float* h_rbar;
-    int32_t* h_idx;
-    float* h_score;
-    float* h_raw;
+    plan::PilePlanes out;   // the caller's [V][U] planes (a NULL one is not wanted)
     int halo;
     int out_device;   // -1: the result planes are host memory; >= 0: they live on this device (peer copies)
 };
 
 typedef plan::RowBlock Chunk;   // owned rows [a, b) of the whole field, computed rows [lo, hi) = owned + halo, clipped
 
-struct PlanePtrs {
-    float *Ce, *Cd, *depth, *raw, *score, *rbar;
-    int32_t* idx;
-    uint8_t* mask;
+// One device's share of one call, chunk by chunk: what the steps of the pipeline share.
+struct Worker {
+    rslf_multi::Dev& d;
+    const MultiJob& j;
+    std::vector<Chunk> chunks;
+    // non-owning: the slab of d.vol[k] as a volume of the height of the chunk it holds (rows beyond are simply unused), with
+    // that chunk's value range -- written by upload(k), read by compute(k); the device's own volumes are never written
+    rslf_volume view[2];
+    size_t row_bytes = 0, stride = 0, epi_bytes = 0;   // of the host EPIs
+    int pin_threads = 1;
+    size_t counts_at = 0;      // where a chunk's copy of the per-scanline pixel counts sits, behind its planes
+    std::vector<int> counts;   // ... and where download() reads it to
+    long long scanned = 0;
+    int kernel = 0, spad = 0;
+
+    int prepare(int r0, int r1, int chunk_rows);
+    int upload(int k);
+    int compute(int k);
+    int download(int k);
+    int run();
 };
 
-PlanePtrs carve(char* blk, size_t n, int C)
+// The chunk plan of rows [r0, r1) and all the memory its chunks take turns in, before the pipeline starts.
+int Worker::prepare(int r0, int r1, int chunk_rows)
 {
-    const plan::PlaneLayout o = plan::plane_layout(n, C, 0);
-    PlanePtrs q;
-    q.Ce = (float*)(blk + o.Ce);
-    q.Cd = (float*)(blk + o.Cd);
-    q.depth = (float*)(blk + o.depth);
-    q.raw = (float*)(blk + o.raw);
-    q.score = (float*)(blk + o.score);
-    q.rbar = (float*)(blk + o.rbar);
-    q.idx = (int32_t*)(blk + o.idx);
-    q.mask = (uint8_t*)(blk + o.mask);
-    return q;
-}
-
-// One device's share: rows [r0, r1) of the field, chunk by chunk.  Returns an rslf status; `err` receives the message.
-int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chunk_rows, long long* scanned, int* kernel,
-                 int* spad, std::string* err)
-{
-#define MW_FAIL(rc_)                  \
-    do {                              \
-        *err = last_error_buffer();                 \
-        return (rc_);                 \
-    } while (0)
-#define MW_HIP(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            (void)fail(RSLF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            MW_FAIL(RSLF_ERR_HIP);                                                                          \
-        }                                                                                                   \
-    } while (0)
-    *scanned = 0;
-    if (r1 <= r0)
-        return RSLF_OK;
     rslf_ctx* ctx = d.ctx;
-    MW_HIP(hipSetDevice(ctx->device));
+    HIP_TRY(hipSetDevice(ctx->device));
     // Do the EPIs follow one another in host memory (a stacked array) or are they scattered over the heap (a Vec<Mat>)?
-    const size_t in_row_bytes = (size_t)j.U * j.C * elem_bytes(j.elem);
-    const size_t in_epi_bytes = in_row_bytes * j.S;
-    const bool scattered = plan::epis_scattered(j.h_epis, r0, r1, j.row_stride_bytes ? j.row_stride_bytes : in_row_bytes,
-                                                in_row_bytes, in_epi_bytes);
+    row_bytes = (size_t)j.U * j.C * elem_bytes(j.elem);
+    stride = j.row_stride_bytes ? j.row_stride_bytes : row_bytes;
+    epi_bytes = row_bytes * j.S;
+    const bool scattered = plan::epis_scattered(j.h_epis, r0, r1, stride, row_bytes, epi_bytes);
     // Chunks (plan::chunk_plan).  A given size: uniform.  Automatic: a short first chunk so that the kernels start early
     // (its upload is the one copy nothing hides), then two large ones (stacked input; scattered input, which is gathered
     // into pinned memory first, takes a middling second chunk and pieces of about V/3.5) -- a chunk's scan is a grid of
     // its own, and a grid of 5.4 rounds of workgroups pays for 6 (eight equal chunks of a 1080-row field ran 16 % longer
     // than one launch over the whole field; measured with rocprofv3 on the host-in / host-out path).
-    const std::vector<Chunk> chunks = plan::chunk_plan(r0, r1, j.V, j.halo, chunk_rows, scattered);
+    chunks = plan::chunk_plan(r0, r1, j.V, j.halo, chunk_rows, scattered);
     const int max_rows = plan::max_held_rows(chunks);
     // two volumes and two sets of result planes, kept from call to call while the shape allows
-    for (int k = 0; k < 2; k++) {
-        if (d.vol[k] && (d.vol_rows[k] < max_rows || d.vol_S != j.S || d.vol_U != j.U || d.vol_C != j.C)) {
-            (void)rslf_volume_destroy(d.vol[k]);
-            d.vol[k] = nullptr;
+    for (rslf_volume*& vol : d.vol)   // (both go before either comes back: the old pair and a new one need not fit together)
+        if (vol && (vol->V < max_rows || vol->S != j.S || vol->U != j.U || vol->C != j.C)) {
+            (void)rslf_volume_destroy(vol);
+            vol = nullptr;
         }
-    }
-    d.vol_S = j.S, d.vol_U = j.U, d.vol_C = j.C;
     for (int k = 0; k < 2; k++) {
-        if (!d.vol[k]) {
-            int rc = rslf_volume_create(ctx, max_rows, j.S, j.U, j.C, &d.vol[k]);
+        rslf_volume*& vol = d.vol[k];
+        if (!vol) {
+            int rc = rslf_volume_create(ctx, max_rows, j.S, j.U, j.C, &vol);
             if (rc)
-                MW_FAIL(rc);
-            d.vol_rows[k] = max_rows;
+                return rc;
         }
+        view[k] = *vol;
     }
-    const size_t n_max = (size_t)max_rows * j.U;
     // result planes of one chunk + a copy of the scan's per-scanline pixel counts (the context's own array is
     // rewritten by the next chunk's kernels, which are already queued when this chunk is collected)
-    const plan::PlaneLayout lay = plan::plane_layout(n_max, j.C, max_rows);
-    const size_t plane_bytes = lay.counts, bytes = lay.bytes;
+    const plan::PlaneLayout lay = plan::plane_layout((size_t)max_rows * j.U, j.C, max_rows);
+    counts_at = lay.counts;
     for (int k = 0; k < 2; k++)
-        MW_HIP(hip_err(d.planes[k].reserve(bytes)));
-    std::vector<int> counts((size_t)max_rows);
+        HIP_TRY(hip_err(d.planes[k].reserve(lay.bytes)));
+    counts.resize((size_t)max_rows);
     // The scan's scratch -- pixel lists, and the records of grouped launches, whose count differs from chunk to chunk (a
     // short first chunk takes more hypothesis groups than the large ones) -- sized ONCE for every chunk of the plan before
     // the pipeline starts: a regrow in the middle is a hipFree + hipMalloc while the previous chunk's kernels are in
     // flight, safe only because hipFree synchronises the device, and it stalls the upload / compute overlap.
-    {
-        std::vector<int> rows_of;
-        for (const Chunk& c : chunks)
-            rows_of.push_back(c.hi - c.lo);
-        int rc = scan_presize(ctx, j.S, j.U, j.C, j.dim_d, j.p, rows_of.data(), (int)rows_of.size());
-        if (rc)
-            MW_FAIL(rc);
-    }
+    std::vector<int> rows_of;
+    for (const Chunk& c : chunks)
+        rows_of.push_back(c.hi - c.lo);
+    int rc = scan_presize(ctx, j.S, j.U, j.C, j.dim_d, j.p, rows_of.data(), (int)rows_of.size());
+    if (rc)
+        return rc;
     // pinned staging for scattered EPIs
-    const int pin_threads = std::max(1, std::min(8, (int)std::thread::hardware_concurrency() / 2));
+    pin_threads = std::max(1, std::min(8, (int)std::thread::hardware_concurrency() / 2));
     for (int k = 0; scattered && k < 2; k++)
-        MW_HIP(hip_err(d.pin[k].reserve((size_t)max_rows * in_epi_bytes)));
+        HIP_TRY(hip_err(d.pin[k].reserve((size_t)max_rows * epi_bytes)));
+    return RSLF_OK;
+}
 
-    // a volume object of the chunk's height over the (larger or equal) allocation: rows beyond are simply unused
-    auto upload = [&](int k) -> int {
-        const Chunk& c = chunks[k];
-        rslf_volume* vol = d.vol[k & 1];
-        vol->V = c.hi - c.lo;
-        vol->bytes = (size_t)vol->V * vol->S * vol->C * vol->pitch * sizeof(float);
-        ctx->stream = d.s_up;
-        // EPIs that follow one another in host memory go up as they are: one pageable copy per run, at the link's rate.
-        // EPIs scattered over the heap (a Vec<Mat>) would be one pageable copy each, and the runtime stages those through
-        // its own bounce buffer on the calling thread at ~10 GB/s -- slower than the kernels consume them.  They are
-        // gathered into a pinned buffer by a few host threads first (dense rows; ~25 GB/s per thread) and go up from there.
-        const size_t row_bytes = (size_t)j.U * j.C * elem_bytes(j.elem);
-        const size_t stride = j.row_stride_bytes ? j.row_stride_bytes : row_bytes;
-        const size_t epi_bytes = row_bytes * j.S;
-        const int rows = c.hi - c.lo;
-        const int runs = plan::count_runs(j.h_epis + c.lo, rows, stride, row_bytes, epi_bytes);
-        const void* const* src = j.h_epis + c.lo;
-        std::vector<const void*> staged;
-        size_t src_stride = j.row_stride_bytes;
-        // (the pinned buffer is sized from the scattered-ness of the device's OWN rows; a chunk's halo rows can add breaks
-        // of their own, so the buffer must also be seen to hold this chunk -- else the direct per-run copies below)
-        if (plan::use_pinned_gather(runs, rows, epi_bytes, d.pin[k & 1].capacity())) {
-            char* pin = d.pin[k & 1].as<char>();
-            const int nt = std::max(1, std::min(rows, pin_threads));
-            for (int i = 0; i < rows; i++)
-                if (j.h_epis[c.lo + i] == nullptr)
-                    return fail(RSLF_ERR_INVALID_ARG, "an EPI pointer is NULL");
-            {
-                JoinGuard pool;   // joined when this scope ends, however it ends
-                for (int t = 0; t < nt; t++)
-                    pool.run([&, t] {
-                        int i0, i1;
-                        plan::split_range(rows, t, nt, &i0, &i1);
-                        for (int i = i0; i < i1; i++) {
-                            const char* e = (const char*)j.h_epis[c.lo + i];
-                            char* o = pin + (size_t)i * epi_bytes;
-                            if (stride == row_bytes)
-                                memcpy(o, e, epi_bytes);
-                            else
-                                for (int r = 0; r < j.S; r++)
-                                    memcpy(o + (size_t)r * row_bytes, e + (size_t)r * stride, row_bytes);
-                        }
-                    });
-            }
-            staged.resize((size_t)rows);
-            for (int i = 0; i < rows; i++)
-                staged[(size_t)i] = pin + (size_t)i * epi_bytes;
-            src = staged.data();
-            src_stride = row_bytes;
-        }
-        const int rc = upload_host_elem(vol, j.elem, src, src_stride, false, scale_of(j.scale_arg));
-        return rc;   // upload_host ends with a synchronisation of its stream (minmax_end): the pinned buffer is free again
-    };
-    auto compute = [&](int k) -> int {
-        const Chunk& c = chunks[k];
-        const size_t n = (size_t)(c.hi - c.lo) * j.U;
-        const PlanePtrs q = carve(d.planes[k & 1].as<char>(), n, j.C);
-        ctx->stream = d.s_comp;
-        int rc = rslf_depth1d_pile_run(ctx, d.vol[k & 1], j.dmin, j.dmax, j.dim_d, j.s_hat, j.p, q.Ce, q.mask, q.Cd, q.depth, q.rbar,
-                                       q.idx, q.score, q.raw, nullptr);
-        if (rc)
-            return rc;
-        *kernel = ctx->last_kernel;
-        *spad = ctx->last_spad;
-        hipError_t e = hipMemcpyAsync(d.planes[k & 1].as<char>() + plane_bytes, ctx->scratch.count.get(), (size_t)(c.hi - c.lo) * sizeof(int),
-                                      hipMemcpyDeviceToDevice, d.s_comp);
-        if (e == hipSuccess)
-            e = hipEventRecord(d.done[k & 1], d.s_comp);
-        return e == hipSuccess ? RSLF_OK : fail(RSLF_ERR_HIP, "queueing the chunk's completion failed: %s", hipGetErrorString(e));
-    };
-    auto download = [&](int k) -> int {
-        const Chunk& c = chunks[k];
-        const int rows = c.hi - c.lo;
-        const size_t n = (size_t)rows * j.U;
-        const PlanePtrs q = carve(d.planes[k & 1].as<char>(), n, j.C);
-        const size_t off = (size_t)(c.a - c.lo) * j.U, cnt = (size_t)(c.b - c.a) * j.U, dst = (size_t)c.a * j.U;
-        hipError_t e = hipStreamWaitEvent(d.s_down, d.done[k & 1], 0);
-        auto pull = [&](void* h, const void* dv, size_t esz, size_t mult) {
-            if (e != hipSuccess || !h)
-                return;
-            if (j.out_device < 0)
-                e = hipMemcpyAsync((char*)h + dst * esz * mult, (const char*)dv + off * esz * mult, cnt * esz * mult, hipMemcpyDeviceToHost,
-                                   d.s_down);
-            else   // device-out: each worker's rows go straight to their place in the planes on the output device (xGMI peer copy)
-                e = multi_copy(nullptr, (char*)h + dst * esz * mult, j.out_device, (const char*)dv + off * esz * mult, ctx->device,
-                               cnt * esz * mult, d.s_down);
-        };
-        pull(j.h_Ce, q.Ce, 4, 1);
-        pull(j.h_mask, q.mask, 1, 1);
-        pull(j.h_Cd, q.Cd, 4, 1);
-        pull(j.h_depth, q.depth, 4, 1);
-        pull(j.h_rbar, q.rbar, 4, (size_t)j.C);
-        pull(j.h_idx, q.idx, 4, 1);
-        pull(j.h_score, q.score, 4, 1);
-        pull(j.h_raw, q.raw, 4, 1);
-        // pixels scanned on the owned rows: the per-scanline counts of the scan's pixel lists
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(counts.data(), d.planes[k & 1].as<char>() + plane_bytes, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, d.s_down);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(d.s_down);
-        if (e != hipSuccess)
-            return fail(RSLF_ERR_HIP, "result download failed: %s", hipGetErrorString(e));
-        for (int r = c.a - c.lo; r < c.b - c.lo; r++)
-            *scanned += counts[(size_t)r];
-        return RSLF_OK;
-    };
-
-    hipStream_t saved = ctx->stream;
-    struct Restore {   // on every path out, exceptions included: the context's stream and the volumes' full height
-        rslf_multi::Dev& d;
-        hipStream_t saved;
-        ~Restore()
+int Worker::upload(int k)
+{
+    const Chunk& c = chunks[k];
+    const int rows = c.hi - c.lo;
+    rslf_volume& vol = view[k & 1];
+    vol.V = rows;
+    vol.bytes = (size_t)rows * vol.S * vol.C * vol.pitch * sizeof(float);
+    StreamScope on(d.ctx, d.s_up);
+    // EPIs that follow one another in host memory go up as they are: one pageable copy per run, at the link's rate.
+    // EPIs scattered over the heap (a Vec<Mat>) would be one pageable copy each, and the runtime stages those through
+    // its own bounce buffer on the calling thread at ~10 GB/s -- slower than the kernels consume them.  They are
+    // gathered into a pinned buffer by a few host threads first (dense rows; ~25 GB/s per thread) and go up from there.
+    const void* const* epis = j.h_epis + c.lo;
+    const void* const* src = epis;
+    size_t src_stride = j.row_stride_bytes;
+    std::vector<const void*> staged;
+    const int runs = plan::count_runs(epis, rows, stride, row_bytes, epi_bytes);
+    // (the pinned buffer is sized from the scattered-ness of the device's OWN rows; a chunk's halo rows can add breaks
+    // of their own, so the buffer must also be seen to hold this chunk -- else the direct per-run copies below)
+    if (plan::use_pinned_gather(runs, rows, epi_bytes, d.pin[k & 1].capacity())) {
+        char* pin = d.pin[k & 1].as<char>();
+        const int nt = std::max(1, std::min(rows, pin_threads));
+        for (int i = 0; i < rows; i++)
+            if (epis[i] == nullptr)
+                return fail(RSLF_ERR_INVALID_ARG, "an EPI pointer is NULL");
         {
-            d.ctx->stream = saved;
-            for (int k = 0; k < 2; k++)
-                if (d.vol[k]) {
-                    d.vol[k]->V = d.vol_rows[k];
-                    d.vol[k]->bytes = (size_t)d.vol[k]->V * d.vol[k]->S * d.vol[k]->C * d.vol[k]->pitch * sizeof(float);
-                }
+            JoinGuard pool;   // joined when this scope ends, however it ends
+            for (int t = 0; t < nt; t++)
+                pool.run([&, t] {
+                    int i0, i1;
+                    plan::split_range(rows, t, nt, &i0, &i1);
+                    plan::gather_epis(pin, epis, i0, i1, j.S, row_bytes, stride);
+                });
         }
-    } restore{d, saved};
+        staged.resize((size_t)rows);
+        for (int i = 0; i < rows; i++)
+            staged[(size_t)i] = pin + (size_t)i * epi_bytes;
+        src = staged.data();
+        src_stride = row_bytes;
+    }
+    // upload_host ends with a synchronisation of its stream (minmax_end): the pinned buffer is free again
+    return upload_host_elem(&vol, j.elem, src, src_stride, false, scale_of(j.scale_arg));
+}
+
+int Worker::compute(int k)
+{
+    const Chunk& c = chunks[k];
+    rslf_ctx* ctx = d.ctx;
+    char* blk = d.planes[k & 1].as<char>();
+    const plan::PilePlanes q = plan::carve(blk, (size_t)(c.hi - c.lo) * j.U, j.C);
+    StreamScope on(ctx, d.s_comp);
+    int rc = rslf_depth1d_pile_run(ctx, &view[k & 1], j.dmin, j.dmax, j.dim_d, j.s_hat, j.p, q.Ce, q.mask, q.Cd, q.depth, q.rbar, q.idx,
+                                   q.score, q.raw, nullptr);
+    if (rc)
+        return rc;
+    kernel = ctx->last_kernel;
+    spad = ctx->last_spad;
+    HIP_TRY(hipMemcpyAsync(blk + counts_at, ctx->scratch.count.get(), (size_t)(c.hi - c.lo) * sizeof(int), hipMemcpyDeviceToDevice, d.s_comp));
+    HIP_TRY(hipEventRecord(d.done[k & 1], d.s_comp));
+    return RSLF_OK;
+}
+
+int Worker::download(int k)
+{
+    const Chunk& c = chunks[k];
+    const int rows = c.hi - c.lo;
+    char* blk = d.planes[k & 1].as<char>();
+    const plan::PilePlanes q = plan::carve(blk, (size_t)rows * j.U, j.C);
+    const size_t off = (size_t)(c.a - c.lo) * j.U, cnt = (size_t)(c.b - c.a) * j.U, dst = (size_t)c.a * j.U;
+    HIP_TRY(hipStreamWaitEvent(d.s_down, d.done[k & 1], 0));
+    // the chunk's own rows of every plane the caller wants, straight to their place in the caller's planes: host memory, or
+    // (device-out) the planes on the output device, by xGMI peer copy
+    int rc = plan::for_each_plane(j.out, q, j.C, [&](void* h, const void* dv, size_t bpp) -> int {
+        char* to = (char*)h + dst * bpp;
+        const char* from = (const char*)dv + off * bpp;
+        if (j.out_device < 0)
+            HIP_TRY(hipMemcpyAsync(to, from, cnt * bpp, hipMemcpyDeviceToHost, d.s_down));
+        else
+            HIP_TRY(multi_copy(nullptr, to, j.out_device, from, d.ctx->device, cnt * bpp, d.s_down));
+        return RSLF_OK;
+    });
+    if (rc)
+        return rc;
+    // pixels scanned on the owned rows: the per-scanline counts of the scan's pixel lists
+    HIP_TRY(hipMemcpyAsync(counts.data(), blk + counts_at, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, d.s_down));
+    HIP_TRY(hipStreamSynchronize(d.s_down));
+    for (int r = c.a - c.lo; r < c.b - c.lo; r++)
+        scanned += counts[(size_t)r];
+    return RSLF_OK;
+}
+
+// The pipeline: per chunk an upload, the kernels and a download, chunk k+1 fed before chunk k is collected.
+int Worker::run()
+{
     struct Drain {     // an exception between queueing and collecting must not leave kernels writing freed planes
         bool armed = true;
         ~Drain()
@@ -420,13 +368,25 @@ int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chun
         if (rc == RSLF_OK)
             rc = download(k);              // waits for chunk k's kernels; chunk k+1 runs meanwhile
     }
-    if (rc != RSLF_OK)
-        *err = last_error_buffer();
-    else
+    if (rc == RSLF_OK)
         drain.armed = false;   // every chunk has been collected: nothing is in flight
     return rc;
-#undef MW_FAIL
-#undef MW_HIP
+}
+
+// One device's share: rows [r0, r1) of the field.  Returns an rslf status, its text in this thread's last_error_buffer().
+int multi_worker(rslf_multi::Dev& d, const MultiJob& j, int r0, int r1, int chunk_rows, long long* scanned, int* kernel, int* spad)
+{
+    *scanned = 0;
+    if (r1 <= r0)
+        return RSLF_OK;
+    Worker w{d, j};
+    int rc = w.prepare(r0, r1, chunk_rows);
+    if (rc == RSLF_OK)
+        rc = w.run();
+    *scanned = w.scanned;
+    *kernel = w.kernel;
+    *spad = w.spad;
+    return rc;
 }
 
 int multi_run(rslf_multi* m, MultiJob j, rslf_stats* stats)
@@ -455,11 +415,15 @@ int multi_run(rslf_multi* m, MultiJob j, rslf_stats* stats)
             // chunks: enough of them to overlap the copies with the kernels, large enough to keep the halo's share small
             const int chunk = m->chunk_rows > 0 ? std::max(1, std::min(m->chunk_rows, std::max(1, blk.b - blk.a))) : 0;   // 0: the graded plan
             pool.run([&, i, blk, chunk] {
-                // nothing may leave a thread function by exception: a status and its text instead
+                // nothing may leave a thread function by exception: a status and its text instead (the text of a status
+                // is thread-local, so it is copied here, on the worker's thread)
                 rcs[(size_t)i] = guarded_status(
                     [&] {
-                        return multi_worker(m->devs[(size_t)i], j, blk.a, blk.b, chunk, &scanned[(size_t)i], &kern[(size_t)i],
-                                            &spads[(size_t)i], &errs[(size_t)i]);
+                        const int rc_i = multi_worker(m->devs[(size_t)i], j, blk.a, blk.b, chunk, &scanned[(size_t)i], &kern[(size_t)i],
+                                                      &spads[(size_t)i]);
+                        if (rc_i != RSLF_OK)
+                            errs[(size_t)i] = last_error_buffer();
+                        return rc_i;
                     },
                     &errs[(size_t)i]);
             });
@@ -502,8 +466,10 @@ static int multi_pile(rslf_multi* m, Elem e, const void* const* h_epis, size_t r
     epi_scale_factor = resolve_scale_factor(e, h_epis, V, S, stride, row_elems, epi_scale_factor, true);
     if (scale_used)
         *scale_used = epi_scale_factor;
-    MultiJob j = {h_epis, e, stride, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat, p,
-                  h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu, h_score_vu, h_depth_raw_vu, 0, out_device};
+    plan::PilePlanes out;
+    out.Ce = h_Ce_vu, out.mask = h_Ce_mask_vu, out.Cd = h_Cd_vu, out.depth = h_depth_vu, out.rbar = h_rbar_vu, out.idx = h_idx_vu;
+    out.score = h_score_vu, out.raw = h_depth_raw_vu;
+    MultiJob j = {h_epis, e, stride, V, S, U, C, epi_scale_factor, dmin, dmax, dim_d, s_hat, p, out, 0, out_device};
     return multi_run(m, j, stats);
 }
 

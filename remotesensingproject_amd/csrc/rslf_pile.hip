@@ -646,36 +646,22 @@ extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol,
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n = (size_t)vol->V * vol->U;
-    // one device block: Ce, Cd, depth, raw, score | rbar (n*C) | idx | mask
-    const size_t f_planes = 5 + (size_t)vol->C;
-    const size_t bytes = n * (f_planes * sizeof(float) + sizeof(int32_t) + 1);
+    const size_t bytes = plan::plane_layout(n, vol->C, 0).bytes;   // one device block for the eight planes
     DevBuf blk;   // (freed when the call returns, however it returns)
     hipError_t e = blk.alloc(bytes);
     if (e != hipSuccess)
         return fail(RSLF_ERR_ALLOC, "hipMalloc(%zu) for result planes failed: %s", bytes, hipGetErrorString(e));
-    float* d_Ce = blk.as<float>();
-    float* d_Cd = d_Ce + n;
-    float* d_depth = d_Cd + n;
-    float* d_raw = d_depth + n;
-    float* d_score = d_raw + n;
-    float* d_rbar = d_score + n;
-    int32_t* d_idx = (int32_t*)(d_rbar + n * vol->C);
-    uint8_t* d_mask = (uint8_t*)(d_idx + n);
-    int rc = rslf_depth1d_pile_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, d_Ce, d_mask, d_Cd, d_depth, d_rbar, d_idx, d_score,
-                                   d_raw, nullptr);
+    const plan::PilePlanes q = plan::carve(blk.as<char>(), n, vol->C);
+    plan::PilePlanes out;
+    out.Ce = h_Ce_vu, out.mask = h_Ce_mask_vu, out.Cd = h_Cd_vu, out.depth = h_depth_vu, out.rbar = h_rbar_vu, out.idx = h_idx_vu;
+    out.score = h_score_vu, out.raw = h_depth_raw_vu;
+    int rc = rslf_depth1d_pile_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, q.Ce, q.mask, q.Cd, q.depth, q.rbar, q.idx, q.score, q.raw,
+                                   nullptr);
     hipStream_t st = ctx->stream;
-    auto pull = [&](void* h, const void* d, size_t b) -> hipError_t {
-        return h ? hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, st) : hipSuccess;
-    };
     if (rc == RSLF_OK) {
-        hipError_t ce = pull(h_Ce_vu, d_Ce, n * 4);
-        if (ce == hipSuccess) ce = pull(h_Ce_mask_vu, d_mask, n);
-        if (ce == hipSuccess) ce = pull(h_Cd_vu, d_Cd, n * 4);
-        if (ce == hipSuccess) ce = pull(h_depth_vu, d_depth, n * 4);
-        if (ce == hipSuccess) ce = pull(h_rbar_vu, d_rbar, n * 4 * vol->C);
-        if (ce == hipSuccess) ce = pull(h_idx_vu, d_idx, n * 4);
-        if (ce == hipSuccess) ce = pull(h_score_vu, d_score, n * 4);
-        if (ce == hipSuccess) ce = pull(h_depth_raw_vu, d_raw, n * 4);
+        hipError_t ce = (hipError_t)plan::for_each_plane(out, q, vol->C, [&](void* h, const void* d, size_t bpp) {
+            return (int)hipMemcpyAsync(h, d, n * bpp, hipMemcpyDeviceToHost, st);
+        });
         if (ce == hipSuccess) ce = hipStreamSynchronize(st);
         if (ce != hipSuccess)
             rc = fail(RSLF_ERR_HIP, "result download failed: %s", hipGetErrorString(ce));

@@ -525,6 +525,22 @@ inline bool use_pinned_gather(int runs, int rows, size_t epi_bytes, size_t pin_c
     return runs > 8 && pin_cap > 0 && (size_t)rows * epi_bytes <= pin_cap;
 }
 
+// The gather itself: EPIs [i0, i1) of `epis` (S rows of row_bytes, `stride` bytes apart) as dense rows at
+// dst + i * S * row_bytes -- one copy per EPI where the rows are dense already, else one per row (a pad is never read).
+inline void gather_epis(char* dst, const void* const* epis, int i0, int i1, int S, size_t row_bytes, size_t stride)
+{
+    const size_t epi_bytes = (size_t)S * row_bytes;
+    for (int i = i0; i < i1; i++) {
+        const char* e = (const char*)epis[i];
+        char* o = dst + (size_t)i * epi_bytes;
+        if (stride == row_bytes)
+            memcpy(o, e, epi_bytes);
+        else
+            for (int r = 0; r < S; r++)
+                memcpy(o + (size_t)r * row_bytes, e + (size_t)r * stride, row_bytes);
+    }
+}
+
 // rows per pass of the chunked host upload through the bounded device staging buffer
 inline int staging_chunk_rows(size_t epi_bytes, int V, size_t budget = kStagingBudget)
 {
@@ -552,6 +568,47 @@ inline PlaneLayout plane_layout(size_t n, int C, int count_rows)
     q.counts = (q.mask + n + 15) & ~(size_t)15;
     q.bytes = q.counts + (size_t)count_rows * sizeof(int);
     return q;
+}
+
+// The eight [V][U] result planes of a pile step as pointers: a carved block on the device, or the caller's planes.
+struct PilePlanes {
+    float *Ce, *Cd, *depth, *raw, *score, *rbar;
+    int32_t* idx;
+    uint8_t* mask;
+};
+
+inline PilePlanes carve(char* base, size_t n, int C)
+{
+    const PlaneLayout o = plane_layout(n, C, 0);
+    PilePlanes q;
+    q.Ce = (float*)(base + o.Ce);
+    q.Cd = (float*)(base + o.Cd);
+    q.depth = (float*)(base + o.depth);
+    q.raw = (float*)(base + o.raw);
+    q.score = (float*)(base + o.score);
+    q.rbar = (float*)(base + o.rbar);
+    q.idx = (int32_t*)(base + o.idx);
+    q.mask = (uint8_t*)(base + o.mask);
+    return q;
+}
+
+// The one enumeration of the planes, in the order the C-ABI lists them: f(host plane, device plane, bytes per pixel) for
+// every plane the caller wants (a NULL host plane is skipped).  f returns 0 to go on; anything else ends the enumeration
+// and is returned.
+template <typename F>
+inline int for_each_plane(const PilePlanes& host, const PilePlanes& dev, int C, F f)
+{
+    const struct {
+        void* host;
+        const void* dev;
+        size_t bytes_per_pixel;
+    } planes[8] = {{host.Ce, dev.Ce, 4},     {host.mask, dev.mask, 1},   {host.Cd, dev.Cd, 4},   {host.depth, dev.depth, 4}, {host.rbar, dev.rbar, 4 * (size_t)C},
+                   {host.idx, dev.idx, 4},   {host.score, dev.score, 4}, {host.raw, dev.raw, 4}};
+    for (const auto& q : planes)
+        if (q.host)
+            if (int rc = f(q.host, q.dev, q.bytes_per_pixel))
+                return rc;
+    return 0;
 }
 
 // ---- scan launches ------------------------------------------------------------------------------------------------

@@ -212,6 +212,89 @@ static void test_plane_layout()
         }
 }
 
+// gather_epis: EPIs [i0, i1) as dense rows at dst + i * S * row_bytes, the rest of dst untouched.  Every source block ends
+// with its last row, so a read of the pad behind it is an AddressSanitizer report.
+static void test_gather_epis()
+{
+    const int n_epis = 5, S = 3;
+    const int ranges[3][2] = {{0, 5}, {2, 4}, {4, 4}};
+    for (size_t row_bytes : {(size_t)7, (size_t)24})
+        for (size_t pad : {(size_t)0, (size_t)1, (size_t)16})
+            for (const auto& range : ranges) {
+                const size_t stride = row_bytes + pad, epi_bytes = (size_t)S * row_bytes;
+                const size_t block = (size_t)(S - 1) * stride + row_bytes;
+                std::vector<char*> blocks;
+                std::vector<const void*> epis;
+                auto value = [&](int i, int r, size_t b) { return (char)(1 + (i * 31 + r * 7 + (int)b) % 120); };
+                for (int i = 0; i < n_epis; i++) {
+                    char* e = (char*)std::malloc(block);
+                    CHECK(e != nullptr);
+                    std::memset(e, 0x7E, block);   // the pad bytes' poison
+                    for (int r = 0; r < S; r++)
+                        for (size_t b = 0; b < row_bytes; b++)
+                            e[(size_t)r * stride + b] = value(i, r, b);
+                    blocks.push_back(e);
+                    epis.push_back(e);
+                }
+                std::vector<char> dst((size_t)n_epis * epi_bytes, (char)0x7F);
+                gather_epis(dst.data(), epis.data(), range[0], range[1], S, row_bytes, stride);
+                for (int i = 0; i < n_epis; i++)
+                    for (int r = 0; r < S; r++)
+                        for (size_t b = 0; b < row_bytes; b++) {
+                            const bool inside = i >= range[0] && i < range[1];
+                            CHECK(dst[(size_t)i * epi_bytes + (size_t)r * row_bytes + b] == (inside ? value(i, r, b) : (char)0x7F));
+                        }
+                for (char* e : blocks)
+                    std::free(e);
+            }
+}
+
+// PilePlanes / carve / for_each_plane: the eight result planes stated once, over plane_layout
+static void test_pile_planes()
+{
+    for (int C : {1, 3})
+        for (size_t n : {(size_t)1, (size_t)63, (size_t)64, (size_t)1000}) {
+            const PlaneLayout o = plane_layout(n, C, 0);
+            std::vector<char> block(o.bytes);
+            char* base = block.data();
+            const PilePlanes d = carve(base, n, C);
+            CHECK((char*)d.Ce == base + o.Ce && (char*)d.Cd == base + o.Cd && (char*)d.depth == base + o.depth);
+            CHECK((char*)d.raw == base + o.raw && (char*)d.score == base + o.score && (char*)d.rbar == base + o.rbar);
+            CHECK((char*)d.idx == base + o.idx && (char*)d.mask == base + o.mask);
+            std::vector<char> host_block(o.bytes);
+            PilePlanes h = carve(host_block.data(), n, C);
+            // eight records, in the order the C-ABI lists the planes: Ce, mask, Cd, depth, rbar, idx, score, raw
+            struct Rec {
+                void* h;
+                const void* d;
+                size_t bpp;
+            };
+            std::vector<Rec> recs;
+            CHECK(for_each_plane(h, d, C, [&](void* hp, const void* dp, size_t bpp) { recs.push_back(Rec{hp, dp, bpp}); return 0; }) == 0);
+            CHECK(recs.size() == 8);
+            const void* want_h[8] = {h.Ce, h.mask, h.Cd, h.depth, h.rbar, h.idx, h.score, h.raw};
+            const void* want_d[8] = {d.Ce, d.mask, d.Cd, d.depth, d.rbar, d.idx, d.score, d.raw};
+            const size_t want_bpp[8] = {4, 1, 4, 4, 4 * (size_t)C, 4, 4, 4};
+            for (int k = 0; k < 8; k++) {
+                CHECK(recs[k].h == want_h[k] && recs[k].d == want_d[k] && recs[k].bpp == want_bpp[k]);
+                const char* lo = (const char*)recs[k].d;   // the extents lie inside the block and apart from one another
+                CHECK(lo >= base && lo + n * recs[k].bpp <= base + o.bytes);
+                for (int q = 0; q < k; q++) {
+                    const char* lo_q = (const char*)recs[q].d;
+                    CHECK(lo + n * recs[k].bpp <= lo_q || lo_q + n * recs[q].bpp <= lo);
+                }
+            }
+            // a NULL host plane is skipped; a callable's status ends the enumeration and is returned
+            h.mask = nullptr;
+            h.raw = nullptr;
+            int seen = 0;
+            CHECK(for_each_plane(h, d, C, [&](void* hp, const void* dp, size_t) { seen++; return hp && dp != d.mask && dp != d.raw ? 0 : 1; }) == 0);
+            CHECK(seen == 6);
+            seen = 0;
+            CHECK(for_each_plane(h, d, C, [&](void*, const void*, size_t) { return ++seen == 3 ? 17 : 0; }) == 17 && seen == 3);
+        }
+}
+
 static ScanRequest request(int V, int U, int S, int C, int D)
 {
     ScanRequest r{};
@@ -871,6 +954,8 @@ int main()
     test_partitions();
     test_host_copies();
     test_plane_layout();
+    test_gather_epis();
+    test_pile_planes();
     test_scan_plans();
     test_scan_kernel_choice();
     test_scan_launches();

@@ -1,6 +1,6 @@
 """The C boundary under failure (include/rslf_hip.h: 'never throws across the boundary'): an exception raised inside a
-device worker of rslf_multi_*, a std::bad_alloc there, and a std::thread that cannot be started all come back as a
-status (or as a completed call), leave nothing running, and the very next call on the same object is bit-identical to
+device worker of rslf_multi_* or inside a sharded sweep, a std::bad_alloc in a worker, and a std::thread that cannot be
+started all come back as a status (or as a completed call), leave nothing running, and the very next call on the same object is bit-identical to
 a clean run.  Armed through rslf_debug_inject (process-wide, off by default)."""
 import numpy as np
 import pytest
@@ -43,6 +43,36 @@ def test_a_throwing_worker_becomes_a_status(rs, site, status):
     for k in PLANES:
         assert np.array_equal(again[k], clean[k]), k
     m.close()
+
+
+def test_a_throwing_sharded_sweep_becomes_a_status(rs):
+    """An exception between the last device's rslf_sweep_begin and the first visit ("sweep": a host exception, no kernel is
+    interrupted) unwinds through the sweep's per-device state: volumes, events, the open sweeps and the contexts' streams
+    all go back, so the next sweep on the same object equals the clean one and the pile path equals a fresh object's."""
+    from remotesensingproject_amd import _lib
+    L = _lib.lib()
+    epis = _epis(V=21)
+    m = rs.MultiDevice([0, 0, 0])
+    clean = m.depth2d(epis, -1.0, 2.0, 10, epi_scale_factor=1.0)
+    assert L.rslf_debug_inject(b"sweep", 1) == 0
+    try:
+        with pytest.raises(_lib.RslfError) as ei:
+            m.depth2d(epis, -1.0, 2.0, 10, epi_scale_factor=1.0)
+    finally:
+        assert L.rslf_debug_inject(b"sweep", 0) == 0
+    assert ei.value.status == -6
+    assert "injected" in str(ei.value)
+    again = m.depth2d(epis, -1.0, 2.0, 10, epi_scale_factor=1.0)
+    assert set(again) == set(clean)
+    for k in clean:
+        assert np.array_equal(again[k], clean[k]), k
+    pile = m.depth1d_pile(epis, -1.0, 2.0, 10, epi_scale_factor=1.0)   # the streams and the kept volumes are intact
+    m.close()
+    fresh = rs.MultiDevice([0, 0, 0])
+    want = fresh.depth1d_pile(epis, -1.0, 2.0, 10, epi_scale_factor=1.0)
+    fresh.close()
+    for k in PLANES:
+        assert np.array_equal(pile[k], want[k]), k
 
 
 def test_without_threads_the_caller_does_the_work(rs):

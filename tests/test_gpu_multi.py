@@ -80,6 +80,25 @@ def test_multi_with_opened_mask_and_wide_median(rs):
         assert np.array_equal(got[k], ref[k]), k
 
 
+def test_multi_kept_volumes_serve_shorter_and_taller_fields(rs):
+    """The two volumes a device keeps from call to call are never rewritten: a field with fewer rows than they hold is
+    computed through views of the chunk's height, and the taller field afterwards finds them as they were made."""
+    S, U, D = 7, 66, 10
+    m = rs.MultiDevice([0, 0])
+    m.set_chunk_rows(4)
+    for V in (19, 11, 19):
+        vol = _field(V, S, U, 1, 50 + V)
+        epis = [vol[v, :, :, 0] for v in range(V)]
+        got = m.depth1d_pile(epis, -1.0, 2.0, D, epi_scale_factor=1.0)
+        fresh = rs.MultiDevice([0, 0])
+        fresh.set_chunk_rows(4)
+        want = fresh.depth1d_pile(epis, -1.0, 2.0, D, epi_scale_factor=1.0)
+        fresh.close()
+        for k in PLANES:
+            assert np.array_equal(got[k], want[k]), (V, k)
+    m.close()
+
+
 def test_multi_rejects_bad_arguments(rs):
     from remotesensingproject_amd import _lib
     with pytest.raises(_lib.RslfError):

@@ -82,6 +82,24 @@ def test_threads_are_owned_by_a_join_guard():
             assert not uses, "%s creates std::thread objects outside JoinGuard" % f
 
 
+def test_streams_and_volumes_are_written_in_one_place():
+    """a context's stream is assigned by rslf_ctx_set_stream and StreamScope only, and a volume's height
+    and size where the volume is made (rslf_core.hip) -- the multi-device paths work on views of their own."""
+    for f in _units() + ["rslf_internal.hpp"]:
+        src = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, f)).read())
+        streams = [m.start() for m in re.finditer(r"(->|\.)stream\s*=[^=]", src)]
+        if f == "rslf_internal.hpp":
+            a = src.index("struct StreamScope")
+            assert len(streams) == 2 and all(a < s < src.index("};", a) for s in streams), f
+        elif f == "rslf_core.hip":
+            a = src.index('extern "C" int rslf_ctx_set_stream')
+            assert len(streams) == 1 and a < streams[0] < src.index("RSLF_API_CATCH", a), f
+        else:
+            assert not streams, "%s assigns a context's stream outside StreamScope" % f
+        if f != "rslf_core.hip":
+            assert not re.search(r"->(V|bytes)\s*=[^=]", src), "%s writes into a volume it was given" % f
+
+
 def test_no_library_source_exceeds_1200_lines():
     big = []
     for f in os.listdir(CSRC):
