@@ -139,6 +139,8 @@ int rslf_ctx_synchronize(rslf_ctx* ctx);
  *                    HYPOTHESES in the lanes of a wave (k2_scan_reg_px, k2_scan_stream_px) instead of 64 pixels
  *   "row_split"      1 (default) packed launches of stream-class volumes scan the rows that hold >= 64 pixels as row tiles of
  *                    the packed list and leave the pixel-per-wave launch the rest | 0 the pixel-per-wave launch takes all
+ *   "tap_table"      1 (default) the register row kernels that have one (k2_scan_reg<104,1>) take the lerp taps and weights that
+ *                    are the same in every lane of a tile from a per-hypothesis table | 0 every lane computes its own
  *   "claim_skip"     1 (default) the 2-D sweep's claims skip views with nothing left to paint within reach | 0 off
  *   "stream_share"   63-pixel tiles sharing taps between lanes in the streaming kernel: 1 (default) where the samples gathered
  *                    again on every pass are at least a quarter of the views | 0 never | 2 always

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 SO = os.path.join(CSRC, "librslf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
-COMMON = ["rslf_internal.hpp", "rslf_plan.hpp", "rslf_scratch.hpp", "rslf_device.hpp", os.path.join(INCLUDE, "rslf_hip.h")]
+COMMON = ["rslf_internal.hpp", "rslf_plan.hpp", "rslf_scratch.hpp", "rslf_device.hpp", "k2_taps.hpp", os.path.join(INCLUDE, "rslf_hip.h")]
 # translation unit -> the kernel headers it alone includes (device code is per unit; rslf_internal.hpp lists the units)
 UNITS = {
     "rslf_core.hip": ["k0_pack.hpp"],

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "k2_scan.hpp"
+#include "k2_taps.hpp"
 
 namespace rslf {
 
@@ -140,6 +141,77 @@ __device__ __forceinline__ void mean_shift_pass(const float (&R)[PK ? 1 : C][PK 
     }
 }
 
+// One gather batch of the row form with a tap table (scan_reg_body, TAPS).  `from_table` (wave-uniform): the tile's pixels
+// are consecutive, every slot of the batch holds a sample and each has an entry that serves every lane -- address and
+// weights are the entry's, one address add per sample.  Otherwise they are computed per lane, as scan_reg_body does
+// without a table.  Both forms feed ONE copy of the loads and the blend: what meets after the branch are the batch's
+// short-lived addresses and weights, not the sample registers (two copies of the blend put those in scratch).
+// Interior hypotheses only: every sample is inside the row, so there is no validity to carry.  (The border form was built
+// as well: validity then meets after the branch as a register and costs the per-lane batches two instructions per sample.)
+template <int SPAD, int C, int BATCH>
+__device__ __forceinline__ void tap_table_batch(const float* epi, const float* otab, const int* tboff, const f2* tw, unsigned du_bytes,
+                                                float uf, int S, int stride_s, bool from_table, int g, int& rowoff, float (&R)[C][SPAD])
+{
+    float tt[BATCH], om[BATCH], e0[C][BATCH], e1[C][BATCH];
+    unsigned bo[BATCH];
+    if (from_table) {
+#pragma unroll
+        for (int j = 0; j < BATCH; j++) {
+            const int s = g * BATCH + j;
+            bo[j] = (unsigned)tboff[s] + du_bytes;
+            const f2 w = tw[s];   // (t, 1 - t)
+            tt[j] = w.x;
+            om[j] = w.y;
+        }
+    } else {
+        int ro = rowoff;
+#pragma unroll
+        for (int j = 0; j < BATCH; j++) {
+            const int s = g * BATCH + j;
+            tt[j] = 0.0f;
+            bo[j] = 0;
+            if (s < SPAD - kPadSlack || s < S) {
+                const float x = otab[s] + uf;      // core.hpp:552
+                tt[j] = lerp_weight(x);            // interp.hpp:181
+                const int i0 = floor_to_int(x);    // interp.hpp:179
+                bo[j] = (unsigned)(i0 * C + ro) << 2;
+            }
+            om[j] = 1.0f - tt[j];
+            ro += stride_s;
+        }
+    }
+    rowoff += BATCH * stride_s;
+    // the batch's loads back to back, then the blend
+#pragma unroll
+    for (int j = 0; j < BATCH; j++) {
+        const int s = g * BATCH + j;
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            e0[c][j] = kSentinel;
+            e1[c][j] = 0.0f;
+        }
+        if (s < SPAD - kPadSlack || s < S) {
+            const float* p = (const float*)((const char*)epi + bo[j]);
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                e0[c][j] = p[c];
+                e1[c][j] = p[C + c];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; j++) {
+        const int s = g * BATCH + j;
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const float m0 = om[j] * e0[c][j];   // interp.hpp:184
+            const float m1 = tt[j] * e1[c][j];
+            const float r = m0 + m1;
+            R[c][s] = (s < SPAD - kPadSlack || s < S) ? r : kSentinel;
+        }
+    }
+}
+
 // BORDER:    some sample line of this wave may leave [0, U-1]: test validity per sample.
 // UNIFORM_D: every pixel shares the hypothesis grid (no per-pixel dmin/dmax planes), so the
 //            view offset fl(fl(float(s_hat - s) * D[d]) * slope) is the same for all 64 lanes:
@@ -156,8 +228,14 @@ __device__ __forceinline__ void mean_shift_pass(const float (&R)[PK ? 1 : C][PK 
 //            d0 + dlane, d0 + dlane + dstep, ... below d1 (a lane past the end repeats d1 - 1 and offers nothing).
 // TRIM:      the last mean-shift pass sums K alone (the score) and `best` is offered the rbar that ENTERED it; the
 //            kernel's epilogue recomputes the last pass for the winning hypothesis of each pixel (last_pass_rbar).
+// TAPS:      (with UNIFORM_D) the lanes that compute the view offsets also compute, per offset, the tap entry of the whole
+//            tile (k2_taps.hpp): {address of the first pixel's left tap, t, 1 - t} and whether it holds for every lane.
+//            `otab` is then three tables in 4 * SPAD floats, [offsets][addresses][(t, 1 - t) pairs].  On a tile of consecutive pixels a
+//            gather batch whose samples all have such an entry takes them from it: per sample one address add and the
+//            blend -- no position add, fract, floor-convert, address shift or 1 - t, which give the same bits in every lane.
+//            Every other batch runs the per-lane form.
 template <int SPAD, int C, bool BORDER, bool UNIFORM_D, bool PK, int GB = 0, class BestT = Best<C>, bool LANE_D = false,
-          bool TRIM = false>
+          bool TRIM = false, bool TAPS = false>
 __device__ __forceinline__ void scan_reg_body(const ScanArgs& a, int v, int u, int d0, int d1, BestT& best,
                                               float* __restrict__ otab, int dlane = 0, int dstep = 1)
 {
@@ -167,6 +245,7 @@ __device__ __forceinline__ void scan_reg_body(const ScanArgs& a, int v, int u, i
     constexpr int kGatherBatch = GB > 0 ? GB : (C == 1 && !PK && SPAD == 104 && RSLF_REG_GB104 == 13) ? 13 : gather_batch(C);
     static_assert(SPAD % kGatherBatch == 0 && (!PK || kGatherBatch % 2 == 0), "whole batches, whole pairs");
     static_assert(SPAD % 8 == 0, "slot counts are multiples of 8");
+    static_assert(!TAPS || (UNIFORM_D && !BORDER && !PK), "the tap table belongs to the interior scalar uniform-D row form");
     const VolView& vol = a.vol;
     const float* epi = vol.row(v, 0);
     const float uf = (float)u;
@@ -187,6 +266,20 @@ __device__ __forceinline__ void scan_reg_body(const ScanArgs& a, int v, int u, i
 #pragma unroll
     for (int c = 0; c < C; c++)
         centre[c] = epi[(long long)a.s_hat * vol.stride_s + u * C + c];
+    // TAPS: the tile's first and last pixel (idle lanes shadow the last one, scan_tile), this lane's place among them as
+    // a byte offset, and whether the lanes hold consecutive pixels -- all the table's entries assume
+    int* const tboff = TAPS ? reinterpret_cast<int*>(otab + SPAD) : nullptr;
+    f2* const tw = TAPS ? reinterpret_cast<f2*>(otab + 2 * SPAD) : nullptr;
+    int u_first = 0, u_last = 0;
+    unsigned du_bytes = 0;
+    bool taps_on = false;
+    if constexpr (TAPS) {
+        u_first = __builtin_amdgcn_readfirstlane(u);
+        u_last = __builtin_amdgcn_readlane(u, 63);
+        const int du = u - u_first;
+        du_bytes = (unsigned)(du * C) << 2;
+        taps_on = a.tap_table != 0 && __all(du == min(lane, u_last - u_first));
+    }
 
 #pragma unroll 1
     for (int dk = d0; dk < d1; dk += (LANE_D ? dstep : 1)) {
@@ -204,91 +297,122 @@ __device__ __forceinline__ void scan_reg_body(const ScanArgs& a, int v, int u, i
         asm volatile("" : "+v"(Ss0));
         int rowoff = 0;
         asm volatile("" : "+s"(rowoff));
+        unsigned fastb = 0;   // TAPS: bit g = gather batch g takes its samples from the tap table
         if (UNIFORM_D) {
+            // (TAPS: what the entries are made from is re-made opaque per hypothesis like the address state above, so that
+            // nothing of it stays in registers through the passes)
+            int lane_s = lane, tile_first = u_first, tile_last = u_last;
+            if constexpr (TAPS)
+                asm volatile("" : "+v"(lane_s), "+s"(tile_first), "+s"(tile_last));
 #pragma unroll
             for (int s0 = 0; s0 < SPAD; s0 += 64) {
-                const int s = s0 + lane;
+                const int s = s0 + lane_s;
                 float off = (float)(a.s_hat - s) * Dd;   // float(s_hat - s) * D[d]   core.hpp:542,550
                 off = off * slope;                       // core.hpp:551
                 if (SPAD % 64 == 0 || s < SPAD)
                     otab[s] = off;
+                if constexpr (TAPS) {
+                    if (taps_on) {   // (wave-uniform)
+                        const TapEntry e = tap_entry(off, tile_first, tile_last, vol.U, C, __mul24(s, stride_s));
+                        if (SPAD % 64 == 0 || s < SPAD) {
+                            tboff[s] = e.byteoff;
+                            tw[s] = f2{e.t, e.omt};
+                        }
+                        // bit 8 k of m: the eight samples from s0 + 8 k on all have an entry for the whole tile
+                        unsigned long long m = __ballot(e.fast);
+                        m &= m >> 1;
+                        m &= m >> 2;
+                        m &= m >> 4;
+                        static_assert(!TAPS || kGatherBatch == 8, "the batch bits are gathered for batches of eight samples");
+#pragma unroll
+                        for (int k = 0; k < 8; k++)
+                            if (s0 + 8 * k < SPAD)
+                                fastb |= ((unsigned)(m >> (8 * k)) & 1u) << (s0 / 8 + k);
+                    }
+                }
             }
             // same wave, LDS is in order: the broadcast reads below see these writes
             __builtin_amdgcn_wave_barrier();
+            if constexpr (TAPS)   // whole batches only: the one that reaches past S has padding slots
+                fastb = __builtin_amdgcn_readfirstlane(fastb & (S >= SPAD ? ~0u : (1u << (S / kGatherBatch)) - 1u));
         }
 #pragma unroll
         for (int g = 0; g < SPAD / kGatherBatch; g++) {
-            float tt[kGatherBatch], e0[C][kGatherBatch], e1[C][kGatherBatch];
-            bool ok[kGatherBatch];
-            // issue the batch's loads back to back, then blend
+            if constexpr (TAPS) {
+                tap_table_batch<SPAD, C, kGatherBatch>(epi, otab, tboff, tw, du_bytes, uf, S, stride_s, (fastb >> g) & 1u, g, rowoff, R);
+            } else {
+                float tt[kGatherBatch], e0[C][kGatherBatch], e1[C][kGatherBatch];
+                bool ok[kGatherBatch];
+                // issue the batch's loads back to back, then blend
 #pragma unroll
-            for (int j = 0; j < kGatherBatch; j++) {
-                const int s = g * kGatherBatch + j;
-                tt[j] = 0.0f;
-                ok[j] = false;
-#pragma unroll
-                for (int c = 0; c < C; c++) {
-                    e0[c][j] = kSentinel;
-                    e1[c][j] = 0.0f;
-                }
-                if (s < SPAD - kPadSlack || s < S) {
-                    float x;
-                    if (UNIFORM_D) {
-                        x = otab[s];                   // one broadcast read for the wave
-                    } else {
-                        x = (Ss0 - (float)s) * Dd;     // float(s_hat - s) * D[d]   core.hpp:542,550
-                        x = x * slope;                 // core.hpp:551
-                    }
-                    x = x + uf;                        // core.hpp:552
-                    tt[j] = lerp_weight(x);            // interp.hpp:181
-                    int i0 = floor_to_int(x);          // interp.hpp:179
-                    ok[j] = true;
-                    if (BORDER) {
-                        // interp.hpp:182: floor(x) >= 0 <=> x >= 0 and ceil(x) <= U-1 <=> x <= U-1.
-                        // x is never -0 (u >= +0 is added last), so both tests are ONE unsigned compare
-                        // of the bit patterns: negative floats have the sign bit set and compare high.
-                        ok[j] = __float_as_uint(x) <= Um1_bits;
-                        i0 = ok[j] ? i0 : 0;           // keep the address inside the row
-                    }
-                    // 32-bit byte offset off the EPI's scalar base
-                    const unsigned byteoff = (unsigned)(i0 * C + rowoff) << 2;
-                    // both taps of every channel are 2*C consecutive floats of the row (interleaved slab).  For
-                    // integral x the reference reads the first tap twice with weights 1 and 0; 0 * (second tap)
-                    // is the same +0 (rows are zero padded, so the second tap is finite)
-                    const float* p = (const float*)((const char*)epi + byteoff);
+                for (int j = 0; j < kGatherBatch; j++) {
+                    const int s = g * kGatherBatch + j;
+                    tt[j] = 0.0f;
+                    ok[j] = false;
 #pragma unroll
                     for (int c = 0; c < C; c++) {
-                        e0[c][j] = p[c];
-                        e1[c][j] = p[C + c];
+                        e0[c][j] = kSentinel;
+                        e1[c][j] = 0.0f;
                     }
+                    if (s < SPAD - kPadSlack || s < S) {
+                        float x;
+                        if (UNIFORM_D) {
+                            x = otab[s];                   // one broadcast read for the wave
+                        } else {
+                            x = (Ss0 - (float)s) * Dd;     // float(s_hat - s) * D[d]   core.hpp:542,550
+                            x = x * slope;                 // core.hpp:551
+                        }
+                        x = x + uf;                        // core.hpp:552
+                        tt[j] = lerp_weight(x);            // interp.hpp:181
+                        int i0 = floor_to_int(x);          // interp.hpp:179
+                        ok[j] = true;
+                        if (BORDER) {
+                            // interp.hpp:182: floor(x) >= 0 <=> x >= 0 and ceil(x) <= U-1 <=> x <= U-1.
+                            // x is never -0 (u >= +0 is added last), so both tests are ONE unsigned compare
+                            // of the bit patterns: negative floats have the sign bit set and compare high.
+                            ok[j] = __float_as_uint(x) <= Um1_bits;
+                            i0 = ok[j] ? i0 : 0;           // keep the address inside the row
+                        }
+                        // 32-bit byte offset off the EPI's scalar base
+                        const unsigned byteoff = (unsigned)(i0 * C + rowoff) << 2;
+                        // both taps of every channel are 2*C consecutive floats of the row (interleaved slab).  For
+                        // integral x the reference reads the first tap twice with weights 1 and 0; 0 * (second tap)
+                        // is the same +0 (rows are zero padded, so the second tap is finite)
+                        const float* p = (const float*)((const char*)epi + byteoff);
+#pragma unroll
+                        for (int c = 0; c < C; c++) {
+                            e0[c][j] = p[c];
+                            e1[c][j] = p[C + c];
+                        }
+                    }
+                    rowoff += stride_s;
                 }
-                rowoff += stride_s;
-            }
 #pragma unroll
-            for (int j = 0; j < kGatherBatch; j++) {
-                const int s = g * kGatherBatch + j;
-                const float omt = 1.0f - tt[j];
+                for (int j = 0; j < kGatherBatch; j++) {
+                    const int s = g * kGatherBatch + j;
+                    const float omt = 1.0f - tt[j];
 #pragma unroll
-                for (int c = 0; c < C; c++) {
-                    const float m0 = omt * e0[c][j];   // interp.hpp:184
-                    const float m1 = tt[j] * e1[c][j];
-                    const float r = m0 + m1;
-                    float val;
-                    if (BORDER)
-                        val = ok[j] ? r : kSentinel;
-                    else
-                        val = (s < SPAD - kPadSlack || s < S) ? r : kSentinel;
-                    if constexpr (PK) {
-                        if (s & 1)
-                            R2[c][s >> 1].y = val;
+                    for (int c = 0; c < C; c++) {
+                        const float m0 = omt * e0[c][j];   // interp.hpp:184
+                        const float m1 = tt[j] * e1[c][j];
+                        const float r = m0 + m1;
+                        float val;
+                        if (BORDER)
+                            val = ok[j] ? r : kSentinel;
                         else
-                            R2[c][s >> 1].x = val;
-                    } else {
-                        R[c][s] = val;
+                            val = (s < SPAD - kPadSlack || s < S) ? r : kSentinel;
+                        if constexpr (PK) {
+                            if (s & 1)
+                                R2[c][s >> 1].y = val;
+                            else
+                                R2[c][s >> 1].x = val;
+                        } else {
+                            R[c][s] = val;
+                        }
                     }
+                    if (BORDER)
+                        card += ok[j] ? 1 : 0;
                 }
-                if (BORDER)
-                    card += ok[j] ? 1 : 0;
             }
             // Pin this batch: its results must exist here, and the next batch's address state is
             // re-made opaque here, so the compiler cannot turn the unrolled gather into "all
@@ -481,6 +605,15 @@ constexpr bool scan_reg_trim(int spad, int c)
 {
     return c == 1 && !scan_reg_packed_math(spad, c) && spad != 48 && !(spad >= 80 && spad <= 88) && !(spad > 112 && spad <= 144);
 }
+// The row kernels whose uniform-D scan takes lane-invariant taps from a per-hypothesis table (scan_reg_body, TAPS): the
+// 104-slot kernel of the c3 shape, VALU-issue bound at 3 waves per SIMD with registers to spare for neither a wider batch
+// nor the table -- its entries live in LDS (+4.9 KiB per workgroup, same occupancy).  Other slot counts stay as they are
+// until a same-box A/B shows them a gain (profiles/r10_tap_table.md).
+#ifndef RSLF_TAP_TABLE
+#define RSLF_TAP_TABLE 1   // 0 builds every row kernel without the table (A/B)
+#endif
+constexpr bool scan_reg_tap_table(int spad, int c) { return RSLF_TAP_TABLE && c == 1 && spad == 104 && scan_reg_trim(spad, c); }
+
 template <int SPAD, int C>
 using ScanRegRbarFix = std::conditional_t<scan_reg_trim(SPAD, C), LastPassRbar<C>, NoRbarFix>;
 
@@ -488,6 +621,7 @@ template <int SPAD, int C, class BestT>
 __device__ __forceinline__ void scan_reg_rows(const ScanArgs& a, int v, int u, int d0, int d1, BestT& best, float* otab)
 {
     constexpr bool PK = scan_reg_packed_math(SPAD, C);
+    constexpr bool kTaps = scan_reg_tap_table(SPAD, C);
     if (a.dmin_vu) {
         scan_reg_body<SPAD, C, true, false, PK, 0, BestT, false, scan_reg_trim(SPAD, C)>(a, v, u, d0, d1, best, otab);
         return;
@@ -508,7 +642,7 @@ __device__ __forceinline__ void scan_reg_rows(const ScanArgs& a, int v, int u, i
         while (e < d1 && interior(e) == in)
             e++;
         if (in)
-            scan_reg_body<SPAD, C, false, true, PK, 0, BestT, false, scan_reg_trim(SPAD, C)>(a, v, u, d, e, best, otab);
+            scan_reg_body<SPAD, C, false, true, PK, 0, BestT, false, scan_reg_trim(SPAD, C), kTaps>(a, v, u, d, e, best, otab);
         else
             scan_reg_body<SPAD, C, true, true, PK, 0, BestT, false, scan_reg_trim(SPAD, C)>(a, v, u, d, e, best, otab);
         d = e;
@@ -519,7 +653,8 @@ template <int SPAD, int C>
 __global__ __launch_bounds__(64 * kScanWaves) __attribute__((amdgpu_waves_per_eu(scan_reg_waves(SPAD, C), scan_reg_waves(SPAD, C))))
 void k2_scan_reg(ScanArgs a)
 {
-    __shared__ float s_otab[kScanWaves][SPAD];
+    // per wave: the view offsets of a hypothesis; with the tap table (scan_reg_body, TAPS) also the addresses and weight pairs
+    __shared__ __attribute__((aligned(16))) float s_otab[kScanWaves][SPAD * (scan_reg_tap_table(SPAD, C) ? 4 : 1)];
     float* otab = s_otab[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
     constexpr bool kEpiDyn = false;
     float* const epi_lds = nullptr;

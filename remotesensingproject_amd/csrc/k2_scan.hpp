@@ -93,6 +93,8 @@ struct ScanArgs {
     // ~8 % density).  rowbase == nullptr: per-row lists at list[v * U] (dense launches); row_min == 0: no split.
     const int* rowbase;
     int row_min;
+    // register row kernels with a tap table (k2_reg.hpp, scan_reg_tap_table): 0 = every gather batch takes the per-lane form
+    int tap_table;
 };
 
 // Laid out WORD-major in memory ([item][word][lane], record_word): a wave's store of one word is then 256 contiguous bytes.

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k2_taps.hpp"
+
 namespace rslf {
 
 constexpr int kWave = 64;              // gfx950 wavefront
@@ -77,17 +79,10 @@ __device__ __forceinline__ float kernel_weight(float q)
 // interp.hpp:179-181 for a position x >= 0: i0 = (int)floor(x) and t = x - floor(x), one instruction each
 // instead of floor + convert + subtract.  v_fract_f32 is x - floor(x) exactly for x >= 0 (for x < 0 close
 // to an integer it stays below 1 where the subtraction rounds to 1 -- callers only use t where x is valid,
-// i.e. non-negative); v_cvt_flr_i32_f32 converts with round toward -inf.
-__device__ __forceinline__ float lerp_weight(float x)
-{
-    return __builtin_amdgcn_fractf(x);
-}
-__device__ __forceinline__ int floor_to_int(float x)
-{
-    int i;
-    asm("v_cvt_flr_i32_f32_e32 %0, %1" : "=v"(i) : "v"(x));
-    return i;
-}
+// i.e. non-negative); v_cvt_flr_i32_f32 converts with round toward -inf.  Stated once, in k2_taps.hpp, with the host's
+// equivalents beside them.
+__device__ __forceinline__ float lerp_weight(float x) { return tap_fract(x); }
+__device__ __forceinline__ int floor_to_int(float x) { return tap_floor(x); }
 
 // Two floats in an aligned register pair: operands of v_pk_add_f32 / v_pk_mul_f32.  Each half is the same
 // IEEE operation as the scalar instruction (tools/ubench_pk.hip checks it bit for bit, sentinel and denormal

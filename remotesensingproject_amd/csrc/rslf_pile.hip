@@ -185,6 +185,7 @@ static plan::ScanRequest scan_request(const rslf_ctx* ctx, int V, int U, int S, 
     rq.stream_groups = ctx->stream_groups;
     rq.stream_share = ctx->stream_share;
     rq.stream_lds_bytes = ctx->stream_lds_bytes;
+    rq.tap_table = ctx->tap_table;
     const bool dense_uniform = !pixel_ranges && !in.packed && ctx->force_packed != 1 && in.lists != ScanInputs::kPackedList;
     plan::choose_scan_kernel(&rq, in_range, linear, ctx->force_scan, dense_uniform, kernel_facts(S, C));
     return rq;
@@ -284,6 +285,7 @@ static void apply_plan(ScanArgs& a, const plan::ScanPlan& p, const rslf_ctx* ctx
     a.packed = p.packed ? 1 : 0;
     a.packed_adapt = p.packed_adapt ? 1 : 0;
     a.px_waves = p.px_waves;
+    a.tap_table = p.tap_table;
     a.stream_park = p.stream_park;
     a.stream_wave_floats = p.stream_wave_floats;
     // grouped launches leave one 32-byte record per (tile, group, lane) for the tile's last group to merge (k2_scan.hpp)
