@@ -161,7 +161,8 @@ int rslf_ctx_set_debug(rslf_ctx* ctx, const char* key, int value);
 /* Fault injection for the tests of the error paths (process-wide, off unless armed): the next `count` visits of `site`
  * fail as if the runtime had -- "worker": a device worker of rslf_multi_* throws std::runtime_error; "thread_create":
  * std::thread cannot be started (the work then runs on the calling thread); "alloc": std::bad_alloc in a worker; "sweep":
- * rslf_multi_depth2d_run_* throws std::runtime_error once every device's sweep is open, before the first visit is queued.
+ * rslf_multi_depth2d_run_* throws std::runtime_error once every device's sweep is open, before the first visit is queued,
+ * and so does a level of the one-context fine-to-coarse loop before its sweep is queued.
  * The entry point reports a status; nothing is left running, nothing leaks.  count = 0 disarms. */
 int rslf_debug_inject(const char* site, int count);
 
@@ -504,7 +505,8 @@ int rslf_fine_to_coarse_run_host_u16(rslf_ctx* ctx, const uint16_t* const* h_epi
  *   accept_all (the last level, when asked to)              everything (C_e > -1)
  *   RSLF_LINE_CONF_GATE without use_disp_confidence_score   C_l > (float)line_score_threshold  (:903-904)
  *   otherwise                                               C_e > (float)edge_score_threshold
- * (validity by C_d under use_disp_confidence_score, :902, is not built).  AS_BUILT changes nothing but the existence of the
+ * (the RSLF_F2C_VALID_COMPAT table: under use_disp_confidence_score it reads C_e, not C_d; the whole chain of :893-915, C_d
+ * included, is RSLF_F2C_VALID_REFERENCE of rslf_f2c_run_host below).  AS_BUILT changes nothing but the existence of the
  * C_l planes.  OFF with levels_out NULL queues exactly the launches of rslf_fine_to_coarse_run_host, which is that call.
  *
  * levels_out (nullable): host copies of every level's planes, finest first.  Each member is NULL (not wanted) or an array
@@ -532,6 +534,98 @@ int rslf_fine_to_coarse_run_host_u16_lc(rslf_ctx* ctx, const uint16_t* const* h_
                                         const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                         float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
                                         int line_mode, const rslf_f2c_levels_out* levels_out);
+
+/* ---- fine-to-coarse kept on the device: a finished run as an object, its pictures rendered there ------------------ */
+/* rslf_f2c_run is what FineToCoarse<T> is after run(): every level's Depth2DComputer results and the fused maps, held on ONE
+ * device.  The getters of include/rslf_fine_to_coarse.hpp:325-519 then render from it (3 bytes per pixel leave the device)
+ * and nothing is uploaded or computed a second time.  The object is bound to its device, not to the context that made it:
+ * like a volume it may outlive that context, and it may be read and rendered through any context of the same device. */
+typedef struct rslf_f2c_run rslf_f2c_run;
+
+#define RSLF_ELEM_F32 0   /* the element type of host EPIs: CV_32F, */
+#define RSLF_ELEM_U8  1   /* CV_8U, */
+#define RSLF_ELEM_U16 2   /* CV_16U */
+
+/* get_valid_depths_mask_s_v_u (dc.hpp:893-915) of every level -- the next level's ranges and the fusion:
+ * COMPAT     the table of rslf_fine_to_coarse_run_host_lc above, what every other entry computes.
+ * REFERENCE  the whole #ifdef chain: accept_all -> everything; else use_disp_confidence_score -> C_d > (float)
+ *            disp_score_threshold (:902); else RSLF_LINE_CONF_GATE -> C_l > (float)line_score_threshold (:904); else
+ *            C_e > (float)edge_score_threshold (:906).  The two differ under use_disp_confidence_score alone. */
+#define RSLF_F2C_VALID_COMPAT    0
+#define RSLF_F2C_VALID_REFERENCE 1
+
+/* The planes of a kept run, [S][V_l][U_l] of level l (float32; VALID and FUSED_VALID bytes 0 / 255).  The fused planes are
+ * at the finest size and are asked for with level 0.  CL is held in modes AS_BUILT and GATE only. */
+#define RSLF_F2C_PLANE_DEPTH       0
+#define RSLF_F2C_PLANE_VALID       1
+#define RSLF_F2C_PLANE_CE          2
+#define RSLF_F2C_PLANE_CD          3
+#define RSLF_F2C_PLANE_CL          4
+#define RSLF_F2C_PLANE_FUSED_MAP   5
+#define RSLF_F2C_PLANE_FUSED_VALID 6
+
+#define RSLF_F2C_MAX_LEVELS 32   /* no pyramid is deeper: every level halves both sides of an int-sized field */
+typedef struct rslf_f2c_run_desc {
+    int n_levels;                                 /* pyramid depth */
+    int S, C;                                     /* views, channels */
+    int device;                                   /* the device that holds the run */
+    int elem;                                     /* RSLF_ELEM_* of the EPIs it was made from */
+    int line_mode;                                /* RSLF_LINE_CONF_* of every level's sweep */
+    int validity_rule;                            /* RSLF_F2C_VALID_* */
+    int keep_volumes;                             /* 1: every level's normalised volume is held */
+    unsigned planes_held;                         /* bit (1 << RSLF_F2C_PLANE_*) set for every plane kind held */
+    int V[RSLF_F2C_MAX_LEVELS];                   /* level sizes, finest first */
+    int U[RSLF_F2C_MAX_LEVELS];
+    float epi_scale_factor[RSLF_F2C_MAX_LEVELS];  /* as used: 255 for CV_8U, else the given factor or the level's own max */
+    size_t device_bytes;                          /* what the object holds on the device */
+} rslf_f2c_run_desc;
+
+/* FineToCoarse<T>'s constructor + run() (rslf_fine_to_coarse.hpp:103-299) and the fusion of get_results() (:302-324) from
+ * host EPIs (arguments as rslf_fine_to_coarse_run_host_lc; elem: RSLF_ELEM_*), kept: the level loop is the one of the
+ * entries above, with an owner that keeps what they free.  Per level, finest first, the run holds the disparities, the
+ * validity, C_e, C_d, C_l in modes 1 and 2 and -- with keep_volumes != 0 -- the normalised volume its sweep ran on; and the
+ * fused map and fused validity.  Returns when the run is complete.  stats: nullable, as rslf_fine_to_coarse_run_host's.
+ * On any failure *run is NULL and nothing stays allocated. */
+int rslf_f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                      float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                      int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                      rslf_stats* stats);
+int rslf_f2c_run_destroy(rslf_f2c_run* run);   /* NULL is RSLF_OK; waits for the device */
+int rslf_f2c_run_describe(const rslf_f2c_run* run, rslf_f2c_run_desc* out);
+/* One plane (which: RSLF_F2C_PLANE_*) of one level into the caller's memory: a device pointer on the run's device, or with
+ * dst_on_host != 0 a host pointer (the call then waits).  stream_ctx (nullable): a context of the run's device whose stream
+ * the copy is queued on; NULL copies on the default stream and waits.  A plane that is not held, a level outside the
+ * pyramid, a fused plane asked for with level != 0: RSLF_ERR_INVALID_ARG. */
+int rslf_f2c_run_copy(const rslf_f2c_run* run, int level, int which, void* dst, int dst_on_host, rslf_ctx* stream_ctx);
+/* Level `level`'s normalised volume, for rslf_volume_describe: owned by the run, gone with it.  RSLF_ERR_INVALID_ARG
+ * without kept volumes.  (The render entries below take the run itself: rslf_render_planes wants a volume of its context.) */
+int rslf_f2c_run_volume(const rslf_f2c_run* run, int level, const rslf_volume** out);
+
+/* The three coloured getters, rendered on ctx (any context of the run's device) from the kept planes; pictures [..][3] uint8
+ * BGR into device memory, or host memory in the _host forms (which wait).  saturate != 0: ImageConverter_uchar::fit's 2 % /
+ * 98 % quantiles, else min and mean + 12 std.  The shadow cut follows the run's cut_shadows / shadow_level and reads the
+ * kept volumes: asked for without them, the call is RSLF_ERR_INVALID_ARG and says so.  The index rules that run off the end
+ * in the reference (rslf_render_centre_index, rslf_render_scaled_row) are RSLF_ERR_INVALID_ARG before anything is queued.
+ *
+ * get_coloured_depth_maps (rslf_fine_to_coarse.hpp:325-378): the fused map of every view through the converter fitted on
+ * the fused plane rslf_render_centre_index(S); RSLF_RENDER_AFFINE, black outside the fused validity, shadow cut against
+ * level 0's volume.  out: [S][V][U][3]. */
+int rslf_f2c_run_render_depth_maps(const rslf_f2c_run* run, rslf_ctx* ctx, int saturate, const uint8_t* lut_bgr, uint8_t* d_bgr_out);
+int rslf_f2c_run_render_depth_maps_host(const rslf_f2c_run* run, rslf_ctx* ctx, int saturate, const uint8_t* lut_bgr, uint8_t* h_bgr_out);
+/* get_coloured_depth_pyr (:491-519): view s (-1: the centre index) of every level through the converter fitted on level
+ * 0's plane before any masking; black outside each level's validity; no shadow cut.  out[l]: [V_l][U_l][3], one pointer
+ * per level. */
+int rslf_f2c_run_render_depth_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int s, int saturate, const uint8_t* lut_bgr,
+                                  uint8_t* const* d_bgr_out);
+int rslf_f2c_run_render_depth_pyr_host(const rslf_f2c_run* run, rslf_ctx* ctx, int s, int saturate, const uint8_t* lut_bgr,
+                                       uint8_t* const* h_bgr_out);
+/* get_coloured_epi_pyr (:432-488): the S x U_l slice of every level at scanline rslf_render_scaled_row(v, V_l, V_0) (v = -1:
+ * the centre index of V_0); invalid pixels count as 0 in the fit (level 0 with its validity) and in the render
+ * (RSLF_MASK_ZERO_VALUE); shadow cut against the level's own volume.  out[l]: [S][U_l][3]. */
+int rslf_f2c_run_render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, const uint8_t* lut_bgr,
+                                uint8_t* const* d_bgr_out);
+int rslf_f2c_run_render_epi_pyr_host(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, const uint8_t* lut_bgr,
+                                     uint8_t* const* h_bgr_out);
 
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit

@@ -768,12 +768,38 @@ public:
         detail::require(mode >= RSLF_LINE_CONF_OFF && mode <= RSLF_LINE_CONF_GATE, "line confidence mode: RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE");
         line_mode_ = mode;
     }
+    // To be called before run(): the run stays on the device (rslf_f2c_run_host) and this object owns it.  get_results()
+    // copies the fused planes out, the coloured getters are rendered there from the kept planes -- nothing is uploaded a
+    // second time --, get_coloured_depth_pyr works in every line mode, get_coloured_epi_pyr exists, and the per-level
+    // getters fill from the device when first asked.  keep_volumes: every level keeps the volume its sweep ran on, which
+    // the shadow cut of get_coloured_depth_maps / get_coloured_epi_pyr reads (par_cut_shadows).  One device only.
+    void keep_on_device(bool keep_volumes = true)
+    {
+        detail::require(!multi_, "FineToCoarse: a kept run lives on one device");
+        keep_ = true;
+        keep_volumes_ = keep_volumes;
+    }
+    // RSLF_F2C_VALID_COMPAT (what every other path computes) or RSLF_F2C_VALID_REFERENCE (the whole chain of
+    // get_valid_depths_mask_s_v_u, validity by C_d under par_use_disp_confidence_score included); after keep_on_device.
+    void set_validity_rule(int rule)
+    {
+        detail::require(keep_, "FineToCoarse: the validity rule belongs to a kept run: call keep_on_device first");
+        detail::require(rule == RSLF_F2C_VALID_COMPAT || rule == RSLF_F2C_VALID_REFERENCE, "validity rule: RSLF_F2C_VALID_COMPAT or _REFERENCE");
+        validity_rule_ = rule;
+    }
+    ~FineToCoarse() { rslf_f2c_run_destroy(run_); }
+    FineToCoarse(const FineToCoarse&) = delete;
+    FineToCoarse& operator=(const FineToCoarse&) = delete;
     void run()
     {
+        const rslf_params p = m_parameters.to_c();
+        if (keep_) {
+            run_kept(p);
+            return;
+        }
         const size_t n = (size_t)dim_s_ * dim_v_ * dim_u_;
         out_map_s_v_u_.assign(n, 0.f);
         out_validity_s_v_u_.assign(n, 0);
-        const rslf_params p = m_parameters.to_c();
         if (line_mode_ >= 0) {
             run_levels(p);
             return;
@@ -807,6 +833,14 @@ public:
     }
     void get_results(std::vector<float>& out_map_s_v_u, std::vector<uint8_t>& out_validity_s_v_u) const
     {
+        if (run_) {   // a kept run: the fused planes come from the device
+            const size_t n = (size_t)dim_s_ * dim_v_ * dim_u_;
+            out_map_s_v_u.resize(n);
+            out_validity_s_v_u.resize(n);
+            check(rslf_f2c_run_copy(run_, 0, RSLF_F2C_PLANE_FUSED_MAP, out_map_s_v_u.data(), 1, nullptr), "rslf_f2c_run_copy");
+            check(rslf_f2c_run_copy(run_, 0, RSLF_F2C_PLANE_FUSED_VALID, out_validity_s_v_u.data(), 1, nullptr), "rslf_f2c_run_copy");
+            return;
+        }
         out_map_s_v_u = out_map_s_v_u_;
         out_validity_s_v_u = out_validity_s_v_u_;
     }
@@ -817,6 +851,11 @@ public:
     // (into a volume of its own, as the constructor's copy would): their buffers must outlive this call.
     std::vector<uint8_t> get_coloured_depth_maps(Context& on, const uint8_t* lut_bgr, bool saturate = true) const
     {
+        if (run_) {   // rendered on the device from the kept planes; the shadow cut reads the kept level-0 volume
+            std::vector<uint8_t> out((size_t)dim_s_ * dim_v_ * dim_u_ * 3);
+            check(rslf_f2c_run_render_depth_maps_host(run_, on.get(), saturate ? 1 : 0, lut_bgr, out.data()), "rslf_f2c_run_render_depth_maps_host");
+            return out;
+        }
         int mid = 0;
         check(rslf_render_centre_index(dim_s_, &mid), "get_coloured_depth_maps");
         detail::require(!out_map_s_v_u_.empty(), "the getters show the results of run(): call it first");
@@ -838,18 +877,29 @@ public:
         return get_coloured_depth_maps(detail::own(ctx_), lut_bgr, saturate);
     }
     int pyramid_depth() const { return n_levels_; }
-    // After a run() that followed set_line_confidence_mode: the level sizes (V_p, U_p), finest first, and every level's
-    // [S][V_p][U_p] disparities, validity mask and line confidence (empty planes with RSLF_LINE_CONF_OFF).
+    // After a run() that followed set_line_confidence_mode or keep_on_device: the level sizes (V_p, U_p), finest first, and
+    // every level's [S][V_p][U_p] disparities, validity mask and line confidence (empty planes with RSLF_LINE_CONF_OFF).
+    // A kept run copies a kind of plane out of the device when it is first asked for, and has the disparity confidence too.
     const std::vector<std::pair<int, int> >& pyramid_dims() const { return dims_; }
-    const std::vector<std::vector<float> >& get_depths_pyr() const { return depths_pyr_; }
-    const std::vector<std::vector<uint8_t> >& get_validity_pyr() const { return validity_pyr_; }
-    const std::vector<std::vector<float> >& get_line_confidence_pyr() const { return line_confidence_pyr_; }
+    const std::vector<std::vector<float> >& get_depths_pyr() const { return kept_pyr(depths_pyr_, RSLF_F2C_PLANE_DEPTH); }
+    const std::vector<std::vector<uint8_t> >& get_validity_pyr() const { return kept_pyr(validity_pyr_, RSLF_F2C_PLANE_VALID); }
+    const std::vector<std::vector<float> >& get_line_confidence_pyr() const
+    {
+        return (run_ && line_mode_ <= RSLF_LINE_CONF_OFF) ? line_confidence_pyr_ : kept_pyr(line_confidence_pyr_, RSLF_F2C_PLANE_CL);
+    }
+    const std::vector<std::vector<float> >& get_disp_confidence_pyr() const
+    {
+        detail::require(run_ != nullptr, "get_disp_confidence_pyr: the disparity confidence of every level is held by a kept run (keep_on_device)");
+        return kept_pyr(disp_confidence_pyr_, RSLF_F2C_PLANE_CD);
+    }
     // rslf_fine_to_coarse.hpp:491-519: view s (-1: (int)std::round(S / 2.0)) of every level, finest first, through the
     // converter fitted on level 0's plane before any masking; black outside each level's validity; no shadow cut ->
     // one [V_p][U_p][3] picture per level.  Throws where the reference's index runs off the end (S = 1).
     std::vector<std::vector<uint8_t> > get_coloured_depth_pyr(Context& on, int s, const uint8_t* lut_bgr, bool saturate = true) const
     {
-        detail::require(!depths_pyr_.empty(), "get_coloured_depth_pyr shows the levels of a run() after set_line_confidence_mode");
+        if (run_)
+            return kept_pictures(on, s, lut_bgr, saturate, false);
+        detail::require(!depths_pyr_.empty(), "get_coloured_depth_pyr shows the levels of a run() after set_line_confidence_mode or keep_on_device");
         if (s == -1)
             check(rslf_render_centre_index(dim_s_, &s), "get_coloured_depth_pyr");
         detail::require(s >= 0 && s < dim_s_, "get_coloured_depth_pyr: the view is not below dim_s");
@@ -870,6 +920,19 @@ public:
     {
         return get_coloured_depth_pyr(detail::own(ctx_), s, lut_bgr, saturate);
     }
+    // rslf_fine_to_coarse.hpp:432-488, of a kept run: the S x U_p slice of every level at scanline
+    // (int)std::round(1.0 * v * V_p / V_0) (v = -1: (int)std::round(V_0 / 2.0)), finest first; invalid pixels count as 0 in the
+    // fit (level 0) and in the render; with par_cut_shadows the shadow cut against the level's own kept volume -> one
+    // [S][U_p][3] picture per level.  Throws where the reference's row index reaches V_p.
+    std::vector<std::vector<uint8_t> > get_coloured_epi_pyr(Context& on, int v, const uint8_t* lut_bgr, bool saturate = true) const
+    {
+        detail::require(run_ != nullptr, "get_coloured_epi_pyr reads every level's planes and volume on the device: call keep_on_device before run()");
+        return kept_pictures(on, v, lut_bgr, saturate, true);
+    }
+    std::vector<std::vector<uint8_t> > get_coloured_epi_pyr(int v, const uint8_t* lut_bgr, bool saturate = true) const
+    {
+        return get_coloured_epi_pyr(detail::own(ctx_), v, lut_bgr, saturate);
+    }
     rslf_stats stats;
 
 private:
@@ -878,9 +941,62 @@ private:
                  int max_pyr_depth, bool accept_all_last_scale)
         : ctx_(ctx), multi_(multi), epis_(epis, epis + dim_v), type_(type), dim_v_(dim_v), dim_s_(dim_s), dim_u_(dim_u),
           stride_(row_stride_bytes), d_min_(d_min), d_max_(d_max), dim_d_(dim_d), scale_(epi_scale_factor),
-          m_parameters(parameters), max_pyr_depth_(max_pyr_depth), accept_all_(accept_all_last_scale), n_levels_(0), line_mode_(-1)
+          m_parameters(parameters), max_pyr_depth_(max_pyr_depth), accept_all_(accept_all_last_scale), n_levels_(0), line_mode_(-1),
+          keep_(false), keep_volumes_(true), validity_rule_(RSLF_F2C_VALID_COMPAT), run_(nullptr)
     {
         stats = rslf_stats();
+    }
+    // run() through rslf_f2c_run_host: the run stays on the device, this object owns the handle
+    void run_kept(const rslf_params& p)
+    {
+        rslf_f2c_run_destroy(run_);
+        run_ = nullptr;
+        out_map_s_v_u_.clear();
+        out_validity_s_v_u_.clear();
+        depths_pyr_.clear();
+        validity_pyr_.clear();
+        line_confidence_pyr_.clear();
+        disp_confidence_pyr_.clear();
+        dims_.clear();
+        const int elem = type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32;
+        check(rslf_f2c_run_host(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_, &p,
+                                max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
+                                keep_volumes_ ? 1 : 0, &run_, &stats),
+              "rslf_f2c_run_host");
+        rslf_f2c_run_desc d;
+        check(rslf_f2c_run_describe(run_, &d), "rslf_f2c_run_describe");
+        n_levels_ = d.n_levels;
+        for (int l = 0; l < d.n_levels; l++)
+            dims_.push_back(std::make_pair(d.V[l], d.U[l]));
+    }
+    // one kind of plane of every level of a kept run, copied out when first asked for; without a kept run, what run() left
+    template <typename T>
+    const std::vector<std::vector<T> >& kept_pyr(std::vector<std::vector<T> >& pyr, int which) const
+    {
+        if (!run_ || !pyr.empty())
+            return pyr;
+        std::vector<std::vector<T> > planes(dims_.size());
+        for (size_t l = 0; l < dims_.size(); l++) {
+            planes[l].resize((size_t)dim_s_ * dims_[l].first * dims_[l].second);
+            check(rslf_f2c_run_copy(run_, (int)l, which, planes[l].data(), 1, nullptr), "rslf_f2c_run_copy");
+        }
+        pyr.swap(planes);
+        return pyr;
+    }
+    // get_coloured_depth_pyr / get_coloured_epi_pyr of a kept run, one picture per level
+    std::vector<std::vector<uint8_t> > kept_pictures(Context& on, int index, const uint8_t* lut_bgr, bool saturate, bool epi) const
+    {
+        std::vector<std::vector<uint8_t> > out(dims_.size());
+        std::vector<uint8_t*> ptrs(dims_.size());
+        for (size_t l = 0; l < dims_.size(); l++) {
+            out[l].resize((size_t)(epi ? dim_s_ : dims_[l].first) * dims_[l].second * 3);
+            ptrs[l] = out[l].data();
+        }
+        if (epi)
+            check(rslf_f2c_run_render_epi_pyr_host(run_, on.get(), index, saturate ? 1 : 0, lut_bgr, ptrs.data()), "rslf_f2c_run_render_epi_pyr_host");
+        else
+            check(rslf_f2c_run_render_depth_pyr_host(run_, on.get(), index, saturate ? 1 : 0, lut_bgr, ptrs.data()), "rslf_f2c_run_render_depth_pyr_host");
+        return out;
     }
     // run() through rslf_fine_to_coarse_run_host_lc / _u16_lc, every level's planes kept
     void run_levels(const rslf_params& p)
@@ -948,8 +1064,11 @@ private:
     std::vector<float> out_map_s_v_u_;
     std::vector<uint8_t> out_validity_s_v_u_;
     std::vector<std::pair<int, int> > dims_;
-    std::vector<std::vector<float> > depths_pyr_, line_confidence_pyr_;
-    std::vector<std::vector<uint8_t> > validity_pyr_;
+    mutable std::vector<std::vector<float> > depths_pyr_, line_confidence_pyr_, disp_confidence_pyr_;   // (filled by the const getters of a kept run)
+    mutable std::vector<std::vector<uint8_t> > validity_pyr_;
+    bool keep_, keep_volumes_;   // keep_on_device
+    int validity_rule_;
+    rslf_f2c_run* run_;          // the kept run, owned
 };
 
 typedef Depth1DComputer_pile<1> Depth1DComputer_pile_1ch;   // dc.hpp:149

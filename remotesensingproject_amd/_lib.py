@@ -42,6 +42,10 @@ SYMBOLS = [
     "rslf_line_confidence_pile", "rslf_sweep_line_confidence", "rslf_depth_epi_2d_lc", "rslf_depth2d_run_lc", "rslf_depth2d_run_host_lc",
     # fine-to-coarse with the line confidence
     "rslf_f2c_pyramid_dims", "rslf_fine_to_coarse_run_host_lc", "rslf_fine_to_coarse_run_host_u16_lc",
+    # fine-to-coarse kept on the device
+    "rslf_f2c_run_host", "rslf_f2c_run_destroy", "rslf_f2c_run_describe", "rslf_f2c_run_copy", "rslf_f2c_run_volume",
+    "rslf_f2c_run_render_depth_maps", "rslf_f2c_run_render_depth_maps_host", "rslf_f2c_run_render_depth_pyr",
+    "rslf_f2c_run_render_depth_pyr_host", "rslf_f2c_run_render_epi_pyr", "rslf_f2c_run_render_epi_pyr_host",
 ]
 
 
@@ -98,6 +102,20 @@ class RslfF2cLevelsOut(C.Structure):
         ("h_valid_svu", C.POINTER(C.c_void_p)),
         ("h_Cl_svu", C.POINTER(C.c_void_p)),
         ("h_Ce_svu", C.POINTER(C.c_void_p)),
+    ]
+
+
+F2C_MAX_LEVELS = 32   # RSLF_F2C_MAX_LEVELS
+
+
+class RslfF2cRunDesc(C.Structure):
+    """rslf_f2c_run_desc: what a kept fine-to-coarse run holds."""
+
+    _fields_ = [
+        ("n_levels", C.c_int), ("S", C.c_int), ("C", C.c_int), ("device", C.c_int), ("elem", C.c_int), ("line_mode", C.c_int),
+        ("validity_rule", C.c_int), ("keep_volumes", C.c_int), ("planes_held", C.c_uint),
+        ("V", C.c_int * F2C_MAX_LEVELS), ("U", C.c_int * F2C_MAX_LEVELS), ("epi_scale_factor", C.c_float * F2C_MAX_LEVELS),
+        ("device_bytes", C.c_size_t),
     ]
 
 
@@ -206,6 +224,18 @@ def lib():
     L.rslf_f2c_pyramid_dims.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(ci)]
     L.rslf_fine_to_coarse_run_host_lc.argtypes = L.rslf_fine_to_coarse_run_host.argtypes + [ci, C.POINTER(RslfF2cLevelsOut)]
     L.rslf_fine_to_coarse_run_host_u16_lc.argtypes = L.rslf_fine_to_coarse_run_host_u16.argtypes + [ci, C.POINTER(RslfF2cLevelsOut)]
+    L.rslf_f2c_run_host.argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.c_size_t, cf, cf, ci, cf, C.POINTER(RslfParams), ci, ci, ci, ci, ci,
+                                    C.POINTER(vp), C.POINTER(RslfStats)]
+    L.rslf_f2c_run_destroy.argtypes = [vp]
+    L.rslf_f2c_run_describe.argtypes = [vp, C.POINTER(RslfF2cRunDesc)]
+    L.rslf_f2c_run_copy.argtypes = [vp, ci, ci, vp, ci, vp]
+    L.rslf_f2c_run_volume.argtypes = [vp, ci, C.POINTER(vp)]
+    L.rslf_f2c_run_render_depth_maps.argtypes = [vp, vp, ci, vp, vp]
+    L.rslf_f2c_run_render_depth_maps_host.argtypes = L.rslf_f2c_run_render_depth_maps.argtypes
+    L.rslf_f2c_run_render_depth_pyr.argtypes = [vp, vp, ci, ci, vp, C.POINTER(vp)]
+    L.rslf_f2c_run_render_depth_pyr_host.argtypes = L.rslf_f2c_run_render_depth_pyr.argtypes
+    L.rslf_f2c_run_render_epi_pyr.argtypes = L.rslf_f2c_run_render_depth_pyr.argtypes
+    L.rslf_f2c_run_render_epi_pyr_host.argtypes = L.rslf_f2c_run_render_depth_pyr.argtypes
     L.rslf_f2c_level_dims.argtypes = [ci, ci, C.POINTER(ci), C.POINTER(ci)]
     L.rslf_downsample_epis_f32.argtypes = [vp, vp, ci, ci, ci, ci, vp]
     L.rslf_downsample_epis_u8.argtypes = [vp, vp, ci, ci, ci, ci, vp]

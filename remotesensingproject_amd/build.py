@@ -28,6 +28,7 @@ UNITS = {
     "rslf_chip_c.hip": ["k2_scan.hpp", "k2_chip.hpp"],
     "rslf_sweep.hip": ["k3_median.hpp", "k4_propagate.hpp", "k_compact.hpp", "k2_scan.hpp", "k7_line_conf.hpp"],
     "rslf_f2c.hip": ["k5_f2c.hpp"],
+    "rslf_f2c_keep.hip": [],
     "rslf_render.hip": ["k6_render.hpp", "rslf_plan_render.hpp"],
     "rslf_multi.hip": [],
     "rslf_multi_sweep.hip": [],

@@ -304,8 +304,8 @@ extern "C" int rslf_volume_create(rslf_ctx* ctx, int V, int S, int U, int C, rsl
     vol->S = S;
     vol->U = U;
     vol->C = C;
-    vol->pitch = ((U + 1 + 63) / 64) * 64;   // pixels per row, > U: the second lerp tap of u = U-1 lands on zeros
-    vol->bytes = (size_t)V * S * C * vol->pitch * sizeof(float);
+    vol->pitch = plan::volume_pitch(U);   // pixels per row, > U: the second lerp tap of u = U-1 lands on zeros
+    vol->bytes = plan::volume_bytes(V, S, U, C);
     hipError_t e = hipMalloc(&vol->base, vol->bytes);
     if (e != hipSuccess) {
         delete vol;

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <stdexcept>
 
 #include "k5_f2c.hpp"
 
@@ -199,8 +200,8 @@ __global__ __launch_bounds__(256) void k_fill_f32(float* __restrict__ out, long 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         out[i] = value;
 }
-// get_valid_depths_mask_s_v_u (dc.hpp:893-915): a confidence plane > thr -- C_e, or C_l where plan::f2c_validity says so;
-// everything (C_e > -1) with accept_all
+// get_valid_depths_mask_s_v_u (dc.hpp:893-915): a confidence plane > thr -- C_e, or C_l / C_d where
+// plan::f2c_validity_by_rule says so; everything (C_e > -1) with accept_all
 __global__ __launch_bounds__(256) void k_valid_mask(const float* __restrict__ conf, uint8_t* __restrict__ out, long long n, float thr)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
@@ -286,11 +287,15 @@ static int f2c_valid_mask(hipStream_t st, const float* conf, uint8_t* out, size_
 int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
                          float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                          int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
-                         int line_mode, const rslf_f2c_levels_out* levels_out,
+                         int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep,
                          const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep)
 {
-    if (!ctx || !h_epis || !h_out_map_svu || !h_out_valid_svu || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
+    if (!ctx || !h_epis || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    if (!keep && (!h_out_map_svu || !h_out_valid_svu))   // a kept run holds the fused planes itself
+        return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    if (!plan::f2c_validity_rule_ok(validity_rule) || (!keep && validity_rule != RSLF_F2C_VALID_COMPAT))
+        return fail(RSLF_ERR_INVALID_ARG, "validity rule %d: RSLF_F2C_VALID_COMPAT or, for a kept run, _REFERENCE", validity_rule);
     if (!plan::line_conf_mode_ok(line_mode))
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
     int rc = check_params(p);
@@ -312,21 +317,25 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         return rc;
 
     // run(): rslf_fine_to_coarse.hpp:171-299, each level built just before its sweep; every level keeps its disparities
-    // and validity for the fusion
-    std::vector<DevBuf> depth(P), valid(P);
+    // and validity for the fusion -- and everything else where the caller owns the planes
+    F2cKept own;
+    F2cKept& K = keep ? *keep : own;
+    K.levels = std::vector<F2cKeptLevel>((size_t)P);
     int64_t pixels = 0;
     rslf_stats st1;
     memset(&st1, 0, sizeof(st1));
     for (int l = 0; l < P; l++) {
+        F2cKeptLevel& kl = K.levels[(size_t)l];
         F2cLevel lv;
-        lv.V = dims[l].V;
-        lv.U = dims[l].U;
+        lv.V = kl.V = dims[l].V;
+        lv.U = kl.U = dims[l].U;
         lv.params = *p;
         lv.params.slope_factor = (float)((0.0 + lv.U) / U);              // f2c.hpp:139
         const size_t n = (size_t)S * lv.V * lv.U;
         rc = f2c_level_scale(ctx, elem, raw.as<const float>(), n * C, epi_scale_factor, &lv.scale);
         if (rc)
             return rc;
+        kl.scale = lv.scale;
         DevBuf next;                                                       // f2c.hpp:145-147: the RAW EPIs go down
         if (l + 1 < P) {
             HIP_TRY(next.alloc((size_t)dims[l + 1].V * S * dims[l + 1].U * C * sizeof(float)));
@@ -334,12 +343,15 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             if (rc)
                 return rc;
         }
-        DevBuf Ce, Cl, dmin, dmax;
+        DevBuf dmin, dmax;
+        DevBuf &Ce = kl.Ce, &Cl = kl.Cl;
         HIP_TRY(Ce.alloc(n * 4));
         if (line_mode != RSLF_LINE_CONF_OFF)
             HIP_TRY(Cl.alloc(n * 4));   // dc.hpp:721-738: every level's computer has a plane of its own
-        HIP_TRY(depth[l].alloc(n * 4));
-        HIP_TRY(valid[l].alloc(n));
+        HIP_TRY(kl.depth.alloc(n * 4));
+        HIP_TRY(kl.valid.alloc(n));
+        if (keep)
+            HIP_TRY(kl.Cd.alloc(n * 4));
         if (l > 0) {
             HIP_TRY(dmin.alloc(n * 4));
             HIP_TRY(dmax.alloc(n * 4));
@@ -347,8 +359,9 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             if (!rc)
                 rc = f2c_fill_f32(st, dmax.as<float>(), n, d_max);
             if (!rc)
-                rc = rslf_f2c_tighten_bounds(ctx, depth[l - 1].as<const float>(), valid[l - 1].as<const uint8_t>(), S, dims[l - 1].V,
-                                             dims[l - 1].U, dmin.as<float>(), dmax.as<float>(), lv.V, lv.U);
+                rc = rslf_f2c_tighten_bounds(ctx, K.levels[(size_t)l - 1].depth.as<const float>(),
+                                             K.levels[(size_t)l - 1].valid.as<const uint8_t>(), S, dims[l - 1].V, dims[l - 1].U,
+                                             dmin.as<float>(), dmax.as<float>(), lv.V, lv.U);
             if (rc)
                 return rc;
         }
@@ -356,24 +369,30 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         lv.dmin_svu = dmin.as<const float>();
         lv.dmax_svu = dmax.as<const float>();
         lv.Ce_svu = Ce.as<float>();
-        lv.depth_svu = depth[l].as<float>();
+        lv.depth_svu = kl.depth.as<float>();
         lv.line_mode = line_mode;
         lv.Cl_svu = Cl.as<float>();
+        lv.Cd_svu = kl.Cd.as<float>();
+        lv.vol_out = (keep && keep->keep_volumes) ? &kl.vol : nullptr;
         rc = sweep(lv, &st1);
         if (rc)
             return rc;
         pixels += st1.pixels_scanned;
         // get_valid_depths_mask_s_v_u (dc.hpp:893-915), asked for by the next level's bounds (f2c.hpp:185-186) and by the
         // fusion (:312): the last level accepts everything when asked to (f2c.hpp:157-158)
-        switch (plan::f2c_validity(accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0, line_mode)) {
+        switch (plan::f2c_validity_by_rule(accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0, line_mode,
+                                           validity_rule)) {
         case plan::kValidAll:
-            rc = f2c_valid_mask(st, Ce.as<const float>(), valid[l].as<uint8_t>(), n, -1.0f);
+            rc = f2c_valid_mask(st, Ce.as<const float>(), kl.valid.as<uint8_t>(), n, -1.0f);
             break;
         case plan::kValidLineConf:
-            rc = f2c_valid_mask(st, Cl.as<const float>(), valid[l].as<uint8_t>(), n, p->line_score_threshold);
+            rc = f2c_valid_mask(st, Cl.as<const float>(), kl.valid.as<uint8_t>(), n, p->line_score_threshold);
             break;
         case plan::kValidEdgeConf:
-            rc = f2c_valid_mask(st, Ce.as<const float>(), valid[l].as<uint8_t>(), n, p->edge_score_threshold);
+            rc = f2c_valid_mask(st, Ce.as<const float>(), kl.valid.as<uint8_t>(), n, p->edge_score_threshold);
+            break;
+        case plan::kValidDispConf:   // the REFERENCE rule alone, so a kept run: C_d is the owner's (dc.hpp:902)
+            rc = f2c_valid_mask(st, kl.Cd.as<const float>(), kl.valid.as<uint8_t>(), n, p->disp_score_threshold);
             break;
         }
         if (rc)
@@ -382,11 +401,15 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             const auto out = [&](void* const* hp, const void* d, size_t bytes) -> hipError_t {
                 return (hp && hp[l] && d) ? hipMemcpyAsync(hp[l], d, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
             };
-            HIP_TRY(out((void* const*)levels_out->h_depth_svu, depth[l].get(), n * 4));
-            HIP_TRY(out((void* const*)levels_out->h_valid_svu, valid[l].get(), n));
+            HIP_TRY(out((void* const*)levels_out->h_depth_svu, kl.depth.get(), n * 4));
+            HIP_TRY(out((void* const*)levels_out->h_valid_svu, kl.valid.get(), n));
             HIP_TRY(out((void* const*)levels_out->h_Cl_svu, Cl.get(), n * 4));
             HIP_TRY(out((void* const*)levels_out->h_Ce_svu, Ce.get(), n * 4));
             HIP_TRY(hipStreamSynchronize(st));
+        }
+        if (!keep) {            // the level's confidences have served
+            Cl.release();
+            Ce.release();
         }
         std::swap(raw, next);   // `next` now frees this level's raw volume
     }
@@ -396,20 +419,22 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     std::vector<const uint8_t*> vp(P);
     std::vector<int> Vp(P), Up(P);
     for (int l = 0; l < P; l++) {
-        dp[l] = depth[l].as<const float>();
-        vp[l] = valid[l].as<const uint8_t>();
+        dp[l] = K.levels[(size_t)l].depth.as<const float>();
+        vp[l] = K.levels[(size_t)l].valid.as<const uint8_t>();
         Vp[l] = dims[l].V;
         Up[l] = dims[l].U;
     }
     const size_t n0 = (size_t)S * V * U;
-    DevBuf omap, ovalid;
+    DevBuf &omap = K.fused_map, &ovalid = K.fused_valid;
     HIP_TRY(omap.alloc(n0 * 4));
     HIP_TRY(ovalid.alloc(n0));
     rc = rslf_f2c_fuse(ctx, dp.data(), vp.data(), Vp.data(), Up.data(), P, S, omap.as<float>(), ovalid.as<uint8_t>());
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.get(), n0 * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_out_valid_svu, ovalid.get(), n0, hipMemcpyDeviceToHost, st));
+    if (h_out_map_svu)
+        HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.get(), n0 * 4, hipMemcpyDeviceToHost, st));
+    if (h_out_valid_svu)
+        HIP_TRY(hipMemcpyAsync(h_out_valid_svu, ovalid.get(), n0, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n_levels)
         *n_levels = P;
@@ -422,30 +447,38 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
 }
 
 // FineToCoarse on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run_lc.
-static int fine_to_coarse_run_host(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C,
-                                   size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
-                                   const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
-                                   uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats, int line_mode,
-                                   const rslf_f2c_levels_out* levels_out)
+int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C,
+                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
+                                     uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats, int line_mode,
+                                     const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep)
 {
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
+        if (inject_hit(kInjectSweep))   // host side, before the level's sweep is queued
+            throw std::runtime_error("injected failure in a fine-to-coarse level (rslf_debug_inject)");
         const size_t n = (size_t)S * lv.V * lv.U;
         DevBuf Cd, rbar, mask;
-        HIP_TRY(Cd.alloc(n * 4));
+        if (!lv.Cd_svu)   // a kept run's C_d is its owner's
+            HIP_TRY(Cd.alloc(n * 4));
         HIP_TRY(rbar.alloc(n * 4 * C));
         HIP_TRY(mask.alloc(n));
-        rslf_volume* vol = nullptr;
-        int rc = rslf_volume_create(ctx, lv.V, S, lv.U, C, &vol);
+        VolumePtr vol;
+        rslf_volume* made = nullptr;
+        int rc = rslf_volume_create(ctx, lv.V, S, lv.U, C, &made);
+        vol.reset(made);
         if (!rc)
-            rc = rslf_volume_pack_device_f32(vol, lv.raw_vsuc, lv.scale, nullptr);
+            rc = rslf_volume_pack_device_f32(vol.get(), lv.raw_vsuc, lv.scale, nullptr);
         if (!rc)
-            rc = depth2d_run_lc(ctx, vol, lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, mask.as<uint8_t>(),
-                                Cd.as<float>(), lv.depth_svu, rbar.as<float>(), nullptr, level_stats, lv.line_mode, lv.Cl_svu);
-        rslf_volume_destroy(vol);
+            rc = depth2d_run_lc(ctx, vol.get(), lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, mask.as<uint8_t>(),
+                                lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(), nullptr, level_stats,
+                                lv.line_mode, lv.Cl_svu);
+        if (!rc && lv.vol_out)
+            *lv.vol_out = std::move(vol);   // kept; otherwise destroyed here, with the sweep's other planes
         return rc;
     };
     return fine_to_coarse(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, line_mode, levels_out, sweep);
+                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, line_mode, levels_out, validity_rule,
+                          keep, sweep);
 }
 
 extern "C" int rslf_f2c_pyramid_dims(int V, int U, int max_pyr_depth, int* Vp, int* Up, int capacity, int* n_levels) RSLF_API_TRY
@@ -470,9 +503,9 @@ extern "C" int rslf_fine_to_coarse_run_host_lc(rslf_ctx* ctx, const void* const*
                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
                                                int line_mode, const rslf_f2c_levels_out* levels_out) RSLF_API_TRY
 {
-    return fine_to_coarse_run_host(ctx, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
-                                   stats, line_mode, levels_out);
+    return fine_to_coarse_one_context(ctx, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                      epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
+                                      stats, line_mode, levels_out, RSLF_F2C_VALID_COMPAT, nullptr);
 }
 RSLF_API_CATCH
 
@@ -483,9 +516,9 @@ extern "C" int rslf_fine_to_coarse_run_host_u16_lc(rslf_ctx* ctx, const uint16_t
                                                    int* n_levels, rslf_stats* stats, int line_mode,
                                                    const rslf_f2c_levels_out* levels_out) RSLF_API_TRY
 {
-    return fine_to_coarse_run_host(ctx, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                   epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
-                                   stats, line_mode, levels_out);
+    return fine_to_coarse_one_context(ctx, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
+                                      epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
+                                      stats, line_mode, levels_out, RSLF_F2C_VALID_COMPAT, nullptr);
 }
 RSLF_API_CATCH
 

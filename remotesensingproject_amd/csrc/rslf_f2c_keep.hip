@@ -1,0 +1,409 @@
+// A finished fine-to-coarse run kept on the device (include/rslf_hip.h, "fine-to-coarse kept on the device"): rslf_f2c_run
+// owns what the level loop of rslf_f2c.hip allocates (F2cKept), hands planes out by copy, and renders the three coloured
+// getters of rslf_fine_to_coarse.hpp:325-519 from them with the renderers of rslf_render.hip.  No kernels of its own.
+#include "rslf_internal.hpp"
+
+using namespace rslf;
+
+namespace {
+
+int elem_of(int elem, Elem* out)
+{
+    switch (elem) {
+    case RSLF_ELEM_F32:
+        *out = Elem::F32;
+        return RSLF_OK;
+    case RSLF_ELEM_U8:
+        *out = Elem::U8;
+        return RSLF_OK;
+    case RSLF_ELEM_U16:
+        *out = Elem::U16;
+        return RSLF_OK;
+    }
+    return fail(RSLF_ERR_INVALID_ARG, "element type %d: RSLF_ELEM_F32, _U8 or _U16", elem);
+}
+
+// A plane of the run: where it lies and how many bytes it has; NULL if it is not held.
+const void* plane_of(const rslf_f2c_run* run, int level, int which, size_t* bytes)
+{
+    const F2cKeptLevel& kl = run->kept.levels[(size_t)level];
+    const size_t n = (size_t)run->S * kl.V * kl.U;
+    *bytes = n * sizeof(float);
+    switch (which) {
+    case RSLF_F2C_PLANE_DEPTH:
+        return kl.depth.get();
+    case RSLF_F2C_PLANE_VALID:
+        *bytes = n;
+        return kl.valid.get();
+    case RSLF_F2C_PLANE_CE:
+        return kl.Ce.get();
+    case RSLF_F2C_PLANE_CD:
+        return kl.Cd.get();
+    case RSLF_F2C_PLANE_CL:
+        return kl.Cl.get();
+    case RSLF_F2C_PLANE_FUSED_MAP:
+        return run->kept.fused_map.get();
+    case RSLF_F2C_PLANE_FUSED_VALID:
+        *bytes = n;
+        return run->kept.fused_valid.get();
+    }
+    return nullptr;
+}
+
+int check_render_args(const rslf_f2c_run* run, const rslf_ctx* ctx, const void* lut_bgr, const void* out)
+{
+    if (!run || !ctx || !lut_bgr || !out)
+        return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    if (ctx->device != run->device)
+        return fail(RSLF_ERR_INVALID_ARG, "the run lives on device %d, the context on device %d", run->device, ctx->device);
+    return RSLF_OK;
+}
+
+// The volume of the getters' shadow cut (f2c.hpp:360-372, :466-481) as the renderers take it: a non-owning copy of the
+// kept volume's description that names the rendering context (the context the run was made on may be gone).
+int shadow_volume(const rslf_f2c_run* run, rslf_ctx* ctx, int level, rslf_volume* view, const rslf_volume** out)
+{
+    *out = nullptr;
+    if (!run->params.cut_shadows)
+        return RSLF_OK;
+    const rslf_volume* vol = run->kept.levels[(size_t)level].vol.get();
+    if (!vol)
+        return fail(RSLF_ERR_INVALID_ARG, "the run was made with cut_shadows but without keep_volumes: the shadow cut reads the "
+                                          "level's volume, which was not kept");
+    *view = *vol;
+    view->ctx = ctx;
+    *out = view;
+    return RSLF_OK;
+}
+
+int fit_mode(int saturate) { return saturate ? RSLF_FIT_QUANTILE : RSLF_FIT_MEANSTD; }   // ImageConverter_uchar::fit(img, saturate)
+
+// One picture of a getter: where it goes in the caller's memory and how large it is.
+struct Picture {
+    uint8_t* dst;
+    size_t bytes;
+};
+
+// The pictures are rendered into the caller's device memory, or -- host form -- into the context's staging buffer and copied
+// out from there; `pics` holds the caller's pointers, `targets` gets the device pointers to render into.
+int stage_pictures(rslf_ctx* ctx, bool host, const std::vector<Picture>& pics, std::vector<uint8_t*>* targets)
+{
+    targets->resize(pics.size());
+    size_t total = 0;
+    for (const Picture& p : pics)
+        total += p.bytes;
+    void* stage = nullptr;
+    if (host) {
+        int rc = helper_scratch(ctx, kSharedStageOut, total, &stage);
+        if (rc)
+            return rc;
+    }
+    size_t o = 0;
+    for (size_t i = 0; i < pics.size(); i++) {
+        (*targets)[i] = host ? (uint8_t*)stage + o : pics[i].dst;
+        o += pics[i].bytes;
+    }
+    return RSLF_OK;
+}
+
+int deliver_pictures(rslf_ctx* ctx, bool host, const std::vector<Picture>& pics, const std::vector<uint8_t*>& targets)
+{
+    if (!host)
+        return RSLF_OK;   // enqueued, not awaited
+    for (size_t i = 0; i < pics.size(); i++)
+        HIP_TRY(hipMemcpyAsync(pics[i].dst, targets[i], pics[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RSLF_OK;
+}
+
+// get_coloured_depth_maps, rslf_fine_to_coarse.hpp:325-378
+int render_depth_maps(const rslf_f2c_run* run, rslf_ctx* ctx, int saturate, const uint8_t* lut_bgr, uint8_t* out, bool host)
+{
+    int rc = check_render_args(run, ctx, lut_bgr, out);
+    if (rc)
+        return rc;
+    const F2cKeptLevel& l0 = run->kept.levels[0];
+    const int S = run->S, V = l0.V, U = l0.U;
+    int mid = 0;
+    rc = rslf_render_centre_index(S, &mid);   // :344
+    if (rc)
+        return rc;
+    rslf_volume view;
+    const rslf_volume* vol = nullptr;
+    rc = shadow_volume(run, ctx, 0, &view, &vol);
+    if (rc)
+        return rc;
+    const std::vector<Picture> pics = {{out, (size_t)S * V * U * 3}};
+    std::vector<uint8_t*> target;
+    rc = stage_pictures(ctx, host, pics, &target);
+    if (rc)
+        return rc;
+    const float* map = run->kept.fused_map.as<const float>();
+    double lo = 0.0, hi = 0.0;
+    rc = rslf_render_fit(ctx, map + (size_t)mid * V * U, V, U, (size_t)U, nullptr, fit_mode(saturate), &lo, &hi);
+    if (!rc)
+        rc = rslf_render_planes(ctx, map, S, (size_t)V * U, V, U, (size_t)U, lo, hi, RSLF_RENDER_AFFINE, lut_bgr,
+                                run->kept.fused_valid.as<const uint8_t>(), RSLF_MASK_BLACK, vol, RSLF_SLICE_VIEW, 0,
+                                run->params.shadow_level, target[0]);
+    if (rc)
+        return rc;
+    return deliver_pictures(ctx, host, pics, target);
+}
+
+// get_coloured_depth_pyr, :491-519
+int render_depth_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int s, int saturate, const uint8_t* lut_bgr, uint8_t* const* out, bool host)
+{
+    int rc = check_render_args(run, ctx, lut_bgr, out);
+    if (rc)
+        return rc;
+    const int S = run->S, P = (int)run->kept.levels.size();
+    if (s == -1) {
+        rc = rslf_render_centre_index(S, &s);   // :497
+        if (rc)
+            return rc;
+    }
+    if (s < 0 || s >= S)
+        return fail(RSLF_ERR_INVALID_ARG, "view %d of %d", s, S);
+    std::vector<Picture> pics((size_t)P);
+    for (int l = 0; l < P; l++) {
+        if (!out[l])
+            return fail(RSLF_ERR_INVALID_ARG, "out[%d] is NULL", l);
+        pics[(size_t)l] = {out[l], (size_t)run->kept.levels[(size_t)l].V * run->kept.levels[(size_t)l].U * 3};
+    }
+    std::vector<uint8_t*> target;
+    rc = stage_pictures(ctx, host, pics, &target);
+    if (rc)
+        return rc;
+    double lo = 0.0, hi = 0.0;
+    for (int l = 0; l < P; l++) {
+        const F2cKeptLevel& kl = run->kept.levels[(size_t)l];
+        const size_t o = (size_t)s * kl.V * kl.U;
+        const float* plane = kl.depth.as<const float>() + o;
+        if (l == 0) {   // the converter is fitted on level 0's plane before any masking
+            rc = rslf_render_fit(ctx, plane, kl.V, kl.U, (size_t)kl.U, nullptr, fit_mode(saturate), &lo, &hi);
+            if (rc)
+                return rc;
+        }
+        rc = rslf_render_planes(ctx, plane, 1, 0, kl.V, kl.U, (size_t)kl.U, lo, hi, RSLF_RENDER_AFFINE, lut_bgr,
+                                kl.valid.as<const uint8_t>() + o, RSLF_MASK_BLACK, nullptr, RSLF_SLICE_VIEW, 0, 0.0f, target[(size_t)l]);
+        if (rc)
+            return rc;
+    }
+    return deliver_pictures(ctx, host, pics, target);
+}
+
+// get_coloured_epi_pyr, :432-488
+int render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, const uint8_t* lut_bgr, uint8_t* const* out, bool host)
+{
+    int rc = check_render_args(run, ctx, lut_bgr, out);
+    if (rc)
+        return rc;
+    const int S = run->S, P = (int)run->kept.levels.size(), V0 = run->kept.levels[0].V;
+    if (v == -1) {
+        rc = rslf_render_centre_index(V0, &v);
+        if (rc)
+            return rc;
+    }
+    std::vector<int> row((size_t)P);
+    std::vector<Picture> pics((size_t)P);
+    std::vector<rslf_volume> views((size_t)P);
+    std::vector<const rslf_volume*> vols((size_t)P, nullptr);
+    for (int l = 0; l < P; l++) {   // every refusal before anything is queued
+        const F2cKeptLevel& kl = run->kept.levels[(size_t)l];
+        rc = rslf_render_scaled_row(v, kl.V, V0, &row[(size_t)l]);   // :451
+        if (!rc)
+            rc = shadow_volume(run, ctx, l, &views[(size_t)l], &vols[(size_t)l]);
+        if (rc)
+            return rc;
+        if (!out[l])
+            return fail(RSLF_ERR_INVALID_ARG, "out[%d] is NULL", l);
+        pics[(size_t)l] = {out[l], (size_t)S * kl.U * 3};
+    }
+    std::vector<uint8_t*> target;
+    rc = stage_pictures(ctx, host, pics, &target);
+    if (rc)
+        return rc;
+    double lo = 0.0, hi = 0.0;
+    for (int l = 0; l < P; l++) {
+        const F2cKeptLevel& kl = run->kept.levels[(size_t)l];
+        const size_t o = (size_t)row[(size_t)l] * kl.U, stride = (size_t)kl.V * kl.U;   // row `row` of every view: an S x U_l plane
+        const float* plane = kl.depth.as<const float>() + o;
+        const uint8_t* valid = kl.valid.as<const uint8_t>() + o;
+        if (l == 0) {   // fitted on level 0, its invalid pixels counting as 0 (:458-459)
+            rc = rslf_render_fit(ctx, plane, S, kl.U, stride, valid, fit_mode(saturate), &lo, &hi);
+            if (rc)
+                return rc;
+        }
+        rc = rslf_render_planes(ctx, plane, 1, 0, S, kl.U, stride, lo, hi, RSLF_RENDER_AFFINE, lut_bgr, valid, RSLF_MASK_ZERO_VALUE,
+                                vols[(size_t)l], RSLF_SLICE_EPI, row[(size_t)l], run->params.shadow_level, target[(size_t)l]);
+        if (rc)
+            return rc;
+    }
+    return deliver_pictures(ctx, host, pics, target);
+}
+
+}  // namespace
+
+extern "C" int rslf_f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                                 float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                                 int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                                 rslf_stats* stats) RSLF_API_TRY
+{
+    if (!run)
+        return fail(RSLF_ERR_INVALID_ARG, "run is NULL");
+    *run = nullptr;
+    if (!ctx || !h_epis || !p)
+        return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    Elem e;
+    int rc = elem_of(elem, &e);
+    if (rc)
+        return rc;
+    if ((int)plan::f2c_pyramid(V, U, max_pyr_depth).size() > RSLF_F2C_MAX_LEVELS)
+        return fail(RSLF_ERR_UNSUPPORTED, "a pyramid deeper than %d levels", RSLF_F2C_MAX_LEVELS);
+    std::unique_ptr<rslf_f2c_run> r(new rslf_f2c_run());   // whatever path leaves this function, a run not handed out is freed
+    r->device = ctx->device;
+    r->S = S;
+    r->C = C;
+    r->elem = elem;
+    r->line_mode = line_mode;
+    r->validity_rule = validity_rule;
+    r->params = *p;
+    r->kept.keep_volumes = keep_volumes != 0;
+    rc = fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                                    accept_all_last_scale, nullptr, nullptr, nullptr, stats, line_mode, nullptr, validity_rule, &r->kept);
+    if (rc)
+        return rc;
+    *run = r.release();
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_destroy(rslf_f2c_run* run) RSLF_API_TRY
+{
+    if (!run)
+        return RSLF_OK;
+    (void)hipSetDevice(run->device);   // the frees wait for the device's outstanding work; no context is touched
+    delete run;
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_describe(const rslf_f2c_run* run, rslf_f2c_run_desc* out) RSLF_API_TRY
+{
+    if (!run || !out)
+        return fail(RSLF_ERR_INVALID_ARG, "run/out is NULL");
+    memset(out, 0, sizeof(*out));
+    const int P = (int)run->kept.levels.size();
+    out->n_levels = P;
+    out->S = run->S;
+    out->C = run->C;
+    out->device = run->device;
+    out->elem = run->elem;
+    out->line_mode = run->line_mode;
+    out->validity_rule = run->validity_rule;
+    out->keep_volumes = run->kept.keep_volumes ? 1 : 0;
+    std::vector<plan::LevelDims> dims;
+    for (int l = 0; l < P; l++) {
+        const F2cKeptLevel& kl = run->kept.levels[(size_t)l];
+        out->V[l] = kl.V;
+        out->U[l] = kl.U;
+        out->epi_scale_factor[l] = kl.scale;
+        dims.push_back(plan::LevelDims{kl.V, kl.U});
+    }
+    for (int which = RSLF_F2C_PLANE_DEPTH; which <= RSLF_F2C_PLANE_FUSED_VALID; which++) {
+        size_t bytes = 0;
+        if (P > 0 && plane_of(run, 0, which, &bytes))
+            out->planes_held |= 1u << which;
+    }
+    out->device_bytes = plan::f2c_kept_bytes(run->S, run->C, dims, run->line_mode, run->kept.keep_volumes);
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_copy(const rslf_f2c_run* run, int level, int which, void* dst, int dst_on_host, rslf_ctx* stream_ctx) RSLF_API_TRY
+{
+    if (!run || !dst)
+        return fail(RSLF_ERR_INVALID_ARG, "run/dst is NULL");
+    if (level < 0 || level >= (int)run->kept.levels.size())
+        return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
+    if (which < RSLF_F2C_PLANE_DEPTH || which > RSLF_F2C_PLANE_FUSED_VALID)
+        return fail(RSLF_ERR_INVALID_ARG, "plane %d: one of RSLF_F2C_PLANE_*", which);
+    if ((which == RSLF_F2C_PLANE_FUSED_MAP || which == RSLF_F2C_PLANE_FUSED_VALID) && level != 0)
+        return fail(RSLF_ERR_INVALID_ARG, "the fused planes are at the finest size: ask for them with level 0, not %d", level);
+    if (stream_ctx && stream_ctx->device != run->device)
+        return fail(RSLF_ERR_INVALID_ARG, "the run lives on device %d, the context on device %d", run->device, stream_ctx->device);
+    size_t bytes = 0;
+    const void* src = plane_of(run, level, which, &bytes);
+    if (!src)
+        return fail(RSLF_ERR_INVALID_ARG, "plane %d is not held by this run (C_l needs a line mode)", which);
+    HIP_TRY(hipSetDevice(run->device));
+    const hipMemcpyKind kind = dst_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (!stream_ctx) {
+        HIP_TRY(hipMemcpy(dst, src, bytes, kind));
+        HIP_TRY(hipDeviceSynchronize());
+        return RSLF_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, stream_ctx->stream));
+    if (dst_on_host)
+        HIP_TRY(hipStreamSynchronize(stream_ctx->stream));
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_volume(const rslf_f2c_run* run, int level, const rslf_volume** out) RSLF_API_TRY
+{
+    if (out)
+        *out = nullptr;
+    if (!run || !out)
+        return fail(RSLF_ERR_INVALID_ARG, "run/out is NULL");
+    if (level < 0 || level >= (int)run->kept.levels.size())
+        return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
+    const rslf_volume* vol = run->kept.levels[(size_t)level].vol.get();
+    if (!vol)
+        return fail(RSLF_ERR_INVALID_ARG, "the run was made without keep_volumes");
+    *out = vol;
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_render_depth_maps(const rslf_f2c_run* run, rslf_ctx* ctx, int saturate, const uint8_t* lut_bgr,
+                                              uint8_t* d_bgr_out) RSLF_API_TRY
+{
+    return render_depth_maps(run, ctx, saturate, lut_bgr, d_bgr_out, false);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_render_depth_maps_host(const rslf_f2c_run* run, rslf_ctx* ctx, int saturate, const uint8_t* lut_bgr,
+                                                   uint8_t* h_bgr_out) RSLF_API_TRY
+{
+    return render_depth_maps(run, ctx, saturate, lut_bgr, h_bgr_out, true);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_render_depth_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int s, int saturate, const uint8_t* lut_bgr,
+                                             uint8_t* const* d_bgr_out) RSLF_API_TRY
+{
+    return render_depth_pyr(run, ctx, s, saturate, lut_bgr, d_bgr_out, false);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_render_depth_pyr_host(const rslf_f2c_run* run, rslf_ctx* ctx, int s, int saturate, const uint8_t* lut_bgr,
+                                                  uint8_t* const* h_bgr_out) RSLF_API_TRY
+{
+    return render_depth_pyr(run, ctx, s, saturate, lut_bgr, h_bgr_out, true);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, const uint8_t* lut_bgr,
+                                           uint8_t* const* d_bgr_out) RSLF_API_TRY
+{
+    return render_epi_pyr(run, ctx, v, saturate, lut_bgr, d_bgr_out, false);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_render_epi_pyr_host(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, const uint8_t* lut_bgr,
+                                                uint8_t* const* h_bgr_out) RSLF_API_TRY
+{
+    return render_epi_pyr(run, ctx, v, saturate, lut_bgr, h_bgr_out, true);
+}
+RSLF_API_CATCH

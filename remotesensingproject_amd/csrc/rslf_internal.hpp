@@ -7,6 +7,7 @@
 //   rslf_chip_a/b/c.hip   the on-chip scan kernel's instantiations, one per rung of its ladder (launched by rslf_pile.hip)
 //   rslf_sweep.hip        the 2-D sweep and its propagation (K4), Depth2DComputer::run
 //   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the one native level loop
+//   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters
 //   rslf_render.hip       the getters' pictures: fit, plane render, EPI line painter (K6)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
@@ -28,6 +29,7 @@
 #include <cstring>
 #include <exception>
 #include <functional>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -412,6 +414,13 @@ int depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_sv
                    float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu);
 
 // rslf_f2c.hip
+// A volume owned by a scope or an object (rslf_volume_destroy is the one place that frees a slab).
+struct VolumeDeleter {
+    void operator()(rslf_volume* vol) const { rslf_volume_destroy(vol); }
+};
+struct VolumePtr : std::unique_ptr<rslf_volume, VolumeDeleter> {
+    using std::unique_ptr<rslf_volume, VolumeDeleter>::unique_ptr;
+};
 // One level of FineToCoarse as its sweep sees it, every pointer on the context's device.
 struct F2cLevel {
     int V = 0, U = 0;
@@ -424,16 +433,40 @@ struct F2cLevel {
     float* depth_svu = nullptr;
     int line_mode = RSLF_LINE_CONF_OFF; // the mode of the level's sweep and its zero-filled [S][V][U] C_l plane (NULL when off)
     float* Cl_svu = nullptr;
+    float* Cd_svu = nullptr;            // a kept run's [S][V][U] disparity confidence; NULL: the sweep has a plane of its own
+    VolumePtr* vol_out = nullptr;         // a kept run with volumes: the sweep leaves the volume it ran on here
+};
+// What the level loop allocates per level and for the fusion.  The loop's own instance frees a level's confidences when the
+// level is done and the rest on return, as it always did; a caller's instance (a kept run, rslf_f2c_run) keeps everything.
+struct F2cKeptLevel {
+    int V = 0, U = 0;
+    float scale = 1.0f;                 // the level's epi_scale_factor as used
+    DevBuf depth, valid, Ce, Cl;        // [S][V][U]: disparities, validity bytes, edge and line confidence (C_l empty when off)
+    DevBuf Cd;                          // the disparity confidence (kept runs only)
+    VolumePtr vol;                      // the normalised volume the sweep ran on (kept runs with volumes only)
+};
+struct F2cKept {
+    bool keep_volumes = false;
+    std::vector<F2cKeptLevel> levels;   // finest first
+    DevBuf fused_map, fused_valid;      // [S][V_0][U_0]
 };
 // FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from host EPIs of element type elem
 // into host planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which
 // reports the level's stats.  line_mode: every level's sweep mode, and through plan::f2c_validity the plane its validity is
-// read from; levels_out (nullable): host copies of every level's planes.
+// read from; levels_out (nullable): host copies of every level's planes.  keep (nullable): the owner of a kept run --
+// nothing is freed, every level also keeps C_d (and its volume, keep->keep_volumes), the validity follows validity_rule
+// (RSLF_F2C_VALID_*; without keep it is COMPAT) and the host planes may be NULL.
 int fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
                    float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                    int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
-                   int line_mode, const rslf_f2c_levels_out* levels_out,
+                   int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep,
                    const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep);
+// The loop on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run_lc.
+int fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
+                               float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                               int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
+                               rslf_stats* stats, int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule,
+                               F2cKept* keep);
 
 // rslf_multi.hip
 void multi_free_dev(rslf_multi::Dev& d);
@@ -442,3 +475,12 @@ void multi_free_dev(rslf_multi::Dev& d);
 hipError_t multi_copy(rslf_multi* m, void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t st);
 
 }  // namespace rslf
+
+// A finished fine-to-coarse run held on one device (rslf_f2c_keep.hip).  Bound to the device, not to a context.
+struct rslf_f2c_run {
+    int device = 0;
+    int S = 0, C = 0, elem = RSLF_ELEM_F32;
+    int line_mode = RSLF_LINE_CONF_OFF, validity_rule = RSLF_F2C_VALID_COMPAT;
+    rslf_params params;   // as given: the getters' cut_shadows / shadow_level
+    rslf::F2cKept kept;
+};

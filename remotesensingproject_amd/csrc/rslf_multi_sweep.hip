@@ -318,7 +318,8 @@ static int multi_fine_to_coarse(rslf_multi* m, Elem elem, const void* const* h_e
         return RSLF_OK;
     };
     return fine_to_coarse(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, RSLF_LINE_CONF_OFF, nullptr, sweep);
+                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, RSLF_LINE_CONF_OFF, nullptr, RSLF_F2C_VALID_COMPAT,
+                          nullptr, sweep);
 }
 
 extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* const* h_epis, int is_u8, int V, int S, int U, int C,

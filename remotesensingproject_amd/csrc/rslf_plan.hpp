@@ -206,13 +206,30 @@ inline SweepGate sweep_gate(bool use_disp_confidence_score, int line_mode)
 // Which plane a level of the pyramid reads its validity from (get_valid_depths_mask_s_v_u, dc.hpp:893-915, asked for by the
 // next level's bounds, f2c.hpp:185-186, and by the fusion, :312): everything (C_e > -1) with accept_all; C_l > the line
 // threshold where the line confidence gates (mode 2, and C_d does not come first in the #ifdef chain); else C_e > the edge
-// threshold.  Validity by C_d under use_disp_confidence_score (:902) is not built: that case reads C_e.
-enum F2cValidity { kValidAll = 0, kValidLineConf = 1, kValidEdgeConf = 2 };
+// threshold.  This is the table of the entries that take no validity rule (RSLF_F2C_VALID_COMPAT): under
+// use_disp_confidence_score it reads C_e, never C_d (:902) -- f2c_validity_by_rule below has that branch.
+enum F2cValidity { kValidAll = 0, kValidLineConf = 1, kValidEdgeConf = 2, kValidDispConf = 3 };
 inline F2cValidity f2c_validity(bool accept_all, bool use_disp_confidence_score, int line_mode)
 {
     if (accept_all)
         return kValidAll;
     return sweep_gate(use_disp_confidence_score, line_mode) == kGateLineConf ? kValidLineConf : kValidEdgeConf;
+}
+
+// The validity of a kept run (rslf_f2c_run_host) under its rule.  Compat: f2c_validity, row for row.  Reference: the whole
+// #ifdef chain of dc.hpp:893-915 -- accept_all, else C_d > the disparity threshold under use_disp_confidence_score (:902),
+// else C_l > the line threshold in the gating mode (:904), else C_e > the edge threshold (:906).
+constexpr int kF2cValidCompat = 0, kF2cValidReference = 1;
+inline bool f2c_validity_rule_ok(int rule) { return rule == kF2cValidCompat || rule == kF2cValidReference; }
+inline F2cValidity f2c_validity_by_rule(bool accept_all, bool use_disp_confidence_score, int line_mode, int rule)
+{
+    if (rule != kF2cValidReference)
+        return f2c_validity(accept_all, use_disp_confidence_score, line_mode);
+    if (accept_all)
+        return kValidAll;
+    if (use_disp_confidence_score)
+        return kValidDispConf;
+    return line_mode == kLineConfGate ? kValidLineConf : kValidEdgeConf;
 }
 
 // K7 runs before the claims only where the claims gate on its plane; it then needs the filtered plane first, from a median
@@ -309,6 +326,36 @@ inline std::vector<LevelDims> f2c_pyramid(int V, int U, int max_depth)
         dim_u = u2;
     }
     return levels;
+}
+
+// Pixels per row of a volume's slab: > U (the second lerp tap of u = U - 1 lands on zeros), a multiple of 64.
+inline int volume_pitch(int U) { return ((U + 1 + 63) / 64) * 64; }
+inline size_t volume_bytes(int V, int S, int U, int C)
+{
+    if (V < 1 || S < 1 || U < 1 || C < 1)
+        return 0;
+    return (size_t)V * (size_t)S * (size_t)C * (size_t)volume_pitch(U) * sizeof(float);
+}
+
+// Device bytes a kept fine-to-coarse run (rslf_f2c_run) holds for one level: disparities, C_e and C_d (float), validity
+// (a byte), C_l with a line mode, and the level's volume where volumes are kept ...
+inline size_t f2c_kept_level_bytes(int S, int C, LevelDims d, int line_mode, bool keep_volumes)
+{
+    if (S < 1 || d.V < 1 || d.U < 1)
+        return 0;
+    const size_t n = (size_t)S * (size_t)d.V * (size_t)d.U;
+    const size_t float_planes = line_mode == kLineConfOff ? 3 : 4;
+    return n * (float_planes * sizeof(float) + 1) + (keep_volumes ? volume_bytes(d.V, S, d.U, C) : 0);
+}
+// ... and for the whole pyramid, with the fused map (float) and the fused validity (a byte) at the finest size.
+inline size_t f2c_kept_bytes(int S, int C, const std::vector<LevelDims>& dims, int line_mode, bool keep_volumes)
+{
+    if (dims.empty() || S < 1)
+        return 0;
+    size_t total = (size_t)S * (size_t)dims[0].V * (size_t)dims[0].U * (sizeof(float) + 1);
+    for (const LevelDims& d : dims)
+        total += f2c_kept_level_bytes(S, C, d, line_mode, keep_volumes);
+    return total;
 }
 
 // ---- the selective median (core.hpp:663-718; k3_median.hpp) -------------------------------------------------------

@@ -1168,16 +1168,115 @@ def f2c_fuse(ctx: Context, depths: Sequence[torch.Tensor], valids: Sequence[torc
     return out_map, out_valid
 
 
+F2C_VALID_COMPAT, F2C_VALID_REFERENCE = 0, 1   # RSLF_F2C_VALID_*
+_ELEM = {np.dtype(np.float32): 0, np.dtype(np.uint8): 1, np.dtype(np.uint16): 2}   # RSLF_ELEM_*
+_F2C_PLANES = dict(depth=(0, torch.float32), valid=(1, torch.uint8), Ce=(2, torch.float32), Cd=(3, torch.float32),
+                   Cl=(4, torch.float32), fused_map=(5, torch.float32), fused_valid=(6, torch.uint8))   # RSLF_F2C_PLANE_*
+
+
+class KeptFineToCoarse:
+    """rslf_f2c_run: a finished fine-to-coarse run held on the device by the library (fine_to_coarse_run_host(keep=True)).
+    Every level's disparities, validity, C_e, C_d (C_l with a line mode) and -- with keep_volumes -- normalised volume, and
+    the fused planes, stay where they were computed; planes come out by copy into tensors of the caller's, and the three
+    coloured getters of rslf::FineToCoarse are rendered from the kept planes.  `ctx` is the context copies and renders are
+    queued on: any context of the run's device."""
+
+    def __init__(self, handle, ctx: Context, stats: RslfStats):
+        self._h, self.ctx, self.stats = handle, ctx, stats
+        d = self.describe()
+        self.S, self.C, self.n_levels = d.S, d.C, d.n_levels
+        self.dims = [(d.V[l], d.U[l]) for l in range(d.n_levels)]            # (V_p, U_p), finest first
+        self.scales = [float(d.epi_scale_factor[l]) for l in range(d.n_levels)]
+        self.line_mode, self.validity_rule, self.keep_volumes = d.line_mode, d.validity_rule, bool(d.keep_volumes)
+
+    def describe(self) -> "_lib.RslfF2cRunDesc":
+        d = _lib.RslfF2cRunDesc()
+        check(_lib.lib().rslf_f2c_run_describe(self._h, C.byref(d)), "rslf_f2c_run_describe")
+        return d
+
+    def plane(self, level: int, name: str) -> torch.Tensor:
+        """One kept plane as a new tensor on the device: "depth", "valid", "Ce", "Cd", "Cl" of a level [S,V_p,U_p], or
+        "fused_map" / "fused_valid" (level 0)."""
+        which, dtype = _F2C_PLANES[name]
+        if not 0 <= level < self.n_levels:
+            raise ValueError("level %d of %d" % (level, self.n_levels))
+        out = torch.empty((self.S,) + self.dims[level], dtype=dtype, device=self.ctx.device)
+        self.ctx.use_current_stream()
+        check(_lib.lib().rslf_f2c_run_copy(self._h, level, which, _ptr(out), 0, self.ctx._h), "rslf_f2c_run_copy")
+        return out
+
+    def volume_desc(self, level: int) -> RslfVolumeDesc:
+        """rslf_volume_describe of a level's kept volume (the slab stays the run's)."""
+        vol, d = C.c_void_p(), RslfVolumeDesc()
+        check(_lib.lib().rslf_f2c_run_volume(self._h, level, C.byref(vol)), "rslf_f2c_run_volume")
+        check(_lib.lib().rslf_volume_describe(vol, C.byref(d)), "rslf_volume_describe")
+        return d
+
+    def get_results(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """f2c.hpp:302-324 -> (out_map_s_v_u [S,V,U] f32, out_validity_s_v_u [S,V,U] u8), copies of the kept fused planes."""
+        return self.plane(0, "fused_map"), self.plane(0, "fused_valid")
+
+    def _render(self, name: str, shapes, *args, lut_bgr=None, stacked: bool = False):
+        table = _table(lut_bgr)
+        outs = [torch.empty(tuple(sh) + (3,), dtype=torch.uint8, device=self.ctx.device) for sh in shapes]
+        dst = _ptr(outs[0]) if stacked else (C.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
+        self.ctx.use_current_stream()
+        st = getattr(_lib.lib(), name)(self._h, self.ctx._h, *args, table.ctypes.data_as(C.c_void_p), dst)
+        if st == -1:   # the getters' index rules and the missing volumes
+            raise ValueError(_lib.lib().rslf_last_error().decode(errors="replace"))
+        check(st, name)
+        return outs[0] if stacked else outs
+
+    def get_coloured_depth_maps(self, lut_bgr=None, saturate: bool = True) -> torch.Tensor:
+        """f2c.hpp:325-378 as FineToCoarse.get_coloured_depth_maps -> [S, V, U, 3] uint8 BGR."""
+        return self._render("rslf_f2c_run_render_depth_maps", [(self.S,) + self.dims[0]], 1 if saturate else 0, lut_bgr=lut_bgr, stacked=True)
+
+    def get_coloured_depth_pyr(self, s: int = -1, lut_bgr=None, saturate: bool = True) -> list:
+        """f2c.hpp:491-519 as FineToCoarse.get_coloured_depth_pyr -> a list of [V_p, U_p, 3] uint8 BGR."""
+        return self._render("rslf_f2c_run_render_depth_pyr", self.dims, int(s), 1 if saturate else 0, lut_bgr=lut_bgr)
+
+    def get_coloured_epi_pyr(self, v: int = -1, lut_bgr=None, saturate: bool = True) -> list:
+        """f2c.hpp:432-488 as FineToCoarse.get_coloured_epi_pyr -> a list of [S, U_p, 3] uint8 BGR."""
+        return self._render("rslf_f2c_run_render_epi_pyr", [(self.S, u) for _, u in self.dims], int(v), 1 if saturate else 0, lut_bgr=lut_bgr)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and not sys.is_finalizing():
+            _lib.lib().rslf_f2c_run_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                             parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                            ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False) -> dict:
+                            ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False, keep: bool = False,
+                            validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
-    (line_confidence is None in mode 0)."""
+    (line_confidence is None in mode 0).
+
+    keep=True: rslf_f2c_run_host -- the run stays on the device and a KeptFineToCoarse comes back; validity_rule
+    (F2C_VALID_COMPAT, or F2C_VALID_REFERENCE for validity by C_d under par_use_disp_confidence_score) and keep_volumes apply
+    to this form alone."""
     ctx = ctx or default_context()
-    keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
+    keep_alive, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
     L = _lib.lib()
+    if keep:
+        if want_levels:
+            raise ValueError("fine_to_coarse_run_host: a kept run hands its levels out itself (KeptFineToCoarse.plane)")
+        p, st, h = (parameters or Depth1DParameters()).to_c(), RslfStats(), C.c_void_p()
+        ctx.use_current_stream()
+        check(L.rslf_f2c_run_host(ctx._h, ptrs, _ELEM[np.dtype(dt)], V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
+                                  float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
+                                  int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st)), "rslf_f2c_run_host")
+        return KeptFineToCoarse(h, ctx, st)
+    if validity_rule != F2C_VALID_COMPAT:
+        raise ValueError("fine_to_coarse_run_host: validity_rule needs keep=True")
     out_map, out_valid = np.empty((S, V, U), np.float32), np.empty((S, V, U), np.uint8)
     p = (parameters or Depth1DParameters()).to_c()
     st, nl = RslfStats(), C.c_int()
