@@ -120,6 +120,7 @@ class PileResult:
     depth_idx: np.ndarray         # argmax index, -1 if none [V,U] i32
     score: np.ndarray             # score[d*] [V,U] f32
     depth_raw: np.ndarray         # best depth before the median [V,U] f32
+    scan_mask: np.ndarray | None = None   # the caller's scan mask after the scan (core.hpp:511) [V,U] u8, where one was passed
 
 
 def normalize_u8(x: np.ndarray) -> np.ndarray:
@@ -198,7 +199,7 @@ def depth_epi_pile(vol, dmin_vu, dmax_vu, dim_d, s_hat, Ce_vu, Ce_mask_vu, param
                                 np.ascontiguousarray(dmax_vu, np.float32).reshape(-1),
                                 dim_d, s_hat, Ce.reshape(-1), cm.reshape(-1), Cd.reshape(-1), depth.reshape(-1),
                                 rbar.reshape(-1), C.byref(p), _ptr(m), _ptr(idx), _ptr(score), _ptr(raw))
-    return PileResult(Ce, cm, Cd, depth, rbar, idx, score, raw)
+    return PileResult(Ce, cm, Cd, depth, rbar, idx, score, raw, m)
 
 
 def depth1d_pile_run(vol, dmin, dmax, dim_d, s_hat=-1, params=None) -> PileResult:

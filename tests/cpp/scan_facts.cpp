@@ -27,8 +27,8 @@ static void stream_prefixes(int C)
 
 int main()
 {
-#define SPAD_1(N) std::printf("spad 1 %d %d %d %d %d\n", N, scan_reg_waves(N, 1), (int)scan_reg_best_in_lds(N, 1), (int)scan_reg_trim(N, 1), (int)packed_long_unit(N, 1));
-#define SPAD_3(N) std::printf("spad 3 %d %d %d %d %d\n", N, scan_reg_waves(N, 3), (int)scan_reg_best_in_lds(N, 3), (int)scan_reg_trim(N, 3), (int)packed_long_unit(N, 3));
+#define SPAD_1(N) std::printf("spad 1 %d %d %d %d %d %d\n", N, scan_reg_waves(N, 1), (int)scan_reg_best_in_lds(N, 1), (int)scan_reg_trim(N, 1), (int)packed_long_unit(N, 1), (int)scan_reg_tap_table(N, 1));
+#define SPAD_3(N) std::printf("spad 3 %d %d %d %d %d %d\n", N, scan_reg_waves(N, 3), (int)scan_reg_best_in_lds(N, 3), (int)scan_reg_trim(N, 3), (int)packed_long_unit(N, 3), (int)scan_reg_tap_table(N, 3));
     RSLF_SPAD_LIST_1CH(SPAD_1)
     RSLF_SPAD_LIST_3CH(SPAD_3)
 #undef SPAD_1

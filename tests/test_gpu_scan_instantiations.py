@@ -8,6 +8,10 @@ plus the top rung's exact and ragged-tail forms (rslf_chip_a/b/c.hip); and the g
 one volume for every cell; tests/test_scan_coverage_cpu.py checks, from the same headers the library is built from,
 that no compiled cell is missing.  They are plain data, importable without torch or a GPU.
 
+Every row here calls the scan in one caller form: Depth1DComputer_pile(vol, dmin, dmax, D, -1, 1.0), a scalar hypothesis
+range and the centre view s_hat = S // 2.  The code the kernels compile for the two other forms -- per-pixel [dmin, dmax]
+planes, and an off-centre s_hat -- has its rows in tests/test_gpu_scan_caller_forms.py, which reuses these tables.
+
 Every volume has hypothesis lines that leave the EPI at both borders and lines that stay inside it, a row length that is
 not a multiple of 64, a hypothesis count that does not split evenly over a tile's waves, a dark band (gaps in the pixel
 lists), and a scanline whose views other than the centre one hold one constant radiance: there every hypothesis whose line
