@@ -270,6 +270,29 @@ int rslf_kernel_columns_pile(rslf_ctx* ctx, const rslf_volume* vol, const float*
                              float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
                              const int32_t* d_idx_vu, float* d_K_vsu);
 
+/* The scan's whole score matrix: what compute_1D_depth_epi leaves in the caller's BufferDepth1D::buf_scores_u_d
+ * (core.hpp:616-625), from which it takes the arg max (:634) and C_d (:641) -- for the scanlines
+ * [v_first, v_first + n_rows) of the volume.
+ *   d_mask_vu       nullable, read-only, a full [V][U] plane: the pixels with a non-zero byte are scanned; NULL => every
+ *                   pixel.  To reproduce the reference pass the mask a scan was ENTERED with (edge mask AND scan mask):
+ *                   the reference writes a pixel's row before it tests raw_score_threshold.
+ *   d_scores_vud    out, [n_rows][U][dim_d], d fastest: d_scores_vud[((v - v_first) * U + u) * dim_d + d] = score[d].
+ *                   Rows of unscanned pixels are left untouched (as rslf_kernel_columns_pile leaves its columns).
+ *   d_dmin_vu, d_dmax_vu   both NULL => the scalars; else the per-pixel [V][U] planes.
+ * Nothing else is written: no C_e, mask, depth or C_d.  Arguments are checked as rslf_depth_epi_scan checks them, plus
+ * the window; stats (nullable; waits) reports the pixels scanned and in scan_kernel the form that ran: RSLF_SCAN_REG for
+ * the volumes the register scan takes, else RSLF_SCAN_GENERIC (also under the "force_scan" hook).  One device; not
+ * inside an open sweep (it uses the context's pixel lists). */
+int rslf_depth_epi_scores(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                          float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
+                          const uint8_t* d_mask_vu, int v_first, int n_rows, float* d_scores_vud, rslf_stats* stats);
+/* The same with the mask and the scores on the host.  The window goes through the context's staging buffer in passes
+ * of as many scanlines as its budget holds (at least one; the "staging_kib" hook sets the budget); rows of unscanned
+ * pixels are written 0, as the reference's zero-filled buffer holds them (core.hpp:167).  Synchronises. */
+int rslf_depth_epi_scores_host(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                               float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
+                               const uint8_t* h_mask_vu, int v_first, int n_rows, float* h_scores_vud, rslf_stats* stats);
+
 /* rslf::selective_median_filter -- core.hpp:366-375, impl :663-718.
  * d_dst_vu must not alias d_src_vu; it is fully written (0 where mask is 0).
  * `size` = a_size: the window is width = (size - 1) / 2 pixels either side (:686), so an even size is the next smaller

@@ -446,6 +446,27 @@ public:
     }
     std::vector<uint8_t> get_disparity_map(const uint8_t* lut_bgr) const { return get_disparity_map(detail::own(ctx_), lut_bgr); }
 
+    // After run(): the score rows [n_rows][U][dim_d] of scanlines [v_first, v_first + n_rows) (n_rows < 0: to the last
+    // one), the reference's buf_scores_u_d of each EPI (core.hpp:616-625), over the pixels of the final edge-confidence
+    // mask -- those that received a disparity; the rows of every other pixel are 0.  A scan of its own on the object's
+    // context.  An object built on a MultiContext keeps no volume on a device: it refuses.
+    std::vector<float> get_scores(int v_first = 0, int n_rows = -1) const
+    {
+        if (multi_)
+            throw std::invalid_argument("get_scores: this object was built on a MultiContext, which keeps no volume on a device: "
+                                        "score rows are built for one context");
+        detail::require(!m_best_depth_v_u.empty(), "the getters show the results of run(): call it first");
+        if (n_rows < 0)
+            n_rows = dim_v_ - v_first;
+        detail::require(v_first >= 0 && n_rows > 0 && n_rows <= dim_v_ - v_first, "get_scores: the scanlines are not a window of the volume");
+        std::vector<float> out((size_t)n_rows * dim_u_ * m_dim_d);
+        const rslf_params p = m_parameters.to_c();
+        check(rslf_depth_epi_scores_host(ctx_->get(), vol_, nullptr, nullptr, m_dmin, m_dmax, m_dim_d, m_s_hat, &p,
+                                         m_edge_confidence_mask_v_u.data(), v_first, n_rows, out.data(), nullptr),
+              "rslf_depth_epi_scores_host");
+        return out;
+    }
+
     int rows() const { return dim_v_; }
     int cols() const { return dim_u_; }
     float epi_scale_factor() const { return scale_used_; }

@@ -46,6 +46,8 @@ SYMBOLS = [
     "rslf_f2c_run_host", "rslf_f2c_run_destroy", "rslf_f2c_run_describe", "rslf_f2c_run_copy", "rslf_f2c_run_volume",
     "rslf_f2c_run_render_depth_maps", "rslf_f2c_run_render_depth_maps_host", "rslf_f2c_run_render_depth_pyr",
     "rslf_f2c_run_render_depth_pyr_host", "rslf_f2c_run_render_epi_pyr", "rslf_f2c_run_render_epi_pyr_host",
+    # the scan's score matrix
+    "rslf_depth_epi_scores", "rslf_depth_epi_scores_host",
 ]
 
 
@@ -183,6 +185,8 @@ def lib():
     L.rslf_selective_median.argtypes = [vp, vp, vp, vp, ci, ci, vp, cf]
     L.rslf_depth_epi_scan.argtypes = [vp, vp, vp, vp, cf, cf, ci, ci, vp, vp, vp, vp, vp, C.POINTER(RslfParams),
                                       vp, vp, vp, C.POINTER(RslfStats)]
+    L.rslf_depth_epi_scores.argtypes = [vp, vp, vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, ci, ci, vp, C.POINTER(RslfStats)]
+    L.rslf_depth_epi_scores_host.argtypes = L.rslf_depth_epi_scores.argtypes
     L.rslf_depth1d_run.argtypes = [vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, vp, vp,
                                    C.POINTER(RslfStats)]
     L.rslf_depth1d_pile_run.argtypes = [vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, vp, vp, vp,

@@ -5,6 +5,7 @@
 //   rslf_core.hip         errors, contexts, volumes, host upload / device pack (K0)
 //   rslf_pile.hip         the hot path: edge confidence (K1), scan (K2), selective median (K3), Depth1DComputer(_pile)
 //   rslf_chip_a/b/c.hip   the on-chip scan kernel's instantiations, one per rung of its ladder (launched by rslf_pile.hip)
+//   rslf_scores.hip       the scan's score matrix as an output: rslf_depth_epi_scores and its host form (k2_scores.hpp)
 //   rslf_sweep.hip        the 2-D sweep and its propagation (K4), Depth2DComputer::run
 //   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the one native level loop
 //   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters

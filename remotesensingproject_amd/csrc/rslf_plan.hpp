@@ -975,6 +975,58 @@ inline void sweep_reserve(const ScanRequest& sparse, const ScanKernelFacts& f, i
     }
 }
 
+// ---- score rows (k2_scores.hpp, rslf_scores.hip): the scan's score matrix [row of the window][U][dim_d] as an output -----
+// A wave parks kScoreRun consecutive hypotheses of its 64 pixels in LDS ([pixel][run + 1], an odd pitch: no bank conflicts
+// either way) and writes them out 64 B per pixel and store instruction.  16: 17 KiB of parking + 1 KiB of pixel numbers, which
+// with the offset tables stays inside a workgroup's LDS share at every occupancy the register kernels run at (8 per CU: 20 KiB).
+constexpr int kScoreRun = 16;
+constexpr size_t kScoreLdsLimit = (size_t)64 << 10;   // static LDS of one workgroup
+inline int score_run_length(int /*spad*/, int /*C*/) { return kScoreRun; }
+// (`table_floats`: floats per slot of the wave's offset table -- 4 with the tap table, else 1; spad == 0: the generic form)
+constexpr size_t score_lds_bytes(int spad, int table_floats)
+{
+    return (size_t)kScanWavesPerTile * (64 * ((size_t)(kScoreRun + 1) * sizeof(float) + sizeof(int)) + (size_t)spad * table_floats * sizeof(float));
+}
+// The form that serves a request: the register one exactly where choose_scan_kernel gives a slot count (radiances in range,
+// linear interpolation, no "force_scan"), else the generic one.  Streaming and on-chip forms are not built.
+inline int choose_score_kernel(int S, int C, bool in_range, bool linear, int force_scan, int* spad)
+{
+    ScanRequest r = {};
+    r.S = S, r.C = C;
+    choose_scan_kernel(&r, in_range, linear, force_scan, false, ScanKernelFacts{0, 0, 0});
+    *spad = r.spad;
+    return r.spad ? RSLF_SCAN_REG : RSLF_SCAN_GENERIC;
+}
+// Row tiles of 64 entries; nothing is merged, so hypothesis groups are free: doubled while the window's tiles are fewer than
+// eight rounds of resident workgroups and every wave keeps two hypotheses.  The launches are scan_launches' over the window.
+inline ScanPlan score_plan(int kind, int spad, int n_rows, int U, int dim_d, int num_cus, int reg_waves, int force_groups)
+{
+    ScanPlan p = {};
+    p.kind = kind, p.spad = spad, p.tile_w = 64, p.tiles_per_row = (U + 63) / 64;
+    const long long tiles = (long long)std::max(1, n_rows) * p.tiles_per_row;
+    int groups = 1;
+    while (groups < 64 && tiles * groups < 8LL * std::max(1, num_cus) * std::max(1, reg_waves) && dim_d >= 4 * kScanWavesPerTile * groups)
+        groups *= 2;
+    groups = force_groups > 0 ? std::min(64, force_groups) : groups;
+    while (groups > 1 && dim_d < 2 * kScanWavesPerTile * groups) groups /= 2;
+    p.groups = groups;
+    p.rows_per_launch = (int)std::max<long long>(1, std::min<long long>(std::max(1, n_rows), ((long long)1 << 30) / ((long long)p.tiles_per_row * groups)));
+    return p;
+}
+inline bool score_launches(int v_first, int n_rows, int U, const ScanPlan& p, std::vector<ScanLaunch>* out, long long* bad_tiles)
+{
+    const bool ok = scan_launches(n_rows, U, p, out, bad_tiles);
+    for (ScanLaunch& l : *out) l.v0 += v_first;
+    return ok;
+}
+inline size_t score_offset(int row, int u, int d, int U, int dim_d) { return ((size_t)row * (size_t)U + (size_t)u) * (size_t)dim_d + (size_t)d; }
+// scanlines per pass of the host form through a staging buffer of budget_bytes: at least one
+inline int score_window_rows(int U, int dim_d, size_t budget_bytes)
+{
+    const size_t row = std::max<size_t>(1, (size_t)U * (size_t)dim_d * sizeof(float));
+    return (int)std::min<size_t>(std::max<size_t>(1, budget_bytes / row), (size_t)INT32_MAX);
+}
+
 // ---- one visit of a sweep sharded over several devices of one process ---------------------------------------------
 //
 // scan on every device; every device fetches its neighbours' boundary rows (needs the neighbour's scan); every device

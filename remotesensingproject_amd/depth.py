@@ -509,6 +509,35 @@ def compute_1D_depth_epi_pile(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int,
     return st
 
 
+def compute_1D_depth_scores(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int, a_s_hat: int,
+                            parameters: Depth1DParameters | None = None, a_mask_v_u: torch.Tensor | None = None,
+                            v_first: int = 0, n_rows: int | None = None, out: torch.Tensor | None = None, *,
+                            want_stats: bool = False):
+    """The scan's whole score matrix (core.hpp:616-625, the caller's BufferDepth1D::buf_scores_u_d) for the scanlines
+    [v_first, v_first + n_rows) -> [n_rows, U, D] f32 on the volume's device, score[d] of every pixel whose byte of
+    a_mask_v_u ([V,U] u8, read-only; None: every pixel) is set.  Rows of other pixels keep what `out` held (zeros when
+    the tensor is made here).  a_dmin_v_u / a_dmax_v_u: [V,U] f32 CUDA tensors or Python floats.  To reproduce the
+    reference pass the mask a scan was entered with (edge mask AND scan mask).  want_stats: returns (scores, rslf_stats)."""
+    p = (parameters or Depth1DParameters()).to_c()
+    planes = isinstance(a_dmin_v_u, torch.Tensor)
+    n_rows = vol.V - int(v_first) if n_rows is None else int(n_rows)
+    shape = (max(n_rows, 0), vol.U, int(a_dim_d))
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.float32, device=vol.ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+    if a_mask_v_u is not None and (tuple(a_mask_v_u.shape) != (vol.V, vol.U) or a_mask_v_u.dtype != torch.uint8
+                                   or not a_mask_v_u.is_contiguous()):
+        raise ValueError("a_mask_v_u must be a contiguous uint8 [V, U] plane")
+    st = RslfStats() if want_stats else None
+    vol.ctx.use_current_stream()
+    check(_lib.lib().rslf_depth_epi_scores(
+        vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
+        0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), int(a_dim_d), int(a_s_hat), C.byref(p),
+        _ptr(a_mask_v_u), int(v_first), n_rows, _ptr(out), C.byref(st) if st is not None else None), "rslf_depth_epi_scores")
+    return (out, st) if want_stats else out
+
+
 def selective_median_filter(a_src: torch.Tensor, vol: Volume, a_s_hat: int, a_size: int, a_mask_v_u: torch.Tensor,
                             a_epsilon: float) -> torch.Tensor:
     """core.hpp:366-375; returns a_dst."""
@@ -570,6 +599,7 @@ class Depth1DComputer_pile:
             _ptr(self.m_best_depth_v_u), _ptr(self.m_rbar_v_u), _ptr(self.m_depth_idx_v_u), _ptr(self.m_score_v_u),
             _ptr(self.m_depth_raw_v_u), C.byref(st) if st is not None else None), "rslf_depth1d_pile_run")
         self.stats = st
+        self._ran = True
 
     def get_s_hat(self) -> int:
         return self.m_s_hat
@@ -590,6 +620,17 @@ class Depth1DComputer_pile:
         lo, hi = render_fit(ctx, self.m_best_depth_v_u, None, FIT_MINMAX)
         return render_planes(ctx, self.m_best_depth_v_u.unsqueeze(0), lo, hi, RENDER_SHIFT, lut_bgr,
                              self.m_edge_confidence_mask_v_u.unsqueeze(0), MASK_BLACK)[0]
+
+    def get_scores(self, v_first: int = 0, n_rows: int | None = None) -> torch.Tensor:
+        """After run(): the score rows [n_rows, U, D] of scanlines [v_first, v_first + n_rows), the reference's
+        buf_scores_u_d of each EPI (core.hpp:616-625), over the pixels of the FINAL edge-confidence mask -- those that
+        received a disparity; the rows of every other pixel are 0.  (The reference also fills the rows of pixels it then
+        rejects at raw_score_threshold; to get those, call compute_1D_depth_scores with the mask the scan was entered
+        with.)  A scan of its own: the scores are computed again, nothing is kept from run()."""
+        if not getattr(self, "_ran", False):
+            raise RuntimeError("get_scores shows the pixels run() gave a disparity: call run() first")
+        return compute_1D_depth_scores(self.m_epis, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, self.m_parameters,
+                                       self.m_edge_confidence_mask_v_u, v_first, n_rows)
 
     def results(self) -> dict:
         """Host copies of every output plane."""
@@ -1035,6 +1076,7 @@ class Depth1DComputer:
             _ptr(self.m_best_depth_u), _ptr(self.m_rbar_u), _ptr(self.m_depth_idx_u), _ptr(self.m_score_u), C.byref(st)),
             "rslf_depth1d_run")
         self.stats = st
+        self._ran = True
 
     def get_coloured_epi(self, lut_bgr=None) -> torch.Tensor:
         """dc.hpp:374-416: as Depth1DComputer_pile.get_coloured_epi for the one EPI -> [S, U, 3] uint8 BGR.  This class
@@ -1044,6 +1086,14 @@ class Depth1DComputer:
         out = _coloured_epi_rows(vol.ctx, self.m_best_depth_u, self.m_edge_confidence_mask_u, vol.S, self.m_s_hat, 0, lut_bgr)
         out[:, 0, :] = 0
         return out
+
+    def get_scores_u_d(self) -> torch.Tensor:
+        """After run(): the EPI's [U, D] score matrix, the reference's buf_scores_u_d (core.hpp:616-625), over the pixels
+        that received a disparity (the final edge-confidence mask); other rows are 0."""
+        if not getattr(self, "_ran", False):
+            raise RuntimeError("get_scores_u_d shows the pixels run() gave a disparity: call run() first")
+        return compute_1D_depth_scores(self.m_epi, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, self.m_parameters,
+                                       self.m_edge_confidence_mask_u)[0]
 
     def results(self) -> dict:
         torch.cuda.synchronize(self.m_epi.ctx.device)
