@@ -141,6 +141,8 @@ int rslf_ctx_synchronize(rslf_ctx* ctx);
  *                    the packed list and leave the pixel-per-wave launch the rest | 0 the pixel-per-wave launch takes all
  *   "tap_table"      1 (default) the register row kernels that have one (k2_scan_reg<104,1>) take the lerp taps and weights that
  *                    are the same in every lane of a tile from a per-hypothesis table | 0 every lane computes its own
+ *   "scalar_taps"    1 (default) with "tap_table" on, hypotheses whose lerp taps and weights are the same for every pixel of the row
+ *                    take them as scalars from a table made once per hypothesis grid and kept by the context | 0 off
  *   "claim_skip"     1 (default) the 2-D sweep's claims skip views with nothing left to paint within reach | 0 off
  *   "stream_share"   63-pixel tiles sharing taps between lanes in the streaming kernel: 1 (default) where the samples gathered
  *                    again on every pass are at least a quarter of the views | 0 never | 2 always
@@ -784,6 +786,10 @@ int rslf_last_scan_kernel_ms(rslf_ctx* ctx, float* ms);
  * a new sum.  For the roofline of the rows around the path: a 2-D sweep is one dense and S - 1 sparse scan launches, a
  * fine-to-coarse run that per pyramid level (core.hpp:993-1028). */
 int rslf_scan_time_total_ms(rslf_ctx* ctx, float* ms, int* launches);
+/* What the last scan of this context took from the row-exact table ("scalar_taps"): *attached = 1 if its launch was handed
+ * one (0: the kernel has no scalar-tap form, a hook is off, per-pixel ranges, a packed launch), *exact_hypotheses = how many
+ * hypotheses of that table are row-exact -- the ones whose interior tiles ran the scalar-tap form.  Waits for the stream. */
+int rslf_last_scan_row_exact(rslf_ctx* ctx, int* attached, int* exact_hypotheses);
 
 #ifdef __cplusplus
 }

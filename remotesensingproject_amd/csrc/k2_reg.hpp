@@ -614,6 +614,129 @@ constexpr bool scan_reg_trim(int spad, int c)
 #endif
 constexpr bool scan_reg_tap_table(int spad, int c) { return RSLF_TAP_TABLE && c == 1 && spad == 104 && scan_reg_trim(spad, c); }
 
+// The row kernels that also have a SCALAR-TAP form (scan_reg_body_scalar) for hypotheses whose every view offset is
+// row-exact (k2_taps.hpp, row_exact_entry): the tap offset and the weights of such an offset are the same for every pixel of
+// every scanline, so they come from a per-launch table in memory (ScanArgs::rx_*) by scalar loads and stay in SGPRs.
+// The 104-slot kernel only, as the tap table (profiles/r12_scalar_taps.md).
+#ifndef RSLF_SCALAR_TAPS
+#define RSLF_SCALAR_TAPS 1   // 0 builds the row kernels without the form (A/B): a table handed in is then ignored
+#endif
+#ifndef RSLF_SCALAR_GB
+#define RSLF_SCALAR_GB 13    // loads in flight per gather round of the scalar-tap form: eight rounds per hypothesis at 104 slots
+#endif
+constexpr bool scan_reg_scalar_taps(int spad, int c) { return RSLF_SCALAR_TAPS && scan_reg_tap_table(spad, c); }
+
+// Uniform-D, interior, TRIM, one channel, and every view offset row-exact: hypotheses [d0, d1) of a tile from the row-exact
+// table.  No offset table, no tap_entry, no ballot, no LDS traffic and no division per hypothesis: D[d] and the entries are
+// scalar loads, a sample's address is the EPI's scalar base plus the entry's offset (two scalar adds) plus this lane's
+// pixel offset (ONE register for the whole kernel), and the blend takes both weights as scalar operands -- the same three
+// operations in the same roles as every other form (interp.hpp:184), hence the same bits.  The next round's entries are
+// asked for while this round's loads are in flight.  The tile's pixels need not be consecutive.  The gather has no branch
+// at all: a padding slot s >= S (only the last kPadSlack slots can be one) repeats the last view's tap with zero weights --
+// three loads of lines the round reads anyway at 101 views -- and its register is never read, mean_shift_pass skips it by
+// S.  (With the slots' wave-uniform tests the tail of the gather was sixteen small blocks: its loads lost the scalar base
+// and the padding selects and SGPR reloads cost 200 VALU per hypothesis, most of what the form saves.)
+template <int SPAD, class BestT>
+__device__ __forceinline__ void scan_reg_body_scalar(const ScanArgs& a, int v, int u, int d0, int d1, BestT& best)
+{
+    constexpr int C = 1, BATCH = RSLF_SCALAR_GB, ROUNDS = SPAD / BATCH;
+    static_assert(SPAD % BATCH == 0, "whole rounds");
+    static_assert(!scan_reg_packed_math(SPAD, 1) && scan_reg_trim(SPAD, 1), "the passes below are the scalar TRIM ones of the other forms");
+    // (constant address space: a uniform index is then a scalar load whatever the kernel stores elsewhere)
+    typedef const __attribute__((address_space(4))) long long* OffPtr;
+    typedef const __attribute__((address_space(4))) f2* WeightPtr;
+    typedef const __attribute__((address_space(4))) float* FloatPtr;
+    const VolView& vol = a.vol;
+    const float* epi = vol.row(v, 0);
+    const int S = vol.S;
+    const float kq = a.k.k1;                       // kernels.cpp:21
+    const unsigned ubytes = (unsigned)u << 2;      // this lane's pixel within the row
+    // core.hpp:577: rbar starts from R[s_hat] = E[s_hat][u] for every hypothesis
+    const float centre = epi[(long long)a.s_hat * vol.stride_s + u];
+    const f2 R2[1][1] = {{f2{0.0f, 0.0f}}};
+
+#pragma unroll 1
+    for (int d = d0; d < d1; d++) {
+        const float Dd = ((FloatPtr)a.rx_D)[d];
+        const OffPtr toff = (OffPtr)a.rx_off + (long long)d * SPAD;
+        const WeightPtr tw = (WeightPtr)a.rx_w + (long long)d * SPAD;
+        float R[C][SPAD];
+        // The offsets of a round are needed before its loads, the weights only once they are back: the weights of this round
+        // and the offsets of the next are asked for while the round's loads are in flight.
+        long long cur[BATCH], nxt[BATCH];
+#pragma unroll
+        for (int j = 0; j < BATCH; j++)
+            cur[j] = toff[j];
+#pragma unroll
+        for (int g = 0; g < ROUNDS; g++) {
+            float e0[BATCH], e1[BATCH];
+            f2 w[BATCH];
+            // (re-made opaque per round: the zero-extension of the lane's offset then sits beside the loads that add it to their
+            // scalar bases, which is what lets them take the base as a scalar operand)
+            unsigned ub = ubytes;
+            asm volatile("" : "+v"(ub));
+            // the round's loads back to back ...
+#pragma unroll
+            for (int j = 0; j < BATCH; j++) {
+                // (the scalar sum is pinned too: left to itself the compiler adds the lane's offset to the EPI's base
+                // once and the entry's offset per sample with a 64-bit VALU add)
+                typedef const __attribute__((address_space(1))) char* GlobalBytes;
+                typedef const __attribute__((address_space(1))) float* GlobalFloats;
+                const unsigned long long sum = (unsigned long long)epi + (unsigned long long)cur[j];
+                unsigned lo = (unsigned)sum;
+                asm volatile("" : "+s"(lo));
+                const unsigned long long row = (sum & 0xFFFFFFFF00000000ull) | lo;
+                const GlobalFloats p = (GlobalFloats)((GlobalBytes)row + ub);
+                e0[j] = p[0];
+                e1[j] = p[1];
+            }
+            // ... this round's weights and the next round's offsets under them ...
+#pragma unroll
+            for (int j = 0; j < BATCH; j++)
+                w[j] = tw[g * BATCH + j];
+            if (g + 1 < ROUNDS) {
+#pragma unroll
+                for (int j = 0; j < BATCH; j++)
+                    nxt[j] = toff[(g + 1) * BATCH + j];
+            }
+            // ... then the blend
+#pragma unroll
+            for (int j = 0; j < BATCH; j++) {
+                const float m0 = w[j].y * e0[j];   // interp.hpp:184: (1 - t) * left tap
+                const float m1 = w[j].x * e1[j];
+                R[0][g * BATCH + j] = m0 + m1;
+            }
+            // pin the round (scan_reg_body): no "all loads first, all blends last"
+#pragma unroll
+            for (int j = 0; j < BATCH; j++)
+                asm volatile("" : "+v"(R[0][g * BATCH + j]));
+#pragma unroll
+            for (int j = 0; j < BATCH; j++)
+                cur[j] = nxt[j];
+        }
+
+        float rbar[C] = {centre};
+        float B = 0.0f;
+#pragma unroll 1
+        for (int it = 0; it < a.k.n_iter; it++) {   // core.hpp:584-610
+            float A[C] = {0.0f};
+            B = 0.0f;
+            if (it == a.k.n_iter - 1) {
+                // the last pass sums K alone, and rbar stays the one that entered it (LastPassRbar)
+                mean_shift_pass<SPAD, C, false, true>(R, R2, S, kq, rbar, A, B);
+                break;
+            }
+            mean_shift_pass<SPAD, C, false, false>(R, R2, S, kq, rbar, A, B);
+            const float qd = (B != 0.0f) ? (A[0] / B) : 0.0f;   // core.cpp:42, OpenCV 3.x: /0 -> 0
+            rbar[0] = (qd > 0.0f) ? qd : 0.0f;                  // core.hpp:609
+        }
+        const float cardf = (float)S;                  // interior: every sample is inside the row
+        float sc = (S != 0) ? (B / cardf) : 0.0f;      // core.hpp:616-620: the last pass's sum of K
+        sc = (sc > 0.0f) ? sc : 0.0f;                  // core.hpp:622
+        best.offer(sc, d, Dd, rbar);
+    }
+}
+
 template <int SPAD, int C>
 using ScanRegRbarFix = std::conditional_t<scan_reg_trim(SPAD, C), LastPassRbar<C>, NoRbarFix>;
 
@@ -631,6 +754,35 @@ __device__ __forceinline__ void scan_reg_rows(const ScanArgs& a, int v, int u, i
     const float max_ds = (float)max(a.s_hat, a.vol.S - 1 - a.s_hat);
     const float range = a.dmax - a.dmin, denom = (float)(a.dim_d - 1);
     const float uf = (float)u, Um1 = (float)(a.vol.U - 1);
+    if constexpr (scan_reg_scalar_taps(SPAD, C)) {
+        // With the launch's row-exact table (ScanArgs::rx_*) the runs are of (interior, row-exact) hypotheses and D[d] is the
+        // table's, so nothing here divides: interior row-exact runs take the scalar-tap form, the others the forms below.
+        // Without one (null pointers) the runs and the forms are the ones below.
+        typedef const __attribute__((address_space(4))) float* FloatPtr;
+        typedef const __attribute__((address_space(4))) int* IntPtr;
+        const bool rx = a.rx_off != nullptr;
+        auto form = [&](int d) -> int {   // 0 border, 1 interior, 2 interior and row-exact
+            const float Dd = rx ? ((FloatPtr)a.rx_D)[d] : hypothesis(a.dmin, range, denom, d);
+            const float reach = max_ds * fabsf(Dd) * fabsf(a.k.slope) + 2.0f;
+            const bool in = __all((uf - reach >= 0.0f) && (uf + reach <= Um1));
+            return !in ? 0 : (rx && ((IntPtr)a.rx_exact)[d]) ? 2 : 1;
+        };
+        int d = d0;
+        while (d < d1) {
+            const int f = form(d);
+            int e = d + 1;
+            while (e < d1 && form(e) == f)
+                e++;
+            if (f == 2)
+                scan_reg_body_scalar<SPAD>(a, v, u, d, e, best);
+            else if (f == 1)
+                scan_reg_body<SPAD, C, false, true, PK, 0, BestT, false, scan_reg_trim(SPAD, C), kTaps>(a, v, u, d, e, best, otab);
+            else
+                scan_reg_body<SPAD, C, true, true, PK, 0, BestT, false, scan_reg_trim(SPAD, C)>(a, v, u, d, e, best, otab);
+            d = e;
+        }
+        return;
+    }
     auto interior = [&](int d) -> bool {
         const float reach = max_ds * fabsf(hypothesis(a.dmin, range, denom, d)) * fabsf(a.k.slope) + 2.0f;
         return __all((uf - reach >= 0.0f) && (uf + reach <= Um1));

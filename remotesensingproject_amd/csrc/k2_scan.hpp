@@ -95,7 +95,18 @@ struct ScanArgs {
     int row_min;
     // register row kernels with a tap table (k2_reg.hpp, scan_reg_tap_table): 0 = every gather batch takes the per-lane form
     int tap_table;
+    // register row kernels with a scalar-tap form (k2_reg.hpp, scan_reg_scalar_taps): the launch's row-exact table
+    // (k2_fill_row_exact, rslf_pile.hip), made once per hypothesis grid and row geometry and kept by the context.  All null: no
+    // table, every hypothesis takes the forms above.
+    const long long* rx_off;   // [dim_d][slots of the kernel] byte offset of pixel 0's left tap from the EPI's base (row_exact_entry), sign-extended:
+                               // two scalar adds put it on the base; padding slots s >= S repeat view S - 1's (a valid address)
+    const float* rx_w;         // [dim_d][slots] pairs (t, 1 - t); zeros in padding slots (what marks them)
+    const float* rx_D;         // [dim_d] hypothesis(dmin, dmax - dmin, dim_d - 1, d)
+    const int* rx_exact;       // [dim_d] 1: every view offset s < S of the hypothesis is row-exact
 };
+
+// (offsets and weights are planes of their own, 8 bytes per slot each: a gather round needs its offsets before its loads and
+// its weights after them, so the two are asked for at different times and never held together for two rounds)
 
 // Laid out WORD-major in memory ([item][word][lane], record_word): a wave's store of one word is then 256 contiguous bytes.
 // Lane-major 32-byte structs made every dword store touch sixteen 128-byte lines in part, and the write-through (sc1) stores

@@ -87,4 +87,37 @@ RSLF_TAPS_FN TapEntry tap_entry(float off, int u_first, int u_last, int U, int C
     return e;
 }
 
+// The same entry for a whole ROW: every pixel 0 <= u <= U - 1 whose sample lies inside the row, on every scanline.  Rule (b)
+// asked at the row's widest pixel does not depend on the tile: when x_last = fl(off + (U - 1)) is the exact sum, `off` is a
+// multiple of x_last's quantum (U - 1 is an integer, the quantum at most 1), so off + u is a multiple of it no larger than
+// x_last for every sample inside [0, x_last]: representable, the sum exact.  Then floor(x) - u = floor(off) and
+// t = off - floor(off) in every pixel, and {tap offset, t, 1 - t} is a function of the view offset alone.
+// The entry is made from x_last, a position inside the row like the ones the lanes compute (positive: fract and the
+// floor-convert are used where scan_reg_body uses them), not from `off`, which may be negative.  `exact` also asks
+// 1 <= x_last < 2^23 (a row some sample can be inside of; quantum below 1) and that `byteoff` did not wrap.
+struct RowExactEntry {
+    int byteoff;    // of pixel 0's left tap, from the EPI's base: ((floor(off)) * C + row) * 4 -- negative where floor(off) < 0;
+                    // pixel u reads at byteoff + u * C * 4
+    float t, omt;
+    bool exact;     // the entry holds for every pixel of the row whose sample lies inside it
+};
+
+RSLF_TAPS_FN RowExactEntry row_exact_entry(float off, int U, int C, int row_floats)
+{
+    const float ul = (float)(U - 1);
+    const float x_last = off + ul;             // core.hpp:552 at the widest pixel
+    const float back = x_last - ul;
+    RowExactEntry e;
+    const bool sane = x_last >= 1.0f && x_last < 8388608.0f;
+    const float xs = sane ? x_last : 1.0f;     // (keeps the conversions below defined)
+    e.t = tap_fract(xs);                       // interp.hpp:181
+    const int i_last = tap_floor(xs);          // interp.hpp:179
+    e.omt = 1.0f - e.t;
+    const long long floats = (long long)(i_last - (U - 1)) * C + row_floats;
+    e.byteoff = (int)((unsigned)floats << 2);
+    const bool fits = floats >= -(1LL << 28) && floats < (1LL << 28);
+    e.exact = sane && fits && back == off;     // rule (b) at u = U - 1
+    return e;
+}
+
 }  // namespace rslf

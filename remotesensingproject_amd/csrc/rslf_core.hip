@@ -251,6 +251,8 @@ extern "C" int rslf_ctx_set_debug(rslf_ctx* ctx, const char* key, int value) RSL
         ctx->row_split = value;
     else if (strcmp(key, "tap_table") == 0 && (value == 0 || value == 1))
         ctx->tap_table = value;
+    else if (strcmp(key, "scalar_taps") == 0 && (value == 0 || value == 1))
+        ctx->scalar_taps = value;
     else if (strcmp(key, "claim_skip") == 0 && (value == 0 || value == 1))
         ctx->claim_skip = value;
     else if (strcmp(key, "time_all") == 0 && (value == 0 || value == 1)) {

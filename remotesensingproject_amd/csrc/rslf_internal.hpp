@@ -212,6 +212,7 @@ struct Scratch {
     DeviceBuf scan_partial; // rslf::Partial [tile][group][64]: records of grouped scan launches
     DeviceBuf scan_ticket;  // int [tile] of the same launches: which group merges the tile (zero between launches)
     DeviceBuf max_partial;  // float [kMaxPartials]: block maxima of rslf_device_max_f32
+    DeviceBuf row_exact;    // the scan's row-exact table (k2_scan.hpp, ScanArgs::rx_*): [D][slots] offsets, [D][slots] weight pairs, [D] floats, [D] ints; RowExactKey says of what
     // 2-D sweep
     DeviceBuf winner;       // int [S][V][U]: the claims (0x7F7F7F7F between visits)
     DeviceBuf sweep_mask;   // u8 [S][V][U]: the running masks, unless the caller gives the plane
@@ -226,6 +227,29 @@ struct Scratch {
     unsigned long long* pixel_total() const { return total.as<unsigned long long>(); }
     int* packed_len() const { return reinterpret_cast<int*>(pixel_total() + 1); }   // an int in the second u64 of `total`
     uint8_t* morph_tmp() const { return depth_tmp.as<uint8_t>(); }                   // V*U floats: room for a byte plane
+};
+
+// Slots per hypothesis of the row-exact table a register row kernel of `spad` slots x C channels reads, 0: the kernel has no
+// scalar-tap form (k2_reg.hpp, scan_reg_scalar_taps: the 104-slot one-channel kernel) -- and the table's size in bytes:
+// [dim_d][slots] 8-byte offsets, [dim_d][slots] weight pairs, [dim_d] disparities, [dim_d] flags.
+constexpr int row_exact_slots(int spad, int C) { return (C == 1 && spad == 104) ? spad : 0; }
+constexpr size_t row_exact_bytes(int dim_d, int slots) { return (size_t)dim_d * ((size_t)slots * 16 + 8); }
+
+// What the row-exact table in Scratch::row_exact was made from: everything its entries depend on.  A scan with the same key
+// finds the table in place (a pile call after another, the frames of a sequence); any other key refills it on the scan's
+// stream, ahead of the scan -- so does each visit of a 2-D sweep that takes the row kernel: the entries depend on s_hat.
+struct RowExactKey {
+    float dmin = 0.0f, dmax = 0.0f, slope = 0.0f;
+    int dim_d = 0, s_hat = 0, S = 0, U = 0, C = 0, slots = 0;   // dim_d == 0: no table yet
+    long long stride_s = 0;
+    const void* queued_on = nullptr;   // the stream the fill was queued on: a scan on another one is not ordered after it, and refills
+    bool same(const RowExactKey& o) const
+    {
+        // (floats by their bits: a NaN key never matches, -0 and +0 differ)
+        return memcmp(&dmin, &o.dmin, sizeof(float)) == 0 && memcmp(&dmax, &o.dmax, sizeof(float)) == 0 &&
+               memcmp(&slope, &o.slope, sizeof(float)) == 0 && dim_d == o.dim_d && s_hat == o.s_hat && S == o.S && U == o.U && C == o.C &&
+               slots == o.slots && stride_s == o.stride_s && queued_on == o.queued_on;
+    }
 };
 
 // An open 2-D sweep (rslf_sweep_begin .. rslf_sweep_end).  The defaults are "no sweep open": sweep_close assigns them.
@@ -280,6 +304,9 @@ struct rslf_ctx {
     size_t stream_lds_bytes = rslf::plan::kStreamLdsBytes;   // dynamic LDS of one streaming workgroup
     int row_split = 1;         // packed launches of stream-class volumes: rows with many pixels as row tiles of the list (0: off; A/B and tests)
     int tap_table = 1;         // register row kernels that have one take lane-invariant lerp taps from it (k2_reg.hpp; 0: off, A/B and tests)
+    int scalar_taps = 1;       // ... and row-exact hypotheses take the scalar-tap form from the per-launch table (k2_reg.hpp; 0: off, A/B and tests)
+    rslf::RowExactKey row_exact_key;   // what scratch.row_exact holds
+    bool last_row_exact = false;       // the last scan's launch was handed the table (rslf_last_scan_row_exact)
     int claim_skip = 1;        // 2-D sweep: the claims skip views with nothing left to paint within reach (0: off, A/B and tests)
     int staging_kib = 0;       // chunked host upload: device staging per pass in KiB (0: plan::kStagingBudget; tests of the later passes)
 };

@@ -15,6 +15,8 @@ using namespace rslf;
 
 static_assert(sizeof(Partial) == plan::kPartialRecordBytes, "rslf_plan.hpp sizes the record scratch");
 static_assert(kScanWaves == plan::kScanWavesPerTile, "rslf_plan.hpp shares the hypotheses out over this many waves");
+static_assert(!RSLF_SCALAR_TAPS || !RSLF_TAP_TABLE || (scan_reg_scalar_taps(104, 1) && row_exact_slots(104, 1) == 104),
+              "rslf_internal.hpp names the kernel that has the scalar-tap form");
 
 // ---- hot path -------------------------------------------------------------
 
@@ -188,6 +190,7 @@ static plan::ScanRequest scan_request(const rslf_ctx* ctx, int V, int U, int S, 
     rq.tap_table = ctx->tap_table;
     const bool dense_uniform = !pixel_ranges && !in.packed && ctx->force_packed != 1 && in.lists != ScanInputs::kPackedList;
     plan::choose_scan_kernel(&rq, in_range, linear, ctx->force_scan, dense_uniform, kernel_facts(S, C));
+    rq.scalar_taps = (ctx->scalar_taps && !pixel_ranges && row_exact_slots(rq.spad, C)) ? 1 : 0;   // the kernel has the scalar-tap form
     return rq;
 }
 
@@ -273,6 +276,76 @@ static int check_scan_args(const rslf_volume* vol, const float* d_dmin_vu, const
         return fail(RSLF_ERR_INVALID_ARG, "s_hat=%d outside [0,%d)", s_hat, vol->S);
     if (!vol->filled)
         return fail(RSLF_ERR_INVALID_ARG, "volume has not been filled");
+    return RSLF_OK;
+}
+
+// The row-exact table of one hypothesis grid and row geometry (k2_taps.hpp, row_exact_entry; read by scan_reg_body_scalar):
+// workgroup d fills hypothesis d -- thread s the entry of view s, padding slots the last view's with zero weights -- its disparity, the same
+// hypothesis() call as the scan's, and whether every view offset s < S is row-exact.
+__global__ __launch_bounds__(128) void k2_fill_row_exact(float dmin, float dmax, int dim_d, float slope, int s_hat, int S, int slots, int U,
+                                                         int C, int stride_s, long long* __restrict__ out_off, f2* __restrict__ out_w,
+                                                         float* __restrict__ out_D, int* __restrict__ out_exact)
+{
+    const int d = blockIdx.x, s = threadIdx.x;
+    const float Dd = hypothesis(dmin, dmax - dmin, (float)(dim_d - 1), d);
+    bool ok = true;
+    if (s < slots) {
+        // (a padding slot: view S - 1's offset, so that a consumer that loads it reads a valid address, and zero weights)
+        const int sv = min(s, S - 1);
+        float off = (float)(s_hat - sv) * Dd;   // float(s_hat - s) * D[d]   core.hpp:542,550
+        off = off * slope;                      // core.hpp:551
+        const RowExactEntry e = row_exact_entry(off, U, C, sv * stride_s);
+        const long long bo = (long long)e.byteoff;
+        const f2 w = s < S ? f2{e.t, e.omt} : f2{0.0f, 0.0f};
+        ok = e.exact;
+        out_off[(size_t)d * slots + s] = bo;
+        out_w[(size_t)d * slots + s] = w;
+    }
+    const int all = __syncthreads_and(ok ? 1 : 0);
+    if (s == 0) {
+        out_D[d] = Dd;
+        out_exact[d] = all ? 1 : 0;
+    }
+}
+
+// Hand the launch its row-exact table where the plan asks for one (one hypothesis grid for all pixels): found in place when
+// the context's last table was made from the same key, else filled on the scan's stream, ahead of the scan -- no host-side
+// fill, no copy.  The kernels of the stream that still read the old table run before the fill.
+static int attach_row_exact(rslf_ctx* ctx, ScanArgs& a, const plan::ScanPlan& p, hipStream_t st)
+{
+    // (the row kernel itself, and only where it is built with the form: an A/B build without it launches nothing extra)
+    const bool has_form = p.kind == RSLF_SCAN_REG && !p.packed && a.vol.C == 1 && p.spad == 104 && scan_reg_scalar_taps(104, 1);
+    const int slots = has_form && p.scalar_taps && !a.dmin_vu ? row_exact_slots(p.spad, a.vol.C) : 0;
+    ctx->last_row_exact = false;
+    if (!slots || a.vol.S > slots || a.vol.S <= slots - 16 || slots > 128 || a.vol.stride_s * (long long)slots > INT32_MAX)
+        return RSLF_OK;
+    RowExactKey key;
+    key.dmin = a.dmin, key.dmax = a.dmax, key.slope = a.k.slope;
+    key.dim_d = a.dim_d, key.s_hat = a.s_hat, key.S = a.vol.S, key.U = a.vol.U, key.C = a.vol.C, key.slots = slots;
+    key.stride_s = a.vol.stride_s;
+    key.queued_on = st;
+    const Reserved r = ctx->scratch.row_exact.reserve(row_exact_bytes(a.dim_d, slots));
+    if (r.err) {
+        ctx->row_exact_key = RowExactKey{};
+        HIP_TRY(hip_err(r));
+    }
+    char* base = ctx->scratch.row_exact.as<char>();
+    long long* d_off = reinterpret_cast<long long*>(base);
+    f2* d_w = reinterpret_cast<f2*>(d_off + (size_t)a.dim_d * slots);
+    float* d_D = reinterpret_cast<float*>(d_w + (size_t)a.dim_d * slots);
+    int* d_exact = reinterpret_cast<int*>(d_D + a.dim_d);
+    if (r.fresh || !key.same(ctx->row_exact_key)) {
+        ctx->row_exact_key = RowExactKey{};
+        hipLaunchKernelGGL(k2_fill_row_exact, dim3(a.dim_d), dim3(128), 0, st, a.dmin, a.dmax, a.dim_d, a.k.slope, a.s_hat, a.vol.S, slots,
+                           a.vol.U, a.vol.C, (int)a.vol.stride_s, d_off, d_w, d_D, d_exact);
+        HIP_TRY(hipGetLastError());
+        ctx->row_exact_key = key;
+    }
+    a.rx_off = d_off;
+    a.rx_w = reinterpret_cast<const float*>(d_w);
+    a.rx_D = d_D;
+    a.rx_exact = d_exact;
+    ctx->last_row_exact = true;
     return RSLF_OK;
 }
 
@@ -425,6 +498,9 @@ int rslf::depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
     apply_plan(a, sp, ctx);
     apply_plan(ar, spr, ctx);
     ar.rowbase = sc.rowbase.as<int>();
+    rc = attach_row_exact(ctx, a, sp, st);   // (the row split's tiles belong to stream-class volumes: no register kernel, no table)
+    if (rc)
+        return rc;
     ctx->last_spad = sp.spad;
     ctx->last_kernel = sp.kind;
     HIP_TRY(hipGetLastError());   // anything an earlier enqueue left behind is not this launch's fault
@@ -695,6 +771,26 @@ extern "C" int rslf_scan_time_total_ms(rslf_ctx* ctx, float* ms, int* launches) 
     if (launches)
         *launches = (int)(ctx->ev_used / 2);
     ctx->ev_used = 0;
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_last_scan_row_exact(rslf_ctx* ctx, int* attached, int* exact_hypotheses) RSLF_API_TRY
+{
+    if (!ctx || !attached || !exact_hypotheses)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    *attached = ctx->last_row_exact ? 1 : 0;
+    *exact_hypotheses = 0;
+    if (!ctx->last_row_exact)
+        return RSLF_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const RowExactKey& k = ctx->row_exact_key;   // (the last launch's: attach_row_exact left it there)
+    std::vector<int> flags((size_t)k.dim_d);
+    const char* d_flags = ctx->scratch.row_exact.as<char>() + (size_t)k.dim_d * ((size_t)k.slots * 16 + sizeof(float));
+    HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, flags.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int f : flags)
+        *exact_hypotheses += f != 0;
     return RSLF_OK;
 }
 RSLF_API_CATCH

@@ -704,7 +704,7 @@ struct ScanRequest {
     int stream_groups;     // 0 = kStreamGroups
     int stream_share;      // 63-pixel row tiles (shared taps): 0 never, 1 where the re-gathered tail is long enough to pay for them, 2 always
     size_t stream_lds_bytes;
-    int tap_table;         // register row kernels that have one: lane-invariant lerp taps from the per-hypothesis table (0: off; A/B and tests)
+    int tap_table, scalar_taps;   // register row kernels that have them: lane-invariant lerp taps from the per-hypothesis table / row-exact hypotheses' taps as scalars from the per-launch table (0: off; A/B and tests)
 };
 
 struct ScanPlan {
@@ -714,7 +714,7 @@ struct ScanPlan {
     bool packed;           // one packed list over all scanlines
     bool packed_adapt;     // the device settles the group count from the list length
     int px_waves;          // > 0: the pixel-per-wave kernel takes the packed list, this many waves per pixel (no groups, no records)
-    int tap_table;         // the register row kernel may take its taps from the table (the request's hook; row tiles only)
+    int tap_table, scalar_taps;   // the register row kernel may take its taps from the table / the launch gets a row-exact table (the request's hooks, both on for the second; row tiles only)
     int tile_w;            // 63 or 64 entries per row tile
     int tiles_per_row;
     int rows_per_launch;   // grouped row-tile launches go by blocks of scanlines
@@ -854,7 +854,7 @@ inline ScanPlan plan_scan(const ScanRequest& r, int nres, int nres_px = -1)
         while (groups > 1 && ((n + 63) / 64) * groups * 64 * kPartialRecordBytes > kPartialBudget)
             groups /= 2;
     p.px_waves = px_w;
-    p.tap_table = (r.spad && !packed && r.tap_table) ? 1 : 0;
+    p.tap_table = (r.spad && !packed && r.tap_table) ? 1 : 0, p.scalar_taps = (p.tap_table && r.scalar_taps) ? 1 : 0;
     p.spad = r.spad;
     p.kind = r.spad ? (px_w ? RSLF_SCAN_REG_PX : RSLF_SCAN_REG)
              : r.use_chip ? RSLF_SCAN_CHIP

@@ -118,7 +118,7 @@ class Context:
         check(_lib.lib().rslf_ctx_synchronize(self._h), "rslf_ctx_synchronize")
 
     _DEBUG_DEFAULTS = dict(force_scan=0, force_groups=0, force_packed=-1, px=-1, stream_share=1, stream_groups=0, stream_lds_kib=80,
-                           claim_skip=1, time_all=0, row_split=1, staging_kib=0, tap_table=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
+                           claim_skip=1, time_all=0, row_split=1, staging_kib=0, tap_table=1, scalar_taps=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
     _FORCE_SCAN = {None: 0, "auto": 0, "generic": 1, "stream": 2}
 
     def set_debug(self, **hooks) -> None:
@@ -136,6 +136,12 @@ class Context:
         ms = C.c_float()
         check(_lib.lib().rslf_last_scan_kernel_ms(self._h, C.byref(ms)), "rslf_last_scan_kernel_ms")
         return float(ms.value)
+
+    def last_scan_row_exact(self) -> tuple[bool, int]:
+        """(the last scan's launch was handed a row-exact table, row-exact hypotheses in it): rslf_last_scan_row_exact."""
+        a, n = C.c_int(), C.c_int()
+        check(_lib.lib().rslf_last_scan_row_exact(self._h, C.byref(a), C.byref(n)), "rslf_last_scan_row_exact")
+        return bool(a.value), int(n.value)
 
     def scan_time_total_ms(self) -> tuple[float, int]:
         """With set_debug(time_all=1): (summed K2 milliseconds, scan launches) since the last call; resets the sum."""
