@@ -295,6 +295,48 @@ int rslf_depth_epi_scores_host(rslf_ctx* ctx, const rslf_volume* vol, const floa
                                float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
                                const uint8_t* h_mask_vu, int v_first, int n_rows, float* h_scores_vud, rslf_stats* stats);
 
+/* The peaks of the score rows: per pixel the winner, a sub-grid disparity and the runner-up peak (the peak-ratio ambiguity
+ * measure), computed on the device from the rows above.  Not in the reference; no existing output changes.
+ * With s[0..D-1] a pixel's scores and [lo, hi] its range (the scalars, or its entries of the planes), every operation one
+ * IEEE binary32 operation in the order written:
+ *   candidates    j with (j == 0 || s[j] > s[j-1]) && (j == D-1 || s[j] >= s[j+1]): the first element of each local
+ *                 maximum or plateau
+ *   idx, score    i1 = the candidate with the largest score, the first on ties (the scan's arg max); s1 = s[i1]
+ *   runner_*      i2 = the candidate with the largest score among the others, the first on ties (a later one as high as
+ *                 the winner counts); s[i2]; -1 and 0 without another candidate
+ *   disp          Dd + delta * step, with Dd = lo + ((float)i1 * (hi - lo)) / (float)(D-1) (the scan's grid value),
+ *                 step = (hi - lo) / (float)(D-1), and delta = 0 at i1 == 0 or D-1, else with a = s[i1-1], c = s[i1+1]:
+ *                 den2 = ((a + c) - (s1 + s1)) doubled by one addition, delta = den2 == 0 ? 0 : (a - c) / den2 clamped
+ *                 to [-0.5, 0.5] -- the vertex of the parabola through the three points
+ * A NaN score gives unspecified values (no fault).  Each of the five planes, [n_rows][U], may be NULL, not all of them. */
+typedef struct rslf_peaks {
+    int32_t* idx;
+    float* score;
+    float* disp;
+    int32_t* runner_idx;
+    float* runner_score;
+} rslf_peaks;
+
+/* The peaks of rows the caller holds: d_scores_vud is [n_rows][U][dim_d] as rslf_depth_epi_scores writes it for the
+ * scanlines [v_first, v_first + n_rows); the mask (nullable) and the range planes (both or neither) are full [V][U]
+ * planes, read at those scanlines.  Pixels whose mask byte is 0 are neither read nor written.  dim_d in [2, 2^24].
+ * Queued on the context's stream; does not wait. */
+int rslf_score_peaks(rslf_ctx* ctx, const float* d_scores_vud, int U, int dim_d, const float* d_dmin_vu, const float* d_dmax_vu,
+                     float dmin, float dmax, const uint8_t* d_mask_vu, int v_first, int n_rows, const rslf_peaks* d_out);
+/* Score rows and their peaks for a window of scanlines: arguments as rslf_depth_epi_scores, checked the same way.  The
+ * rows go through the context's staging buffer in passes of as many scanlines as its budget holds (at least one; the
+ * "staging_kib" hook sets the budget) and never leave the device.  d_out: device planes [n_rows][U]; pixels outside the
+ * mask are left untouched.  Everything is queued on the context's stream; it waits only when stats is given.  One device;
+ * not inside an open sweep. */
+int rslf_depth_epi_peaks(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                         float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
+                         const uint8_t* d_mask_vu, int v_first, int n_rows, const rslf_peaks* d_out, rslf_stats* stats);
+/* The same with the mask and the five planes on the host (the range planes stay device pointers, as in
+ * rslf_depth_epi_scores_host).  Unscanned pixels get idx = runner_idx = -1 and the floats 0.  Synchronises. */
+int rslf_depth_epi_peaks_host(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                              float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
+                              const uint8_t* h_mask_vu, int v_first, int n_rows, const rslf_peaks* h_out, rslf_stats* stats);
+
 /* rslf::selective_median_filter -- core.hpp:366-375, impl :663-718.
  * d_dst_vu must not alias d_src_vu; it is fully written (0 where mask is 0).
  * `size` = a_size: the window is width = (size - 1) / 2 pixels either side (:686), so an even size is the next smaller

@@ -467,6 +467,33 @@ public:
         return out;
     }
 
+    // After run(): the peaks of those score rows (rslf_hip.h, rslf_peaks) -- winner, sub-grid disparity, runner-up -- over
+    // the pixels of the final edge-confidence mask, [n_rows][U] each; other pixels hold -1 / 0.  The rows stay on the
+    // device.  Refused on a MultiContext, as get_scores is.
+    struct Peaks {
+        std::vector<int32_t> idx, runner_idx;
+        std::vector<float> score, disp, runner_score;
+    };
+    Peaks get_peaks(int v_first = 0, int n_rows = -1) const
+    {
+        if (multi_)
+            throw std::invalid_argument("get_peaks: this object was built on a MultiContext, which keeps no volume on a device: "
+                                        "score-row peaks are built for one context");
+        detail::require(!m_best_depth_v_u.empty(), "the getters show the results of run(): call it first");
+        if (n_rows < 0)
+            n_rows = dim_v_ - v_first;
+        detail::require(v_first >= 0 && n_rows > 0 && n_rows <= dim_v_ - v_first, "get_peaks: the scanlines are not a window of the volume");
+        const size_t n = (size_t)n_rows * dim_u_;
+        Peaks out;
+        out.idx.resize(n), out.runner_idx.resize(n), out.score.resize(n), out.disp.resize(n), out.runner_score.resize(n);
+        const rslf_peaks planes = {out.idx.data(), out.score.data(), out.disp.data(), out.runner_idx.data(), out.runner_score.data()};
+        const rslf_params p = m_parameters.to_c();
+        check(rslf_depth_epi_peaks_host(ctx_->get(), vol_, nullptr, nullptr, m_dmin, m_dmax, m_dim_d, m_s_hat, &p,
+                                        m_edge_confidence_mask_v_u.data(), v_first, n_rows, &planes, nullptr),
+              "rslf_depth_epi_peaks_host");
+        return out;
+    }
+
     int rows() const { return dim_v_; }
     int cols() const { return dim_u_; }
     float epi_scale_factor() const { return scale_used_; }

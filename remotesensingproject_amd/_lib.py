@@ -48,6 +48,8 @@ SYMBOLS = [
     "rslf_f2c_run_render_depth_pyr_host", "rslf_f2c_run_render_epi_pyr", "rslf_f2c_run_render_epi_pyr_host",
     # the scan's score matrix
     "rslf_depth_epi_scores", "rslf_depth_epi_scores_host",
+    # ... and its peaks
+    "rslf_score_peaks", "rslf_depth_epi_peaks", "rslf_depth_epi_peaks_host",
 ]
 
 
@@ -92,6 +94,14 @@ class RslfStats(C.Structure):
         ("units", C.c_int64),
         ("scan_kernel", C.c_int),
         ("s_pad", C.c_int),
+    ]
+
+
+class RslfPeaks(C.Structure):
+    """rslf_peaks: the five planes of the score-row peaks, device or host pointers, each nullable."""
+
+    _fields_ = [
+        ("idx", C.c_void_p), ("score", C.c_void_p), ("disp", C.c_void_p), ("runner_idx", C.c_void_p), ("runner_score", C.c_void_p),
     ]
 
 
@@ -187,6 +197,10 @@ def lib():
                                       vp, vp, vp, C.POINTER(RslfStats)]
     L.rslf_depth_epi_scores.argtypes = [vp, vp, vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, ci, ci, vp, C.POINTER(RslfStats)]
     L.rslf_depth_epi_scores_host.argtypes = L.rslf_depth_epi_scores.argtypes
+    L.rslf_score_peaks.argtypes = [vp, vp, ci, ci, vp, vp, cf, cf, vp, ci, ci, C.POINTER(RslfPeaks)]
+    L.rslf_depth_epi_peaks.argtypes = [vp, vp, vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, ci, ci, C.POINTER(RslfPeaks),
+                                       C.POINTER(RslfStats)]
+    L.rslf_depth_epi_peaks_host.argtypes = L.rslf_depth_epi_peaks.argtypes
     L.rslf_depth1d_run.argtypes = [vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, vp, vp,
                                    C.POINTER(RslfStats)]
     L.rslf_depth1d_pile_run.argtypes = [vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, vp, vp, vp,

@@ -6,6 +6,7 @@
 //   rslf_pile.hip         the hot path: edge confidence (K1), scan (K2), selective median (K3), Depth1DComputer(_pile)
 //   rslf_chip_a/b/c.hip   the on-chip scan kernel's instantiations, one per rung of its ladder (launched by rslf_pile.hip)
 //   rslf_scores.hip       the scan's score matrix as an output: rslf_depth_epi_scores and its host form (k2_scores.hpp)
+//   rslf_peaks.hip        the score rows' consumer: winner, sub-grid disparity and runner-up per pixel (k8_peaks.hpp)
 //   rslf_sweep.hip        the 2-D sweep and its propagation (K4), Depth2DComputer::run
 //   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the one native level loop
 //   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters
@@ -428,6 +429,18 @@ void fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_stats* st
 int read_stats(rslf_ctx* ctx, int dim_d, rslf_stats* stats);
 int scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf_params* p, const int* rows, int n_rows);
 int sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const ScanInputs& sparse);
+
+// rslf_scores.hip
+// What rslf_depth_epi_scores checks before anything is queued (`out`: the caller's output, non-NULL), and the rows of the
+// scanlines [v_first, v_first + n_rows) into d_scores ([n_rows][U][dim_d]) with arguments already checked: queued on the
+// context's stream, the scanned pixels left in scratch.pixel_total().  read_pixel_total waits for the stream.
+int check_score_args(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat,
+                     const rslf_params* p, int v_first, int n_rows, const void* out);
+int score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax, int dim_d,
+               int s_hat, const rslf_params* p, const uint8_t* d_mask_vu, int v_first, int n_rows, float* d_scores, int* kind_out,
+               int* spad_out);
+int read_pixel_total(rslf_ctx* ctx, unsigned long long* tot);
+void score_stats(unsigned long long pixels, int dim_d, int kind, int spad, rslf_stats* stats);
 
 // rslf_sweep.hip
 // Depth2DComputer::run (dc.hpp:748-805) on device planes; d_dmin_svu / d_dmax_svu: per-pixel ranges (a fine-to-coarse

@@ -37,8 +37,8 @@ static int launch_score_rows_reg(int spad, int C, const ScanArgs& a, const Score
     return fail(RSLF_ERR_UNSUPPORTED, "no register score kernel with %d slots x %d channels", spad, C);
 }
 
-// Everything both forms check, before anything is queued
-static int check_score_args(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat,
+// Everything both forms check, before anything is queued (rslf_peaks.hip checks its windows the same way)
+int rslf::check_score_args(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat,
                             const rslf_params* p, int v_first, int n_rows, const void* scores)
 {
     if (!ctx || !vol || !scores)
@@ -62,7 +62,7 @@ static int check_score_args(rslf_ctx* ctx, const rslf_volume* vol, const float* 
 }
 
 // The rows of scanlines [v_first, v_first + n_rows) into d_scores (that window's [n_rows][U][dim_d]); arguments checked.
-static int score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
+int rslf::score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
                       int dim_d, int s_hat, const rslf_params* p, const uint8_t* d_mask_vu, int v_first, int n_rows, float* d_scores,
                       int* kind_out, int* spad_out)
 {
@@ -121,7 +121,7 @@ static int score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin
     return RSLF_OK;
 }
 
-static void score_stats(unsigned long long pixels, int dim_d, int kind, int spad, rslf_stats* stats)
+void rslf::score_stats(unsigned long long pixels, int dim_d, int kind, int spad, rslf_stats* stats)
 {
     stats->pixels_scanned = (int64_t)pixels;
     stats->units = (int64_t)pixels * dim_d;
@@ -129,7 +129,7 @@ static void score_stats(unsigned long long pixels, int dim_d, int kind, int spad
     stats->s_pad = spad;
 }
 
-static int read_pixel_total(rslf_ctx* ctx, unsigned long long* tot)
+int rslf::read_pixel_total(rslf_ctx* ctx, unsigned long long* tot)
 {
     HIP_TRY(hipMemcpyAsync(tot, ctx->scratch.pixel_total(), sizeof(*tot), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -18,7 +18,7 @@ import copy
 import ctypes as C
 import sys
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -544,6 +544,84 @@ def compute_1D_depth_scores(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int, a
     return (out, st) if want_stats else out
 
 
+class Peaks(NamedTuple):
+    """The peaks of score rows, [n_rows, U] each: the winner's index and score (the scan's arg max), the sub-grid
+    disparity (the vertex of the parabola through the winner and its two neighbours, within half a grid step of the
+    winner's grid value), and the runner-up peak's index (-1: none) and score (0 without one).  include/rslf_hip.h,
+    rslf_peaks, states the arithmetic."""
+    idx: Optional[torch.Tensor]
+    score: Optional[torch.Tensor]
+    disp: Optional[torch.Tensor]
+    runner_idx: Optional[torch.Tensor]
+    runner_score: Optional[torch.Tensor]
+
+
+def _peak_planes(out: Peaks | None, n_rows: int, U: int, device) -> tuple[Peaks, _lib.RslfPeaks]:
+    """The planes a peaks call writes -- made here (-1 / 0, what an unscanned pixel keeps) or the caller's, of which some
+    may be None -- and the C struct of their pointers."""
+    shape = (max(n_rows, 0), U)
+    if out is None:
+        out = Peaks(*(torch.full(shape, -1, dtype=torch.int32, device=device) if name.endswith("idx")
+                      else torch.zeros(shape, dtype=torch.float32, device=device) for name in Peaks._fields))
+    else:
+        out = Peaks(*out)
+        for name, t in zip(Peaks._fields, out):
+            want = torch.int32 if name.endswith("idx") else torch.float32
+            if t is not None and (tuple(t.shape) != shape or t.dtype != want or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("out.%s must be a contiguous %s CUDA tensor of shape %s" % (name, want, shape))
+    return out, _lib.RslfPeaks(*(None if t is None else t.data_ptr() for t in out))
+
+
+def _check_mask_plane(a_mask_v_u, V: int | None, U: int) -> None:
+    if a_mask_v_u is not None and (a_mask_v_u.dim() != 2 or a_mask_v_u.shape[1] != U or (V is not None and a_mask_v_u.shape[0] != V)
+                                   or a_mask_v_u.dtype != torch.uint8 or not a_mask_v_u.is_contiguous()):
+        raise ValueError("a_mask_v_u must be a contiguous uint8 [V, U] plane")
+
+
+def score_peaks(scores: torch.Tensor, a_dmin_v_u, a_dmax_v_u, a_mask_v_u: torch.Tensor | None = None, v_first: int = 0,
+                out: Peaks | None = None, ctx: Context | None = None) -> Peaks:
+    """Peaks of score rows the caller holds: `scores` is [n_rows, U, D] f32 on the device, as compute_1D_depth_scores
+    returns it for the scanlines from v_first on.  a_dmin_v_u / a_dmax_v_u: Python floats, or full [V, U] f32 planes read
+    at those scanlines, like the mask ([V, U] u8; None: every pixel).  Pixels outside the mask keep what `out` held
+    (-1 / 0 when the tensors are made here); members of `out` may be None, not all.  Nothing leaves the device."""
+    if scores.dim() != 3 or scores.dtype != torch.float32 or not scores.is_cuda or not scores.is_contiguous():
+        raise ValueError("scores must be a contiguous float32 CUDA tensor [n_rows, U, D]")
+    n_rows, U, D = (int(x) for x in scores.shape)
+    planes = isinstance(a_dmin_v_u, torch.Tensor)
+    _check_mask_plane(a_mask_v_u, None, U)
+    for t in ((a_mask_v_u, a_dmin_v_u, a_dmax_v_u) if planes else (a_mask_v_u,)):
+        if t is not None and (t.dim() != 2 or t.shape[1] != U or t.shape[0] < int(v_first) + n_rows):
+            raise ValueError("the mask and the range planes are [V, U] planes that hold the scanlines [v_first, v_first + n_rows)")
+    ctx = ctx or default_context(scores.device)
+    out, c_out = _peak_planes(out, n_rows, U, scores.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_score_peaks(
+        ctx._h, _ptr(scores), U, D, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
+        0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), _ptr(a_mask_v_u), int(v_first), n_rows,
+        C.byref(c_out)), "rslf_score_peaks")
+    return out
+
+
+def compute_1D_depth_peaks(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int, a_s_hat: int,
+                           parameters: Depth1DParameters | None = None, a_mask_v_u: torch.Tensor | None = None,
+                           v_first: int = 0, n_rows: int | None = None, out: Peaks | None = None, *, want_stats: bool = False):
+    """Score rows and their peaks for the scanlines [v_first, v_first + n_rows) -> Peaks of [n_rows, U] tensors on the
+    volume's device.  Arguments as compute_1D_depth_scores; the rows themselves pass through the context's staging buffer
+    and are not kept.  want_stats: returns (peaks, rslf_stats), and waits."""
+    p = (parameters or Depth1DParameters()).to_c()
+    planes = isinstance(a_dmin_v_u, torch.Tensor)
+    n_rows = vol.V - int(v_first) if n_rows is None else int(n_rows)
+    _check_mask_plane(a_mask_v_u, vol.V, vol.U)
+    out, c_out = _peak_planes(out, n_rows, vol.U, vol.ctx.device)
+    st = RslfStats() if want_stats else None
+    vol.ctx.use_current_stream()
+    check(_lib.lib().rslf_depth_epi_peaks(
+        vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
+        0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), int(a_dim_d), int(a_s_hat), C.byref(p),
+        _ptr(a_mask_v_u), int(v_first), n_rows, C.byref(c_out), C.byref(st) if st is not None else None), "rslf_depth_epi_peaks")
+    return (out, st) if want_stats else out
+
+
 def selective_median_filter(a_src: torch.Tensor, vol: Volume, a_s_hat: int, a_size: int, a_mask_v_u: torch.Tensor,
                             a_epsilon: float) -> torch.Tensor:
     """core.hpp:366-375; returns a_dst."""
@@ -637,6 +715,16 @@ class Depth1DComputer_pile:
             raise RuntimeError("get_scores shows the pixels run() gave a disparity: call run() first")
         return compute_1D_depth_scores(self.m_epis, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, self.m_parameters,
                                        self.m_edge_confidence_mask_v_u, v_first, n_rows)
+
+    def get_peaks(self, v_first: int = 0, n_rows: int | None = None) -> Peaks:
+        """After run(): the peaks of the score rows of scanlines [v_first, v_first + n_rows) over the pixels of the final
+        edge-confidence mask, like get_scores -> Peaks of [n_rows, U] tensors: idx equals m_depth_idx_v_u and score
+        m_score_v_u there, disp is the winner's grid value moved by at most half a grid step, runner_idx / runner_score the
+        second peak.  Other pixels hold -1 / 0.  A scan of its own; the rows stay on the device and are not kept."""
+        if not getattr(self, "_ran", False):
+            raise RuntimeError("get_peaks shows the pixels run() gave a disparity: call run() first")
+        return compute_1D_depth_peaks(self.m_epis, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, self.m_parameters,
+                                      self.m_edge_confidence_mask_v_u, v_first, n_rows)
 
     def results(self) -> dict:
         """Host copies of every output plane."""
@@ -1100,6 +1188,13 @@ class Depth1DComputer:
             raise RuntimeError("get_scores_u_d shows the pixels run() gave a disparity: call run() first")
         return compute_1D_depth_scores(self.m_epi, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, self.m_parameters,
                                        self.m_edge_confidence_mask_u)[0]
+
+    def get_peaks_u(self) -> Peaks:
+        """After run(): the EPI's peaks (Depth1DComputer_pile.get_peaks), [U] each."""
+        if not getattr(self, "_ran", False):
+            raise RuntimeError("get_peaks_u shows the pixels run() gave a disparity: call run() first")
+        return Peaks(*(t[0] for t in compute_1D_depth_peaks(self.m_epi, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat,
+                                                            self.m_parameters, self.m_edge_confidence_mask_u)))
 
     def results(self) -> dict:
         torch.cuda.synchronize(self.m_epi.ctx.device)
