@@ -115,6 +115,23 @@ static void test_window_plans()
     CHECK(score_plan(RSLF_SCAN_REG, 104, 1080, 1920, 256, 256, 3, 0).groups == 1);
     CHECK(score_plan(RSLF_SCAN_REG, 104, 128, 1920, 256, 256, 3, 0).groups == 2);   // 3840 tiles: five rounds of 768 workgroups
     CHECK(score_plan(RSLF_SCAN_GENERIC, 0, 2, 64, 2, 256, 4, 0).groups == 1);
+    // the long rows of tests/test_gpu_score_instantiations.py: the "force_groups" hook holds at 70 and 133 hypotheses, for
+    // every kernel and window they run, so a wave's share is ceil(D / (4 * groups)) -- more than one run of kScoreRun
+    for (int n_rows : {1, 2})
+        for (int spad : {0, 16, 24, 104}) {
+            const int kind = spad ? RSLF_SCAN_REG : RSLF_SCAN_GENERIC, waves = spad == 104 ? 3 : spad == 16 ? 7 : 4;
+            CHECK(score_plan(kind, spad, n_rows, 300, 70, 256, waves, 1).groups == 1);
+            CHECK(score_plan(kind, spad, n_rows, 300, 133, 256, waves, 1).groups == 1);
+            CHECK(score_plan(kind, spad, n_rows, 300, 133, 256, waves, 2).groups == 2);
+            CHECK(score_plan(kind, spad, n_rows, 300, 70, 256, waves, 2).groups == 2);
+            CHECK(score_plan(kind, spad, n_rows, 300, 70, 256, waves, 0).groups == 8);     // left alone: waves of 3, no full run
+            CHECK(score_plan(kind, spad, n_rows, 300, 133, 256, waves, 0).groups == 16);   // ... of 3
+        }
+    CHECK((70 + 3) / 4 == 18 && 70 - 3 * 18 == kScoreRun);                // waves of 18, 18, 18 and one of exactly a run
+    CHECK((133 + 3) / 4 == 34 && 34 > 2 * kScoreRun && 133 - 3 * 34 == 31);
+    CHECK((133 + 7) / 8 == 17 && 17 == kScoreRun + 1 && 133 - 7 * 17 == 14);
+    // the table's own rows (300 pixels, 24 hypotheses) run in two groups: waves of 3
+    CHECK(score_plan(RSLF_SCAN_REG, 104, 1, 300, 24, 256, 3, 0).groups == 2);
     // a window too large for one grid goes in several launches
     {
         const ScanPlan p = score_plan(RSLF_SCAN_GENERIC, 0, 65535, 1 << 22, 512, 256, 4, 0);
