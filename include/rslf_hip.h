@@ -363,6 +363,58 @@ int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin
                                float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu, float* h_depth_raw_vu,
                                rslf_stats* stats);
 
+/* ---- sub-grid disparities in the pile step ------------------------------ */
+/* A scan's arg max moved off the hypothesis grid without a score row in memory.  Not in the reference; no existing entry
+ * changes.  d_idx_vu is the arg-max plane a scan produced, d_score_vu (nullable) its score plane (rslf_depth_epi_scan /
+ * rslf_depth_epi_pile with the same volume, ranges, dim_d, s_hat and parameters).  For every pixel with 0 <= idx < dim_d the
+ * hypotheses idx - 1 and idx + 1 are scored again with the scan's arithmetic -- the scan's own bits, whichever kernel ran
+ * it -- and, when no score plane is given, idx itself; with a, s1, c the three scores
+ *   d_disp_vu    the `disp` of rslf_peaks above: the vertex of the parabola through the three points, clamped to half a
+ *                step; the grid value at idx == 0, idx == dim_d - 1 and where den2 == 0.  It may be the scan's depth
+ *                plane: nothing is read from it
+ *   d_left_vu    nullable: a, written 0 at idx == 0
+ *   d_right_vu   nullable: c, written 0 at idx == dim_d - 1
+ * A pixel with idx < 0 (or >= dim_d) is left untouched in every output.  Costs 2 / dim_d of a generic scan (3 / dim_d
+ * without the score plane).  Arguments are checked as rslf_kernel_columns_pile checks them; one launch, queued on the
+ * context's stream, does not wait; it uses no context lists, so it is legal inside an open sweep. */
+int rslf_subgrid_refine(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                        float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
+                        const int32_t* d_idx_vu, const float* d_score_vu /*nullable*/, float* d_disp_vu,
+                        float* d_left_vu /*nullable*/, float* d_right_vu /*nullable*/);
+
+/* The entries above with a last argument `subgrid`.  0: exactly the namesake's launches and planes.  1: after the scan every
+ * pixel with idx >= 0 has its disparity replaced by rslf_subgrid_refine's disp (the arg-max and score planes are the
+ * caller's, or the context's own where NULL is passed), and the selective median, where the namesake has one, filters that
+ * plane; d_depth_raw_vu holds the refined, unfiltered plane.  C_e, the mask, C_d, rbar, idx and score are bit for bit what
+ * subgrid = 0 gives (rbar stays the grid winner's).  One device; the 2-D sweep and fine-to-coarse have no such mode. */
+int rslf_depth_epi_pile_sub(rslf_ctx* ctx, const rslf_volume* vol,
+                            const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
+                            int dim_d, int s_hat,
+                            float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                            float* d_rbar_vu, const rslf_params* p, uint8_t* d_mask_vu,
+                            int32_t* d_idx_vu, float* d_score_vu, float* d_depth_raw_vu,
+                            rslf_stats* stats, int subgrid);
+int rslf_depth_epi_scan_sub(rslf_ctx* ctx, const rslf_volume* vol,
+                            const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
+                            int dim_d, int s_hat,
+                            float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                            float* d_rbar_vu, const rslf_params* p, uint8_t* d_mask_vu,
+                            int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats, int subgrid);
+int rslf_depth1d_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                         const rslf_params* p,
+                         float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                         float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats, int subgrid);
+int rslf_depth1d_pile_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                              const rslf_params* p,
+                              float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                              float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu, float* d_depth_raw_vu,
+                              rslf_stats* stats, int subgrid);
+int rslf_depth1d_pile_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                   const rslf_params* p,
+                                   float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu,
+                                   float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu, float* h_depth_raw_vu,
+                                   rslf_stats* stats, int subgrid);
+
 /* ---- the hot path from host buffers, pipelined, over one or several devices --------------------------------- */
 /* Depth1DComputer_pile<T>'s constructor + run() + result Mats (include/rslf_depth_computation.hpp:425-565) in ONE
  * call on host buffers: h_epis[v] is EPI v (S rows of U pixels, C channels interleaved, rows row_stride_bytes apart,

@@ -412,12 +412,26 @@ public:
                       "rslf_multi_depth1d_pile_f32");
             return;
         }
-        check(rslf_depth1d_pile_run_host(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, m_s_hat, &p, m_edge_confidence_v_u.data(),
-                                         m_edge_confidence_mask_v_u.data(), m_disp_confidence_v_u.data(),
-                                         m_best_depth_v_u.data(), m_rbar_v_u.data(), m_depth_idx_v_u.data(),
-                                         m_score_v_u.data(), nullptr, &stats),
-              "rslf_depth1d_pile_run_host");
+        // (subgrid 0: exactly rslf_depth1d_pile_run_host's launches and planes)
+        check(rslf_depth1d_pile_run_host_sub(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, m_s_hat, &p, m_edge_confidence_v_u.data(),
+                                             m_edge_confidence_mask_v_u.data(), m_disp_confidence_v_u.data(),
+                                             m_best_depth_v_u.data(), m_rbar_v_u.data(), m_depth_idx_v_u.data(),
+                                             m_score_v_u.data(), nullptr, &stats, subgrid_ ? 1 : 0),
+              "rslf_depth1d_pile_run_host_sub");
     }
+
+    // Not in the reference: with the mode on, run() moves every disparity the scan assigns off the hypothesis grid -- the
+    // vertex of the parabola through the winner's score and its two neighbours', within half a grid step
+    // (rslf_subgrid_refine, rslf_hip.h) -- before the selective median filters the plane; m_best_depth_v_u and the pictures
+    // of the getters then hold refined values, every other member is unchanged.  Default off.  One context: an object built
+    // on a MultiContext throws with the mode on, as get_peaks does.
+    void set_subgrid(bool on)
+    {
+        if (on && multi_)
+            throw std::invalid_argument("set_subgrid: this object was built on a MultiContext: the sub-grid mode is built for one context");
+        subgrid_ = on;
+    }
+    bool get_subgrid() const { return subgrid_; }
 
     int get_s_hat() const { return m_s_hat; }
 
@@ -555,6 +569,7 @@ private:
     float m_dmin, m_dmax;
     int m_s_hat;
     float scale_used_;
+    bool subgrid_ = false;
     const Depth1DParameters m_parameters;
 };
 

@@ -50,6 +50,9 @@ SYMBOLS = [
     "rslf_depth_epi_scores", "rslf_depth_epi_scores_host",
     # ... and its peaks
     "rslf_score_peaks", "rslf_depth_epi_peaks", "rslf_depth_epi_peaks_host",
+    # sub-grid disparities in the pile step (K9)
+    "rslf_subgrid_refine", "rslf_depth_epi_pile_sub", "rslf_depth_epi_scan_sub", "rslf_depth1d_run_sub", "rslf_depth1d_pile_run_sub",
+    "rslf_depth1d_pile_run_host_sub",
 ]
 
 
@@ -206,6 +209,12 @@ def lib():
     L.rslf_depth1d_pile_run.argtypes = [vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp, vp, vp, vp,
                                         C.POINTER(RslfStats)]
     L.rslf_depth1d_pile_run_host.argtypes = L.rslf_depth1d_pile_run.argtypes
+    L.rslf_subgrid_refine.argtypes = [vp, vp, vp, vp, cf, cf, ci, ci, C.POINTER(RslfParams), vp, vp, vp, vp, vp]
+    L.rslf_depth_epi_pile_sub.argtypes = L.rslf_depth_epi_pile.argtypes + [ci]
+    L.rslf_depth_epi_scan_sub.argtypes = L.rslf_depth_epi_scan.argtypes + [ci]
+    L.rslf_depth1d_run_sub.argtypes = L.rslf_depth1d_run.argtypes + [ci]
+    L.rslf_depth1d_pile_run_sub.argtypes = L.rslf_depth1d_pile_run.argtypes + [ci]
+    L.rslf_depth1d_pile_run_host_sub.argtypes = L.rslf_depth1d_pile_run.argtypes + [ci]
     L.rslf_last_scan_kernel_ms.argtypes = [vp, C.POINTER(cf)]
     L.rslf_scan_time_total_ms.argtypes = [vp, C.POINTER(cf), C.POINTER(ci)]
     L.rslf_last_scan_row_exact.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]

@@ -34,6 +34,31 @@ struct PeakResult {
     float runner_score;   // s[i2], 0 without one
 };
 
+// The sub-grid disparity of a winner i1 whose score is s1 and whose neighbours scored a (i1 - 1) and c (i1 + 1): the grid value
+// moved by the vertex of the parabola through the three points.  Stated once: PeakScan::finish below has the three scores
+// from a whole row, k9_subgrid_refine (k9_subgrid.hpp) from re-scoring the two neighbours.  a and c are not read at the ends
+// of the grid.  lo, hi: the pixel's disparity range; the grid value is the scan's hypothesis() (k2_scan.hpp).
+RSLF_PEAK_FN float peak_disp(int i1, int D, float lo, float hi, float a, float s1, float c)
+{
+    const float range = hi - lo, denom = (float)(D - 1);
+    const float num_d = (float)i1 * range;
+    const float quo = num_d / denom;
+    const float Dd = lo + quo;
+    float delta = 0.0f;
+    if (i1 > 0 && i1 < D - 1) {
+        const float num = a - c;
+        const float t = a + c;
+        const float bb = s1 + s1;
+        const float den = t - bb;
+        const float den2 = den + den;
+        delta = den2 == 0.0f ? 0.0f : num / den2;
+        delta = fminf(fmaxf(delta, -0.5f), 0.5f);
+    }
+    const float step = range / denom;
+    const float move = delta * step;
+    return Dd + move;
+}
+
 struct PeakScan {
     float before, last;   // s[d-2], s[d-1] once s[d-1] has been offered
     int i1, i2;
@@ -74,30 +99,14 @@ struct PeakScan {
         before = last;
         last = s;
     }
-    // After all D >= 1 values.  lo, hi: the pixel's disparity range; the grid value is the scan's hypothesis() (k2_scan.hpp).
+    // After all D >= 1 values.  lo, hi: the pixel's disparity range (peak_disp).
     RSLF_PEAK_FN PeakResult finish(int D, float lo, float hi)
     {
         judge(D - 1, 0.0f, false);
         PeakResult r;
         r.idx = i1, r.score = s1;
         r.runner_idx = i2, r.runner_score = i2 < 0 ? 0.0f : s2;
-        const float range = hi - lo, denom = (float)(D - 1);
-        const float num_d = (float)i1 * range;
-        const float quo = num_d / denom;
-        const float Dd = lo + quo;
-        float delta = 0.0f;
-        if (i1 > 0 && i1 < D - 1) {
-            const float num = a - c;
-            const float t = a + c;
-            const float bb = s1 + s1;
-            const float den = t - bb;
-            const float den2 = den + den;
-            delta = den2 == 0.0f ? 0.0f : num / den2;
-            delta = fminf(fmaxf(delta, -0.5f), 0.5f);
-        }
-        const float step = range / denom;
-        const float move = delta * step;
-        r.disp = Dd + move;
+        r.disp = peak_disp(i1, D, lo, hi, a, s1, c);
         return r;
     }
 };

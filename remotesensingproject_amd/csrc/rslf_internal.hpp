@@ -7,6 +7,7 @@
 //   rslf_chip_a/b/c.hip   the on-chip scan kernel's instantiations, one per rung of its ladder (launched by rslf_pile.hip)
 //   rslf_scores.hip       the scan's score matrix as an output: rslf_depth_epi_scores and its host form (k2_scores.hpp)
 //   rslf_peaks.hip        the score rows' consumer: winner, sub-grid disparity and runner-up per pixel (k8_peaks.hpp)
+//   rslf_subgrid.hip      the arg max moved off the grid: the winner's two neighbours re-scored, no row in memory (k9_subgrid.hpp)
 //   rslf_sweep.hip        the 2-D sweep and its propagation (K4), Depth2DComputer::run
 //   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the one native level loop
 //   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters
@@ -213,6 +214,8 @@ struct Scratch {
     DeviceBuf scan_partial; // rslf::Partial [tile][group][64]: records of grouped scan launches
     DeviceBuf scan_ticket;  // int [tile] of the same launches: which group merges the tile (zero between launches)
     DeviceBuf max_partial;  // float [kMaxPartials]: block maxima of rslf_device_max_f32
+    DeviceBuf sub_idx;      // int32 [V*U]: a sub-grid pile step's arg-max plane when the caller passes none (subgrid_planes)
+    DeviceBuf sub_score;    // float [V*U]: ... and its score plane
     DeviceBuf row_exact;    // the scan's row-exact table (k2_scan.hpp, ScanArgs::rx_*): [D][slots] offsets, [D][slots] weight pairs, [D] floats, [D] ints; RowExactKey says of what
     // 2-D sweep
     DeviceBuf winner;       // int [S][V][U]: the claims (0x7F7F7F7F between visits)
@@ -425,6 +428,8 @@ int depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu
                    int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu,
                    const rslf_params* p, uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats,
                    const ScanInputs& in);
+// The arguments every scan of the hypothesis grid takes (K2, the K columns, the sub-grid refinement)
+int check_scan_args(const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat, const rslf_params* p);
 void fill_stats(rslf_ctx* ctx, unsigned long long tot, int dim_d, rslf_stats* stats);
 int read_stats(rslf_ctx* ctx, int dim_d, rslf_stats* stats);
 int scan_presize(rslf_ctx* ctx, int S, int U, int C, int dim_d, const rslf_params* p, const int* rows, int n_rows);
@@ -441,6 +446,13 @@ int score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, co
                int* spad_out);
 int read_pixel_total(rslf_ctx* ctx, unsigned long long* tot);
 void score_stats(unsigned long long pixels, int dim_d, int kind, int spad, rslf_stats* stats);
+
+// rslf_subgrid.hip
+// k9_subgrid_refine over a volume's [V][U] planes, arguments already checked (check_scan_args): one launch queued on the
+// context's stream.  d_score_vu, d_left_vu, d_right_vu nullable; d_disp_vu may be the scan's depth plane.
+int subgrid_refine(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
+                   int dim_d, int s_hat, const rslf_params* p, const int32_t* d_idx_vu, const float* d_score_vu, float* d_disp_vu,
+                   float* d_left_vu, float* d_right_vu);
 
 // rslf_sweep.hip
 // Depth2DComputer::run (dc.hpp:748-805) on device planes; d_dmin_svu / d_dmax_svu: per-pixel ranges (a fine-to-coarse

@@ -261,9 +261,9 @@ ScanInputs rslf::scan_defaults(const rslf_ctx* ctx)
     return in;
 }
 
-// The arguments every scan of the hypothesis grid takes (K2, the K columns)
-static int check_scan_args(const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat,
-                           const rslf_params* p)
+// The arguments every scan of the hypothesis grid takes (K2, the K columns, the sub-grid refinement)
+int rslf::check_scan_args(const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat,
+                          const rslf_params* p)
 {
     int rc = check_params(p);
     if (rc)
@@ -561,6 +561,63 @@ extern "C" int rslf_depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const 
 }
 RSLF_API_CATCH
 
+// The sub-grid mode of the *_sub entries (include/rslf_hip.h).  The refinement reads the scan's arg-max and score planes: the
+// caller's, or the context's own where the caller passes none.
+static int subgrid_planes(rslf_ctx* ctx, const rslf_volume* vol, int subgrid, int32_t** idx, float** score)
+{
+    if (subgrid != 0 && subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
+    if (!subgrid)
+        return RSLF_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = (size_t)vol->V * vol->U;
+    Scratch& sc = ctx->scratch;
+    if (!*idx) {
+        HIP_TRY(hip_err(sc.sub_idx.reserve(n * sizeof(int32_t))));
+        *idx = sc.sub_idx.as<int32_t>();
+    }
+    if (!*score) {
+        HIP_TRY(hip_err(sc.sub_score.reserve(n * sizeof(float))));
+        *score = sc.sub_score.as<float>();
+    }
+    return RSLF_OK;
+}
+
+// depth_epi_scan, then with subgrid = 1 the refinement (k9_subgrid.hpp) of every pixel that received a disparity, in place on
+// the depth plane.  subgrid = 0: depth_epi_scan's launches and nothing else.
+static int depth_epi_scan_refined(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin,
+                                  float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu,
+                                  float* d_depth_vu, float* d_rbar_vu, const rslf_params* p, uint8_t* d_mask_vu, int32_t* d_idx_vu,
+                                  float* d_score_vu, rslf_stats* stats, const ScanInputs& in, int subgrid)
+{
+    if (!ctx || !vol)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    int rc = subgrid_planes(ctx, vol, subgrid, &d_idx_vu, &d_score_vu);
+    if (rc)
+        return rc;
+    rc = depth_epi_scan(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu, d_rbar_vu,
+                        p, d_mask_vu, d_idx_vu, d_score_vu, subgrid ? nullptr : stats, in);
+    if (rc || !subgrid)
+        return rc;
+    rc = subgrid_refine(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, p, d_idx_vu, d_score_vu, d_depth_vu, nullptr, nullptr);
+    if (rc)
+        return rc;
+    return stats ? read_stats(ctx, dim_d, stats) : RSLF_OK;
+}
+
+extern "C" int rslf_depth_epi_scan_sub(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                                       float dmin, float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu,
+                                       float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu, const rslf_params* p,
+                                       uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats,
+                                       int subgrid) RSLF_API_TRY
+{
+    if (!ctx)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    return depth_epi_scan_refined(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,
+                                  d_rbar_vu, p, d_mask_vu, d_idx_vu, d_score_vu, stats, scan_defaults(ctx), subgrid);
+}
+RSLF_API_CATCH
+
 extern "C" int rslf_kernel_columns_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
                                         float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
                                         const int32_t* d_idx_vu, float* d_K_vsu) RSLF_API_TRY
@@ -594,7 +651,7 @@ RSLF_API_CATCH
 static int depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin,
                           float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
                           float* d_rbar_vu, const rslf_params* p, uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu,
-                          float* d_depth_raw_vu, rslf_stats* stats, const ScanInputs& in)
+                          float* d_depth_raw_vu, rslf_stats* stats, const ScanInputs& in, int subgrid = 0)
 {
     if (!ctx || !vol || !d_depth_vu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -614,8 +671,9 @@ static int depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const float* d_
         HIP_TRY(hipMemcpyAsync(raw, d_depth_vu, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     else if (d_depth_raw_vu)
         HIP_TRY(hipMemsetAsync(d_depth_raw_vu, 0, n * sizeof(float), st));
-    rc = depth_epi_scan(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, raw, d_rbar_vu,
-                        p, d_mask_vu, d_idx_vu, d_score_vu, nullptr, in);
+    // (subgrid = 1: every disparity the scan wrote is then moved off the grid, in place -- the median filters refined values)
+    rc = depth_epi_scan_refined(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, raw, d_rbar_vu,
+                                p, d_mask_vu, d_idx_vu, d_score_vu, nullptr, in, subgrid);
     if (rc)
         return rc;
     // ... then core.hpp:881-892: median over the EDGE mask, result replaces best_depth -- written straight into the
@@ -639,13 +697,29 @@ extern "C" int rslf_depth_epi_pile(rslf_ctx* ctx, const rslf_volume* vol, const 
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
-                                     const rslf_params* p, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu,
-                                     float* d_depth_vu, float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu,
-                                     float* d_depth_raw_vu, rslf_stats* stats) RSLF_API_TRY
+extern "C" int rslf_depth_epi_pile_sub(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
+                                       float dmin, float dmax, int dim_d, int s_hat, float* d_Ce_vu, uint8_t* d_Ce_mask_vu,
+                                       float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu, const rslf_params* p,
+                                       uint8_t* d_mask_vu, int32_t* d_idx_vu, float* d_score_vu, float* d_depth_raw_vu,
+                                       rslf_stats* stats, int subgrid) RSLF_API_TRY
+{
+    if (!ctx)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    return depth_epi_pile(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,
+                          d_rbar_vu, p, d_mask_vu, d_idx_vu, d_score_vu, d_depth_raw_vu, stats, scan_defaults(ctx), subgrid);
+}
+RSLF_API_CATCH
+
+// rslf_depth1d_pile_run and its _sub form
+static int depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                            const rslf_params* p, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                            float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu, float* d_depth_raw_vu, rslf_stats* stats,
+                            int subgrid)
 {
     if (!ctx || !vol || !d_Ce_vu || !d_Ce_mask_vu || !d_Cd_vu || !d_depth_vu || !d_rbar_vu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (subgrid != 0 && subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     HIP_TRY(hipSetDevice(ctx->device));
     s_hat = plan::resolve_s_hat(s_hat, vol->S);
     const size_t n = (size_t)vol->V * vol->U;
@@ -688,13 +762,33 @@ extern "C" int rslf_depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, floa
             return rc;
     }
     return depth_epi_pile(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,   // dc.hpp:547
-                          d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, d_depth_raw_vu, stats, in);
+                          d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, d_depth_raw_vu, stats, in, subgrid);
+}
+
+extern "C" int rslf_depth1d_pile_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                     const rslf_params* p, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu,
+                                     float* d_depth_vu, float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu,
+                                     float* d_depth_raw_vu, rslf_stats* stats) RSLF_API_TRY
+{
+    return depth1d_pile_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu, d_rbar_vu, d_idx_vu,
+                            d_score_vu, d_depth_raw_vu, stats, 0);
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_depth1d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
-                                const rslf_params* p, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
-                                float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats) RSLF_API_TRY
+extern "C" int rslf_depth1d_pile_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                         const rslf_params* p, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu,
+                                         float* d_depth_vu, float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu,
+                                         float* d_depth_raw_vu, rslf_stats* stats, int subgrid) RSLF_API_TRY
+{
+    return depth1d_pile_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu, d_rbar_vu, d_idx_vu,
+                            d_score_vu, d_depth_raw_vu, stats, subgrid);
+}
+RSLF_API_CATCH
+
+// rslf_depth1d_run and its _sub form
+static int depth1d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
+                       float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu, float* d_rbar_vu, int32_t* d_idx_vu,
+                       float* d_score_vu, rslf_stats* stats, int subgrid)
 {
     if (!ctx || !vol || !d_Ce_vu || !d_Ce_mask_vu || !d_Cd_vu || !d_depth_vu || !d_rbar_vu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -710,15 +804,34 @@ extern "C" int rslf_depth1d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmi
     int rc = rslf_edge_confidence_pile(ctx, vol, s_hat, p, d_Ce_vu, d_Ce_mask_vu);   // dc.hpp:347
     if (rc)
         return rc;
-    return depth_epi_scan(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,   // dc.hpp:356
-                          d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, stats, scan_defaults(ctx));
+    return depth_epi_scan_refined(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, s_hat, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu,   // dc.hpp:356
+                                  d_rbar_vu, p, nullptr, d_idx_vu, d_score_vu, stats, scan_defaults(ctx), subgrid);
+}
+
+extern "C" int rslf_depth1d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                const rslf_params* p, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                                float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats) RSLF_API_TRY
+{
+    return depth1d_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu, d_rbar_vu, d_idx_vu, d_score_vu,
+                       stats, 0);
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
-                                          const rslf_params* p, float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu,
-                                          float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu,
-                                          float* h_depth_raw_vu, rslf_stats* stats) RSLF_API_TRY
+extern "C" int rslf_depth1d_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                    const rslf_params* p, float* d_Ce_vu, uint8_t* d_Ce_mask_vu, float* d_Cd_vu, float* d_depth_vu,
+                                    float* d_rbar_vu, int32_t* d_idx_vu, float* d_score_vu, rslf_stats* stats,
+                                    int subgrid) RSLF_API_TRY
+{
+    return depth1d_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, d_Ce_vu, d_Ce_mask_vu, d_Cd_vu, d_depth_vu, d_rbar_vu, d_idx_vu, d_score_vu,
+                       stats, subgrid);
+}
+RSLF_API_CATCH
+
+// rslf_depth1d_pile_run_host and its _sub form
+static int depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                 const rslf_params* p, float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu, float* h_depth_vu,
+                                 float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu, float* h_depth_raw_vu, rslf_stats* stats,
+                                 int subgrid)
 {
     if (!ctx || !vol)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -733,8 +846,8 @@ extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol,
     plan::PilePlanes out;
     out.Ce = h_Ce_vu, out.mask = h_Ce_mask_vu, out.Cd = h_Cd_vu, out.depth = h_depth_vu, out.rbar = h_rbar_vu, out.idx = h_idx_vu;
     out.score = h_score_vu, out.raw = h_depth_raw_vu;
-    int rc = rslf_depth1d_pile_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, q.Ce, q.mask, q.Cd, q.depth, q.rbar, q.idx, q.score, q.raw,
-                                   nullptr);
+    int rc = depth1d_pile_run(ctx, vol, dmin, dmax, dim_d, s_hat, p, q.Ce, q.mask, q.Cd, q.depth, q.rbar, q.idx, q.score, q.raw, nullptr,
+                              subgrid);
     hipStream_t st = ctx->stream;
     if (rc == RSLF_OK) {
         hipError_t ce = (hipError_t)plan::for_each_plane(out, q, vol->C, [&](void* h, const void* d, size_t bpp) {
@@ -752,6 +865,25 @@ extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol,
             fill_stats(ctx, tot, dim_d, stats);
     }
     return rc;
+}
+
+extern "C" int rslf_depth1d_pile_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                          const rslf_params* p, float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu,
+                                          float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu,
+                                          float* h_depth_raw_vu, rslf_stats* stats) RSLF_API_TRY
+{
+    return depth1d_pile_run_host(ctx, vol, dmin, dmax, dim_d, s_hat, p, h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu,
+                                 h_score_vu, h_depth_raw_vu, stats, 0);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_depth1d_pile_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, int s_hat,
+                                              const rslf_params* p, float* h_Ce_vu, uint8_t* h_Ce_mask_vu, float* h_Cd_vu,
+                                              float* h_depth_vu, float* h_rbar_vu, int32_t* h_idx_vu, float* h_score_vu,
+                                              float* h_depth_raw_vu, rslf_stats* stats, int subgrid) RSLF_API_TRY
+{
+    return depth1d_pile_run_host(ctx, vol, dmin, dmax, dim_d, s_hat, p, h_Ce_vu, h_Ce_mask_vu, h_Cd_vu, h_depth_vu, h_rbar_vu, h_idx_vu,
+                                 h_score_vu, h_depth_raw_vu, stats, subgrid);
 }
 RSLF_API_CATCH
 

@@ -98,6 +98,14 @@ def require_no_line_confidence(parameters, who: str) -> None:
                          % (who, int(parameters.par_line_confidence_mode)))
 
 
+def require_no_subgrid(subgrid, who: str) -> None:
+    """The sub-grid mode is built for the one-device pile step alone (DESIGN.md 3 "Sub-grid pile"): every multi-device form
+    refuses it instead of ignoring it."""
+    if subgrid:
+        raise ValueError("%s: subgrid=True is not built here (one device: Depth1DComputer_pile, Depth1DComputer and the "
+                         "compute_1D_depth_epi functions)" % who)
+
+
 class Context:
     """rslf_ctx bound to one GPU; launches go to torch's current stream on it."""
 
@@ -489,24 +497,30 @@ def compute_1D_depth_epi_pile(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int,
                               a_rbar_v_u: torch.Tensor, a_parameters: Depth1DParameters | None = None,
                               a_mask_v_u: torch.Tensor | None = None, *, idx_v_u: torch.Tensor | None = None,
                               score_v_u: torch.Tensor | None = None, depth_raw_v_u: torch.Tensor | None = None,
-                              want_stats: bool = False, a_K_r_m_rbar_v_s_u: torch.Tensor | None = None) -> RslfStats | None:
+                              want_stats: bool = False, a_K_r_m_rbar_v_s_u: torch.Tensor | None = None,
+                              subgrid: bool = False) -> RslfStats | None:
     """core.hpp:293-310.  a_dmin_v_u / a_dmax_v_u are [V,U] f32 CUDA tensors or
     Python floats (the constant planes of dc.hpp:486-487).  All planes are
     updated in place; a_best_depth_v_u ends as the selective median (core.hpp:892).
     a_K_r_m_rbar_v_s_u ([V,S,U] f32, the reference's optional last argument, core.hpp:309): receives
-    K(r - rbar)[:, d*] for every pixel that got a disparity (core.hpp:647-651)."""
+    K(r - rbar)[:, d*] for every pixel that got a disparity (core.hpp:647-651).
+    subgrid (not in the reference): every disparity the scan writes is moved off the hypothesis grid (subgrid_refine)
+    before the median filters it; depth_raw_v_u then holds the refined, unfiltered plane."""
     p = (a_parameters or Depth1DParameters()).to_c()
     planes = isinstance(a_dmin_v_u, torch.Tensor)
     st = RslfStats() if want_stats else None
     vol.ctx.use_current_stream()
     if a_K_r_m_rbar_v_s_u is not None and idx_v_u is None:
         idx_v_u = torch.empty((vol.V, vol.U), dtype=torch.int32, device=a_best_depth_v_u.device)
-    check(_lib.lib().rslf_depth_epi_pile(
-        vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
-        0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), a_dim_d, a_s_hat,
-        _ptr(a_edge_confidence_v_u), _ptr(a_edge_confidence_mask_v_u), _ptr(a_disp_confidence_v_u),
-        _ptr(a_best_depth_v_u), _ptr(a_rbar_v_u), C.byref(p), _ptr(a_mask_v_u), _ptr(idx_v_u), _ptr(score_v_u),
-        _ptr(depth_raw_v_u), C.byref(st) if st is not None else None), "rslf_depth_epi_pile")
+    args = (vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
+            0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), a_dim_d, a_s_hat,
+            _ptr(a_edge_confidence_v_u), _ptr(a_edge_confidence_mask_v_u), _ptr(a_disp_confidence_v_u),
+            _ptr(a_best_depth_v_u), _ptr(a_rbar_v_u), C.byref(p), _ptr(a_mask_v_u), _ptr(idx_v_u), _ptr(score_v_u),
+            _ptr(depth_raw_v_u), C.byref(st) if st is not None else None)
+    if subgrid:
+        check(_lib.lib().rslf_depth_epi_pile_sub(*args, 1), "rslf_depth_epi_pile_sub")
+    else:
+        check(_lib.lib().rslf_depth_epi_pile(*args), "rslf_depth_epi_pile")
     if a_K_r_m_rbar_v_s_u is not None:
         check(_lib.lib().rslf_kernel_columns_pile(
             vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
@@ -622,6 +636,45 @@ def compute_1D_depth_peaks(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int, a_
     return (out, st) if want_stats else out
 
 
+class SubGrid(NamedTuple):
+    """What subgrid_refine writes, [V, U] f32 each: the sub-grid disparity (Peaks.disp, from three scores instead of a row)
+    and the scores of the winner's two neighbours (0 at the end of the grid that has none)."""
+    disp: torch.Tensor
+    left: Optional[torch.Tensor]
+    right: Optional[torch.Tensor]
+
+
+def subgrid_refine(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int, a_s_hat: int, idx_v_u: torch.Tensor,
+                   score_v_u: torch.Tensor | None = None, parameters: Depth1DParameters | None = None, *,
+                   disp: torch.Tensor | None = None, left: torch.Tensor | None = None, right: torch.Tensor | None = None,
+                   neighbours: bool = True) -> SubGrid:
+    """A scan's arg max moved off the hypothesis grid: for every pixel with idx >= 0 the hypotheses idx - 1 and idx + 1
+    are scored again (and idx itself without score_v_u) and the parabola through the three scores gives `disp`, within
+    half a grid step of the grid value.  idx_v_u / score_v_u: the planes a scan of the same volume, range, a_dim_d,
+    a_s_hat and parameters wrote.  Pixels with idx < 0 keep what the output planes held (zeros when made here); `disp`
+    may be the scan's depth plane.  neighbours=False: no left / right planes unless given.  No score row is made."""
+    p = (parameters or Depth1DParameters()).to_c()
+    planes = isinstance(a_dmin_v_u, torch.Tensor)
+    shape = (vol.V, vol.U)
+    if tuple(idx_v_u.shape) != shape or idx_v_u.dtype != torch.int32 or not idx_v_u.is_cuda or not idx_v_u.is_contiguous():
+        raise ValueError("idx_v_u must be a contiguous int32 CUDA tensor of shape %s" % (shape,))
+    if disp is None:
+        disp = torch.zeros(shape, dtype=torch.float32, device=idx_v_u.device)
+    if neighbours and left is None:
+        left = torch.zeros(shape, dtype=torch.float32, device=idx_v_u.device)
+    if neighbours and right is None:
+        right = torch.zeros(shape, dtype=torch.float32, device=idx_v_u.device)
+    for name, t in (("score_v_u", score_v_u), ("disp", disp), ("left", left), ("right", right)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, shape))
+    vol.ctx.use_current_stream()
+    check(_lib.lib().rslf_subgrid_refine(
+        vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
+        0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), int(a_dim_d), int(a_s_hat), C.byref(p),
+        _ptr(idx_v_u), _ptr(score_v_u), _ptr(disp), _ptr(left), _ptr(right)), "rslf_subgrid_refine")
+    return SubGrid(disp, left, right)
+
+
 def selective_median_filter(a_src: torch.Tensor, vol: Volume, a_s_hat: int, a_size: int, a_mask_v_u: torch.Tensor,
                             a_epsilon: float) -> torch.Tensor:
     """core.hpp:366-375; returns a_dst."""
@@ -642,8 +695,11 @@ class Depth1DComputer_pile:
     is already resident.  After run(), the result members hold CUDA tensors."""
 
     def __init__(self, epis, dmin: float, dmax: float, dim_d: int, s_hat: int = -1, epi_scale_factor: float = -1.0,
-                 parameters: Depth1DParameters | None = None, ctx: Context | None = None):
+                 parameters: Depth1DParameters | None = None, ctx: Context | None = None, subgrid: bool = False):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        # not in the reference: the scan's disparities are moved off the hypothesis grid before the median (subgrid_refine);
+        # m_depth_raw_v_u is then the refined plane, and the getters show refined values
+        self.m_subgrid = bool(subgrid)
         if isinstance(epis, Volume):
             self.m_epis = epis
         elif isinstance(epis, (list, tuple)):
@@ -677,11 +733,14 @@ class Depth1DComputer_pile:
         p = self.m_parameters.to_c()
         st = RslfStats() if want_stats else None
         vol.ctx.use_current_stream()
-        check(_lib.lib().rslf_depth1d_pile_run(
-            vol.ctx._h, vol._h, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, C.byref(p),
-            _ptr(self.m_edge_confidence_v_u), _ptr(self.m_edge_confidence_mask_v_u), _ptr(self.m_disp_confidence_v_u),
-            _ptr(self.m_best_depth_v_u), _ptr(self.m_rbar_v_u), _ptr(self.m_depth_idx_v_u), _ptr(self.m_score_v_u),
-            _ptr(self.m_depth_raw_v_u), C.byref(st) if st is not None else None), "rslf_depth1d_pile_run")
+        args = (vol.ctx._h, vol._h, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, C.byref(p),
+                _ptr(self.m_edge_confidence_v_u), _ptr(self.m_edge_confidence_mask_v_u), _ptr(self.m_disp_confidence_v_u),
+                _ptr(self.m_best_depth_v_u), _ptr(self.m_rbar_v_u), _ptr(self.m_depth_idx_v_u), _ptr(self.m_score_v_u),
+                _ptr(self.m_depth_raw_v_u), C.byref(st) if st is not None else None)
+        if self.m_subgrid:
+            check(_lib.lib().rslf_depth1d_pile_run_sub(*args, 1), "rslf_depth1d_pile_run_sub")
+        else:
+            check(_lib.lib().rslf_depth1d_pile_run(*args), "rslf_depth1d_pile_run")
         self.stats = st
         self._ran = True
 
@@ -820,8 +879,9 @@ class MultiDevice:
         return [[int(_lib.lib().rslf_multi_peer_access(self._h, i, k)) for k in range(n)] for i in range(n)]
 
     def depth1d_pile(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, s_hat: int = -1,
-                     epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None) -> dict:
+                     epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None, subgrid: bool = False) -> dict:
         """epis: the reference's Vec<Mat> -- V arrays [S,U] or [S,U,3], all uint8, all uint16 or all float32."""
+        require_no_subgrid(subgrid, "MultiDevice.depth1d_pile")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((V, U), np.float32), edge_mask=np.empty((V, U), np.uint8),
                    disp_confidence=np.empty((V, U), np.float32), depth=np.empty((V, U), np.float32),
@@ -894,9 +954,11 @@ class MultiDevice:
         return out_map, out_valid, int(nl.value)
 
     def depth1d_pile_device_out(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, out_device: int = 0,
-                                s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None) -> dict:
+                                s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None,
+                                subgrid: bool = False) -> dict:
         """The same with the result planes left on `out_device` as CUDA tensors (float32 EPIs): every worker copies its
         rows there with a peer copy (rslf_multi_depth1d_pile_f32_dev)."""
+        require_no_subgrid(subgrid, "MultiDevice.depth1d_pile_device_out")
         keep, ptrs, _, V, S, U, C_, stride = host_epis(epis, np.float32, stride=True)
         dev = torch.device("cuda", out_device)
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
@@ -1121,18 +1183,22 @@ def compute_1D_depth_epi(vol: Volume, a_dmin_v_u, a_dmax_v_u, a_dim_d: int, a_s_
                          a_disp_confidence_v_u: torch.Tensor, a_best_depth_v_u: torch.Tensor, a_rbar_v_u: torch.Tensor,
                          a_parameters: Depth1DParameters | None = None, a_mask_v_u: torch.Tensor | None = None, *,
                          idx_v_u: torch.Tensor | None = None, score_v_u: torch.Tensor | None = None,
-                         want_stats: bool = False) -> RslfStats | None:
-    """core.hpp:251-267 for every EPI of the volume: the scan alone, no selective median."""
+                         want_stats: bool = False, subgrid: bool = False) -> RslfStats | None:
+    """core.hpp:251-267 for every EPI of the volume: the scan alone, no selective median.  subgrid (not in the reference):
+    every disparity the scan writes is moved off the hypothesis grid (subgrid_refine)."""
     p = (a_parameters or Depth1DParameters()).to_c()
     planes = isinstance(a_dmin_v_u, torch.Tensor)
     st = RslfStats() if want_stats else None
     vol.ctx.use_current_stream()
-    check(_lib.lib().rslf_depth_epi_scan(
-        vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
-        0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), a_dim_d, a_s_hat,
-        _ptr(a_edge_confidence_v_u), _ptr(a_edge_confidence_mask_v_u), _ptr(a_disp_confidence_v_u),
-        _ptr(a_best_depth_v_u), _ptr(a_rbar_v_u), C.byref(p), _ptr(a_mask_v_u), _ptr(idx_v_u), _ptr(score_v_u),
-        C.byref(st) if st is not None else None), "rslf_depth_epi_scan")
+    args = (vol.ctx._h, vol._h, _ptr(a_dmin_v_u if planes else None), _ptr(a_dmax_v_u if planes else None),
+            0.0 if planes else float(a_dmin_v_u), 0.0 if planes else float(a_dmax_v_u), a_dim_d, a_s_hat,
+            _ptr(a_edge_confidence_v_u), _ptr(a_edge_confidence_mask_v_u), _ptr(a_disp_confidence_v_u),
+            _ptr(a_best_depth_v_u), _ptr(a_rbar_v_u), C.byref(p), _ptr(a_mask_v_u), _ptr(idx_v_u), _ptr(score_v_u),
+            C.byref(st) if st is not None else None)
+    if subgrid:
+        check(_lib.lib().rslf_depth_epi_scan_sub(*args, 1), "rslf_depth_epi_scan_sub")
+    else:
+        check(_lib.lib().rslf_depth_epi_scan(*args), "rslf_depth_epi_scan")
     return st
 
 
@@ -1141,8 +1207,9 @@ class Depth1DComputer:
     confidence + scan, no median.  Results are [U] CUDA tensors."""
 
     def __init__(self, epi, dmin: float, dmax: float, dim_d: int, s_hat: int = -1, epi_scale_factor: float = -1.0,
-                 parameters: Depth1DParameters | None = None, ctx: Context | None = None):
+                 parameters: Depth1DParameters | None = None, ctx: Context | None = None, subgrid: bool = False):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        self.m_subgrid = bool(subgrid)   # not in the reference: disparities moved off the hypothesis grid (subgrid_refine)
         self.m_epi = Volume.from_epis([np.asarray(epi)], epi_scale_factor, ctx)
         vol = self.m_epi
         self.m_dim_d, self.m_dmin, self.m_dmax = int(dim_d), float(dmin), float(dmax)
@@ -1164,11 +1231,13 @@ class Depth1DComputer:
         p = self.m_parameters.to_c()
         st = RslfStats()
         vol.ctx.use_current_stream()
-        check(_lib.lib().rslf_depth1d_run(
-            vol.ctx._h, vol._h, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, C.byref(p),
-            _ptr(self.m_edge_confidence_u), _ptr(self.m_edge_confidence_mask_u), _ptr(self.m_disp_confidence_u),
-            _ptr(self.m_best_depth_u), _ptr(self.m_rbar_u), _ptr(self.m_depth_idx_u), _ptr(self.m_score_u), C.byref(st)),
-            "rslf_depth1d_run")
+        args = (vol.ctx._h, vol._h, self.m_dmin, self.m_dmax, self.m_dim_d, self.m_s_hat, C.byref(p),
+                _ptr(self.m_edge_confidence_u), _ptr(self.m_edge_confidence_mask_u), _ptr(self.m_disp_confidence_u),
+                _ptr(self.m_best_depth_u), _ptr(self.m_rbar_u), _ptr(self.m_depth_idx_u), _ptr(self.m_score_u), C.byref(st))
+        if self.m_subgrid:
+            check(_lib.lib().rslf_depth1d_run_sub(*args, 1), "rslf_depth1d_run_sub")
+        else:
+            check(_lib.lib().rslf_depth1d_run(*args), "rslf_depth1d_run")
         self.stats = st
         self._ran = True
 

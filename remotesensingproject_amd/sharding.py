@@ -227,9 +227,14 @@ def gather_planes(planes: Dict[str, torch.Tensor], shard: Shard, U: int, C: int,
 
 
 def run_sharded(local_compute: Callable[[Shard], Dict[str, torch.Tensor]], V: int, U: int, C: int,
-                median_filter_size: int = 5, group=None, opening_size: int = 1) -> Optional[Dict[str, torch.Tensor]]:
+                median_filter_size: int = 5, group=None, opening_size: int = 1,
+                subgrid: bool = False) -> Optional[Dict[str, torch.Tensor]]:
     """local_compute(shard) -> output planes for rows [shard.lo, shard.hi) (it must run the
-    full K1+K2+K3 path on exactly those rows); returns the stitched planes on rank 0."""
+    full K1+K2+K3 path on exactly those rows); returns the stitched planes on rank 0.
+    subgrid: refused -- the sub-grid pile step is a one-device mode (depth.require_no_subgrid)."""
+    if subgrid:
+        from . import depth as rs
+        rs.require_no_subgrid(subgrid, "sharding.run_sharded")
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     shard = make_shard(V, rank, world, median_filter_size, opening_size)
