@@ -144,6 +144,8 @@ int rslf_ctx_synchronize(rslf_ctx* ctx);
  *   "scalar_taps"    1 (default) with "tap_table" on, hypotheses whose lerp taps and weights are the same for every pixel of the row
  *                    take them as scalars from a table made once per hypothesis grid and kept by the context | 0 off
  *   "claim_skip"     1 (default) the 2-D sweep's claims skip views with nothing left to paint within reach | 0 off
+ *   "subgrid_list"   1 (default) a 2-D sweep in the sub-grid mode (rslf_sweep_subgrid) refines a visit whose scan took the packed
+ *                    list over that list | 0 every visit refines over the whole plane (k9_subgrid_refine), the same bits
  *   "stream_share"   63-pixel tiles sharing taps between lanes in the streaming kernel: 1 (default) where the samples gathered
  *                    again on every pass are at least a quarter of the views | 0 never | 2 always
  *   "stream_groups"  0 automatic | hypothesis groups per tile of the streaming kernel's dense launches
@@ -386,7 +388,8 @@ int rslf_subgrid_refine(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dm
  * pixel with idx >= 0 has its disparity replaced by rslf_subgrid_refine's disp (the arg-max and score planes are the
  * caller's, or the context's own where NULL is passed), and the selective median, where the namesake has one, filters that
  * plane; d_depth_raw_vu holds the refined, unfiltered plane.  C_e, the mask, C_d, rbar, idx and score are bit for bit what
- * subgrid = 0 gives (rbar stays the grid winner's).  One device; the 2-D sweep and fine-to-coarse have no such mode. */
+ * subgrid = 0 gives (rbar stays the grid winner's).  One device.  The 2-D sweep and fine-to-coarse have the mode as state of
+ * an open sweep: rslf_sweep_subgrid and the *_sub entries below it. */
 int rslf_depth_epi_pile_sub(rslf_ctx* ctx, const rslf_volume* vol,
                             const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
                             int dim_d, int s_hat,
@@ -559,6 +562,38 @@ int rslf_depth2d_run_host_lc(rslf_ctx* ctx, const rslf_volume* vol, float dmin, 
                              float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
                              float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu);
 
+/* ---- sub-grid disparities in the 2-D sweep (K9 inside a visit) ------------- */
+/* The sub-grid mode is state of an open sweep, as line confidence is: valid between rslf_sweep_begin and the first visit,
+ * cleared by rslf_sweep_end.  on = 1 sizes the visits' arg-max and score planes in the context's grow-only scratch (with
+ * line confidence on, the scan writes ONE arg-max plane for K7 and K9): no visit allocates.  A visit is then
+ *   scan (also writes idx and score) -> refinement -> the rest of the visit as without the mode
+ * The refinement is queued at the end of rslf_sweep_visit_scan, in place on the view's raw depth plane: every pixel this
+ * visit scanned and accepted (idx >= 0) gets rslf_subgrid_refine's disp; pixels painted by earlier visits keep the refined
+ * value they were painted with.  The median, the claims' target columns u + round(d * (s_hat - s) * slope), the apply pass
+ * and K7's positions then read refined floats.  rbar and the K columns stay the grid winner's; C_d, C_e and the masks are
+ * what the scan wrote.  A visit whose scan took the packed list of the previous apply pass refines over that list
+ * (k9_subgrid_refine_list, lane = entry); every other visit -- the first, "force_packed" = 0, planes beyond INT32_MAX pixels,
+ * "subgrid_list" = 0 -- over the whole plane; the bits are the same.  With the mode off every entry queues the launches and
+ * writes the bits it always did.  Between the visits of a sweep in the mode, the pile step's *_sub entries with NULL arg-max or
+ * score planes are not supported: they would take the context's own planes, which are the visits'.
+ * RSLF_ERR_INVALID_ARG: on outside 0..1, a call outside that window; nothing is launched. */
+int rslf_sweep_subgrid(rslf_ctx* ctx, const rslf_volume* vol, int on);
+
+/* The _lc entries with a last argument `subgrid`: 1 runs every visit in the mode, 0 is the _lc entry, launch for launch.  One
+ * device: the multi-device forms (rslf_multi_*) have no such mode. */
+int rslf_depth_epi_2d_sub(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                          float dmin, float dmax, int dim_d,
+                          float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                          float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats,
+                          int line_mode, float* d_Cl_svu, int subgrid);
+int rslf_depth2d_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                         float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                         float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu,
+                         int subgrid);
+int rslf_depth2d_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                              float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                              float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid);
+
 /* ---- "next" row: fine-to-coarse ---------------------- */
 /* rslf::FineToCoarse<T> (include/rslf_fine_to_coarse.hpp:26-81) is a host-side loop over pyramid
  * levels, each a Depth2DComputer (rslf_depth2d_run / rslf_depth_epi_2d above).  These are the pieces
@@ -709,6 +744,22 @@ int rslf_f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V,
                       float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                       int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
                       rslf_stats* stats);
+/* Fine-to-coarse with every level's sweep in the sub-grid mode (rslf_sweep_subgrid), through the one level loop: the bound
+ * tightening, the validity rules and the fusion are untouched and receive off-grid disparities; coarser levels refine inside
+ * their per-pixel ranges (lo == hi included: the refined value is lo).  subgrid = 0 is the namesake, launch for launch.
+ * rslf_fine_to_coarse_run_host_sub: rslf_fine_to_coarse_run_host_lc's arguments with elem (RSLF_ELEM_*) in place of is_u8 --
+ * so it has no u16 twin -- plus subgrid.  rslf_f2c_run_host_sub: rslf_f2c_run_host plus subgrid; rslf_f2c_run_subgrid reads
+ * it back from a kept run (0 or 1; rslf_f2c_run_desc keeps its size).  One device. */
+int rslf_fine_to_coarse_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                     float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                     int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid);
+int rslf_f2c_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                          float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                          int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                          rslf_stats* stats, int subgrid);
+int rslf_f2c_run_subgrid(const rslf_f2c_run* run);
 int rslf_f2c_run_destroy(rslf_f2c_run* run);   /* NULL is RSLF_OK; waits for the device */
 int rslf_f2c_run_describe(const rslf_f2c_run* run, rslf_f2c_run_desc* out);
 /* One plane (which: RSLF_F2C_PLANE_*) of one level into the caller's memory: a device pointer on the run's device, or with

@@ -662,6 +662,16 @@ public:
                       "rslf_multi_depth2d_run_f32");
             return;
         }
+        if (subgrid_) {   // every visit in the sub-grid mode (rslf_sweep_subgrid), with or without line confidence
+            if (line_mode != RSLF_LINE_CONF_OFF)
+                m_line_confidence_s_v_u.assign(n, 0.f);
+            check(rslf_depth2d_run_host_sub(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
+                                            m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
+                                            m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
+                                            line_mode != RSLF_LINE_CONF_OFF ? m_line_confidence_s_v_u.data() : nullptr, 1),
+                  "rslf_depth2d_run_host_sub");
+            return;
+        }
         if (line_mode != RSLF_LINE_CONF_OFF) {   // dc.hpp:721-738, :791-792
             m_line_confidence_s_v_u.assign(n, 0.f);
             check(rslf_depth2d_run_host_lc(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
@@ -676,6 +686,17 @@ public:
                                     m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats),
               "rslf_depth2d_run_host");
     }
+    // Not in the reference: with the mode on, every visit of run() moves the disparities its scan assigns off the hypothesis
+    // grid (rslf_sweep_subgrid, rslf_hip.h) before the selective median and the propagation read them; m_best_depth_s_v_u
+    // and the pictures of every getter then hold refined values.  Default off.  One context: an object built on a
+    // MultiContext throws with the mode on, as Depth1DComputer_pile::set_subgrid does.
+    void set_subgrid(bool on)
+    {
+        if (on && multi_)
+            throw std::invalid_argument("set_subgrid: this object was built on a MultiContext: the sub-grid mode is built for one context");
+        subgrid_ = on;
+    }
+    bool get_subgrid() const { return subgrid_; }
     const std::vector<float>& get_depths_s_v_u() const { return m_best_depth_s_v_u; }
 
     // dc.hpp:808-856: the S x U slice of the disparities at scanline a_v (< 0: floor(V / 2.0)) over its own min / max,
@@ -762,6 +783,7 @@ private:
     int dim_v_, dim_s_, dim_u_, m_dim_d;
     float m_dmin, m_dmax;
     const Depth1DParameters m_parameters;
+    bool subgrid_ = false;   // set_subgrid
 };
 
 // rslf::FineToCoarse<DataType> (include/rslf_fine_to_coarse.hpp:26-81): constructor arguments as in the
@@ -850,6 +872,16 @@ public:
         detail::require(rule == RSLF_F2C_VALID_COMPAT || rule == RSLF_F2C_VALID_REFERENCE, "validity rule: RSLF_F2C_VALID_COMPAT or _REFERENCE");
         validity_rule_ = rule;
     }
+    // Not in the reference, to be called before run(): every level's sweep runs in the sub-grid mode (rslf_sweep_subgrid), so
+    // the coarser levels' ranges are tightened from off-grid disparities and every getter shows refined planes.  run() then
+    // also keeps every level's planes, as after set_line_confidence_mode.  One device only: throws on a MultiContext.
+    void set_subgrid(bool on)
+    {
+        if (on && multi_)
+            throw std::invalid_argument("set_subgrid: this object was built on a MultiContext: the sub-grid mode is built for one context");
+        subgrid_ = on;
+    }
+    bool get_subgrid() const { return subgrid_; }
     ~FineToCoarse() { rslf_f2c_run_destroy(run_); }
     FineToCoarse(const FineToCoarse&) = delete;
     FineToCoarse& operator=(const FineToCoarse&) = delete;
@@ -863,7 +895,7 @@ public:
         const size_t n = (size_t)dim_s_ * dim_v_ * dim_u_;
         out_map_s_v_u_.assign(n, 0.f);
         out_validity_s_v_u_.assign(n, 0);
-        if (line_mode_ >= 0) {
+        if (line_mode_ >= 0 || subgrid_) {
             run_levels(p);
             return;
         }
@@ -1022,10 +1054,16 @@ private:
         disp_confidence_pyr_.clear();
         dims_.clear();
         const int elem = type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32;
-        check(rslf_f2c_run_host(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_, &p,
-                                max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
-                                keep_volumes_ ? 1 : 0, &run_, &stats),
-              "rslf_f2c_run_host");
+        if (subgrid_)
+            check(rslf_f2c_run_host_sub(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
+                                        scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
+                                        validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, 1),
+                  "rslf_f2c_run_host_sub");
+        else
+            check(rslf_f2c_run_host(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
+                                    &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
+                                    keep_volumes_ ? 1 : 0, &run_, &stats),
+                  "rslf_f2c_run_host");
         rslf_f2c_run_desc d;
         check(rslf_f2c_run_describe(run_, &d), "rslf_f2c_run_describe");
         n_levels_ = d.n_levels;
@@ -1064,6 +1102,7 @@ private:
     // run() through rslf_fine_to_coarse_run_host_lc / _u16_lc, every level's planes kept
     void run_levels(const rslf_params& p)
     {
+        const int mode = line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_;   // (set_subgrid alone leaves the line mode unset)
         int P = 0;
         check(rslf_f2c_pyramid_dims(dim_v_, dim_u_, max_pyr_depth_, nullptr, nullptr, 0, &P), "rslf_f2c_pyramid_dims");
         std::vector<int> Vp(P), Up(P);
@@ -1079,11 +1118,11 @@ private:
             dims_.push_back(std::make_pair(Vp[l], Up[l]));
             depths_pyr_[l].assign(nl, 0.f);
             validity_pyr_[l].assign(nl, 0);
-            if (line_mode_ != RSLF_LINE_CONF_OFF)
+            if (mode != RSLF_LINE_CONF_OFF)
                 line_confidence_pyr_[l].assign(nl, 0.f);
             hd[l] = depths_pyr_[l].data();
             hv[l] = validity_pyr_[l].data();
-            hl[l] = line_mode_ != RSLF_LINE_CONF_OFF ? line_confidence_pyr_[l].data() : nullptr;
+            hl[l] = mode != RSLF_LINE_CONF_OFF ? line_confidence_pyr_[l].data() : nullptr;
         }
         rslf_f2c_levels_out lo;
         lo.capacity = P;
@@ -1091,15 +1130,22 @@ private:
         lo.h_valid_svu = hv.data();
         lo.h_Cl_svu = hl.data();
         lo.h_Ce_svu = nullptr;
-        if (type_ == InputType::U16)
+        if (subgrid_)
+            check(rslf_fine_to_coarse_run_host_sub(ctx_->get(), epis_.data(),
+                                                   type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32,
+                                                   dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_,
+                                                   accept_all_ ? 1 : 0, out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats,
+                                                   mode, &lo, 1),
+                  "rslf_fine_to_coarse_run_host_sub");
+        else if (type_ == InputType::U16)
             check(rslf_fine_to_coarse_run_host_u16_lc(ctx_->get(), (const uint16_t* const*)epis_.data(), dim_v_, dim_s_, dim_u_, CHANNELS,
                                                       stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
-                                                      out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, line_mode_, &lo),
+                                                      out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo),
                   "rslf_fine_to_coarse_run_host_u16_lc");
         else
             check(rslf_fine_to_coarse_run_host_lc(ctx_->get(), epis_.data(), type_ == InputType::U8 ? 1 : 0, dim_v_, dim_s_, dim_u_, CHANNELS,
                                                   stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
-                                                  out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, line_mode_, &lo),
+                                                  out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo),
                   "rslf_fine_to_coarse_run_host_lc");
     }
 #ifdef RSLFX_HAVE_OPENCV
@@ -1130,6 +1176,7 @@ private:
     mutable std::vector<std::vector<float> > depths_pyr_, line_confidence_pyr_, disp_confidence_pyr_;   // (filled by the const getters of a kept run)
     mutable std::vector<std::vector<uint8_t> > validity_pyr_;
     bool keep_, keep_volumes_;   // keep_on_device
+    bool subgrid_ = false;       // set_subgrid
     int validity_rule_;
     rslf_f2c_run* run_;          // the kept run, owned
 };

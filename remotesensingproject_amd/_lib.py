@@ -53,6 +53,9 @@ SYMBOLS = [
     # sub-grid disparities in the pile step (K9)
     "rslf_subgrid_refine", "rslf_depth_epi_pile_sub", "rslf_depth_epi_scan_sub", "rslf_depth1d_run_sub", "rslf_depth1d_pile_run_sub",
     "rslf_depth1d_pile_run_host_sub",
+    # ... in the 2-D sweep and fine-to-coarse
+    "rslf_sweep_subgrid", "rslf_depth_epi_2d_sub", "rslf_depth2d_run_sub", "rslf_depth2d_run_host_sub",
+    "rslf_fine_to_coarse_run_host_sub", "rslf_f2c_run_host_sub", "rslf_f2c_run_subgrid",
 ]
 
 
@@ -289,6 +292,13 @@ def lib():
     L.rslf_depth_epi_2d_lc.argtypes = L.rslf_depth_epi_2d.argtypes + [ci, vp]
     L.rslf_depth2d_run_lc.argtypes = L.rslf_depth2d_run.argtypes + [ci, vp]
     L.rslf_depth2d_run_host_lc.argtypes = L.rslf_depth2d_run_host.argtypes + [ci, vp]
+    L.rslf_sweep_subgrid.argtypes = [vp, vp, ci]
+    L.rslf_depth_epi_2d_sub.argtypes = L.rslf_depth_epi_2d_lc.argtypes + [ci]
+    L.rslf_depth2d_run_sub.argtypes = L.rslf_depth2d_run_lc.argtypes + [ci]
+    L.rslf_depth2d_run_host_sub.argtypes = L.rslf_depth2d_run_host_lc.argtypes + [ci]
+    L.rslf_fine_to_coarse_run_host_sub.argtypes = L.rslf_fine_to_coarse_run_host_lc.argtypes + [ci]   # (elem where is_u8 is: an int too)
+    L.rslf_f2c_run_host_sub.argtypes = L.rslf_f2c_run_host.argtypes + [ci]
+    L.rslf_f2c_run_subgrid.argtypes = [vp]
     for name in SYMBOLS:
         f = getattr(L, name)   # AttributeError here = the library does not export the ABI
         if f.restype is C.c_int and name not in ("rslf_abi_version", "rslf_device_count"):

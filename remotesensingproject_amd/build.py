@@ -28,8 +28,8 @@ UNITS = {
     "rslf_chip_c.hip": ["k2_scan.hpp", "k2_chip.hpp"],
     "rslf_scores.hip": ["k2_scan.hpp", "k2_reg.hpp", "k2_scores.hpp"],
     "rslf_peaks.hip": ["k8_peaks.hpp", "k8_peak_rule.hpp", "rslf_plan_peaks.hpp"],
-    "rslf_subgrid.hip": ["k2_scan.hpp", "k9_subgrid.hpp", "k8_peak_rule.hpp"],
-    "rslf_sweep.hip": ["k3_median.hpp", "k4_propagate.hpp", "k_compact.hpp", "k2_scan.hpp", "k7_line_conf.hpp"],
+    "rslf_subgrid.hip": ["k2_scan.hpp", "k9_subgrid.hpp", "k8_peak_rule.hpp", "rslf_plan_subgrid.hpp"],
+    "rslf_sweep.hip": ["k3_median.hpp", "k4_propagate.hpp", "k_compact.hpp", "k2_scan.hpp", "k7_line_conf.hpp", "rslf_plan_subgrid.hpp"],
     "rslf_f2c.hip": ["k5_f2c.hpp"],
     "rslf_f2c_keep.hip": [],
     "rslf_render.hip": ["k6_render.hpp", "rslf_plan_render.hpp"],

@@ -37,16 +37,15 @@ struct SubgridArgs {
 // `a`: the scan's arguments -- volume, ranges, dim_d, s_hat, constants (the lists and output planes are not read).
 // CENTRE: no score plane, the winner is the third hypothesis.  NEAREST: a.k.interp != 0, the one-tap modes (a kernel of their
 // own, so that the linear one carries no test of the mode in its loop over the views).
+//
+// subgrid_refine_pixel is the body of one pixel (v, u), in range; both kernels below call it and nothing else touches a
+// score.  In the dense kernel v is the workgroup's (the EPI base a scalar); in the list form it is the lane's.
 template <int C, bool CENTRE, bool NEAREST>
-__global__ __launch_bounds__(256) void k9_subgrid_refine(ScanArgs a, SubgridArgs q)
+__device__ __forceinline__ void subgrid_refine_pixel(const ScanArgs& a, const SubgridArgs& q, const int v, const int u)
 {
     constexpr int NH = CENTRE ? 3 : 2;
     constexpr int N = C == 1 ? kSubgridBatch : kSubgridBatch / 2;
     const VolView& vol = a.vol;
-    const int v = blockIdx.y;
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= vol.U)
-        return;
     const long long o = (long long)v * vol.U + u;
     const int i1 = q.idx[o];
     if ((unsigned)i1 >= (unsigned)a.dim_d)   // -1: no disparity, nothing is touched; >= dim_d: not a scan's plane (the host cannot see it)
@@ -198,6 +197,36 @@ __global__ __launch_bounds__(256) void k9_subgrid_refine(ScanArgs a, SubgridArgs
         q.left[o] = i1 == 0 ? 0.0f : sc[0];
     if (q.right)
         q.right[o] = i1 == last ? 0.0f : sc[1];
+}
+
+template <int C, bool CENTRE, bool NEAREST>
+__global__ __launch_bounds__(256) void k9_subgrid_refine(ScanArgs a, SubgridArgs q)
+{
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= a.vol.U)
+        return;
+    subgrid_refine_pixel<C, CENTRE, NEAREST>(a, q, blockIdx.y, u);
+}
+
+// The list-driven form: lane = entry of a 2-D sweep's packed list (a.list: pixel indices v * U + u, row-contiguous,
+// ascending u; a.packed_n: its length, known to the device alone).  After the centre view a visit scans a few pixels per
+// scanline; over the whole plane nearly every wave of the dense kernel would still hold one live lane and walk all the
+// sample passes for it.  Here 64 consecutive entries make a wave -- mostly one scanline's, neighbours in u, so their taps
+// share cache lines as a row's do -- and each lane carries its own row pointer.  A fixed grid strides over the entries (no
+// host read of the length); a lane past the end, or whose idx is not in [0, dim_d), does nothing.  Same body, nothing
+// crosses lanes: the bits are the dense kernel's whatever the mapping.  No LDS, no scratch.
+template <int C, bool CENTRE, bool NEAREST>
+__global__ __launch_bounds__(256) void k9_subgrid_refine_list(ScanArgs a, SubgridArgs q)
+{
+    const unsigned n = (unsigned)max(*a.packed_n, 0);
+    const int U = a.vol.U;
+    // (unsigned: an entry index below 2^31 plus the grid's stride, at most 2^22 lanes, cannot wrap)
+    for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
+        const int px = a.list[e];
+        if ((unsigned)px >= (unsigned)(a.vol.V * U))   // not an entry of this plane's list: nothing is touched
+            continue;
+        subgrid_refine_pixel<C, CENTRE, NEAREST>(a, q, px / U, px % U);
+    }
 }
 
 }  // namespace rslf

@@ -451,8 +451,10 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const
                                      size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                      const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
                                      uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats, int line_mode,
-                                     const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep)
+                                     const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep, int subgrid)
 {
+    if (subgrid != 0 && subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
         if (inject_hit(kInjectSweep))   // host side, before the level's sweep is queued
             throw std::runtime_error("injected failure in a fine-to-coarse level (rslf_debug_inject)");
@@ -471,7 +473,7 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const
         if (!rc)
             rc = depth2d_run_lc(ctx, vol.get(), lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, mask.as<uint8_t>(),
                                 lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(), nullptr, level_stats,
-                                lv.line_mode, lv.Cl_svu);
+                                lv.line_mode, lv.Cl_svu, subgrid);
         if (!rc && lv.vol_out)
             *lv.vol_out = std::move(vol);   // kept; otherwise destroyed here, with the sweep's other planes
         return rc;
@@ -506,6 +508,22 @@ extern "C" int rslf_fine_to_coarse_run_host_lc(rslf_ctx* ctx, const void* const*
     return fine_to_coarse_one_context(ctx, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
                                       epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
                                       stats, line_mode, levels_out, RSLF_F2C_VALID_COMPAT, nullptr);
+}
+RSLF_API_CATCH
+
+// ... any element type (RSLF_ELEM_*), every level's sweep in the sub-grid mode with subgrid = 1
+extern "C" int rslf_fine_to_coarse_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                                size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                                const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                                int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid) RSLF_API_TRY
+{
+    if (elem != RSLF_ELEM_F32 && elem != RSLF_ELEM_U8 && elem != RSLF_ELEM_U16)
+        return fail(RSLF_ERR_INVALID_ARG, "element type %d: RSLF_ELEM_F32, _U8 or _U16", elem);
+    const Elem e = elem == RSLF_ELEM_U8 ? Elem::U8 : elem == RSLF_ELEM_U16 ? Elem::U16 : Elem::F32;
+    return fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                                      max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, line_mode,
+                                      levels_out, RSLF_F2C_VALID_COMPAT, nullptr, subgrid);
 }
 RSLF_API_CATCH
 

@@ -244,16 +244,18 @@ int render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, 
 
 }  // namespace
 
-extern "C" int rslf_f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
                                  float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                  int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
-                                 rslf_stats* stats) RSLF_API_TRY
+                                 rslf_stats* stats, int subgrid)
 {
     if (!run)
         return fail(RSLF_ERR_INVALID_ARG, "run is NULL");
     *run = nullptr;
     if (!ctx || !h_epis || !p)
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    if (subgrid != 0 && subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     Elem e;
     int rc = elem_of(elem, &e);
     if (rc)
@@ -267,14 +269,43 @@ extern "C" int rslf_f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int e
     r->elem = elem;
     r->line_mode = line_mode;
     r->validity_rule = validity_rule;
+    r->subgrid = subgrid;
     r->params = *p;
     r->kept.keep_volumes = keep_volumes != 0;
     rc = fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                                    accept_all_last_scale, nullptr, nullptr, nullptr, stats, line_mode, nullptr, validity_rule, &r->kept);
+                                    accept_all_last_scale, nullptr, nullptr, nullptr, stats, line_mode, nullptr, validity_rule, &r->kept,
+                                    subgrid);
     if (rc)
         return rc;
     *run = r.release();
     return RSLF_OK;
+}
+
+extern "C" int rslf_f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                                 float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                                 int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                                 rslf_stats* stats) RSLF_API_TRY
+{
+    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, 0);
+}
+RSLF_API_CATCH
+
+// ... every level's sweep in the sub-grid mode (rslf_sweep_subgrid); subgrid = 0 is rslf_f2c_run_host
+extern "C" int rslf_f2c_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
+                                     int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid) RSLF_API_TRY
+{
+    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid);
+}
+RSLF_API_CATCH
+
+// (not a field of rslf_f2c_run_desc: the structure keeps its size)
+extern "C" int rslf_f2c_run_subgrid(const rslf_f2c_run* run) RSLF_API_TRY
+{
+    return run ? run->subgrid : 0;
 }
 RSLF_API_CATCH
 

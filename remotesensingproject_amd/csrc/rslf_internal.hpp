@@ -15,6 +15,7 @@
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
+//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp   ... continued, for the units that need them
 //   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
 //
 // Two rules of the multi-device paths: they never write into a rslf_volume they did not create (a chunk of another height
@@ -214,8 +215,8 @@ struct Scratch {
     DeviceBuf scan_partial; // rslf::Partial [tile][group][64]: records of grouped scan launches
     DeviceBuf scan_ticket;  // int [tile] of the same launches: which group merges the tile (zero between launches)
     DeviceBuf max_partial;  // float [kMaxPartials]: block maxima of rslf_device_max_f32
-    DeviceBuf sub_idx;      // int32 [V*U]: a sub-grid pile step's arg-max plane when the caller passes none (subgrid_planes)
-    DeviceBuf sub_score;    // float [V*U]: ... and its score plane
+    DeviceBuf sub_idx;      // int32 [V*U]: a sub-grid pile step's arg-max plane when the caller passes none (subgrid_planes); a sub-grid sweep's visits' (rslf_sweep_subgrid)
+    DeviceBuf sub_score;    // float [V*U]: ... and their score plane
     DeviceBuf row_exact;    // the scan's row-exact table (k2_scan.hpp, ScanArgs::rx_*): [D][slots] offsets, [D][slots] weight pairs, [D] floats, [D] ints; RowExactKey says of what
     // 2-D sweep
     DeviceBuf winner;       // int [S][V][U]: the claims (0x7F7F7F7F between visits)
@@ -278,6 +279,10 @@ struct SweepState {
     float lc_dmin = 0.0f, lc_dmax = 0.0f;
     int lc_dim_d = 0;
     ScanConsts lc_consts = {};
+    // sub-grid mode (rslf_sweep_subgrid; k9_subgrid.hpp): state of ONE sweep too.  The visit's arg-max and score planes are
+    // Scratch::sub_idx / sub_score, sized when the mode is set; with line confidence on, the arg-max plane is K7's
+    // (Scratch::lc_argmax): one plane for both.
+    bool subgrid = false;
 };
 
 }  // namespace rslf
@@ -311,6 +316,7 @@ struct rslf_ctx {
     int scalar_taps = 1;       // ... and row-exact hypotheses take the scalar-tap form from the per-launch table (k2_reg.hpp; 0: off, A/B and tests)
     rslf::RowExactKey row_exact_key;   // what scratch.row_exact holds
     bool last_row_exact = false;       // the last scan's launch was handed the table (rslf_last_scan_row_exact)
+    int subgrid_list = 1;      // 2-D sweep in the sub-grid mode: sparse visits refine over the packed list (0: every visit the dense form; A/B and tests)
     int claim_skip = 1;        // 2-D sweep: the claims skip views with nothing left to paint within reach (0: off, A/B and tests)
     int staging_kib = 0;       // chunked host upload: device staging per pass in KiB (0: plan::kStagingBudget; tests of the later passes)
 };
@@ -422,6 +428,7 @@ struct ScanInputs {
     bool packed_n_zero = false;   // the packed list's length is already 0
     bool zero_total = true;       // the pixel total starts again
     bool timed = true;            // ctx->ev0 / ev1 bracket the launches (rslf_last_scan_kernel_ms)
+    bool clear_score = true;      // a score plane starts at 0 (a sweep's sub-grid visits read it only where this scan wrote idx: no fill)
 };
 ScanInputs scan_defaults(const rslf_ctx* ctx);
 int depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
@@ -449,10 +456,11 @@ void score_stats(unsigned long long pixels, int dim_d, int kind, int spad, rslf_
 
 // rslf_subgrid.hip
 // k9_subgrid_refine over a volume's [V][U] planes, arguments already checked (check_scan_args): one launch queued on the
-// context's stream.  d_score_vu, d_left_vu, d_right_vu nullable; d_disp_vu may be the scan's depth plane.
+// context's stream.  d_score_vu, d_left_vu, d_right_vu nullable; d_disp_vu may be the scan's depth plane.  listed: lane =
+// entry of the context's packed list (k9_subgrid_refine_list), for a sweep's visit whose scan took that list.
 int subgrid_refine(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
                    int dim_d, int s_hat, const rslf_params* p, const int32_t* d_idx_vu, const float* d_score_vu, float* d_disp_vu,
-                   float* d_left_vu, float* d_right_vu);
+                   float* d_left_vu, float* d_right_vu, bool listed = false);
 
 // rslf_sweep.hip
 // Depth2DComputer::run (dc.hpp:748-805) on device planes; d_dmin_svu / d_dmax_svu: per-pixel ranges (a fine-to-coarse
@@ -461,10 +469,11 @@ int depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, 
                 int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                 float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats);
 // The same with the line-confidence plane of dc.hpp:721-738, :791-792: line_mode RSLF_LINE_CONF_*, d_Cl_svu [S][V][U]
-// (zero-filled here; NULL with RSLF_LINE_CONF_OFF, which queues exactly the launches of depth2d_run).
+// (zero-filled here; NULL with RSLF_LINE_CONF_OFF, which queues exactly the launches of depth2d_run).  subgrid = 1: every
+// visit in the sub-grid mode (rslf_sweep_subgrid).
 int depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
                    int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
-                   float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu);
+                   float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid = 0);
 
 // rslf_f2c.hip
 // A volume owned by a scope or an object (rslf_volume_destroy is the one place that frees a slab).
@@ -514,12 +523,13 @@ int fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, i
                    int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
                    int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep,
                    const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep);
-// The loop on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run_lc.
+// The loop on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run_lc -- with
+// subgrid = 1 in the sub-grid mode: the bound tightening, the validity and the fusion then receive off-grid disparities.
 int fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
                                float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
                                rslf_stats* stats, int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule,
-                               F2cKept* keep);
+                               F2cKept* keep, int subgrid = 0);
 
 // rslf_multi.hip
 void multi_free_dev(rslf_multi::Dev& d);
@@ -534,6 +544,7 @@ struct rslf_f2c_run {
     int device = 0;
     int S = 0, C = 0, elem = RSLF_ELEM_F32;
     int line_mode = RSLF_LINE_CONF_OFF, validity_rule = RSLF_F2C_VALID_COMPAT;
+    int subgrid = 0;      // every level was swept in the sub-grid mode (rslf_f2c_run_host_sub)
     rslf_params params;   // as given: the getters' cut_shadows / shadow_level
     rslf::F2cKept kept;
 };

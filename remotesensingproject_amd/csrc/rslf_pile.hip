@@ -455,7 +455,7 @@ int rslf::depth_epi_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
     const Scratch& sc = ctx->scratch;
     if (d_idx_vu)
         HIP_TRY(hipMemsetAsync(d_idx_vu, 0xFF, n * sizeof(int32_t), st));   // -1
-    if (d_score_vu)
+    if (d_score_vu && in.clear_score)
         HIP_TRY(hipMemsetAsync(d_score_vu, 0, n * sizeof(float), st));
     if (in.zero_total && in.lists == ScanInputs::kCompact)
         HIP_TRY(hipMemsetAsync(sc.pixel_total(), 0, sizeof(unsigned long long), st));

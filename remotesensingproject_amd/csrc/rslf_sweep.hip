@@ -2,6 +2,7 @@
 // selective median + claims, apply + the next visit's compaction (K4), and the sweep's line confidence (K7).  C-ABI:
 // include/rslf_hip.h.
 #include "rslf_internal.hpp"
+#include "rslf_plan_subgrid.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -166,8 +167,11 @@ extern "C" int rslf_sweep_line_confidence(rslf_ctx* ctx, const rslf_volume* vol,
     HIP_TRY(hipSetDevice(ctx->device));
     sw.lc_mode = RSLF_LINE_CONF_OFF;
     sw.lc_Cl_svu = nullptr;
-    if (mode == RSLF_LINE_CONF_OFF)
+    if (mode == RSLF_LINE_CONF_OFF) {
+        if (sw.subgrid)   // line confidence switched off again after rslf_sweep_subgrid: the visits need an arg-max plane of their own
+            HIP_TRY(hip_err(ctx->scratch.sub_idx.reserve(plan::sweep_subgrid_plane_bytes(true, vol->V, vol->U))));
         return RSLF_OK;
+    }
     // buffers of their own, not shared ones: they are held until rslf_sweep_end
     Scratch& sc = ctx->scratch;
     const size_t kb = plan::line_conf_columns_bytes(mode, vol->V, vol->S, vol->U);
@@ -180,6 +184,33 @@ extern "C" int rslf_sweep_line_confidence(rslf_ctx* ctx, const rslf_volume* vol,
     sw.lc_idx_vu = sc.lc_argmax.as<int32_t>();
     sw.lc_Cl_svu = d_Cl_svu;
     sw.lc_mode = mode;
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+// The sub-grid mode of an open sweep (include/rslf_hip.h; k9_subgrid.hpp): every visit's scan keeps its arg max and the
+// winner's score, and the refinement follows the scan in place on the view's raw depth plane.
+extern "C" int rslf_sweep_subgrid(rslf_ctx* ctx, const rslf_volume* vol, int on) RSLF_API_TRY
+{
+    if (!ctx || !vol)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (on != 0 && on != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_subgrid: on=%d: 0 or 1", on);
+    SweepState& sw = ctx->sweep;
+    if (!sw.open || sw.scanned || !sw.first)
+        return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_subgrid belongs between rslf_sweep_begin and the first visit");
+    HIP_TRY(hipSetDevice(ctx->device));
+    sw.subgrid = false;
+    if (!on)
+        return RSLF_OK;
+    // sized here, never inside a visit; held until rslf_sweep_end (buffers of the context's own, not shared ones).  With line
+    // confidence on, the visits' arg-max plane is K7's: no second one (the two setters come in either order)
+    Scratch& sc = ctx->scratch;
+    const size_t bytes = plan::sweep_subgrid_plane_bytes(true, vol->V, vol->U);
+    if (sw.lc_mode == RSLF_LINE_CONF_OFF)
+        HIP_TRY(hip_err(sc.sub_idx.reserve(bytes)));
+    HIP_TRY(hip_err(sc.sub_score.reserve(bytes)));
+    sw.subgrid = true;
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -205,16 +236,31 @@ extern "C" int rslf_sweep_visit_scan(rslf_ctx* ctx, const rslf_volume* vol, cons
     // goes to Scratch::filtered (rslf_sweep_visit_finish) -- no plane copies.
     ctx->sweep.scanned = true;
     const bool lc = ctx->sweep.lc_mode != RSLF_LINE_CONF_OFF;   // K7 re-runs the winners: the scan keeps its arg-max indices
-    const int rc = depth_epi_scan(ctx, vol, d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr,
-                                  d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr, dmin, dmax, dim_d, s_hat, d_Ce_svu + (size_t)s_hat * n,
-                                  d_Ce_mask_svu + (size_t)s_hat * n, d_Cd_svu + (size_t)s_hat * n, d_depth_svu + (size_t)s_hat * n,
-                                  d_rbar_svu + (size_t)s_hat * n * vol->C, p, ctx->sweep.mask_run + (size_t)s_hat * n,
-                                  lc ? ctx->sweep.lc_idx_vu : nullptr, nullptr, nullptr, visit_inputs(ctx->sweep.first, ctx->sweep.listed));
+    // Sub-grid mode: the scan also keeps the winner's score, and K9 follows it.  Which form is decided before the scan so
+    // that nothing below can fail between the two; one arg-max plane serves K7 and K9.
+    const plan::SubgridForm form = plan::sweep_subgrid_form(ctx->sweep.subgrid, ctx->sweep.first, ctx->sweep.listed,
+                                                            ctx->subgrid_list, (long long)n);
+    const float* dmin_vu = d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr;
+    const float* dmax_vu = d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr;
+    int32_t* idx_vu = lc ? ctx->sweep.lc_idx_vu : form != plan::kSubgridNone ? ctx->scratch.sub_idx.as<int32_t>() : nullptr;
+    float* score_vu = form != plan::kSubgridNone ? ctx->scratch.sub_score.as<float>() : nullptr;
+    ScanInputs in = visit_inputs(ctx->sweep.first, ctx->sweep.listed);
+    in.clear_score = false;   // K9 reads a score only where this scan wrote idx >= 0, and so the score: one fill less a visit
+    int rc = depth_epi_scan(ctx, vol, dmin_vu, dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_svu + (size_t)s_hat * n,
+                            d_Ce_mask_svu + (size_t)s_hat * n, d_Cd_svu + (size_t)s_hat * n, d_depth_svu + (size_t)s_hat * n,
+                            d_rbar_svu + (size_t)s_hat * n * vol->C, p, ctx->sweep.mask_run + (size_t)s_hat * n, idx_vu, score_vu,
+                            nullptr, in);
+    // The refinement, queued here: before k34_median_claim (or, gating on C_l, k3_selective_median) zeroes the packed list's
+    // length, and before a caller's halo exchange.  Only pixels this visit scanned have idx >= 0; painted ones keep the
+    // refined value they were painted with.  r-bar, the K columns, C_d, C_e and the masks stay the grid winner's.
+    if (!rc && form != plan::kSubgridNone)
+        rc = subgrid_refine(ctx, vol, dmin_vu, dmax_vu, dmin, dmax, dim_d, s_hat, p, idx_vu, score_vu, d_depth_svu + (size_t)s_hat * n,
+                            nullptr, nullptr, form == plan::kSubgridList);
     if (rc || !lc)
         return rc;
     ctx->sweep.lc_Ce_svu = d_Ce_svu;
-    ctx->sweep.lc_dmin_vu = d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr;
-    ctx->sweep.lc_dmax_vu = d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr;
+    ctx->sweep.lc_dmin_vu = dmin_vu;
+    ctx->sweep.lc_dmax_vu = dmax_vu;
     ctx->sweep.lc_dmin = dmin, ctx->sweep.lc_dmax = dmax, ctx->sweep.lc_dim_d = dim_d;
     ctx->sweep.lc_consts = make_scan_consts(p);
     return RSLF_OK;
@@ -359,7 +405,7 @@ RSLF_API_CATCH
 static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
                         float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                         float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                        float* d_Cl_svu)
+                        float* d_Cl_svu, int subgrid)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -367,6 +413,8 @@ static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dm
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
     if (line_mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
+    if (subgrid != 0 && subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     int rc = check_params(p);
     if (rc)
         return rc;
@@ -375,6 +423,8 @@ static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dm
         return rc;
     if (line_mode != RSLF_LINE_CONF_OFF)
         rc = rslf_sweep_line_confidence(ctx, vol, line_mode, d_Cl_svu);
+    if (!rc && subgrid)
+        rc = rslf_sweep_subgrid(ctx, vol, 1);
     for (int s_hat : plan::sweep_order(vol->S)) {   // core.hpp:981-990
         if (!rc)
             rc = rslf_sweep_visit_scan(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, s_hat, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu,
@@ -396,7 +446,7 @@ extern "C" int rslf_depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const fl
                                  rslf_stats* stats) RSLF_API_TRY
 {
     return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                        p, d_scan_mask_svu, stats, RSLF_LINE_CONF_OFF, nullptr);
+                        p, d_scan_mask_svu, stats, RSLF_LINE_CONF_OFF, nullptr, 0);
 }
 RSLF_API_CATCH
 
@@ -407,14 +457,25 @@ extern "C" int rslf_depth_epi_2d_lc(rslf_ctx* ctx, const rslf_volume* vol, const
                                     rslf_stats* stats, int line_mode, float* d_Cl_svu) RSLF_API_TRY
 {
     return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu);
+                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, 0);
+}
+RSLF_API_CATCH
+
+// ... and the sub-grid mode: subgrid = 0 queues exactly rslf_depth_epi_2d_lc's launches
+extern "C" int rslf_depth_epi_2d_sub(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                                     float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
+                                     float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
+                                     rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid) RSLF_API_TRY
+{
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid);
 }
 RSLF_API_CATCH
 
 int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
                          float dmax, int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
                          float* d_depth_svu, float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                         float* d_Cl_svu)
+                         float* d_Cl_svu, int subgrid)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -422,6 +483,8 @@ int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
     if (line_mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
+    if (subgrid != 0 && subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n = (size_t)vol->S * vol->V * vol->U;
     hipStream_t st = ctx->stream;
@@ -436,7 +499,7 @@ int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
     if (rc)
         return rc;
     return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
-                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu);
+                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid);
 }
 
 int rslf::depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
@@ -466,12 +529,24 @@ extern "C" int rslf_depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, float 
 }
 RSLF_API_CATCH
 
+// ... and the sub-grid mode of every visit (rslf_sweep_subgrid); subgrid = 0 queues exactly rslf_depth2d_run_lc's launches
+extern "C" int rslf_depth2d_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                    float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
+                                    uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid) RSLF_API_TRY
+{
+    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                          d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid);
+}
+RSLF_API_CATCH
+
 static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                             float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
-                            rslf_stats* stats, int line_mode, float* h_Cl_svu)
+                            rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid)
 {
     if (!ctx || !vol)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (subgrid != 0 && subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     if (!plan::line_conf_mode_ok(line_mode))
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
     if (line_mode != RSLF_LINE_CONF_OFF && !h_Cl_svu)
@@ -487,7 +562,7 @@ static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, f
     if (line_mode != RSLF_LINE_CONF_OFF)
         HIP_TRY(Cl.alloc(n * 4));
     int rc = depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, Ce.as<float>(), mask.as<uint8_t>(), Cd.as<float>(),
-                            depth.as<float>(), rbar.as<float>(), nullptr, stats, line_mode, Cl.as<float>());
+                            depth.as<float>(), rbar.as<float>(), nullptr, stats, line_mode, Cl.as<float>(), subgrid);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
@@ -506,7 +581,7 @@ extern "C" int rslf_depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, floa
                                      float* h_rbar_svu, rslf_stats* stats) RSLF_API_TRY
 {
     return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
-                            RSLF_LINE_CONF_OFF, nullptr);
+                            RSLF_LINE_CONF_OFF, nullptr, 0);
 }
 RSLF_API_CATCH
 
@@ -515,6 +590,15 @@ extern "C" int rslf_depth2d_run_host_lc(rslf_ctx* ctx, const rslf_volume* vol, f
                                         float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu) RSLF_API_TRY
 {
     return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
-                            line_mode, h_Cl_svu);
+                            line_mode, h_Cl_svu, 0);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_depth2d_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                         float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                                         float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid) RSLF_API_TRY
+{
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
+                            line_mode, h_Cl_svu, subgrid);
 }
 RSLF_API_CATCH

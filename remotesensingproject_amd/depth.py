@@ -99,11 +99,11 @@ def require_no_line_confidence(parameters, who: str) -> None:
 
 
 def require_no_subgrid(subgrid, who: str) -> None:
-    """The sub-grid mode is built for the one-device pile step alone (DESIGN.md 3 "Sub-grid pile"): every multi-device form
-    refuses it instead of ignoring it."""
+    """The sub-grid mode is built for one device -- the pile step (DESIGN.md 3 "Sub-grid pile"), the 2-D sweep and the
+    pyramid ("Sub-grid sweep") -- and every multi-device form refuses it instead of ignoring it."""
     if subgrid:
-        raise ValueError("%s: subgrid=True is not built here (one device: Depth1DComputer_pile, Depth1DComputer and the "
-                         "compute_1D_depth_epi functions)" % who)
+        raise ValueError("%s: subgrid=True is not built here (one device: Depth1DComputer_pile, Depth1DComputer, "
+                         "Depth2DComputer, FineToCoarse, fine_to_coarse_run_host and the compute_*_depth_epi functions)" % who)
 
 
 class Context:
@@ -126,7 +126,8 @@ class Context:
         check(_lib.lib().rslf_ctx_synchronize(self._h), "rslf_ctx_synchronize")
 
     _DEBUG_DEFAULTS = dict(force_scan=0, force_groups=0, force_packed=-1, px=-1, stream_share=1, stream_groups=0, stream_lds_kib=80,
-                           claim_skip=1, time_all=0, row_split=1, staging_kib=0, tap_table=1, scalar_taps=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
+                           claim_skip=1, time_all=0, row_split=1, staging_kib=0, tap_table=1, scalar_taps=1,
+                           subgrid_list=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
     _FORCE_SCAN = {None: 0, "auto": 0, "generic": 1, "stream": 2}
 
     def set_debug(self, **hooks) -> None:
@@ -906,10 +907,11 @@ class MultiDevice:
         return out
 
     def depth2d(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
-                parameters: Depth1DParameters | None = None) -> dict:
+                parameters: Depth1DParameters | None = None, subgrid: bool = False) -> dict:
         """Depth2DComputer (constructor + run + getters) over this object's devices: the 2-D sweep cut into one block of
         scanlines per device, the neighbours' boundary rows exchanged by peer copy on every visit
         (rslf_multi_depth2d_run_f32 / _u8 / _u16).  Host EPIs in, numpy planes [S, V, U] out."""
+        require_no_subgrid(subgrid, "MultiDevice.depth2d")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((S, V, U), np.float32), edge_mask=np.empty((S, V, U), np.uint8),
                    disp_confidence=np.empty((S, V, U), np.float32), depth=np.empty((S, V, U), np.float32),
@@ -933,9 +935,11 @@ class MultiDevice:
         return out
 
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
-                       parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True):
+                       parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
+                       subgrid: bool = False):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
+        require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
@@ -1021,12 +1025,15 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
                          a_edge_confidence_mask_s_v_u: torch.Tensor, a_disp_confidence_s_v_u: torch.Tensor,
                          a_best_depth_s_v_u: torch.Tensor, a_rbar_s_v_u: torch.Tensor,
                          a_parameters: Depth1DParameters | None = None, *, scan_mask_s_v_u: torch.Tensor | None = None,
-                         want_stats: bool = False, a_line_confidence_s_v_u: torch.Tensor | None = None) -> RslfStats | None:
+                         want_stats: bool = False, a_line_confidence_s_v_u: torch.Tensor | None = None,
+                         subgrid: bool = False) -> RslfStats | None:
     """core.hpp:336-351.  a_line_confidence_s_v_u ([S,V,U] f32, pass zeros) is the argument of the
     _USE_LINE_CONFIDENCE_SCORE build (:345): with it the call goes through rslf_depth_epi_2d_lc in
     a_parameters.par_line_confidence_mode -- mode 0 is then the default build and leaves the plane untouched; modes 1 and 2
     need the plane (without it the library returns RSLF_ERR_INVALID_ARG).
-    a_dmin_s_v_u / a_dmax_s_v_u: [S,V,U] f32 CUDA tensors or Python floats."""
+    a_dmin_s_v_u / a_dmax_s_v_u: [S,V,U] f32 CUDA tensors or Python floats.
+    subgrid (not in the reference): every visit moves the disparities its scan wrote off the hypothesis grid before the
+    median and the propagation read them (rslf_depth_epi_2d_sub)."""
     par = a_parameters or Depth1DParameters()
     p = par.to_c()
     planes = isinstance(a_dmin_s_v_u, torch.Tensor)
@@ -1038,7 +1045,9 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
             _ptr(a_best_depth_s_v_u), _ptr(a_rbar_s_v_u), C.byref(p), _ptr(scan_mask_s_v_u),
             C.byref(st) if st is not None else None)
     mode = int(par.par_line_confidence_mode)
-    if a_line_confidence_s_v_u is None and mode == LINE_CONF_OFF:
+    if subgrid:
+        check(_lib.lib().rslf_depth_epi_2d_sub(*args, mode, _ptr(a_line_confidence_s_v_u), 1), "rslf_depth_epi_2d_sub")
+    elif a_line_confidence_s_v_u is None and mode == LINE_CONF_OFF:
         check(_lib.lib().rslf_depth_epi_2d(*args), "rslf_depth_epi_2d")
     else:
         check(_lib.lib().rslf_depth_epi_2d_lc(*args, mode, _ptr(a_line_confidence_s_v_u)), "rslf_depth_epi_2d_lc")
@@ -1050,8 +1059,12 @@ class Depth2DComputer:
     visiting the views from the centre outwards and propagating along EPI lines."""
 
     def __init__(self, epis, dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
-                 parameters: Depth1DParameters | None = None, verbose: bool = False, ctx: Context | None = None):
+                 parameters: Depth1DParameters | None = None, verbose: bool = False, ctx: Context | None = None,
+                 subgrid: bool = False):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        # not in the reference: every visit's disparities are moved off the hypothesis grid before the median and the
+        # propagation (rslf_sweep_subgrid); every getter then shows refined planes
+        self.m_subgrid = bool(subgrid)
         if isinstance(epis, Volume):
             self.m_epis = epis
         elif isinstance(epis, (list, tuple)):
@@ -1093,11 +1106,13 @@ class Depth2DComputer:
                 _ptr(self.m_edge_confidence_mask_s_v_u), _ptr(self.m_disp_confidence_s_v_u), _ptr(self.m_best_depth_s_v_u),
                 _ptr(self.m_rbar_s_v_u), _ptr(self.m_scan_mask_s_v_u), C.byref(st) if st is not None else None)
         mode = self._line_mode()
-        if mode == LINE_CONF_OFF:
+        if mode != LINE_CONF_OFF and self.m_line_confidence_s_v_u is None:   # the mode was set after the constructor ran
+            self.m_line_confidence_s_v_u = torch.empty_like(self.m_edge_confidence_s_v_u)
+        if self.m_subgrid:
+            check(_lib.lib().rslf_depth2d_run_sub(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1), "rslf_depth2d_run_sub")
+        elif mode == LINE_CONF_OFF:
             check(_lib.lib().rslf_depth2d_run(*args), "rslf_depth2d_run")
         else:
-            if self.m_line_confidence_s_v_u is None:   # the mode was set after the constructor ran
-                self.m_line_confidence_s_v_u = torch.empty_like(self.m_edge_confidence_s_v_u)
             check(_lib.lib().rslf_depth2d_run_lc(*args, mode, _ptr(self.m_line_confidence_s_v_u)), "rslf_depth2d_run_lc")
         self.stats = st
 
@@ -1408,6 +1423,7 @@ class KeptFineToCoarse:
         self.dims = [(d.V[l], d.U[l]) for l in range(d.n_levels)]            # (V_p, U_p), finest first
         self.scales = [float(d.epi_scale_factor[l]) for l in range(d.n_levels)]
         self.line_mode, self.validity_rule, self.keep_volumes = d.line_mode, d.validity_rule, bool(d.keep_volumes)
+        self.subgrid = bool(_lib.lib().rslf_f2c_run_subgrid(self._h))   # every level was swept in the sub-grid mode
 
     def describe(self) -> "_lib.RslfF2cRunDesc":
         d = _lib.RslfF2cRunDesc()
@@ -1474,7 +1490,7 @@ class KeptFineToCoarse:
 def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                             parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                             ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False, keep: bool = False,
-                            validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True):
+                            validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -1482,7 +1498,10 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
 
     keep=True: rslf_f2c_run_host -- the run stays on the device and a KeptFineToCoarse comes back; validity_rule
     (F2C_VALID_COMPAT, or F2C_VALID_REFERENCE for validity by C_d under par_use_disp_confidence_score) and keep_volumes apply
-    to this form alone."""
+    to this form alone.
+
+    subgrid (not in the reference): every level's sweep runs in the sub-grid mode (rslf_fine_to_coarse_run_host_sub,
+    rslf_f2c_run_host_sub): the bounds of the coarser levels are tightened from off-grid disparities."""
     ctx = ctx or default_context()
     keep_alive, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
     L = _lib.lib()
@@ -1491,9 +1510,13 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
             raise ValueError("fine_to_coarse_run_host: a kept run hands its levels out itself (KeptFineToCoarse.plane)")
         p, st, h = (parameters or Depth1DParameters()).to_c(), RslfStats(), C.c_void_p()
         ctx.use_current_stream()
-        check(L.rslf_f2c_run_host(ctx._h, ptrs, _ELEM[np.dtype(dt)], V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
-                                  float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
-                                  int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st)), "rslf_f2c_run_host")
+        args = (ctx._h, ptrs, _ELEM[np.dtype(dt)], V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
+                float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
+                int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
+        if subgrid:
+            check(L.rslf_f2c_run_host_sub(*args, 1), "rslf_f2c_run_host_sub")
+        else:
+            check(L.rslf_f2c_run_host(*args), "rslf_f2c_run_host")
         return KeptFineToCoarse(h, ctx, st)
     if validity_rule != F2C_VALID_COMPAT:
         raise ValueError("fine_to_coarse_run_host: validity_rule needs keep=True")
@@ -1517,7 +1540,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
             1 if accept_all_last_scale else 0, out_map.ctypes.data_as(C.c_void_p), out_valid.ctypes.data_as(C.c_void_p),
             C.byref(nl), C.byref(st), int(line_mode), C.byref(lo) if lo is not None else None)
     ctx.use_current_stream()
-    if dt == np.uint16:
+    if subgrid:
+        check(L.rslf_fine_to_coarse_run_host_sub(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1), "rslf_fine_to_coarse_run_host_sub")
+    elif dt == np.uint16:
         check(L.rslf_fine_to_coarse_run_host_u16_lc(ctx._h, ptrs, *rest), "rslf_fine_to_coarse_run_host_u16_lc")
     else:
         check(L.rslf_fine_to_coarse_run_host_lc(ctx._h, ptrs, 1 if dt == np.uint8 else 0, *rest), "rslf_fine_to_coarse_run_host_lc")
@@ -1543,8 +1568,9 @@ class FineToCoarse:
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                 ctx: Context | None = None, line_confidence_mode: int | None = None):
+                 ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        self.m_subgrid = bool(subgrid)   # not in the reference: every level's sweep in the sub-grid mode (Depth2DComputer)
         f2c_line_mode(self.m_parameters, line_confidence_mode, "FineToCoarse")
         ctx = ctx or default_context()
         self.m_computers: list[Depth2DComputer] = []
@@ -1552,7 +1578,7 @@ class FineToCoarse:
         for _, _, par, scale, raw in f2c_pyramid(*f2c_input(epis, ctx), epi_scale_factor, self.m_parameters, max_pyr_depth, ctx,
                                                  line_confidence_mode):
             vol = Volume.from_dense(raw, scale, ctx)
-            self.m_computers.append(Depth2DComputer(vol, d_min, d_max, dim_d, parameters=par))
+            self.m_computers.append(Depth2DComputer(vol, d_min, d_max, dim_d, parameters=par, subgrid=self.m_subgrid))
             self.m_parameter_instances.append(par)
         if accept_all_last_scale:
             self.m_computers[-1].set_accept_all(True)                                              # f2c.hpp:157-158
@@ -1577,7 +1603,7 @@ class FineToCoarse:
                                               comp.m_edge_confidence_mask_s_v_u, comp.m_disp_confidence_s_v_u,
                                               comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u, comp.m_parameters,
                                               scan_mask_s_v_u=comp.m_scan_mask_s_v_u, want_stats=True,
-                                              a_line_confidence_s_v_u=comp.m_line_confidence_s_v_u)
+                                              a_line_confidence_s_v_u=comp.m_line_confidence_s_v_u, subgrid=self.m_subgrid)
 
     def get_results(self):
         """f2c.hpp:302-324 -> (out_map_s_v_u [S,V,U] f32, out_validity_s_v_u [S,V,U] u8) at the finest scale."""
