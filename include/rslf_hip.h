@@ -146,6 +146,8 @@ int rslf_ctx_synchronize(rslf_ctx* ctx);
  *   "claim_skip"     1 (default) the 2-D sweep's claims skip views with nothing left to paint within reach | 0 off
  *   "subgrid_list"   1 (default) a 2-D sweep in the sub-grid mode (rslf_sweep_subgrid) refines a visit whose scan took the packed
  *                    list over that list | 0 every visit refines over the whole plane (k9_subgrid_refine), the same bits
+ *   "peaks_list"     1 (default) a 2-D sweep in the peaks mode (rslf_sweep_peaks) takes the peaks of a visit whose scan took the
+ *                    packed list over that list (k10_peaks_list) | 0 every visit takes the dense form, the same bits
  *   "stream_share"   63-pixel tiles sharing taps between lanes in the streaming kernel: 1 (default) where the samples gathered
  *                    again on every pass are at least a quarter of the views | 0 never | 2 always
  *   "stream_groups"  0 automatic | hypothesis groups per tile of the streaming kernel's dense launches
@@ -329,7 +331,7 @@ int rslf_score_peaks(rslf_ctx* ctx, const float* d_scores_vud, int U, int dim_d,
  * rows go through the context's staging buffer in passes of as many scanlines as its budget holds (at least one; the
  * "staging_kib" hook sets the budget) and never leave the device.  d_out: device planes [n_rows][U]; pixels outside the
  * mask are left untouched.  Everything is queued on the context's stream; it waits only when stats is given.  One device;
- * not inside an open sweep. */
+ * not inside an open sweep (it uses the context's pixel lists; a sweep has rslf_sweep_peaks). */
 int rslf_depth_epi_peaks(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu,
                          float dmin, float dmax, int dim_d, int s_hat, const rslf_params* p,
                          const uint8_t* d_mask_vu, int v_first, int n_rows, const rslf_peaks* d_out, rslf_stats* stats);
@@ -593,6 +595,54 @@ int rslf_depth2d_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, floa
 int rslf_depth2d_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                               float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
                               float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid);
+
+/* ---- runner-up peaks in the 2-D sweep (K10 inside a visit) ----------------- */
+/* The peaks mode is a third state of an open sweep, beside line confidence and the sub-grid mode: valid between
+ * rslf_sweep_begin and the first visit, cleared by rslf_sweep_end.  Not in the reference; it changes no other plane.
+ * d_out_svu: four caller planes [S][V][U] on the device -- idx, score, runner_idx, runner_score, whose meaning is exactly
+ * that of rslf_peaks' fields of the same names above; each may be NULL, not all four.  `disp` is ignored by the visits and
+ * must be NULL: the sub-grid mode already puts that value in the depth plane.  d_out_svu = NULL switches the mode off again.
+ * Setting the mode sizes everything its visits use in the context's grow-only scratch: no visit allocates.  A visit is then
+ *   scan (also writes idx and the winner's score: one arg-max plane for all three modes) -> sub-grid refinement if on ->
+ *   peaks -> the rest of the visit as without the mode
+ * The step is queued at the end of rslf_sweep_visit_scan.  A pixel gets its four values one of two ways:
+ *   - a visit scanned and accepted it (the visit's arg-max plane has idx >= 0): the peaks of its own score row, every score
+ *     the scan's own bits -- idx and score equal the scan's arg max and its score bit for bit;
+ *   - a visit paints it: it takes its source's four values in the apply pass, as C_d and C_l are carried.
+ * Every other pixel keeps what the caller put there (rslf_depth_epi_2d_pk fills nothing; the _run entries below fill
+ * idx = runner_idx = -1 and the floats 0 first, as rslf_depth_epi_peaks_host does for unscanned pixels).
+ * No score row is kept.  A visit whose scan took the packed list of the previous apply pass takes the list form
+ * (k10_peaks_list: a wave per list entry, lanes = hypotheses in rounds of 64, each lane scoring its own hypothesis with the
+ * generic scan's operations in their order, the peak rule across the lanes); every other visit -- the first,
+ * "force_packed" = 0, planes beyond INT32_MAX pixels, "peaks_list" = 0 -- the dense form: the score rows of the plane,
+ * window by window through the context's staging buffer (the "staging_kib" hook sets the budget), reduced by the kernel of
+ * rslf_score_peaks under the mask "this visit's idx >= 0", on pixel lists of the step's own -- the sweep's packed list and
+ * its length are read, never written.  The bits are the same; the cost is not: the list form pays a wave per pixel in the generic
+ * per-hypothesis arithmetic, which wins where the later visits scan a few pixels per scanline (the usual sweep) and loses to
+ * the dense form where they still scan a large share of a view -- on a 960 x 540 field of 100 views whose later visits scan a
+ * quarter of a view each, 1679 ms against 483 ms (profiles/r16_sweep_peaks.md); set "peaks_list" = 0 for such fields.  The
+ * form is chosen on the host, which does not know the list's length.  Line confidence modes 0 / 1 / 2 and the sub-grid mode combine
+ * with the mode: it reads planes they write and writes none of theirs.  With the mode off every entry queues the launches
+ * and writes the bits it always did.  One device; the pyramid and the multi-device forms have no such mode.
+ * RSLF_ERR_INVALID_ARG: a call outside that window, a non-NULL disp, four NULL planes, a sweep begun with dim_d above 2^24
+ * (the limit of rslf_score_peaks); nothing is launched.  The _pk entries below return the same for the same causes. */
+int rslf_sweep_peaks(rslf_ctx* ctx, const rslf_volume* vol, const rslf_peaks* d_out_svu);
+
+/* The _sub entries with a last argument: the four planes (device pointers; for rslf_depth2d_run_host_pk host planes
+ * [S][V][U]).  NULL is the _sub entry, launch for launch. */
+int rslf_depth_epi_2d_pk(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                         float dmin, float dmax, int dim_d,
+                         float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                         float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats,
+                         int line_mode, float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu);
+int rslf_depth2d_run_pk(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                        float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                        float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu,
+                        int subgrid, const rslf_peaks* d_pk_svu);
+int rslf_depth2d_run_host_pk(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                             float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                             float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid,
+                             const rslf_peaks* h_pk_svu);
 
 /* ---- "next" row: fine-to-coarse ---------------------- */
 /* rslf::FineToCoarse<T> (include/rslf_fine_to_coarse.hpp:26-81) is a host-side loop over pyramid

@@ -662,6 +662,21 @@ public:
                       "rslf_multi_depth2d_run_f32");
             return;
         }
+        if (peaks_) {   // every visit in the peaks mode (rslf_sweep_peaks), with or without the other two
+            if (line_mode != RSLF_LINE_CONF_OFF)
+                m_line_confidence_s_v_u.assign(n, 0.f);
+            peaks_s_v_u_.idx.assign(n, -1), peaks_s_v_u_.runner_idx.assign(n, -1);
+            peaks_s_v_u_.score.assign(n, 0.f), peaks_s_v_u_.runner_score.assign(n, 0.f);
+            const rslf_peaks planes = {peaks_s_v_u_.idx.data(), peaks_s_v_u_.score.data(), nullptr, peaks_s_v_u_.runner_idx.data(),
+                                       peaks_s_v_u_.runner_score.data()};
+            check(rslf_depth2d_run_host_pk(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
+                                           m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
+                                           m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
+                                           line_mode != RSLF_LINE_CONF_OFF ? m_line_confidence_s_v_u.data() : nullptr, subgrid_ ? 1 : 0,
+                                           &planes),
+                  "rslf_depth2d_run_host_pk");
+            return;
+        }
         if (subgrid_) {   // every visit in the sub-grid mode (rslf_sweep_subgrid), with or without line confidence
             if (line_mode != RSLF_LINE_CONF_OFF)
                 m_line_confidence_s_v_u.assign(n, 0.f);
@@ -697,6 +712,29 @@ public:
         subgrid_ = on;
     }
     bool get_subgrid() const { return subgrid_; }
+    // Not in the reference: with the mode on, run() also fills, for every view, the winner and the runner-up peak of the score
+    // row of every pixel a visit scanned and accepted, and a painted pixel takes its source's (rslf_sweep_peaks, rslf_hip.h);
+    // a pixel no visit scanned or painted holds -1 / 0.  No other plane changes.  Default off.  One context: an object built
+    // on a MultiContext throws, as Depth1DComputer_pile::get_peaks does.
+    struct Peaks {
+        std::vector<int32_t> idx, runner_idx;      // [S][V][U]
+        std::vector<float> score, runner_score;
+    };
+    void set_peaks(bool on)
+    {
+        if (on && multi_)
+            throw std::invalid_argument("set_peaks: this object was built on a MultiContext: the sweep's peaks are built for one context");
+        peaks_ = on;
+    }
+    const Peaks& get_peaks() const
+    {
+        if (multi_)
+            throw std::invalid_argument("get_peaks: this object was built on a MultiContext: the sweep's peaks are built for one context");
+        if (!peaks_)
+            throw std::invalid_argument("get_peaks: the mode is off: set_peaks(true) before run()");
+        detail::require(!peaks_s_v_u_.idx.empty(), "the getters show the results of run(): call it first");
+        return peaks_s_v_u_;
+    }
     const std::vector<float>& get_depths_s_v_u() const { return m_best_depth_s_v_u; }
 
     // dc.hpp:808-856: the S x U slice of the disparities at scanline a_v (< 0: floor(V / 2.0)) over its own min / max,
@@ -784,6 +822,8 @@ private:
     float m_dmin, m_dmax;
     const Depth1DParameters m_parameters;
     bool subgrid_ = false;   // set_subgrid
+    bool peaks_ = false;     // set_peaks
+    Peaks peaks_s_v_u_;      // filled by run() with the mode on
 };
 
 // rslf::FineToCoarse<DataType> (include/rslf_fine_to_coarse.hpp:26-81): constructor arguments as in the

@@ -56,6 +56,8 @@ SYMBOLS = [
     # ... in the 2-D sweep and fine-to-coarse
     "rslf_sweep_subgrid", "rslf_depth_epi_2d_sub", "rslf_depth2d_run_sub", "rslf_depth2d_run_host_sub",
     "rslf_fine_to_coarse_run_host_sub", "rslf_f2c_run_host_sub", "rslf_f2c_run_subgrid",
+    # runner-up peaks in the 2-D sweep (K10)
+    "rslf_sweep_peaks", "rslf_depth_epi_2d_pk", "rslf_depth2d_run_pk", "rslf_depth2d_run_host_pk",
 ]
 
 
@@ -299,6 +301,10 @@ def lib():
     L.rslf_fine_to_coarse_run_host_sub.argtypes = L.rslf_fine_to_coarse_run_host_lc.argtypes + [ci]   # (elem where is_u8 is: an int too)
     L.rslf_f2c_run_host_sub.argtypes = L.rslf_f2c_run_host.argtypes + [ci]
     L.rslf_f2c_run_subgrid.argtypes = [vp]
+    L.rslf_sweep_peaks.argtypes = [vp, vp, vp]
+    L.rslf_depth_epi_2d_pk.argtypes = L.rslf_depth_epi_2d_sub.argtypes + [vp]
+    L.rslf_depth2d_run_pk.argtypes = L.rslf_depth2d_run_sub.argtypes + [vp]
+    L.rslf_depth2d_run_host_pk.argtypes = L.rslf_depth2d_run_host_sub.argtypes + [vp]
     for name in SYMBOLS:
         f = getattr(L, name)   # AttributeError here = the library does not export the ABI
         if f.restype is C.c_int and name not in ("rslf_abi_version", "rslf_device_count"):

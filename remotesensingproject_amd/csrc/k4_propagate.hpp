@@ -191,12 +191,23 @@ __global__ __launch_bounds__(256) void k34_median_claim(VolView vol, int s_hat, 
 // was its last reader).  s_next < 0: apply only.
 // `dirty` has one byte per 256-column segment of every row, set by the claims: after the first visits most segments hold
 // no claim, and the pass reads the flags (S*V*ceil(U/256) bytes) instead of the winners (4 bytes per cell of the volume).
-// One 256-column segment of row r = s*V + v of the planes.
+// The peaks mode's four [S][V][U] planes (rslf_sweep_peaks), each nullable: a painted pixel takes its source's values from
+// the visited view's planes, as it takes C_d and C_l.  All NULL out of the mode.
+struct ApplyPeaks {
+    int32_t* idx;
+    float* score;
+    int32_t* runner_idx;
+    float* runner_score;
+};
+
+// One 256-column segment of row r = s*V + v of the planes.  PEAKS = false: pk and hat are not read -- the code of a sweep
+// out of the peaks mode is what it was before the mode existed.
+template <bool PEAKS>
 __device__ __forceinline__ void apply_segment(long long r, int seg, int V, int U, const float* __restrict__ filtered_vu,
                                               const float* __restrict__ Cd_hat_vu, float* __restrict__ depth_svu,
                                               float* __restrict__ Cd_svu, uint8_t* mask_svu, int* __restrict__ winner_svu,
                                               int* __restrict__ remain, const float* __restrict__ Cl_hat_vu,
-                                              float* __restrict__ Cl_svu)
+                                              float* __restrict__ Cl_svu, const ApplyPeaks& pk, long long hat)
 {
     const int u = (seg << 8) + threadIdx.x;
     const long long t = r * U + (u < U ? u : U - 1);
@@ -213,6 +224,17 @@ __device__ __forceinline__ void apply_segment(long long r, int seg, int V, int U
     Cd_svu[t] = Cd_hat_vu[src];
     if (Cl_svu)   // core.hpp:1122-1124: the line confidence travels with the disparity (both NULL: not kept)
         Cl_svu[t] = Cl_hat_vu[src];
+    // the source's peaks, at hat + src in the same planes (hat = s_hat * V * U; self-assignments in the visited view, as above)
+    if (PEAKS) {
+        if (pk.idx)
+            pk.idx[t] = pk.idx[hat + src];
+        if (pk.score)
+            pk.score[t] = pk.score[hat + src];
+        if (pk.runner_idx)
+            pk.runner_idx[t] = pk.runner_idx[hat + src];
+        if (pk.runner_score)
+            pk.runner_score[t] = pk.runner_score[hat + src];
+    }
     mask_svu[t] = 0;
     winner_svu[t] = kNoWinner;
 }
@@ -242,16 +264,18 @@ __global__ __launch_bounds__(256) void k4_count_segments(const uint8_t* __restri
 constexpr int kApplyRowsPerBlock = 4;     // rows a workgroup of the general part takes (their flags: one load)
 constexpr int kApplyFlagSlots = 1024;     // >= kApplyRowsPerBlock * ceil(U / 256) for U <= 65536
 
-__global__ __launch_bounds__(256) void k4_propagate_apply(int S, int V, int U, int s_hat, const float* __restrict__ filtered_vu,
+template <bool PEAKS>
+__device__ __forceinline__ void propagate_apply_body(int S, int V, int U, int s_hat, const float* __restrict__ filtered_vu,
                                                          const float* __restrict__ Cd_hat_vu, float* __restrict__ depth_svu,
                                                          float* __restrict__ Cd_svu, uint8_t* mask_svu, int* __restrict__ winner_svu,
                                                          uint8_t* __restrict__ dirty, int s_next, const uint8_t* __restrict__ edge_mask_next_vu,
                                                          int* __restrict__ list, int* __restrict__ count,
                                                          unsigned long long* __restrict__ total, int* __restrict__ packed_n,
                                                          int* __restrict__ remain, int* __restrict__ rowbase,
-                                                         const float* __restrict__ Cl_hat_vu, float* __restrict__ Cl_svu)
+                                                         const float* __restrict__ Cl_hat_vu, float* __restrict__ Cl_svu, const ApplyPeaks& pk)
 {
     __shared__ uint8_t s_flags[kApplyFlagSlots];
+    const long long hat = PEAKS ? (long long)s_hat * V * U : 0;
     const int nseg = (U + 255) >> 8;
     const int lead = s_next >= 0 ? V : 0;       // workgroups [0, lead): the rows of view s_next, one each
     if ((int)blockIdx.x < lead) {
@@ -260,7 +284,7 @@ __global__ __launch_bounds__(256) void k4_propagate_apply(int S, int V, int U, i
         uint8_t* flags = dirty + r * nseg;
         for (int seg = 0; seg < nseg; seg++)
             if (flags[seg])   // the same byte for the whole workgroup
-                apply_segment(r, seg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain, Cl_hat_vu, Cl_svu);
+                apply_segment<PEAKS>(r, seg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain, Cl_hat_vu, Cl_svu, pk, hat);
         __syncthreads();      // every thread has read the flags, and this row's mask writes are the workgroup's own
         if ((int)threadIdx.x < nseg)
             flags[threadIdx.x] = 0;
@@ -286,7 +310,35 @@ __global__ __launch_bounds__(256) void k4_propagate_apply(int S, int V, int U, i
     __syncthreads();
     for (int i = 0; i < nfl; i++)
         if (s_flags[i])
-            apply_segment(r0 + i / nseg, i % nseg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain, Cl_hat_vu, Cl_svu);
+            apply_segment<PEAKS>(r0 + i / nseg, i % nseg, V, U, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, remain, Cl_hat_vu, Cl_svu, pk, hat);
+}
+
+// The kernel of every sweep out of the peaks mode: the argument block and the code it always had.
+__global__ __launch_bounds__(256) void k4_propagate_apply(int S, int V, int U, int s_hat, const float* __restrict__ filtered_vu,
+                                                         const float* __restrict__ Cd_hat_vu, float* __restrict__ depth_svu,
+                                                         float* __restrict__ Cd_svu, uint8_t* mask_svu, int* __restrict__ winner_svu,
+                                                         uint8_t* __restrict__ dirty, int s_next, const uint8_t* __restrict__ edge_mask_next_vu,
+                                                         int* __restrict__ list, int* __restrict__ count,
+                                                         unsigned long long* __restrict__ total, int* __restrict__ packed_n,
+                                                         int* __restrict__ remain, int* __restrict__ rowbase,
+                                                         const float* __restrict__ Cl_hat_vu, float* __restrict__ Cl_svu)
+{
+    propagate_apply_body<false>(S, V, U, s_hat, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, dirty, s_next,
+                                edge_mask_next_vu, list, count, total, packed_n, remain, rowbase, Cl_hat_vu, Cl_svu, ApplyPeaks{});
+}
+
+// ... and of a sweep in the peaks mode (rslf_sweep_peaks): the same pass with the four nullable planes
+__global__ __launch_bounds__(256) void k4_propagate_apply_peaks(int S, int V, int U, int s_hat, const float* __restrict__ filtered_vu,
+                                                               const float* __restrict__ Cd_hat_vu, float* __restrict__ depth_svu,
+                                                               float* __restrict__ Cd_svu, uint8_t* mask_svu, int* __restrict__ winner_svu,
+                                                               uint8_t* __restrict__ dirty, int s_next,
+                                                               const uint8_t* __restrict__ edge_mask_next_vu, int* __restrict__ list,
+                                                               int* __restrict__ count, unsigned long long* __restrict__ total,
+                                                               int* __restrict__ packed_n, int* __restrict__ remain, int* __restrict__ rowbase,
+                                                               const float* __restrict__ Cl_hat_vu, float* __restrict__ Cl_svu, ApplyPeaks pk)
+{
+    propagate_apply_body<true>(S, V, U, s_hat, filtered_vu, Cd_hat_vu, depth_svu, Cd_svu, mask_svu, winner_svu, dirty, s_next,
+                               edge_mask_next_vu, list, count, total, packed_n, remain, rowbase, Cl_hat_vu, Cl_svu, pk);
 }
 
 }  // namespace rslf

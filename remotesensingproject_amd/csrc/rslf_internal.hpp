@@ -8,6 +8,7 @@
 //   rslf_scores.hip       the scan's score matrix as an output: rslf_depth_epi_scores and its host form (k2_scores.hpp)
 //   rslf_peaks.hip        the score rows' consumer: winner, sub-grid disparity and runner-up per pixel (k8_peaks.hpp)
 //   rslf_subgrid.hip      the arg max moved off the grid: the winner's two neighbours re-scored, no row in memory (k9_subgrid.hpp)
+//   rslf_sweep_peaks.hip  the 2-D sweep's peaks mode: winner and runner-up of a visit's scanned pixels, no row kept (k10_sweep_peaks.hpp)
 //   rslf_sweep.hip        the 2-D sweep and its propagation (K4), Depth2DComputer::run
 //   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the one native level loop
 //   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters
@@ -217,6 +218,9 @@ struct Scratch {
     DeviceBuf max_partial;  // float [kMaxPartials]: block maxima of rslf_device_max_f32
     DeviceBuf sub_idx;      // int32 [V*U]: a sub-grid pile step's arg-max plane when the caller passes none (subgrid_planes); a sub-grid sweep's visits' (rslf_sweep_subgrid)
     DeviceBuf sub_score;    // float [V*U]: ... and their score plane
+    DeviceBuf pk_list;      // int [V*U]: per-scanline pixel lists of a peaks sweep's dense step (rslf_sweep_peaks) -- its own: `list` is the scans'
+    DeviceBuf pk_count;     // int [V] + one u64: ... their counts and pixel total (plan::sweep_peaks_count_bytes)
+    DeviceBuf pk_mask;      // u8 [V*U]: ... and the step's mask, "this visit's idx >= 0"
     DeviceBuf row_exact;    // the scan's row-exact table (k2_scan.hpp, ScanArgs::rx_*): [D][slots] offsets, [D][slots] weight pairs, [D] floats, [D] ints; RowExactKey says of what
     // 2-D sweep
     DeviceBuf winner;       // int [S][V][U]: the claims (0x7F7F7F7F between visits)
@@ -283,6 +287,11 @@ struct SweepState {
     // Scratch::sub_idx / sub_score, sized when the mode is set; with line confidence on, the arg-max plane is K7's
     // (Scratch::lc_argmax): one plane for both.
     bool subgrid = false;
+    // peaks mode (rslf_sweep_peaks; k10_sweep_peaks.hpp): state of ONE sweep too.  The caller's four [S][V][U] planes (disp
+    // stays NULL); the visits' arg-max plane is the one above, the dense step's lists Scratch::pk_*.
+    bool peaks = false;
+    rslf_peaks pk = {};
+    int dim_d = 0;              // what rslf_sweep_begin was given: sizes the dense step's staging when the mode is set
 };
 
 }  // namespace rslf
@@ -317,6 +326,7 @@ struct rslf_ctx {
     rslf::RowExactKey row_exact_key;   // what scratch.row_exact holds
     bool last_row_exact = false;       // the last scan's launch was handed the table (rslf_last_scan_row_exact)
     int subgrid_list = 1;      // 2-D sweep in the sub-grid mode: sparse visits refine over the packed list (0: every visit the dense form; A/B and tests)
+    int peaks_list = 1;        // 2-D sweep in the peaks mode: sparse visits take k10_peaks_list over the packed list (0: every visit the dense form; A/B and tests)
     int claim_skip = 1;        // 2-D sweep: the claims skip views with nothing left to paint within reach (0: off, A/B and tests)
     int staging_kib = 0;       // chunked host upload: device staging per pass in KiB (0: plan::kStagingBudget; tests of the later passes)
 };
@@ -448,11 +458,30 @@ int sweep_scan_presize(rslf_ctx* ctx, const rslf_volume* vol, int dim_d, const S
 // context's stream, the scanned pixels left in scratch.pixel_total().  read_pixel_total waits for the stream.
 int check_score_args(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, int dim_d, int s_hat,
                      const rslf_params* p, int v_first, int n_rows, const void* out);
+// own (nullable): pixel lists [V][U], counts [V] and a pixel total that are not the context's -- a peaks sweep's dense step,
+// inside an open sweep whose lists and total are in use (rslf_sweep_peaks.hip).
+struct ScoreLists {
+    int* list;
+    int* count;
+    unsigned long long* total;
+};
 int score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax, int dim_d,
                int s_hat, const rslf_params* p, const uint8_t* d_mask_vu, int v_first, int n_rows, float* d_scores, int* kind_out,
-               int* spad_out);
+               int* spad_out, const ScoreLists* own = nullptr);
 int read_pixel_total(rslf_ctx* ctx, unsigned long long* tot);
 void score_stats(unsigned long long pixels, int dim_d, int kind, int spad, rslf_stats* stats);
+
+// rslf_peaks.hip
+// k8_score_peaks over the pixels of scanlines [v_first, v_first + n_rows) of [V][U] planes (`out`: that window's planes);
+// arguments checked, one launch queued on the context's stream.
+int launch_score_peaks(rslf_ctx* ctx, const float* d_scores, int U, int dim_d, const float* d_dmin_vu, const float* d_dmax_vu, float dmin,
+                       float dmax, const uint8_t* d_mask_vu, int v_first, int n_rows, const rslf_peaks& out);
+
+// rslf_sweep_peaks.hip
+// The peaks step of a visit of an open sweep in the mode (rslf_sweep_peaks), queued after the scan: form is a
+// plan::PeaksForm (0: nothing).  idx_vu: the visit's arg-max plane.  Writes the visited view's planes of ctx->sweep.pk.
+int sweep_peaks_step(rslf_ctx* ctx, const rslf_volume* vol, const float* dmin_vu, const float* dmax_vu, float dmin, float dmax,
+                     int dim_d, int s_hat, const rslf_params* p, const int32_t* idx_vu, int form);
 
 // rslf_subgrid.hip
 // k9_subgrid_refine over a volume's [V][U] planes, arguments already checked (check_scan_args): one launch queued on the
@@ -470,10 +499,12 @@ int depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, 
                 float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats);
 // The same with the line-confidence plane of dc.hpp:721-738, :791-792: line_mode RSLF_LINE_CONF_*, d_Cl_svu [S][V][U]
 // (zero-filled here; NULL with RSLF_LINE_CONF_OFF, which queues exactly the launches of depth2d_run).  subgrid = 1: every
-// visit in the sub-grid mode (rslf_sweep_subgrid).
+// visit in the sub-grid mode (rslf_sweep_subgrid).  d_pk_svu (nullable): the peaks mode's four planes (rslf_sweep_peaks), filled
+// here with idx = runner_idx = -1 and the floats 0.
 int depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
                    int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
-                   float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid = 0);
+                   float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid = 0,
+                   const rslf_peaks* d_pk_svu = nullptr);
 
 // rslf_f2c.hip
 // A volume owned by a scope or an object (rslf_volume_destroy is the one place that frees a slab).

@@ -13,8 +13,8 @@ using namespace rslf;
 static bool any_plane(const rslf_peaks* o) { return o->idx || o->score || o->disp || o->runner_idx || o->runner_score; }
 
 // k8_score_peaks over the pixels of scanlines [v_first, v_first + n_rows) of [V][U] planes; arguments checked
-static int launch_peaks(rslf_ctx* ctx, const float* d_scores, int U, int dim_d, const float* d_dmin_vu, const float* d_dmax_vu, float dmin,
-                        float dmax, const uint8_t* d_mask_vu, int v_first, int n_rows, const rslf_peaks& out)
+int rslf::launch_score_peaks(rslf_ctx* ctx, const float* d_scores, int U, int dim_d, const float* d_dmin_vu, const float* d_dmax_vu,
+                             float dmin, float dmax, const uint8_t* d_mask_vu, int v_first, int n_rows, const rslf_peaks& out)
 {
     PeakArgs a = {};
     a.scores = d_scores;
@@ -79,7 +79,7 @@ extern "C" int rslf_score_peaks(rslf_ctx* ctx, const float* d_scores_vud, int U,
     if (ctx->sweep.open)
         return fail(RSLF_ERR_INVALID_ARG, "a sweep is open on this context");
     HIP_TRY(hipSetDevice(ctx->device));
-    return launch_peaks(ctx, d_scores_vud, U, dim_d, d_dmin_vu, d_dmax_vu, dmin, dmax, d_mask_vu, v_first, n_rows, *d_out);
+    return launch_score_peaks(ctx, d_scores_vud, U, dim_d, d_dmin_vu, d_dmax_vu, dmin, dmax, d_mask_vu, v_first, n_rows, *d_out);
 }
 RSLF_API_CATCH
 
@@ -106,7 +106,7 @@ extern "C" int rslf_depth_epi_peaks(rslf_ctx* ctx, const rslf_volume* vol, const
         const int rows = std::min(pass_rows, n_rows - r0);
         rc = score_rows(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, p, d_mask_vu, v_first + r0, rows, rows_buf, &kind, &spad);
         if (rc == RSLF_OK)
-            rc = launch_peaks(ctx, rows_buf, vol->U, dim_d, d_dmin_vu, d_dmax_vu, dmin, dmax, d_mask_vu, v_first + r0, rows,
+            rc = launch_score_peaks(ctx, rows_buf, vol->U, dim_d, d_dmin_vu, d_dmax_vu, dmin, dmax, d_mask_vu, v_first + r0, rows,
                               planes_at(*d_out, (size_t)r0 * vol->U));
         if (rc)
             return rc;
@@ -169,7 +169,7 @@ extern "C" int rslf_depth_epi_peaks_host(rslf_ctx* ctx, const rslf_volume* vol, 
         HIP_TRY(hipMemsetAsync(planes + 2 * pass_px, 0, 3 * pass_px * sizeof(float), st));   // ... and 0
         rc = score_rows(ctx, vol, d_dmin_vu, d_dmax_vu, dmin, dmax, dim_d, s_hat, p, d_mask, v_first + r0, rows, rows_buf, &kind, &spad);
         if (rc == RSLF_OK)
-            rc = launch_peaks(ctx, rows_buf, vol->U, dim_d, d_dmin_vu, d_dmax_vu, dmin, dmax, d_mask, v_first + r0, rows, d);
+            rc = launch_score_peaks(ctx, rows_buf, vol->U, dim_d, d_dmin_vu, d_dmax_vu, dmin, dmax, d_mask, v_first + r0, rows, d);
         if (rc) {
             (void)hipStreamSynchronize(st);
             return rc;

@@ -64,9 +64,10 @@ int rslf::check_score_args(rslf_ctx* ctx, const rslf_volume* vol, const float* d
 // The rows of scanlines [v_first, v_first + n_rows) into d_scores (that window's [n_rows][U][dim_d]); arguments checked.
 int rslf::score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu, const float* d_dmax_vu, float dmin, float dmax,
                       int dim_d, int s_hat, const rslf_params* p, const uint8_t* d_mask_vu, int v_first, int n_rows, float* d_scores,
-                      int* kind_out, int* spad_out)
+                      int* kind_out, int* spad_out, const ScoreLists* own)
 {
-    int rc = ensure_plane_scratch(ctx, vol->V, vol->U);
+    // (own lists: an open sweep's step -- the context's lists and pixel total are the sweep's, and already sized)
+    int rc = own ? RSLF_OK : ensure_plane_scratch(ctx, vol->V, vol->U);
     if (rc)
         return rc;
     int spad = 0;
@@ -81,15 +82,17 @@ int rslf::score_rows(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_
 
     hipStream_t st = ctx->stream;
     const Scratch& sc = ctx->scratch;
-    HIP_TRY(hipMemsetAsync(sc.pixel_total(), 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_score_lists, dim3(n_rows), dim3(256), 0, st, d_mask_vu, vol->U, v_first, sc.list.as<int>(), sc.count.as<int>(),
-                       sc.pixel_total());
+    int* const list = own ? own->list : sc.list.as<int>();
+    int* const count = own ? own->count : sc.count.as<int>();
+    unsigned long long* const total = own ? own->total : sc.pixel_total();
+    HIP_TRY(hipMemsetAsync(total, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_score_lists, dim3(n_rows), dim3(256), 0, st, d_mask_vu, vol->U, v_first, list, count, total);
     HIP_TRY(hipGetLastError());
 
     ScanArgs a = {};
     a.vol = view_of(vol);
-    a.list = sc.list.as<int>();
-    a.count = sc.count.as<int>();
+    a.list = list;
+    a.count = count;
     a.dmin_vu = d_dmin_vu;
     a.dmax_vu = d_dmax_vu;
     a.dmin = dmin;

@@ -1,8 +1,9 @@
-// librslf_hip.so, unit 6 of 9: the 2-D sweep (Depth2DComputer::run, core.hpp:901-1133) -- one visit per view, scan (unit 2),
-// selective median + claims, apply + the next visit's compaction (K4), and the sweep's line confidence (K7).  C-ABI:
-// include/rslf_hip.h.
+// librslf_hip.so: the 2-D sweep (Depth2DComputer::run, core.hpp:901-1133) -- one visit per view, scan (unit 2),
+// selective median + claims, apply + the next visit's compaction (K4), and the sweep's line confidence (K7).  The peaks mode's
+// step is rslf_sweep_peaks.hip's.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
 #include "rslf_plan_subgrid.hpp"
+#include "rslf_plan_sweep_peaks.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -109,6 +110,7 @@ extern "C" int rslf_sweep_begin(rslf_ctx* ctx, const rslf_volume* vol, const uin
     sw.keep_total = true;
     sw.mask_run = mask_svu;
     sw.expect = plan::sweep_order(S)[0];
+    sw.dim_d = dim_d;
     ctx->sweep = sw;
     return RSLF_OK;
 }
@@ -168,7 +170,7 @@ extern "C" int rslf_sweep_line_confidence(rslf_ctx* ctx, const rslf_volume* vol,
     sw.lc_mode = RSLF_LINE_CONF_OFF;
     sw.lc_Cl_svu = nullptr;
     if (mode == RSLF_LINE_CONF_OFF) {
-        if (sw.subgrid)   // line confidence switched off again after rslf_sweep_subgrid: the visits need an arg-max plane of their own
+        if (sw.subgrid || sw.peaks)   // line confidence switched off again after rslf_sweep_subgrid / _peaks: the visits need an arg-max plane of their own
             HIP_TRY(hip_err(ctx->scratch.sub_idx.reserve(plan::sweep_subgrid_plane_bytes(true, vol->V, vol->U))));
         return RSLF_OK;
     }
@@ -242,8 +244,12 @@ extern "C" int rslf_sweep_visit_scan(rslf_ctx* ctx, const rslf_volume* vol, cons
                                                             ctx->subgrid_list, (long long)n);
     const float* dmin_vu = d_dmin_svu ? d_dmin_svu + (size_t)s_hat * n : nullptr;
     const float* dmax_vu = d_dmax_svu ? d_dmax_svu + (size_t)s_hat * n : nullptr;
-    int32_t* idx_vu = lc ? ctx->sweep.lc_idx_vu : form != plan::kSubgridNone ? ctx->scratch.sub_idx.as<int32_t>() : nullptr;
-    float* score_vu = form != plan::kSubgridNone ? ctx->scratch.sub_score.as<float>() : nullptr;
+    // Peaks mode: the step follows the refinement; it reads the same arg-max plane (one for all three modes).
+    const plan::PeaksForm pk_form = plan::sweep_peaks_form(ctx->sweep.peaks, ctx->sweep.first, ctx->sweep.listed, ctx->peaks_list,
+                                                           (long long)n);
+    const bool keep = form != plan::kSubgridNone || pk_form != plan::kPeaksNone;
+    int32_t* idx_vu = lc ? ctx->sweep.lc_idx_vu : keep ? ctx->scratch.sub_idx.as<int32_t>() : nullptr;
+    float* score_vu = keep ? ctx->scratch.sub_score.as<float>() : nullptr;
     ScanInputs in = visit_inputs(ctx->sweep.first, ctx->sweep.listed);
     in.clear_score = false;   // K9 reads a score only where this scan wrote idx >= 0, and so the score: one fill less a visit
     int rc = depth_epi_scan(ctx, vol, dmin_vu, dmax_vu, dmin, dmax, dim_d, s_hat, d_Ce_svu + (size_t)s_hat * n,
@@ -256,6 +262,10 @@ extern "C" int rslf_sweep_visit_scan(rslf_ctx* ctx, const rslf_volume* vol, cons
     if (!rc && form != plan::kSubgridNone)
         rc = subgrid_refine(ctx, vol, dmin_vu, dmax_vu, dmin, dmax, dim_d, s_hat, p, idx_vu, score_vu, d_depth_svu + (size_t)s_hat * n,
                             nullptr, nullptr, form == plan::kSubgridList);
+    // The peaks of the pixels this visit scanned and accepted, queued here for the same two reasons; the packed list and its
+    // length are read, never written, and the dense form brings lists of its own.
+    if (!rc)
+        rc = sweep_peaks_step(ctx, vol, dmin_vu, dmax_vu, dmin, dmax, dim_d, s_hat, p, idx_vu, pk_form);
     if (rc || !lc)
         return rc;
     ctx->sweep.lc_Ce_svu = d_Ce_svu;
@@ -375,9 +385,19 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
         if (int rc = line_confidence())
             return rc;
     const unsigned apply_blocks = (unsigned)((s_next >= 0 ? V : 0) + ((long long)S * V + kApplyRowsPerBlock - 1) / kApplyRowsPerBlock);
-    hipLaunchKernelGGL(k4_propagate_apply, dim3(apply_blocks), dim3(256), 0, st, S, V, U, s_hat, filtered, Cd, d_depth_svu,
-                       d_Cd_svu, mask_svu, winner, dirty, s_next, s_next >= 0 ? d_Ce_mask_svu + (size_t)s_next * n : nullptr, sc.list.as<int>(),
-                       sc.count.as<int>(), sc.pixel_total(), packed_n, remain, sc.rowbase.as<int>(), Cl, lc_mode ? ctx->sweep.lc_Cl_svu : nullptr);
+    const uint8_t* const next_mask = s_next >= 0 ? d_Ce_mask_svu + (size_t)s_next * n : nullptr;
+    float* const Cl_svu = lc_mode ? ctx->sweep.lc_Cl_svu : nullptr;
+    if (ctx->sweep.peaks) {   // the peaks mode's planes travel with the disparity, as C_d and C_l do: the kernel that takes them
+        const rslf_peaks& pk = ctx->sweep.pk;
+        const ApplyPeaks apk = {pk.idx, pk.score, pk.runner_idx, pk.runner_score};
+        hipLaunchKernelGGL(k4_propagate_apply_peaks, dim3(apply_blocks), dim3(256), 0, st, S, V, U, s_hat, filtered, Cd, d_depth_svu,
+                           d_Cd_svu, mask_svu, winner, dirty, s_next, next_mask, sc.list.as<int>(), sc.count.as<int>(),
+                           sc.pixel_total(), packed_n, remain, sc.rowbase.as<int>(), Cl, Cl_svu, apk);
+    } else {                  // out of the mode: the kernel, the argument block and the code of every sweep before the mode existed
+        hipLaunchKernelGGL(k4_propagate_apply, dim3(apply_blocks), dim3(256), 0, st, S, V, U, s_hat, filtered, Cd, d_depth_svu,
+                           d_Cd_svu, mask_svu, winner, dirty, s_next, next_mask, sc.list.as<int>(), sc.count.as<int>(),
+                           sc.pixel_total(), packed_n, remain, sc.rowbase.as<int>(), Cl, Cl_svu);
+    }
     HIP_TRY(hipGetLastError());
     ctx->sweep.listed = s_next >= 0;
     ctx->sweep.expect = s_after;
@@ -405,7 +425,7 @@ RSLF_API_CATCH
 static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
                         float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                         float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                        float* d_Cl_svu, int subgrid)
+                        float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu = nullptr)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -425,6 +445,8 @@ static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dm
         rc = rslf_sweep_line_confidence(ctx, vol, line_mode, d_Cl_svu);
     if (!rc && subgrid)
         rc = rslf_sweep_subgrid(ctx, vol, 1);
+    if (!rc && d_pk_svu)
+        rc = rslf_sweep_peaks(ctx, vol, d_pk_svu);
     for (int s_hat : plan::sweep_order(vol->S)) {   // core.hpp:981-990
         if (!rc)
             rc = rslf_sweep_visit_scan(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, s_hat, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu,
@@ -472,10 +494,21 @@ extern "C" int rslf_depth_epi_2d_sub(rslf_ctx* ctx, const rslf_volume* vol, cons
 }
 RSLF_API_CATCH
 
+// ... and the peaks mode (rslf_sweep_peaks): d_pk_svu = NULL queues exactly rslf_depth_epi_2d_sub's launches
+extern "C" int rslf_depth_epi_2d_pk(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                                    float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
+                                    float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
+                                    rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu) RSLF_API_TRY
+{
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu);
+}
+RSLF_API_CATCH
+
 int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
                          float dmax, int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
                          float* d_depth_svu, float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                         float* d_Cl_svu, int subgrid)
+                         float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -495,11 +528,17 @@ int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
     HIP_TRY(hipMemsetAsync(d_rbar_svu, 0, n * vol->C * sizeof(float), st));
     if (line_mode != RSLF_LINE_CONF_OFF)
         HIP_TRY(hipMemsetAsync(d_Cl_svu, 0, n * sizeof(float), st));   // dc.hpp:737
+    if (d_pk_svu) {   // pixels no visit scans or paints: no index and 0, as rslf_depth_epi_peaks_host leaves unscanned ones
+        if (d_pk_svu->idx) HIP_TRY(hipMemsetAsync(d_pk_svu->idx, 0xFF, n * sizeof(int32_t), st));
+        if (d_pk_svu->runner_idx) HIP_TRY(hipMemsetAsync(d_pk_svu->runner_idx, 0xFF, n * sizeof(int32_t), st));
+        if (d_pk_svu->score) HIP_TRY(hipMemsetAsync(d_pk_svu->score, 0, n * sizeof(float), st));
+        if (d_pk_svu->runner_score) HIP_TRY(hipMemsetAsync(d_pk_svu->runner_score, 0, n * sizeof(float), st));
+    }
     int rc = rslf_edge_confidence_2d(ctx, vol, p, d_Ce_svu, d_Ce_mask_svu);   // dc.hpp:772
     if (rc)
         return rc;
     return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
-                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid);
+                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu);
 }
 
 int rslf::depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
@@ -539,9 +578,20 @@ extern "C" int rslf_depth2d_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float
 }
 RSLF_API_CATCH
 
+// ... and the peaks mode of every visit (rslf_sweep_peaks); d_pk_svu = NULL queues exactly rslf_depth2d_run_sub's launches
+extern "C" int rslf_depth2d_run_pk(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                   float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
+                                   uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid,
+                                   const rslf_peaks* d_pk_svu) RSLF_API_TRY
+{
+    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                          d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu);
+}
+RSLF_API_CATCH
+
 static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                             float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
-                            rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid)
+                            rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid, const rslf_peaks* h_pk_svu = nullptr)
 {
     if (!ctx || !vol)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -561,11 +611,31 @@ static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, f
     HIP_TRY(mask.alloc(n));
     if (line_mode != RSLF_LINE_CONF_OFF)
         HIP_TRY(Cl.alloc(n * 4));
+    // the peaks mode's planes: a device plane for each one the caller asks for
+    DevBuf pk_buf[4];
+    rslf_peaks d_pk = {};
+    if (h_pk_svu) {
+        if (h_pk_svu->disp)
+            return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_peaks: disp must be NULL (the sub-grid mode puts that value in the depth plane)");
+        const void* want[4] = {h_pk_svu->idx, h_pk_svu->score, h_pk_svu->runner_idx, h_pk_svu->runner_score};
+        for (int i = 0; i < 4; i++)
+            if (want[i])
+                HIP_TRY(pk_buf[i].alloc(n * 4));
+        d_pk.idx = pk_buf[0].as<int32_t>(), d_pk.score = pk_buf[1].as<float>();
+        d_pk.runner_idx = pk_buf[2].as<int32_t>(), d_pk.runner_score = pk_buf[3].as<float>();
+    }
     int rc = depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, Ce.as<float>(), mask.as<uint8_t>(), Cd.as<float>(),
-                            depth.as<float>(), rbar.as<float>(), nullptr, stats, line_mode, Cl.as<float>(), subgrid);
+                            depth.as<float>(), rbar.as<float>(), nullptr, stats, line_mode, Cl.as<float>(), subgrid,
+                            h_pk_svu ? &d_pk : nullptr);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
+    if (h_pk_svu) {
+        void* to[4] = {h_pk_svu->idx, h_pk_svu->score, h_pk_svu->runner_idx, h_pk_svu->runner_score};
+        for (int i = 0; i < 4; i++)
+            if (to[i])
+                HIP_TRY(hipMemcpyAsync(to[i], pk_buf[i].get(), n * 4, hipMemcpyDeviceToHost, st));
+    }
     if (h_Ce_svu) HIP_TRY(hipMemcpyAsync(h_Ce_svu, Ce.get(), n * 4, hipMemcpyDeviceToHost, st));
     if (h_Ce_mask_svu) HIP_TRY(hipMemcpyAsync(h_Ce_mask_svu, mask.get(), n, hipMemcpyDeviceToHost, st));
     if (h_Cd_svu) HIP_TRY(hipMemcpyAsync(h_Cd_svu, Cd.get(), n * 4, hipMemcpyDeviceToHost, st));
@@ -600,5 +670,15 @@ extern "C" int rslf_depth2d_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, 
 {
     return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
                             line_mode, h_Cl_svu, subgrid);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_depth2d_run_host_pk(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                        float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                                        float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid,
+                                        const rslf_peaks* h_pk_svu) RSLF_API_TRY
+{
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
+                            line_mode, h_Cl_svu, subgrid, h_pk_svu);
 }
 RSLF_API_CATCH

@@ -106,6 +106,13 @@ def require_no_subgrid(subgrid, who: str) -> None:
                          "Depth2DComputer, FineToCoarse, fine_to_coarse_run_host and the compute_*_depth_epi functions)" % who)
 
 
+def require_no_peaks(peaks, who: str) -> None:
+    """The peaks mode of the 2-D sweep (DESIGN.md 3 "Sweep peaks") is built for Depth2DComputer and compute_2D_depth_epi on
+    one device; the pyramid and every multi-device form refuse it instead of ignoring it."""
+    if peaks is not None and peaks is not False:
+        raise ValueError("%s: peaks is not built here (one device, one sweep: Depth2DComputer and compute_2D_depth_epi)" % who)
+
+
 class Context:
     """rslf_ctx bound to one GPU; launches go to torch's current stream on it."""
 
@@ -127,7 +134,7 @@ class Context:
 
     _DEBUG_DEFAULTS = dict(force_scan=0, force_groups=0, force_packed=-1, px=-1, stream_share=1, stream_groups=0, stream_lds_kib=80,
                            claim_skip=1, time_all=0, row_split=1, staging_kib=0, tap_table=1, scalar_taps=1,
-                           subgrid_list=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
+                           subgrid_list=1, peaks_list=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
     _FORCE_SCAN = {None: 0, "auto": 0, "generic": 1, "stream": 2}
 
     def set_debug(self, **hooks) -> None:
@@ -587,6 +594,20 @@ def _peak_planes(out: Peaks | None, n_rows: int, U: int, device) -> tuple[Peaks,
     return out, _lib.RslfPeaks(*(None if t is None else t.data_ptr() for t in out))
 
 
+def _sweep_peak_planes(out: "Peaks", S: int, V: int, U: int) -> _lib.RslfPeaks:
+    """The C struct of a sweep's four peak planes [S, V, U] (rslf_sweep_peaks): members may be None, not all; disp must be."""
+    out = Peaks(*out)
+    if out.disp is not None:
+        raise ValueError("peaks.disp must be None: the sub-grid mode puts that value in the depth plane")
+    for name, t in zip(Peaks._fields, out):
+        want = torch.int32 if name.endswith("idx") else torch.float32
+        if t is not None and (tuple(t.shape) != (S, V, U) or t.dtype != want or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError("peaks.%s must be a contiguous %s CUDA tensor of shape %s" % (name, want, (S, V, U)))
+    if all(t is None for t in out):
+        raise ValueError("peaks: all four planes are None, nothing to compute")
+    return _lib.RslfPeaks(*(None if t is None else t.data_ptr() for t in out))
+
+
 def _check_mask_plane(a_mask_v_u, V: int | None, U: int) -> None:
     if a_mask_v_u is not None and (a_mask_v_u.dim() != 2 or a_mask_v_u.shape[1] != U or (V is not None and a_mask_v_u.shape[0] != V)
                                    or a_mask_v_u.dtype != torch.uint8 or not a_mask_v_u.is_contiguous()):
@@ -907,11 +928,12 @@ class MultiDevice:
         return out
 
     def depth2d(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
-                parameters: Depth1DParameters | None = None, subgrid: bool = False) -> dict:
+                parameters: Depth1DParameters | None = None, subgrid: bool = False, peaks=None) -> dict:
         """Depth2DComputer (constructor + run + getters) over this object's devices: the 2-D sweep cut into one block of
         scanlines per device, the neighbours' boundary rows exchanged by peer copy on every visit
         (rslf_multi_depth2d_run_f32 / _u8 / _u16).  Host EPIs in, numpy planes [S, V, U] out."""
         require_no_subgrid(subgrid, "MultiDevice.depth2d")
+        require_no_peaks(peaks, "MultiDevice.depth2d")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((S, V, U), np.float32), edge_mask=np.empty((S, V, U), np.uint8),
                    disp_confidence=np.empty((S, V, U), np.float32), depth=np.empty((S, V, U), np.float32),
@@ -936,10 +958,11 @@ class MultiDevice:
 
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                       subgrid: bool = False):
+                       subgrid: bool = False, peaks=None):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
+        require_no_peaks(peaks, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
@@ -1026,14 +1049,19 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
                          a_best_depth_s_v_u: torch.Tensor, a_rbar_s_v_u: torch.Tensor,
                          a_parameters: Depth1DParameters | None = None, *, scan_mask_s_v_u: torch.Tensor | None = None,
                          want_stats: bool = False, a_line_confidence_s_v_u: torch.Tensor | None = None,
-                         subgrid: bool = False) -> RslfStats | None:
+                         subgrid: bool = False, peaks: "Peaks | None" = None) -> RslfStats | None:
     """core.hpp:336-351.  a_line_confidence_s_v_u ([S,V,U] f32, pass zeros) is the argument of the
     _USE_LINE_CONFIDENCE_SCORE build (:345): with it the call goes through rslf_depth_epi_2d_lc in
     a_parameters.par_line_confidence_mode -- mode 0 is then the default build and leaves the plane untouched; modes 1 and 2
     need the plane (without it the library returns RSLF_ERR_INVALID_ARG).
     a_dmin_s_v_u / a_dmax_s_v_u: [S,V,U] f32 CUDA tensors or Python floats.
     subgrid (not in the reference): every visit moves the disparities its scan wrote off the hypothesis grid before the
-    median and the propagation read them (rslf_depth_epi_2d_sub)."""
+    median and the propagation read them (rslf_depth_epi_2d_sub).
+    peaks (not in the reference): a Peaks of [S,V,U] planes (idx / runner_idx int32, score / runner_score f32, disp None;
+    members may be None) -- every pixel a visit scans and accepts gets the winner and the runner-up peak of its score row,
+    every pixel a visit paints its source's; the others keep what the planes held (rslf_depth_epi_2d_pk).  a_dim_d above
+    2 ** 24 is refused.  Where the later visits still scan a large share of a view, Context.set_debug(peaks_list=0) is the
+    faster form (include/rslf_hip.h, rslf_sweep_peaks)."""
     par = a_parameters or Depth1DParameters()
     p = par.to_c()
     planes = isinstance(a_dmin_s_v_u, torch.Tensor)
@@ -1045,7 +1073,11 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
             _ptr(a_best_depth_s_v_u), _ptr(a_rbar_s_v_u), C.byref(p), _ptr(scan_mask_s_v_u),
             C.byref(st) if st is not None else None)
     mode = int(par.par_line_confidence_mode)
-    if subgrid:
+    if peaks is not None:
+        c_pk = _sweep_peak_planes(peaks, vol.S, vol.V, vol.U)
+        check(_lib.lib().rslf_depth_epi_2d_pk(*args, mode, _ptr(a_line_confidence_s_v_u), 1 if subgrid else 0, C.byref(c_pk)),
+              "rslf_depth_epi_2d_pk")
+    elif subgrid:
         check(_lib.lib().rslf_depth_epi_2d_sub(*args, mode, _ptr(a_line_confidence_s_v_u), 1), "rslf_depth_epi_2d_sub")
     elif a_line_confidence_s_v_u is None and mode == LINE_CONF_OFF:
         check(_lib.lib().rslf_depth_epi_2d(*args), "rslf_depth_epi_2d")
@@ -1060,8 +1092,12 @@ class Depth2DComputer:
 
     def __init__(self, epis, dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, verbose: bool = False, ctx: Context | None = None,
-                 subgrid: bool = False):
+                 subgrid: bool = False, peaks: bool = False):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        # not in the reference: run() also fills the winner and the runner-up peak of every scanned or painted pixel
+        # (rslf_sweep_peaks; get_peaks_s_v_u)
+        self.m_peaks = bool(peaks)
+        self.m_peaks_s_v_u: Peaks | None = None
         # not in the reference: every visit's disparities are moved off the hypothesis grid before the median and the
         # propagation (rslf_sweep_subgrid); every getter then shows refined planes
         self.m_subgrid = bool(subgrid)
@@ -1108,7 +1144,15 @@ class Depth2DComputer:
         mode = self._line_mode()
         if mode != LINE_CONF_OFF and self.m_line_confidence_s_v_u is None:   # the mode was set after the constructor ran
             self.m_line_confidence_s_v_u = torch.empty_like(self.m_edge_confidence_s_v_u)
-        if self.m_subgrid:
+        if self.m_peaks:
+            shape, dev = tuple(self.m_edge_confidence_s_v_u.shape), vol.ctx.device
+            self.m_peaks_s_v_u = Peaks(torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev),
+                                       None, torch.empty(shape, dtype=torch.int32, device=dev),
+                                       torch.empty(shape, dtype=torch.float32, device=dev))
+            c_pk = _sweep_peak_planes(self.m_peaks_s_v_u, *shape)
+            check(_lib.lib().rslf_depth2d_run_pk(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1 if self.m_subgrid else 0,
+                                                 C.byref(c_pk)), "rslf_depth2d_run_pk")
+        elif self.m_subgrid:
             check(_lib.lib().rslf_depth2d_run_sub(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1), "rslf_depth2d_run_sub")
         elif mode == LINE_CONF_OFF:
             check(_lib.lib().rslf_depth2d_run(*args), "rslf_depth2d_run")
@@ -1122,6 +1166,17 @@ class Depth2DComputer:
 
     def get_depths_s_v_u(self) -> torch.Tensor:
         return self.m_best_depth_s_v_u
+
+    def get_peaks_s_v_u(self) -> Peaks:
+        """Not in the reference: after run() with peaks=True, the Peaks of [S,V,U] planes on the device -- idx / score (the
+        scan's arg max and its score), runner_idx / runner_score (-1 / 0 without another candidate); disp is None.  A pixel no
+        visit scanned or painted holds -1 / 0.  (run() refuses dim_d above 2 ** 24 with the mode on; for fields whose later
+        visits still scan a large share of a view, Context.set_debug(peaks_list=0) is the faster form.)"""
+        if not self.m_peaks:
+            raise ValueError("get_peaks_s_v_u: this object was built without peaks=True")
+        if self.m_peaks_s_v_u is None:
+            raise ValueError("get_peaks_s_v_u: run() first")
+        return self.m_peaks_s_v_u
 
     def set_accept_all(self, b: bool) -> None:
         self.m_accept_all = bool(b)
@@ -1188,6 +1243,10 @@ class Depth2DComputer:
                    scan_mask=self.m_scan_mask_s_v_u.cpu().numpy())
         if self.m_line_confidence_s_v_u is not None:
             out["line_confidence"] = self.m_line_confidence_s_v_u.cpu().numpy()
+        if self.m_peaks and self.m_peaks_s_v_u is not None:
+            pk = self.m_peaks_s_v_u
+            out.update(peak_idx=pk.idx.cpu().numpy(), peak_score=pk.score.cpu().numpy(),
+                       peak_runner_idx=pk.runner_idx.cpu().numpy(), peak_runner_score=pk.runner_score.cpu().numpy())
         return out
 
 
@@ -1490,7 +1549,7 @@ class KeptFineToCoarse:
 def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                             parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                             ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False, keep: bool = False,
-                            validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False):
+                            validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -1502,6 +1561,7 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
 
     subgrid (not in the reference): every level's sweep runs in the sub-grid mode (rslf_fine_to_coarse_run_host_sub,
     rslf_f2c_run_host_sub): the bounds of the coarser levels are tightened from off-grid disparities."""
+    require_no_peaks(peaks, "fine_to_coarse_run_host")   # (the pyramid's levels carry no peak planes)
     ctx = ctx or default_context()
     keep_alive, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
     L = _lib.lib()
@@ -1568,7 +1628,8 @@ class FineToCoarse:
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                 ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False):
+                 ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None):
+        require_no_peaks(peaks, "FineToCoarse")   # (the pyramid's levels carry no peak planes)
         self.m_parameters = parameters or Depth1DParameters.get_default()
         self.m_subgrid = bool(subgrid)   # not in the reference: every level's sweep in the sub-grid mode (Depth2DComputer)
         f2c_line_mode(self.m_parameters, line_confidence_mode, "FineToCoarse")
