@@ -623,7 +623,8 @@ int rslf_depth2d_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin,
  * quarter of a view each, 1679 ms against 483 ms (profiles/r16_sweep_peaks.md); set "peaks_list" = 0 for such fields.  The
  * form is chosen on the host, which does not know the list's length.  Line confidence modes 0 / 1 / 2 and the sub-grid mode combine
  * with the mode: it reads planes they write and writes none of theirs.  With the mode off every entry queues the launches
- * and writes the bits it always did.  One device; the pyramid and the multi-device forms have no such mode.
+ * and writes the bits it always did.  One device; a kept fine-to-coarse run has the mode per level (rslf_f2c_run_host_pk), the
+ * host-planes pyramid entries and the multi-device forms have none.
  * RSLF_ERR_INVALID_ARG: a call outside that window, a non-NULL disp, four NULL planes, a sweep begun with dim_d above 2^24
  * (the limit of rslf_score_peaks); nothing is launched.  The _pk entries below return the same for the same causes. */
 int rslf_sweep_peaks(rslf_ctx* ctx, const rslf_volume* vol, const rslf_peaks* d_out_svu);
@@ -759,7 +760,8 @@ typedef struct rslf_f2c_run rslf_f2c_run;
 #define RSLF_F2C_VALID_REFERENCE 1
 
 /* The planes of a kept run, [S][V_l][U_l] of level l (float32; VALID and FUSED_VALID bytes 0 / 255).  The fused planes are
- * at the finest size and are asked for with level 0.  CL is held in modes AS_BUILT and GATE only. */
+ * at the finest size and are asked for with level 0.  CL is held in modes AS_BUILT and GATE only.  (Planes 7 .. 15: the peak
+ * planes of rslf_f2c_run_host_pk below.) */
 #define RSLF_F2C_PLANE_DEPTH       0
 #define RSLF_F2C_PLANE_VALID       1
 #define RSLF_F2C_PLANE_CE          2
@@ -846,6 +848,62 @@ int rslf_f2c_run_render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, i
                                 uint8_t* const* d_bgr_out);
 int rslf_f2c_run_render_epi_pyr_host(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, const uint8_t* lut_bgr,
                                      uint8_t* const* h_bgr_out);
+
+/* ---- a kept run's peaks per level and validity by uniqueness (K11) ---------- */
+/* Two options of a kept run, both off by default, neither in the reference, one device only.
+ *
+ * peaks = 1: every level's sweep runs in the peaks mode as well (rslf_sweep_peaks above, through the one level loop), and the
+ * run keeps four more planes [S][V_p][U_p] per level -- idx, score, runner_idx, runner_score, with the meaning they have
+ * there; -1 / 0 where no visit scanned or painted a pixel.  With subgrid = 1 both modes run; `disp` stays in the depth plane.
+ * The run also keeps the FUSED peaks at the finest size: four planes [S][V_0][U_0] and a uint8 plane fused_level.  For
+ * every pixel of the fused map, fused_level is the level that decided it and the fused peaks are the peaks of the pixel of
+ * that level it was taken from.  "Decided" follows the fusion's own mask chain (the INTER_NEAREST upscaling of the running
+ * mask, rslf_f2c_fuse): at level p and pixel (y, x), a non-zero validity byte makes that pixel the origin; else the walk goes
+ * on at level p + 1, pixel (min(floor(y * (1 / (V_p / V_{p+1}))), V_{p+1} - 1), min(floor(x * (1 / (U_p / U_{p+1}))),
+ * U_{p+1} - 1)), scale and product in double.  No valid pixel on the walk: fused_level = 255, idx = runner_idx = -1, the
+ * scores 0 -- and the fused validity is 0 there: it is the same chain.  NOTE: the fused DISPARITY of a pixel decided by a
+ * coarser level is a bilinear blend of that level's running map followed by the 3 x 3 median; the fused peaks describe the
+ * NEAREST pixel of the deciding level, not that blend.  A level accepted whole (accept_all_last_scale) is valid where it
+ * has no peaks: such pixels hold -1 / 0 under that level's number.
+ *
+ * uniqueness_ratio = r in (0, 1] (0: off; needs peaks = 1): after a level's sweep and its validity rule (either
+ * RSLF_F2C_VALID_*, any line mode), a pixel becomes invalid if
+ *     idx >= 0 && runner_idx >= 0 && runner_score > r * score        (the product one binary32 multiply)
+ * and keeps what the rule gave otherwise; the level accept_all_last_scale accepts whole is not touched.  The plane then
+ * tightens the next level's ranges and feeds the fusion as ever: an ambiguous pixel of a fine level is decided by a coarser
+ * one.  With both options off the entry queues the launches and writes the bits of rslf_f2c_run_host_sub.
+ * RSLF_ERR_INVALID_ARG, before anything is queued, with the argument named in rslf_last_error(): peaks outside 0 / 1; a
+ * uniqueness_ratio below 0, above 1 or NaN; a ratio without peaks; with peaks, dim_d above 2^24 (rslf_sweep_peaks' limit). */
+int rslf_f2c_run_host_pk(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                         int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                         rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio);
+/* The options read back from a run: 0 for NULL and for a run made without them (rslf_f2c_run_desc keeps its size). */
+int rslf_f2c_run_peaks(const rslf_f2c_run* run);
+float rslf_f2c_run_uniqueness(const rslf_f2c_run* run);
+/* More planes for rslf_f2c_run_copy, reported as bits of planes_held like the others (a run without peaks keeps the bits it
+ * had).  PK_*: int32 / float32 [S][V_l][U_l] of any level.  FUSED_PK_* and FUSED_LEVEL (uint8): the finest size, asked for
+ * with level 0.  Asked of a run that holds none: RSLF_ERR_INVALID_ARG, `which` named. */
+#define RSLF_F2C_PLANE_PK_IDX                 7
+#define RSLF_F2C_PLANE_PK_SCORE               8
+#define RSLF_F2C_PLANE_PK_RUNNER_IDX          9
+#define RSLF_F2C_PLANE_PK_RUNNER_SCORE       10
+#define RSLF_F2C_PLANE_FUSED_PK_IDX          11
+#define RSLF_F2C_PLANE_FUSED_PK_SCORE        12
+#define RSLF_F2C_PLANE_FUSED_PK_RUNNER_IDX   13
+#define RSLF_F2C_PLANE_FUSED_PK_RUNNER_SCORE 14
+#define RSLF_F2C_PLANE_FUSED_LEVEL           15
+/* The two steps as device-pointer primitives, beside rslf_f2c_tighten_bounds and rslf_f2c_fuse: enqueued on the context's
+ * stream, not awaited.
+ * rslf_f2c_unique_mask: the predicate above in place on n validity bytes; d_pk: idx, score, runner_idx, runner_score of n
+ * entries each (disp is ignored); ratio in (0, 1].  Bytes that are 0 stay 0 and their peaks are not read.
+ * rslf_f2c_fuse_peaks: the walk above over a pyramid of P levels (1 .. RSLF_F2C_MAX_LEVELS), finest first, in one launch:
+ * d_valid[p] and the four planes of d_pk[p] are [S][Vp[p]][Up[p]] (all required; disp ignored); d_out_svu's four planes and
+ * d_out_level_svu are [S][Vp[0]][Up[0]], each nullable, not all five.  Any level sizes >= 1 are safe: every index of the
+ * walk is clamped into its plane. */
+int rslf_f2c_unique_mask(rslf_ctx* ctx, uint8_t* d_valid, const rslf_peaks* d_pk, float ratio, size_t n);
+int rslf_f2c_fuse_peaks(rslf_ctx* ctx, const uint8_t* const* d_valid, const rslf_peaks* d_pk, const int* Vp, const int* Up,
+                        int P, int S, const rslf_peaks* d_out_svu, uint8_t* d_out_level_svu);
 
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit

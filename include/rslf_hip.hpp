@@ -922,6 +922,54 @@ public:
         subgrid_ = on;
     }
     bool get_subgrid() const { return subgrid_; }
+    // Not in the reference, to be called before run() and after keep_on_device: every level's sweep also runs in the peaks
+    // mode (rslf_sweep_peaks) and the kept run holds every level's peak planes and the fused peaks (rslf_f2c_run_host_pk).
+    // One device only: throws on a MultiContext.
+    struct Peaks {
+        std::vector<int32_t> idx, runner_idx;      // [S][V_p][U_p]
+        std::vector<float> score, runner_score;
+    };
+    void set_peaks(bool on)
+    {
+        if (multi_)
+            throw std::invalid_argument("set_peaks: this object was built on a MultiContext: the pyramid's peaks are built for one context");
+        detail::require(keep_, "FineToCoarse: the peak planes belong to a kept run: call keep_on_device first");
+        peaks_ = on;
+    }
+    bool get_peaks_mode() const { return peaks_; }
+    // ... and validity by uniqueness: ratio in (0, 1], 0 switches it off.  A level's valid pixels whose runner-up scores more
+    // than ratio * the winner's score become invalid (the level accept_all_last_scale accepts whole apart), so the next
+    // level's ranges and the fusion leave them to a coarser level.  Needs set_peaks(true) by the time run() is called.
+    void set_uniqueness_ratio(float ratio)
+    {
+        if (multi_)
+            throw std::invalid_argument("set_uniqueness_ratio: this object was built on a MultiContext: the pyramid's peaks are built for one context");
+        detail::require(keep_, "FineToCoarse: the uniqueness ratio belongs to a kept run: call keep_on_device first");
+        detail::require(ratio >= 0.f && ratio <= 1.f, "uniqueness ratio: 0 (off) or a ratio in (0, 1]");
+        uniqueness_ = ratio;
+    }
+    float get_uniqueness_ratio() const { return uniqueness_; }
+    // After run() with set_peaks(true): a level's four planes; the fused peaks at the finest size -- for every pixel of the
+    // fused map the peaks of the pixel of the deciding level it was taken from (the NEAREST pixel down the fusion's mask
+    // chain, not the bilinear blend and median the fused disparity went through); and the level that decided it (255: none).
+    Peaks get_level_peaks(int level) const
+    {
+        detail::require(run_ != nullptr && peaks_held_, "get_level_peaks: the peak planes are held by a kept run made with set_peaks(true)");
+        detail::require(level >= 0 && level < (int)dims_.size(), "get_level_peaks: the level is not in the pyramid");
+        return copy_peaks(level, (size_t)dim_s_ * dims_[level].first * dims_[level].second, RSLF_F2C_PLANE_PK_IDX);
+    }
+    Peaks get_fused_peaks() const
+    {
+        detail::require(run_ != nullptr && peaks_held_, "get_fused_peaks: the peak planes are held by a kept run made with set_peaks(true)");
+        return copy_peaks(0, (size_t)dim_s_ * dim_v_ * dim_u_, RSLF_F2C_PLANE_FUSED_PK_IDX);
+    }
+    std::vector<uint8_t> get_fused_level() const
+    {
+        detail::require(run_ != nullptr && peaks_held_, "get_fused_level: the peak planes are held by a kept run made with set_peaks(true)");
+        std::vector<uint8_t> out((size_t)dim_s_ * dim_v_ * dim_u_);
+        check(rslf_f2c_run_copy(run_, 0, RSLF_F2C_PLANE_FUSED_LEVEL, out.data(), 1, nullptr), "rslf_f2c_run_copy");
+        return out;
+    }
     ~FineToCoarse() { rslf_f2c_run_destroy(run_); }
     FineToCoarse(const FineToCoarse&) = delete;
     FineToCoarse& operator=(const FineToCoarse&) = delete;
@@ -1094,7 +1142,15 @@ private:
         disp_confidence_pyr_.clear();
         dims_.clear();
         const int elem = type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32;
-        if (subgrid_)
+        peaks_held_ = false;
+        detail::require(peaks_ || uniqueness_ == 0.f, "FineToCoarse: the uniqueness ratio reads the peak planes: call set_peaks(true)");
+        if (peaks_) {
+            check(rslf_f2c_run_host_pk(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
+                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
+                                       validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, 1, uniqueness_),
+                  "rslf_f2c_run_host_pk");
+            peaks_held_ = true;
+        } else if (subgrid_)
             check(rslf_f2c_run_host_sub(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
                                         scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
                                         validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, 1),
@@ -1109,6 +1165,17 @@ private:
         n_levels_ = d.n_levels;
         for (int l = 0; l < d.n_levels; l++)
             dims_.push_back(std::make_pair(d.V[l], d.U[l]));
+    }
+    // four peak planes of a kept run, RSLF_F2C_PLANE_PK_* or _FUSED_PK_* counted from `first`
+    Peaks copy_peaks(int level, size_t n, int first) const
+    {
+        Peaks out;
+        out.idx.resize(n), out.score.resize(n), out.runner_idx.resize(n), out.runner_score.resize(n);
+        check(rslf_f2c_run_copy(run_, level, first, out.idx.data(), 1, nullptr), "rslf_f2c_run_copy");
+        check(rslf_f2c_run_copy(run_, level, first + 1, out.score.data(), 1, nullptr), "rslf_f2c_run_copy");
+        check(rslf_f2c_run_copy(run_, level, first + 2, out.runner_idx.data(), 1, nullptr), "rslf_f2c_run_copy");
+        check(rslf_f2c_run_copy(run_, level, first + 3, out.runner_score.data(), 1, nullptr), "rslf_f2c_run_copy");
+        return out;
     }
     // one kind of plane of every level of a kept run, copied out when first asked for; without a kept run, what run() left
     template <typename T>
@@ -1217,6 +1284,9 @@ private:
     mutable std::vector<std::vector<uint8_t> > validity_pyr_;
     bool keep_, keep_volumes_;   // keep_on_device
     bool subgrid_ = false;       // set_subgrid
+    bool peaks_ = false;         // set_peaks
+    float uniqueness_ = 0.f;     // set_uniqueness_ratio
+    bool peaks_held_ = false;    // the kept run was made with peaks
     int validity_rule_;
     rslf_f2c_run* run_;          // the kept run, owned
 };

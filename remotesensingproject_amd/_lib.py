@@ -58,6 +58,8 @@ SYMBOLS = [
     "rslf_fine_to_coarse_run_host_sub", "rslf_f2c_run_host_sub", "rslf_f2c_run_subgrid",
     # runner-up peaks in the 2-D sweep (K10)
     "rslf_sweep_peaks", "rslf_depth_epi_2d_pk", "rslf_depth2d_run_pk", "rslf_depth2d_run_host_pk",
+    # a kept fine-to-coarse run's peaks per level and validity by uniqueness (K11)
+    "rslf_f2c_run_host_pk", "rslf_f2c_run_peaks", "rslf_f2c_run_uniqueness", "rslf_f2c_unique_mask", "rslf_f2c_fuse_peaks",
 ]
 
 
@@ -305,6 +307,12 @@ def lib():
     L.rslf_depth_epi_2d_pk.argtypes = L.rslf_depth_epi_2d_sub.argtypes + [vp]
     L.rslf_depth2d_run_pk.argtypes = L.rslf_depth2d_run_sub.argtypes + [vp]
     L.rslf_depth2d_run_host_pk.argtypes = L.rslf_depth2d_run_host_sub.argtypes + [vp]
+    L.rslf_f2c_run_host_pk.argtypes = L.rslf_f2c_run_host_sub.argtypes + [ci, cf]
+    L.rslf_f2c_run_peaks.argtypes = [vp]
+    L.rslf_f2c_run_uniqueness.argtypes = [vp]
+    L.rslf_f2c_run_uniqueness.restype = cf
+    L.rslf_f2c_unique_mask.argtypes = [vp, vp, C.POINTER(RslfPeaks), cf, C.c_size_t]
+    L.rslf_f2c_fuse_peaks.argtypes = [vp, C.POINTER(vp), C.POINTER(RslfPeaks), C.POINTER(ci), C.POINTER(ci), ci, ci, C.POINTER(RslfPeaks), vp]
     for name in SYMBOLS:
         f = getattr(L, name)   # AttributeError here = the library does not export the ABI
         if f.restype is C.c_int and name not in ("rslf_abi_version", "rslf_device_count"):

@@ -2,6 +2,7 @@
 // the pyramid (Gaussian blur + halving), the bound tightening, the fusion (K5) and the native level loop, whose one-context
 // form is here and whose multi-device form is in rslf_multi_sweep.hip.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
+#include "rslf_plan_f2c_peaks.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -352,6 +353,18 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         HIP_TRY(kl.valid.alloc(n));
         if (keep)
             HIP_TRY(kl.Cd.alloc(n * 4));
+        rslf_peaks pk = {};
+        if (K.peaks) {   // the level's sweep fills them with -1 / 0 before its first visit (depth2d_run_lc)
+            HIP_TRY(kl.pk_idx.alloc(n * 4));
+            HIP_TRY(kl.pk_score.alloc(n * 4));
+            HIP_TRY(kl.pk_runner_idx.alloc(n * 4));
+            HIP_TRY(kl.pk_runner_score.alloc(n * 4));
+            pk.idx = kl.pk_idx.as<int32_t>();
+            pk.score = kl.pk_score.as<float>();
+            pk.runner_idx = kl.pk_runner_idx.as<int32_t>();
+            pk.runner_score = kl.pk_runner_score.as<float>();
+            lv.peaks = &pk;
+        }
         if (l > 0) {
             HIP_TRY(dmin.alloc(n * 4));
             HIP_TRY(dmax.alloc(n * 4));
@@ -380,8 +393,9 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         pixels += st1.pixels_scanned;
         // get_valid_depths_mask_s_v_u (dc.hpp:893-915), asked for by the next level's bounds (f2c.hpp:185-186) and by the
         // fusion (:312): the last level accepts everything when asked to (f2c.hpp:157-158)
-        switch (plan::f2c_validity_by_rule(accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0, line_mode,
-                                           validity_rule)) {
+        const plan::F2cValidity by = plan::f2c_validity_by_rule(accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0,
+                                                                line_mode, validity_rule);
+        switch (by) {
         case plan::kValidAll:
             rc = f2c_valid_mask(st, Ce.as<const float>(), kl.valid.as<uint8_t>(), n, -1.0f);
             break;
@@ -395,6 +409,9 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             rc = f2c_valid_mask(st, kl.Cd.as<const float>(), kl.valid.as<uint8_t>(), n, p->disp_score_threshold);
             break;
         }
+        // validity by uniqueness: what the rule left valid goes invalid where the runner-up is within the ratio of the winner
+        if (!rc && K.peaks && plan::f2c_unique_applies(K.uniqueness, by))
+            rc = rslf_f2c_unique_mask(ctx, kl.valid.as<uint8_t>(), &pk, K.uniqueness, n);
         if (rc)
             return rc;
         if (levels_out) {   // host copies of the level's planes; C_e and C_l leave the device with this iteration
@@ -431,6 +448,24 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     rc = rslf_f2c_fuse(ctx, dp.data(), vp.data(), Vp.data(), Up.data(), P, S, omap.as<float>(), ovalid.as<uint8_t>());
     if (rc)
         return rc;
+    if (K.peaks) {   // which level decided each fused pixel, and that level's peaks there: one launch over the whole pyramid
+        std::vector<rslf_peaks> pp((size_t)P);
+        for (int l = 0; l < P; l++) {
+            F2cKeptLevel& kl = K.levels[(size_t)l];
+            pp[(size_t)l] = rslf_peaks{kl.pk_idx.as<int32_t>(), kl.pk_score.as<float>(), nullptr, kl.pk_runner_idx.as<int32_t>(),
+                                       kl.pk_runner_score.as<float>()};
+        }
+        HIP_TRY(K.fused_pk_idx.alloc(n0 * 4));
+        HIP_TRY(K.fused_pk_score.alloc(n0 * 4));
+        HIP_TRY(K.fused_pk_runner_idx.alloc(n0 * 4));
+        HIP_TRY(K.fused_pk_runner_score.alloc(n0 * 4));
+        HIP_TRY(K.fused_level.alloc(n0));
+        const rslf_peaks fused = {K.fused_pk_idx.as<int32_t>(), K.fused_pk_score.as<float>(), nullptr,
+                                  K.fused_pk_runner_idx.as<int32_t>(), K.fused_pk_runner_score.as<float>()};
+        rc = rslf_f2c_fuse_peaks(ctx, vp.data(), pp.data(), Vp.data(), Up.data(), P, S, &fused, K.fused_level.as<uint8_t>());
+        if (rc)
+            return rc;
+    }
     if (h_out_map_svu)
         HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.get(), n0 * 4, hipMemcpyDeviceToHost, st));
     if (h_out_valid_svu)
@@ -473,7 +508,7 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const
         if (!rc)
             rc = depth2d_run_lc(ctx, vol.get(), lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, mask.as<uint8_t>(),
                                 lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(), nullptr, level_stats,
-                                lv.line_mode, lv.Cl_svu, subgrid);
+                                lv.line_mode, lv.Cl_svu, subgrid, lv.peaks);
         if (!rc && lv.vol_out)
             *lv.vol_out = std::move(vol);   // kept; otherwise destroyed here, with the sweep's other planes
         return rc;

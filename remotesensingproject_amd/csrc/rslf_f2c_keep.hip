@@ -2,6 +2,7 @@
 // owns what the level loop of rslf_f2c.hip allocates (F2cKept), hands planes out by copy, and renders the three coloured
 // getters of rslf_fine_to_coarse.hpp:325-519 from them with the renderers of rslf_render.hip.  No kernels of its own.
 #include "rslf_internal.hpp"
+#include "rslf_plan_f2c_peaks.hpp"
 
 using namespace rslf;
 
@@ -21,6 +22,12 @@ int elem_of(int elem, Elem* out)
         return RSLF_OK;
     }
     return fail(RSLF_ERR_INVALID_ARG, "element type %d: RSLF_ELEM_F32, _U8 or _U16", elem);
+}
+
+bool is_peak_plane(int which) { return which >= RSLF_F2C_PLANE_PK_IDX && which <= RSLF_F2C_PLANE_FUSED_LEVEL; }
+bool is_fused_plane(int which)
+{
+    return which == RSLF_F2C_PLANE_FUSED_MAP || which == RSLF_F2C_PLANE_FUSED_VALID || which >= RSLF_F2C_PLANE_FUSED_PK_IDX;
 }
 
 // A plane of the run: where it lies and how many bytes it has; NULL if it is not held.
@@ -46,6 +53,25 @@ const void* plane_of(const rslf_f2c_run* run, int level, int which, size_t* byte
     case RSLF_F2C_PLANE_FUSED_VALID:
         *bytes = n;
         return run->kept.fused_valid.get();
+    case RSLF_F2C_PLANE_PK_IDX:
+        return kl.pk_idx.get();
+    case RSLF_F2C_PLANE_PK_SCORE:
+        return kl.pk_score.get();
+    case RSLF_F2C_PLANE_PK_RUNNER_IDX:
+        return kl.pk_runner_idx.get();
+    case RSLF_F2C_PLANE_PK_RUNNER_SCORE:
+        return kl.pk_runner_score.get();
+    case RSLF_F2C_PLANE_FUSED_PK_IDX:
+        return run->kept.fused_pk_idx.get();
+    case RSLF_F2C_PLANE_FUSED_PK_SCORE:
+        return run->kept.fused_pk_score.get();
+    case RSLF_F2C_PLANE_FUSED_PK_RUNNER_IDX:
+        return run->kept.fused_pk_runner_idx.get();
+    case RSLF_F2C_PLANE_FUSED_PK_RUNNER_SCORE:
+        return run->kept.fused_pk_runner_score.get();
+    case RSLF_F2C_PLANE_FUSED_LEVEL:
+        *bytes = n;
+        return run->kept.fused_level.get();
     }
     return nullptr;
 }
@@ -247,7 +273,7 @@ int render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, 
 static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
                                  float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                  int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
-                                 rslf_stats* stats, int subgrid)
+                                 rslf_stats* stats, int subgrid, int peaks = 0, float uniqueness_ratio = 0.0f)
 {
     if (!run)
         return fail(RSLF_ERR_INVALID_ARG, "run is NULL");
@@ -256,6 +282,18 @@ static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int 
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
     if (subgrid != 0 && subgrid != 1)
         return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
+    switch (plan::f2c_peaks_args(peaks, uniqueness_ratio, dim_d)) {
+    case plan::kF2cPeaksOk:
+        break;
+    case plan::kF2cPeaksBadFlag:
+        return fail(RSLF_ERR_INVALID_ARG, "peaks=%d: 0 or 1", peaks);
+    case plan::kF2cPeaksBadRatio:
+        return fail(RSLF_ERR_INVALID_ARG, "uniqueness_ratio=%g: 0 (off) or a ratio in (0, 1]", (double)uniqueness_ratio);
+    case plan::kF2cPeaksRatioAlone:
+        return fail(RSLF_ERR_INVALID_ARG, "uniqueness_ratio=%g reads the peak planes: it needs peaks = 1", (double)uniqueness_ratio);
+    case plan::kF2cPeaksBadDimD:
+        return fail(RSLF_ERR_INVALID_ARG, "dim_d=%d: the peaks take at most %d hypotheses", dim_d, plan::kPeakMaxDimD);
+    }
     Elem e;
     int rc = elem_of(elem, &e);
     if (rc)
@@ -272,6 +310,10 @@ static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int 
     r->subgrid = subgrid;
     r->params = *p;
     r->kept.keep_volumes = keep_volumes != 0;
+    r->peaks = peaks;
+    r->uniqueness = uniqueness_ratio;
+    r->kept.peaks = peaks != 0;
+    r->kept.uniqueness = uniqueness_ratio;
     rc = fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
                                     accept_all_last_scale, nullptr, nullptr, nullptr, stats, line_mode, nullptr, validity_rule, &r->kept,
                                     subgrid);
@@ -301,6 +343,31 @@ extern "C" int rslf_f2c_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, i
                         accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid);
 }
 RSLF_API_CATCH
+
+// ... and with peaks = 1 every level's sweep in the peaks mode as well (rslf_sweep_peaks), the four planes of every level and
+// the fused peaks kept; uniqueness_ratio > 0: validity by uniqueness.  peaks = 0, uniqueness_ratio = 0 is rslf_f2c_run_host_sub
+extern "C" int rslf_f2c_run_host_pk(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
+                                    int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
+                                    float uniqueness_ratio) RSLF_API_TRY
+{
+    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio);
+}
+RSLF_API_CATCH
+
+// (not fields of rslf_f2c_run_desc: the structure keeps its size)
+extern "C" int rslf_f2c_run_peaks(const rslf_f2c_run* run) RSLF_API_TRY
+{
+    return run ? run->peaks : 0;
+}
+RSLF_API_CATCH
+
+extern "C" float rslf_f2c_run_uniqueness(const rslf_f2c_run* run)
+{
+    return run ? run->uniqueness : 0.0f;
+}
 
 // (not a field of rslf_f2c_run_desc: the structure keeps its size)
 extern "C" int rslf_f2c_run_subgrid(const rslf_f2c_run* run) RSLF_API_TRY
@@ -341,12 +408,13 @@ extern "C" int rslf_f2c_run_describe(const rslf_f2c_run* run, rslf_f2c_run_desc*
         out->epi_scale_factor[l] = kl.scale;
         dims.push_back(plan::LevelDims{kl.V, kl.U});
     }
-    for (int which = RSLF_F2C_PLANE_DEPTH; which <= RSLF_F2C_PLANE_FUSED_VALID; which++) {
+    for (int which = RSLF_F2C_PLANE_DEPTH; which <= RSLF_F2C_PLANE_FUSED_LEVEL; which++) {
         size_t bytes = 0;
         if (P > 0 && plane_of(run, 0, which, &bytes))
             out->planes_held |= 1u << which;
     }
-    out->device_bytes = plan::f2c_kept_bytes(run->S, run->C, dims, run->line_mode, run->kept.keep_volumes);
+    out->device_bytes = plan::f2c_kept_bytes(run->S, run->C, dims, run->line_mode, run->kept.keep_volumes) +
+                        plan::f2c_peaks_bytes(run->peaks != 0, run->S, dims);
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -357,14 +425,16 @@ extern "C" int rslf_f2c_run_copy(const rslf_f2c_run* run, int level, int which, 
         return fail(RSLF_ERR_INVALID_ARG, "run/dst is NULL");
     if (level < 0 || level >= (int)run->kept.levels.size())
         return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
-    if (which < RSLF_F2C_PLANE_DEPTH || which > RSLF_F2C_PLANE_FUSED_VALID)
+    if (which < RSLF_F2C_PLANE_DEPTH || which > RSLF_F2C_PLANE_FUSED_LEVEL)
         return fail(RSLF_ERR_INVALID_ARG, "plane %d: one of RSLF_F2C_PLANE_*", which);
-    if ((which == RSLF_F2C_PLANE_FUSED_MAP || which == RSLF_F2C_PLANE_FUSED_VALID) && level != 0)
+    if (is_fused_plane(which) && level != 0)
         return fail(RSLF_ERR_INVALID_ARG, "the fused planes are at the finest size: ask for them with level 0, not %d", level);
     if (stream_ctx && stream_ctx->device != run->device)
         return fail(RSLF_ERR_INVALID_ARG, "the run lives on device %d, the context on device %d", run->device, stream_ctx->device);
     size_t bytes = 0;
     const void* src = plane_of(run, level, which, &bytes);
+    if (!src && is_peak_plane(which))
+        return fail(RSLF_ERR_INVALID_ARG, "which=%d: a peak plane, and this run holds none (it was made with peaks = 0)", which);
     if (!src)
         return fail(RSLF_ERR_INVALID_ARG, "plane %d is not held by this run (C_l needs a line mode)", which);
     HIP_TRY(hipSetDevice(run->device));

@@ -12,6 +12,7 @@
 //   rslf_sweep.hip        the 2-D sweep and its propagation (K4), Depth2DComputer::run
 //   rslf_f2c.hip          fine-to-coarse: pyramid, bound tightening, fusion (K5) and the one native level loop
 //   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters
+//   rslf_f2c_peaks.hip    a kept run's peak planes: validity by uniqueness and the fused peaks (k11_f2c_peaks.hpp)
 //   rslf_render.hip       the getters' pictures: fit, plane render, EPI line painter (K6)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
@@ -528,6 +529,8 @@ struct F2cLevel {
     float* Cl_svu = nullptr;
     float* Cd_svu = nullptr;            // a kept run's [S][V][U] disparity confidence; NULL: the sweep has a plane of its own
     VolumePtr* vol_out = nullptr;         // a kept run with volumes: the sweep leaves the volume it ran on here
+    const rslf_peaks* peaks = nullptr;    // a kept run with peak planes: the level's four [S][V][U] planes, for the sweep's peaks
+                                          // mode (rslf_sweep_peaks; depth2d_run_lc fills them with -1 / 0 first); NULL: mode off
 };
 // What the level loop allocates per level and for the fusion.  The loop's own instance frees a level's confidences when the
 // level is done and the rest on return, as it always did; a caller's instance (a kept run, rslf_f2c_run) keeps everything.
@@ -537,18 +540,26 @@ struct F2cKeptLevel {
     DevBuf depth, valid, Ce, Cl;        // [S][V][U]: disparities, validity bytes, edge and line confidence (C_l empty when off)
     DevBuf Cd;                          // the disparity confidence (kept runs only)
     VolumePtr vol;                      // the normalised volume the sweep ran on (kept runs with volumes only)
+    DevBuf pk_idx, pk_score, pk_runner_idx, pk_runner_score;   // the sweep's peak planes (kept runs with peaks only)
 };
 struct F2cKept {
     bool keep_volumes = false;
     std::vector<F2cKeptLevel> levels;   // finest first
     DevBuf fused_map, fused_valid;      // [S][V_0][U_0]
+    // peak planes (rslf_f2c_run_host_pk), set by the owner before the loop runs: every level's sweep in the peaks mode, and
+    // with uniqueness > 0 a level's valid pixels whose runner-up is within that ratio of the winner become invalid
+    // (k11_unique_mask) before the next level's bounds and the fusion read the plane
+    bool peaks = false;
+    float uniqueness = 0.0f;
+    DevBuf fused_pk_idx, fused_pk_score, fused_pk_runner_idx, fused_pk_runner_score, fused_level;   // [S][V_0][U_0] (k11_fuse_peaks)
 };
 // FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from host EPIs of element type elem
 // into host planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which
 // reports the level's stats.  line_mode: every level's sweep mode, and through plan::f2c_validity the plane its validity is
 // read from; levels_out (nullable): host copies of every level's planes.  keep (nullable): the owner of a kept run --
 // nothing is freed, every level also keeps C_d (and its volume, keep->keep_volumes), the validity follows validity_rule
-// (RSLF_F2C_VALID_*; without keep it is COMPAT) and the host planes may be NULL.
+// (RSLF_F2C_VALID_*; without keep it is COMPAT) and the host planes may be NULL.  keep->peaks / keep->uniqueness: the peak
+// planes of every level and of the fused map, and the validity by uniqueness; off, the loop queues what it always did.
 int fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
                    float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                    int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
@@ -576,6 +587,8 @@ struct rslf_f2c_run {
     int S = 0, C = 0, elem = RSLF_ELEM_F32;
     int line_mode = RSLF_LINE_CONF_OFF, validity_rule = RSLF_F2C_VALID_COMPAT;
     int subgrid = 0;      // every level was swept in the sub-grid mode (rslf_f2c_run_host_sub)
+    int peaks = 0;        // the run holds peak planes (rslf_f2c_run_host_pk)
+    float uniqueness = 0.0f;   // ... and its validity went through the uniqueness ratio (0: off)
     rslf_params params;   // as given: the getters' cut_shadows / shadow_level
     rslf::F2cKept kept;
 };

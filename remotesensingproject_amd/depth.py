@@ -1465,7 +1465,60 @@ def f2c_fuse(ctx: Context, depths: Sequence[torch.Tensor], valids: Sequence[torc
 F2C_VALID_COMPAT, F2C_VALID_REFERENCE = 0, 1   # RSLF_F2C_VALID_*
 _ELEM = {np.dtype(np.float32): 0, np.dtype(np.uint8): 1, np.dtype(np.uint16): 2}   # RSLF_ELEM_*
 _F2C_PLANES = dict(depth=(0, torch.float32), valid=(1, torch.uint8), Ce=(2, torch.float32), Cd=(3, torch.float32),
-                   Cl=(4, torch.float32), fused_map=(5, torch.float32), fused_valid=(6, torch.uint8))   # RSLF_F2C_PLANE_*
+                   Cl=(4, torch.float32), fused_map=(5, torch.float32), fused_valid=(6, torch.uint8),
+                   pk_idx=(7, torch.int32), pk_score=(8, torch.float32), pk_runner_idx=(9, torch.int32),
+                   pk_runner_score=(10, torch.float32), fused_pk_idx=(11, torch.int32), fused_pk_score=(12, torch.float32),
+                   fused_pk_runner_idx=(13, torch.int32), fused_pk_runner_score=(14, torch.float32),
+                   fused_level=(15, torch.uint8))   # RSLF_F2C_PLANE_*
+
+
+def _f2c_peak_struct(pk: "Peaks", shape: tuple, who: str) -> _lib.RslfPeaks:
+    """The C struct of four peak planes of `shape` (idx / runner_idx int32, score / runner_score f32, all given; disp None)."""
+    pk = Peaks(*pk)
+    for name, t in zip(Peaks._fields, pk):
+        if name == "disp":
+            continue
+        want = torch.int32 if name.endswith("idx") else torch.float32
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != want or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s: peaks.%s must be a contiguous %s CUDA tensor of shape %s" % (who, name, want, tuple(shape)))
+    return _lib.RslfPeaks(pk.idx.data_ptr(), pk.score.data_ptr(), None, pk.runner_idx.data_ptr(), pk.runner_score.data_ptr())
+
+
+def f2c_unique_mask(ctx: Context, valid: torch.Tensor, peaks: "Peaks", ratio: float) -> torch.Tensor:
+    """rslf_f2c_unique_mask, in place on `valid` (uint8, any shape): a non-zero byte whose pixel has a winner and a runner-up
+    with runner_score > ratio * score (one float32 multiply) becomes 0; ratio in (0, 1].  peaks: a Peaks of valid's shape
+    (disp None).  Returns valid.  Queued, not awaited."""
+    if valid.dtype != torch.uint8 or not valid.is_cuda or not valid.is_contiguous():
+        raise ValueError("f2c_unique_mask: valid must be a contiguous uint8 CUDA tensor")
+    c_pk = _f2c_peak_struct(peaks, valid.shape, "f2c_unique_mask")
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_f2c_unique_mask(ctx._h, _ptr(valid), C.byref(c_pk), float(ratio), valid.numel()), "rslf_f2c_unique_mask")
+    return valid
+
+
+def f2c_fuse_peaks(ctx: Context, valids: Sequence[torch.Tensor], peaks: Sequence["Peaks"]) -> tuple["Peaks", torch.Tensor]:
+    """rslf_f2c_fuse_peaks: the levels' validity masks and peak planes [S,V_p,U_p], finest first -> (the fused Peaks
+    [S,V_0,U_0], fused_level [S,V_0,U_0] uint8): per pixel of the finest plane the first level down the fusion's nearest-pixel
+    mask chain whose validity is set, and that pixel's peaks; 255 and -1 / 0 where no level is valid."""
+    P = len(valids)
+    if P < 1 or len(peaks) != P:
+        raise ValueError("f2c_fuse_peaks: one Peaks per level")
+    S, V, U = valids[0].shape
+    structs = (_lib.RslfPeaks * P)(*[_f2c_peak_struct(pk, v.shape, "f2c_fuse_peaks") for pk, v in zip(peaks, valids)])
+    for v in valids:
+        if v.dtype != torch.uint8 or not v.is_cuda or not v.is_contiguous() or v.shape[0] != S:
+            raise ValueError("f2c_fuse_peaks: every validity plane must be a contiguous uint8 CUDA tensor [S,V_p,U_p]")
+    vp = (C.c_void_p * P)(*[t.data_ptr() for t in valids])
+    Vp = (C.c_int * P)(*[t.shape[1] for t in valids])
+    Up = (C.c_int * P)(*[t.shape[2] for t in valids])
+    dev = ctx.device
+    out = Peaks(torch.empty((S, V, U), dtype=torch.int32, device=dev), torch.empty((S, V, U), dtype=torch.float32, device=dev), None,
+                torch.empty((S, V, U), dtype=torch.int32, device=dev), torch.empty((S, V, U), dtype=torch.float32, device=dev))
+    level = torch.empty((S, V, U), dtype=torch.uint8, device=dev)
+    c_out = _f2c_peak_struct(out, (S, V, U), "f2c_fuse_peaks")
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_f2c_fuse_peaks(ctx._h, vp, structs, Vp, Up, P, S, C.byref(c_out), _ptr(level)), "rslf_f2c_fuse_peaks")
+    return out, level
 
 
 class KeptFineToCoarse:
@@ -1483,6 +1536,8 @@ class KeptFineToCoarse:
         self.scales = [float(d.epi_scale_factor[l]) for l in range(d.n_levels)]
         self.line_mode, self.validity_rule, self.keep_volumes = d.line_mode, d.validity_rule, bool(d.keep_volumes)
         self.subgrid = bool(_lib.lib().rslf_f2c_run_subgrid(self._h))   # every level was swept in the sub-grid mode
+        self.peaks = bool(_lib.lib().rslf_f2c_run_peaks(self._h))       # the run holds peak planes (get_peaks, get_fused_peaks)
+        self.uniqueness_ratio = float(_lib.lib().rslf_f2c_run_uniqueness(self._h))   # 0.0: validity by uniqueness was off
 
     def describe(self) -> "_lib.RslfF2cRunDesc":
         d = _lib.RslfF2cRunDesc()
@@ -1491,7 +1546,8 @@ class KeptFineToCoarse:
 
     def plane(self, level: int, name: str) -> torch.Tensor:
         """One kept plane as a new tensor on the device: "depth", "valid", "Ce", "Cd", "Cl" of a level [S,V_p,U_p], or
-        "fused_map" / "fused_valid" (level 0)."""
+        "fused_map" / "fused_valid" (level 0); of a run made with peaks=True also "pk_idx", "pk_score", "pk_runner_idx",
+        "pk_runner_score" of a level and "fused_pk_*" / "fused_level" (level 0)."""
         which, dtype = _F2C_PLANES[name]
         if not 0 <= level < self.n_levels:
             raise ValueError("level %d of %d" % (level, self.n_levels))
@@ -1510,6 +1566,25 @@ class KeptFineToCoarse:
     def get_results(self) -> tuple[torch.Tensor, torch.Tensor]:
         """f2c.hpp:302-324 -> (out_map_s_v_u [S,V,U] f32, out_validity_s_v_u [S,V,U] u8), copies of the kept fused planes."""
         return self.plane(0, "fused_map"), self.plane(0, "fused_valid")
+
+    def get_peaks(self, level: int) -> "Peaks":
+        """Not in the reference: a level's four peak planes [S,V_p,U_p] as a Peaks (disp None: the sub-grid value lives in the
+        depth plane) -- idx / score the winner, runner_idx / runner_score the runner-up, -1 / 0 where no visit scanned or
+        painted the pixel.  Needs a run made with peaks=True."""
+        if not self.peaks:
+            raise ValueError("get_peaks: this run was made without peaks=True")
+        return Peaks(self.plane(level, "pk_idx"), self.plane(level, "pk_score"), None, self.plane(level, "pk_runner_idx"),
+                     self.plane(level, "pk_runner_score"))
+
+    def get_fused_peaks(self) -> tuple["Peaks", torch.Tensor]:
+        """Not in the reference: (Peaks [S,V,U], fused_level [S,V,U] uint8) at the finest size -- for every pixel of the fused
+        map the level that decided it (255: none) and the peaks of the pixel of that level it was taken from: the NEAREST
+        pixel down the fusion's mask chain, while the fused disparity of a pixel decided by a coarser level is a bilinear
+        blend and a 3 x 3 median away from it."""
+        if not self.peaks:
+            raise ValueError("get_fused_peaks: this run was made without peaks=True")
+        return (Peaks(self.plane(0, "fused_pk_idx"), self.plane(0, "fused_pk_score"), None, self.plane(0, "fused_pk_runner_idx"),
+                      self.plane(0, "fused_pk_runner_score")), self.plane(0, "fused_level"))
 
     def _render(self, name: str, shapes, *args, lut_bgr=None, stacked: bool = False):
         table = _table(lut_bgr)
@@ -1549,7 +1624,8 @@ class KeptFineToCoarse:
 def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                             parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                             ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False, keep: bool = False,
-                            validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None):
+                            validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None,
+                            uniqueness_ratio: float | None = None):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -1560,8 +1636,26 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     to this form alone.
 
     subgrid (not in the reference): every level's sweep runs in the sub-grid mode (rslf_fine_to_coarse_run_host_sub,
-    rslf_f2c_run_host_sub): the bounds of the coarser levels are tightened from off-grid disparities."""
-    require_no_peaks(peaks, "fine_to_coarse_run_host")   # (the pyramid's levels carry no peak planes)
+    rslf_f2c_run_host_sub): the bounds of the coarser levels are tightened from off-grid disparities.
+
+    peaks=True (not in the reference; keep=True only: rslf_f2c_run_host_pk): every level's sweep also runs in the peaks mode
+    and the run keeps every level's peak planes and the fused peaks (KeptFineToCoarse.get_peaks / get_fused_peaks).
+    uniqueness_ratio (None or 0: off; else in (0, 1], needs peaks=True): a level's valid pixels whose runner-up scores more
+    than ratio * the winner's score become invalid, so a coarser level decides them."""
+    want_peaks = peaks is not None and peaks is not False
+    want_ratio = uniqueness_ratio is not None and uniqueness_ratio != 0
+    if not keep:
+        if want_ratio:
+            raise ValueError("fine_to_coarse_run_host: uniqueness_ratio reads the peaks planes of a kept run: pass keep=True, peaks=True")
+        if want_peaks:   # the host-planes entries have a fixed set of level planes
+            raise ValueError("fine_to_coarse_run_host: peaks is built for a kept run: pass keep=True (the host-planes form "
+                             "hands out a fixed set of level planes)")
+    if peaks is not None and not isinstance(peaks, (bool, np.bool_)):
+        raise ValueError("fine_to_coarse_run_host: peaks is True or False (the kept run owns its peak planes)")
+    if want_ratio and not want_peaks:
+        raise ValueError("fine_to_coarse_run_host: uniqueness_ratio reads the peaks planes: pass peaks=True")
+    if want_ratio and not 0.0 < float(uniqueness_ratio) <= 1.0:
+        raise ValueError("fine_to_coarse_run_host: uniqueness_ratio %r is not in (0, 1]" % (uniqueness_ratio,))
     ctx = ctx or default_context()
     keep_alive, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
     L = _lib.lib()
@@ -1573,7 +1667,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
         args = (ctx._h, ptrs, _ELEM[np.dtype(dt)], V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
                 float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
                 int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
-        if subgrid:
+        if want_peaks:
+            check(L.rslf_f2c_run_host_pk(*args, 1 if subgrid else 0, 1, float(uniqueness_ratio or 0.0)), "rslf_f2c_run_host_pk")
+        elif subgrid:
             check(L.rslf_f2c_run_host_sub(*args, 1), "rslf_f2c_run_host_sub")
         else:
             check(L.rslf_f2c_run_host(*args), "rslf_f2c_run_host")
