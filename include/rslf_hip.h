@@ -645,6 +645,57 @@ int rslf_depth2d_run_host_pk(rslf_ctx* ctx, const rslf_volume* vol, float dmin, 
                              float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid,
                              const rslf_peaks* h_pk_svu);
 
+/* ---- the sweep gate: ambiguous pixels withheld from propagation by peak ratio ---- */
+/* A fourth state of an open sweep, on top of the peaks mode with ALL FOUR planes given: valid between rslf_sweep_peaks and
+ * the first visit; cleared by rslf_sweep_end and by every later call of rslf_sweep_peaks (which is how the mode is switched
+ * off).  ratio = r in (0, 1]; 0 switches the gate off again.  Not in the reference, which has two gates of the same shape
+ * (core.hpp:1097-1103: C_d > par_disp_score_threshold, and in line mode 2 C_l > par_line_score_threshold); this is a third.
+ *
+ * THE RULE.  In visit s_hat, pixel (v, u) is a propagation source only if
+ *   1. it passes the gate it passes without the ratio: the edge mask, or C_d with use_disp_confidence_score, or C_l in line
+ *      mode 2; and
+ *   2. it is not ambiguous: NOT (idx >= 0 && runner_idx >= 0 && runner_score > r * score), the product one binary32
+ *      multiply, the four values read from the peaks planes at (s_hat, v, u) -- the predicate of a kept pyramid's validity
+ *      by uniqueness (rslf_f2c_run_host_pk below), one statement in the source for both.
+ * The values exist at that moment: a pixel this visit scanned got them from the peaks step rslf_sweep_visit_scan queues; a
+ * pixel painted earlier carries its source's.  A withheld source makes NO claim, the one on itself (s == s_hat,
+ * core.hpp:1119-1121) included -- exactly what happens to a pixel the C_d or C_l gate withholds today:
+ *   - its depth plane keeps the raw scan value, not the median;
+ *   - it stays in the running mask (scan_mask differs from the ungated sweep's);
+ *   - a later visit's unambiguous source whose line passes through it and whose radiance matches may still paint it: it
+ *     then takes that source's disparity, C_d, C_l and peaks;
+ *   - the pixels it would have painted stay in their views' running masks and are scanned in their own visits.
+ * r = 1 withholds nothing (a runner-up never scores above its winner: the bits of the plain peaks-mode sweep).  A NaN score
+ * compares false: never ambiguous.  The line modes, use_disp_confidence_score, the sub-grid mode, per-pixel ranges, every
+ * median window and the hooks ("force_packed", "peaks_list", "subgrid_list", "claim_skip", "staging_kib") combine with the
+ * gate unchanged: it only narrows the set of sources.  With the ratio off every entry queues the launches and writes the
+ * bits it always did; with it on, a visit's median + claims launch is k34_median_claim_gated, which loads the pixel's four
+ * values (16 bytes a pixel, coalesced) and counts the withheld sources -- pixels that pass 1 and fail 2, summed over the
+ * visits of the sweep -- with one atomic per wave.  Setting the ratio sizes the counter in the context's grow-only scratch
+ * and zeroes it on the stream: no visit allocates.  One device; the multi-device entries have no such mode.
+ * RSLF_ERR_INVALID_ARG with the cause in rslf_last_error(), nothing launched: a ratio below 0, above 1 or NaN; a call
+ * outside that window; a ratio above 0 while the peaks mode is off; a NULL among the four planes. */
+int rslf_sweep_propagation_ratio(rslf_ctx* ctx, const rslf_volume* vol, float ratio);
+/* The withheld sources of the last sweep that ended with ok = 1 on this context: 0 if it had no ratio.  Synchronises the
+ * context's stream.  RSLF_ERR_INVALID_ARG while a sweep is open. */
+int rslf_sweep_withheld(rslf_ctx* ctx, unsigned long long* n);
+
+/* The _pk entries with a last argument: the ratio.  0 is the _pk entry, launch for launch; above 0 it needs d_pk_svu with
+ * four planes, refused before anything is queued otherwise. */
+int rslf_depth_epi_2d_pr(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                         float dmin, float dmax, int dim_d,
+                         float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                         float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats,
+                         int line_mode, float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu, float propagation_ratio);
+int rslf_depth2d_run_pr(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                        float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
+                        float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu,
+                        int subgrid, const rslf_peaks* d_pk_svu, float propagation_ratio);
+int rslf_depth2d_run_host_pr(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                             float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                             float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid,
+                             const rslf_peaks* h_pk_svu, float propagation_ratio);
+
 /* ---- "next" row: fine-to-coarse ---------------------- */
 /* rslf::FineToCoarse<T> (include/rslf_fine_to_coarse.hpp:26-81) is a host-side loop over pyramid
  * levels, each a Depth2DComputer (rslf_depth2d_run / rslf_depth_epi_2d above).  These are the pieces
@@ -881,6 +932,17 @@ int rslf_f2c_run_host_pk(rslf_ctx* ctx, const void* const* h_epis, int elem, int
 /* The options read back from a run: 0 for NULL and for a run made without them (rslf_f2c_run_desc keeps its size). */
 int rslf_f2c_run_peaks(const rslf_f2c_run* run);
 float rslf_f2c_run_uniqueness(const rslf_f2c_run* run);
+/* ... and with a last argument propagation_ratio (0: rslf_f2c_run_host_pk, launch for launch): every level's sweep is gated
+ * by it (rslf_sweep_propagation_ratio above).  Independent of uniqueness_ratio -- the gate acts inside a level's sweep, the
+ * uniqueness on the level's validity after it -- and both may be set.  Needs peaks = 1; a ratio below 0, above 1 or NaN, or
+ * one without peaks, is RSLF_ERR_INVALID_ARG before anything is queued.  The run remembers the ratio and, per level, the
+ * sources its sweep withheld (0 on every level without the ratio; RSLF_ERR_INVALID_ARG for a level the run does not have). */
+int rslf_f2c_run_host_pr(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                         int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                         rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio, float propagation_ratio);
+float rslf_f2c_run_propagation_ratio(const rslf_f2c_run* run);
+int rslf_f2c_run_withheld(const rslf_f2c_run* run, int level, unsigned long long* n);
 /* More planes for rslf_f2c_run_copy, reported as bits of planes_held like the others (a run without peaks keeps the bits it
  * had).  PK_*: int32 / float32 [S][V_l][U_l] of any level.  FUSED_PK_* and FUSED_LEVEL (uint8): the finest size, asked for
  * with level 0.  Asked of a run that holds none: RSLF_ERR_INVALID_ARG, `which` named. */

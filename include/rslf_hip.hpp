@@ -641,6 +641,8 @@ public:
         const rslf_params p = m_parameters.to_c();
         const int line_mode = m_parameters.par_line_confidence_mode;
         detail::require(!multi_ || line_mode == RSLF_LINE_CONF_OFF, "Depth2DComputer: line confidence runs on one device");
+        detail::require(peaks_ || propagation_ratio_ == 0.f, "Depth2DComputer: the propagation ratio reads the peak planes: call set_peaks(true)");
+        withheld_ = 0;
         if (multi_) {
             if (type_ == InputType::U8)
                 check(rslf_multi_depth2d_run_u8(multi_->get(), (const uint8_t* const*)epis_.data(), stride_, dim_v_, dim_s_, dim_u_, CHANNELS,
@@ -669,6 +671,16 @@ public:
             peaks_s_v_u_.score.assign(n, 0.f), peaks_s_v_u_.runner_score.assign(n, 0.f);
             const rslf_peaks planes = {peaks_s_v_u_.idx.data(), peaks_s_v_u_.score.data(), nullptr, peaks_s_v_u_.runner_idx.data(),
                                        peaks_s_v_u_.runner_score.data()};
+            if (propagation_ratio_ != 0.f) {   // ... and gated by the peak ratio (rslf_sweep_propagation_ratio)
+                check(rslf_depth2d_run_host_pr(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
+                                               m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
+                                               m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
+                                               line_mode != RSLF_LINE_CONF_OFF ? m_line_confidence_s_v_u.data() : nullptr,
+                                               subgrid_ ? 1 : 0, &planes, propagation_ratio_),
+                      "rslf_depth2d_run_host_pr");
+                check(rslf_sweep_withheld(ctx_->get(), &withheld_), "rslf_sweep_withheld");
+                return;
+            }
             check(rslf_depth2d_run_host_pk(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
                                            m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
                                            m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
@@ -734,6 +746,25 @@ public:
             throw std::invalid_argument("get_peaks: the mode is off: set_peaks(true) before run()");
         detail::require(!peaks_s_v_u_.idx.empty(), "the getters show the results of run(): call it first");
         return peaks_s_v_u_;
+    }
+    // Not in the reference: the sweep gate (rslf_sweep_propagation_ratio, rslf_hip.h).  ratio in (0, 1], 0 switches it off:
+    // a pixel whose runner-up scores more than ratio * its winner is withheld from propagation -- no claim, its raw
+    // disparity, still in the running mask.  Needs set_peaks(true) by the time run() is called.  After run():
+    // get_withheld_sources, the sources the sweep withheld (0 without the ratio).  On a MultiContext throws, as set_peaks.
+    void set_propagation_ratio(float ratio)
+    {
+        if (ratio != 0.f && multi_)
+            throw std::invalid_argument("set_propagation_ratio: this object was built on a MultiContext: the sweep gate is built for one context");
+        detail::require(ratio >= 0.f && ratio <= 1.f, "propagation ratio: 0 (off) or a ratio in (0, 1]");
+        propagation_ratio_ = ratio;
+    }
+    float get_propagation_ratio() const { return propagation_ratio_; }
+    unsigned long long get_withheld_sources() const
+    {
+        if (multi_)
+            throw std::invalid_argument("get_withheld_sources: this object was built on a MultiContext: the sweep gate is built for one context");
+        detail::require(!m_best_depth_s_v_u.empty(), "the getters show the results of run(): call it first");
+        return withheld_;
     }
     const std::vector<float>& get_depths_s_v_u() const { return m_best_depth_s_v_u; }
 
@@ -824,6 +855,8 @@ private:
     bool subgrid_ = false;   // set_subgrid
     bool peaks_ = false;     // set_peaks
     Peaks peaks_s_v_u_;      // filled by run() with the mode on
+    float propagation_ratio_ = 0.f;      // set_propagation_ratio
+    unsigned long long withheld_ = 0;    // what run() withheld (0 without the ratio)
 };
 
 // rslf::FineToCoarse<DataType> (include/rslf_fine_to_coarse.hpp:26-81): constructor arguments as in the
@@ -949,6 +982,25 @@ public:
         uniqueness_ = ratio;
     }
     float get_uniqueness_ratio() const { return uniqueness_; }
+    // ... and the sweep gate of every level (rslf_f2c_run_host_pr): ratio in (0, 1], 0 switches it off.  Independent of the
+    // uniqueness ratio; a kept run only, and it needs set_peaks(true) by the time run() is called.  After run():
+    // get_withheld_sources(level), the sources that level's sweep withheld.
+    void set_propagation_ratio(float ratio)
+    {
+        if (ratio != 0.f && multi_)
+            throw std::invalid_argument("set_propagation_ratio: this object was built on a MultiContext: the sweep gate is built for one context");
+        detail::require(keep_, "FineToCoarse: the propagation ratio belongs to a kept run: call keep_on_device first");
+        detail::require(ratio >= 0.f && ratio <= 1.f, "propagation ratio: 0 (off) or a ratio in (0, 1]");
+        propagation_ratio_ = ratio;
+    }
+    float get_propagation_ratio() const { return propagation_ratio_; }
+    unsigned long long get_withheld_sources(int level) const
+    {
+        detail::require(run_ != nullptr, "get_withheld_sources: the counts are held by a kept run: keep_on_device, then run()");
+        unsigned long long n = 0;
+        check(rslf_f2c_run_withheld(run_, level, &n), "rslf_f2c_run_withheld");
+        return n;
+    }
     // After run() with set_peaks(true): a level's four planes; the fused peaks at the finest size -- for every pixel of the
     // fused map the peaks of the pixel of the deciding level it was taken from (the NEAREST pixel down the fusion's mask
     // chain, not the bilinear blend and median the fused disparity went through); and the level that decided it (255: none).
@@ -1144,7 +1196,15 @@ private:
         const int elem = type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32;
         peaks_held_ = false;
         detail::require(peaks_ || uniqueness_ == 0.f, "FineToCoarse: the uniqueness ratio reads the peak planes: call set_peaks(true)");
-        if (peaks_) {
+        detail::require(peaks_ || propagation_ratio_ == 0.f, "FineToCoarse: the propagation ratio reads the peak planes: call set_peaks(true)");
+        if (peaks_ && propagation_ratio_ != 0.f) {
+            check(rslf_f2c_run_host_pr(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
+                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
+                                       validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, 1, uniqueness_,
+                                       propagation_ratio_),
+                  "rslf_f2c_run_host_pr");
+            peaks_held_ = true;
+        } else if (peaks_) {
             check(rslf_f2c_run_host_pk(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
                                        scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
                                        validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, 1, uniqueness_),
@@ -1286,6 +1346,7 @@ private:
     bool subgrid_ = false;       // set_subgrid
     bool peaks_ = false;         // set_peaks
     float uniqueness_ = 0.f;     // set_uniqueness_ratio
+    float propagation_ratio_ = 0.f;   // set_propagation_ratio
     bool peaks_held_ = false;    // the kept run was made with peaks
     int validity_rule_;
     rslf_f2c_run* run_;          // the kept run, owned

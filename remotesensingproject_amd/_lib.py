@@ -60,6 +60,9 @@ SYMBOLS = [
     "rslf_sweep_peaks", "rslf_depth_epi_2d_pk", "rslf_depth2d_run_pk", "rslf_depth2d_run_host_pk",
     # a kept fine-to-coarse run's peaks per level and validity by uniqueness (K11)
     "rslf_f2c_run_host_pk", "rslf_f2c_run_peaks", "rslf_f2c_run_uniqueness", "rslf_f2c_unique_mask", "rslf_f2c_fuse_peaks",
+    # the sweep gate: ambiguous pixels withheld from propagation by peak ratio
+    "rslf_sweep_propagation_ratio", "rslf_sweep_withheld", "rslf_depth_epi_2d_pr", "rslf_depth2d_run_pr", "rslf_depth2d_run_host_pr",
+    "rslf_f2c_run_host_pr", "rslf_f2c_run_propagation_ratio", "rslf_f2c_run_withheld",
 ]
 
 
@@ -308,6 +311,15 @@ def lib():
     L.rslf_depth2d_run_pk.argtypes = L.rslf_depth2d_run_sub.argtypes + [vp]
     L.rslf_depth2d_run_host_pk.argtypes = L.rslf_depth2d_run_host_sub.argtypes + [vp]
     L.rslf_f2c_run_host_pk.argtypes = L.rslf_f2c_run_host_sub.argtypes + [ci, cf]
+    L.rslf_sweep_propagation_ratio.argtypes = [vp, vp, cf]
+    L.rslf_sweep_withheld.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+    L.rslf_depth_epi_2d_pr.argtypes = L.rslf_depth_epi_2d_pk.argtypes + [cf]
+    L.rslf_depth2d_run_pr.argtypes = L.rslf_depth2d_run_pk.argtypes + [cf]
+    L.rslf_depth2d_run_host_pr.argtypes = L.rslf_depth2d_run_host_pk.argtypes + [cf]
+    L.rslf_f2c_run_host_pr.argtypes = L.rslf_f2c_run_host_pk.argtypes + [cf]
+    L.rslf_f2c_run_propagation_ratio.argtypes = [vp]
+    L.rslf_f2c_run_propagation_ratio.restype = cf
+    L.rslf_f2c_run_withheld.argtypes = [vp, ci, C.POINTER(C.c_ulonglong)]
     L.rslf_f2c_run_peaks.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.restype = cf

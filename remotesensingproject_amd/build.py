@@ -30,11 +30,11 @@ UNITS = {
     "rslf_peaks.hip": ["k8_peaks.hpp", "k8_peak_rule.hpp", "rslf_plan_peaks.hpp"],
     "rslf_subgrid.hip": ["k2_scan.hpp", "k9_subgrid.hpp", "k8_peak_rule.hpp", "rslf_plan_subgrid.hpp"],
     "rslf_sweep.hip": ["k3_median.hpp", "k4_propagate.hpp", "k_compact.hpp", "k2_scan.hpp", "k7_line_conf.hpp", "rslf_plan_subgrid.hpp",
-                       "rslf_plan_sweep_peaks.hpp", "rslf_plan_peaks.hpp"],
+                       "rslf_plan_sweep_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_sweep_gate.hpp", "k11_f2c_peak_rule.hpp"],
     "rslf_sweep_peaks.hip": ["k2_scan.hpp", "k10_sweep_peaks.hpp", "k10_peak_merge.hpp", "k8_peak_rule.hpp", "rslf_plan_sweep_peaks.hpp",
                              "rslf_plan_peaks.hpp", "rslf_plan_subgrid.hpp"],
     "rslf_f2c.hip": ["k5_f2c.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp"],
-    "rslf_f2c_keep.hip": ["rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp"],
+    "rslf_f2c_keep.hip": ["rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_sweep_gate.hpp", "k11_f2c_peak_rule.hpp"],
     "rslf_f2c_peaks.hip": ["k11_f2c_peaks.hpp", "k11_f2c_peak_rule.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp"],
     "rslf_render.hip": ["k6_render.hpp", "rslf_plan_render.hpp"],
     "rslf_multi.hip": [],

@@ -14,6 +14,7 @@
 #pragma once
 
 #include "k_compact.hpp"
+#include "k11_f2c_peak_rule.hpp"
 #include "k3_median.hpp"
 #include "rslf_device.hpp"
 
@@ -106,14 +107,30 @@ __device__ __forceinline__ void propagate_claim_pixel(const VolView& vol, int s_
 // K3 + claim in one launch (a sweep visit): a pixel's median needs its neighbours' RAW depths only (what the scan
 // left), and its claims need its own median only -- so the thread that filters a pixel also makes its claims.  The
 // filtered plane is still written: the apply pass reads the winners' values from it.
-template <int C, int MODE>
-__global__ __launch_bounds__(256) void k34_median_claim(VolView vol, int s_hat, const float* __restrict__ raw_vu,
-                                                       float* __restrict__ filtered_vu, const uint8_t* __restrict__ edge_mask_vu,
-                                                       int w, plan::NormThreshold median_thr, const float* __restrict__ rbar_vu,
-                                                       const uint8_t* __restrict__ mask_svu, int* __restrict__ winner_svu,
-                                                       uint8_t* __restrict__ dirty, float slope, plan::NormThreshold prop_thr,
-                                                       const float* __restrict__ gate_Cd_vu, float disp_thr, int* __restrict__ reset,
-                                                       const int* __restrict__ remain)
+//
+// The sweep gate (rslf_sweep_propagation_ratio): the peaks mode's four [S][V][U] planes, hat = s_hat * V * U, the ratio and
+// the sweep's counter of withheld sources.  A pixel that passes the gate of core.hpp:1097-1103 and whose runner-up is within
+// the ratio of its winner (f2c_peak_ambiguous, the predicate of a kept pyramid's validity: one statement for both) is no
+// source: it makes no claim, not even the one on itself, exactly as a pixel withheld by C_d or C_l.
+struct ClaimGate {
+    const int32_t* idx;
+    const float* score;
+    const int32_t* runner_idx;
+    const float* runner_score;
+    long long hat;
+    float ratio;
+    unsigned long long* withheld;
+};
+
+// GATED = false: `gate` is not read -- the code of a sweep without the ratio is what it was before the gate existed.
+template <int C, int MODE, bool GATED>
+__device__ __forceinline__ void median_claim_body(const VolView& vol, int s_hat, const float* __restrict__ raw_vu,
+                                                  float* __restrict__ filtered_vu, const uint8_t* __restrict__ edge_mask_vu,
+                                                  int w, const plan::NormThreshold& median_thr, const float* __restrict__ rbar_vu,
+                                                  const uint8_t* __restrict__ mask_svu, int* __restrict__ winner_svu,
+                                                  uint8_t* __restrict__ dirty, float slope, const plan::NormThreshold& prop_thr,
+                                                  const float* __restrict__ gate_Cd_vu, float disp_thr, int* __restrict__ reset,
+                                                  const int* __restrict__ remain, const ClaimGate& gate)
 {
     // `reset`: the packed list's length, which the scan before this launch was the last to read and the apply pass after
     // it counts up again from 0
@@ -126,11 +143,31 @@ __global__ __launch_bounds__(256) void k34_median_claim(VolView vol, int s_hat, 
     const int u = u_first + threadIdx.x;
     const bool inside = u < vol.U;
     const long long o = (long long)v * vol.U + (inside ? u : vol.U - 1);
+    // the pixel's peaks, four UNCONDITIONAL loads at the clamped address, in flight under the median (a load under `if`
+    // waits in a block of its own: propagate_claim_pixel)
+    int32_t pk_idx = -1, pk_runner_idx = -1;
+    float pk_score = 0.0f, pk_runner_score = 0.0f;
+    if (GATED) {
+        const long long g = gate.hat + o;
+        pk_idx = gate.idx[g];
+        pk_runner_idx = gate.runner_idx[g];
+        pk_score = gate.score[g];
+        pk_runner_score = gate.runner_score[g];
+    }
     // core.hpp:678-679, :881-892: the median over the edge mask, 0 elsewhere
     const float cur = selective_median_block<C, MODE>(vol, raw_vu, edge_mask_vu, s_hat, w, median_thr, v, u_first, s_median_tile);
     if (inside)
         filtered_vu[o] = cur;
-    const bool source = inside && (gate_Cd_vu ? gate_Cd_vu[o] > disp_thr : edge_mask_vu[o] != 0);   // core.hpp:1097-1103
+    bool source = inside && (gate_Cd_vu ? gate_Cd_vu[o] > disp_thr : edge_mask_vu[o] != 0);   // core.hpp:1097-1103
+    if (GATED) {
+        // before the reach reduction and the workgroup's "any source?": a withheld pixel widens no reach and keeps no workgroup.
+        // Counted per wave: one ballot, one vector atomic by the first lane (every lane of the workgroup is still here)
+        const bool withheld = source && f2c_peak_ambiguous(pk_idx, pk_runner_idx, pk_score, pk_runner_score, gate.ratio);
+        const unsigned long long b = __ballot(withheld);
+        if (b != 0 && (threadIdx.x & 63) == 0)
+            atomicAdd(gate.withheld, (unsigned long long)__popcll(b));
+        source = source && !withheld;
+    }
     // the range of the disparities the workgroup's sources hold (a non-finite one: everywhere)
     __shared__ float s_lo[4], s_hi[4];
     const bool finite = fabsf(cur) < 1.0e9f;   // false for NaN too
@@ -181,6 +218,34 @@ __global__ __launch_bounds__(256) void k34_median_claim(VolView vol, int s_hat, 
         __syncthreads();
     }
     propagate_claim_pixel<C>(vol, s_hat, v, u, cur, source, rbar_vu, mask_svu, winner_svu, dirty, slope, prop_thr, skipping ? s_live : nullptr);
+}
+
+// The kernel of every sweep without the ratio: the argument block and the code it always had.
+template <int C, int MODE>
+__global__ __launch_bounds__(256) void k34_median_claim(VolView vol, int s_hat, const float* __restrict__ raw_vu,
+                                                       float* __restrict__ filtered_vu, const uint8_t* __restrict__ edge_mask_vu,
+                                                       int w, plan::NormThreshold median_thr, const float* __restrict__ rbar_vu,
+                                                       const uint8_t* __restrict__ mask_svu, int* __restrict__ winner_svu,
+                                                       uint8_t* __restrict__ dirty, float slope, plan::NormThreshold prop_thr,
+                                                       const float* __restrict__ gate_Cd_vu, float disp_thr, int* __restrict__ reset,
+                                                       const int* __restrict__ remain)
+{
+    median_claim_body<C, MODE, false>(vol, s_hat, raw_vu, filtered_vu, edge_mask_vu, w, median_thr, rbar_vu, mask_svu, winner_svu, dirty,
+                                      slope, prop_thr, gate_Cd_vu, disp_thr, reset, remain, ClaimGate{});
+}
+
+// ... and of a sweep with the ratio set (rslf_sweep_propagation_ratio): the same pass with the gate's planes and counter
+template <int C, int MODE>
+__global__ __launch_bounds__(256) void k34_median_claim_gated(VolView vol, int s_hat, const float* __restrict__ raw_vu,
+                                                             float* __restrict__ filtered_vu, const uint8_t* __restrict__ edge_mask_vu,
+                                                             int w, plan::NormThreshold median_thr, const float* __restrict__ rbar_vu,
+                                                             const uint8_t* __restrict__ mask_svu, int* __restrict__ winner_svu,
+                                                             uint8_t* __restrict__ dirty, float slope, plan::NormThreshold prop_thr,
+                                                             const float* __restrict__ gate_Cd_vu, float disp_thr,
+                                                             int* __restrict__ reset, const int* __restrict__ remain, ClaimGate gate)
+{
+    median_claim_body<C, MODE, true>(vol, s_hat, raw_vu, filtered_vu, edge_mask_vu, w, median_thr, rbar_vu, mask_svu, winner_svu, dirty,
+                                     slope, prop_thr, gate_Cd_vu, disp_thr, reset, remain, gate);
 }
 
 // The apply pass of a visit (core.hpp:1119-1127) and, in the same launch, the pixel list of the NEXT visit's scan: one

@@ -364,6 +364,8 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             pk.runner_idx = kl.pk_runner_idx.as<int32_t>();
             pk.runner_score = kl.pk_runner_score.as<float>();
             lv.peaks = &pk;
+            lv.propagation_ratio = K.propagation_ratio;   // 0 unless a kept run asked for the gate
+            lv.withheld = &kl.withheld;
         }
         if (l > 0) {
             HIP_TRY(dmin.alloc(n * 4));
@@ -508,7 +510,9 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const
         if (!rc)
             rc = depth2d_run_lc(ctx, vol.get(), lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, mask.as<uint8_t>(),
                                 lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(), nullptr, level_stats,
-                                lv.line_mode, lv.Cl_svu, subgrid, lv.peaks);
+                                lv.line_mode, lv.Cl_svu, subgrid, lv.peaks, lv.propagation_ratio);
+        if (!rc && lv.propagation_ratio > 0.0f && lv.withheld)
+            rc = rslf_sweep_withheld(ctx, lv.withheld);
         if (!rc && lv.vol_out)
             *lv.vol_out = std::move(vol);   // kept; otherwise destroyed here, with the sweep's other planes
         return rc;

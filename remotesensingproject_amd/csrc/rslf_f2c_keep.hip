@@ -3,6 +3,7 @@
 // getters of rslf_fine_to_coarse.hpp:325-519 from them with the renderers of rslf_render.hip.  No kernels of its own.
 #include "rslf_internal.hpp"
 #include "rslf_plan_f2c_peaks.hpp"
+#include "rslf_plan_sweep_gate.hpp"
 
 using namespace rslf;
 
@@ -273,7 +274,8 @@ int render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, 
 static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
                                  float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                  int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
-                                 rslf_stats* stats, int subgrid, int peaks = 0, float uniqueness_ratio = 0.0f)
+                                 rslf_stats* stats, int subgrid, int peaks = 0, float uniqueness_ratio = 0.0f,
+                                 float propagation_ratio = 0.0f)
 {
     if (!run)
         return fail(RSLF_ERR_INVALID_ARG, "run is NULL");
@@ -294,6 +296,11 @@ static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int 
     case plan::kF2cPeaksBadDimD:
         return fail(RSLF_ERR_INVALID_ARG, "dim_d=%d: the peaks take at most %d hypotheses", dim_d, plan::kPeakMaxDimD);
     }
+    // the sweeps' gate by peak ratio: independent of the uniqueness ratio; it reads the levels' peak planes
+    if (!plan::sweep_gate_ratio_ok(propagation_ratio))
+        return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g: 0 (off) or a ratio in (0, 1]", (double)propagation_ratio);
+    if (propagation_ratio != 0.0f && !peaks)
+        return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g reads the peak planes: it needs peaks = 1", (double)propagation_ratio);
     Elem e;
     int rc = elem_of(elem, &e);
     if (rc)
@@ -314,6 +321,8 @@ static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int 
     r->uniqueness = uniqueness_ratio;
     r->kept.peaks = peaks != 0;
     r->kept.uniqueness = uniqueness_ratio;
+    r->propagation_ratio = propagation_ratio;
+    r->kept.propagation_ratio = propagation_ratio;
     rc = fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
                                     accept_all_last_scale, nullptr, nullptr, nullptr, stats, line_mode, nullptr, validity_rule, &r->kept,
                                     subgrid);
@@ -354,6 +363,36 @@ extern "C" int rslf_f2c_run_host_pk(rslf_ctx* ctx, const void* const* h_epis, in
 {
     return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
                         accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio);
+}
+RSLF_API_CATCH
+
+// ... and with propagation_ratio > 0 every level's sweep gated by it (rslf_sweep_propagation_ratio); 0 is rslf_f2c_run_host_pk
+extern "C" int rslf_f2c_run_host_pr(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
+                                    int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
+                                    float uniqueness_ratio, float propagation_ratio) RSLF_API_TRY
+{
+    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio,
+                        propagation_ratio);
+}
+RSLF_API_CATCH
+
+extern "C" float rslf_f2c_run_propagation_ratio(const rslf_f2c_run* run)
+{
+    return run ? run->propagation_ratio : 0.0f;
+}
+
+// the sources level `level`'s sweep withheld; 0 on every level of a run without the ratio
+extern "C" int rslf_f2c_run_withheld(const rslf_f2c_run* run, int level, unsigned long long* n) RSLF_API_TRY
+{
+    if (!run || !n)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (level < 0 || level >= (int)run->kept.levels.size())
+        return fail(RSLF_ERR_INVALID_ARG, "level=%d outside [0,%d)", level, (int)run->kept.levels.size());
+    *n = run->kept.levels[(size_t)level].withheld;
+    return RSLF_OK;
 }
 RSLF_API_CATCH
 

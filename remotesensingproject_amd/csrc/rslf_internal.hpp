@@ -17,7 +17,7 @@
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
-//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp   ... continued, for the units that need them
+//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp   ... continued, for the units that need them
 //   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
 //
 // Two rules of the multi-device paths: they never write into a rslf_volume they did not create (a chunk of another height
@@ -229,6 +229,7 @@ struct Scratch {
     DeviceBuf dirty;        // u8 [S][V][ceil(U/256)]: segments of the winner rows that hold a claim (all 0 between visits)
     DeviceBuf remain;       // int [S][V][ceil(U/256)]: pixels left in the running mask per segment (lets the claims skip views)
     DeviceBuf filtered;     // float [V][U]: median of the visited view, the propagation's source
+    DeviceBuf withheld;     // one u64: sources a gated sweep withheld (rslf_sweep_propagation_ratio zeroes it, the claims count, rslf_sweep_withheld reads)
     DeviceBuf lc_columns;   // float [V][S][U]: K(r - rbar) columns of a sweep with line confidence, kept from visit to visit
     DeviceBuf lc_argmax;    // int32 [V][U]: arg-max indices of the visit's scan, -1 where it accepted nothing
     DeviceBuf shared[kSharedBufs];
@@ -293,6 +294,9 @@ struct SweepState {
     bool peaks = false;
     rslf_peaks pk = {};
     int dim_d = 0;              // what rslf_sweep_begin was given: sizes the dense step's staging when the mode is set
+    // gate by peak ratio (rslf_sweep_propagation_ratio; k4_propagate.hpp): state of ONE sweep too, 0 = off.  Needs the peaks
+    // mode with all four planes; its counter is Scratch::withheld.
+    float prop_ratio = 0.0f;
 };
 
 }  // namespace rslf
@@ -312,6 +316,7 @@ struct rslf_ctx {
     size_t ev_used = 0;
     int last_spad = 0;   // register-scan slot count of the last K2 launch, 0 = none
     int last_kernel = 0; // RSLF_SCAN_* of the last K2 launch
+    bool last_gated = false;   // the last sweep that ended well had the ratio set: Scratch::withheld holds its count (rslf_sweep_withheld)
     int num_cus = 0;           // compute units of the device (how many workgroups a launch needs to fill it)
     // test / tuning hooks (rslf_ctx_set_debug), per context: 0 / -1 = automatic
     int force_scan = 0;        // 1 generic kernel, 2 streaming kernel wherever it can run (never the on-chip one)
@@ -501,11 +506,11 @@ int depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, 
 // The same with the line-confidence plane of dc.hpp:721-738, :791-792: line_mode RSLF_LINE_CONF_*, d_Cl_svu [S][V][U]
 // (zero-filled here; NULL with RSLF_LINE_CONF_OFF, which queues exactly the launches of depth2d_run).  subgrid = 1: every
 // visit in the sub-grid mode (rslf_sweep_subgrid).  d_pk_svu (nullable): the peaks mode's four planes (rslf_sweep_peaks), filled
-// here with idx = runner_idx = -1 and the floats 0.
+// here with idx = runner_idx = -1 and the floats 0.  propagation_ratio > 0: the sweep gated by it (rslf_sweep_propagation_ratio).
 int depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
                    int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                    float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid = 0,
-                   const rslf_peaks* d_pk_svu = nullptr);
+                   const rslf_peaks* d_pk_svu = nullptr, float propagation_ratio = 0.0f);
 
 // rslf_f2c.hip
 // A volume owned by a scope or an object (rslf_volume_destroy is the one place that frees a slab).
@@ -531,6 +536,8 @@ struct F2cLevel {
     VolumePtr* vol_out = nullptr;         // a kept run with volumes: the sweep leaves the volume it ran on here
     const rslf_peaks* peaks = nullptr;    // a kept run with peak planes: the level's four [S][V][U] planes, for the sweep's peaks
                                           // mode (rslf_sweep_peaks; depth2d_run_lc fills them with -1 / 0 first); NULL: mode off
+    float propagation_ratio = 0.0f;       // ... and the level's sweep gated by this ratio (rslf_sweep_propagation_ratio; 0: off)
+    unsigned long long* withheld = nullptr;   // where the sweep leaves its count of withheld sources (gated levels only)
 };
 // What the level loop allocates per level and for the fusion.  The loop's own instance frees a level's confidences when the
 // level is done and the rest on return, as it always did; a caller's instance (a kept run, rslf_f2c_run) keeps everything.
@@ -541,6 +548,7 @@ struct F2cKeptLevel {
     DevBuf Cd;                          // the disparity confidence (kept runs only)
     VolumePtr vol;                      // the normalised volume the sweep ran on (kept runs with volumes only)
     DevBuf pk_idx, pk_score, pk_runner_idx, pk_runner_score;   // the sweep's peak planes (kept runs with peaks only)
+    unsigned long long withheld = 0;    // sources the level's sweep withheld (kept runs with a propagation ratio only)
 };
 struct F2cKept {
     bool keep_volumes = false;
@@ -551,6 +559,7 @@ struct F2cKept {
     // (k11_unique_mask) before the next level's bounds and the fusion read the plane
     bool peaks = false;
     float uniqueness = 0.0f;
+    float propagation_ratio = 0.0f;     // every level's sweep gated by this ratio (rslf_f2c_run_host_pr; needs peaks; 0: off)
     DevBuf fused_pk_idx, fused_pk_score, fused_pk_runner_idx, fused_pk_runner_score, fused_level;   // [S][V_0][U_0] (k11_fuse_peaks)
 };
 // FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from host EPIs of element type elem
@@ -571,7 +580,7 @@ int fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const* h_ep
                                float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
                                rslf_stats* stats, int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule,
-                               F2cKept* keep, int subgrid = 0);
+                               F2cKept* keep, int subgrid = 0);   // (keep->propagation_ratio: every level's sweep gated)
 
 // rslf_multi.hip
 void multi_free_dev(rslf_multi::Dev& d);
@@ -589,6 +598,7 @@ struct rslf_f2c_run {
     int subgrid = 0;      // every level was swept in the sub-grid mode (rslf_f2c_run_host_sub)
     int peaks = 0;        // the run holds peak planes (rslf_f2c_run_host_pk)
     float uniqueness = 0.0f;   // ... and its validity went through the uniqueness ratio (0: off)
+    float propagation_ratio = 0.0f;   // ... and every level's sweep was gated by this ratio (rslf_f2c_run_host_pr; 0: off)
     rslf_params params;   // as given: the getters' cut_shadows / shadow_level
     rslf::F2cKept kept;
 };

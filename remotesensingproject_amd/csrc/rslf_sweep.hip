@@ -3,6 +3,7 @@
 // step is rslf_sweep_peaks.hip's.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
 #include "rslf_plan_subgrid.hpp"
+#include "rslf_plan_sweep_gate.hpp"
 #include "rslf_plan_sweep_peaks.hpp"
 
 #include <algorithm>
@@ -43,6 +44,7 @@ static int ensure_sweep_scratch(rslf_ctx* ctx, const rslf_volume* vol)
 // The order of the visits (core.hpp:981-990): plan::sweep_order.
 static void sweep_close(rslf_ctx* ctx, bool ok)
 {
+    ctx->last_gated = ok && ctx->sweep.prop_ratio > 0.0f;   // the count rslf_sweep_withheld reports; 0 for any other sweep
     ctx->sweep = SweepState();   // line confidence too is state of ONE sweep (rslf_sweep_line_confidence)
     if (!ok) {
         ctx->scratch.winner.mark_stale();   // claims without their apply pass may be left behind: fresh winners and flags next time
@@ -217,6 +219,63 @@ extern "C" int rslf_sweep_subgrid(rslf_ctx* ctx, const rslf_volume* vol, int on)
 }
 RSLF_API_CATCH
 
+// The gate by peak ratio of an open sweep in the peaks mode (include/rslf_hip.h; k4_propagate.hpp, ClaimGate): every visit's
+// claims come from k34_median_claim_gated.  The refusals: plan::sweep_gate_args.
+static int gate_refusal(plan::SweepGateArg why, float ratio, const char* who)
+{
+    switch (why) {
+    case plan::kSweepGateOk:
+        return RSLF_OK;
+    case plan::kSweepGateBadRatio:
+        return fail(RSLF_ERR_INVALID_ARG, "%s: propagation_ratio=%g: 0 (off) or a ratio in (0, 1]", who, (double)ratio);
+    case plan::kSweepGateWindow:
+        return fail(RSLF_ERR_INVALID_ARG, "%s belongs between rslf_sweep_peaks and the first visit", who);
+    case plan::kSweepGateNoPeaks:
+        return fail(RSLF_ERR_INVALID_ARG, "%s: propagation_ratio=%g reads the peak planes: it needs the peaks mode (rslf_sweep_peaks)", who,
+                    (double)ratio);
+    case plan::kSweepGateNullPlane:
+        return fail(RSLF_ERR_INVALID_ARG, "%s: propagation_ratio=%g needs all four peak planes, and one is NULL", who, (double)ratio);
+    }
+    return fail(RSLF_ERR_INTERNAL, "%s: unknown refusal", who);
+}
+
+extern "C" int rslf_sweep_propagation_ratio(rslf_ctx* ctx, const rslf_volume* vol, float ratio) RSLF_API_TRY
+{
+    if (!ctx || !vol)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    SweepState& sw = ctx->sweep;
+    const rslf_peaks& pk = sw.pk;
+    if (int rc = gate_refusal(plan::sweep_gate_args(ratio, sw.open, sw.scanned, sw.first, sw.peaks, pk.idx != nullptr, pk.score != nullptr,
+                                                    pk.runner_idx != nullptr, pk.runner_score != nullptr),
+                              ratio, "rslf_sweep_propagation_ratio"))
+        return rc;
+    sw.prop_ratio = 0.0f;
+    if (!plan::sweep_gate_on(ratio))
+        return RSLF_OK;
+    // sized here, never inside a visit; the count starts at 0 in stream order, ahead of the first visit's claims
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hip_err(ctx->scratch.withheld.reserve(plan::sweep_gate_counter_bytes(ratio))));
+    HIP_TRY(hipMemsetAsync(ctx->scratch.withheld.get(), 0, sizeof(unsigned long long), ctx->stream));
+    sw.prop_ratio = ratio;
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_sweep_withheld(rslf_ctx* ctx, unsigned long long* n) RSLF_API_TRY
+{
+    if (!ctx || !n)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (ctx->sweep.open)
+        return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_withheld reports an ended sweep: call it after rslf_sweep_end");
+    HIP_TRY(hipSetDevice(ctx->device));
+    *n = 0;
+    if (ctx->last_gated)
+        HIP_TRY(hipMemcpyAsync(n, ctx->scratch.withheld.get(), sizeof(*n), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
 extern "C" int rslf_sweep_visit_scan(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
                                      float dmin, float dmax, int dim_d, int s_hat, float* d_Ce_svu, uint8_t* d_Ce_mask_svu,
                                      float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu, const rslf_params* p) RSLF_API_TRY
@@ -364,6 +423,24 @@ extern "C" int rslf_sweep_visit_finish(rslf_ctx* ctx, const rslf_volume* vol, in
     }
     const float* gate_vu = gate == plan::kGateDispConf ? Cd : gate == plan::kGateLineConf ? Cl : nullptr;
     const float gate_thr = gate == plan::kGateLineConf ? p->line_score_threshold : p->disp_score_threshold;
+    // the gate by peak ratio: the claim kernel that takes the peaks planes; out of it, the kernel, the argument block and the
+    // code of every sweep before the gate existed
+    const bool gated = ctx->sweep.prop_ratio > 0.0f;
+    const ClaimGate cg = {ctx->sweep.pk.idx, ctx->sweep.pk.score, ctx->sweep.pk.runner_idx, ctx->sweep.pk.runner_score,
+                          (long long)s_hat * (long long)n, ctx->sweep.prop_ratio, sc.withheld.as<unsigned long long>()};
+#define RSLF_K34G_CASE(CC, MODE)                                                                                                 \
+    if (gated && !launched && C == CC && mp.mode == MODE) {                                                                       \
+        if (mp.lds_bytes > ((size_t)64 << 10))                                                                                    \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k34_median_claim_gated<CC, MODE>),                        \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds_bytes));                         \
+        hipLaunchKernelGGL((k34_median_claim_gated<CC, MODE>), grid_vu, dim3(256), mp.lds_bytes, st, view_of(vol), s_hat, depth,  \
+                           filtered, cem, mp.w, median_thr, rbar, mask_svu, winner, dirty, p->slope_factor, prop_thr,             \
+                           gate_vu, gate_thr, packed_n, ctx->claim_skip ? remain : nullptr, cg);                                  \
+        launched = true;                                                                                                          \
+    }
+    RSLF_MEDIAN_MODES(RSLF_K34G_CASE, 1)
+    RSLF_MEDIAN_MODES(RSLF_K34G_CASE, 3)
+#undef RSLF_K34G_CASE
 #define RSLF_K34_CASE(CC, MODE)                                                                                                  \
     if (!launched && C == CC && mp.mode == MODE) {                                                                                \
         if (mp.lds_bytes > ((size_t)64 << 10))                                                                                    \
@@ -420,15 +497,25 @@ extern "C" int rslf_sweep_end(rslf_ctx* ctx, int ok, int dim_d, rslf_stats* stat
 }
 RSLF_API_CATCH
 
+// What a *_pr entry refuses before it queues anything: a bad ratio, and a ratio without the peaks mode's four planes
+static int entry_gate_check(float ratio, const rslf_peaks* pk)
+{
+    return gate_refusal(plan::sweep_gate_entry_args(ratio, pk != nullptr, pk && pk->idx, pk && pk->score, pk && pk->runner_idx,
+                                                    pk && pk->runner_score),
+                        ratio, "the sweep");
+}
+
 // compute_2D_depth_epi (core.hpp:933-1133) as begin + (scan, finish) per view + end; line_mode / d_Cl_svu: the extra argument
 // a_line_confidence_s_v_u of the -D_USE_LINE_CONFIDENCE_SCORE build (core.hpp:345), RSLF_LINE_CONF_OFF / NULL without it
 static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
                         float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
                         float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                        float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu = nullptr)
+                        float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu = nullptr, float propagation_ratio = 0.0f)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = entry_gate_check(propagation_ratio, d_pk_svu))   // before anything is queued
+        return rc;
     if (!plan::line_conf_mode_ok(line_mode))
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
     if (line_mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
@@ -447,6 +534,8 @@ static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dm
         rc = rslf_sweep_subgrid(ctx, vol, 1);
     if (!rc && d_pk_svu)
         rc = rslf_sweep_peaks(ctx, vol, d_pk_svu);
+    if (!rc && propagation_ratio != 0.0f)
+        rc = rslf_sweep_propagation_ratio(ctx, vol, propagation_ratio);
     for (int s_hat : plan::sweep_order(vol->S)) {   // core.hpp:981-990
         if (!rc)
             rc = rslf_sweep_visit_scan(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, s_hat, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu,
@@ -505,10 +594,22 @@ extern "C" int rslf_depth_epi_2d_pk(rslf_ctx* ctx, const rslf_volume* vol, const
 }
 RSLF_API_CATCH
 
+// ... and the gate by peak ratio (rslf_sweep_propagation_ratio): propagation_ratio = 0 queues exactly rslf_depth_epi_2d_pk's launches
+extern "C" int rslf_depth_epi_2d_pr(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
+                                    float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
+                                    float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
+                                    rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu,
+                                    float propagation_ratio) RSLF_API_TRY
+{
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu, propagation_ratio);
+}
+RSLF_API_CATCH
+
 int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
                          float dmax, int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
                          float* d_depth_svu, float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                         float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu)
+                         float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu, float propagation_ratio)
 {
     if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
@@ -518,6 +619,8 @@ int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
     if (subgrid != 0 && subgrid != 1)
         return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
+    if (int rc = entry_gate_check(propagation_ratio, d_pk_svu))   // before anything is queued
+        return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n = (size_t)vol->S * vol->V * vol->U;
     hipStream_t st = ctx->stream;
@@ -538,7 +641,7 @@ int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_d
     if (rc)
         return rc;
     return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
-                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu);
+                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu, propagation_ratio);
 }
 
 int rslf::depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
@@ -589,12 +692,26 @@ extern "C" int rslf_depth2d_run_pk(rslf_ctx* ctx, const rslf_volume* vol, float 
 }
 RSLF_API_CATCH
 
+// ... and the gate by peak ratio; propagation_ratio = 0 queues exactly rslf_depth2d_run_pk's launches
+extern "C" int rslf_depth2d_run_pr(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                   float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
+                                   uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid,
+                                   const rslf_peaks* d_pk_svu, float propagation_ratio) RSLF_API_TRY
+{
+    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
+                          d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu, propagation_ratio);
+}
+RSLF_API_CATCH
+
 static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                             float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
-                            rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid, const rslf_peaks* h_pk_svu = nullptr)
+                            rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid, const rslf_peaks* h_pk_svu = nullptr,
+                            float propagation_ratio = 0.0f)
 {
     if (!ctx || !vol)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = entry_gate_check(propagation_ratio, h_pk_svu))   // before anything is allocated or queued
+        return rc;
     if (subgrid != 0 && subgrid != 1)
         return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     if (!plan::line_conf_mode_ok(line_mode))
@@ -626,7 +743,7 @@ static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, f
     }
     int rc = depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, Ce.as<float>(), mask.as<uint8_t>(), Cd.as<float>(),
                             depth.as<float>(), rbar.as<float>(), nullptr, stats, line_mode, Cl.as<float>(), subgrid,
-                            h_pk_svu ? &d_pk : nullptr);
+                            h_pk_svu ? &d_pk : nullptr, propagation_ratio);
     if (rc)
         return rc;
     hipStream_t st = ctx->stream;
@@ -680,5 +797,15 @@ extern "C" int rslf_depth2d_run_host_pk(rslf_ctx* ctx, const rslf_volume* vol, f
 {
     return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
                             line_mode, h_Cl_svu, subgrid, h_pk_svu);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_depth2d_run_host_pr(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                                        float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
+                                        float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid,
+                                        const rslf_peaks* h_pk_svu, float propagation_ratio) RSLF_API_TRY
+{
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
+                            line_mode, h_Cl_svu, subgrid, h_pk_svu, propagation_ratio);
 }
 RSLF_API_CATCH

@@ -29,6 +29,7 @@ extern "C" int rslf_sweep_peaks(rslf_ctx* ctx, const rslf_volume* vol, const rsl
     HIP_TRY(hipSetDevice(ctx->device));
     sw.peaks = false;
     sw.pk = rslf_peaks{};
+    sw.prop_ratio = 0.0f;   // the gate by peak ratio reads these planes: every call here clears it (rslf_sweep_propagation_ratio follows)
     if (!d_out_svu)
         return RSLF_OK;
     // sized here, never inside a visit; held until rslf_sweep_end.  The visits' arg-max and score planes are the sub-grid

@@ -113,6 +113,28 @@ def require_no_peaks(peaks, who: str) -> None:
         raise ValueError("%s: peaks is not built here (one device, one sweep: Depth2DComputer and compute_2D_depth_epi)" % who)
 
 
+def _ratio_on(ratio) -> bool:
+    return ratio is not None and ratio is not False and ratio != 0
+
+
+def require_no_propagation_ratio(ratio, who: str) -> None:
+    """The sweep gate (DESIGN.md 3 "Sweep gate") is built where the peaks mode is and for a kept pyramid: one device.  Every
+    other form refuses it instead of ignoring it."""
+    if _ratio_on(ratio):
+        raise ValueError("%s: propagation_ratio is not built here (one device, a sweep in the peaks mode: Depth2DComputer, "
+                         "compute_2D_depth_epi and fine_to_coarse_run_host(keep=True, peaks=True))" % who)
+
+
+def _propagation_ratio(ratio, who: str) -> float:
+    """None / 0 -> 0.0 (off); else a ratio in (0, 1] (a NaN is none)."""
+    if not _ratio_on(ratio):
+        return 0.0
+    r = float(ratio)
+    if not 0.0 < r <= 1.0:
+        raise ValueError("%s: propagation_ratio %r is not in (0, 1]" % (who, ratio))
+    return r
+
+
 class Context:
     """rslf_ctx bound to one GPU; launches go to torch's current stream on it."""
 
@@ -164,6 +186,13 @@ class Context:
         ms, n = C.c_float(), C.c_int()
         check(_lib.lib().rslf_scan_time_total_ms(self._h, C.byref(ms), C.byref(n)), "rslf_scan_time_total_ms")
         return float(ms.value), int(n.value)
+
+    def get_withheld_sources(self) -> int:
+        """rslf_sweep_withheld: the sources the last finished 2-D sweep on this context withheld from propagation
+        (propagation_ratio); 0 if it had no ratio.  Waits for the stream."""
+        n = C.c_ulonglong()
+        check(_lib.lib().rslf_sweep_withheld(self._h, C.byref(n)), "rslf_sweep_withheld")
+        return int(n.value)
 
     def close(self) -> None:
         # at interpreter shutdown the HIP runtime may already be gone: leave the handle to the OS
@@ -928,12 +957,13 @@ class MultiDevice:
         return out
 
     def depth2d(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
-                parameters: Depth1DParameters | None = None, subgrid: bool = False, peaks=None) -> dict:
+                parameters: Depth1DParameters | None = None, subgrid: bool = False, peaks=None, propagation_ratio=None) -> dict:
         """Depth2DComputer (constructor + run + getters) over this object's devices: the 2-D sweep cut into one block of
         scanlines per device, the neighbours' boundary rows exchanged by peer copy on every visit
         (rslf_multi_depth2d_run_f32 / _u8 / _u16).  Host EPIs in, numpy planes [S, V, U] out."""
         require_no_subgrid(subgrid, "MultiDevice.depth2d")
         require_no_peaks(peaks, "MultiDevice.depth2d")
+        require_no_propagation_ratio(propagation_ratio, "MultiDevice.depth2d")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((S, V, U), np.float32), edge_mask=np.empty((S, V, U), np.uint8),
                    disp_confidence=np.empty((S, V, U), np.float32), depth=np.empty((S, V, U), np.float32),
@@ -958,11 +988,12 @@ class MultiDevice:
 
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                       subgrid: bool = False, peaks=None):
+                       subgrid: bool = False, peaks=None, propagation_ratio=None):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
         require_no_peaks(peaks, "MultiDevice.fine_to_coarse")
+        require_no_propagation_ratio(propagation_ratio, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
@@ -1049,7 +1080,8 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
                          a_best_depth_s_v_u: torch.Tensor, a_rbar_s_v_u: torch.Tensor,
                          a_parameters: Depth1DParameters | None = None, *, scan_mask_s_v_u: torch.Tensor | None = None,
                          want_stats: bool = False, a_line_confidence_s_v_u: torch.Tensor | None = None,
-                         subgrid: bool = False, peaks: "Peaks | None" = None) -> RslfStats | None:
+                         subgrid: bool = False, peaks: "Peaks | None" = None,
+                         propagation_ratio: float | None = None) -> RslfStats | None:
     """core.hpp:336-351.  a_line_confidence_s_v_u ([S,V,U] f32, pass zeros) is the argument of the
     _USE_LINE_CONFIDENCE_SCORE build (:345): with it the call goes through rslf_depth_epi_2d_lc in
     a_parameters.par_line_confidence_mode -- mode 0 is then the default build and leaves the plane untouched; modes 1 and 2
@@ -1061,7 +1093,14 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
     members may be None) -- every pixel a visit scans and accepts gets the winner and the runner-up peak of its score row,
     every pixel a visit paints its source's; the others keep what the planes held (rslf_depth_epi_2d_pk).  a_dim_d above
     2 ** 24 is refused.  Where the later visits still scan a large share of a view, Context.set_debug(peaks_list=0) is the
-    faster form (include/rslf_hip.h, rslf_sweep_peaks)."""
+    faster form (include/rslf_hip.h, rslf_sweep_peaks).
+    propagation_ratio (not in the reference; None or 0: off; else r in (0, 1], needs `peaks` with all four planes): a pixel
+    whose runner-up scores more than r times its winner is withheld from propagation -- it makes no claim, keeps its raw
+    disparity and stays in the running mask (rslf_depth_epi_2d_pr; the rule: include/rslf_hip.h,
+    rslf_sweep_propagation_ratio).  Context.get_withheld_sources() then tells how many sources the sweep withheld."""
+    ratio = _propagation_ratio(propagation_ratio, "compute_2D_depth_epi")
+    if ratio and (peaks is None or any(getattr(peaks, k) is None for k in ("idx", "score", "runner_idx", "runner_score"))):
+        raise ValueError("compute_2D_depth_epi: propagation_ratio reads the peak planes: pass peaks= with all four planes")
     par = a_parameters or Depth1DParameters()
     p = par.to_c()
     planes = isinstance(a_dmin_s_v_u, torch.Tensor)
@@ -1075,8 +1114,12 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
     mode = int(par.par_line_confidence_mode)
     if peaks is not None:
         c_pk = _sweep_peak_planes(peaks, vol.S, vol.V, vol.U)
-        check(_lib.lib().rslf_depth_epi_2d_pk(*args, mode, _ptr(a_line_confidence_s_v_u), 1 if subgrid else 0, C.byref(c_pk)),
-              "rslf_depth_epi_2d_pk")
+        if ratio:
+            check(_lib.lib().rslf_depth_epi_2d_pr(*args, mode, _ptr(a_line_confidence_s_v_u), 1 if subgrid else 0, C.byref(c_pk), ratio),
+                  "rslf_depth_epi_2d_pr")
+        else:
+            check(_lib.lib().rslf_depth_epi_2d_pk(*args, mode, _ptr(a_line_confidence_s_v_u), 1 if subgrid else 0, C.byref(c_pk)),
+                  "rslf_depth_epi_2d_pk")
     elif subgrid:
         check(_lib.lib().rslf_depth_epi_2d_sub(*args, mode, _ptr(a_line_confidence_s_v_u), 1), "rslf_depth_epi_2d_sub")
     elif a_line_confidence_s_v_u is None and mode == LINE_CONF_OFF:
@@ -1092,8 +1135,14 @@ class Depth2DComputer:
 
     def __init__(self, epis, dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, verbose: bool = False, ctx: Context | None = None,
-                 subgrid: bool = False, peaks: bool = False):
+                 subgrid: bool = False, peaks: bool = False, propagation_ratio: float | None = None):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        # not in the reference: ambiguous pixels are withheld from propagation (rslf_sweep_propagation_ratio;
+        # get_withheld_sources); reads the peak planes
+        self.m_propagation_ratio = _propagation_ratio(propagation_ratio, "Depth2DComputer")
+        if self.m_propagation_ratio and not peaks:
+            raise ValueError("Depth2DComputer: propagation_ratio reads the peak planes: pass peaks=True")
+        self.m_withheld: int | None = None
         # not in the reference: run() also fills the winner and the runner-up peak of every scanned or painted pixel
         # (rslf_sweep_peaks; get_peaks_s_v_u)
         self.m_peaks = bool(peaks)
@@ -1150,8 +1199,13 @@ class Depth2DComputer:
                                        None, torch.empty(shape, dtype=torch.int32, device=dev),
                                        torch.empty(shape, dtype=torch.float32, device=dev))
             c_pk = _sweep_peak_planes(self.m_peaks_s_v_u, *shape)
-            check(_lib.lib().rslf_depth2d_run_pk(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1 if self.m_subgrid else 0,
-                                                 C.byref(c_pk)), "rslf_depth2d_run_pk")
+            if self.m_propagation_ratio:
+                check(_lib.lib().rslf_depth2d_run_pr(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1 if self.m_subgrid else 0,
+                                                     C.byref(c_pk), self.m_propagation_ratio), "rslf_depth2d_run_pr")
+            else:
+                check(_lib.lib().rslf_depth2d_run_pk(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1 if self.m_subgrid else 0,
+                                                     C.byref(c_pk)), "rslf_depth2d_run_pk")
+            self.m_withheld = None   # read on demand: the count waits for the stream
         elif self.m_subgrid:
             check(_lib.lib().rslf_depth2d_run_sub(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1), "rslf_depth2d_run_sub")
         elif mode == LINE_CONF_OFF:
@@ -1177,6 +1231,22 @@ class Depth2DComputer:
         if self.m_peaks_s_v_u is None:
             raise ValueError("get_peaks_s_v_u: run() first")
         return self.m_peaks_s_v_u
+
+    def get_propagation_ratio(self) -> float:
+        return self.m_propagation_ratio
+
+    def get_withheld_sources(self) -> int:
+        """Not in the reference: after run(), the sources the sweep withheld from propagation -- pixels that passed the
+        reference's gate and whose peaks were ambiguous at propagation_ratio, summed over the visits; 0 without the ratio.
+        Waits for the stream the first time.  Another sweep on the same context in between takes the count's place: ask
+        before it."""
+        if self.m_peaks and self.m_peaks_s_v_u is None:
+            raise ValueError("get_withheld_sources: run() first")
+        if not self.m_propagation_ratio:
+            return 0
+        if self.m_withheld is None:
+            self.m_withheld = self.m_epis.ctx.get_withheld_sources()
+        return self.m_withheld
 
     def set_accept_all(self, b: bool) -> None:
         self.m_accept_all = bool(b)
@@ -1538,6 +1608,7 @@ class KeptFineToCoarse:
         self.subgrid = bool(_lib.lib().rslf_f2c_run_subgrid(self._h))   # every level was swept in the sub-grid mode
         self.peaks = bool(_lib.lib().rslf_f2c_run_peaks(self._h))       # the run holds peak planes (get_peaks, get_fused_peaks)
         self.uniqueness_ratio = float(_lib.lib().rslf_f2c_run_uniqueness(self._h))   # 0.0: validity by uniqueness was off
+        self.propagation_ratio = float(_lib.lib().rslf_f2c_run_propagation_ratio(self._h))   # 0.0: the sweeps were not gated
 
     def describe(self) -> "_lib.RslfF2cRunDesc":
         d = _lib.RslfF2cRunDesc()
@@ -1575,6 +1646,13 @@ class KeptFineToCoarse:
             raise ValueError("get_peaks: this run was made without peaks=True")
         return Peaks(self.plane(level, "pk_idx"), self.plane(level, "pk_score"), None, self.plane(level, "pk_runner_idx"),
                      self.plane(level, "pk_runner_score"))
+
+    def withheld(self, level: int) -> int:
+        """Not in the reference: the sources the sweep of `level` withheld from propagation (propagation_ratio); 0 on every
+        level of a run made without the ratio."""
+        n = C.c_ulonglong()
+        check(_lib.lib().rslf_f2c_run_withheld(self._h, int(level), C.byref(n)), "rslf_f2c_run_withheld")
+        return int(n.value)
 
     def get_fused_peaks(self) -> tuple["Peaks", torch.Tensor]:
         """Not in the reference: (Peaks [S,V,U], fused_level [S,V,U] uint8) at the finest size -- for every pixel of the fused
@@ -1625,7 +1703,7 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                             parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                             ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False, keep: bool = False,
                             validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None,
-                            uniqueness_ratio: float | None = None):
+                            uniqueness_ratio: float | None = None, propagation_ratio: float | None = None):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -1641,8 +1719,17 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     peaks=True (not in the reference; keep=True only: rslf_f2c_run_host_pk): every level's sweep also runs in the peaks mode
     and the run keeps every level's peak planes and the fused peaks (KeptFineToCoarse.get_peaks / get_fused_peaks).
     uniqueness_ratio (None or 0: off; else in (0, 1], needs peaks=True): a level's valid pixels whose runner-up scores more
-    than ratio * the winner's score become invalid, so a coarser level decides them."""
+    than ratio * the winner's score become invalid, so a coarser level decides them.
+    propagation_ratio (None or 0: off; else in (0, 1], needs keep=True and peaks=True; rslf_f2c_run_host_pr): every level's
+    sweep withholds such pixels from propagation (Depth2DComputer); independent of uniqueness_ratio, both may be set.
+    KeptFineToCoarse.propagation_ratio and .withheld(level) read it back."""
     want_peaks = peaks is not None and peaks is not False
+    want_gate = _ratio_on(propagation_ratio)
+    if want_gate and not keep:
+        raise ValueError("fine_to_coarse_run_host: propagation_ratio reads the peaks planes of a kept run: pass keep=True, peaks=True")
+    if want_gate and not want_peaks:
+        raise ValueError("fine_to_coarse_run_host: propagation_ratio reads the peaks planes: pass peaks=True")
+    gate = _propagation_ratio(propagation_ratio, "fine_to_coarse_run_host")
     want_ratio = uniqueness_ratio is not None and uniqueness_ratio != 0
     if not keep:
         if want_ratio:
@@ -1667,7 +1754,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
         args = (ctx._h, ptrs, _ELEM[np.dtype(dt)], V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
                 float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
                 int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
-        if want_peaks:
+        if want_peaks and gate:
+            check(L.rslf_f2c_run_host_pr(*args, 1 if subgrid else 0, 1, float(uniqueness_ratio or 0.0), gate), "rslf_f2c_run_host_pr")
+        elif want_peaks:
             check(L.rslf_f2c_run_host_pk(*args, 1 if subgrid else 0, 1, float(uniqueness_ratio or 0.0)), "rslf_f2c_run_host_pk")
         elif subgrid:
             check(L.rslf_f2c_run_host_sub(*args, 1), "rslf_f2c_run_host_sub")
@@ -1724,8 +1813,10 @@ class FineToCoarse:
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                 ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None):
+                 ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None,
+                 propagation_ratio=None):
         require_no_peaks(peaks, "FineToCoarse")   # (the pyramid's levels carry no peak planes)
+        require_no_propagation_ratio(propagation_ratio, "FineToCoarse")
         self.m_parameters = parameters or Depth1DParameters.get_default()
         self.m_subgrid = bool(subgrid)   # not in the reference: every level's sweep in the sub-grid mode (Depth2DComputer)
         f2c_line_mode(self.m_parameters, line_confidence_mode, "FineToCoarse")
