@@ -148,6 +148,8 @@ int rslf_ctx_synchronize(rslf_ctx* ctx);
  *                    list over that list | 0 every visit refines over the whole plane (k9_subgrid_refine), the same bits
  *   "peaks_list"     1 (default) a 2-D sweep in the peaks mode (rslf_sweep_peaks) takes the peaks of a visit whose scan took the
  *                    packed list over that list (k10_peaks_list) | 0 every visit takes the dense form, the same bits
+ *   "consistency_order"  0 (default) rslf_view_consistency's workgroups in scanline order, the scanlines dealt to the XCDs in
+ *                    turn | 1 scanline order as dispatched | 2 the planes' own order (profiles/r19_consistency.md)
  *   "stream_share"   63-pixel tiles sharing taps between lanes in the streaming kernel: 1 (default) where the samples gathered
  *                    again on every pass are at least a quarter of the views | 0 never | 2 always
  *   "stream_groups"  0 automatic | hypothesis groups per tile of the streaming kernel's dense launches
@@ -966,6 +968,53 @@ int rslf_f2c_run_withheld(const rslf_f2c_run* run, int level, unsigned long long
 int rslf_f2c_unique_mask(rslf_ctx* ctx, uint8_t* d_valid, const rslf_peaks* d_pk, float ratio, size_t n);
 int rslf_f2c_fuse_peaks(rslf_ctx* ctx, const uint8_t* const* d_valid, const rslf_peaks* d_pk, const int* Vp, const int* Up,
                         int P, int S, const rslf_peaks* d_out_svu, uint8_t* d_out_level_svu);
+
+/* ---- cross-view consistency of a sweep's disparity planes (K12) -------- */
+/* Not in the reference, whose classes judge a pixel inside its own view (C_e, C_d, C_l): do the views of a finished sweep
+ * agree with one another?  A pixel (s, v, u) of disparity d lies, in view t, at column u + (int)roundf(d * (s - t) * slope) of
+ * the same scanline -- the propagation's column rule with the pixel's own view for s_hat, both products single and unfused.
+ * ok(s, v, u): d_valid_svu is NULL or non-zero there and the disparity is finite.  For an ok pixel and every view t != s in
+ * ascending order (radius > 0: only |t - s| <= radius; radius <= 0: every view):
+ *   out of field   !(|offset| < 1e9f) -- a NaN included; nothing is converted to int then -- or a column outside [0, U)
+ *   seen           the views in field
+ *   agree          ... whose pixel there is ok and within tol of d (|d_t - d| <= tol); its disparity joins a running sum
+ *   above          ... whose pixel is ok and d_t - d > tol
+ *   below          ... whose pixel is ok otherwise
+ *   fused          (d + the agreeing disparities, added in ascending t) / (float)(1 + agree): the same bits wherever computed
+ *   valid_out      255 where agree >= min_agree, else 0
+ * A pixel that is not ok has four counts of 0, fused 0.0f and valid_out 0, and is never agree / above / below for another
+ * (the view that shows it still counts as seen).  `above` and `below` stay apart because their meaning depends on the
+ * field's sign convention: with disparities that grow towards the camera, a neighbour above is a legitimate occluder and one
+ * below a free-space violation; the caller decides.  The rule is stated once, in csrc/k12_consistency_rule.hpp.
+ * Planes are [S][V][U]; every output is nullable, not all six; only the planes asked for are written.  No output plane may be
+ * an input plane -- d_valid_out_svu may NOT alias d_valid_svu: a thread reads the other views' rows while they are written --
+ * and equal pointers are RSLF_ERR_INVALID_ARG, as are a NULL depth plane, S, V or U below 1, a tol that is negative or not
+ * finite, and a negative min_agree.  RSLF_ERR_UNSUPPORTED: U above 2^30, or more 256-column segments (8 * ceil(V / 8) * S *
+ * ceil(U / 256)) than one launch's grid holds.  One launch, enqueued on the context's stream, not awaited; no scratch. */
+typedef struct rslf_view_counts {
+    int32_t* seen;     /* [S][V][U], each nullable */
+    int32_t* agree;
+    int32_t* above;
+    int32_t* below;
+} rslf_view_counts;
+int rslf_view_consistency(rslf_ctx* ctx, const float* d_depth_svu, const uint8_t* d_valid_svu, int S, int V, int U, float slope,
+                          float tol, int radius, int min_agree, const rslf_view_counts* d_out, float* d_fused_svu,
+                          uint8_t* d_valid_out_svu);
+/* The same with every plane on the HOST (d_out -> h_out: host planes): uploads through the context's grow-only staging,
+ * runs the launch, downloads the planes asked for and waits.  Refused while a sweep is open on the context. */
+int rslf_view_consistency_host(rslf_ctx* ctx, const float* h_depth_svu, const uint8_t* h_valid_svu, int S, int V, int U, float slope,
+                               float tol, int radius, int min_agree, const rslf_view_counts* h_out, float* h_fused_svu,
+                               uint8_t* h_valid_out_svu);
+/* The same on a kept fine-to-coarse run's planes, read in place: RSLF_F2C_PLANE_DEPTH / _VALID of `level`, or -- with
+ * fused_result != 0, which needs level 0 -- RSLF_F2C_PLANE_FUSED_MAP / _FUSED_VALID.  The slope is the factor the level's sweep
+ * propagated with (U_level / U_0, which the run keeps; 1 for the fused planes).  Outputs: device planes [S][V_level][U_level].
+ * ctx: any context of the run's device; enqueued on its stream, not awaited. */
+int rslf_f2c_run_consistency(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, float tol, int radius, int min_agree,
+                             const rslf_view_counts* d_out, float* d_fused_svu, uint8_t* d_valid_out_svu);
+/* ... and with the result planes on the HOST (what rslfx::FineToCoarse holds): staged through the context's grow-only
+ * scratch, copied out, awaited.  Refused while a sweep is open on the context. */
+int rslf_f2c_run_consistency_host(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, float tol, int radius,
+                                  int min_agree, const rslf_view_counts* h_out, float* h_fused_svu, uint8_t* h_valid_out_svu);
 
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit

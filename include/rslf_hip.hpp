@@ -266,6 +266,32 @@ inline Context& own(Context* ctx)   // the context an object was built on
 
 // Several devices (or several workers on one device) behind one handle: the pile path then cuts the scanlines into one
 // block per device and overlaps upload, kernels and download chunk by chunk (rslf_hip.h, rslf_multi_*).
+// Not in the reference: the result of the cross-view consistency check (rslf_view_consistency, rslf_hip.h), [S][V][U] each
+// -- per pixel the other views in field (seen), those whose pixel on the pixel's EPI line is valid and within tol (agree),
+// more than tol above, more than tol below; fused, the mean of the pixel's disparity and the agreeing ones; valid, 255
+// where agree >= min_agree.  What above and below mean depends on the field's sign convention (rslf_hip.h).
+struct Consistency {
+    std::vector<int32_t> seen, agree, above, below;
+    std::vector<float> fused;
+    std::vector<uint8_t> valid;
+};
+
+namespace detail {
+// n cells each, and the C struct of the four count planes
+inline rslf_view_counts consistency_planes(Consistency& c, size_t n)
+{
+    c.seen.resize(n), c.agree.resize(n), c.above.resize(n), c.below.resize(n), c.fused.resize(n), c.valid.resize(n);
+    const rslf_view_counts counts = {c.seen.data(), c.agree.data(), c.above.data(), c.below.data()};
+    return counts;
+}
+// the getters' default tolerance: one step of the hypothesis grid
+inline float grid_step(float dmin, float dmax, int dim_d)
+{
+    require(dim_d >= 2, "get_consistency: one hypothesis has no grid step: pass tol");
+    return (float)(((double)dmax - (double)dmin) / (dim_d - 1));
+}
+}  // namespace detail
+
 class MultiContext {
 public:
     MultiContext() : h_(nullptr) { check(rslf_multi_create(nullptr, 0, &h_), "rslf_multi_create"); }
@@ -767,6 +793,42 @@ public:
         return withheld_;
     }
     const std::vector<float>& get_depths_s_v_u() const { return m_best_depth_s_v_u; }
+    // dc.hpp:893-915, default build: C_e > edge threshold -- or, with RSLF_LINE_CONF_GATE and without
+    // par_use_disp_confidence_score, C_l > line threshold (dc.hpp:904)
+    std::vector<uint8_t> get_valid_depths_mask_s_v_u() const
+    {
+        detail::require(!m_best_depth_s_v_u.empty(), "the getters show the results of run(): call it first");
+        const bool by_line = !m_parameters.par_use_disp_confidence_score && m_parameters.par_line_confidence_mode == RSLF_LINE_CONF_GATE;
+        const std::vector<float>& score = by_line ? m_line_confidence_s_v_u : m_edge_confidence_s_v_u;
+        const float thr = by_line ? m_parameters.par_line_score_threshold : m_parameters.par_edge_score_threshold;
+        std::vector<uint8_t> mask(score.size());
+        for (size_t i = 0; i < mask.size(); i++)
+            mask[i] = score[i] > thr ? 255 : 0;
+        return mask;
+    }
+    // Not in the reference: after run(), do the views agree with one another (rslf_view_consistency_host, rslf_hip.h)?  The
+    // disparity planes with the sweep's own slope factor; tol < 0: one step of the hypothesis grid, (dmax - dmin) / (dim_d - 1);
+    // mask (nullable, [S][V][U]): get_valid_depths_mask_s_v_u().  An object built on a MultiContext takes the Context to run on.
+    Consistency get_consistency(Context& on, float tol = -1.f, int radius = 0, int min_agree = 0, const uint8_t* mask = nullptr) const
+    {
+        detail::require(!m_best_depth_s_v_u.empty(), "the getters show the results of run(): call it first");
+        std::vector<uint8_t> own_mask;
+        if (!mask) {
+            own_mask = get_valid_depths_mask_s_v_u();
+            mask = own_mask.data();
+        }
+        Consistency out;
+        const rslf_view_counts counts = detail::consistency_planes(out, m_best_depth_s_v_u.size());
+        check(rslf_view_consistency_host(on.get(), m_best_depth_s_v_u.data(), mask, dim_s_, dim_v_, dim_u_, m_parameters.par_slope_factor,
+                                         tol < 0.f ? detail::grid_step(m_dmin, m_dmax, m_dim_d) : tol, radius, min_agree, &counts,
+                                         out.fused.data(), out.valid.data()),
+              "rslf_view_consistency_host");
+        return out;
+    }
+    Consistency get_consistency(float tol = -1.f, int radius = 0, int min_agree = 0, const uint8_t* mask = nullptr) const
+    {
+        return get_consistency(detail::own(ctx_), tol, radius, min_agree, mask);
+    }
 
     // dc.hpp:808-856: the S x U slice of the disparities at scanline a_v (< 0: floor(V / 2.0)) over its own min / max,
     // colour-mapped, black outside the mask; no line drawing -> [S][U][3].  The slice is read through its row stride.
@@ -1021,6 +1083,27 @@ public:
         std::vector<uint8_t> out((size_t)dim_s_ * dim_v_ * dim_u_);
         check(rslf_f2c_run_copy(run_, 0, RSLF_F2C_PLANE_FUSED_LEVEL, out.data(), 1, nullptr), "rslf_f2c_run_copy");
         return out;
+    }
+    // Not in the reference: after a run() that followed keep_on_device, the cross-view consistency of a kept plane pair, read
+    // in place on the device (rslf_f2c_run_consistency_host, rslf_hip.h): the fused map and its validity (fused_result, which
+    // needs level 0) or a level's disparities and validity, with the slope factor the level's sweep ran with.  tol < 0: one
+    // step of the hypothesis grid.  -> planes [S][V_level][U_level].  An object built on a MultiContext has no kept run.
+    Consistency get_consistency(Context& on, int level = 0, bool fused_result = true, float tol = -1.f, int radius = 0,
+                                int min_agree = 0) const
+    {
+        detail::require(run_ != nullptr, "get_consistency reads a kept run's planes on the device: call keep_on_device before run()");
+        detail::require(level >= 0 && level < (int)dims_.size(), "get_consistency: the level is not in the pyramid");
+        Consistency out;
+        const rslf_view_counts counts = detail::consistency_planes(out, (size_t)dim_s_ * dims_[level].first * dims_[level].second);
+        check(rslf_f2c_run_consistency_host(run_, on.get(), level, fused_result ? 1 : 0,
+                                            tol < 0.f ? detail::grid_step(d_min_, d_max_, dim_d_) : tol, radius, min_agree, &counts,
+                                            out.fused.data(), out.valid.data()),
+              "rslf_f2c_run_consistency_host");
+        return out;
+    }
+    Consistency get_consistency(int level = 0, bool fused_result = true, float tol = -1.f, int radius = 0, int min_agree = 0) const
+    {
+        return get_consistency(detail::own(ctx_), level, fused_result, tol, radius, min_agree);
     }
     ~FineToCoarse() { rslf_f2c_run_destroy(run_); }
     FineToCoarse(const FineToCoarse&) = delete;

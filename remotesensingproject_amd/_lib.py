@@ -63,6 +63,8 @@ SYMBOLS = [
     # the sweep gate: ambiguous pixels withheld from propagation by peak ratio
     "rslf_sweep_propagation_ratio", "rslf_sweep_withheld", "rslf_depth_epi_2d_pr", "rslf_depth2d_run_pr", "rslf_depth2d_run_host_pr",
     "rslf_f2c_run_host_pr", "rslf_f2c_run_propagation_ratio", "rslf_f2c_run_withheld",
+    # cross-view consistency of a sweep's disparity planes (K12)
+    "rslf_view_consistency", "rslf_view_consistency_host", "rslf_f2c_run_consistency", "rslf_f2c_run_consistency_host",
 ]
 
 
@@ -116,6 +118,12 @@ class RslfPeaks(C.Structure):
     _fields_ = [
         ("idx", C.c_void_p), ("score", C.c_void_p), ("disp", C.c_void_p), ("runner_idx", C.c_void_p), ("runner_score", C.c_void_p),
     ]
+
+
+class RslfViewCounts(C.Structure):
+    """rslf_view_counts: the four count planes of the cross-view consistency check, int32 [S][V][U], each nullable."""
+
+    _fields_ = [("seen", C.c_void_p), ("agree", C.c_void_p), ("above", C.c_void_p), ("below", C.c_void_p)]
 
 
 class RslfF2cLevelsOut(C.Structure):
@@ -320,6 +328,10 @@ def lib():
     L.rslf_f2c_run_propagation_ratio.argtypes = [vp]
     L.rslf_f2c_run_propagation_ratio.restype = cf
     L.rslf_f2c_run_withheld.argtypes = [vp, ci, C.POINTER(C.c_ulonglong)]
+    L.rslf_view_consistency.argtypes = [vp, vp, vp, ci, ci, ci, cf, cf, ci, ci, C.POINTER(RslfViewCounts), vp, vp]
+    L.rslf_view_consistency_host.argtypes = L.rslf_view_consistency.argtypes
+    L.rslf_f2c_run_consistency.argtypes = [vp, vp, ci, ci, cf, ci, ci, C.POINTER(RslfViewCounts), vp, vp]
+    L.rslf_f2c_run_consistency_host.argtypes = L.rslf_f2c_run_consistency.argtypes
     L.rslf_f2c_run_peaks.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.restype = cf

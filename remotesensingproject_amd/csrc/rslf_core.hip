@@ -259,6 +259,8 @@ extern "C" int rslf_ctx_set_debug(rslf_ctx* ctx, const char* key, int value) RSL
         ctx->subgrid_list = value;
     else if (strcmp(key, "peaks_list") == 0 && (value == 0 || value == 1))
         ctx->peaks_list = value;
+    else if (strcmp(key, "consistency_order") == 0 && value >= 0 && value <= 2)
+        ctx->consistency_order = value;
     else if (strcmp(key, "time_all") == 0 && (value == 0 || value == 1)) {
         ctx->time_all = value;
         ctx->ev_used = 0;

@@ -332,6 +332,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         lv.U = kl.U = dims[l].U;
         lv.params = *p;
         lv.params.slope_factor = (float)((0.0 + lv.U) / U);              // f2c.hpp:139
+        kl.slope = lv.params.slope_factor;
         const size_t n = (size_t)S * lv.V * lv.U;
         rc = f2c_level_scale(ctx, elem, raw.as<const float>(), n * C, epi_scale_factor, &lv.scale);
         if (rc)

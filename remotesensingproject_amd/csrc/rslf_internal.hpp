@@ -14,10 +14,11 @@
 //   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters
 //   rslf_f2c_peaks.hip    a kept run's peak planes: validity by uniqueness and the fused peaks (k11_f2c_peaks.hpp)
 //   rslf_render.hip       the getters' pictures: fit, plane render, EPI line painter (K6)
+//   rslf_consistency.hip  cross-view consistency of a sweep's disparity planes: counts, fused value, validity (k12_consistency.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
-//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp   ... continued, for the units that need them
+//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp, rslf_plan_consistency.hpp   ... continued, for the units that need them
 //   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
 //
 // Two rules of the multi-device paths: they never write into a rslf_volume they did not create (a chunk of another height
@@ -335,6 +336,7 @@ struct rslf_ctx {
     int peaks_list = 1;        // 2-D sweep in the peaks mode: sparse visits take k10_peaks_list over the packed list (0: every visit the dense form; A/B and tests)
     int claim_skip = 1;        // 2-D sweep: the claims skip views with nothing left to paint within reach (0: off, A/B and tests)
     int staging_kib = 0;       // chunked host upload: device staging per pass in KiB (0: plan::kStagingBudget; tests of the later passes)
+    int consistency_order = 0; // K12: the grid's order (k12_consistency.hpp, ConsistencyOrder; 0: scanlines dealt to the XCDs; A/B and tests)
 };
 
 struct rslf_volume {
@@ -544,6 +546,7 @@ struct F2cLevel {
 struct F2cKeptLevel {
     int V = 0, U = 0;
     float scale = 1.0f;                 // the level's epi_scale_factor as used
+    float slope = 1.0f;                 // the slope factor the level's sweep ran with (f2c.hpp:139; rslf_f2c_run_consistency)
     DevBuf depth, valid, Ce, Cl;        // [S][V][U]: disparities, validity bytes, edge and line confidence (C_l empty when off)
     DevBuf Cd;                          // the disparity confidence (kept runs only)
     VolumePtr vol;                      // the normalised volume the sweep ran on (kept runs with volumes only)

@@ -156,7 +156,7 @@ class Context:
 
     _DEBUG_DEFAULTS = dict(force_scan=0, force_groups=0, force_packed=-1, px=-1, stream_share=1, stream_groups=0, stream_lds_kib=80,
                            claim_skip=1, time_all=0, row_split=1, staging_kib=0, tap_table=1, scalar_taps=1,
-                           subgrid_list=1, peaks_list=1)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
+                           subgrid_list=1, peaks_list=1, consistency_order=0)   # = the library's own defaults (rslf_internal.hpp, plan::kStreamLdsBytes)
     _FORCE_SCAN = {None: 0, "auto": 0, "generic": 1, "stream": 2}
 
     def set_debug(self, **hooks) -> None:
@@ -1011,6 +1011,9 @@ class MultiDevice:
         self.stats = st
         return out_map, out_valid, int(nl.value)
 
+    def get_consistency(self, *args, **kwargs):
+        no_consistency("MultiDevice")
+
     def depth1d_pile_device_out(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, out_device: int = 0,
                                 s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None,
                                 subgrid: bool = False) -> dict:
@@ -1127,6 +1130,71 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
     else:
         check(_lib.lib().rslf_depth_epi_2d_lc(*args, mode, _ptr(a_line_confidence_s_v_u)), "rslf_depth_epi_2d_lc")
     return st
+
+
+class Consistency(NamedTuple):
+    """Cross-view consistency of a sweep's disparity planes, [S, V, U] each (include/rslf_hip.h, rslf_view_consistency, states
+    the rule): per pixel the other views that are in field (seen) and, of those, the ones whose pixel on the pixel's EPI line
+    is valid and within tol (agree), more than tol above, more than tol below; fused, the mean of the pixel's disparity and
+    the agreeing ones; valid, 255 where agree >= min_agree.  What above and below mean depends on the field's sign
+    convention: with disparities that grow towards the camera, above is a legitimate occluder and below a free-space
+    violation."""
+    seen: Optional[torch.Tensor]
+    agree: Optional[torch.Tensor]
+    above: Optional[torch.Tensor]
+    below: Optional[torch.Tensor]
+    fused: Optional[torch.Tensor]
+    valid: Optional[torch.Tensor]
+
+
+def _consistency_args(tol, radius, min_agree, who: str) -> tuple[float, int, int]:
+    tol = float(tol)
+    if not 0.0 <= tol <= float(np.finfo(np.float32).max):   # (a NaN compares false; finite as the float32 it is sent as)
+        raise ValueError("%s: tol %r is not a finite tolerance >= 0" % (who, tol))
+    if int(min_agree) < 0:
+        raise ValueError("%s: min_agree %r is negative" % (who, min_agree))
+    return tol, int(radius), int(min_agree)
+
+
+def _consistency_out(shape, device, counts: bool, fused: bool) -> tuple[Consistency, _lib.RslfViewCounts]:
+    """The planes a consistency call writes (seen .. below with counts, fused with fused, valid always) and the C struct."""
+    new = lambda dtype: torch.empty(shape, dtype=dtype, device=device)
+    cs = [new(torch.int32) if counts else None for _ in range(4)]
+    out = Consistency(*cs, new(torch.float32) if fused else None, new(torch.uint8))
+    return out, _lib.RslfViewCounts(*(None if t is None else t.data_ptr() for t in cs))
+
+
+def view_consistency(ctx: Context, depth_s_v_u: torch.Tensor, valid_s_v_u: torch.Tensor | None, slope: float, tol: float,
+                     radius: int = 0, min_agree: int = 0, counts: bool = True, fused: bool = True) -> Consistency:
+    """rslf_view_consistency (not in the reference): do the views of a finished sweep agree with one another?  depth_s_v_u
+    [S, V, U] f32 and valid_s_v_u ([S, V, U] u8, or None for every pixel) on the context's device; slope: the sweep's
+    par_slope_factor; radius <= 0: every view, else only views within it.  Returns a Consistency of new tensors -- the four
+    counts are None with counts=False, fused with fused=False.  Queued on the context's stream, not awaited."""
+    tol, radius, min_agree = _consistency_args(tol, radius, min_agree, "view_consistency")
+    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
+        raise ValueError("view_consistency: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]")
+    if valid_s_v_u is not None and (valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8
+                                    or not valid_s_v_u.is_cuda or not valid_s_v_u.is_contiguous()):
+        raise ValueError("view_consistency: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape")
+    S, V, U = (int(x) for x in depth_s_v_u.shape)
+    out, c_counts = _consistency_out((S, V, U), depth_s_v_u.device, counts, fused)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_view_consistency(ctx._h, _ptr(depth_s_v_u), _ptr(valid_s_v_u), S, V, U, float(slope), tol, radius, min_agree,
+                                           C.byref(c_counts), _ptr(out.fused), _ptr(out.valid)), "rslf_view_consistency")
+    return out
+
+
+def no_consistency(who: str) -> None:
+    """The forms that have no consistency getter say so (no multi-device form before a multi-GPU lease)."""
+    raise ValueError("%s: get_consistency is not built here: bring the [S, V, U] planes to one device and call view_consistency, "
+                     "or use Depth2DComputer / fine_to_coarse_run_host(keep=True)" % who)
+
+
+def grid_step(dmin: float, dmax: float, dim_d: int, who: str) -> float:
+    """One step of the hypothesis grid, (dmax - dmin) / (dim_d - 1): the default tolerance of the consistency getters."""
+    if int(dim_d) < 2:
+        raise ValueError("%s: dim_d=%d has no grid step: pass tol" % (who, dim_d))
+    return (float(dmax) - float(dmin)) / (int(dim_d) - 1)
 
 
 class Depth2DComputer:
@@ -1303,6 +1371,22 @@ class Depth2DComputer:
             return (self.m_line_confidence_s_v_u > float(np.float32(self.m_parameters.par_line_score_threshold))).to(torch.uint8) * 255
         thr = -1.0 if self.m_accept_all else float(np.float32(self.m_parameters.par_edge_score_threshold))
         return (self.m_edge_confidence_s_v_u > thr).to(torch.uint8) * 255
+
+    def get_consistency(self, tol: float | None = None, radius: int = 0, min_agree: int = 0, mask: torch.Tensor | None = None,
+                        counts: bool = True, fused: bool = True) -> Consistency:
+        """Not in the reference: after run(), view_consistency of the disparity planes with the sweep's own slope factor.
+        tol=None: one step of the hypothesis grid, (dmax - dmin) / (dim_d - 1); mask=None: get_valid_depths_mask_s_v_u().
+        The sweep's planes are read, never written."""
+        tol = grid_step(self.m_dmin, self.m_dmax, self.m_dim_d, "get_consistency") if tol is None else tol
+        mask = self.get_valid_depths_mask_s_v_u() if mask is None else mask
+        return view_consistency(self.m_epis.ctx, self.m_best_depth_s_v_u, mask, float(np.float32(self.m_parameters.par_slope_factor)),
+                                tol, radius, min_agree, counts, fused)
+
+    def get_consistent_depths_mask_s_v_u(self, tol: float | None = None, radius: int = 0, min_agree: int = 1,
+                                         mask: torch.Tensor | None = None) -> torch.Tensor:
+        """Not in the reference: the `valid` plane of get_consistency alone -- 255 where the pixel is in `mask`, its disparity
+        is finite and at least min_agree other views agree with it -- [S, V, U] uint8; no other plane is computed."""
+        return self.get_consistency(tol, radius, min_agree, mask, counts=False, fused=False).valid
 
     def results(self) -> dict:
         torch.cuda.synchronize(self.m_epis.ctx.device)
@@ -1598,8 +1682,9 @@ class KeptFineToCoarse:
     coloured getters of rslf::FineToCoarse are rendered from the kept planes.  `ctx` is the context copies and renders are
     queued on: any context of the run's device."""
 
-    def __init__(self, handle, ctx: Context, stats: RslfStats):
+    def __init__(self, handle, ctx: Context, stats: RslfStats, grid: tuple | None = None):
         self._h, self.ctx, self.stats = handle, ctx, stats
+        self.grid = grid   # (d_min, d_max, dim_d) the run was made with: get_consistency's default tolerance
         d = self.describe()
         self.S, self.C, self.n_levels = d.S, d.C, d.n_levels
         self.dims = [(d.V[l], d.U[l]) for l in range(d.n_levels)]            # (V_p, U_p), finest first
@@ -1663,6 +1748,27 @@ class KeptFineToCoarse:
             raise ValueError("get_fused_peaks: this run was made without peaks=True")
         return (Peaks(self.plane(0, "fused_pk_idx"), self.plane(0, "fused_pk_score"), None, self.plane(0, "fused_pk_runner_idx"),
                       self.plane(0, "fused_pk_runner_score")), self.plane(0, "fused_level"))
+
+    def get_consistency(self, level: int = 0, fused_result: bool = True, tol: float | None = None, radius: int = 0,
+                        min_agree: int = 0, counts: bool = True, fused: bool = True) -> Consistency:
+        """Not in the reference: rslf_f2c_run_consistency -- view_consistency of a kept plane pair, read in place: the fused
+        map and its validity (fused_result=True, which needs level 0) or a level's depth / valid planes, with the slope
+        factor the level's sweep propagated with.  tol=None: one step of the run's hypothesis grid.  Returns a Consistency
+        of new [S, V_p, U_p] tensors; the run's planes are not written."""
+        if not 0 <= level < self.n_levels:
+            raise ValueError("level %d of %d" % (level, self.n_levels))
+        if fused_result and level != 0:
+            raise ValueError("get_consistency: the fused planes are at the finest size: level 0, or fused_result=False")
+        if tol is None:
+            if self.grid is None:
+                raise ValueError("get_consistency: this object does not know the run's hypothesis grid: pass tol")
+            tol = grid_step(*self.grid, "get_consistency")
+        tol, radius, min_agree = _consistency_args(tol, radius, min_agree, "get_consistency")
+        out, c_counts = _consistency_out((self.S,) + self.dims[level], self.ctx.device, counts, fused)
+        self.ctx.use_current_stream()
+        check(_lib.lib().rslf_f2c_run_consistency(self._h, self.ctx._h, int(level), 1 if fused_result else 0, tol, radius, min_agree,
+                                                  C.byref(c_counts), _ptr(out.fused), _ptr(out.valid)), "rslf_f2c_run_consistency")
+        return out
 
     def _render(self, name: str, shapes, *args, lut_bgr=None, stacked: bool = False):
         table = _table(lut_bgr)
@@ -1762,7 +1868,7 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
             check(L.rslf_f2c_run_host_sub(*args, 1), "rslf_f2c_run_host_sub")
         else:
             check(L.rslf_f2c_run_host(*args), "rslf_f2c_run_host")
-        return KeptFineToCoarse(h, ctx, st)
+        return KeptFineToCoarse(h, ctx, st, (float(d_min), float(d_max), int(dim_d)))
     if validity_rule != F2C_VALID_COMPAT:
         raise ValueError("fine_to_coarse_run_host: validity_rule needs keep=True")
     out_map, out_valid = np.empty((S, V, U), np.float32), np.empty((S, V, U), np.uint8)
@@ -1858,6 +1964,9 @@ class FineToCoarse:
         comps = self.m_computers
         return f2c_fuse(comps[0].m_epis.ctx, [c.m_best_depth_s_v_u.contiguous() for c in comps],
                         [c.get_valid_depths_mask_s_v_u().contiguous() for c in comps])
+
+    def get_consistency(self, *args, **kwargs):
+        no_consistency("FineToCoarse (the Python level loop)")
 
     def _fit_mode(self, saturate: bool) -> int:
         return FIT_QUANTILE if saturate else FIT_MEANSTD   # ImageConverter_uchar::fit(img, saturate), rslf_plot.cpp:65-98

@@ -391,6 +391,11 @@ class ShardedDepth2D:
         return dict(edge_confidence=self.Ce[:, o], edge_mask=self.cem[:, o], disp_confidence=self.Cd[:, o], depth=self.depth[:, o],
                     rbar=self.rbar[:, o], scan_mask=self.scan_mask[:, o])
 
+    def get_consistency(self, *args, **kwargs):
+        """A shard holds a block of scanlines and the check is local to a scanline, so it would shard; it is not built."""
+        from . import depth
+        depth.no_consistency("ShardedDepth2D")
+
     # -- helpers -------------------------------------------------------------------------------------------------------------
     @staticmethod
     def _L():
@@ -529,6 +534,10 @@ class ShardedFineToCoarse:
     def get_results(self):
         """f2c.hpp:302-324 on the gathered planes -> (out_map_s_v_u, out_validity_s_v_u) at the finest scale."""
         return self.rs.f2c_fuse(self.ctx, [lv["depth"] for lv in self.levels], [lv["valid"] for lv in self.levels])
+
+    def get_consistency(self, *args, **kwargs):
+        from . import depth
+        depth.no_consistency("ShardedFineToCoarse")
 
     @property
     def pixels_scanned(self) -> int:
