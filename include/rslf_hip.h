@@ -1016,6 +1016,51 @@ int rslf_f2c_run_consistency(const rslf_f2c_run* run, rslf_ctx* ctx, int level, 
 int rslf_f2c_run_consistency_host(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, float tol, int radius,
                                   int min_agree, const rslf_view_counts* h_out, float* h_fused_svu, uint8_t* h_valid_out_svu);
 
+/* ---- a kept run's validity by cross-view consistency (K13) -------------- */
+/* A third option of a kept run, off by default, not in the reference, one device only.  The validity rule, the uniqueness
+ * ratio and the sweep gate all judge a pixel inside its own view; this asks the other views, with the check above, while the
+ * pyramid is built.  With consistency_min_agree = m >= 1, after a level's sweep, its validity rule and -- if set -- its
+ * uniqueness ratio, a pixel that is still valid becomes invalid unless
+ *     consistency_gate(seen, agree, m)  :=  agree >= min(seen, m)
+ * with seen and agree as rslf_view_consistency counts them on the level's disparities, that validity (so a pixel the rule or
+ * the ratio made invalid neither votes nor is voted on), the level's slope factor, consistency_tol and consistency_radius.
+ * At least m of the views that can see the pixel agree with it; where fewer than m can see it, all of them do; a pixel no view
+ * can see (seen = 0) is kept -- unlike valid_out above (agree >= min_agree), the rule drops no pixel for lying where its EPI
+ * line leaves the field, and no outer view for the radius.  The plane then tightens the next level's ranges and feeds the
+ * fusion as ever: a contradicted pixel of a fine level is decided by a coarser one.  The level accept_all_last_scale accepts
+ * whole is not touched.  Order within a level: sweep, validity rule, uniqueness, this gate, the next level's ranges.
+ * rslf_f2c_run_host_cs is rslf_f2c_run_host_pr plus the three trailing arguments; consistency_min_agree = 0 is that entry,
+ * launch for launch and bit for bit (tol and radius are then not looked at).  It needs no peaks and combines with subgrid,
+ * peaks, both ratios, any line mode and either validity rule.  RSLF_ERR_INVALID_ARG, before anything is queued, the argument
+ * named in rslf_last_error(): a negative consistency_min_agree; with the gate on, a consistency_tol that is negative or not
+ * finite, or a sweep left open on the context.  RSLF_ERR_UNSUPPORTED, before anything is queued: rslf_view_consistency's grid limits at the finest level. */
+int rslf_f2c_run_host_cs(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                         int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                         rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio, float propagation_ratio,
+                         float consistency_tol, int consistency_radius, int consistency_min_agree);
+/* The options read back (each pointer nullable): zeros for NULL and for a run made without the gate. */
+int rslf_f2c_run_consistency_gate(const rslf_f2c_run* run, float* tol, int* radius, int* min_agree);
+/* The pixels the gate made invalid on `level`: 0 for a level accepted whole and for every level of a run made without the
+ * gate; RSLF_ERR_INVALID_ARG for a level the run does not have. */
+int rslf_f2c_run_inconsistent(const rslf_f2c_run* run, int level, unsigned long long* n);
+/* Two more planes for rslf_f2c_run_copy, int32 [S][V_l][U_l] of any gated level, reported as bits 16 and 17 of planes_held (a
+ * run without the gate keeps the planes_held and device_bytes it had): the gate's OWN counts at gate time, which explain a
+ * drop.  rslf_f2c_run_consistency run afterwards reads the gated validity and counts differently.  Asked of a run or a level
+ * that holds none (the level accepted whole): RSLF_ERR_INVALID_ARG, `which` named. */
+#define RSLF_F2C_PLANE_CS_AGREE 16
+#define RSLF_F2C_PLANE_CS_SEEN  17
+/* The gate as a device-pointer primitive, beside rslf_f2c_unique_mask: one launch, enqueued on the context's stream, not
+ * awaited; no scratch.  d_valid_svu is required (it is what the gate gates); d_valid_out_svu [S][V][U] receives the input byte
+ * where the pixel is kept -- a pixel that is not ok (byte 0, or a non-finite disparity) is kept as it is -- and 0 where it is
+ * dropped, and may NOT be d_valid_svu: a thread reads the other views' rows while they are written.  d_agree_svu / d_seen_svu
+ * (nullable): the two counts, 0 where the pixel is not ok.  d_dropped (nullable): a device counter the launch ADDS the number
+ * of pixels it made invalid to (one 64-bit atomic per 256-column segment that dropped any); the caller zeroes it.
+ * Refusals: rslf_view_consistency's, with min_agree >= 1 required. */
+int rslf_f2c_consistency_mask(rslf_ctx* ctx, const float* d_depth_svu, const uint8_t* d_valid_svu, int S, int V, int U, float slope,
+                              float tol, int radius, int min_agree, uint8_t* d_valid_out_svu, int32_t* d_agree_svu,
+                              int32_t* d_seen_svu, unsigned long long* d_dropped);
+
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit
  * exchanges the neighbours' boundary rows (median reach) of the visited view's raw disparities and edge mask by peer

@@ -1105,6 +1105,45 @@ public:
     {
         return get_consistency(detail::own(ctx_), level, fused_result, tol, radius, min_agree);
     }
+    // Not in the reference, to be called before run() and after keep_on_device: validity by cross-view consistency
+    // (rslf_f2c_run_host_cs, rslf_hip.h).  After a level's sweep, validity rule and uniqueness ratio, a pixel that is still
+    // valid becomes invalid unless agree >= min(seen, min_agree) among the other views (radius > 0: |t - s| <= radius), so the
+    // next level's ranges and the fusion leave it to a coarser level.  min_agree = 0 switches it off; tol < 0: one step of
+    // the hypothesis grid.  Needs no peaks.  One device only: throws on a MultiContext.
+    void set_consistency_gate(int min_agree, float tol = -1.f, int radius = 0)
+    {
+        if (multi_)
+            throw std::invalid_argument("set_consistency_gate: this object was built on a MultiContext: the pyramid's consistency gate is built for one context");
+        detail::require(keep_, "FineToCoarse: the consistency gate belongs to a kept run: call keep_on_device first");
+        detail::require(min_agree >= 0, "consistency gate: min_agree is 0 (off) or a count of agreeing views >= 1");
+        if (min_agree > 0 && tol < 0.f)
+            tol = detail::grid_step(d_min_, d_max_, dim_d_);
+        detail::require(min_agree == 0 || (tol >= 0.f && tol <= 3.402823466e+38f), "consistency gate: tol is a finite tolerance >= 0");
+        gate_min_agree_ = min_agree;
+        gate_tol_ = min_agree > 0 ? tol : 0.f;
+        gate_radius_ = min_agree > 0 ? radius : 0;
+    }
+    int get_consistency_min_agree() const { return gate_min_agree_; }
+    // After run() with the gate set: the pixels the gate made invalid on a level (0 on a level accepted whole), and the
+    // gate's own counts at gate time -- agree and seen [S][V_level][U_level], the other planes of the Consistency empty.
+    unsigned long long get_inconsistent(int level) const
+    {
+        detail::require(run_ != nullptr, "get_inconsistent: the counts are held by a kept run: keep_on_device, then run()");
+        unsigned long long n = 0;
+        check(rslf_f2c_run_inconsistent(run_, level, &n), "rslf_f2c_run_inconsistent");
+        return n;
+    }
+    Consistency get_gate_counts(int level) const
+    {
+        detail::require(run_ != nullptr && gate_held_, "get_gate_counts: the planes are held by a kept run made with set_consistency_gate");
+        detail::require(level >= 0 && level < (int)dims_.size(), "get_gate_counts: the level is not in the pyramid");
+        Consistency out;
+        const size_t n = (size_t)dim_s_ * dims_[level].first * dims_[level].second;
+        out.agree.resize(n), out.seen.resize(n);
+        check(rslf_f2c_run_copy(run_, level, RSLF_F2C_PLANE_CS_AGREE, out.agree.data(), 1, nullptr), "rslf_f2c_run_copy");
+        check(rslf_f2c_run_copy(run_, level, RSLF_F2C_PLANE_CS_SEEN, out.seen.data(), 1, nullptr), "rslf_f2c_run_copy");
+        return out;
+    }
     ~FineToCoarse() { rslf_f2c_run_destroy(run_); }
     FineToCoarse(const FineToCoarse&) = delete;
     FineToCoarse& operator=(const FineToCoarse&) = delete;
@@ -1280,7 +1319,16 @@ private:
         peaks_held_ = false;
         detail::require(peaks_ || uniqueness_ == 0.f, "FineToCoarse: the uniqueness ratio reads the peak planes: call set_peaks(true)");
         detail::require(peaks_ || propagation_ratio_ == 0.f, "FineToCoarse: the propagation ratio reads the peak planes: call set_peaks(true)");
-        if (peaks_ && propagation_ratio_ != 0.f) {
+        gate_held_ = false;
+        if (gate_min_agree_ > 0) {
+            check(rslf_f2c_run_host_cs(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
+                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
+                                       validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, peaks_ ? 1 : 0, uniqueness_,
+                                       propagation_ratio_, gate_tol_, gate_radius_, gate_min_agree_),
+                  "rslf_f2c_run_host_cs");
+            peaks_held_ = peaks_;
+            gate_held_ = true;
+        } else if (peaks_ && propagation_ratio_ != 0.f) {
             check(rslf_f2c_run_host_pr(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
                                        scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
                                        validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, 1, uniqueness_,
@@ -1431,6 +1479,9 @@ private:
     float uniqueness_ = 0.f;     // set_uniqueness_ratio
     float propagation_ratio_ = 0.f;   // set_propagation_ratio
     bool peaks_held_ = false;    // the kept run was made with peaks
+    int gate_min_agree_ = 0, gate_radius_ = 0;   // set_consistency_gate
+    float gate_tol_ = 0.f;
+    bool gate_held_ = false;     // the kept run was made with the consistency gate
     int validity_rule_;
     rslf_f2c_run* run_;          // the kept run, owned
 };

@@ -65,6 +65,8 @@ SYMBOLS = [
     "rslf_f2c_run_host_pr", "rslf_f2c_run_propagation_ratio", "rslf_f2c_run_withheld",
     # cross-view consistency of a sweep's disparity planes (K12)
     "rslf_view_consistency", "rslf_view_consistency_host", "rslf_f2c_run_consistency", "rslf_f2c_run_consistency_host",
+    # a kept fine-to-coarse run's validity by cross-view consistency (K13)
+    "rslf_f2c_run_host_cs", "rslf_f2c_run_consistency_gate", "rslf_f2c_run_inconsistent", "rslf_f2c_consistency_mask",
 ]
 
 
@@ -332,6 +334,10 @@ def lib():
     L.rslf_view_consistency_host.argtypes = L.rslf_view_consistency.argtypes
     L.rslf_f2c_run_consistency.argtypes = [vp, vp, ci, ci, cf, ci, ci, C.POINTER(RslfViewCounts), vp, vp]
     L.rslf_f2c_run_consistency_host.argtypes = L.rslf_f2c_run_consistency.argtypes
+    L.rslf_f2c_run_host_cs.argtypes = L.rslf_f2c_run_host_pr.argtypes + [cf, ci, ci]
+    L.rslf_f2c_run_consistency_gate.argtypes = [vp, C.POINTER(cf), C.POINTER(ci), C.POINTER(ci)]
+    L.rslf_f2c_run_inconsistent.argtypes = [vp, ci, C.POINTER(C.c_ulonglong)]
+    L.rslf_f2c_consistency_mask.argtypes = [vp, vp, vp, ci, ci, ci, cf, cf, ci, ci, vp, vp, vp, vp]
     L.rslf_f2c_run_peaks.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.restype = cf

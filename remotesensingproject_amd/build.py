@@ -33,11 +33,14 @@ UNITS = {
                        "rslf_plan_sweep_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_sweep_gate.hpp", "k11_f2c_peak_rule.hpp"],
     "rslf_sweep_peaks.hip": ["k2_scan.hpp", "k10_sweep_peaks.hpp", "k10_peak_merge.hpp", "k8_peak_rule.hpp", "rslf_plan_sweep_peaks.hpp",
                              "rslf_plan_peaks.hpp", "rslf_plan_subgrid.hpp"],
-    "rslf_f2c.hip": ["k5_f2c.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp"],
-    "rslf_f2c_keep.hip": ["rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_sweep_gate.hpp", "k11_f2c_peak_rule.hpp"],
+    "rslf_f2c.hip": ["k5_f2c.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_f2c_consistency.hpp",
+                     "rslf_plan_consistency.hpp", "k12_consistency_rule.hpp"],
+    "rslf_f2c_keep.hip": ["rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_sweep_gate.hpp", "k11_f2c_peak_rule.hpp",
+                          "rslf_plan_f2c_consistency.hpp", "rslf_plan_consistency.hpp", "k12_consistency_rule.hpp"],
     "rslf_f2c_peaks.hip": ["k11_f2c_peaks.hpp", "k11_f2c_peak_rule.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp"],
     "rslf_render.hip": ["k6_render.hpp", "rslf_plan_render.hpp"],
-    "rslf_consistency.hip": ["k12_consistency.hpp", "k12_consistency_rule.hpp", "rslf_plan_consistency.hpp"],
+    "rslf_consistency.hip": ["k12_consistency.hpp", "k12_consistency_rule.hpp", "rslf_plan_consistency.hpp", "k13_f2c_consistency.hpp",
+                             "rslf_plan_f2c_consistency.hpp"],
     "rslf_multi.hip": [],
     "rslf_multi_sweep.hip": [],
 }

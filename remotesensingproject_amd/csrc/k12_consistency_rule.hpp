@@ -121,6 +121,23 @@ RSLF_K12_FN ConsistencyResult consistency_finish(const ConsistencyAcc& a, int mi
     return r;
 }
 
+// The gate a kept fine-to-coarse run puts on a level's validity (k13_f2c_consistency.hpp): a pixel keeps its
+// validity if at least min_agree of the views that can see it agree with it -- and, where fewer than min_agree views can see
+// it, if all of them do.  seen == 0 (the pixel's line leaves the field in every view asked): kept.  Unlike valid_out above
+// (agree >= min_agree) the rule does not drop a pixel for lying near the field's border or in an outer view of a radius.
+RSLF_K12_FN bool consistency_gate(int32_t seen, int32_t agree, int32_t min_agree)
+{
+    return agree >= (seen < min_agree ? seen : min_agree);
+}
+
+// What the gate accumulates: consistency_visit's `seen` and `agree`, the same tests, nothing else.
+RSLF_K12_FN void consistency_gate_visit(int32_t* seen, int32_t* agree, bool in_field, float d, float dt, bool ok_t, float tol)
+{
+    const float diff = dt - d;
+    *seen += in_field ? 1 : 0;
+    *agree += (in_field & ok_t & (fabsf(diff) <= tol)) ? 1 : 0;
+}
+
 RSLF_K12_FN ConsistencyResult consistency_nothing()
 {
     ConsistencyResult r;

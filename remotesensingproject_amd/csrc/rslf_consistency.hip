@@ -1,10 +1,13 @@
 // librslf_hip.so: cross-view consistency of a sweep's disparity planes (K12, k12_consistency.hpp) -- rslf_view_consistency on
 // planes the caller holds on the device, rslf_view_consistency_host, which stages host planes through the context's shared
 // buffers, and rslf_f2c_run_consistency (with its host-output form), which reads a kept fine-to-coarse run's planes in place.
-// C-ABI: include/rslf_hip.h.  One device.
+// And its gate form (K13, k13_f2c_consistency.hpp): rslf_f2c_consistency_mask, the primitive the level loop of rslf_f2c.hip
+// calls for a kept run with the gate set.  C-ABI: include/rslf_hip.h.  One device.
 #include "rslf_internal.hpp"
+#include "rslf_plan_f2c_consistency.hpp"
 
 #include "k12_consistency.hpp"
+#include "k13_f2c_consistency.hpp"
 
 using namespace rslf;
 
@@ -148,6 +151,46 @@ extern "C" int rslf_view_consistency_host(rslf_ctx* ctx, const float* h_depth_sv
         HIP_TRY(hipMemcpyAsync(d_valid, h_valid_svu, n, hipMemcpyHostToDevice, st));
     return consistency_to_host(ctx, grid, static_cast<const float*>(d_depth), static_cast<const uint8_t*>(d_valid), S, V, U, slope, tol,
                                radius, min_agree, c, h_fused_svu, h_valid_out_svu);
+}
+RSLF_API_CATCH
+
+// The gate form: the level's validity in, the gated validity out (another plane), the pixels made invalid added to *d_dropped.
+extern "C" int rslf_f2c_consistency_mask(rslf_ctx* ctx, const float* d_depth_svu, const uint8_t* d_valid_svu, int S, int V, int U, float slope,
+                                         float tol, int radius, int min_agree, uint8_t* d_valid_out_svu, int32_t* d_agree_svu,
+                                         int32_t* d_seen_svu, unsigned long long* d_dropped) RSLF_API_TRY
+{
+    if (!ctx || !d_depth_svu || !d_valid_svu || !d_valid_out_svu)
+        return fail(RSLF_ERR_INVALID_ARG, "rslf_f2c_consistency_mask: ctx, d_depth_svu, d_valid_svu or d_valid_out_svu is NULL");
+    const void* outs[4] = {d_valid_out_svu, d_agree_svu, d_seen_svu, d_dropped};
+    bool aliased = false;
+    for (const void* o : outs)
+        aliased = aliased || (o != nullptr && (o == (const void*)d_depth_svu || o == (const void*)d_valid_svu));
+    switch (plan::f2c_consistency_mask_args(S, V, U, tol, min_agree, aliased)) {
+    case plan::kConsistencyBadShape:
+        return fail(RSLF_ERR_INVALID_ARG, "S=%d V=%d U=%d: not a stack of planes", S, V, U);
+    case plan::kConsistencyBadTol:
+        return fail(RSLF_ERR_INVALID_ARG, "tol=%g: a finite tolerance >= 0", (double)tol);
+    case plan::kConsistencyBadMinAgree:
+        return fail(RSLF_ERR_INVALID_ARG, "min_agree=%d: the gate asks for a count of agreeing views >= 1", min_agree);
+    case plan::kConsistencyAlias:
+        return fail(RSLF_ERR_INVALID_ARG, "an output plane is an input plane: the gate reads the other views' rows while they are "
+                                          "written (d_valid_out_svu may not be the validity plane it reads)");
+    default:
+        break;
+    }
+    const unsigned grid = plan::consistency_grid(S, V, U);
+    if (!grid)
+        return fail(RSLF_ERR_UNSUPPORTED, "S=%d V=%d U=%d exceed the grid limit of one launch (or U > %d)", S, V, U, plan::kConsistencyMaxU);
+    HIP_TRY(hipSetDevice(ctx->device));
+    F2cConsistencyArgs a = {};
+    a.depth = d_depth_svu, a.valid = d_valid_svu;
+    a.S = S, a.V = V, a.U = U, a.nseg = plan::consistency_segments(U);
+    a.slope = slope, a.tol = tol, a.radius = radius, a.min_agree = min_agree;
+    a.order = ctx->consistency_order;
+    a.valid_out = d_valid_out_svu, a.agree = d_agree_svu, a.seen = d_seen_svu, a.dropped = d_dropped;
+    hipLaunchKernelGGL(k13_f2c_consistency_gate, dim3(grid), dim3(plan::kConsistencyBlock), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return RSLF_OK;   // enqueued, not awaited
 }
 RSLF_API_CATCH
 

@@ -2,6 +2,7 @@
 // the pyramid (Gaussian blur + halving), the bound tightening, the fusion (K5) and the native level loop, whose one-context
 // form is here and whose multi-device form is in rslf_multi_sweep.hip.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
+#include "rslf_plan_f2c_consistency.hpp"
 #include "rslf_plan_f2c_peaks.hpp"
 
 #include <algorithm>
@@ -325,6 +326,11 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     int64_t pixels = 0;
     rslf_stats st1;
     memset(&st1, 0, sizeof(st1));
+    DevBuf cs_dropped;   // the consistency gate's counters, one per level: zeroed here, read once after the loop's last wait
+    if (K.cs_min_agree > 0) {
+        HIP_TRY(cs_dropped.alloc((size_t)P * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(cs_dropped.get(), 0, (size_t)P * sizeof(unsigned long long), st));
+    }
     for (int l = 0; l < P; l++) {
         F2cKeptLevel& kl = K.levels[(size_t)l];
         F2cLevel lv;
@@ -345,7 +351,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             if (rc)
                 return rc;
         }
-        DevBuf dmin, dmax;
+        DevBuf dmin, dmax, ungated;   // (ungated: the validity the consistency gate read, freed with the level's ranges)
         DevBuf &Ce = kl.Ce, &Cl = kl.Cl;
         HIP_TRY(Ce.alloc(n * 4));
         if (line_mode != RSLF_LINE_CONF_OFF)
@@ -390,6 +396,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         lv.Cl_svu = Cl.as<float>();
         lv.Cd_svu = kl.Cd.as<float>();
         lv.vol_out = (keep && keep->keep_volumes) ? &kl.vol : nullptr;
+        lv.consistency_min_agree = K.cs_min_agree;
         rc = sweep(lv, &st1);
         if (rc)
             return rc;
@@ -415,6 +422,17 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         // validity by uniqueness: what the rule left valid goes invalid where the runner-up is within the ratio of the winner
         if (!rc && K.peaks && plan::f2c_unique_applies(K.uniqueness, by))
             rc = rslf_f2c_unique_mask(ctx, kl.valid.as<uint8_t>(), &pk, K.uniqueness, n);
+        // validity by cross-view consistency: what is still valid goes invalid where the other views contradict it.  The gate
+        // writes a second plane (a thread reads the other views' rows while they are written), which takes the first one's place
+        if (!rc && plan::f2c_consistency_applies(K.cs_min_agree, by)) {
+            HIP_TRY(ungated.alloc(n));
+            HIP_TRY(kl.cs_agree.alloc(n * 4));
+            HIP_TRY(kl.cs_seen.alloc(n * 4));
+            rc = rslf_f2c_consistency_mask(ctx, kl.depth.as<const float>(), kl.valid.as<const uint8_t>(), S, lv.V, lv.U, kl.slope, K.cs_tol,
+                                           K.cs_radius, K.cs_min_agree, ungated.as<uint8_t>(), kl.cs_agree.as<int32_t>(),
+                                           kl.cs_seen.as<int32_t>(), cs_dropped.as<unsigned long long>() + l);
+            std::swap(kl.valid, ungated);   // kl.valid: the gated plane
+        }
         if (rc)
             return rc;
         if (levels_out) {   // host copies of the level's planes; C_e and C_l leave the device with this iteration
@@ -473,7 +491,12 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.get(), n0 * 4, hipMemcpyDeviceToHost, st));
     if (h_out_valid_svu)
         HIP_TRY(hipMemcpyAsync(h_out_valid_svu, ovalid.get(), n0, hipMemcpyDeviceToHost, st));
+    std::vector<unsigned long long> dropped((size_t)P, 0ull);
+    if (K.cs_min_agree > 0)
+        HIP_TRY(hipMemcpyAsync(dropped.data(), cs_dropped.get(), (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    for (int l = 0; l < P; l++)
+        K.levels[(size_t)l].inconsistent = dropped[(size_t)l];
     if (n_levels)
         *n_levels = P;
     if (stats) {

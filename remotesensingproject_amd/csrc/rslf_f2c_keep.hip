@@ -2,6 +2,7 @@
 // owns what the level loop of rslf_f2c.hip allocates (F2cKept), hands planes out by copy, and renders the three coloured
 // getters of rslf_fine_to_coarse.hpp:325-519 from them with the renderers of rslf_render.hip.  No kernels of its own.
 #include "rslf_internal.hpp"
+#include "rslf_plan_f2c_consistency.hpp"
 #include "rslf_plan_f2c_peaks.hpp"
 #include "rslf_plan_sweep_gate.hpp"
 
@@ -26,9 +27,11 @@ int elem_of(int elem, Elem* out)
 }
 
 bool is_peak_plane(int which) { return which >= RSLF_F2C_PLANE_PK_IDX && which <= RSLF_F2C_PLANE_FUSED_LEVEL; }
+bool is_gate_plane(int which) { return which == RSLF_F2C_PLANE_CS_AGREE || which == RSLF_F2C_PLANE_CS_SEEN; }
 bool is_fused_plane(int which)
 {
-    return which == RSLF_F2C_PLANE_FUSED_MAP || which == RSLF_F2C_PLANE_FUSED_VALID || which >= RSLF_F2C_PLANE_FUSED_PK_IDX;
+    return which == RSLF_F2C_PLANE_FUSED_MAP || which == RSLF_F2C_PLANE_FUSED_VALID ||
+           (which >= RSLF_F2C_PLANE_FUSED_PK_IDX && which <= RSLF_F2C_PLANE_FUSED_LEVEL);
 }
 
 // A plane of the run: where it lies and how many bytes it has; NULL if it is not held.
@@ -73,6 +76,10 @@ const void* plane_of(const rslf_f2c_run* run, int level, int which, size_t* byte
     case RSLF_F2C_PLANE_FUSED_LEVEL:
         *bytes = n;
         return run->kept.fused_level.get();
+    case RSLF_F2C_PLANE_CS_AGREE:
+        return kl.cs_agree.get();
+    case RSLF_F2C_PLANE_CS_SEEN:
+        return kl.cs_seen.get();
     }
     return nullptr;
 }
@@ -275,7 +282,8 @@ static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int 
                                  float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                  int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
                                  rslf_stats* stats, int subgrid, int peaks = 0, float uniqueness_ratio = 0.0f,
-                                 float propagation_ratio = 0.0f)
+                                 float propagation_ratio = 0.0f, float consistency_tol = 0.0f, int consistency_radius = 0,
+                                 int consistency_min_agree = 0)
 {
     if (!run)
         return fail(RSLF_ERR_INVALID_ARG, "run is NULL");
@@ -301,12 +309,28 @@ static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int 
         return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g: 0 (off) or a ratio in (0, 1]", (double)propagation_ratio);
     if (propagation_ratio != 0.0f && !peaks)
         return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g reads the peak planes: it needs peaks = 1", (double)propagation_ratio);
+    // the validity by cross-view consistency: independent of the peaks; 0 is off, and then tol and radius are not looked at
+    switch (plan::f2c_consistency_args(consistency_tol, consistency_min_agree)) {
+    case plan::kF2cConsistencyOk:
+        break;
+    case plan::kF2cConsistencyBadMinAgree:
+        return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree=%d: 0 (off) or a count of agreeing views >= 1", consistency_min_agree);
+    case plan::kF2cConsistencyBadTol:
+        return fail(RSLF_ERR_INVALID_ARG, "consistency_tol=%g: a finite tolerance >= 0", (double)consistency_tol);
+    }
+    // (the level's sweeps would end a sweep the caller left open; the entries without the gate do what they always did)
+    if (consistency_min_agree > 0 && ctx->sweep.open)
+        return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree: a sweep is open on this context");
     Elem e;
     int rc = elem_of(elem, &e);
     if (rc)
         return rc;
     if ((int)plan::f2c_pyramid(V, U, max_pyr_depth).size() > RSLF_F2C_MAX_LEVELS)
         return fail(RSLF_ERR_UNSUPPORTED, "a pyramid deeper than %d levels", RSLF_F2C_MAX_LEVELS);
+    // (the finest level has the largest grid; a shape that is none is refused by the loop)
+    if (consistency_min_agree > 0 && S >= 1 && V >= 1 && U >= 1 && !plan::consistency_grid(S, V, U))
+        return fail(RSLF_ERR_UNSUPPORTED, "consistency_min_agree: S=%d V=%d U=%d exceed the grid limit of one gate launch (or U > %d)", S, V, U,
+                    plan::kConsistencyMaxU);
     std::unique_ptr<rslf_f2c_run> r(new rslf_f2c_run());   // whatever path leaves this function, a run not handed out is freed
     r->device = ctx->device;
     r->S = S;
@@ -323,6 +347,11 @@ static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int 
     r->kept.uniqueness = uniqueness_ratio;
     r->propagation_ratio = propagation_ratio;
     r->kept.propagation_ratio = propagation_ratio;
+    if (consistency_min_agree > 0) {
+        r->kept.cs_min_agree = consistency_min_agree;
+        r->kept.cs_tol = consistency_tol;
+        r->kept.cs_radius = consistency_radius;
+    }
     rc = fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
                                     accept_all_last_scale, nullptr, nullptr, nullptr, stats, line_mode, nullptr, validity_rule, &r->kept,
                                     subgrid);
@@ -376,6 +405,45 @@ extern "C" int rslf_f2c_run_host_pr(rslf_ctx* ctx, const void* const* h_epis, in
     return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
                         accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio,
                         propagation_ratio);
+}
+RSLF_API_CATCH
+
+// ... and with consistency_min_agree > 0 every level's validity gated by the other views (k13_f2c_consistency_gate); 0 is
+// rslf_f2c_run_host_pr
+extern "C" int rslf_f2c_run_host_cs(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
+                                    int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
+                                    float uniqueness_ratio, float propagation_ratio, float consistency_tol, int consistency_radius,
+                                    int consistency_min_agree) RSLF_API_TRY
+{
+    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio,
+                        propagation_ratio, consistency_tol, consistency_radius, consistency_min_agree);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_f2c_run_consistency_gate(const rslf_f2c_run* run, float* tol, int* radius, int* min_agree) RSLF_API_TRY
+{
+    if (tol)
+        *tol = run ? run->kept.cs_tol : 0.0f;
+    if (radius)
+        *radius = run ? run->kept.cs_radius : 0;
+    if (min_agree)
+        *min_agree = run ? run->kept.cs_min_agree : 0;
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+// the pixels the gate made invalid on `level`; 0 on a level accepted whole and on every level of a run without the gate
+extern "C" int rslf_f2c_run_inconsistent(const rslf_f2c_run* run, int level, unsigned long long* n) RSLF_API_TRY
+{
+    if (!run || !n)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (level < 0 || level >= (int)run->kept.levels.size())
+        return fail(RSLF_ERR_INVALID_ARG, "level=%d outside [0,%d)", level, (int)run->kept.levels.size());
+    *n = run->kept.levels[(size_t)level].inconsistent;
+    return RSLF_OK;
 }
 RSLF_API_CATCH
 
@@ -454,6 +522,12 @@ extern "C" int rslf_f2c_run_describe(const rslf_f2c_run* run, rslf_f2c_run_desc*
     }
     out->device_bytes = plan::f2c_kept_bytes(run->S, run->C, dims, run->line_mode, run->kept.keep_volumes) +
                         plan::f2c_peaks_bytes(run->peaks != 0, run->S, dims);
+    for (int l = 0; l < P; l++) {   // the gate's planes: a gated run holds them on every level that was not accepted whole
+        const bool gated = run->kept.levels[(size_t)l].cs_agree.get() != nullptr;
+        if (gated)
+            out->planes_held |= (1u << RSLF_F2C_PLANE_CS_AGREE) | (1u << RSLF_F2C_PLANE_CS_SEEN);
+        out->device_bytes += plan::f2c_consistency_level_bytes(gated, run->S, dims[(size_t)l]);
+    }
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -464,7 +538,7 @@ extern "C" int rslf_f2c_run_copy(const rslf_f2c_run* run, int level, int which, 
         return fail(RSLF_ERR_INVALID_ARG, "run/dst is NULL");
     if (level < 0 || level >= (int)run->kept.levels.size())
         return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
-    if (which < RSLF_F2C_PLANE_DEPTH || which > RSLF_F2C_PLANE_FUSED_LEVEL)
+    if (which < RSLF_F2C_PLANE_DEPTH || which > RSLF_F2C_PLANE_CS_SEEN)
         return fail(RSLF_ERR_INVALID_ARG, "plane %d: one of RSLF_F2C_PLANE_*", which);
     if (is_fused_plane(which) && level != 0)
         return fail(RSLF_ERR_INVALID_ARG, "the fused planes are at the finest size: ask for them with level 0, not %d", level);
@@ -474,6 +548,9 @@ extern "C" int rslf_f2c_run_copy(const rslf_f2c_run* run, int level, int which, 
     const void* src = plane_of(run, level, which, &bytes);
     if (!src && is_peak_plane(which))
         return fail(RSLF_ERR_INVALID_ARG, "which=%d: a peak plane, and this run holds none (it was made with peaks = 0)", which);
+    if (!src && is_gate_plane(which))
+        return fail(RSLF_ERR_INVALID_ARG, "which=%d: a plane of the consistency gate, and level %d holds none (the run was made with "
+                                          "consistency_min_agree = 0, or the level was accepted whole)", which, level);
     if (!src)
         return fail(RSLF_ERR_INVALID_ARG, "plane %d is not held by this run (C_l needs a line mode)", which);
     HIP_TRY(hipSetDevice(run->device));

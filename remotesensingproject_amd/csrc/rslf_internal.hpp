@@ -14,7 +14,8 @@
 //   rslf_f2c_keep.hip     a finished fine-to-coarse run kept on the device (rslf_f2c_run): copies out, the coloured getters
 //   rslf_f2c_peaks.hip    a kept run's peak planes: validity by uniqueness and the fused peaks (k11_f2c_peaks.hpp)
 //   rslf_render.hip       the getters' pictures: fit, plane render, EPI line painter (K6)
-//   rslf_consistency.hip  cross-view consistency of a sweep's disparity planes: counts, fused value, validity (k12_consistency.hpp)
+//   rslf_consistency.hip  cross-view consistency of a sweep's disparity planes: counts, fused value, validity (k12_consistency.hpp),
+//                         and its gate form for a kept fine-to-coarse run's levels (k13_f2c_consistency.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
@@ -540,6 +541,8 @@ struct F2cLevel {
                                           // mode (rslf_sweep_peaks; depth2d_run_lc fills them with -1 / 0 first); NULL: mode off
     float propagation_ratio = 0.0f;       // ... and the level's sweep gated by this ratio (rslf_sweep_propagation_ratio; 0: off)
     unsigned long long* withheld = nullptr;   // where the sweep leaves its count of withheld sources (gated levels only)
+    int consistency_min_agree = 0;        // the run's validity by cross-view consistency is on (the loop applies it; a sweep
+                                          // callable that cannot serve such a run refuses it by this)
 };
 // What the level loop allocates per level and for the fusion.  The loop's own instance frees a level's confidences when the
 // level is done and the rest on return, as it always did; a caller's instance (a kept run, rslf_f2c_run) keeps everything.
@@ -552,6 +555,8 @@ struct F2cKeptLevel {
     VolumePtr vol;                      // the normalised volume the sweep ran on (kept runs with volumes only)
     DevBuf pk_idx, pk_score, pk_runner_idx, pk_runner_score;   // the sweep's peak planes (kept runs with peaks only)
     unsigned long long withheld = 0;    // sources the level's sweep withheld (kept runs with a propagation ratio only)
+    DevBuf cs_agree, cs_seen;           // the consistency gate's own counts at gate time, int32 (gated levels only)
+    unsigned long long inconsistent = 0;   // pixels the gate made invalid (gated levels only)
 };
 struct F2cKept {
     bool keep_volumes = false;
@@ -564,6 +569,10 @@ struct F2cKept {
     float uniqueness = 0.0f;
     float propagation_ratio = 0.0f;     // every level's sweep gated by this ratio (rslf_f2c_run_host_pr; needs peaks; 0: off)
     DevBuf fused_pk_idx, fused_pk_score, fused_pk_runner_idx, fused_pk_runner_score, fused_level;   // [S][V_0][U_0] (k11_fuse_peaks)
+    // validity by cross-view consistency (rslf_f2c_run_host_cs), set by the owner: with cs_min_agree > 0, after a level's rule
+    // and uniqueness, a valid pixel the other views contradict (consistency_gate, k13_f2c_consistency_gate) becomes invalid
+    int cs_min_agree = 0, cs_radius = 0;
+    float cs_tol = 0.0f;
 };
 // FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from host EPIs of element type elem
 // into host planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which

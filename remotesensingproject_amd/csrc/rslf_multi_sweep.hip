@@ -310,6 +310,8 @@ static int multi_fine_to_coarse(rslf_multi* m, Elem elem, const void* const* h_e
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
         if (lv.peaks)   // (and with them the validity by uniqueness, which reads them)
             return fail(RSLF_ERR_INVALID_ARG, "peaks: the pyramid's peak planes and its uniqueness ratio are built for one device");
+        if (lv.consistency_min_agree)
+            return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree: the pyramid's validity by cross-view consistency is built for one device");
         const FirstDevicePlanes first{lv.raw_vsuc, lv.dmin_svu, lv.dmax_svu, lv.Ce_svu, lv.depth_svu};
         HIP_TRY(hipStreamSynchronize(ctx->stream));   // what the other devices' streams are about to read is complete
         int rc = multi_depth2d(m, nullptr, Elem::F32, 0, lv.V, S, lv.U, C, lv.scale, d_min, d_max, dim_d, &lv.params, nullptr, nullptr,

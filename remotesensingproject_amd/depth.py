@@ -125,6 +125,13 @@ def require_no_propagation_ratio(ratio, who: str) -> None:
                          "compute_2D_depth_epi and fine_to_coarse_run_host(keep=True, peaks=True))" % who)
 
 
+def require_no_consistency_gate(min_agree, who: str) -> None:
+    """A pyramid's validity by cross-view consistency (DESIGN.md 3 "Consistency gate") is built for a kept run on one device.
+    Every other form refuses it instead of ignoring it."""
+    if min_agree is not None and min_agree is not False and min_agree != 0:
+        raise ValueError("%s: consistency_min_agree is not built here (one device, a kept run: fine_to_coarse_run_host(keep=True))" % who)
+
+
 def _propagation_ratio(ratio, who: str) -> float:
     """None / 0 -> 0.0 (off); else a ratio in (0, 1] (a NaN is none)."""
     if not _ratio_on(ratio):
@@ -988,12 +995,13 @@ class MultiDevice:
 
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                       subgrid: bool = False, peaks=None, propagation_ratio=None):
+                       subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
         require_no_peaks(peaks, "MultiDevice.fine_to_coarse")
         require_no_propagation_ratio(propagation_ratio, "MultiDevice.fine_to_coarse")
+        require_no_consistency_gate(consistency_min_agree, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
@@ -1624,6 +1632,32 @@ _F2C_PLANES = dict(depth=(0, torch.float32), valid=(1, torch.uint8), Ce=(2, torc
                    pk_runner_score=(10, torch.float32), fused_pk_idx=(11, torch.int32), fused_pk_score=(12, torch.float32),
                    fused_pk_runner_idx=(13, torch.int32), fused_pk_runner_score=(14, torch.float32),
                    fused_level=(15, torch.uint8))   # RSLF_F2C_PLANE_*
+_F2C_GATE_PLANES = dict(cs_agree=(16, torch.int32), cs_seen=(17, torch.int32))   # RSLF_F2C_PLANE_CS_*: the consistency gate's counts
+
+
+def f2c_consistency_mask(ctx: Context, depth_s_v_u: torch.Tensor, valid_s_v_u: torch.Tensor, slope: float, tol: float, radius: int = 0,
+                         min_agree: int = 1, counts: bool = True, dropped: torch.Tensor | None = None):
+    """rslf_f2c_consistency_mask (not in the reference): the gate a kept fine-to-coarse run puts on a level's validity.
+    depth_s_v_u [S, V, U] f32 and valid_s_v_u [S, V, U] u8 on the context's device; a pixel that is valid with a finite
+    disparity becomes 0 in the returned plane unless agree >= min(seen, min_agree), counted as view_consistency counts them;
+    every other byte is copied.  Returns (valid_out, agree, seen) as new tensors (agree / seen None with counts=False).
+    dropped: a one-element int64 CUDA tensor the launch adds the number of pixels it made invalid to.  Queued, not awaited."""
+    tol, radius, min_agree = _consistency_args(tol, radius, min_agree, "f2c_consistency_mask")
+    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
+        raise ValueError("f2c_consistency_mask: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]")
+    if (valid_s_v_u is None or valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8 or not valid_s_v_u.is_cuda
+            or not valid_s_v_u.is_contiguous()):
+        raise ValueError("f2c_consistency_mask: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape")
+    if dropped is not None and (dropped.numel() != 1 or dropped.dtype != torch.int64 or not dropped.is_cuda):
+        raise ValueError("f2c_consistency_mask: dropped must be a one-element int64 CUDA tensor")
+    S, V, U = (int(x) for x in depth_s_v_u.shape)
+    out = torch.empty((S, V, U), dtype=torch.uint8, device=depth_s_v_u.device)
+    agree = torch.empty((S, V, U), dtype=torch.int32, device=depth_s_v_u.device) if counts else None
+    seen = torch.empty((S, V, U), dtype=torch.int32, device=depth_s_v_u.device) if counts else None
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_f2c_consistency_mask(ctx._h, _ptr(depth_s_v_u), _ptr(valid_s_v_u), S, V, U, float(slope), tol, radius, min_agree,
+                                               _ptr(out), _ptr(agree), _ptr(seen), _ptr(dropped)), "rslf_f2c_consistency_mask")
+    return out, agree, seen
 
 
 def _f2c_peak_struct(pk: "Peaks", shape: tuple, who: str) -> _lib.RslfPeaks:
@@ -1694,6 +1728,10 @@ class KeptFineToCoarse:
         self.peaks = bool(_lib.lib().rslf_f2c_run_peaks(self._h))       # the run holds peak planes (get_peaks, get_fused_peaks)
         self.uniqueness_ratio = float(_lib.lib().rslf_f2c_run_uniqueness(self._h))   # 0.0: validity by uniqueness was off
         self.propagation_ratio = float(_lib.lib().rslf_f2c_run_propagation_ratio(self._h))   # 0.0: the sweeps were not gated
+        tol, radius, min_agree = C.c_float(), C.c_int(), C.c_int()
+        check(_lib.lib().rslf_f2c_run_consistency_gate(self._h, C.byref(tol), C.byref(radius), C.byref(min_agree)), "rslf_f2c_run_consistency_gate")
+        # (tol, radius, min_agree) of the validity by cross-view consistency, None: the run was made without it
+        self.consistency_gate = (float(tol.value), int(radius.value), int(min_agree.value)) if min_agree.value else None
 
     def describe(self) -> "_lib.RslfF2cRunDesc":
         d = _lib.RslfF2cRunDesc()
@@ -1703,8 +1741,9 @@ class KeptFineToCoarse:
     def plane(self, level: int, name: str) -> torch.Tensor:
         """One kept plane as a new tensor on the device: "depth", "valid", "Ce", "Cd", "Cl" of a level [S,V_p,U_p], or
         "fused_map" / "fused_valid" (level 0); of a run made with peaks=True also "pk_idx", "pk_score", "pk_runner_idx",
-        "pk_runner_score" of a level and "fused_pk_*" / "fused_level" (level 0)."""
-        which, dtype = _F2C_PLANES[name]
+        "pk_runner_score" of a level and "fused_pk_*" / "fused_level" (level 0); of a run made with the consistency gate also
+        "cs_agree" / "cs_seen" of a gated level."""
+        which, dtype = _F2C_GATE_PLANES[name] if name in _F2C_GATE_PLANES else _F2C_PLANES[name]
         if not 0 <= level < self.n_levels:
             raise ValueError("level %d of %d" % (level, self.n_levels))
         out = torch.empty((self.S,) + self.dims[level], dtype=dtype, device=self.ctx.device)
@@ -1738,6 +1777,21 @@ class KeptFineToCoarse:
         n = C.c_ulonglong()
         check(_lib.lib().rslf_f2c_run_withheld(self._h, int(level), C.byref(n)), "rslf_f2c_run_withheld")
         return int(n.value)
+
+    def inconsistent(self, level: int) -> int:
+        """Not in the reference: the pixels the consistency gate made invalid on `level`; 0 on a level accepted whole and on
+        every level of a run made without the gate."""
+        n = C.c_ulonglong()
+        check(_lib.lib().rslf_f2c_run_inconsistent(self._h, int(level), C.byref(n)), "rslf_f2c_run_inconsistent")
+        return int(n.value)
+
+    def get_gate_counts(self, level: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """Not in the reference: (agree, seen) [S,V_p,U_p] int32, the consistency gate's own counts on `level` at gate time --
+        they explain a drop: agree < min(seen, min_agree).  get_consistency afterwards reads the gated validity and counts
+        differently.  Needs a run made with the gate, and a level it touched (not the one accepted whole)."""
+        if self.consistency_gate is None:
+            raise ValueError("get_gate_counts: this run was made without consistency_min_agree")
+        return self.plane(level, "cs_agree"), self.plane(level, "cs_seen")
 
     def get_fused_peaks(self) -> tuple["Peaks", torch.Tensor]:
         """Not in the reference: (Peaks [S,V,U], fused_level [S,V,U] uint8) at the finest size -- for every pixel of the fused
@@ -1809,7 +1863,8 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                             parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                             ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False, keep: bool = False,
                             validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None,
-                            uniqueness_ratio: float | None = None, propagation_ratio: float | None = None):
+                            uniqueness_ratio: float | None = None, propagation_ratio: float | None = None,
+                            consistency_min_agree: int | None = None, consistency_tol: float | None = None, consistency_radius: int = 0):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -1828,7 +1883,22 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     than ratio * the winner's score become invalid, so a coarser level decides them.
     propagation_ratio (None or 0: off; else in (0, 1], needs keep=True and peaks=True; rslf_f2c_run_host_pr): every level's
     sweep withholds such pixels from propagation (Depth2DComputer); independent of uniqueness_ratio, both may be set.
-    KeptFineToCoarse.propagation_ratio and .withheld(level) read it back."""
+    KeptFineToCoarse.propagation_ratio and .withheld(level) read it back.
+    consistency_min_agree (not in the reference; None or 0: off; else m >= 1, needs keep=True and nothing else;
+    rslf_f2c_run_host_cs): after a level's sweep, validity rule and uniqueness ratio, a pixel that is still valid becomes invalid
+    unless agree >= min(seen, m) among the other views (view_consistency's counts; consistency_radius > 0: only views within
+    it), so a coarser level decides it.  consistency_tol=None: one step of the hypothesis grid.
+    KeptFineToCoarse.consistency_gate, .inconsistent(level) and .get_gate_counts(level) read it back."""
+    want_cs = consistency_min_agree is not None and consistency_min_agree is not False and consistency_min_agree != 0
+    cs_tol, cs_radius, cs_min_agree = 0.0, 0, 0
+    if want_cs:
+        if int(consistency_min_agree) < 0:
+            raise ValueError("fine_to_coarse_run_host: consistency_min_agree %r is negative" % (consistency_min_agree,))
+        if not keep:
+            raise ValueError("fine_to_coarse_run_host: consistency_min_agree gates the validity of a kept run: pass keep=True")
+        cs_tol, cs_radius, cs_min_agree = _consistency_args(
+            grid_step(d_min, d_max, dim_d, "fine_to_coarse_run_host") if consistency_tol is None else consistency_tol,
+            consistency_radius, consistency_min_agree, "fine_to_coarse_run_host: consistency_tol")
     want_peaks = peaks is not None and peaks is not False
     want_gate = _ratio_on(propagation_ratio)
     if want_gate and not keep:
@@ -1860,7 +1930,10 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
         args = (ctx._h, ptrs, _ELEM[np.dtype(dt)], V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
                 float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
                 int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
-        if want_peaks and gate:
+        if want_cs:
+            check(L.rslf_f2c_run_host_cs(*args, 1 if subgrid else 0, 1 if want_peaks else 0, float(uniqueness_ratio or 0.0), gate,
+                                         cs_tol, cs_radius, cs_min_agree), "rslf_f2c_run_host_cs")
+        elif want_peaks and gate:
             check(L.rslf_f2c_run_host_pr(*args, 1 if subgrid else 0, 1, float(uniqueness_ratio or 0.0), gate), "rslf_f2c_run_host_pr")
         elif want_peaks:
             check(L.rslf_f2c_run_host_pk(*args, 1 if subgrid else 0, 1, float(uniqueness_ratio or 0.0)), "rslf_f2c_run_host_pk")
@@ -1920,9 +1993,10 @@ class FineToCoarse:
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                  ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None,
-                 propagation_ratio=None):
+                 propagation_ratio=None, consistency_min_agree=None):
         require_no_peaks(peaks, "FineToCoarse")   # (the pyramid's levels carry no peak planes)
         require_no_propagation_ratio(propagation_ratio, "FineToCoarse")
+        require_no_consistency_gate(consistency_min_agree, "FineToCoarse")
         self.m_parameters = parameters or Depth1DParameters.get_default()
         self.m_subgrid = bool(subgrid)   # not in the reference: every level's sweep in the sub-grid mode (Depth2DComputer)
         f2c_line_mode(self.m_parameters, line_confidence_mode, "FineToCoarse")
