@@ -1061,6 +1061,65 @@ int rslf_f2c_consistency_mask(rslf_ctx* ctx, const float* d_depth_svu, const uin
                               float tol, int radius, int min_agree, uint8_t* d_valid_out_svu, int32_t* d_agree_svu,
                               int32_t* d_seen_svu, unsigned long long* d_dropped);
 
+/* ---- the view warp: any view position from a sweep's planes (K14) -------- */
+/* Not in the reference.  The check above looks along a pixel's own EPI line; this asks the opposite: what does a view at
+ * position t look like, given what the views hold?  A scatter with an occlusion order -- render a view nobody took, fill a view
+ * from the others, or (with a view excluded from its own prediction) measure how well the disparities explain the light field.
+ * t is a float, finite, |t| <= 65536; it need not be integral and need not lie inside [0, S - 1].  A source pixel (s, v, u) of
+ * disparity d is a CANDIDATE for column x of scanline v of target t when it is ok (as above: d_valid_svu NULL or non-zero there,
+ * d finite), s != exclude, radius <= 0 or fabsf((float)s - t) <= (float)radius, and
+ *     x = u + (int)roundf(fl(fl(d * fl((float)s - t)) * slope))
+ * is in [0, U) with the offset below 1e9f in magnitude (a NaN is never converted) -- for an integral t the column rule above,
+ * bit for bit.  Among the candidates of (v, x) the WINNER has the greatest z = nearer >= 0 ? d : -d (-0.0f and +0.0f are equal;
+ * nearer = +1: larger disparities are nearer, the reference's occlusion map and rslf_render_epi_lines' order; -1: the opposite
+ * convention); among equal z the smaller fabsf((float)s - t); among equal distances the smaller s.  The order is total, so the
+ * result does not depend on the order the sources are visited in.  The rule is stated once, in csrc/k14_warp_rule.hpp.
+ * Outputs per target k of the T targets, each nullable, not all nine; only the planes asked for are written:
+ *   hit       u8  [T][V][U]     255 where a candidate arrived, else 0
+ *   depth     f32 [T][V][U]     the winner's stored disparity, its own bits; 0 where none
+ *   src_view  i32 [T][V][U]     the winner's s; -1 where none
+ *   src_col   i32 [T][V][U]     the winner's u; -1 where none
+ *   count     i32 [T][V][U]     the candidates that arrived, winners or not
+ *   colour    f32 [T][V][U][C]  the volume's radiance at (v, src_view, src_col, :), as it holds it (normalised); 0 where none
+ *   err       f32 [T][V][U]     the leave-one-out residual against the slab's own row (v, t): acc = 0; for c ascending:
+ *                               acc = acc + fabsf(colour[c] - L[x][c]); acc / (float)C; 0 where none
+ *   row_err   f64 [T][V]        the sum of err over a row's hit pixels, in double, in an order left open
+ *   row_hits  i32 [T][V]        their number
+ * colour, err and row_err need `volume` (else nullable), of the planes' V, S, U; err and row_err also need every target to be a
+ * view: integral and in [0, S).  targets [T] and exclude [T] (nullable: nobody; an entry of -1: nobody) are HOST arrays, read
+ * before the return.  RSLF_ERR_INVALID_ARG, before anything is queued, the argument named in rslf_last_error(): a NULL depth
+ * plane or targets, S, V or U below 1, T below 1, nearer == 0, no output, an output plane that is an input plane, a volume
+ * missing or of another shape, a target that is not finite or beyond 65536 (for err: not a view).  RSLF_ERR_UNSUPPORTED: U
+ * above 8192 (the z-buffer of a row, one 64-bit key per column in LDS), S above 65536, or T * 8 * ceil(V / 8) not below 2^31.
+ * One launch per 256 targets, enqueued on the context's stream, not awaited; no scratch. */
+typedef struct rslf_view_warp_out {
+    uint8_t* hit;
+    float* depth;
+    int32_t* src_view;
+    int32_t* src_col;
+    int32_t* count;
+    float* colour;
+    float* err;
+    double* row_err;
+    int32_t* row_hits;
+} rslf_view_warp_out;
+int rslf_view_warp(rslf_ctx* ctx, const float* d_depth_svu, const uint8_t* d_valid_svu, int S, int V, int U, float slope,
+                   const rslf_volume* volume, const float* targets, const int* exclude, int T, int radius, int nearer,
+                   const rslf_view_warp_out* d_out);
+/* The same with the planes on the HOST (the volume stays a device object): uploads through the context's grow-only staging,
+ * runs the launches, downloads the planes asked for and waits.  Refused while a sweep is open on the context. */
+int rslf_view_warp_host(rslf_ctx* ctx, const float* h_depth_svu, const uint8_t* h_valid_svu, int S, int V, int U, float slope,
+                        const rslf_volume* volume, const float* targets, const int* exclude, int T, int radius, int nearer,
+                        const rslf_view_warp_out* h_out);
+/* The same on a kept fine-to-coarse run's planes, read in place, as rslf_f2c_run_consistency reads them: a level's depth and
+ * validity, or with fused_result != 0 (level 0) the fused pair; the slope the level ran with; the level's kept volume.  A run
+ * made without keep_volumes refuses colour, err and row_err by name.  ctx: any context of the run's device. */
+int rslf_f2c_run_view_warp(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets, const int* exclude,
+                           int T, int radius, int nearer, const rslf_view_warp_out* d_out);
+/* ... and with the result planes on the HOST: staged, copied out, awaited.  Refused while a sweep is open on the context. */
+int rslf_f2c_run_view_warp_host(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets,
+                                const int* exclude, int T, int radius, int nearer, const rslf_view_warp_out* h_out);
+
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit
  * exchanges the neighbours' boundary rows (median reach) of the visited view's raw disparities and edge mask by peer

@@ -292,6 +292,65 @@ inline float grid_step(float dmin, float dmax, int dim_d)
 }
 }  // namespace detail
 
+// Not in the reference: the planes of the view warp (rslf_view_warp, rslf_hip.h) for the T targets of a call, [T][V][U] each
+// (colour [T][V][U][C]) -- hit 255 where a source pixel arrived; depth, src_view, src_col the winner's stored disparity, view
+// and column (0, -1, -1 where none); count the candidates that arrived; colour the light field's radiance at the winner.
+struct Warp {
+    std::vector<uint8_t> hit;
+    std::vector<float> depth;
+    std::vector<int32_t> src_view, src_col, count;
+    std::vector<float> colour;
+};
+// ... and the leave-one-out yardstick: every target view predicted from the OTHER views and compared with the view that was
+// taken -- err and hit [T][V][U], row_err / row_hits [T][V], and per target mean_abs_error (NaN where nothing arrived) and
+// coverage (hits over V * U).
+struct ViewPrediction {
+    std::vector<float> err;
+    std::vector<uint8_t> hit;
+    std::vector<double> row_err;
+    std::vector<int32_t> row_hits;
+    std::vector<double> mean_abs_error, coverage;
+};
+
+namespace detail {
+inline rslf_view_warp_out warp_planes(Warp& w, size_t n, int channels, bool colour)
+{
+    w.hit.resize(n), w.depth.resize(n), w.src_view.resize(n), w.src_col.resize(n), w.count.resize(n);
+    if (colour)
+        w.colour.resize(n * (size_t)channels);
+    const rslf_view_warp_out out = {w.hit.data(), w.depth.data(), w.src_view.data(), w.src_col.data(), w.count.data(),
+                                    colour ? w.colour.data() : nullptr, nullptr, nullptr, nullptr};
+    return out;
+}
+inline rslf_view_warp_out prediction_planes(ViewPrediction& p, int T, int V, int U)
+{
+    p.err.resize((size_t)T * V * U), p.hit.resize((size_t)T * V * U), p.row_err.resize((size_t)T * V), p.row_hits.resize((size_t)T * V);
+    const rslf_view_warp_out out = {p.hit.data(), nullptr, nullptr, nullptr, nullptr, nullptr, p.err.data(), p.row_err.data(), p.row_hits.data()};
+    return out;
+}
+inline void prediction_finish(ViewPrediction& p, int T, int V, int U)
+{
+    p.mean_abs_error.assign((size_t)T, std::nan("")), p.coverage.assign((size_t)T, 0.0);
+    for (int k = 0; k < T; k++) {
+        double e = 0.0;
+        long long hits = 0;
+        for (int v = 0; v < V; v++)
+            e += p.row_err[(size_t)k * V + v], hits += p.row_hits[(size_t)k * V + v];
+        if (hits)
+            p.mean_abs_error[(size_t)k] = e / (double)hits;
+        p.coverage[(size_t)k] = (double)hits / ((double)V * U);
+    }
+}
+// the default targets of a prediction: every view, each excluded from its own
+inline std::vector<float> prediction_targets(std::vector<int>& views, int S)
+{
+    if (views.empty())
+        for (int s = 0; s < S; s++)
+            views.push_back(s);
+    return std::vector<float>(views.begin(), views.end());
+}
+}  // namespace detail
+
 class MultiContext {
 public:
     MultiContext() : h_(nullptr) { check(rslf_multi_create(nullptr, 0, &h_), "rslf_multi_create"); }
@@ -830,6 +889,60 @@ public:
         return get_consistency(detail::own(ctx_), tol, radius, min_agree, mask);
     }
 
+    // Not in the reference: after run(), the view at position `target` (a float: it need not be a view, nor inside the range)
+    // as the disparity planes of the views predict it (rslf_view_warp_host, rslf_hip.h): every source pixel is sent to its
+    // column in the target and the nearest wins (nearer = +1: the largest disparity, so one wrong large value wins its pixel;
+    // -1: the smallest).  exclude: a view that takes no part (-1: nobody); radius > 0: only views within it; mask (nullable,
+    // [S][V][U]): get_valid_depths_mask_s_v_u().  colour reads the object's volume, which an object built on a MultiContext
+    // does not hold; such an object takes the Context to run on.  -> planes [1][V][U].
+    Warp get_warped_view(Context& on, float target, int exclude = -1, int radius = 0, int nearer = 1, const uint8_t* mask = nullptr,
+                         bool colour = true) const
+    {
+        detail::require(!m_best_depth_s_v_u.empty(), "the getters show the results of run(): call it first");
+        detail::require(!colour || vol_ != nullptr, "get_warped_view: colour reads the volume, which an object built on a MultiContext does not hold");
+        std::vector<uint8_t> own_mask;
+        if (!mask) {
+            own_mask = get_valid_depths_mask_s_v_u();
+            mask = own_mask.data();
+        }
+        Warp out;
+        const rslf_view_warp_out planes = detail::warp_planes(out, (size_t)dim_v_ * dim_u_, CHANNELS, colour);
+        check(rslf_view_warp_host(on.get(), m_best_depth_s_v_u.data(), mask, dim_s_, dim_v_, dim_u_, m_parameters.par_slope_factor,
+                                  colour ? vol_ : nullptr, &target, &exclude, 1, radius, nearer, &planes),
+              "rslf_view_warp_host");
+        return out;
+    }
+    Warp get_warped_view(float target, int exclude = -1, int radius = 0, int nearer = 1, const uint8_t* mask = nullptr, bool colour = true) const
+    {
+        return get_warped_view(detail::own(ctx_), target, exclude, radius, nearer, mask, colour);
+    }
+    // ... and the leave-one-out yardstick: the views `views` (empty: all of them), each predicted from the others and compared
+    // with the view that was taken.  It judges a mask or a parameter choice without ground-truth depth.
+    ViewPrediction get_view_prediction(Context& on, std::vector<int> views = std::vector<int>(), int radius = 0, int nearer = 1,
+                                       const uint8_t* mask = nullptr) const
+    {
+        detail::require(!m_best_depth_s_v_u.empty(), "the getters show the results of run(): call it first");
+        detail::require(vol_ != nullptr, "get_view_prediction reads the volume, which an object built on a MultiContext does not hold");
+        std::vector<uint8_t> own_mask;
+        if (!mask) {
+            own_mask = get_valid_depths_mask_s_v_u();
+            mask = own_mask.data();
+        }
+        const std::vector<float> targets = detail::prediction_targets(views, dim_s_);
+        ViewPrediction out;
+        const rslf_view_warp_out planes = detail::prediction_planes(out, (int)views.size(), dim_v_, dim_u_);
+        check(rslf_view_warp_host(on.get(), m_best_depth_s_v_u.data(), mask, dim_s_, dim_v_, dim_u_, m_parameters.par_slope_factor, vol_,
+                                  targets.data(), views.data(), (int)views.size(), radius, nearer, &planes),
+              "rslf_view_warp_host");
+        detail::prediction_finish(out, (int)views.size(), dim_v_, dim_u_);
+        return out;
+    }
+    ViewPrediction get_view_prediction(std::vector<int> views = std::vector<int>(), int radius = 0, int nearer = 1,
+                                       const uint8_t* mask = nullptr) const
+    {
+        return get_view_prediction(detail::own(ctx_), views, radius, nearer, mask);
+    }
+
     // dc.hpp:808-856: the S x U slice of the disparities at scanline a_v (< 0: floor(V / 2.0)) over its own min / max,
     // colour-mapped, black outside the mask; no line drawing -> [S][U][3].  The slice is read through its row stride.
     std::vector<uint8_t> get_coloured_epi(Context& on, int a_v, const uint8_t* lut_bgr) const
@@ -1104,6 +1217,45 @@ public:
     Consistency get_consistency(int level = 0, bool fused_result = true, float tol = -1.f, int radius = 0, int min_agree = 0) const
     {
         return get_consistency(detail::own(ctx_), level, fused_result, tol, radius, min_agree);
+    }
+    // Not in the reference: after a run() that followed keep_on_device, the view warp of a kept plane pair, read in place on the
+    // device (rslf_f2c_run_view_warp_host, rslf_hip.h): the fused map and its validity (fused_result, which needs level 0) or
+    // a level's disparities and validity, with the slope factor the level's sweep ran with and the level's kept volume -- a
+    // run kept without its volumes refuses colour.  -> planes [1][V_level][U_level].
+    Warp get_warped_view(Context& on, float target, int level = 0, bool fused_result = true, int exclude = -1, int radius = 0,
+                         int nearer = 1, bool colour = true) const
+    {
+        detail::require(run_ != nullptr, "get_warped_view reads a kept run's planes on the device: call keep_on_device before run()");
+        detail::require(level >= 0 && level < (int)dims_.size(), "get_warped_view: the level is not in the pyramid");
+        Warp out;
+        const rslf_view_warp_out planes = detail::warp_planes(out, (size_t)dims_[level].first * dims_[level].second, CHANNELS, colour);
+        check(rslf_f2c_run_view_warp_host(run_, on.get(), level, fused_result ? 1 : 0, &target, &exclude, 1, radius, nearer, &planes),
+              "rslf_f2c_run_view_warp_host");
+        return out;
+    }
+    Warp get_warped_view(float target, int level = 0, bool fused_result = true, int exclude = -1, int radius = 0, int nearer = 1,
+                         bool colour = true) const
+    {
+        return get_warped_view(detail::own(ctx_), target, level, fused_result, exclude, radius, nearer, colour);
+    }
+    ViewPrediction get_view_prediction(Context& on, int level = 0, bool fused_result = true, std::vector<int> views = std::vector<int>(),
+                                       int radius = 0, int nearer = 1) const
+    {
+        detail::require(run_ != nullptr, "get_view_prediction reads a kept run's planes on the device: call keep_on_device before run()");
+        detail::require(level >= 0 && level < (int)dims_.size(), "get_view_prediction: the level is not in the pyramid");
+        const std::vector<float> targets = detail::prediction_targets(views, dim_s_);
+        ViewPrediction out;
+        const rslf_view_warp_out planes = detail::prediction_planes(out, (int)views.size(), dims_[level].first, dims_[level].second);
+        check(rslf_f2c_run_view_warp_host(run_, on.get(), level, fused_result ? 1 : 0, targets.data(), views.data(), (int)views.size(), radius,
+                                          nearer, &planes),
+              "rslf_f2c_run_view_warp_host");
+        detail::prediction_finish(out, (int)views.size(), dims_[level].first, dims_[level].second);
+        return out;
+    }
+    ViewPrediction get_view_prediction(int level = 0, bool fused_result = true, std::vector<int> views = std::vector<int>(), int radius = 0,
+                                       int nearer = 1) const
+    {
+        return get_view_prediction(detail::own(ctx_), level, fused_result, views, radius, nearer);
     }
     // Not in the reference, to be called before run() and after keep_on_device: validity by cross-view consistency
     // (rslf_f2c_run_host_cs, rslf_hip.h).  After a level's sweep, validity rule and uniqueness ratio, a pixel that is still

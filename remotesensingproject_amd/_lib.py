@@ -67,6 +67,8 @@ SYMBOLS = [
     "rslf_view_consistency", "rslf_view_consistency_host", "rslf_f2c_run_consistency", "rslf_f2c_run_consistency_host",
     # a kept fine-to-coarse run's validity by cross-view consistency (K13)
     "rslf_f2c_run_host_cs", "rslf_f2c_run_consistency_gate", "rslf_f2c_run_inconsistent", "rslf_f2c_consistency_mask",
+    # the view warp: any view position from a sweep's planes, z-buffered (K14)
+    "rslf_view_warp", "rslf_view_warp_host", "rslf_f2c_run_view_warp", "rslf_f2c_run_view_warp_host",
 ]
 
 
@@ -126,6 +128,13 @@ class RslfViewCounts(C.Structure):
     """rslf_view_counts: the four count planes of the cross-view consistency check, int32 [S][V][U], each nullable."""
 
     _fields_ = [("seen", C.c_void_p), ("agree", C.c_void_p), ("above", C.c_void_p), ("below", C.c_void_p)]
+
+
+class RslfViewWarpOut(C.Structure):
+    """rslf_view_warp_out: the nine planes of the view warp, device or host pointers, each nullable."""
+
+    _fields_ = [("hit", C.c_void_p), ("depth", C.c_void_p), ("src_view", C.c_void_p), ("src_col", C.c_void_p), ("count", C.c_void_p),
+                ("colour", C.c_void_p), ("err", C.c_void_p), ("row_err", C.c_void_p), ("row_hits", C.c_void_p)]
 
 
 class RslfF2cLevelsOut(C.Structure):
@@ -338,6 +347,10 @@ def lib():
     L.rslf_f2c_run_consistency_gate.argtypes = [vp, C.POINTER(cf), C.POINTER(ci), C.POINTER(ci)]
     L.rslf_f2c_run_inconsistent.argtypes = [vp, ci, C.POINTER(C.c_ulonglong)]
     L.rslf_f2c_consistency_mask.argtypes = [vp, vp, vp, ci, ci, ci, cf, cf, ci, ci, vp, vp, vp, vp]
+    L.rslf_view_warp.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp, C.POINTER(cf), C.POINTER(ci), ci, ci, ci, C.POINTER(RslfViewWarpOut)]
+    L.rslf_view_warp_host.argtypes = L.rslf_view_warp.argtypes
+    L.rslf_f2c_run_view_warp.argtypes = [vp, vp, ci, ci, C.POINTER(cf), C.POINTER(ci), ci, ci, ci, C.POINTER(RslfViewWarpOut)]
+    L.rslf_f2c_run_view_warp_host.argtypes = L.rslf_f2c_run_view_warp.argtypes
     L.rslf_f2c_run_peaks.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.restype = cf

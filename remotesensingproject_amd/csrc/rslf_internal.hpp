@@ -16,10 +16,11 @@
 //   rslf_render.hip       the getters' pictures: fit, plane render, EPI line painter (K6)
 //   rslf_consistency.hip  cross-view consistency of a sweep's disparity planes: counts, fused value, validity (k12_consistency.hpp),
 //                         and its gate form for a kept fine-to-coarse run's levels (k13_f2c_consistency.hpp)
+//   rslf_warp.hip         the view warp: any view position from a sweep's planes, z-buffered (k14_view_warp.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
-//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp, rslf_plan_consistency.hpp   ... continued, for the units that need them
+//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp, rslf_plan_consistency.hpp, rslf_plan_warp.hpp   ... continued, for the units that need them
 //   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
 //
 // Two rules of the multi-device paths: they never write into a rslf_volume they did not create (a chunk of another height

@@ -1022,6 +1022,12 @@ class MultiDevice:
     def get_consistency(self, *args, **kwargs):
         no_consistency("MultiDevice")
 
+    def get_warped_views(self, *args, **kwargs):
+        no_view_warp("MultiDevice")
+
+    def get_view_prediction(self, *args, **kwargs):
+        no_view_warp("MultiDevice", "get_view_prediction")
+
     def depth1d_pile_device_out(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, out_device: int = 0,
                                 s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None,
                                 subgrid: bool = False) -> dict:
@@ -1196,6 +1202,107 @@ def no_consistency(who: str) -> None:
     """The forms that have no consistency getter say so (no multi-device form before a multi-GPU lease)."""
     raise ValueError("%s: get_consistency is not built here: bring the [S, V, U] planes to one device and call view_consistency, "
                      "or use Depth2DComputer / fine_to_coarse_run_host(keep=True)" % who)
+
+
+class Warp(NamedTuple):
+    """The view warp's planes (include/rslf_hip.h, rslf_view_warp, states the rule), per target k of the T targets of a call;
+    None where not asked for.  hit [T, V, U] uint8: 255 where a candidate arrived; depth f32: the winner's stored disparity
+    (0 where none); src_view / src_col int32: the winner's view and column (-1 where none); count int32: the candidates that
+    arrived; colour [T, V, U, C] f32: the volume's radiance at the winner (0 where none); err f32: the leave-one-out residual
+    against the view that was taken; row_err [T, V] f64 / row_hits [T, V] int32: the sum of err over a row's hit pixels and
+    their number."""
+    hit: Optional[torch.Tensor]
+    depth: Optional[torch.Tensor]
+    src_view: Optional[torch.Tensor]
+    src_col: Optional[torch.Tensor]
+    count: Optional[torch.Tensor]
+    colour: Optional[torch.Tensor]
+    err: Optional[torch.Tensor]
+    row_err: Optional[torch.Tensor]
+    row_hits: Optional[torch.Tensor]
+
+
+class ViewPrediction(NamedTuple):
+    """The leave-one-out yardstick: err / hit [T, V, U] on the device (Warp's planes), and per target, as numpy float64 [T],
+    mean_abs_error = row_err.sum() / row_hits.sum() (NaN where nothing arrived) and coverage = hits / (V * U)."""
+    err: torch.Tensor
+    hit: torch.Tensor
+    mean_abs_error: np.ndarray
+    coverage: np.ndarray
+    row_err: torch.Tensor
+    row_hits: torch.Tensor
+
+
+WARP_MAX_TARGET = 65536.0   # kWarpMaxTarget (csrc/k14_warp_rule.hpp)
+
+
+def _warp_args(targets, exclude, radius, nearer, who: str):
+    """-> (c_float array, c_int array or None, T, radius, nearer); the refusals the library would make, made by name first."""
+    targets = [float(t) for t in (targets.tolist() if hasattr(targets, "tolist") else targets)]
+    if not targets:
+        raise ValueError("%s: no targets" % who)
+    for k, t in enumerate(targets):
+        if not abs(t) <= WARP_MAX_TARGET:   # (a NaN compares false)
+            raise ValueError("%s: targets[%d] = %r is not a finite position within +-65536" % (who, k, t))
+    if int(nearer) == 0:
+        raise ValueError("%s: nearer is +1 (larger disparities are nearer) or -1, not 0" % who)
+    c_ex = None
+    if exclude is not None:
+        exclude = [int(e) for e in (exclude.tolist() if hasattr(exclude, "tolist") else exclude)]
+        if len(exclude) != len(targets):
+            raise ValueError("%s: exclude has %d entries for %d targets" % (who, len(exclude), len(targets)))
+        c_ex = (C.c_int * len(exclude))(*exclude)
+    return (C.c_float * len(targets))(*targets), c_ex, len(targets), int(radius), int(nearer)
+
+
+def _warp_out(T: int, V: int, U: int, C_: int, device, hit, depth, src, count, colour, err, rows) -> tuple[Warp, _lib.RslfViewWarpOut]:
+    new = lambda shape, dtype, on: torch.empty(shape, dtype=dtype, device=device) if on else None
+    out = Warp(new((T, V, U), torch.uint8, hit), new((T, V, U), torch.float32, depth), new((T, V, U), torch.int32, src),
+               new((T, V, U), torch.int32, src), new((T, V, U), torch.int32, count), new((T, V, U, C_), torch.float32, colour),
+               new((T, V, U), torch.float32, err), new((T, V), torch.float64, rows and err), new((T, V), torch.int32, rows))
+    return out, _lib.RslfViewWarpOut(*(None if t is None else t.data_ptr() for t in out))
+
+
+def view_warp(ctx: Context, depth_s_v_u: torch.Tensor, valid_s_v_u: torch.Tensor | None, slope: float, targets, exclude=None,
+              radius: int = 0, nearer: int = 1, volume: "Volume | None" = None, hit: bool = True, depth: bool = True, src: bool = True,
+              count: bool = False, colour: bool | None = None, err: bool = False, rows: bool = False) -> Warp:
+    """rslf_view_warp (not in the reference): what the view positions `targets` (floats, each finite and within +-65536; they
+    need not be integral or inside [0, S - 1]) look like given the disparity planes depth_s_v_u [S, V, U] f32 and
+    valid_s_v_u ([S, V, U] u8, or None for every pixel) -- every source pixel is sent to its column in the target, and of the
+    pixels that meet in a column the NEAREST wins (nearer=+1: the largest disparity; -1: the smallest), then the nearest
+    view, then the smaller view index.  exclude: per target a view that does not take part (-1 / None: nobody); radius > 0:
+    only views within it.  colour (default: whenever a volume is given) and err need `volume`; err and rows' row_err also need
+    every target to be a view index.  Returns a Warp of new tensors.  Queued on the context's stream, not awaited."""
+    c_t, c_ex, T, radius, nearer = _warp_args(targets, exclude, radius, nearer, "view_warp")
+    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
+        raise ValueError("view_warp: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]")
+    if valid_s_v_u is not None and (valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8
+                                    or not valid_s_v_u.is_cuda or not valid_s_v_u.is_contiguous()):
+        raise ValueError("view_warp: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape")
+    colour = volume is not None if colour is None else bool(colour)
+    if (colour or err) and volume is None:
+        raise ValueError("view_warp: colour and err read the light field: pass volume")
+    S, V, U = (int(x) for x in depth_s_v_u.shape)
+    out, c_out = _warp_out(T, V, U, volume.C if volume is not None else 0, depth_s_v_u.device, hit, depth, src, count, colour, err, rows)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_view_warp(ctx._h, _ptr(depth_s_v_u), _ptr(valid_s_v_u), S, V, U, float(slope),
+                                    volume._h if volume is not None else None, c_t, c_ex, T, radius, nearer, C.byref(c_out)), "rslf_view_warp")
+    return out
+
+
+def no_view_warp(who: str, what: str = "get_warped_views") -> None:
+    """The forms that have no warp getter say so (every multi-device and sharded form is left out)."""
+    raise ValueError("%s: %s is not built here: bring the [S, V, U] planes to one device and call view_warp, "
+                     "or use Depth2DComputer / fine_to_coarse_run_host(keep=True)" % (who, what))
+
+
+def _view_prediction(w: Warp) -> ViewPrediction:
+    """Per target, from the row sums (waits for the stream)."""
+    row_err, row_hits = w.row_err.cpu().numpy(), w.row_hits.cpu().numpy().astype(np.int64)
+    hits = row_hits.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mae = np.where(hits > 0, row_err.sum(axis=1) / hits, np.nan)
+    return ViewPrediction(w.err, w.hit, mae, hits / float(w.hit.shape[1] * w.hit.shape[2]), w.row_err, w.row_hits)
 
 
 def grid_step(dmin: float, dmax: float, dim_d: int, who: str) -> float:
@@ -1395,6 +1502,28 @@ class Depth2DComputer:
         """Not in the reference: the `valid` plane of get_consistency alone -- 255 where the pixel is in `mask`, its disparity
         is finite and at least min_agree other views agree with it -- [S, V, U] uint8; no other plane is computed."""
         return self.get_consistency(tol, radius, min_agree, mask, counts=False, fused=False).valid
+
+    def get_warped_views(self, targets, mask: torch.Tensor | None = None, radius: int = 0, nearer: int = 1, exclude=None,
+                         colour: bool = True, count: bool = False) -> Warp:
+        """Not in the reference: after run(), view_warp of the disparity planes with the sweep's own slope factor -- the views
+        at the positions `targets` as the other views predict them: hit, depth, src_view, src_col and (colour=True) the
+        light field's radiance at the winner.  mask=None: get_valid_depths_mask_s_v_u().  A z-buffer keeps the LARGEST
+        disparity that arrives (nearer=1), so one wrong large value wins its pixel: get_consistent_depths_mask_s_v_u() is the
+        mask to pass when that matters.  The sweep's planes are read, never written."""
+        mask = self.get_valid_depths_mask_s_v_u() if mask is None else mask
+        return view_warp(self.m_epis.ctx, self.m_best_depth_s_v_u, mask, float(np.float32(self.m_parameters.par_slope_factor)), targets,
+                         exclude, radius, nearer, self.m_epis, count=count, colour=colour)
+
+    def get_view_prediction(self, targets=None, mask: torch.Tensor | None = None, radius: int = 0, nearer: int = 1) -> ViewPrediction:
+        """Not in the reference: the leave-one-out yardstick -- every view of `targets` (default: all of them) predicted from
+        the disparities and radiances of the OTHER views and compared with the view that was taken: the err and hit planes,
+        and per target mean_abs_error (row_err.sum() / row_hits.sum(), NaN where nothing arrived) and coverage (hits over
+        V * U).  It judges a mask or a parameter choice without ground-truth depth.  Waits for the stream."""
+        targets = list(range(self.m_epis.S)) if targets is None else [int(t) for t in targets]
+        mask = self.get_valid_depths_mask_s_v_u() if mask is None else mask
+        w = view_warp(self.m_epis.ctx, self.m_best_depth_s_v_u, mask, float(np.float32(self.m_parameters.par_slope_factor)), targets,
+                      targets, radius, nearer, self.m_epis, depth=False, src=False, colour=False, err=True, rows=True)
+        return _view_prediction(w)
 
     def results(self) -> dict:
         torch.cuda.synchronize(self.m_epis.ctx.device)
@@ -1824,6 +1953,39 @@ class KeptFineToCoarse:
                                                   C.byref(c_counts), _ptr(out.fused), _ptr(out.valid)), "rslf_f2c_run_consistency")
         return out
 
+    def _view_warp(self, who: str, targets, exclude, level: int, fused_result: bool, radius: int, nearer: int, **planes) -> Warp:
+        if not 0 <= level < self.n_levels:
+            raise ValueError("level %d of %d" % (level, self.n_levels))
+        if fused_result and level != 0:
+            raise ValueError("%s: the fused planes are at the finest size: level 0, or fused_result=False" % who)
+        if (planes["colour"] or planes["err"]) and not self.keep_volumes:
+            raise ValueError("%s: colour and err read the level's volume: this run was made without keep_volumes" % who)
+        c_t, c_ex, T, radius, nearer = _warp_args(targets, exclude, radius, nearer, who)
+        out, c_out = _warp_out(T, *self.dims[level], self.C, self.ctx.device, **planes)
+        self.ctx.use_current_stream()
+        check(_lib.lib().rslf_f2c_run_view_warp(self._h, self.ctx._h, int(level), 1 if fused_result else 0, c_t, c_ex, T, radius, nearer,
+                                                C.byref(c_out)), "rslf_f2c_run_view_warp")
+        return out
+
+    def get_warped_views(self, targets, level: int = 0, fused_result: bool = True, radius: int = 0, nearer: int = 1, exclude=None,
+                         colour: bool | None = None, count: bool = False) -> Warp:
+        """Not in the reference: rslf_f2c_run_view_warp -- view_warp of a kept plane pair, read in place: the fused map and its
+        validity (fused_result=True, which needs level 0) or a level's depth / valid planes, with the slope factor the level's
+        sweep ran with and the level's kept volume.  colour=None: whenever the run keeps its volumes.  A z-buffer keeps the
+        largest disparity that arrives (nearer=1), so one wrong large value wins its pixel.  Returns a Warp of new
+        [T, V_p, U_p] tensors; the run's planes are not written."""
+        colour = self.keep_volumes if colour is None else bool(colour)
+        return self._view_warp("get_warped_views", targets, exclude, level, fused_result, radius, nearer, hit=True, depth=True, src=True,
+                               count=count, colour=colour, err=False, rows=False)
+
+    def get_view_prediction(self, targets=None, level: int = 0, fused_result: bool = True, radius: int = 0,
+                            nearer: int = 1) -> ViewPrediction:
+        """Not in the reference: the leave-one-out yardstick of Depth2DComputer.get_view_prediction on a kept plane pair; needs
+        a run made with keep_volumes.  Waits for the stream."""
+        targets = list(range(self.S)) if targets is None else [int(t) for t in targets]
+        return _view_prediction(self._view_warp("get_view_prediction", targets, targets, level, fused_result, radius, nearer, hit=True,
+                                                depth=False, src=False, count=False, colour=False, err=True, rows=True))
+
     def _render(self, name: str, shapes, *args, lut_bgr=None, stacked: bool = False):
         table = _table(lut_bgr)
         outs = [torch.empty(tuple(sh) + (3,), dtype=torch.uint8, device=self.ctx.device) for sh in shapes]
@@ -2041,6 +2203,12 @@ class FineToCoarse:
 
     def get_consistency(self, *args, **kwargs):
         no_consistency("FineToCoarse (the Python level loop)")
+
+    def get_warped_views(self, *args, **kwargs):
+        no_view_warp("FineToCoarse (the Python level loop)")
+
+    def get_view_prediction(self, *args, **kwargs):
+        no_view_warp("FineToCoarse (the Python level loop)", "get_view_prediction")
 
     def _fit_mode(self, saturate: bool) -> int:
         return FIT_QUANTILE if saturate else FIT_MEANSTD   # ImageConverter_uchar::fit(img, saturate), rslf_plot.cpp:65-98

@@ -396,6 +396,14 @@ class ShardedDepth2D:
         from . import depth
         depth.no_consistency("ShardedDepth2D")
 
+    def get_warped_views(self, *args, **kwargs):
+        from . import depth
+        depth.no_view_warp("ShardedDepth2D")
+
+    def get_view_prediction(self, *args, **kwargs):
+        from . import depth
+        depth.no_view_warp("ShardedDepth2D", "get_view_prediction")
+
     # -- helpers -------------------------------------------------------------------------------------------------------------
     @staticmethod
     def _L():
@@ -539,6 +547,14 @@ class ShardedFineToCoarse:
     def get_consistency(self, *args, **kwargs):
         from . import depth
         depth.no_consistency("ShardedFineToCoarse")
+
+    def get_warped_views(self, *args, **kwargs):
+        from . import depth
+        depth.no_view_warp("ShardedFineToCoarse")
+
+    def get_view_prediction(self, *args, **kwargs):
+        from . import depth
+        depth.no_view_warp("ShardedFineToCoarse", "get_view_prediction")
 
     @property
     def pixels_scanned(self) -> int:
