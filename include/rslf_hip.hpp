@@ -749,54 +749,24 @@ public:
                       "rslf_multi_depth2d_run_f32");
             return;
         }
-        if (peaks_) {   // every visit in the peaks mode (rslf_sweep_peaks), with or without the other two
-            if (line_mode != RSLF_LINE_CONF_OFF)
-                m_line_confidence_s_v_u.assign(n, 0.f);
+        if (line_mode != RSLF_LINE_CONF_OFF)   // dc.hpp:721-738, :791-792
+            m_line_confidence_s_v_u.assign(n, 0.f);
+        rslf_peaks planes = {};
+        if (peaks_) {   // every visit in the peaks mode (rslf_sweep_peaks)
             peaks_s_v_u_.idx.assign(n, -1), peaks_s_v_u_.runner_idx.assign(n, -1);
             peaks_s_v_u_.score.assign(n, 0.f), peaks_s_v_u_.runner_score.assign(n, 0.f);
-            const rslf_peaks planes = {peaks_s_v_u_.idx.data(), peaks_s_v_u_.score.data(), nullptr, peaks_s_v_u_.runner_idx.data(),
-                                       peaks_s_v_u_.runner_score.data()};
-            if (propagation_ratio_ != 0.f) {   // ... and gated by the peak ratio (rslf_sweep_propagation_ratio)
-                check(rslf_depth2d_run_host_pr(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
-                                               m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
-                                               m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
-                                               line_mode != RSLF_LINE_CONF_OFF ? m_line_confidence_s_v_u.data() : nullptr,
-                                               subgrid_ ? 1 : 0, &planes, propagation_ratio_),
-                      "rslf_depth2d_run_host_pr");
-                check(rslf_sweep_withheld(ctx_->get(), &withheld_), "rslf_sweep_withheld");
-                return;
-            }
-            check(rslf_depth2d_run_host_pk(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
-                                           m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
-                                           m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
-                                           line_mode != RSLF_LINE_CONF_OFF ? m_line_confidence_s_v_u.data() : nullptr, subgrid_ ? 1 : 0,
-                                           &planes),
-                  "rslf_depth2d_run_host_pk");
-            return;
+            planes.idx = peaks_s_v_u_.idx.data(), planes.score = peaks_s_v_u_.score.data();
+            planes.runner_idx = peaks_s_v_u_.runner_idx.data(), planes.runner_score = peaks_s_v_u_.runner_score.data();
         }
-        if (subgrid_) {   // every visit in the sub-grid mode (rslf_sweep_subgrid), with or without line confidence
-            if (line_mode != RSLF_LINE_CONF_OFF)
-                m_line_confidence_s_v_u.assign(n, 0.f);
-            check(rslf_depth2d_run_host_sub(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
-                                            m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
-                                            m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
-                                            line_mode != RSLF_LINE_CONF_OFF ? m_line_confidence_s_v_u.data() : nullptr, 1),
-                  "rslf_depth2d_run_host_sub");
-            return;
-        }
-        if (line_mode != RSLF_LINE_CONF_OFF) {   // dc.hpp:721-738, :791-792
-            m_line_confidence_s_v_u.assign(n, 0.f);
-            check(rslf_depth2d_run_host_lc(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
-                                           m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
-                                           m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats, line_mode,
-                                           m_line_confidence_s_v_u.data()),
-                  "rslf_depth2d_run_host_lc");
-            return;
-        }
-        check(rslf_depth2d_run_host(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
-                                    m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(),
-                                    m_best_depth_s_v_u.data(), m_rbar_s_v_u.data(), &stats),
-              "rslf_depth2d_run_host");
+        // the family's widest entry: a mode that is off goes in neutral, and the call is the narrower entry's (rslf_hip.h)
+        check(rslf_depth2d_run_host_pr(ctx_->get(), vol_, m_dmin, m_dmax, m_dim_d, &p, m_edge_confidence_s_v_u.data(),
+                                       m_edge_confidence_mask_s_v_u.data(), m_disp_confidence_s_v_u.data(), m_best_depth_s_v_u.data(),
+                                       m_rbar_s_v_u.data(), &stats, line_mode,
+                                       line_mode != RSLF_LINE_CONF_OFF ? m_line_confidence_s_v_u.data() : nullptr, subgrid_ ? 1 : 0,
+                                       peaks_ ? &planes : nullptr, propagation_ratio_),
+              "rslf_depth2d_run_host_pr");
+        if (propagation_ratio_ != 0.f)   // gated by the peak ratio (rslf_sweep_propagation_ratio): what it withheld
+            check(rslf_sweep_withheld(ctx_->get(), &withheld_), "rslf_sweep_withheld");
     }
     // Not in the reference: with the mode on, every visit of run() moves the disparities its scan assigns off the hypothesis
     // grid (rslf_sweep_subgrid, rslf_hip.h) before the selective median and the propagation read them; m_best_depth_s_v_u
@@ -1313,32 +1283,26 @@ public:
             run_levels(p);
             return;
         }
-        if (type_ == InputType::U16) {   // ushort arithmetic through the pyramid
-            const uint16_t* const* e = (const uint16_t* const*)epis_.data();
-            if (multi_)
-                check(rslf_multi_fine_to_coarse_run_host_u16(multi_->get(), e, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
-                                                             dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
-                                                             out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats),
+        if (multi_) {
+            if (type_ == InputType::U16)   // ushort arithmetic through the pyramid
+                check(rslf_multi_fine_to_coarse_run_host_u16(multi_->get(), (const uint16_t* const*)epis_.data(), dim_v_, dim_s_, dim_u_,
+                                                             CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_,
+                                                             accept_all_ ? 1 : 0, out_map_s_v_u_.data(), out_validity_s_v_u_.data(),
+                                                             &n_levels_, &stats),
                       "rslf_multi_fine_to_coarse_run_host_u16");
             else
-                check(rslf_fine_to_coarse_run_host_u16(ctx_->get(), e, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
-                                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
-                                                       out_validity_s_v_u_.data(), &n_levels_, &stats),
-                      "rslf_fine_to_coarse_run_host_u16");
+                check(rslf_multi_fine_to_coarse_run_host(multi_->get(), epis_.data(), type_ == InputType::U8 ? 1 : 0, dim_v_, dim_s_, dim_u_,
+                                                         CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_,
+                                                         accept_all_ ? 1 : 0, out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_,
+                                                         &stats),
+                      "rslf_multi_fine_to_coarse_run_host");
             return;
         }
-        const int is_u8 = type_ == InputType::U8 ? 1 : 0;
-        if (multi_) {
-            check(rslf_multi_fine_to_coarse_run_host(multi_->get(), epis_.data(), is_u8, dim_v_, dim_s_, dim_u_, CHANNELS, stride_,
-                                                     d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
-                                                     out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats),
-                  "rslf_multi_fine_to_coarse_run_host");
-            return;
-        }
-        check(rslf_fine_to_coarse_run_host(ctx_->get(), epis_.data(), is_u8, dim_v_, dim_s_, dim_u_, CHANNELS, stride_,
-                                           d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
-                                           out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats),
-              "rslf_fine_to_coarse_run_host");
+        // the family's widest entry, which takes any element type: no mode, no levels out
+        check(rslf_fine_to_coarse_run_host_sub(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
+                                               out_validity_s_v_u_.data(), &n_levels_, &stats, RSLF_LINE_CONF_OFF, nullptr, 0),
+              "rslf_fine_to_coarse_run_host_sub");
     }
     void get_results(std::vector<float>& out_map_s_v_u, std::vector<uint8_t>& out_validity_s_v_u) const
     {
@@ -1467,42 +1431,18 @@ private:
         line_confidence_pyr_.clear();
         disp_confidence_pyr_.clear();
         dims_.clear();
-        const int elem = type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32;
         peaks_held_ = false;
         detail::require(peaks_ || uniqueness_ == 0.f, "FineToCoarse: the uniqueness ratio reads the peak planes: call set_peaks(true)");
         detail::require(peaks_ || propagation_ratio_ == 0.f, "FineToCoarse: the propagation ratio reads the peak planes: call set_peaks(true)");
         gate_held_ = false;
-        if (gate_min_agree_ > 0) {
-            check(rslf_f2c_run_host_cs(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
-                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
-                                       validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, peaks_ ? 1 : 0, uniqueness_,
-                                       propagation_ratio_, gate_tol_, gate_radius_, gate_min_agree_),
-                  "rslf_f2c_run_host_cs");
-            peaks_held_ = peaks_;
-            gate_held_ = true;
-        } else if (peaks_ && propagation_ratio_ != 0.f) {
-            check(rslf_f2c_run_host_pr(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
-                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
-                                       validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, 1, uniqueness_,
-                                       propagation_ratio_),
-                  "rslf_f2c_run_host_pr");
-            peaks_held_ = true;
-        } else if (peaks_) {
-            check(rslf_f2c_run_host_pk(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
-                                       scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
-                                       validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, 1, uniqueness_),
-                  "rslf_f2c_run_host_pk");
-            peaks_held_ = true;
-        } else if (subgrid_)
-            check(rslf_f2c_run_host_sub(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_,
-                                        scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_,
-                                        validity_rule_, keep_volumes_ ? 1 : 0, &run_, &stats, 1),
-                  "rslf_f2c_run_host_sub");
-        else
-            check(rslf_f2c_run_host(ctx_->get(), epis_.data(), elem, dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
-                                    &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
-                                    keep_volumes_ ? 1 : 0, &run_, &stats),
-                  "rslf_f2c_run_host");
+        // the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's (rslf_hip.h)
+        check(rslf_f2c_run_host_cs(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
+                                   &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
+                                   keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, peaks_ ? 1 : 0, uniqueness_, propagation_ratio_,
+                                   gate_tol_, gate_radius_, gate_min_agree_),
+              "rslf_f2c_run_host_cs");
+        peaks_held_ = peaks_;
+        gate_held_ = gate_min_agree_ > 0;
         rslf_f2c_run_desc d;
         check(rslf_f2c_run_describe(run_, &d), "rslf_f2c_run_describe");
         n_levels_ = d.n_levels;
@@ -1549,7 +1489,7 @@ private:
             check(rslf_f2c_run_render_depth_pyr_host(run_, on.get(), index, saturate ? 1 : 0, lut_bgr, ptrs.data()), "rslf_f2c_run_render_depth_pyr_host");
         return out;
     }
-    // run() through rslf_fine_to_coarse_run_host_lc / _u16_lc, every level's planes kept
+    // run() through rslf_fine_to_coarse_run_host_sub, every level's planes kept
     void run_levels(const rslf_params& p)
     {
         const int mode = line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_;   // (set_subgrid alone leaves the line mode unset)
@@ -1580,24 +1520,13 @@ private:
         lo.h_valid_svu = hv.data();
         lo.h_Cl_svu = hl.data();
         lo.h_Ce_svu = nullptr;
-        if (subgrid_)
-            check(rslf_fine_to_coarse_run_host_sub(ctx_->get(), epis_.data(),
-                                                   type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32,
-                                                   dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_,
-                                                   accept_all_ ? 1 : 0, out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats,
-                                                   mode, &lo, 1),
-                  "rslf_fine_to_coarse_run_host_sub");
-        else if (type_ == InputType::U16)
-            check(rslf_fine_to_coarse_run_host_u16_lc(ctx_->get(), (const uint16_t* const*)epis_.data(), dim_v_, dim_s_, dim_u_, CHANNELS,
-                                                      stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
-                                                      out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo),
-                  "rslf_fine_to_coarse_run_host_u16_lc");
-        else
-            check(rslf_fine_to_coarse_run_host_lc(ctx_->get(), epis_.data(), type_ == InputType::U8 ? 1 : 0, dim_v_, dim_s_, dim_u_, CHANNELS,
-                                                  stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0,
-                                                  out_map_s_v_u_.data(), out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo),
-                  "rslf_fine_to_coarse_run_host_lc");
+        // the family's widest entry, which takes any element type
+        check(rslf_fine_to_coarse_run_host_sub(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
+                                               out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo, subgrid_ ? 1 : 0),
+              "rslf_fine_to_coarse_run_host_sub");
     }
+    int elem() const { return type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32; }
 #ifdef RSLFX_HAVE_OPENCV
     FineToCoarse(Context* ctx, MultiContext* multi, const detail::MatInput& in, float d_min, float d_max, int dim_d,
                  float epi_scale_factor, const Depth1DParameters& parameters, int max_pyr_depth, bool accept_all_last_scale)

@@ -286,35 +286,34 @@ static int f2c_valid_mask(hipStream_t st, const float* conf, uint8_t* out, size_
     return RSLF_OK;
 }
 
-int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
-                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
-                         int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
-                         int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep,
-                         const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep)
+int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& o, const F2cHostOut& out, rslf_stats* stats,
+                         F2cKept* keep, const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep)
 {
-    if (!ctx || !h_epis || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
+    const int V = req.V, S = req.S, U = req.U, C = req.C;
+    const rslf_params* const p = req.p;
+    if (!ctx || !req.h_epis || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
-    if (!keep && (!h_out_map_svu || !h_out_valid_svu))   // a kept run holds the fused planes itself
+    if (!keep && (!out.map_svu || !out.valid_svu))   // a kept run holds the fused planes itself
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
-    if (!plan::f2c_validity_rule_ok(validity_rule) || (!keep && validity_rule != RSLF_F2C_VALID_COMPAT))
-        return fail(RSLF_ERR_INVALID_ARG, "validity rule %d: RSLF_F2C_VALID_COMPAT or, for a kept run, _REFERENCE", validity_rule);
-    if (!plan::line_conf_mode_ok(line_mode))
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
+    if (!plan::f2c_validity_rule_ok(o.validity_rule) || (!keep && o.validity_rule != RSLF_F2C_VALID_COMPAT))
+        return fail(RSLF_ERR_INVALID_ARG, "validity rule %d: RSLF_F2C_VALID_COMPAT or, for a kept run, _REFERENCE", o.validity_rule);
+    if (!plan::line_conf_mode_ok(o.line_mode))
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", o.line_mode);
     int rc = check_params(p);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     // constructor: rslf_fine_to_coarse.hpp:103-159 -- the level sizes are plan::f2c_pyramid
-    const std::vector<plan::LevelDims> dims = plan::f2c_pyramid(V, U, max_pyr_depth);
+    const std::vector<plan::LevelDims> dims = plan::f2c_pyramid(V, U, req.max_pyr_depth);
     if (dims.empty())
         return fail(RSLF_ERR_INVALID_ARG, "light field %dx%d is not larger than _MIN_SPATIAL_DIM: no pyramid level", V, U);
     const int P = (int)dims.size();
-    if (levels_out && levels_out->capacity < P)
-        return fail(RSLF_ERR_INVALID_ARG, "levels out: capacity %d < pyramid depth %d", levels_out->capacity, P);
+    if (out.levels && out.levels->capacity < P)
+        return fail(RSLF_ERR_INVALID_ARG, "levels out: capacity %d < pyramid depth %d", out.levels->capacity, P);
     DevBuf raw;   // the raw (un-normalised) values of the level at hand, [V][S][U][C]
     HIP_TRY(raw.alloc((size_t)V * S * U * C * sizeof(float)));
-    rc = f2c_upload_raw(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, raw.as<float>());
+    rc = f2c_upload_raw(ctx, req.elem, req.h_epis, V, S, U, C, req.row_stride_bytes, raw.as<float>());
     if (rc)
         return rc;
 
@@ -327,7 +326,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     rslf_stats st1;
     memset(&st1, 0, sizeof(st1));
     DevBuf cs_dropped;   // the consistency gate's counters, one per level: zeroed here, read once after the loop's last wait
-    if (K.cs_min_agree > 0) {
+    if (o.cs_min_agree > 0) {
         HIP_TRY(cs_dropped.alloc((size_t)P * sizeof(unsigned long long)));
         HIP_TRY(hipMemsetAsync(cs_dropped.get(), 0, (size_t)P * sizeof(unsigned long long), st));
     }
@@ -340,28 +339,28 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         lv.params.slope_factor = (float)((0.0 + lv.U) / U);              // f2c.hpp:139
         kl.slope = lv.params.slope_factor;
         const size_t n = (size_t)S * lv.V * lv.U;
-        rc = f2c_level_scale(ctx, elem, raw.as<const float>(), n * C, epi_scale_factor, &lv.scale);
+        rc = f2c_level_scale(ctx, req.elem, raw.as<const float>(), n * C, req.epi_scale_factor, &lv.scale);
         if (rc)
             return rc;
         kl.scale = lv.scale;
         DevBuf next;                                                       // f2c.hpp:145-147: the RAW EPIs go down
         if (l + 1 < P) {
             HIP_TRY(next.alloc((size_t)dims[l + 1].V * S * dims[l + 1].U * C * sizeof(float)));
-            rc = f2c_downsample(ctx, elem, raw.as<const float>(), lv.V, S, lv.U, C, next.as<float>());
+            rc = f2c_downsample(ctx, req.elem, raw.as<const float>(), lv.V, S, lv.U, C, next.as<float>());
             if (rc)
                 return rc;
         }
         DevBuf dmin, dmax, ungated;   // (ungated: the validity the consistency gate read, freed with the level's ranges)
         DevBuf &Ce = kl.Ce, &Cl = kl.Cl;
         HIP_TRY(Ce.alloc(n * 4));
-        if (line_mode != RSLF_LINE_CONF_OFF)
+        if (o.line_mode != RSLF_LINE_CONF_OFF)
             HIP_TRY(Cl.alloc(n * 4));   // dc.hpp:721-738: every level's computer has a plane of its own
         HIP_TRY(kl.depth.alloc(n * 4));
         HIP_TRY(kl.valid.alloc(n));
         if (keep)
             HIP_TRY(kl.Cd.alloc(n * 4));
         rslf_peaks pk = {};
-        if (K.peaks) {   // the level's sweep fills them with -1 / 0 before its first visit (depth2d_run_lc)
+        if (o.peaks) {   // the level's sweep fills them with -1 / 0 before its first visit (depth2d_run)
             HIP_TRY(kl.pk_idx.alloc(n * 4));
             HIP_TRY(kl.pk_score.alloc(n * 4));
             HIP_TRY(kl.pk_runner_idx.alloc(n * 4));
@@ -371,15 +370,14 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             pk.runner_idx = kl.pk_runner_idx.as<int32_t>();
             pk.runner_score = kl.pk_runner_score.as<float>();
             lv.peaks = &pk;
-            lv.propagation_ratio = K.propagation_ratio;   // 0 unless a kept run asked for the gate
             lv.withheld = &kl.withheld;
         }
         if (l > 0) {
             HIP_TRY(dmin.alloc(n * 4));
             HIP_TRY(dmax.alloc(n * 4));
-            rc = f2c_fill_f32(st, dmin.as<float>(), n, d_min);
+            rc = f2c_fill_f32(st, dmin.as<float>(), n, req.d_min);
             if (!rc)
-                rc = f2c_fill_f32(st, dmax.as<float>(), n, d_max);
+                rc = f2c_fill_f32(st, dmax.as<float>(), n, req.d_max);
             if (!rc)
                 rc = rslf_f2c_tighten_bounds(ctx, K.levels[(size_t)l - 1].depth.as<const float>(),
                                              K.levels[(size_t)l - 1].valid.as<const uint8_t>(), S, dims[l - 1].V, dims[l - 1].U,
@@ -392,19 +390,18 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         lv.dmax_svu = dmax.as<const float>();
         lv.Ce_svu = Ce.as<float>();
         lv.depth_svu = kl.depth.as<float>();
-        lv.line_mode = line_mode;
+        lv.options = &o;
         lv.Cl_svu = Cl.as<float>();
         lv.Cd_svu = kl.Cd.as<float>();
-        lv.vol_out = (keep && keep->keep_volumes) ? &kl.vol : nullptr;
-        lv.consistency_min_agree = K.cs_min_agree;
+        lv.vol_out = (keep && o.keep_volumes) ? &kl.vol : nullptr;
         rc = sweep(lv, &st1);
         if (rc)
             return rc;
         pixels += st1.pixels_scanned;
         // get_valid_depths_mask_s_v_u (dc.hpp:893-915), asked for by the next level's bounds (f2c.hpp:185-186) and by the
         // fusion (:312): the last level accepts everything when asked to (f2c.hpp:157-158)
-        const plan::F2cValidity by = plan::f2c_validity_by_rule(accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0,
-                                                                line_mode, validity_rule);
+        const plan::F2cValidity by = plan::f2c_validity_by_rule(req.accept_all_last_scale && l == P - 1, p->use_disp_confidence_score != 0,
+                                                                o.line_mode, o.validity_rule);
         switch (by) {
         case plan::kValidAll:
             rc = f2c_valid_mask(st, Ce.as<const float>(), kl.valid.as<uint8_t>(), n, -1.0f);
@@ -420,29 +417,29 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
             break;
         }
         // validity by uniqueness: what the rule left valid goes invalid where the runner-up is within the ratio of the winner
-        if (!rc && K.peaks && plan::f2c_unique_applies(K.uniqueness, by))
-            rc = rslf_f2c_unique_mask(ctx, kl.valid.as<uint8_t>(), &pk, K.uniqueness, n);
+        if (!rc && o.peaks && plan::f2c_unique_applies(o.uniqueness, by))
+            rc = rslf_f2c_unique_mask(ctx, kl.valid.as<uint8_t>(), &pk, o.uniqueness, n);
         // validity by cross-view consistency: what is still valid goes invalid where the other views contradict it.  The gate
         // writes a second plane (a thread reads the other views' rows while they are written), which takes the first one's place
-        if (!rc && plan::f2c_consistency_applies(K.cs_min_agree, by)) {
+        if (!rc && plan::f2c_consistency_applies(o.cs_min_agree, by)) {
             HIP_TRY(ungated.alloc(n));
             HIP_TRY(kl.cs_agree.alloc(n * 4));
             HIP_TRY(kl.cs_seen.alloc(n * 4));
-            rc = rslf_f2c_consistency_mask(ctx, kl.depth.as<const float>(), kl.valid.as<const uint8_t>(), S, lv.V, lv.U, kl.slope, K.cs_tol,
-                                           K.cs_radius, K.cs_min_agree, ungated.as<uint8_t>(), kl.cs_agree.as<int32_t>(),
+            rc = rslf_f2c_consistency_mask(ctx, kl.depth.as<const float>(), kl.valid.as<const uint8_t>(), S, lv.V, lv.U, kl.slope, o.cs_tol,
+                                           o.cs_radius, o.cs_min_agree, ungated.as<uint8_t>(), kl.cs_agree.as<int32_t>(),
                                            kl.cs_seen.as<int32_t>(), cs_dropped.as<unsigned long long>() + l);
             std::swap(kl.valid, ungated);   // kl.valid: the gated plane
         }
         if (rc)
             return rc;
-        if (levels_out) {   // host copies of the level's planes; C_e and C_l leave the device with this iteration
-            const auto out = [&](void* const* hp, const void* d, size_t bytes) -> hipError_t {
+        if (out.levels) {   // host copies of the level's planes; C_e and C_l leave the device with this iteration
+            const auto copy = [&](void* const* hp, const void* d, size_t bytes) -> hipError_t {
                 return (hp && hp[l] && d) ? hipMemcpyAsync(hp[l], d, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
             };
-            HIP_TRY(out((void* const*)levels_out->h_depth_svu, kl.depth.get(), n * 4));
-            HIP_TRY(out((void* const*)levels_out->h_valid_svu, kl.valid.get(), n));
-            HIP_TRY(out((void* const*)levels_out->h_Cl_svu, Cl.get(), n * 4));
-            HIP_TRY(out((void* const*)levels_out->h_Ce_svu, Ce.get(), n * 4));
+            HIP_TRY(copy((void* const*)out.levels->h_depth_svu, kl.depth.get(), n * 4));
+            HIP_TRY(copy((void* const*)out.levels->h_valid_svu, kl.valid.get(), n));
+            HIP_TRY(copy((void* const*)out.levels->h_Cl_svu, Cl.get(), n * 4));
+            HIP_TRY(copy((void* const*)out.levels->h_Ce_svu, Ce.get(), n * 4));
             HIP_TRY(hipStreamSynchronize(st));
         }
         if (!keep) {            // the level's confidences have served
@@ -469,7 +466,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
     rc = rslf_f2c_fuse(ctx, dp.data(), vp.data(), Vp.data(), Up.data(), P, S, omap.as<float>(), ovalid.as<uint8_t>());
     if (rc)
         return rc;
-    if (K.peaks) {   // which level decided each fused pixel, and that level's peaks there: one launch over the whole pyramid
+    if (o.peaks) {   // which level decided each fused pixel, and that level's peaks there: one launch over the whole pyramid
         std::vector<rslf_peaks> pp((size_t)P);
         for (int l = 0; l < P; l++) {
             F2cKeptLevel& kl = K.levels[(size_t)l];
@@ -487,35 +484,35 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, in
         if (rc)
             return rc;
     }
-    if (h_out_map_svu)
-        HIP_TRY(hipMemcpyAsync(h_out_map_svu, omap.get(), n0 * 4, hipMemcpyDeviceToHost, st));
-    if (h_out_valid_svu)
-        HIP_TRY(hipMemcpyAsync(h_out_valid_svu, ovalid.get(), n0, hipMemcpyDeviceToHost, st));
+    if (out.map_svu)
+        HIP_TRY(hipMemcpyAsync(out.map_svu, omap.get(), n0 * 4, hipMemcpyDeviceToHost, st));
+    if (out.valid_svu)
+        HIP_TRY(hipMemcpyAsync(out.valid_svu, ovalid.get(), n0, hipMemcpyDeviceToHost, st));
     std::vector<unsigned long long> dropped((size_t)P, 0ull);
-    if (K.cs_min_agree > 0)
+    if (o.cs_min_agree > 0)
         HIP_TRY(hipMemcpyAsync(dropped.data(), cs_dropped.get(), (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int l = 0; l < P; l++)
         K.levels[(size_t)l].inconsistent = dropped[(size_t)l];
-    if (n_levels)
-        *n_levels = P;
+    if (out.n_levels)
+        *out.n_levels = P;
     if (stats) {
         *stats = st1;
         stats->pixels_scanned = pixels;
-        stats->units = pixels * dim_d;
+        stats->units = pixels * req.dim_d;
     }
     return RSLF_OK;
 }
 
-// FineToCoarse on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run_lc.
-int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C,
-                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
-                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, float* h_out_map_svu,
-                                     uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats, int line_mode,
-                                     const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep, int subgrid)
+// FineToCoarse on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run.
+int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& o, const F2cHostOut& out,
+                                     rslf_stats* stats, F2cKept* keep)
 {
-    if (subgrid != 0 && subgrid != 1)
-        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
+    SweepModes asked;   // what of the levels' modes can be refused before the loop allocates: the planes come with each level
+    asked.subgrid = o.subgrid;
+    if (int rc = check_sweep_modes(asked))
+        return rc;
+    const int S = req.S, C = req.C;
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
         if (inject_hit(kInjectSweep))   // host side, before the level's sweep is queued
             throw std::runtime_error("injected failure in a fine-to-coarse level (rslf_debug_inject)");
@@ -531,19 +528,20 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const
         vol.reset(made);
         if (!rc)
             rc = rslf_volume_pack_device_f32(vol.get(), lv.raw_vsuc, lv.scale, nullptr);
+        const SweepPlanes planes = {lv.Ce_svu, mask.as<uint8_t>(), lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(),
+                                    nullptr};
+        SweepModes modes;
+        modes.line_mode = o.line_mode, modes.Cl_svu = lv.Cl_svu, modes.subgrid = o.subgrid;
+        modes.peaks = lv.peaks, modes.propagation_ratio = o.propagation_ratio;
         if (!rc)
-            rc = depth2d_run_lc(ctx, vol.get(), lv.dmin_svu, lv.dmax_svu, d_min, d_max, dim_d, &lv.params, lv.Ce_svu, mask.as<uint8_t>(),
-                                lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(), nullptr, level_stats,
-                                lv.line_mode, lv.Cl_svu, subgrid, lv.peaks, lv.propagation_ratio);
-        if (!rc && lv.propagation_ratio > 0.0f && lv.withheld)
+            rc = depth2d_run(ctx, vol.get(), lv.dmin_svu, lv.dmax_svu, req.d_min, req.d_max, req.dim_d, &lv.params, planes, level_stats, modes);
+        if (!rc && o.propagation_ratio > 0.0f && lv.withheld)
             rc = rslf_sweep_withheld(ctx, lv.withheld);
         if (!rc && lv.vol_out)
             *lv.vol_out = std::move(vol);   // kept; otherwise destroyed here, with the sweep's other planes
         return rc;
     };
-    return fine_to_coarse(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, line_mode, levels_out, validity_rule,
-                          keep, sweep);
+    return fine_to_coarse(ctx, req, o, out, stats, keep, sweep);
 }
 
 extern "C" int rslf_f2c_pyramid_dims(int V, int U, int max_pyr_depth, int* Vp, int* Up, int capacity, int* n_levels) RSLF_API_TRY
@@ -562,31 +560,41 @@ extern "C" int rslf_f2c_pyramid_dims(int V, int U, int max_pyr_depth, int* Vp, i
 }
 RSLF_API_CATCH
 
+// The host-planes entries: the same call, the request in the order of their arguments; what an entry lacks stays off.
+
+extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
+                                            size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                            const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                            float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+{
+    const F2cRequest req = {is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                            max_pyr_depth, accept_all_last_scale};
+    return fine_to_coarse_one_context(ctx, req, F2cOptions(), {h_out_map_svu, h_out_valid_svu, n_levels, nullptr}, stats, nullptr);
+}
+RSLF_API_CATCH
+
+extern "C" int rslf_fine_to_coarse_run_host_u16(rslf_ctx* ctx, const uint16_t* const* h_epis, int V, int S, int U, int C,
+                                                size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                                const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+{
+    const F2cRequest req = {Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                            max_pyr_depth, accept_all_last_scale};
+    return fine_to_coarse_one_context(ctx, req, F2cOptions(), {h_out_map_svu, h_out_valid_svu, n_levels, nullptr}, stats, nullptr);
+}
+RSLF_API_CATCH
+
 extern "C" int rslf_fine_to_coarse_run_host_lc(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
                                                size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                                const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
                                                int line_mode, const rslf_f2c_levels_out* levels_out) RSLF_API_TRY
 {
-    return fine_to_coarse_one_context(ctx, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                      epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
-                                      stats, line_mode, levels_out, RSLF_F2C_VALID_COMPAT, nullptr);
-}
-RSLF_API_CATCH
-
-// ... any element type (RSLF_ELEM_*), every level's sweep in the sub-grid mode with subgrid = 1
-extern "C" int rslf_fine_to_coarse_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
-                                                size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
-                                                const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
-                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
-                                                int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid) RSLF_API_TRY
-{
-    if (elem != RSLF_ELEM_F32 && elem != RSLF_ELEM_U8 && elem != RSLF_ELEM_U16)
-        return fail(RSLF_ERR_INVALID_ARG, "element type %d: RSLF_ELEM_F32, _U8 or _U16", elem);
-    const Elem e = elem == RSLF_ELEM_U8 ? Elem::U8 : elem == RSLF_ELEM_U16 ? Elem::U16 : Elem::F32;
-    return fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
-                                      max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, line_mode,
-                                      levels_out, RSLF_F2C_VALID_COMPAT, nullptr, subgrid);
+    const F2cRequest req = {is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                            max_pyr_depth, accept_all_last_scale};
+    F2cOptions options;
+    options.line_mode = line_mode;
+    return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
 }
 RSLF_API_CATCH
 
@@ -597,30 +605,28 @@ extern "C" int rslf_fine_to_coarse_run_host_u16_lc(rslf_ctx* ctx, const uint16_t
                                                    int* n_levels, rslf_stats* stats, int line_mode,
                                                    const rslf_f2c_levels_out* levels_out) RSLF_API_TRY
 {
-    return fine_to_coarse_one_context(ctx, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                      epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels,
-                                      stats, line_mode, levels_out, RSLF_F2C_VALID_COMPAT, nullptr);
+    const F2cRequest req = {Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                            max_pyr_depth, accept_all_last_scale};
+    F2cOptions options;
+    options.line_mode = line_mode;
+    return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
 }
 RSLF_API_CATCH
 
-extern "C" int rslf_fine_to_coarse_run_host(rslf_ctx* ctx, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
-                                            size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
-                                            const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
-                                            float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
-{
-    return rslf_fine_to_coarse_run_host_lc(ctx, h_epis, is_u8, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
-                                           max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats,
-                                           RSLF_LINE_CONF_OFF, nullptr);
-}
-RSLF_API_CATCH
-
-extern "C" int rslf_fine_to_coarse_run_host_u16(rslf_ctx* ctx, const uint16_t* const* h_epis, int V, int S, int U, int C,
+// ... any element type (RSLF_ELEM_*), every level's sweep in the sub-grid mode with subgrid = 1
+extern "C" int rslf_fine_to_coarse_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
                                                 size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                                 const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
-                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
+                                                float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                                int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid) RSLF_API_TRY
 {
-    return rslf_fine_to_coarse_run_host_u16_lc(ctx, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
-                                               max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats,
-                                               RSLF_LINE_CONF_OFF, nullptr);
+    Elem e;
+    if (int rc = elem_of(elem, &e))
+        return rc;
+    const F2cRequest req = {e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions options;
+    options.line_mode = line_mode, options.subgrid = subgrid;
+    return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
 }
 RSLF_API_CATCH

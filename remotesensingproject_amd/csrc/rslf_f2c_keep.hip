@@ -10,22 +10,6 @@ using namespace rslf;
 
 namespace {
 
-int elem_of(int elem, Elem* out)
-{
-    switch (elem) {
-    case RSLF_ELEM_F32:
-        *out = Elem::F32;
-        return RSLF_OK;
-    case RSLF_ELEM_U8:
-        *out = Elem::U8;
-        return RSLF_OK;
-    case RSLF_ELEM_U16:
-        *out = Elem::U16;
-        return RSLF_OK;
-    }
-    return fail(RSLF_ERR_INVALID_ARG, "element type %d: RSLF_ELEM_F32, _U8 or _U16", elem);
-}
-
 bool is_peak_plane(int which) { return which >= RSLF_F2C_PLANE_PK_IDX && which <= RSLF_F2C_PLANE_FUSED_LEVEL; }
 bool is_gate_plane(int which) { return which == RSLF_F2C_PLANE_CS_AGREE || which == RSLF_F2C_PLANE_CS_SEEN; }
 bool is_fused_plane(int which)
@@ -82,6 +66,20 @@ const void* plane_of(const rslf_f2c_run* run, int level, int which, size_t* byte
         return kl.cs_seen.get();
     }
     return nullptr;
+}
+
+// The two wordings of "the run has no such level"
+int check_level_outside(const rslf_f2c_run* run, int level)
+{
+    if (level < 0 || level >= (int)run->kept.levels.size())
+        return fail(RSLF_ERR_INVALID_ARG, "level=%d outside [0,%d)", level, (int)run->kept.levels.size());
+    return RSLF_OK;
+}
+int check_level_of(const rslf_f2c_run* run, int level)
+{
+    if (level < 0 || level >= (int)run->kept.levels.size())
+        return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
+    return RSLF_OK;
 }
 
 int check_render_args(const rslf_f2c_run* run, const rslf_ctx* ctx, const void* lut_bgr, const void* out)
@@ -278,138 +276,131 @@ int render_epi_pyr(const rslf_f2c_run* run, rslf_ctx* ctx, int v, int saturate, 
 
 }  // namespace
 
-static int f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
-                                 float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
-                                 int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
-                                 rslf_stats* stats, int subgrid, int peaks = 0, float uniqueness_ratio = 0.0f,
-                                 float propagation_ratio = 0.0f, float consistency_tol = 0.0f, int consistency_radius = 0,
-                                 int consistency_min_agree = 0)
+// A pyramid run and kept: req.elem comes from `elem` here, everything else of req and o as the entry filled it.
+static int f2c_run_host(rslf_ctx* ctx, int elem, F2cRequest req, const F2cOptions& o, rslf_f2c_run** run, rslf_stats* stats)
 {
     if (!run)
         return fail(RSLF_ERR_INVALID_ARG, "run is NULL");
     *run = nullptr;
-    if (!ctx || !h_epis || !p)
+    if (!ctx || !req.h_epis || !req.p)
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
-    if (subgrid != 0 && subgrid != 1)
-        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
-    switch (plan::f2c_peaks_args(peaks, uniqueness_ratio, dim_d)) {
+    switch (plan::f2c_peaks_args(o.peaks, o.uniqueness, req.dim_d)) {
     case plan::kF2cPeaksOk:
         break;
     case plan::kF2cPeaksBadFlag:
-        return fail(RSLF_ERR_INVALID_ARG, "peaks=%d: 0 or 1", peaks);
+        return fail(RSLF_ERR_INVALID_ARG, "peaks=%d: 0 or 1", o.peaks);
     case plan::kF2cPeaksBadRatio:
-        return fail(RSLF_ERR_INVALID_ARG, "uniqueness_ratio=%g: 0 (off) or a ratio in (0, 1]", (double)uniqueness_ratio);
+        return fail(RSLF_ERR_INVALID_ARG, "uniqueness_ratio=%g: 0 (off) or a ratio in (0, 1]", (double)o.uniqueness);
     case plan::kF2cPeaksRatioAlone:
-        return fail(RSLF_ERR_INVALID_ARG, "uniqueness_ratio=%g reads the peak planes: it needs peaks = 1", (double)uniqueness_ratio);
+        return fail(RSLF_ERR_INVALID_ARG, "uniqueness_ratio=%g reads the peak planes: it needs peaks = 1", (double)o.uniqueness);
     case plan::kF2cPeaksBadDimD:
-        return fail(RSLF_ERR_INVALID_ARG, "dim_d=%d: the peaks take at most %d hypotheses", dim_d, plan::kPeakMaxDimD);
+        return fail(RSLF_ERR_INVALID_ARG, "dim_d=%d: the peaks take at most %d hypotheses", req.dim_d, plan::kPeakMaxDimD);
     }
     // the sweeps' gate by peak ratio: independent of the uniqueness ratio; it reads the levels' peak planes
-    if (!plan::sweep_gate_ratio_ok(propagation_ratio))
-        return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g: 0 (off) or a ratio in (0, 1]", (double)propagation_ratio);
-    if (propagation_ratio != 0.0f && !peaks)
-        return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g reads the peak planes: it needs peaks = 1", (double)propagation_ratio);
+    if (!plan::sweep_gate_ratio_ok(o.propagation_ratio))
+        return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g: 0 (off) or a ratio in (0, 1]", (double)o.propagation_ratio);
+    if (o.propagation_ratio != 0.0f && !o.peaks)
+        return fail(RSLF_ERR_INVALID_ARG, "propagation_ratio=%g reads the peak planes: it needs peaks = 1", (double)o.propagation_ratio);
     // the validity by cross-view consistency: independent of the peaks; 0 is off, and then tol and radius are not looked at
-    switch (plan::f2c_consistency_args(consistency_tol, consistency_min_agree)) {
+    switch (plan::f2c_consistency_args(o.cs_tol, o.cs_min_agree)) {
     case plan::kF2cConsistencyOk:
         break;
     case plan::kF2cConsistencyBadMinAgree:
-        return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree=%d: 0 (off) or a count of agreeing views >= 1", consistency_min_agree);
+        return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree=%d: 0 (off) or a count of agreeing views >= 1", o.cs_min_agree);
     case plan::kF2cConsistencyBadTol:
-        return fail(RSLF_ERR_INVALID_ARG, "consistency_tol=%g: a finite tolerance >= 0", (double)consistency_tol);
+        return fail(RSLF_ERR_INVALID_ARG, "consistency_tol=%g: a finite tolerance >= 0", (double)o.cs_tol);
     }
     // (the level's sweeps would end a sweep the caller left open; the entries without the gate do what they always did)
-    if (consistency_min_agree > 0 && ctx->sweep.open)
+    if (o.cs_min_agree > 0 && ctx->sweep.open)
         return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree: a sweep is open on this context");
-    Elem e;
-    int rc = elem_of(elem, &e);
+    int rc = elem_of(elem, &req.elem);
     if (rc)
         return rc;
-    if ((int)plan::f2c_pyramid(V, U, max_pyr_depth).size() > RSLF_F2C_MAX_LEVELS)
+    if ((int)plan::f2c_pyramid(req.V, req.U, req.max_pyr_depth).size() > RSLF_F2C_MAX_LEVELS)
         return fail(RSLF_ERR_UNSUPPORTED, "a pyramid deeper than %d levels", RSLF_F2C_MAX_LEVELS);
     // (the finest level has the largest grid; a shape that is none is refused by the loop)
-    if (consistency_min_agree > 0 && S >= 1 && V >= 1 && U >= 1 && !plan::consistency_grid(S, V, U))
-        return fail(RSLF_ERR_UNSUPPORTED, "consistency_min_agree: S=%d V=%d U=%d exceed the grid limit of one gate launch (or U > %d)", S, V, U,
-                    plan::kConsistencyMaxU);
+    if (o.cs_min_agree > 0 && req.S >= 1 && req.V >= 1 && req.U >= 1 && !plan::consistency_grid(req.S, req.V, req.U))
+        return fail(RSLF_ERR_UNSUPPORTED, "consistency_min_agree: S=%d V=%d U=%d exceed the grid limit of one gate launch (or U > %d)", req.S,
+                    req.V, req.U, plan::kConsistencyMaxU);
     std::unique_ptr<rslf_f2c_run> r(new rslf_f2c_run());   // whatever path leaves this function, a run not handed out is freed
     r->device = ctx->device;
-    r->S = S;
-    r->C = C;
+    r->S = req.S;
+    r->C = req.C;
     r->elem = elem;
-    r->line_mode = line_mode;
-    r->validity_rule = validity_rule;
-    r->subgrid = subgrid;
-    r->params = *p;
-    r->kept.keep_volumes = keep_volumes != 0;
-    r->peaks = peaks;
-    r->uniqueness = uniqueness_ratio;
-    r->kept.peaks = peaks != 0;
-    r->kept.uniqueness = uniqueness_ratio;
-    r->propagation_ratio = propagation_ratio;
-    r->kept.propagation_ratio = propagation_ratio;
-    if (consistency_min_agree > 0) {
-        r->kept.cs_min_agree = consistency_min_agree;
-        r->kept.cs_tol = consistency_tol;
-        r->kept.cs_radius = consistency_radius;
-    }
-    rc = fine_to_coarse_one_context(ctx, e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                                    accept_all_last_scale, nullptr, nullptr, nullptr, stats, line_mode, nullptr, validity_rule, &r->kept,
-                                    subgrid);
+    r->params = *req.p;
+    r->options = o;
+    if (o.cs_min_agree == 0)   // off: tol and radius were not looked at, and the run reports none
+        r->options.cs_tol = 0.0f, r->options.cs_radius = 0;
+    rc = fine_to_coarse_one_context(ctx, req, r->options, F2cHostOut(), stats, &r->kept);
     if (rc)
         return rc;
     *run = r.release();
     return RSLF_OK;
 }
 
+// The kept-run entries: the same call, the request in the order of their arguments; what an entry lacks stays off.
+
 extern "C" int rslf_f2c_run_host(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
                                  float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
                                  int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
                                  rslf_stats* stats) RSLF_API_TRY
 {
-    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, 0);
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
 }
 RSLF_API_CATCH
 
-// ... every level's sweep in the sub-grid mode (rslf_sweep_subgrid); subgrid = 0 is rslf_f2c_run_host
+// ... every level's sweep in the sub-grid mode (rslf_sweep_subgrid)
 extern "C" int rslf_f2c_run_host_sub(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
                                      size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                      const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
                                      int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid) RSLF_API_TRY
 {
-    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid);
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
 }
 RSLF_API_CATCH
 
 // ... and with peaks = 1 every level's sweep in the peaks mode as well (rslf_sweep_peaks), the four planes of every level and
-// the fused peaks kept; uniqueness_ratio > 0: validity by uniqueness.  peaks = 0, uniqueness_ratio = 0 is rslf_f2c_run_host_sub
+// the fused peaks kept; uniqueness_ratio > 0: validity by uniqueness
 extern "C" int rslf_f2c_run_host_pk(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
                                     int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
                                     float uniqueness_ratio) RSLF_API_TRY
 {
-    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio);
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
+    o.peaks = peaks, o.uniqueness = uniqueness_ratio;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
 }
 RSLF_API_CATCH
 
-// ... and with propagation_ratio > 0 every level's sweep gated by it (rslf_sweep_propagation_ratio); 0 is rslf_f2c_run_host_pk
+// ... and with propagation_ratio > 0 every level's sweep gated by it (rslf_sweep_propagation_ratio)
 extern "C" int rslf_f2c_run_host_pr(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
                                     int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
                                     float uniqueness_ratio, float propagation_ratio) RSLF_API_TRY
 {
-    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio,
-                        propagation_ratio);
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
+    o.peaks = peaks, o.uniqueness = uniqueness_ratio, o.propagation_ratio = propagation_ratio;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
 }
 RSLF_API_CATCH
 
-// ... and with consistency_min_agree > 0 every level's validity gated by the other views (k13_f2c_consistency_gate); 0 is
-// rslf_f2c_run_host_pr
+// ... and with consistency_min_agree > 0 every level's validity gated by the other views (k13_f2c_consistency_gate)
 extern "C" int rslf_f2c_run_host_cs(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
                                     size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
                                     const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
@@ -417,20 +408,24 @@ extern "C" int rslf_f2c_run_host_cs(rslf_ctx* ctx, const void* const* h_epis, in
                                     float uniqueness_ratio, float propagation_ratio, float consistency_tol, int consistency_radius,
                                     int consistency_min_agree) RSLF_API_TRY
 {
-    return f2c_run_host(ctx, h_epis, elem, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                        accept_all_last_scale, line_mode, validity_rule, keep_volumes, run, stats, subgrid, peaks, uniqueness_ratio,
-                        propagation_ratio, consistency_tol, consistency_radius, consistency_min_agree);
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
+    o.peaks = peaks, o.uniqueness = uniqueness_ratio, o.propagation_ratio = propagation_ratio;
+    o.cs_tol = consistency_tol, o.cs_radius = consistency_radius, o.cs_min_agree = consistency_min_agree;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
 }
 RSLF_API_CATCH
 
 extern "C" int rslf_f2c_run_consistency_gate(const rslf_f2c_run* run, float* tol, int* radius, int* min_agree) RSLF_API_TRY
 {
     if (tol)
-        *tol = run ? run->kept.cs_tol : 0.0f;
+        *tol = run ? run->options.cs_tol : 0.0f;
     if (radius)
-        *radius = run ? run->kept.cs_radius : 0;
+        *radius = run ? run->options.cs_radius : 0;
     if (min_agree)
-        *min_agree = run ? run->kept.cs_min_agree : 0;
+        *min_agree = run ? run->options.cs_min_agree : 0;
     return RSLF_OK;
 }
 RSLF_API_CATCH
@@ -440,8 +435,8 @@ extern "C" int rslf_f2c_run_inconsistent(const rslf_f2c_run* run, int level, uns
 {
     if (!run || !n)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (level < 0 || level >= (int)run->kept.levels.size())
-        return fail(RSLF_ERR_INVALID_ARG, "level=%d outside [0,%d)", level, (int)run->kept.levels.size());
+    if (int rc = check_level_outside(run, level))
+        return rc;
     *n = run->kept.levels[(size_t)level].inconsistent;
     return RSLF_OK;
 }
@@ -449,7 +444,7 @@ RSLF_API_CATCH
 
 extern "C" float rslf_f2c_run_propagation_ratio(const rslf_f2c_run* run)
 {
-    return run ? run->propagation_ratio : 0.0f;
+    return run ? run->options.propagation_ratio : 0.0f;
 }
 
 // the sources level `level`'s sweep withheld; 0 on every level of a run without the ratio
@@ -457,8 +452,8 @@ extern "C" int rslf_f2c_run_withheld(const rslf_f2c_run* run, int level, unsigne
 {
     if (!run || !n)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (level < 0 || level >= (int)run->kept.levels.size())
-        return fail(RSLF_ERR_INVALID_ARG, "level=%d outside [0,%d)", level, (int)run->kept.levels.size());
+    if (int rc = check_level_outside(run, level))
+        return rc;
     *n = run->kept.levels[(size_t)level].withheld;
     return RSLF_OK;
 }
@@ -467,19 +462,19 @@ RSLF_API_CATCH
 // (not fields of rslf_f2c_run_desc: the structure keeps its size)
 extern "C" int rslf_f2c_run_peaks(const rslf_f2c_run* run) RSLF_API_TRY
 {
-    return run ? run->peaks : 0;
+    return run ? run->options.peaks : 0;
 }
 RSLF_API_CATCH
 
 extern "C" float rslf_f2c_run_uniqueness(const rslf_f2c_run* run)
 {
-    return run ? run->uniqueness : 0.0f;
+    return run ? run->options.uniqueness : 0.0f;
 }
 
 // (not a field of rslf_f2c_run_desc: the structure keeps its size)
 extern "C" int rslf_f2c_run_subgrid(const rslf_f2c_run* run) RSLF_API_TRY
 {
-    return run ? run->subgrid : 0;
+    return run ? run->options.subgrid : 0;
 }
 RSLF_API_CATCH
 
@@ -504,9 +499,9 @@ extern "C" int rslf_f2c_run_describe(const rslf_f2c_run* run, rslf_f2c_run_desc*
     out->C = run->C;
     out->device = run->device;
     out->elem = run->elem;
-    out->line_mode = run->line_mode;
-    out->validity_rule = run->validity_rule;
-    out->keep_volumes = run->kept.keep_volumes ? 1 : 0;
+    out->line_mode = run->options.line_mode;
+    out->validity_rule = run->options.validity_rule;
+    out->keep_volumes = run->options.keep_volumes ? 1 : 0;
     std::vector<plan::LevelDims> dims;
     for (int l = 0; l < P; l++) {
         const F2cKeptLevel& kl = run->kept.levels[(size_t)l];
@@ -520,8 +515,8 @@ extern "C" int rslf_f2c_run_describe(const rslf_f2c_run* run, rslf_f2c_run_desc*
         if (P > 0 && plane_of(run, 0, which, &bytes))
             out->planes_held |= 1u << which;
     }
-    out->device_bytes = plan::f2c_kept_bytes(run->S, run->C, dims, run->line_mode, run->kept.keep_volumes) +
-                        plan::f2c_peaks_bytes(run->peaks != 0, run->S, dims);
+    out->device_bytes = plan::f2c_kept_bytes(run->S, run->C, dims, run->options.line_mode, run->options.keep_volumes) +
+                        plan::f2c_peaks_bytes(run->options.peaks != 0, run->S, dims);
     for (int l = 0; l < P; l++) {   // the gate's planes: a gated run holds them on every level that was not accepted whole
         const bool gated = run->kept.levels[(size_t)l].cs_agree.get() != nullptr;
         if (gated)
@@ -536,8 +531,8 @@ extern "C" int rslf_f2c_run_copy(const rslf_f2c_run* run, int level, int which, 
 {
     if (!run || !dst)
         return fail(RSLF_ERR_INVALID_ARG, "run/dst is NULL");
-    if (level < 0 || level >= (int)run->kept.levels.size())
-        return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
+    if (int rc = check_level_of(run, level))
+        return rc;
     if (which < RSLF_F2C_PLANE_DEPTH || which > RSLF_F2C_PLANE_CS_SEEN)
         return fail(RSLF_ERR_INVALID_ARG, "plane %d: one of RSLF_F2C_PLANE_*", which);
     if (is_fused_plane(which) && level != 0)
@@ -573,8 +568,8 @@ extern "C" int rslf_f2c_run_volume(const rslf_f2c_run* run, int level, const rsl
         *out = nullptr;
     if (!run || !out)
         return fail(RSLF_ERR_INVALID_ARG, "run/out is NULL");
-    if (level < 0 || level >= (int)run->kept.levels.size())
-        return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
+    if (int rc = check_level_of(run, level))
+        return rc;
     const rslf_volume* vol = run->kept.levels[(size_t)level].vol.get();
     if (!vol)
         return fail(RSLF_ERR_INVALID_ARG, "the run was made without keep_volumes");

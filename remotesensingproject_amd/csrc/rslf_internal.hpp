@@ -504,17 +504,30 @@ int subgrid_refine(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_vu
 // rslf_sweep.hip
 // Depth2DComputer::run (dc.hpp:748-805) on device planes; d_dmin_svu / d_dmax_svu: per-pixel ranges (a fine-to-coarse
 // level, dc.hpp:201-203), or both NULL for the scalar range.
+// The six [S][V][U] result planes of a sweep, which always travel together (rbar has C floats per pixel; scan_mask nullable).
+struct SweepPlanes {
+    float* Ce = nullptr;
+    uint8_t* Ce_mask = nullptr;
+    float* Cd = nullptr;
+    float* depth = nullptr;
+    float* rbar = nullptr;
+    uint8_t* scan_mask = nullptr;
+};
+// What a sweep is asked for beyond the reference's arguments; the defaults are the reference's sweep, and every mode left at
+// its default queues exactly the launches of the sweep without it.
+struct SweepModes {
+    int line_mode = RSLF_LINE_CONF_OFF;   // RSLF_LINE_CONF_* (dc.hpp:721-738, :791-792) ...
+    float* Cl_svu = nullptr;              // ... and its [S][V][U] plane, zero-filled by depth2d_run; NULL when off
+    int subgrid = 0;                      // 1: every visit in the sub-grid mode (rslf_sweep_subgrid)
+    const rslf_peaks* peaks = nullptr;    // the peaks mode's four planes (rslf_sweep_peaks), filled by depth2d_run with
+                                          // idx = runner_idx = -1 and the floats 0; NULL: mode off
+    float propagation_ratio = 0.0f;       // > 0: the sweep gated by it (rslf_sweep_propagation_ratio); needs the four planes
+};
+// The one place a sweep's modes are checked: the gate, the line mode, its plane, subgrid.  Every entry runs it once, before
+// anything is allocated or queued.
+int check_sweep_modes(const SweepModes& modes);
 int depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
-                int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
-                float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats);
-// The same with the line-confidence plane of dc.hpp:721-738, :791-792: line_mode RSLF_LINE_CONF_*, d_Cl_svu [S][V][U]
-// (zero-filled here; NULL with RSLF_LINE_CONF_OFF, which queues exactly the launches of depth2d_run).  subgrid = 1: every
-// visit in the sub-grid mode (rslf_sweep_subgrid).  d_pk_svu (nullable): the peaks mode's four planes (rslf_sweep_peaks), filled
-// here with idx = runner_idx = -1 and the floats 0.  propagation_ratio > 0: the sweep gated by it (rslf_sweep_propagation_ratio).
-int depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
-                   int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
-                   float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid = 0,
-                   const rslf_peaks* d_pk_svu = nullptr, float propagation_ratio = 0.0f);
+                int dim_d, const rslf_params* p, const SweepPlanes& d_out, rslf_stats* stats, const SweepModes& modes);
 
 // rslf_f2c.hip
 // A volume owned by a scope or an object (rslf_volume_destroy is the one place that frees a slab).
@@ -523,6 +536,57 @@ struct VolumeDeleter {
 };
 struct VolumePtr : std::unique_ptr<rslf_volume, VolumeDeleter> {
     using std::unique_ptr<rslf_volume, VolumeDeleter>::unique_ptr;
+};
+// The element type of a C-ABI entry's RSLF_ELEM_* argument, or the refusal of any other value.
+inline int elem_of(int elem, Elem* out)
+{
+    switch (elem) {
+    case RSLF_ELEM_F32:
+        *out = Elem::F32;
+        return RSLF_OK;
+    case RSLF_ELEM_U8:
+        *out = Elem::U8;
+        return RSLF_OK;
+    case RSLF_ELEM_U16:
+        *out = Elem::U16;
+        return RSLF_OK;
+    }
+    return fail(RSLF_ERR_INVALID_ARG, "element type %d: RSLF_ELEM_F32, _U8 or _U16", elem);
+}
+// What every pyramid entry shares: the host light field and the arguments of FineToCoarse's constructor and run()
+// (rslf_fine_to_coarse.hpp:103-299).
+struct F2cRequest {
+    Elem elem = Elem::F32;
+    const void* const* h_epis = nullptr;
+    int V = 0, S = 0, U = 0, C = 0;
+    size_t row_stride_bytes = 0;
+    float d_min = 0.0f, d_max = 0.0f;
+    int dim_d = 0;
+    float epi_scale_factor = 1.0f;
+    const rslf_params* p = nullptr;
+    int max_pyr_depth = 0;
+    int accept_all_last_scale = 0;
+};
+// What a pyramid is asked for beyond that; the defaults are "off": the reference's pyramid.  A kept run (rslf_f2c_run) holds
+// the one copy of its options; the level loop and the sweep callables read the struct they are handed.
+struct F2cOptions {
+    int line_mode = RSLF_LINE_CONF_OFF;             // every level's sweep mode, and through plan::f2c_validity the plane its validity is read from
+    int validity_rule = RSLF_F2C_VALID_COMPAT;      // RSLF_F2C_VALID_*; anything but COMPAT needs a kept run
+    int subgrid = 0;                                // 1: every level's sweep in the sub-grid mode: the bound tightening, the validity and the fusion receive off-grid disparities
+    bool keep_volumes = false;                      // a kept run keeps every level's normalised volume
+    int peaks = 0;                                  // 1: a kept run's peak planes, of every level and of the fused map (rslf_f2c_run_host_pk) ...
+    float uniqueness = 0.0f;                        // ... > 0: a level's valid pixels whose runner-up is within that ratio of the winner become
+                                                    // invalid (k11_unique_mask) before the next level's bounds and the fusion read the plane
+    float propagation_ratio = 0.0f;                 // > 0: every level's sweep gated by this ratio (rslf_f2c_run_host_pr; needs peaks)
+    float cs_tol = 0.0f;                            // validity by cross-view consistency (rslf_f2c_run_host_cs): with cs_min_agree > 0, after a
+    int cs_radius = 0, cs_min_agree = 0;            // level's rule and uniqueness, a valid pixel the other views contradict becomes invalid
+};
+// The host outputs of a pyramid, each nullable: the fused planes, the depth, every level's planes.
+struct F2cHostOut {
+    float* map_svu = nullptr;
+    uint8_t* valid_svu = nullptr;
+    int* n_levels = nullptr;
+    const rslf_f2c_levels_out* levels = nullptr;
 };
 // One level of FineToCoarse as its sweep sees it, every pointer on the context's device.
 struct F2cLevel {
@@ -534,16 +598,13 @@ struct F2cLevel {
     const float* dmax_svu = nullptr;
     float* Ce_svu = nullptr;            // [S][V][U] results the sweep fills: edge confidence, disparities
     float* depth_svu = nullptr;
-    int line_mode = RSLF_LINE_CONF_OFF; // the mode of the level's sweep and its zero-filled [S][V][U] C_l plane (NULL when off)
-    float* Cl_svu = nullptr;
+    const F2cOptions* options = nullptr;   // the run's: the sweep's modes; a sweep callable that cannot serve one refuses it by this
+    float* Cl_svu = nullptr;            // the zero-filled [S][V][U] C_l plane of the level's sweep (NULL when the line mode is off)
     float* Cd_svu = nullptr;            // a kept run's [S][V][U] disparity confidence; NULL: the sweep has a plane of its own
     VolumePtr* vol_out = nullptr;         // a kept run with volumes: the sweep leaves the volume it ran on here
     const rslf_peaks* peaks = nullptr;    // a kept run with peak planes: the level's four [S][V][U] planes, for the sweep's peaks
-                                          // mode (rslf_sweep_peaks; depth2d_run_lc fills them with -1 / 0 first); NULL: mode off
-    float propagation_ratio = 0.0f;       // ... and the level's sweep gated by this ratio (rslf_sweep_propagation_ratio; 0: off)
+                                          // mode (rslf_sweep_peaks; depth2d_run fills them with -1 / 0 first); NULL: mode off
     unsigned long long* withheld = nullptr;   // where the sweep leaves its count of withheld sources (gated levels only)
-    int consistency_min_agree = 0;        // the run's validity by cross-view consistency is on (the loop applies it; a sweep
-                                          // callable that cannot serve such a run refuses it by this)
 };
 // What the level loop allocates per level and for the fusion.  The loop's own instance frees a level's confidences when the
 // level is done and the rest on return, as it always did; a caller's instance (a kept run, rslf_f2c_run) keeps everything.
@@ -560,40 +621,20 @@ struct F2cKeptLevel {
     unsigned long long inconsistent = 0;   // pixels the gate made invalid (gated levels only)
 };
 struct F2cKept {
-    bool keep_volumes = false;
     std::vector<F2cKeptLevel> levels;   // finest first
     DevBuf fused_map, fused_valid;      // [S][V_0][U_0]
-    // peak planes (rslf_f2c_run_host_pk), set by the owner before the loop runs: every level's sweep in the peaks mode, and
-    // with uniqueness > 0 a level's valid pixels whose runner-up is within that ratio of the winner become invalid
-    // (k11_unique_mask) before the next level's bounds and the fusion read the plane
-    bool peaks = false;
-    float uniqueness = 0.0f;
-    float propagation_ratio = 0.0f;     // every level's sweep gated by this ratio (rslf_f2c_run_host_pr; needs peaks; 0: off)
-    DevBuf fused_pk_idx, fused_pk_score, fused_pk_runner_idx, fused_pk_runner_score, fused_level;   // [S][V_0][U_0] (k11_fuse_peaks)
-    // validity by cross-view consistency (rslf_f2c_run_host_cs), set by the owner: with cs_min_agree > 0, after a level's rule
-    // and uniqueness, a valid pixel the other views contradict (consistency_gate, k13_f2c_consistency_gate) becomes invalid
-    int cs_min_agree = 0, cs_radius = 0;
-    float cs_tol = 0.0f;
+    DevBuf fused_pk_idx, fused_pk_score, fused_pk_runner_idx, fused_pk_runner_score, fused_level;   // [S][V_0][U_0] (k11_fuse_peaks; runs with peaks only)
 };
-// FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from host EPIs of element type elem
-// into host planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which
-// reports the level's stats.  line_mode: every level's sweep mode, and through plan::f2c_validity the plane its validity is
-// read from; levels_out (nullable): host copies of every level's planes.  keep (nullable): the owner of a kept run --
-// nothing is freed, every level also keeps C_d (and its volume, keep->keep_volumes), the validity follows validity_rule
-// (RSLF_F2C_VALID_*; without keep it is COMPAT) and the host planes may be NULL.  keep->peaks / keep->uniqueness: the peak
-// planes of every level and of the fused map, and the validity by uniqueness; off, the loop queues what it always did.
-int fine_to_coarse(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
-                   float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
-                   int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
-                   int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule, F2cKept* keep,
-                   const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep);
-// The loop on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run_lc -- with
-// subgrid = 1 in the sub-grid mode: the bound tightening, the validity and the fusion then receive off-grid disparities.
-int fine_to_coarse_one_context(rslf_ctx* ctx, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
-                               float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
-                               int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
-                               rslf_stats* stats, int line_mode, const rslf_f2c_levels_out* levels_out, int validity_rule,
-                               F2cKept* keep, int subgrid = 0);   // (keep->propagation_ratio: every level's sweep gated)
+// FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from the request's host EPIs into host
+// planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which reports the level's
+// stats.  keep (nullable): the owner of a kept run -- nothing is freed, every level also keeps C_d (and its volume,
+// options.keep_volumes), the validity follows options.validity_rule (without keep it is COMPAT) and the host planes may be
+// NULL.  With every option off, the loop queues what it always did.
+int fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& options, const F2cHostOut& out, rslf_stats* stats,
+                   F2cKept* keep, const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep);
+// The loop on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run.
+int fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& options, const F2cHostOut& out,
+                               rslf_stats* stats, F2cKept* keep);
 
 // rslf_multi.hip
 void multi_free_dev(rslf_multi::Dev& d);
@@ -607,11 +648,7 @@ hipError_t multi_copy(rslf_multi* m, void* dst, int dst_dev, const void* src, in
 struct rslf_f2c_run {
     int device = 0;
     int S = 0, C = 0, elem = RSLF_ELEM_F32;
-    int line_mode = RSLF_LINE_CONF_OFF, validity_rule = RSLF_F2C_VALID_COMPAT;
-    int subgrid = 0;      // every level was swept in the sub-grid mode (rslf_f2c_run_host_sub)
-    int peaks = 0;        // the run holds peak planes (rslf_f2c_run_host_pk)
-    float uniqueness = 0.0f;   // ... and its validity went through the uniqueness ratio (0: off)
-    float propagation_ratio = 0.0f;   // ... and every level's sweep was gated by this ratio (rslf_f2c_run_host_pr; 0: off)
+    rslf::F2cOptions options;   // what the run was made with: the loop read them, the getters do
     rslf_params params;   // as given: the getters' cut_shadows / shadow_level
     rslf::F2cKept kept;
 };

@@ -299,31 +299,26 @@ int multi_depth2d(rslf_multi* m, const void* const* h_epis, Elem elem, size_t ro
 // device, where each level's raw volume, ranges, disparities and confidences live; each level's 2-D sweep -- where the
 // time goes -- runs sharded (multi_depth2d), the devices taking their rows from there and leaving their results there by
 // peer copies (FirstDevicePlanes).  The host sees the EPIs going up once and the fused map coming down.
-static int multi_fine_to_coarse(rslf_multi* m, Elem elem, const void* const* h_epis, int V, int S, int U, int C, size_t row_stride_bytes,
-                                float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
-                                int accept_all_last_scale, float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
-                                rslf_stats* stats)
+static int multi_fine_to_coarse(rslf_multi* m, const F2cRequest& req, const F2cOptions& options, const F2cHostOut& out, rslf_stats* stats)
 {
     if (!m)
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
     rslf_ctx* ctx = m->devs[0].ctx;
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
-        if (lv.peaks)   // (and with them the validity by uniqueness, which reads them)
+        if (lv.options->peaks)   // (and with them the validity by uniqueness, which reads them)
             return fail(RSLF_ERR_INVALID_ARG, "peaks: the pyramid's peak planes and its uniqueness ratio are built for one device");
-        if (lv.consistency_min_agree)
+        if (lv.options->cs_min_agree)
             return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree: the pyramid's validity by cross-view consistency is built for one device");
         const FirstDevicePlanes first{lv.raw_vsuc, lv.dmin_svu, lv.dmax_svu, lv.Ce_svu, lv.depth_svu};
         HIP_TRY(hipStreamSynchronize(ctx->stream));   // what the other devices' streams are about to read is complete
-        int rc = multi_depth2d(m, nullptr, Elem::F32, 0, lv.V, S, lv.U, C, lv.scale, d_min, d_max, dim_d, &lv.params, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, nullptr, level_stats, &first);
+        int rc = multi_depth2d(m, nullptr, Elem::F32, 0, lv.V, req.S, lv.U, req.C, lv.scale, req.d_min, req.d_max, req.dim_d, &lv.params,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, level_stats, &first);
         if (rc)
             return rc;
         HIP_TRY(hipSetDevice(ctx->device));
         return RSLF_OK;
     };
-    return fine_to_coarse(ctx, elem, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
-                          accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats, RSLF_LINE_CONF_OFF, nullptr, RSLF_F2C_VALID_COMPAT,
-                          nullptr, sweep);
+    return fine_to_coarse(ctx, req, options, out, stats, nullptr, sweep);
 }
 
 extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* const* h_epis, int is_u8, int V, int S, int U, int C,
@@ -331,8 +326,9 @@ extern "C" int rslf_multi_fine_to_coarse_run_host(rslf_multi* m, const void* con
                                                   const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
                                                   float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats) RSLF_API_TRY
 {
-    return multi_fine_to_coarse(m, is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats);
+    const F2cRequest req = {is_u8 ? Elem::U8 : Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                            max_pyr_depth, accept_all_last_scale};
+    return multi_fine_to_coarse(m, req, F2cOptions(), {h_out_map_svu, h_out_valid_svu, n_levels, nullptr}, stats);
 }
 RSLF_API_CATCH
 
@@ -342,8 +338,9 @@ extern "C" int rslf_multi_fine_to_coarse_run_host_u16(rslf_multi* m, const uint1
                                                       float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels,
                                                       rslf_stats* stats) RSLF_API_TRY
 {
-    return multi_fine_to_coarse(m, Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d,
-                                epi_scale_factor, p, max_pyr_depth, accept_all_last_scale, h_out_map_svu, h_out_valid_svu, n_levels, stats);
+    const F2cRequest req = {Elem::U16, (const void* const*)h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p,
+                            max_pyr_depth, accept_all_last_scale};
+    return multi_fine_to_coarse(m, req, F2cOptions(), {h_out_map_svu, h_out_valid_svu, n_levels, nullptr}, stats);
 }
 RSLF_API_CATCH
 

@@ -156,15 +156,23 @@ extern "C" int rslf_line_confidence_pile(rslf_ctx* ctx, int V, int S, int U, int
 }
 RSLF_API_CATCH
 
+// A line mode that is none, or one that lacks its plane
+static int line_conf_refusal(int mode, const float* Cl_svu)
+{
+    if (!plan::line_conf_mode_ok(mode))
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", mode);
+    if (mode != RSLF_LINE_CONF_OFF && !Cl_svu)
+        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", mode);
+    return RSLF_OK;
+}
+
 // dc.hpp:721-738, :791-792 and core.hpp:975-979: the planes a sweep with line confidence keeps (include/rslf_hip.h)
 extern "C" int rslf_sweep_line_confidence(rslf_ctx* ctx, const rslf_volume* vol, int mode, float* d_Cl_svu) RSLF_API_TRY
 {
     if (!ctx || !vol)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (!plan::line_conf_mode_ok(mode))
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", mode);
-    if (mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", mode);
+    if (int rc = line_conf_refusal(mode, d_Cl_svu))
+        return rc;
     SweepState& sw = ctx->sweep;
     if (!sw.open || sw.scanned || !sw.first)
         return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_line_confidence belongs between rslf_sweep_begin and the first visit");
@@ -497,51 +505,48 @@ extern "C" int rslf_sweep_end(rslf_ctx* ctx, int ok, int dim_d, rslf_stats* stat
 }
 RSLF_API_CATCH
 
-// What a *_pr entry refuses before it queues anything: a bad ratio, and a ratio without the peaks mode's four planes
-static int entry_gate_check(float ratio, const rslf_peaks* pk)
+// What every entry below refuses before it allocates or queues anything: a bad ratio or a ratio without the peaks mode's four
+// planes, a line mode that is none or lacks its plane, a subgrid that is no flag
+int rslf::check_sweep_modes(const SweepModes& m)
 {
-    return gate_refusal(plan::sweep_gate_entry_args(ratio, pk != nullptr, pk && pk->idx, pk && pk->score, pk && pk->runner_idx,
-                                                    pk && pk->runner_score),
-                        ratio, "the sweep");
+    const rslf_peaks* pk = m.peaks;
+    if (int rc = gate_refusal(plan::sweep_gate_entry_args(m.propagation_ratio, pk != nullptr, pk && pk->idx, pk && pk->score,
+                                                          pk && pk->runner_idx, pk && pk->runner_score),
+                              m.propagation_ratio, "the sweep"))
+        return rc;
+    if (int rc = line_conf_refusal(m.line_mode, m.Cl_svu))
+        return rc;
+    if (m.subgrid != 0 && m.subgrid != 1)
+        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", m.subgrid);
+    return RSLF_OK;
 }
 
-// compute_2D_depth_epi (core.hpp:933-1133) as begin + (scan, finish) per view + end; line_mode / d_Cl_svu: the extra argument
-// a_line_confidence_s_v_u of the -D_USE_LINE_CONFIDENCE_SCORE build (core.hpp:345), RSLF_LINE_CONF_OFF / NULL without it
-static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
-                        float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
-                        float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                        float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu = nullptr, float propagation_ratio = 0.0f)
+static bool all_planes(const SweepPlanes& o) { return o.Ce && o.Ce_mask && o.Cd && o.depth && o.rbar; }
+
+// compute_2D_depth_epi (core.hpp:933-1133) as begin + (scan, finish) per view + end, arguments and modes already checked;
+// modes.line_mode / Cl_svu: the extra argument a_line_confidence_s_v_u of the -D_USE_LINE_CONFIDENCE_SCORE build (core.hpp:345)
+static int sweep_views(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
+                       int dim_d, const SweepPlanes& o, const rslf_params* p, rslf_stats* stats, const SweepModes& m)
 {
-    if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (int rc = entry_gate_check(propagation_ratio, d_pk_svu))   // before anything is queued
-        return rc;
-    if (!plan::line_conf_mode_ok(line_mode))
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
-    if (line_mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
-    if (subgrid != 0 && subgrid != 1)
-        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
     int rc = check_params(p);
     if (rc)
         return rc;
-    rc = rslf_sweep_begin(ctx, vol, d_Ce_mask_svu, d_scan_mask_svu, dim_d, 0, vol->V);
+    rc = rslf_sweep_begin(ctx, vol, o.Ce_mask, o.scan_mask, dim_d, 0, vol->V);
     if (rc)
         return rc;
-    if (line_mode != RSLF_LINE_CONF_OFF)
-        rc = rslf_sweep_line_confidence(ctx, vol, line_mode, d_Cl_svu);
-    if (!rc && subgrid)
+    if (m.line_mode != RSLF_LINE_CONF_OFF)
+        rc = rslf_sweep_line_confidence(ctx, vol, m.line_mode, m.Cl_svu);
+    if (!rc && m.subgrid)
         rc = rslf_sweep_subgrid(ctx, vol, 1);
-    if (!rc && d_pk_svu)
-        rc = rslf_sweep_peaks(ctx, vol, d_pk_svu);
-    if (!rc && propagation_ratio != 0.0f)
-        rc = rslf_sweep_propagation_ratio(ctx, vol, propagation_ratio);
+    if (!rc && m.peaks)
+        rc = rslf_sweep_peaks(ctx, vol, m.peaks);
+    if (!rc && m.propagation_ratio != 0.0f)
+        rc = rslf_sweep_propagation_ratio(ctx, vol, m.propagation_ratio);
     for (int s_hat : plan::sweep_order(vol->S)) {   // core.hpp:981-990
         if (!rc)
-            rc = rslf_sweep_visit_scan(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, s_hat, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu,
-                                       d_depth_svu, d_rbar_svu, p);
+            rc = rslf_sweep_visit_scan(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, s_hat, o.Ce, o.Ce_mask, o.Cd, o.depth, o.rbar, p);
         if (!rc)
-            rc = rslf_sweep_visit_finish(ctx, vol, s_hat, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, p);
+            rc = rslf_sweep_visit_finish(ctx, vol, s_hat, o.Ce_mask, o.Cd, o.depth, o.rbar, p);
         if (rc) {
             const std::string msg = last_error_buffer();
             (void)rslf_sweep_end(ctx, 0, dim_d, nullptr);
@@ -551,13 +556,118 @@ static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dm
     return rslf_sweep_end(ctx, 1, dim_d, stats);
 }
 
+static int depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
+                        float dmax, int dim_d, const SweepPlanes& d_out, const rslf_params* p, rslf_stats* stats, const SweepModes& modes)
+{
+    if (!ctx || !vol || !all_planes(d_out))
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = check_sweep_modes(modes))
+        return rc;
+    return sweep_views(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_out, p, stats, modes);
+}
+
+// Depth2DComputer::run (dc.hpp:748-805) on device planes, arguments and modes already checked
+static int run_planes(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
+                      int dim_d, const rslf_params* p, const SweepPlanes& o, rslf_stats* stats, const SweepModes& m)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = (size_t)vol->S * vol->V * vol->U;
+    hipStream_t st = ctx->stream;
+    // dc.hpp:733-750 (C_e, C_d and C_l are uninitialised there; zero is the intended start)
+    HIP_TRY(hipMemsetAsync(o.Ce, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o.Cd, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o.depth, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o.rbar, 0, n * vol->C * sizeof(float), st));
+    if (m.line_mode != RSLF_LINE_CONF_OFF)
+        HIP_TRY(hipMemsetAsync(m.Cl_svu, 0, n * sizeof(float), st));   // dc.hpp:737
+    if (const rslf_peaks* pk = m.peaks) {   // pixels no visit scans or paints: no index and 0, as rslf_depth_epi_peaks_host leaves unscanned ones
+        if (pk->idx) HIP_TRY(hipMemsetAsync(pk->idx, 0xFF, n * sizeof(int32_t), st));
+        if (pk->runner_idx) HIP_TRY(hipMemsetAsync(pk->runner_idx, 0xFF, n * sizeof(int32_t), st));
+        if (pk->score) HIP_TRY(hipMemsetAsync(pk->score, 0, n * sizeof(float), st));
+        if (pk->runner_score) HIP_TRY(hipMemsetAsync(pk->runner_score, 0, n * sizeof(float), st));
+    }
+    int rc = rslf_edge_confidence_2d(ctx, vol, p, o.Ce, o.Ce_mask);   // dc.hpp:772
+    if (rc)
+        return rc;
+    return sweep_views(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, o, p, stats, m);   // dc.hpp:780
+}
+
+int rslf::depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
+                      int dim_d, const rslf_params* p, const SweepPlanes& d_out, rslf_stats* stats, const SweepModes& modes)
+{
+    if (!ctx || !vol || !all_planes(d_out))
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = check_sweep_modes(modes))
+        return rc;
+    return run_planes(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, p, d_out, stats, modes);
+}
+
+// ... from a volume into host planes (each nullable; h_modes: the host's C_l plane and peak planes)
+static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
+                            const SweepPlanes& h_out, rslf_stats* stats, const SweepModes& h_modes)
+{
+    if (!ctx || !vol)
+        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = check_sweep_modes(h_modes))
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = (size_t)vol->S * vol->V * vol->U;
+    DevBuf Ce, Cd, depth, rbar, mask, Cl;
+    HIP_TRY(Ce.alloc(n * 4));
+    HIP_TRY(Cd.alloc(n * 4));
+    HIP_TRY(depth.alloc(n * 4));
+    HIP_TRY(rbar.alloc(n * 4 * vol->C));
+    HIP_TRY(mask.alloc(n));
+    if (h_modes.line_mode != RSLF_LINE_CONF_OFF)
+        HIP_TRY(Cl.alloc(n * 4));
+    // the peaks mode's planes: a device plane for each one the caller asks for
+    const rslf_peaks* const h_pk = h_modes.peaks;
+    DevBuf pk_buf[4];
+    rslf_peaks d_pk = {};
+    if (h_pk) {
+        if (h_pk->disp)
+            return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_peaks: disp must be NULL (the sub-grid mode puts that value in the depth plane)");
+        const void* want[4] = {h_pk->idx, h_pk->score, h_pk->runner_idx, h_pk->runner_score};
+        for (int i = 0; i < 4; i++)
+            if (want[i])
+                HIP_TRY(pk_buf[i].alloc(n * 4));
+        d_pk.idx = pk_buf[0].as<int32_t>(), d_pk.score = pk_buf[1].as<float>();
+        d_pk.runner_idx = pk_buf[2].as<int32_t>(), d_pk.runner_score = pk_buf[3].as<float>();
+    }
+    SweepModes d_modes = h_modes;   // the same modes on the device's planes
+    d_modes.Cl_svu = Cl.as<float>();
+    d_modes.peaks = h_pk ? &d_pk : nullptr;
+    const SweepPlanes d_out = {Ce.as<float>(), mask.as<uint8_t>(), Cd.as<float>(), depth.as<float>(), rbar.as<float>(), nullptr};
+    int rc = run_planes(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_out, stats, d_modes);
+    if (rc)
+        return rc;
+    hipStream_t st = ctx->stream;
+    if (h_pk) {
+        void* to[4] = {h_pk->idx, h_pk->score, h_pk->runner_idx, h_pk->runner_score};
+        for (int i = 0; i < 4; i++)
+            if (to[i])
+                HIP_TRY(hipMemcpyAsync(to[i], pk_buf[i].get(), n * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (h_out.Ce) HIP_TRY(hipMemcpyAsync(h_out.Ce, Ce.get(), n * 4, hipMemcpyDeviceToHost, st));
+    if (h_out.Ce_mask) HIP_TRY(hipMemcpyAsync(h_out.Ce_mask, mask.get(), n, hipMemcpyDeviceToHost, st));
+    if (h_out.Cd) HIP_TRY(hipMemcpyAsync(h_out.Cd, Cd.get(), n * 4, hipMemcpyDeviceToHost, st));
+    if (h_out.depth) HIP_TRY(hipMemcpyAsync(h_out.depth, depth.get(), n * 4, hipMemcpyDeviceToHost, st));
+    if (h_out.rbar) HIP_TRY(hipMemcpyAsync(h_out.rbar, rbar.get(), n * 4 * vol->C, hipMemcpyDeviceToHost, st));
+    if (h_modes.line_mode != RSLF_LINE_CONF_OFF) HIP_TRY(hipMemcpyAsync(h_modes.Cl_svu, Cl.get(), n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RSLF_OK;
+}
+
+// ---- the C entries: each family's wider entry adds one mode, and with that mode neutral queues exactly the narrower one's
+// launches -- all of a family fill the structs and make the same call ------------------------------------------------------
+
 extern "C" int rslf_depth_epi_2d(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
                                  float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
                                  float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
                                  rslf_stats* stats) RSLF_API_TRY
 {
-    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                        p, d_scan_mask_svu, stats, RSLF_LINE_CONF_OFF, nullptr, 0);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, out, p, stats, SweepModes());
 }
 RSLF_API_CATCH
 
@@ -567,97 +677,60 @@ extern "C" int rslf_depth_epi_2d_lc(rslf_ctx* ctx, const rslf_volume* vol, const
                                     float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
                                     rslf_stats* stats, int line_mode, float* d_Cl_svu) RSLF_API_TRY
 {
-    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, 0);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu;
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, out, p, stats, modes);
 }
 RSLF_API_CATCH
 
-// ... and the sub-grid mode: subgrid = 0 queues exactly rslf_depth_epi_2d_lc's launches
+// ... and the sub-grid mode
 extern "C" int rslf_depth_epi_2d_sub(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
                                      float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
                                      float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
                                      rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid) RSLF_API_TRY
 {
-    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu, modes.subgrid = subgrid;
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, out, p, stats, modes);
 }
 RSLF_API_CATCH
 
-// ... and the peaks mode (rslf_sweep_peaks): d_pk_svu = NULL queues exactly rslf_depth_epi_2d_sub's launches
+// ... and the peaks mode (rslf_sweep_peaks)
 extern "C" int rslf_depth_epi_2d_pk(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
                                     float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
                                     float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
                                     rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu) RSLF_API_TRY
 {
-    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu, modes.subgrid = subgrid, modes.peaks = d_pk_svu;
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, out, p, stats, modes);
 }
 RSLF_API_CATCH
 
-// ... and the gate by peak ratio (rslf_sweep_propagation_ratio): propagation_ratio = 0 queues exactly rslf_depth_epi_2d_pk's launches
+// ... and the gate by peak ratio (rslf_sweep_propagation_ratio)
 extern "C" int rslf_depth_epi_2d_pr(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu,
                                     float dmin, float dmax, int dim_d, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
                                     float* d_depth_svu, float* d_rbar_svu, const rslf_params* p, uint8_t* d_scan_mask_svu,
                                     rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu,
                                     float propagation_ratio) RSLF_API_TRY
 {
-    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                        p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu, propagation_ratio);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu, modes.subgrid = subgrid, modes.peaks = d_pk_svu;
+    modes.propagation_ratio = propagation_ratio;
+    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, out, p, stats, modes);
 }
 RSLF_API_CATCH
-
-int rslf::depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin,
-                         float dmax, int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu,
-                         float* d_depth_svu, float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode,
-                         float* d_Cl_svu, int subgrid, const rslf_peaks* d_pk_svu, float propagation_ratio)
-{
-    if (!ctx || !vol || !d_Ce_svu || !d_Ce_mask_svu || !d_Cd_svu || !d_depth_svu || !d_rbar_svu)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (!plan::line_conf_mode_ok(line_mode))
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
-    if (line_mode != RSLF_LINE_CONF_OFF && !d_Cl_svu)
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
-    if (subgrid != 0 && subgrid != 1)
-        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
-    if (int rc = entry_gate_check(propagation_ratio, d_pk_svu))   // before anything is queued
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = (size_t)vol->S * vol->V * vol->U;
-    hipStream_t st = ctx->stream;
-    // dc.hpp:733-750 (C_e, C_d and C_l are uninitialised there; zero is the intended start)
-    HIP_TRY(hipMemsetAsync(d_Ce_svu, 0, n * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(d_Cd_svu, 0, n * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(d_depth_svu, 0, n * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(d_rbar_svu, 0, n * vol->C * sizeof(float), st));
-    if (line_mode != RSLF_LINE_CONF_OFF)
-        HIP_TRY(hipMemsetAsync(d_Cl_svu, 0, n * sizeof(float), st));   // dc.hpp:737
-    if (d_pk_svu) {   // pixels no visit scans or paints: no index and 0, as rslf_depth_epi_peaks_host leaves unscanned ones
-        if (d_pk_svu->idx) HIP_TRY(hipMemsetAsync(d_pk_svu->idx, 0xFF, n * sizeof(int32_t), st));
-        if (d_pk_svu->runner_idx) HIP_TRY(hipMemsetAsync(d_pk_svu->runner_idx, 0xFF, n * sizeof(int32_t), st));
-        if (d_pk_svu->score) HIP_TRY(hipMemsetAsync(d_pk_svu->score, 0, n * sizeof(float), st));
-        if (d_pk_svu->runner_score) HIP_TRY(hipMemsetAsync(d_pk_svu->runner_score, 0, n * sizeof(float), st));
-    }
-    int rc = rslf_edge_confidence_2d(ctx, vol, p, d_Ce_svu, d_Ce_mask_svu);   // dc.hpp:772
-    if (rc)
-        return rc;
-    return depth_epi_2d(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,   // dc.hpp:780
-                        d_rbar_svu, p, d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu, propagation_ratio);
-}
-
-int rslf::depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, const float* d_dmin_svu, const float* d_dmax_svu, float dmin, float dmax,
-                      int dim_d, const rslf_params* p, float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu,
-                      float* d_rbar_svu, uint8_t* d_scan_mask_svu, rslf_stats* stats)
-{
-    return depth2d_run_lc(ctx, vol, d_dmin_svu, d_dmax_svu, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu,
-                          d_rbar_svu, d_scan_mask_svu, stats, RSLF_LINE_CONF_OFF, nullptr);
-}
 
 extern "C" int rslf_depth2d_run(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                                 float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
                                 uint8_t* d_scan_mask_svu, rslf_stats* stats) RSLF_API_TRY
 {
-    return depth2d_run(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                       d_scan_mask_svu, stats);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    return depth2d_run(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, out, stats, SweepModes());
 }
 RSLF_API_CATCH
 
@@ -666,109 +739,58 @@ extern "C" int rslf_depth2d_run_lc(rslf_ctx* ctx, const rslf_volume* vol, float 
                                    float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
                                    uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu) RSLF_API_TRY
 {
-    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                          d_scan_mask_svu, stats, line_mode, d_Cl_svu);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu;
+    return depth2d_run(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH
 
-// ... and the sub-grid mode of every visit (rslf_sweep_subgrid); subgrid = 0 queues exactly rslf_depth2d_run_lc's launches
+// ... and the sub-grid mode of every visit (rslf_sweep_subgrid)
 extern "C" int rslf_depth2d_run_sub(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                                     float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
                                     uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid) RSLF_API_TRY
 {
-    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                          d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu, modes.subgrid = subgrid;
+    return depth2d_run(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH
 
-// ... and the peaks mode of every visit (rslf_sweep_peaks); d_pk_svu = NULL queues exactly rslf_depth2d_run_sub's launches
+// ... and the peaks mode of every visit (rslf_sweep_peaks)
 extern "C" int rslf_depth2d_run_pk(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                                    float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
                                    uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid,
                                    const rslf_peaks* d_pk_svu) RSLF_API_TRY
 {
-    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                          d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu, modes.subgrid = subgrid, modes.peaks = d_pk_svu;
+    return depth2d_run(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH
 
-// ... and the gate by peak ratio; propagation_ratio = 0 queues exactly rslf_depth2d_run_pk's launches
+// ... and the gate by peak ratio
 extern "C" int rslf_depth2d_run_pr(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                                    float* d_Ce_svu, uint8_t* d_Ce_mask_svu, float* d_Cd_svu, float* d_depth_svu, float* d_rbar_svu,
                                    uint8_t* d_scan_mask_svu, rslf_stats* stats, int line_mode, float* d_Cl_svu, int subgrid,
                                    const rslf_peaks* d_pk_svu, float propagation_ratio) RSLF_API_TRY
 {
-    return depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu,
-                          d_scan_mask_svu, stats, line_mode, d_Cl_svu, subgrid, d_pk_svu, propagation_ratio);
+    const SweepPlanes out = {d_Ce_svu, d_Ce_mask_svu, d_Cd_svu, d_depth_svu, d_rbar_svu, d_scan_mask_svu};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = d_Cl_svu, modes.subgrid = subgrid, modes.peaks = d_pk_svu;
+    modes.propagation_ratio = propagation_ratio;
+    return depth2d_run(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH
-
-static int depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
-                            float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu, float* h_rbar_svu,
-                            rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid, const rslf_peaks* h_pk_svu = nullptr,
-                            float propagation_ratio = 0.0f)
-{
-    if (!ctx || !vol)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (int rc = entry_gate_check(propagation_ratio, h_pk_svu))   // before anything is allocated or queued
-        return rc;
-    if (subgrid != 0 && subgrid != 1)
-        return fail(RSLF_ERR_INVALID_ARG, "subgrid=%d: 0 or 1", subgrid);
-    if (!plan::line_conf_mode_ok(line_mode))
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", line_mode);
-    if (line_mode != RSLF_LINE_CONF_OFF && !h_Cl_svu)
-        return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d needs the [S][V][U] plane", line_mode);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = (size_t)vol->S * vol->V * vol->U;
-    DevBuf Ce, Cd, depth, rbar, mask, Cl;
-    HIP_TRY(Ce.alloc(n * 4));
-    HIP_TRY(Cd.alloc(n * 4));
-    HIP_TRY(depth.alloc(n * 4));
-    HIP_TRY(rbar.alloc(n * 4 * vol->C));
-    HIP_TRY(mask.alloc(n));
-    if (line_mode != RSLF_LINE_CONF_OFF)
-        HIP_TRY(Cl.alloc(n * 4));
-    // the peaks mode's planes: a device plane for each one the caller asks for
-    DevBuf pk_buf[4];
-    rslf_peaks d_pk = {};
-    if (h_pk_svu) {
-        if (h_pk_svu->disp)
-            return fail(RSLF_ERR_INVALID_ARG, "rslf_sweep_peaks: disp must be NULL (the sub-grid mode puts that value in the depth plane)");
-        const void* want[4] = {h_pk_svu->idx, h_pk_svu->score, h_pk_svu->runner_idx, h_pk_svu->runner_score};
-        for (int i = 0; i < 4; i++)
-            if (want[i])
-                HIP_TRY(pk_buf[i].alloc(n * 4));
-        d_pk.idx = pk_buf[0].as<int32_t>(), d_pk.score = pk_buf[1].as<float>();
-        d_pk.runner_idx = pk_buf[2].as<int32_t>(), d_pk.runner_score = pk_buf[3].as<float>();
-    }
-    int rc = depth2d_run_lc(ctx, vol, nullptr, nullptr, dmin, dmax, dim_d, p, Ce.as<float>(), mask.as<uint8_t>(), Cd.as<float>(),
-                            depth.as<float>(), rbar.as<float>(), nullptr, stats, line_mode, Cl.as<float>(), subgrid,
-                            h_pk_svu ? &d_pk : nullptr, propagation_ratio);
-    if (rc)
-        return rc;
-    hipStream_t st = ctx->stream;
-    if (h_pk_svu) {
-        void* to[4] = {h_pk_svu->idx, h_pk_svu->score, h_pk_svu->runner_idx, h_pk_svu->runner_score};
-        for (int i = 0; i < 4; i++)
-            if (to[i])
-                HIP_TRY(hipMemcpyAsync(to[i], pk_buf[i].get(), n * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (h_Ce_svu) HIP_TRY(hipMemcpyAsync(h_Ce_svu, Ce.get(), n * 4, hipMemcpyDeviceToHost, st));
-    if (h_Ce_mask_svu) HIP_TRY(hipMemcpyAsync(h_Ce_mask_svu, mask.get(), n, hipMemcpyDeviceToHost, st));
-    if (h_Cd_svu) HIP_TRY(hipMemcpyAsync(h_Cd_svu, Cd.get(), n * 4, hipMemcpyDeviceToHost, st));
-    if (h_depth_svu) HIP_TRY(hipMemcpyAsync(h_depth_svu, depth.get(), n * 4, hipMemcpyDeviceToHost, st));
-    if (h_rbar_svu) HIP_TRY(hipMemcpyAsync(h_rbar_svu, rbar.get(), n * 4 * vol->C, hipMemcpyDeviceToHost, st));
-    if (line_mode != RSLF_LINE_CONF_OFF) HIP_TRY(hipMemcpyAsync(h_Cl_svu, Cl.get(), n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RSLF_OK;
-}
 
 extern "C" int rslf_depth2d_run_host(rslf_ctx* ctx, const rslf_volume* vol, float dmin, float dmax, int dim_d, const rslf_params* p,
                                      float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
                                      float* h_rbar_svu, rslf_stats* stats) RSLF_API_TRY
 {
-    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
-                            RSLF_LINE_CONF_OFF, nullptr, 0);
+    const SweepPlanes out = {h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, nullptr};
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, out, stats, SweepModes());
 }
 RSLF_API_CATCH
 
@@ -776,8 +798,10 @@ extern "C" int rslf_depth2d_run_host_lc(rslf_ctx* ctx, const rslf_volume* vol, f
                                         float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
                                         float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu) RSLF_API_TRY
 {
-    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
-                            line_mode, h_Cl_svu, 0);
+    const SweepPlanes out = {h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, nullptr};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = h_Cl_svu;
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH
 
@@ -785,8 +809,10 @@ extern "C" int rslf_depth2d_run_host_sub(rslf_ctx* ctx, const rslf_volume* vol, 
                                          float* h_Ce_svu, uint8_t* h_Ce_mask_svu, float* h_Cd_svu, float* h_depth_svu,
                                          float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid) RSLF_API_TRY
 {
-    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
-                            line_mode, h_Cl_svu, subgrid);
+    const SweepPlanes out = {h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, nullptr};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = h_Cl_svu, modes.subgrid = subgrid;
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH
 
@@ -795,8 +821,10 @@ extern "C" int rslf_depth2d_run_host_pk(rslf_ctx* ctx, const rslf_volume* vol, f
                                         float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid,
                                         const rslf_peaks* h_pk_svu) RSLF_API_TRY
 {
-    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
-                            line_mode, h_Cl_svu, subgrid, h_pk_svu);
+    const SweepPlanes out = {h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, nullptr};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = h_Cl_svu, modes.subgrid = subgrid, modes.peaks = h_pk_svu;
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH
 
@@ -805,7 +833,10 @@ extern "C" int rslf_depth2d_run_host_pr(rslf_ctx* ctx, const rslf_volume* vol, f
                                         float* h_rbar_svu, rslf_stats* stats, int line_mode, float* h_Cl_svu, int subgrid,
                                         const rslf_peaks* h_pk_svu, float propagation_ratio) RSLF_API_TRY
 {
-    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, stats,
-                            line_mode, h_Cl_svu, subgrid, h_pk_svu, propagation_ratio);
+    const SweepPlanes out = {h_Ce_svu, h_Ce_mask_svu, h_Cd_svu, h_depth_svu, h_rbar_svu, nullptr};
+    SweepModes modes;
+    modes.line_mode = line_mode, modes.Cl_svu = h_Cl_svu, modes.subgrid = subgrid, modes.peaks = h_pk_svu;
+    modes.propagation_ratio = propagation_ratio;
+    return depth2d_run_host(ctx, vol, dmin, dmax, dim_d, p, out, stats, modes);
 }
 RSLF_API_CATCH

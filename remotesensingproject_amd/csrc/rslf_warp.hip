@@ -243,7 +243,7 @@ static int f2c_run_view_warp(const rslf_f2c_run* run, rslf_ctx* ctx, int level, 
     const float* depth = fused_result ? run->kept.fused_map.as<const float>() : kl.depth.as<const float>();
     const uint8_t* valid = fused_result ? run->kept.fused_valid.as<const uint8_t>() : kl.valid.as<const uint8_t>();
     const rslf_view_warp_out& o = out ? *out : kNoPlanes;
-    const rslf_volume* vol = run->kept.keep_volumes ? kl.vol.get() : nullptr;
+    const rslf_volume* vol = run->options.keep_volumes ? kl.vol.get() : nullptr;
     if (!vol && (o.colour || o.err || o.row_err))
         return fail(RSLF_ERR_INVALID_ARG, "colour, err and row_err read the level's volume: the run was made without keep_volumes");
     int rc = check_warp_args(depth, valid, run->S, kl.V, kl.U, vol, targets, T, nearer, o);

@@ -1129,20 +1129,10 @@ def compute_2D_depth_epi(vol: Volume, a_dmin_s_v_u, a_dmax_s_v_u, a_dim_d: int, 
             _ptr(a_best_depth_s_v_u), _ptr(a_rbar_s_v_u), C.byref(p), _ptr(scan_mask_s_v_u),
             C.byref(st) if st is not None else None)
     mode = int(par.par_line_confidence_mode)
-    if peaks is not None:
-        c_pk = _sweep_peak_planes(peaks, vol.S, vol.V, vol.U)
-        if ratio:
-            check(_lib.lib().rslf_depth_epi_2d_pr(*args, mode, _ptr(a_line_confidence_s_v_u), 1 if subgrid else 0, C.byref(c_pk), ratio),
-                  "rslf_depth_epi_2d_pr")
-        else:
-            check(_lib.lib().rslf_depth_epi_2d_pk(*args, mode, _ptr(a_line_confidence_s_v_u), 1 if subgrid else 0, C.byref(c_pk)),
-                  "rslf_depth_epi_2d_pk")
-    elif subgrid:
-        check(_lib.lib().rslf_depth_epi_2d_sub(*args, mode, _ptr(a_line_confidence_s_v_u), 1), "rslf_depth_epi_2d_sub")
-    elif a_line_confidence_s_v_u is None and mode == LINE_CONF_OFF:
-        check(_lib.lib().rslf_depth_epi_2d(*args), "rslf_depth_epi_2d")
-    else:
-        check(_lib.lib().rslf_depth_epi_2d_lc(*args, mode, _ptr(a_line_confidence_s_v_u)), "rslf_depth_epi_2d_lc")
+    c_pk = None if peaks is None else C.byref(_sweep_peak_planes(peaks, vol.S, vol.V, vol.U))
+    # the family's widest entry: a mode that is off goes in neutral, and the call is the narrower entry's
+    check(_lib.lib().rslf_depth_epi_2d_pr(*args, mode, _ptr(a_line_confidence_s_v_u), 1 if subgrid else 0, c_pk, ratio),
+          "rslf_depth_epi_2d_pr")
     return st
 
 
@@ -1376,25 +1366,17 @@ class Depth2DComputer:
         mode = self._line_mode()
         if mode != LINE_CONF_OFF and self.m_line_confidence_s_v_u is None:   # the mode was set after the constructor ran
             self.m_line_confidence_s_v_u = torch.empty_like(self.m_edge_confidence_s_v_u)
+        c_pk, ratio = None, 0.0
         if self.m_peaks:
             shape, dev = tuple(self.m_edge_confidence_s_v_u.shape), vol.ctx.device
             self.m_peaks_s_v_u = Peaks(torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev),
                                        None, torch.empty(shape, dtype=torch.int32, device=dev),
                                        torch.empty(shape, dtype=torch.float32, device=dev))
-            c_pk = _sweep_peak_planes(self.m_peaks_s_v_u, *shape)
-            if self.m_propagation_ratio:
-                check(_lib.lib().rslf_depth2d_run_pr(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1 if self.m_subgrid else 0,
-                                                     C.byref(c_pk), self.m_propagation_ratio), "rslf_depth2d_run_pr")
-            else:
-                check(_lib.lib().rslf_depth2d_run_pk(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1 if self.m_subgrid else 0,
-                                                     C.byref(c_pk)), "rslf_depth2d_run_pk")
+            c_pk, ratio = C.byref(_sweep_peak_planes(self.m_peaks_s_v_u, *shape)), self.m_propagation_ratio
             self.m_withheld = None   # read on demand: the count waits for the stream
-        elif self.m_subgrid:
-            check(_lib.lib().rslf_depth2d_run_sub(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1), "rslf_depth2d_run_sub")
-        elif mode == LINE_CONF_OFF:
-            check(_lib.lib().rslf_depth2d_run(*args), "rslf_depth2d_run")
-        else:
-            check(_lib.lib().rslf_depth2d_run_lc(*args, mode, _ptr(self.m_line_confidence_s_v_u)), "rslf_depth2d_run_lc")
+        # the family's widest entry: a mode that is off goes in neutral, and the call is the narrower entry's
+        check(_lib.lib().rslf_depth2d_run_pr(*args, mode, _ptr(self.m_line_confidence_s_v_u), 1 if self.m_subgrid else 0, c_pk, ratio),
+              "rslf_depth2d_run_pr")
         self.stats = st
 
     def _line_gates(self) -> bool:
@@ -2092,17 +2074,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
         args = (ctx._h, ptrs, _ELEM[np.dtype(dt)], V, S, U, C_, stride, float(d_min), float(d_max), int(dim_d),
                 float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
                 int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
-        if want_cs:
-            check(L.rslf_f2c_run_host_cs(*args, 1 if subgrid else 0, 1 if want_peaks else 0, float(uniqueness_ratio or 0.0), gate,
-                                         cs_tol, cs_radius, cs_min_agree), "rslf_f2c_run_host_cs")
-        elif want_peaks and gate:
-            check(L.rslf_f2c_run_host_pr(*args, 1 if subgrid else 0, 1, float(uniqueness_ratio or 0.0), gate), "rslf_f2c_run_host_pr")
-        elif want_peaks:
-            check(L.rslf_f2c_run_host_pk(*args, 1 if subgrid else 0, 1, float(uniqueness_ratio or 0.0)), "rslf_f2c_run_host_pk")
-        elif subgrid:
-            check(L.rslf_f2c_run_host_sub(*args, 1), "rslf_f2c_run_host_sub")
-        else:
-            check(L.rslf_f2c_run_host(*args), "rslf_f2c_run_host")
+        # the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's
+        check(L.rslf_f2c_run_host_cs(*args, 1 if subgrid else 0, 1 if want_peaks else 0, float(uniqueness_ratio or 0.0), gate,
+                                     cs_tol, cs_radius, cs_min_agree), "rslf_f2c_run_host_cs")
         return KeptFineToCoarse(h, ctx, st, (float(d_min), float(d_max), int(dim_d)))
     if validity_rule != F2C_VALID_COMPAT:
         raise ValueError("fine_to_coarse_run_host: validity_rule needs keep=True")
@@ -2126,12 +2100,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
             1 if accept_all_last_scale else 0, out_map.ctypes.data_as(C.c_void_p), out_valid.ctypes.data_as(C.c_void_p),
             C.byref(nl), C.byref(st), int(line_mode), C.byref(lo) if lo is not None else None)
     ctx.use_current_stream()
-    if subgrid:
-        check(L.rslf_fine_to_coarse_run_host_sub(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1), "rslf_fine_to_coarse_run_host_sub")
-    elif dt == np.uint16:
-        check(L.rslf_fine_to_coarse_run_host_u16_lc(ctx._h, ptrs, *rest), "rslf_fine_to_coarse_run_host_u16_lc")
-    else:
-        check(L.rslf_fine_to_coarse_run_host_lc(ctx._h, ptrs, 1 if dt == np.uint8 else 0, *rest), "rslf_fine_to_coarse_run_host_lc")
+    # the family's widest entry, which takes any element type
+    check(L.rslf_fine_to_coarse_run_host_sub(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0),
+          "rslf_fine_to_coarse_run_host_sub")
     out = dict(out_map=out_map, out_valid=out_valid, n_levels=int(nl.value), stats=st)
     if want_levels:
         out["levels"] = levels
