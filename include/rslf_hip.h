@@ -1120,6 +1120,69 @@ int rslf_f2c_run_view_warp(const rslf_f2c_run* run, rslf_ctx* ctx, int level, in
 int rslf_f2c_run_view_warp_host(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets,
                                 const int* exclude, int T, int radius, int nearer, const rslf_view_warp_out* h_out);
 
+/* ---- the novel view: the warp's holes filled, the views that see a point blended (K15) -------- */
+/* Not in the reference.  The warp above stops at one source pixel per target pixel, or nothing.  This is the second half of
+ * depth-image-based rendering: a finished image of view position t.  Per target and scanline, three stages; the rule is
+ * stated once, in csrc/k15_novel_rule.hpp.
+ *   A  z-buffer   the warp's rule unchanged (exclude, params->radius, params->nearer): per column a hit and the winner's
+ *                 stored disparity, its own bits.
+ *   B  fill       a RUN is a maximal stretch of columns without a hit, n columns long, with the column before it as its
+ *                 left bound (none at the row's start) and the column after it as its right bound (none at the row's end).
+ *                 It stays a hole with no bound at all, or when max_gap > 0 && n > max_gap.  Otherwise every column of it
+ *                 takes the disparity of one bound: the only one, or of two the FARTHER (the smaller z; a disocclusion
+ *                 belongs to the background), the left one on equal z.
+ *   C  gather     for a pixel x that is not a hole, of disparity d, the views are walked by (distance to t, s); the walk
+ *                 stops at the first view outside the radius and skips `exclude`.  For view s
+ *                     off = fl(fl(d * fl((float)s - t)) * slope)     out of field unless fabsf(off) < 1e9f
+ *                     p = (float)x - off,  ur = (int)roundf(p)       out of field unless ur in [0, U)
+ *                 and the view AGREES when depth[s][v][ur] is ok and fabsf(depth[s][v][ur] - d) <= tol.  Its sample is
+ *                     i0 = floorf(p), i1 = ceilf(p), w = p - (float)i0, both taps clamped into [0, U - 1]
+ *                     sample[c] = (1 - w) * E[i0][c] + w * E[i1][c]    (two products, one sum, no FMA)
+ *                 An agreeing view joins the blend with weight g = 1.0f / (1.0f + fabsf((float)s - t)), in walk order:
+ *                 acc[c] = acc[c] + g * sample[c], wsum = wsum + g; the walk ends after `sources` agreeing views.
+ * Outputs per target k of the T targets, each nullable, not all seven; only the planes asked for are written:
+ *   colour   f32 [T][V][U][C]  acc[c] / wsum where n_src > 0; where nobody agreed the sample of the FIRST view of the walk
+ *                              that was in field, unverified; 0 if none was, and 0 at a hole
+ *   depth    f32 [T][V][U]     the winner's stored disparity at hits, the bound's bits at filled pixels, 0 at holes
+ *   fill     u8  [T][V][U]     0 hole, 1 hit, 2 filled from the left bound, 3 filled from the right bound
+ *   n_src    i32 [T][V][U]     the views blended
+ *   err      f32 [T][V][U]     the residual of colour against the slab's own row (v, t), as rslf_view_warp's, wherever a
+ *                              colour was taken from a view; else 0
+ *   row_err  f64 [T][V]        the sum of err over a row's pixels with n_src > 0, in double, in an order left open
+ *   row_cov  i32 [T][V]        their number
+ * colour, err and row_err need `volume`; depth, fill, n_src and row_cov do not.  err and row_err need every target to be a
+ * view.  RSLF_ERR_INVALID_ARG as rslf_view_warp, and: params NULL, sources < 1, tol negative or a NaN (+inf accepts every ok
+ * pixel), nearer == 0, no output, an output plane that is an input plane.  RSLF_ERR_UNSUPPORTED as rslf_view_warp (U above
+ * 8192, S above 65536, the grid).  One launch per 256 targets, enqueued on the context's stream, not awaited; no scratch. */
+typedef struct rslf_novel_view_params {
+    int radius, nearer, max_gap, sources;
+    float tol;
+} rslf_novel_view_params;
+typedef struct rslf_novel_view_out {
+    float* colour;
+    float* depth;
+    uint8_t* fill;
+    int32_t* n_src;
+    float* err;
+    double* row_err;
+    int32_t* row_cov;
+} rslf_novel_view_out;
+int rslf_novel_view(rslf_ctx* ctx, const float* d_depth_svu, const uint8_t* d_valid_svu, int S, int V, int U, float slope,
+                    const rslf_volume* volume, const float* targets, const int* exclude, int T, const rslf_novel_view_params* params,
+                    const rslf_novel_view_out* d_out);
+/* The same with the planes on the HOST (the volume stays a device object): staged through the context's buffers, awaited.
+ * Refused while a sweep is open on the context. */
+int rslf_novel_view_host(rslf_ctx* ctx, const float* h_depth_svu, const uint8_t* h_valid_svu, int S, int V, int U, float slope,
+                         const rslf_volume* volume, const float* targets, const int* exclude, int T, const rslf_novel_view_params* params,
+                         const rslf_novel_view_out* h_out);
+/* The same on a kept fine-to-coarse run's planes, read in place, as rslf_f2c_run_view_warp reads them.  A run made without
+ * keep_volumes refuses colour, err and row_err by name. */
+int rslf_f2c_run_novel_view(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets, const int* exclude,
+                            int T, const rslf_novel_view_params* params, const rslf_novel_view_out* d_out);
+/* ... and with the result planes on the HOST: staged, copied out, awaited.  Refused while a sweep is open on the context. */
+int rslf_f2c_run_novel_view_host(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets,
+                                 const int* exclude, int T, const rslf_novel_view_params* params, const rslf_novel_view_out* h_out);
+
 /* Depth2DComputer<T>'s constructor + run() + getters (rslf_depth_computation.hpp:651-805) over the context's devices,
  * host EPIs in, host [S][V][U] planes out.  The 2-D sweep is cut into one block of scanlines per device; every visit
  * exchanges the neighbours' boundary rows (median reach) of the visited view's raw disparities and edge mask by peer

@@ -312,7 +312,35 @@ struct ViewPrediction {
     std::vector<double> mean_abs_error, coverage;
 };
 
+// Not in the reference: the planes of the novel view (rslf_novel_view, rslf_hip.h) of one target, [V][U] each (colour
+// [V][U][C]) -- fill 0 hole / 1 hit / 2, 3 filled from the left / right bound; depth the disparity of every target pixel (0 at
+// holes); n_src the views blended; colour the finished image (empty when not asked for).
+struct NovelView {
+    std::vector<float> colour, depth;
+    std::vector<uint8_t> fill;
+    std::vector<int32_t> n_src;
+};
+// What a novel view is made with: radius, nearer as the warp's; max_gap > 0: runs of more columns stay holes; sources: the
+// views blended at most; tol < 0: one step of the hypothesis grid.
+struct NovelViewOptions {
+    int radius = 0, nearer = 1, max_gap = 0, sources = 4;
+    float tol = -1.f;
+};
+
 namespace detail {
+inline rslf_novel_view_out novel_planes(NovelView& w, size_t n, int channels, bool colour)
+{
+    w.depth.resize(n), w.fill.resize(n), w.n_src.resize(n);
+    if (colour)
+        w.colour.resize(n * (size_t)channels);
+    const rslf_novel_view_out out = {colour ? w.colour.data() : nullptr, w.depth.data(), w.fill.data(), w.n_src.data(), nullptr, nullptr, nullptr};
+    return out;
+}
+inline rslf_novel_view_params novel_params(const NovelViewOptions& o, float step)
+{
+    const rslf_novel_view_params p = {o.radius, o.nearer, o.max_gap, o.sources, o.tol < 0.f ? step : o.tol};
+    return p;
+}
 inline rslf_view_warp_out warp_planes(Warp& w, size_t n, int channels, bool colour)
 {
     w.hit.resize(n), w.depth.resize(n), w.src_view.resize(n), w.src_col.resize(n), w.count.resize(n);
@@ -912,6 +940,33 @@ public:
     {
         return get_view_prediction(detail::own(ctx_), views, radius, nearer, mask);
     }
+    // Not in the reference: after run(), the view at position `target` as a finished image (rslf_novel_view_host, rslf_hip.h):
+    // the warp's z-buffer, its holes filled from the farther bound, and every pixel's colour gathered backwards from the views
+    // that agree with its disparity, blended at sub-pixel columns.  mask as get_warped_view's.  An object built on a
+    // MultiContext takes the Context to run on and holds no volume: it gives depth, fill and n_src only (colour = false).
+    NovelView get_novel_view(Context& on, float target, int exclude = -1, const NovelViewOptions& options = NovelViewOptions(),
+                             const uint8_t* mask = nullptr, bool colour = true) const
+    {
+        detail::require(!m_best_depth_s_v_u.empty(), "the getters show the results of run(): call it first");
+        detail::require(!colour || vol_ != nullptr, "get_novel_view: colour reads the volume, which an object built on a MultiContext does not hold");
+        std::vector<uint8_t> own_mask;
+        if (!mask) {
+            own_mask = get_valid_depths_mask_s_v_u();
+            mask = own_mask.data();
+        }
+        NovelView out;
+        const rslf_novel_view_out planes = detail::novel_planes(out, (size_t)dim_v_ * dim_u_, CHANNELS, colour);
+        const rslf_novel_view_params params = detail::novel_params(options, options.tol < 0.f ? detail::grid_step(m_dmin, m_dmax, m_dim_d) : 0.f);
+        check(rslf_novel_view_host(on.get(), m_best_depth_s_v_u.data(), mask, dim_s_, dim_v_, dim_u_, m_parameters.par_slope_factor,
+                                   colour ? vol_ : nullptr, &target, &exclude, 1, &params, &planes),
+              "rslf_novel_view_host");
+        return out;
+    }
+    NovelView get_novel_view(float target, int exclude = -1, const NovelViewOptions& options = NovelViewOptions(), const uint8_t* mask = nullptr,
+                             bool colour = true) const
+    {
+        return get_novel_view(detail::own(ctx_), target, exclude, options, mask, colour);
+    }
 
     // dc.hpp:808-856: the S x U slice of the disparities at scanline a_v (< 0: floor(V / 2.0)) over its own min / max,
     // colour-mapped, black outside the mask; no line drawing -> [S][U][3].  The slice is read through its row stride.
@@ -1207,6 +1262,25 @@ public:
                          bool colour = true) const
     {
         return get_warped_view(detail::own(ctx_), target, level, fused_result, exclude, radius, nearer, colour);
+    }
+    // ... and the novel view of a kept plane pair (rslf_f2c_run_novel_view_host): a finished image of `target`, with the
+    // level's kept volume -- a run kept without its volumes refuses colour.  -> planes [V_level][U_level].
+    NovelView get_novel_view(Context& on, float target, int level = 0, bool fused_result = true, int exclude = -1,
+                             const NovelViewOptions& options = NovelViewOptions(), bool colour = true) const
+    {
+        detail::require(run_ != nullptr, "get_novel_view reads a kept run's planes on the device: call keep_on_device before run()");
+        detail::require(level >= 0 && level < (int)dims_.size(), "get_novel_view: the level is not in the pyramid");
+        NovelView out;
+        const rslf_novel_view_out planes = detail::novel_planes(out, (size_t)dims_[level].first * dims_[level].second, CHANNELS, colour);
+        const rslf_novel_view_params params = detail::novel_params(options, options.tol < 0.f ? detail::grid_step(d_min_, d_max_, dim_d_) : 0.f);
+        check(rslf_f2c_run_novel_view_host(run_, on.get(), level, fused_result ? 1 : 0, &target, &exclude, 1, &params, &planes),
+              "rslf_f2c_run_novel_view_host");
+        return out;
+    }
+    NovelView get_novel_view(float target, int level = 0, bool fused_result = true, int exclude = -1,
+                             const NovelViewOptions& options = NovelViewOptions(), bool colour = true) const
+    {
+        return get_novel_view(detail::own(ctx_), target, level, fused_result, exclude, options, colour);
     }
     ViewPrediction get_view_prediction(Context& on, int level = 0, bool fused_result = true, std::vector<int> views = std::vector<int>(),
                                        int radius = 0, int nearer = 1) const

@@ -69,6 +69,8 @@ SYMBOLS = [
     "rslf_f2c_run_host_cs", "rslf_f2c_run_consistency_gate", "rslf_f2c_run_inconsistent", "rslf_f2c_consistency_mask",
     # the view warp: any view position from a sweep's planes, z-buffered (K14)
     "rslf_view_warp", "rslf_view_warp_host", "rslf_f2c_run_view_warp", "rslf_f2c_run_view_warp_host",
+    # the novel view: the warp's holes filled, the views that see a point blended (K15)
+    "rslf_novel_view", "rslf_novel_view_host", "rslf_f2c_run_novel_view", "rslf_f2c_run_novel_view_host",
 ]
 
 
@@ -135,6 +137,19 @@ class RslfViewWarpOut(C.Structure):
 
     _fields_ = [("hit", C.c_void_p), ("depth", C.c_void_p), ("src_view", C.c_void_p), ("src_col", C.c_void_p), ("count", C.c_void_p),
                 ("colour", C.c_void_p), ("err", C.c_void_p), ("row_err", C.c_void_p), ("row_hits", C.c_void_p)]
+
+
+class RslfNovelViewParams(C.Structure):
+    """rslf_novel_view_params."""
+
+    _fields_ = [("radius", C.c_int), ("nearer", C.c_int), ("max_gap", C.c_int), ("sources", C.c_int), ("tol", C.c_float)]
+
+
+class RslfNovelViewOut(C.Structure):
+    """rslf_novel_view_out: the seven planes of the novel view, device or host pointers, each nullable."""
+
+    _fields_ = [("colour", C.c_void_p), ("depth", C.c_void_p), ("fill", C.c_void_p), ("n_src", C.c_void_p), ("err", C.c_void_p),
+                ("row_err", C.c_void_p), ("row_cov", C.c_void_p)]
 
 
 class RslfF2cLevelsOut(C.Structure):
@@ -351,6 +366,12 @@ def lib():
     L.rslf_view_warp_host.argtypes = L.rslf_view_warp.argtypes
     L.rslf_f2c_run_view_warp.argtypes = [vp, vp, ci, ci, C.POINTER(cf), C.POINTER(ci), ci, ci, ci, C.POINTER(RslfViewWarpOut)]
     L.rslf_f2c_run_view_warp_host.argtypes = L.rslf_f2c_run_view_warp.argtypes
+    L.rslf_novel_view.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp, C.POINTER(cf), C.POINTER(ci), ci, C.POINTER(RslfNovelViewParams),
+                                  C.POINTER(RslfNovelViewOut)]
+    L.rslf_novel_view_host.argtypes = L.rslf_novel_view.argtypes
+    L.rslf_f2c_run_novel_view.argtypes = [vp, vp, ci, ci, C.POINTER(cf), C.POINTER(ci), ci, C.POINTER(RslfNovelViewParams),
+                                          C.POINTER(RslfNovelViewOut)]
+    L.rslf_f2c_run_novel_view_host.argtypes = L.rslf_f2c_run_novel_view.argtypes
     L.rslf_f2c_run_peaks.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.restype = cf

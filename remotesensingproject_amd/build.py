@@ -42,6 +42,8 @@ UNITS = {
     "rslf_consistency.hip": ["k12_consistency.hpp", "k12_consistency_rule.hpp", "rslf_plan_consistency.hpp", "k13_f2c_consistency.hpp",
                              "rslf_plan_f2c_consistency.hpp"],
     "rslf_warp.hip": ["k14_view_warp.hpp", "k14_warp_rule.hpp", "rslf_plan_warp.hpp", "k12_consistency_rule.hpp"],
+    "rslf_novel.hip": ["k15_novel_view.hpp", "k15_novel_rule.hpp", "rslf_plan_novel.hpp", "k14_warp_rule.hpp", "rslf_plan_warp.hpp",
+                       "k12_consistency_rule.hpp"],
     "rslf_multi.hip": [],
     "rslf_multi_sweep.hip": [],
 }

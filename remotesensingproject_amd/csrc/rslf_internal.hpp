@@ -17,6 +17,7 @@
 //   rslf_consistency.hip  cross-view consistency of a sweep's disparity planes: counts, fused value, validity (k12_consistency.hpp),
 //                         and its gate form for a kept fine-to-coarse run's levels (k13_f2c_consistency.hpp)
 //   rslf_warp.hip         the view warp: any view position from a sweep's planes, z-buffered (k14_view_warp.hpp)
+//   rslf_novel.hip        the novel view: the warp's holes filled, the views that see a point blended (k15_novel_view.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)

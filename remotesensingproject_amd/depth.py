@@ -1028,6 +1028,12 @@ class MultiDevice:
     def get_view_prediction(self, *args, **kwargs):
         no_view_warp("MultiDevice", "get_view_prediction")
 
+    def get_novel_views(self, *args, **kwargs):
+        no_novel_view("MultiDevice")
+
+    def get_novel_view_prediction(self, *args, **kwargs):
+        no_novel_view("MultiDevice", "get_novel_view_prediction")
+
     def depth1d_pile_device_out(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, out_device: int = 0,
                                 s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None,
                                 subgrid: bool = False) -> dict:
@@ -1295,6 +1301,98 @@ def _view_prediction(w: Warp) -> ViewPrediction:
     return ViewPrediction(w.err, w.hit, mae, hits / float(w.hit.shape[1] * w.hit.shape[2]), w.row_err, w.row_hits)
 
 
+class NovelView(NamedTuple):
+    """The novel view's planes (include/rslf_hip.h, rslf_novel_view, states the rule), per target k of the T targets of a
+    call; None where not asked for.  colour [T, V, U, C] f32: the blend of the views that agree with the pixel's disparity
+    (where nobody agreed the first view in field, unverified; 0 at holes); depth f32: the disparity of every target pixel,
+    the z-buffer's at hits, a bound's at filled pixels, 0 at holes; fill uint8: 0 hole, 1 hit, 2 filled from the left, 3 from
+    the right; n_src int32: the views blended; err f32: the residual against the view that was taken; row_err [T, V] f64 /
+    row_cov [T, V] int32: the sum of err over a row's pixels with n_src > 0 and their number."""
+    colour: Optional[torch.Tensor]
+    depth: Optional[torch.Tensor]
+    fill: Optional[torch.Tensor]
+    n_src: Optional[torch.Tensor]
+    err: Optional[torch.Tensor]
+    row_err: Optional[torch.Tensor]
+    row_cov: Optional[torch.Tensor]
+
+
+class NovelViewPrediction(NamedTuple):
+    """The leave-one-out yardstick of the novel view: err / fill / n_src [T, V, U] on the device, and per target, as numpy
+    float64 [T], mean_abs_error = row_err.sum() / row_cov.sum() (NaN where nobody was blended) and coverage = the pixels with
+    n_src > 0 over V * U."""
+    err: torch.Tensor
+    fill: torch.Tensor
+    n_src: torch.Tensor
+    mean_abs_error: np.ndarray
+    coverage: np.ndarray
+    row_err: torch.Tensor
+    row_cov: torch.Tensor
+
+
+def _novel_args(targets, exclude, radius, nearer, max_gap, sources, tol, who: str):
+    """-> (c_float array, c_int array or None, T, RslfNovelViewParams); the refusals the library would make, by name first."""
+    c_t, c_ex, T, radius, nearer = _warp_args(targets, exclude, radius, nearer, who)
+    if int(sources) < 1:
+        raise ValueError("%s: sources %r: at least one view to blend" % (who, sources))
+    tol = float(tol)
+    if not tol >= 0.0:   # (a NaN compares false; +inf accepts every ok pixel)
+        raise ValueError("%s: tol %r is not a tolerance >= 0" % (who, tol))
+    return c_t, c_ex, T, _lib.RslfNovelViewParams(radius, nearer, int(max_gap), int(sources), tol)
+
+
+def _novel_out(T: int, V: int, U: int, C_: int, device, colour, depth, fill, n_src, err, rows) -> tuple[NovelView, _lib.RslfNovelViewOut]:
+    new = lambda shape, dtype, on: torch.empty(shape, dtype=dtype, device=device) if on else None
+    out = NovelView(new((T, V, U, C_), torch.float32, colour), new((T, V, U), torch.float32, depth), new((T, V, U), torch.uint8, fill),
+                    new((T, V, U), torch.int32, n_src), new((T, V, U), torch.float32, err), new((T, V), torch.float64, rows and err),
+                    new((T, V), torch.int32, rows))
+    return out, _lib.RslfNovelViewOut(*(None if t is None else t.data_ptr() for t in out))
+
+
+def novel_view(ctx: Context, depth_s_v_u: torch.Tensor, valid_s_v_u: torch.Tensor | None, volume: "Volume | None", slope: float, targets,
+               exclude=None, radius: int = 0, nearer: int = 1, max_gap: int = 0, sources: int = 4, tol: float = float("inf"),
+               colour: bool | None = None, depth: bool = True, fill: bool = True, n_src: bool = True, err: bool = False,
+               rows: bool = False) -> NovelView:
+    """rslf_novel_view (not in the reference): the view positions `targets` as finished images.  view_warp's z-buffer gives
+    every target column a hit or nothing; runs without a hit are filled with the disparity of their FARTHER bound (max_gap > 0:
+    only runs of at most that many columns), and every pixel that has a disparity gathers its colour backwards along it from
+    the views that agree with it within `tol` (the default, +inf, accepts every ok pixel), nearest views first, at most
+    `sources` of them, lerped at sub-pixel columns and blended with weights 1 / (1 + distance).  colour (default: whenever a
+    volume is given) and err need `volume`; err and rows' row_err also need every target to be a view index.  Returns a
+    NovelView of new tensors.  Queued on the context's stream, not awaited."""
+    c_t, c_ex, T, params = _novel_args(targets, exclude, radius, nearer, max_gap, sources, tol, "novel_view")
+    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
+        raise ValueError("novel_view: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]")
+    if valid_s_v_u is not None and (valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8
+                                    or not valid_s_v_u.is_cuda or not valid_s_v_u.is_contiguous()):
+        raise ValueError("novel_view: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape")
+    colour = volume is not None if colour is None else bool(colour)
+    if (colour or err) and volume is None:
+        raise ValueError("novel_view: colour and err read the light field: pass volume")
+    S, V, U = (int(x) for x in depth_s_v_u.shape)
+    out, c_out = _novel_out(T, V, U, volume.C if volume is not None else 0, depth_s_v_u.device, colour, depth, fill, n_src, err, rows)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_novel_view(ctx._h, _ptr(depth_s_v_u), _ptr(valid_s_v_u), S, V, U, float(slope),
+                                     volume._h if volume is not None else None, c_t, c_ex, T, C.byref(params), C.byref(c_out)),
+          "rslf_novel_view")
+    return out
+
+
+def no_novel_view(who: str, what: str = "get_novel_views") -> None:
+    """The forms that have no novel-view getter say so (every multi-device and sharded form is left out)."""
+    raise ValueError("%s: %s is not built here: bring the [S, V, U] planes to one device and call novel_view, "
+                     "or use Depth2DComputer / fine_to_coarse_run_host(keep=True)" % (who, what))
+
+
+def _novel_view_prediction(w: NovelView) -> NovelViewPrediction:
+    """Per target, from the row sums (waits for the stream)."""
+    row_err, row_cov = w.row_err.cpu().numpy(), w.row_cov.cpu().numpy().astype(np.int64)
+    cov = row_cov.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mae = np.where(cov > 0, row_err.sum(axis=1) / cov, np.nan)
+    return NovelViewPrediction(w.err, w.fill, w.n_src, mae, cov / float(w.fill.shape[1] * w.fill.shape[2]), w.row_err, w.row_cov)
+
+
 def grid_step(dmin: float, dmax: float, dim_d: int, who: str) -> float:
     """One step of the hypothesis grid, (dmax - dmin) / (dim_d - 1): the default tolerance of the consistency getters."""
     if int(dim_d) < 2:
@@ -1506,6 +1604,29 @@ class Depth2DComputer:
         w = view_warp(self.m_epis.ctx, self.m_best_depth_s_v_u, mask, float(np.float32(self.m_parameters.par_slope_factor)), targets,
                       targets, radius, nearer, self.m_epis, depth=False, src=False, colour=False, err=True, rows=True)
         return _view_prediction(w)
+
+    def get_novel_views(self, targets, mask: torch.Tensor | None = None, radius: int = 0, nearer: int = 1, exclude=None, max_gap: int = 0,
+                        sources: int = 4, tol: float | None = None, colour: bool = True) -> NovelView:
+        """Not in the reference: after run(), novel_view of the disparity planes with the sweep's own slope factor and the
+        light field itself -- the views at the positions `targets` as finished images: colour, depth, fill and n_src.
+        mask=None: get_valid_depths_mask_s_v_u(), as get_warped_views; tol=None: one step of the hypothesis grid.  The sweep's
+        planes are read, never written."""
+        tol = grid_step(self.m_dmin, self.m_dmax, self.m_dim_d, "get_novel_views") if tol is None else tol
+        mask = self.get_valid_depths_mask_s_v_u() if mask is None else mask
+        return novel_view(self.m_epis.ctx, self.m_best_depth_s_v_u, mask, self.m_epis, float(np.float32(self.m_parameters.par_slope_factor)),
+                          targets, exclude, radius, nearer, max_gap, sources, tol, colour=colour)
+
+    def get_novel_view_prediction(self, targets=None, mask: torch.Tensor | None = None, radius: int = 0, nearer: int = 1, max_gap: int = 0,
+                                  sources: int = 4, tol: float | None = None) -> NovelViewPrediction:
+        """Not in the reference: get_view_prediction with the novel view in the warp's place -- every view of `targets`
+        (default: all of them) rendered from the OTHER views and compared with the view that was taken: err, fill and n_src,
+        and per target mean_abs_error and coverage over the pixels somebody was blended into.  Waits for the stream."""
+        targets = list(range(self.m_epis.S)) if targets is None else [int(t) for t in targets]
+        tol = grid_step(self.m_dmin, self.m_dmax, self.m_dim_d, "get_novel_view_prediction") if tol is None else tol
+        mask = self.get_valid_depths_mask_s_v_u() if mask is None else mask
+        w = novel_view(self.m_epis.ctx, self.m_best_depth_s_v_u, mask, self.m_epis, float(np.float32(self.m_parameters.par_slope_factor)),
+                       targets, targets, radius, nearer, max_gap, sources, tol, colour=False, depth=False, err=True, rows=True)
+        return _novel_view_prediction(w)
 
     def results(self) -> dict:
         torch.cuda.synchronize(self.m_epis.ctx.device)
@@ -1968,6 +2089,43 @@ class KeptFineToCoarse:
         return _view_prediction(self._view_warp("get_view_prediction", targets, targets, level, fused_result, radius, nearer, hit=True,
                                                 depth=False, src=False, count=False, colour=False, err=True, rows=True))
 
+    def _novel_view(self, who: str, targets, exclude, level: int, fused_result: bool, radius: int, nearer: int, max_gap: int, sources: int,
+                    tol, **planes) -> NovelView:
+        if not 0 <= level < self.n_levels:
+            raise ValueError("level %d of %d" % (level, self.n_levels))
+        if fused_result and level != 0:
+            raise ValueError("%s: the fused planes are at the finest size: level 0, or fused_result=False" % who)
+        if (planes["colour"] or planes["err"]) and not self.keep_volumes:
+            raise ValueError("%s: colour and err read the level's volume: this run was made without keep_volumes" % who)
+        if tol is None:
+            if self.grid is None:
+                raise ValueError("%s: this object does not know the run's hypothesis grid: pass tol" % who)
+            tol = grid_step(*self.grid, who)
+        c_t, c_ex, T, params = _novel_args(targets, exclude, radius, nearer, max_gap, sources, tol, who)
+        out, c_out = _novel_out(T, *self.dims[level], self.C, self.ctx.device, **planes)
+        self.ctx.use_current_stream()
+        check(_lib.lib().rslf_f2c_run_novel_view(self._h, self.ctx._h, int(level), 1 if fused_result else 0, c_t, c_ex, T, C.byref(params),
+                                                 C.byref(c_out)), "rslf_f2c_run_novel_view")
+        return out
+
+    def get_novel_views(self, targets, level: int = 0, fused_result: bool = True, radius: int = 0, nearer: int = 1, exclude=None,
+                        max_gap: int = 0, sources: int = 4, tol: float | None = None, colour: bool | None = None) -> NovelView:
+        """Not in the reference: rslf_f2c_run_novel_view -- novel_view of a kept plane pair, read in place, as get_warped_views
+        reads it, with the level's kept volume.  colour=None: whenever the run keeps its volumes; tol=None: one step of the
+        run's hypothesis grid.  Returns a NovelView of new [T, V_p, U_p] tensors; the run's planes are not written."""
+        colour = self.keep_volumes if colour is None else bool(colour)
+        return self._novel_view("get_novel_views", targets, exclude, level, fused_result, radius, nearer, max_gap, sources, tol,
+                                colour=colour, depth=True, fill=True, n_src=True, err=False, rows=False)
+
+    def get_novel_view_prediction(self, targets=None, level: int = 0, fused_result: bool = True, radius: int = 0, nearer: int = 1,
+                                  max_gap: int = 0, sources: int = 4, tol: float | None = None) -> NovelViewPrediction:
+        """Not in the reference: Depth2DComputer.get_novel_view_prediction on a kept plane pair; needs a run made with
+        keep_volumes.  Waits for the stream."""
+        targets = list(range(self.S)) if targets is None else [int(t) for t in targets]
+        return _novel_view_prediction(self._novel_view("get_novel_view_prediction", targets, targets, level, fused_result, radius, nearer,
+                                                       max_gap, sources, tol, colour=False, depth=False, fill=True, n_src=True, err=True,
+                                                       rows=True))
+
     def _render(self, name: str, shapes, *args, lut_bgr=None, stacked: bool = False):
         table = _table(lut_bgr)
         outs = [torch.empty(tuple(sh) + (3,), dtype=torch.uint8, device=self.ctx.device) for sh in shapes]
@@ -2180,6 +2338,12 @@ class FineToCoarse:
 
     def get_view_prediction(self, *args, **kwargs):
         no_view_warp("FineToCoarse (the Python level loop)", "get_view_prediction")
+
+    def get_novel_views(self, *args, **kwargs):
+        no_novel_view("FineToCoarse (the Python level loop)")
+
+    def get_novel_view_prediction(self, *args, **kwargs):
+        no_novel_view("FineToCoarse (the Python level loop)", "get_novel_view_prediction")
 
     def _fit_mode(self, saturate: bool) -> int:
         return FIT_QUANTILE if saturate else FIT_MEANSTD   # ImageConverter_uchar::fit(img, saturate), rslf_plot.cpp:65-98

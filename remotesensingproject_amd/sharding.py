@@ -404,6 +404,14 @@ class ShardedDepth2D:
         from . import depth
         depth.no_view_warp("ShardedDepth2D", "get_view_prediction")
 
+    def get_novel_views(self, *args, **kwargs):
+        from . import depth
+        depth.no_novel_view("ShardedDepth2D")
+
+    def get_novel_view_prediction(self, *args, **kwargs):
+        from . import depth
+        depth.no_novel_view("ShardedDepth2D", "get_novel_view_prediction")
+
     # -- helpers -------------------------------------------------------------------------------------------------------------
     @staticmethod
     def _L():
@@ -555,6 +563,14 @@ class ShardedFineToCoarse:
     def get_view_prediction(self, *args, **kwargs):
         from . import depth
         depth.no_view_warp("ShardedFineToCoarse", "get_view_prediction")
+
+    def get_novel_views(self, *args, **kwargs):
+        from . import depth
+        depth.no_novel_view("ShardedFineToCoarse")
+
+    def get_novel_view_prediction(self, *args, **kwargs):
+        from . import depth
+        depth.no_novel_view("ShardedFineToCoarse", "get_novel_view_prediction")
 
     @property
     def pixels_scanned(self) -> int:
