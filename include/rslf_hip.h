@@ -185,6 +185,36 @@ int rslf_volume_create(rslf_ctx* ctx, int V, int S, int U, int C, rslf_volume** 
 int rslf_volume_destroy(rslf_volume* vol);   /* waits for the device; contexts and volumes may be destroyed in either order */
 int rslf_volume_describe(const rslf_volume* vol, rslf_volume_desc* out);
 
+/* ---- dilation along u (K16; not in the reference's code: the fourth lead of its report) ---- */
+/* Small slopes put most of a line's samples at sub-pixel offsets, where the scan's 2-tap lerp blurs each by an amount that
+ * depends on the offset.  The remedy is to resample the volume once along u by an integer factor with a good kernel and to
+ * run every path unchanged with slope_factor * factor (params.slope_factor is the caller's to set).
+ *   U' = factor * (U - 1) + 1; output column i * factor + p lies at source coordinate i + p / factor.
+ *   Phase 0 copies source column i bit for bit (factor 1 copies the volume).  Every other phase is a sum of T = 2 R taps,
+ *   acc = w[0] * x[i - R + 1], then acc += w[m] * x[i - R + 1 + m] for ascending m (binary32 multiply, then add), indices
+ *   clamped to [0, U - 1], and out = min(max(acc, min_value), max_value) of the source: the new volume has the source's
+ *   min_value and max_value exactly, and a non-negative volume stays one (RSLF_SCAN_* above).  The weights are the kind's
+ *   kernel h(p / factor - (m - R + 1)) in double, divided by their double sum, rounded to float.  Channels are independent. */
+#define RSLF_DILATE_LINEAR    0   /* R = 1: the lerp (what the scan does by itself: changes nothing) */
+#define RSLF_DILATE_CUBIC     1   /* R = 2: Keys' cubic convolution, a = -0.5 */
+#define RSLF_DILATE_LANCZOS3  2   /* R = 3: sinc(x) * sinc(x / 3) */
+/* *U_out = factor * (U - 1) + 1.  RSLF_ERR_INVALID_ARG: U < 1, factor outside 1..8, NULL; RSLF_ERR_UNSUPPORTED: U' and its pad
+ * do not fit an int (rslf_volume_dilate_u also applies rslf_volume_create's limits to the new volume). */
+int rslf_dilated_width(int U, int factor, int* U_out);
+/* A new volume [V][S][U'][C] from a filled one of the same context's device; enqueued on the context's stream, not awaited.
+ * The new volume is the caller's (rslf_volume_destroy).  A failed call leaves *out NULL and frees what it allocated --
+ * except where *out IS src on entry (the call would overwrite the source's handle): refused, *out untouched.
+ * RSLF_ERR_INVALID_ARG: NULL, factor outside 1..8, an unknown kind, a source never filled, a source of another device. */
+int rslf_volume_dilate_u(rslf_ctx* ctx, const rslf_volume* src, int factor, int kind, rslf_volume** out);
+/* d_out[r][u] = d_in[r][u * factor]: planes [rows][U_dilated] of the dilated frame on the source grid, [rows][U], dense.
+ * elem_bytes 1 (masks) or 4 (float, int32).  Enqueued, not awaited.  RSLF_ERR_INVALID_ARG: NULL, d_out == d_in, elem_bytes
+ * other than 1 or 4, factor outside 1..8, U_dilated not factor * (U - 1) + 1 for an integer U >= 1. */
+int rslf_planes_undilate_u(rslf_ctx* ctx, const void* d_in, int elem_bytes, size_t rows, int U_dilated, int factor, void* d_out);
+/* The same on host pointers, rows `*_row_stride_bytes` apart (0: dense).  A strided copy on the calling thread: no context,
+ * no device.  Also refuses a stride shorter than its row. */
+int rslf_planes_undilate_u_host(const void* h_in, size_t in_row_stride_bytes, int elem_bytes, size_t rows, int U_dilated, int factor,
+                                void* h_out, size_t out_row_stride_bytes);
+
 /* Host EPIs as the reference holds them: h_epis[v] -> S rows of U*C values,
  * row_stride_bytes apart (cv::Mat::step).  u8: x * float(1/255) (dc.hpp:470).
  * f32: x * float(1/double(scale)); scale < 0 => the max over all EPIs

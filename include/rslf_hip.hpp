@@ -262,6 +262,53 @@ inline Context& own(Context* ctx)   // the context an object was built on
         throw std::invalid_argument("this object was built on a MultiContext: pass the Context to render on");
     return *ctx;
 }
+
+// Not in the reference: the dilation along u (rslf_volume_dilate_u, rslf_hip.h) as the computers' set_u_dilation holds it --
+// the volume as it was uploaded, its width and the caller's slope factor, and the factor in force.
+struct Dilation {
+    rslf_volume* source;
+    int dim_u, factor;
+    float slope;
+    Dilation() : source(nullptr), dim_u(0), factor(1), slope(1.f) {}
+};
+// The computer's volume, width and slope factor (its members, by reference) put into the frame of `factor`: the volume
+// dilated from the source on the device, U' = factor * (U - 1) + 1 columns, slope factor float(source's) * float(factor).
+// Factor 1 puts the source back; nothing is launched or allocated for it.
+inline void set_u_dilation(Dilation& d, Context* ctx, rslf_volume*& vol, int& dim_u, float& slope, int factor, int kind)
+{
+    if (!ctx)
+        throw std::invalid_argument("set_u_dilation: this object was built on a MultiContext: the dilation along u is built for one context");
+    if (!d.source) {
+        d.source = vol;
+        d.dim_u = dim_u;
+        d.slope = slope;
+    }
+    int wide = 0;
+    check(rslf_dilated_width(d.dim_u, factor, &wide), "rslf_dilated_width");
+    require(kind == RSLF_DILATE_LINEAR || kind == RSLF_DILATE_CUBIC || kind == RSLF_DILATE_LANCZOS3,
+            "set_u_dilation: RSLF_DILATE_LINEAR, RSLF_DILATE_CUBIC or RSLF_DILATE_LANCZOS3");
+    rslf_volume* next = nullptr;
+    if (factor != 1)
+        check(rslf_volume_dilate_u(ctx->get(), d.source, factor, kind, &next), "rslf_volume_dilate_u");
+    else
+        next = d.source;
+    if (vol != d.source)
+        rslf_volume_destroy(vol);
+    vol = next;
+    dim_u = wide;
+    slope = d.slope * (float)factor;
+    d.factor = factor;
+}
+// planes[rows][U'] of the dilated frame on the source grid, [rows][U] (rslf_planes_undilate_u_host).
+template <typename T>
+inline std::vector<T> undilated(const std::vector<T>& planes, int dim_u, int factor)
+{
+    require(!planes.empty(), "the getters show the results of run(): call it first");
+    const size_t rows = planes.size() / (size_t)dim_u;
+    std::vector<T> out(rows * (size_t)((dim_u - 1) / factor + 1));
+    check(rslf_planes_undilate_u_host(planes.data(), 0, (int)sizeof(T), rows, dim_u, factor, out.data(), 0), "rslf_planes_undilate_u_host");
+    return out;
+}
 }  // namespace detail
 
 // Several devices (or several workers on one device) behind one handle: the pile path then cuts the scanlines into one
@@ -484,7 +531,12 @@ public:
     cv::Mat get_rbar() const { return cv::Mat(dim_v_, dim_u_, CV_32FC(CHANNELS), (void*)m_rbar_v_u.data()).clone(); }
 #endif
 
-    ~Depth1DComputer_pile() { rslf_volume_destroy(vol_); }
+    ~Depth1DComputer_pile()
+    {
+        rslf_volume_destroy(vol_);
+        if (dilation_.source != vol_)
+            rslf_volume_destroy(dilation_.source);
+    }
     Depth1DComputer_pile(const Depth1DComputer_pile&) = delete;
     Depth1DComputer_pile& operator=(const Depth1DComputer_pile&) = delete;
 
@@ -545,6 +597,26 @@ public:
         subgrid_ = on;
     }
     bool get_subgrid() const { return subgrid_; }
+
+    // Not in the reference's code (its report's fourth lead), to be called before run(): the EPIs are resampled along u on the
+    // device by the integer `factor` (1..8) with the kernel `kind` (RSLF_DILATE_*; rslf_volume_dilate_u, rslf_hip.h), and the
+    // object then behaves bit for bit as if built from the dilated EPIs with par_slope_factor * factor: every member and
+    // getter answers in the dilated frame, u_dilated() = factor * (dim_u - 1) + 1 columns wide (cols() too).  The results of
+    // an earlier run() are dropped.  Factor 1 puts the source back.  One context: throws on a MultiContext.
+    void set_u_dilation(int factor, int kind = RSLF_DILATE_CUBIC)
+    {
+        detail::set_u_dilation(dilation_, multi_ ? nullptr : ctx_, vol_, dim_u_, m_parameters.par_slope_factor, factor, kind);
+        m_edge_confidence_v_u.clear(), m_edge_confidence_mask_v_u.clear(), m_disp_confidence_v_u.clear(), m_best_depth_v_u.clear();
+        m_rbar_v_u.clear(), m_depth_idx_v_u.clear(), m_score_v_u.clear();
+    }
+    int get_u_dilation() const { return dilation_.factor; }
+    int u_dilated() const { return dim_u_; }
+    // m_best_depth_v_u and m_edge_confidence_mask_v_u on the source grid, [V][U]: their columns u * factor.
+    std::vector<float> get_best_depth_undilated() const { return detail::undilated(m_best_depth_v_u, dim_u_, dilation_.factor); }
+    std::vector<uint8_t> get_edge_confidence_mask_undilated() const
+    {
+        return detail::undilated(m_edge_confidence_mask_v_u, dim_u_, dilation_.factor);
+    }
 
     int get_s_hat() const { return m_s_hat; }
 
@@ -683,7 +755,8 @@ private:
     int m_s_hat;
     float scale_used_;
     bool subgrid_ = false;
-    const Depth1DParameters m_parameters;
+    detail::Dilation dilation_;          // set_u_dilation
+    Depth1DParameters m_parameters;      // (a copy: set_u_dilation scales its slope factor, the caller's object stays)
 };
 
 // rslf::Depth2DComputer<DataType> (dc.hpp:166-225, :651-805): disparities for every view, centre outwards,
@@ -739,7 +812,12 @@ public:
     {
     }
 #endif
-    ~Depth2DComputer() { rslf_volume_destroy(vol_); }
+    ~Depth2DComputer()
+    {
+        rslf_volume_destroy(vol_);
+        if (dilation_.source != vol_)
+            rslf_volume_destroy(dilation_.source);
+    }
     Depth2DComputer(const Depth2DComputer&) = delete;
     Depth2DComputer& operator=(const Depth2DComputer&) = delete;
 
@@ -754,6 +832,9 @@ public:
         const rslf_params p = m_parameters.to_c();
         const int line_mode = m_parameters.par_line_confidence_mode;
         detail::require(!multi_ || line_mode == RSLF_LINE_CONF_OFF, "Depth2DComputer: line confidence runs on one device");
+        // K7 samples C_e along u + (s_hat - s) * d with no slope factor (core.hpp:1058): in a dilated frame it would walk the wrong line
+        detail::require(dilation_.factor == 1 || line_mode == RSLF_LINE_CONF_OFF,
+                        "Depth2DComputer: par_line_confidence_mode together with set_u_dilation is not built (the line confidence takes no slope factor)");
         detail::require(peaks_ || propagation_ratio_ == 0.f, "Depth2DComputer: the propagation ratio reads the peak planes: call set_peaks(true)");
         withheld_ = 0;
         if (multi_) {
@@ -807,6 +888,25 @@ public:
         subgrid_ = on;
     }
     bool get_subgrid() const { return subgrid_; }
+    // Not in the reference's code, to be called before run(): as Depth1DComputer_pile::set_u_dilation.  The sweep, its
+    // propagation, get_consistency, get_warped_view, get_view_prediction, get_novel_view and the pictures all answer in the
+    // dilated frame, u_dilated() columns wide, with the slope factor par_slope_factor * factor.  Refused together with a line
+    // confidence mode (by run()).  One context: throws on a MultiContext.
+    void set_u_dilation(int factor, int kind = RSLF_DILATE_CUBIC)
+    {
+        detail::set_u_dilation(dilation_, multi_ ? nullptr : ctx_, vol_, dim_u_, m_parameters.par_slope_factor, factor, kind);
+        m_edge_confidence_s_v_u.clear(), m_edge_confidence_mask_s_v_u.clear(), m_disp_confidence_s_v_u.clear(), m_best_depth_s_v_u.clear();
+        m_rbar_s_v_u.clear(), m_line_confidence_s_v_u.clear();
+        peaks_s_v_u_ = Peaks();
+    }
+    int get_u_dilation() const { return dilation_.factor; }
+    int u_dilated() const { return dim_u_; }
+    // get_depths_s_v_u() and get_valid_depths_mask_s_v_u() on the source grid, [S][V][U]: their columns u * factor.
+    std::vector<float> get_depths_undilated() const { return detail::undilated(m_best_depth_s_v_u, dim_u_, dilation_.factor); }
+    std::vector<uint8_t> get_valid_depths_mask_undilated() const
+    {
+        return detail::undilated(get_valid_depths_mask_s_v_u(), dim_u_, dilation_.factor);
+    }
     // Not in the reference: with the mode on, run() also fills, for every view, the winner and the runner-up peak of the score
     // row of every pixel a visit scanned and accepted, and a painted pixel takes its source's (rslf_sweep_peaks, rslf_hip.h);
     // a pixel no visit scanned or painted holds -1 / 0.  No other plane changes.  Default off.  One context: an object built
@@ -1051,7 +1151,8 @@ private:
     float scale_;
     int dim_v_, dim_s_, dim_u_, m_dim_d;
     float m_dmin, m_dmax;
-    const Depth1DParameters m_parameters;
+    Depth1DParameters m_parameters;      // (a copy: set_u_dilation scales its slope factor, the caller's object stays)
+    detail::Dilation dilation_;          // set_u_dilation
     bool subgrid_ = false;   // set_subgrid
     bool peaks_ = false;     // set_peaks
     Peaks peaks_s_v_u_;      // filled by run() with the mode on
@@ -1125,6 +1226,14 @@ public:
         detail::require(!multi_, "FineToCoarse: line confidence runs on one device");
         detail::require(mode >= RSLF_LINE_CONF_OFF && mode <= RSLF_LINE_CONF_GATE, "line confidence mode: RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE");
         line_mode_ = mode;
+    }
+    // The dilation along u (Depth2DComputer::set_u_dilation) is not built for the pyramid -- its levels would need a decision
+    // about uchar arithmetic in dilated levels and about the width the pyramid starts from: any factor but 1 throws.
+    void set_u_dilation(int factor, int kind = RSLF_DILATE_CUBIC)
+    {
+        (void)kind;
+        if (factor != 1)
+            throw std::invalid_argument("set_u_dilation: the dilation along u is not built for FineToCoarse (one level: Depth1DComputer_pile, Depth2DComputer)");
     }
     // To be called before run(): the run stays on the device (rslf_f2c_run_host) and this object owns it.  get_results()
     // copies the fused planes out, the coloured getters are rendered there from the kept planes -- nothing is uploaded a

@@ -71,6 +71,8 @@ SYMBOLS = [
     "rslf_view_warp", "rslf_view_warp_host", "rslf_f2c_run_view_warp", "rslf_f2c_run_view_warp_host",
     # the novel view: the warp's holes filled, the views that see a point blended (K15)
     "rslf_novel_view", "rslf_novel_view_host", "rslf_f2c_run_novel_view", "rslf_f2c_run_novel_view_host",
+    # the dilation along u and the way back (K16)
+    "rslf_dilated_width", "rslf_volume_dilate_u", "rslf_planes_undilate_u", "rslf_planes_undilate_u_host",
 ]
 
 
@@ -372,6 +374,10 @@ def lib():
     L.rslf_f2c_run_novel_view.argtypes = [vp, vp, ci, ci, C.POINTER(cf), C.POINTER(ci), ci, C.POINTER(RslfNovelViewParams),
                                           C.POINTER(RslfNovelViewOut)]
     L.rslf_f2c_run_novel_view_host.argtypes = L.rslf_f2c_run_novel_view.argtypes
+    L.rslf_dilated_width.argtypes = [ci, ci, C.POINTER(ci)]
+    L.rslf_volume_dilate_u.argtypes = [vp, vp, ci, ci, C.POINTER(vp)]
+    L.rslf_planes_undilate_u.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, vp]
+    L.rslf_planes_undilate_u_host.argtypes = [vp, C.c_size_t, ci, C.c_size_t, ci, ci, vp, C.c_size_t]
     L.rslf_f2c_run_peaks.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.restype = cf

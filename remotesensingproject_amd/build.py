@@ -44,6 +44,7 @@ UNITS = {
     "rslf_warp.hip": ["k14_view_warp.hpp", "k14_warp_rule.hpp", "rslf_plan_warp.hpp", "k12_consistency_rule.hpp"],
     "rslf_novel.hip": ["k15_novel_view.hpp", "k15_novel_rule.hpp", "rslf_plan_novel.hpp", "k14_warp_rule.hpp", "rslf_plan_warp.hpp",
                        "k12_consistency_rule.hpp"],
+    "rslf_dilate.hip": ["k16_dilate.hpp", "k16_dilate_rule.hpp", "rslf_plan_dilate.hpp"],
     "rslf_multi.hip": [],
     "rslf_multi_sweep.hip": [],
 }

@@ -18,10 +18,11 @@
 //                         and its gate form for a kept fine-to-coarse run's levels (k13_f2c_consistency.hpp)
 //   rslf_warp.hip         the view warp: any view position from a sweep's planes, z-buffered (k14_view_warp.hpp)
 //   rslf_novel.hip        the novel view: the warp's holes filled, the views that see a point blended (k15_novel_view.hpp)
+//   rslf_dilate.hip       the dilation along u: a volume f times as wide by a good kernel, result planes back (k16_dilate.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
-//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp, rslf_plan_consistency.hpp, rslf_plan_warp.hpp   ... continued, for the units that need them
+//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp, rslf_plan_consistency.hpp, rslf_plan_warp.hpp, rslf_plan_dilate.hpp   ... continued, for the units that need them
 //   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
 //
 // Two rules of the multi-device paths: they never write into a rslf_volume they did not create (a chunk of another height

@@ -142,6 +142,45 @@ def _propagation_ratio(ratio, who: str) -> float:
     return r
 
 
+DILATE_LINEAR, DILATE_CUBIC, DILATE_LANCZOS3 = 0, 1, 2   # RSLF_DILATE_*
+DILATE_MAX_FACTOR = 8                                     # kDilateMaxFactor (csrc/k16_dilate_rule.hpp)
+
+
+def _u_dilation(u_dilation, dilation_kind, who: str) -> tuple[int, int]:
+    """(factor, kind) of the u_dilation / dilation_kind arguments; a factor is an integer in 1..8, a kind a DILATE_*."""
+    f = 1 if u_dilation is None else u_dilation
+    if isinstance(f, bool) or int(f) != f or not 1 <= int(f) <= DILATE_MAX_FACTOR:
+        raise ValueError("%s: u_dilation %r is not an integer in 1..%d" % (who, u_dilation, DILATE_MAX_FACTOR))
+    if dilation_kind not in (DILATE_LINEAR, DILATE_CUBIC, DILATE_LANCZOS3):
+        raise ValueError("%s: dilation_kind %r is not DILATE_LINEAR, DILATE_CUBIC or DILATE_LANCZOS3" % (who, dilation_kind))
+    return int(f), int(dilation_kind)
+
+
+def require_no_u_dilation(u_dilation, who: str) -> None:
+    """The dilation along u (DESIGN.md 3 "K16") is built for one device and one level: Depth1DComputer_pile, Depth1DComputer
+    and Depth2DComputer.  The pyramid needs a decision about uchar arithmetic in dilated levels and about start_dim_u, and
+    every multi-device or sharded form would have to dilate per chunk: they refuse it instead of ignoring it."""
+    if u_dilation is not None and u_dilation != 1:
+        raise ValueError("%s: u_dilation=%r is not built here (one device, one level: Depth1DComputer_pile, Depth1DComputer, "
+                         "Depth2DComputer; or Volume.dilated_u and a slope factor of your own)" % (who, u_dilation))
+
+
+def require_no_line_confidence_dilated(parameters, u_dilation: int, who: str) -> None:
+    """K7 samples C_e along u + (s_hat - s) * d with no slope factor, as the reference writes it (core.hpp:1058): in a
+    dilated frame it would walk the wrong line."""
+    if u_dilation != 1 and parameters is not None and int(parameters.par_line_confidence_mode) != LINE_CONF_OFF:
+        raise ValueError("%s: par_line_confidence_mode=%d together with u_dilation=%d is not built (the line confidence "
+                         "takes no slope factor)" % (who, int(parameters.par_line_confidence_mode), u_dilation))
+
+
+def _dilated_parameters(parameters: "Depth1DParameters", factor: int) -> "Depth1DParameters":
+    """A copy of the parameters for the dilated frame: slope factor float32(par_slope_factor) * float32(factor).  The
+    caller's object is not modified."""
+    p = copy.copy(parameters)
+    p.par_slope_factor = float(np.float32(parameters.par_slope_factor) * np.float32(factor))
+    return p
+
+
 class Context:
     """rslf_ctx bound to one GPU; launches go to torch's current stream on it."""
 
@@ -257,6 +296,8 @@ class Volume:
         self._h = h
         self.V, self.S, self.U, self.C = V, S, U, C_
         self.scale_used: float | None = None
+        self.u_dilation = 1                    # of a volume dilated_u() made: the factor ...
+        self.u_source: Volume | None = None    # ... and the volume it was made from
 
     # -- constructors -----------------------------------------------------
     @staticmethod
@@ -341,6 +382,22 @@ class Volume:
         vol.scale_used = float(su.value)
         return vol
 
+    def dilated_u(self, factor: int, kind: int = DILATE_CUBIC) -> "Volume":
+        """Not in the reference's code (its report's fourth lead): a new Volume resampled along u by the integer `factor`
+        (1..8) with the kernel `kind` (DILATE_*), U' = factor * (U - 1) + 1 columns wide (rslf_volume_dilate_u).  Column
+        i * factor holds this volume's column i bit for bit; min and max are this volume's.  Run any path on it with
+        par_slope_factor * factor.  The result carries .u_dilation and .u_source."""
+        factor, kind = _u_dilation(factor, kind, "Volume.dilated_u")
+        self.ctx.use_current_stream()
+        h = C.c_void_p()
+        check(_lib.lib().rslf_volume_dilate_u(self.ctx._h, self._h, factor, kind, C.byref(h)), "rslf_volume_dilate_u")
+        out = Volume.__new__(Volume)
+        out.ctx, out._h = self.ctx, h
+        out.V, out.S, out.U, out.C = self.V, self.S, factor * (self.U - 1) + 1, self.C
+        out.scale_used = self.scale_used
+        out.u_dilation, out.u_source = factor, self
+        return out
+
     def describe(self) -> RslfVolumeDesc:
         d = RslfVolumeDesc()
         check(_lib.lib().rslf_volume_describe(self._h, C.byref(d)), "rslf_volume_describe")
@@ -356,6 +413,39 @@ class Volume:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def undilate_u(ctx: Context, planes: torch.Tensor, factor: int) -> torch.Tensor:
+    """Result planes of a dilated frame on the source grid: planes[..., ::factor] as a new dense tensor, on the device
+    (rslf_planes_undilate_u).  Any leading dimensions; uint8, float32 or int32 CUDA tensors whose last dimension is
+    factor * (U - 1) + 1."""
+    factor, _ = _u_dilation(factor, DILATE_CUBIC, "undilate_u")
+    if not planes.is_cuda or planes.dtype not in (torch.uint8, torch.float32, torch.int32):
+        raise ValueError("undilate_u needs a uint8, float32 or int32 CUDA tensor")
+    if planes.dim() < 1 or planes.shape[-1] < 1 or (planes.shape[-1] - 1) % factor != 0:
+        raise ValueError("undilate_u: the last dimension %s is not factor * (U - 1) + 1 for factor=%d"
+                         % (planes.shape[-1] if planes.dim() else None, factor))
+    t = planes.contiguous()
+    Ud = t.shape[-1]
+    out = torch.empty(tuple(t.shape[:-1]) + ((Ud - 1) // factor + 1,), dtype=t.dtype, device=t.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_planes_undilate_u(ctx._h, _ptr(t), t.element_size(), t.numel() // Ud, Ud, factor, _ptr(out)),
+          "rslf_planes_undilate_u")
+    return out
+
+
+def _undilated(who: str, planes: dict, name: str, vol: "Volume", channels_last=()) -> torch.Tensor:
+    """The plane `name` of a computer's members on the source grid (the `undilated` getters)."""
+    if name not in planes:
+        raise ValueError("%s.undilated: no plane %r (one of %s)" % (who, name, ", ".join(sorted(planes))))
+    t = planes[name]
+    if t is None:
+        raise ValueError("%s.undilated: the plane %r is not held by this object" % (who, name))
+    if vol.u_dilation == 1:
+        return t
+    if name in channels_last:   # [..., U', C]: the columns are the last dimension but one
+        return undilate_u(vol.ctx, t.movedim(-1, 0), vol.u_dilation).movedim(0, -1).contiguous()
+    return undilate_u(vol.ctx, t, vol.u_dilation)
 
 
 # ---- rendering: the getters' pictures (include/rslf_hip.h, "rendering"; csrc/k6_render.hpp) ----------------------
@@ -753,8 +843,13 @@ class Depth1DComputer_pile:
     is already resident.  After run(), the result members hold CUDA tensors."""
 
     def __init__(self, epis, dmin: float, dmax: float, dim_d: int, s_hat: int = -1, epi_scale_factor: float = -1.0,
-                 parameters: Depth1DParameters | None = None, ctx: Context | None = None, subgrid: bool = False):
+                 parameters: Depth1DParameters | None = None, ctx: Context | None = None, subgrid: bool = False,
+                 u_dilation: int = 1, dilation_kind=DILATE_CUBIC):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        # not in the reference: the EPIs are dilated along u on the device (Volume.dilated_u) and the object behaves bit for
+        # bit as if built from the dilated EPIs with par_slope_factor * u_dilation: every member is U' wide; undilated()
+        # brings a plane back.  1: nothing happens
+        self.m_u_dilation, self.m_dilation_kind = _u_dilation(u_dilation, dilation_kind, "Depth1DComputer_pile")
         # not in the reference: the scan's disparities are moved off the hypothesis grid before the median (subgrid_refine);
         # m_depth_raw_v_u is then the refined plane, and the getters show refined values
         self.m_subgrid = bool(subgrid)
@@ -767,6 +862,9 @@ class Depth1DComputer_pile:
             self.m_epis = Volume.from_epis(list(a), epi_scale_factor, ctx)
         else:
             self.m_epis = Volume.from_dense(epis, epi_scale_factor if epi_scale_factor > 0 else 1.0, ctx)
+        if self.m_u_dilation != 1:
+            self.m_epis = self.m_epis.dilated_u(self.m_u_dilation, self.m_dilation_kind)
+            self.m_parameters = _dilated_parameters(self.m_parameters, self.m_u_dilation)
         vol = self.m_epis
         self.m_dim_d = int(dim_d)
         self.m_dmin, self.m_dmax = float(dmin), float(dmax)
@@ -804,6 +902,15 @@ class Depth1DComputer_pile:
 
     def get_s_hat(self) -> int:
         return self.m_s_hat
+
+    def undilated(self, name: str) -> torch.Tensor:
+        """A result plane on the source grid, [V, U] (rbar [V, U, C]): its columns u * u_dilation.  Names: depth, valid
+        (the edge mask), edge_confidence, disp_confidence, rbar, depth_idx, score, depth_raw.  With u_dilation = 1 the
+        member itself."""
+        planes = dict(depth=self.m_best_depth_v_u, valid=self.m_edge_confidence_mask_v_u, edge_confidence=self.m_edge_confidence_v_u,
+                      disp_confidence=self.m_disp_confidence_v_u, rbar=self.m_rbar_v_u, depth_idx=self.m_depth_idx_v_u,
+                      score=self.m_score_v_u, depth_raw=self.m_depth_raw_v_u)
+        return _undilated("Depth1DComputer_pile", planes, name, self.m_epis, ("rbar",))
 
     def get_coloured_epi(self, a_v=-1, lut_bgr=None) -> torch.Tensor:
         """dc.hpp:568-617: the EPI of scanline a_v (< 0: floor(V / 2.0)) with every confident pixel's line drawn in the
@@ -937,9 +1044,11 @@ class MultiDevice:
         return [[int(_lib.lib().rslf_multi_peer_access(self._h, i, k)) for k in range(n)] for i in range(n)]
 
     def depth1d_pile(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, s_hat: int = -1,
-                     epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None, subgrid: bool = False) -> dict:
+                     epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None, subgrid: bool = False,
+                     u_dilation: int = 1) -> dict:
         """epis: the reference's Vec<Mat> -- V arrays [S,U] or [S,U,3], all uint8, all uint16 or all float32."""
         require_no_subgrid(subgrid, "MultiDevice.depth1d_pile")
+        require_no_u_dilation(u_dilation, "MultiDevice.depth1d_pile")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((V, U), np.float32), edge_mask=np.empty((V, U), np.uint8),
                    disp_confidence=np.empty((V, U), np.float32), depth=np.empty((V, U), np.float32),
@@ -964,13 +1073,15 @@ class MultiDevice:
         return out
 
     def depth2d(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
-                parameters: Depth1DParameters | None = None, subgrid: bool = False, peaks=None, propagation_ratio=None) -> dict:
+                parameters: Depth1DParameters | None = None, subgrid: bool = False, peaks=None, propagation_ratio=None,
+                u_dilation: int = 1) -> dict:
         """Depth2DComputer (constructor + run + getters) over this object's devices: the 2-D sweep cut into one block of
         scanlines per device, the neighbours' boundary rows exchanged by peer copy on every visit
         (rslf_multi_depth2d_run_f32 / _u8 / _u16).  Host EPIs in, numpy planes [S, V, U] out."""
         require_no_subgrid(subgrid, "MultiDevice.depth2d")
         require_no_peaks(peaks, "MultiDevice.depth2d")
         require_no_propagation_ratio(propagation_ratio, "MultiDevice.depth2d")
+        require_no_u_dilation(u_dilation, "MultiDevice.depth2d")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out = dict(edge_confidence=np.empty((S, V, U), np.float32), edge_mask=np.empty((S, V, U), np.uint8),
                    disp_confidence=np.empty((S, V, U), np.float32), depth=np.empty((S, V, U), np.float32),
@@ -995,13 +1106,14 @@ class MultiDevice:
 
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                       subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None):
+                       subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
         require_no_peaks(peaks, "MultiDevice.fine_to_coarse")
         require_no_propagation_ratio(propagation_ratio, "MultiDevice.fine_to_coarse")
         require_no_consistency_gate(consistency_min_agree, "MultiDevice.fine_to_coarse")
+        require_no_u_dilation(u_dilation, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
@@ -1036,10 +1148,11 @@ class MultiDevice:
 
     def depth1d_pile_device_out(self, epis: Sequence[np.ndarray], dmin: float, dmax: float, dim_d: int, out_device: int = 0,
                                 s_hat: int = -1, epi_scale_factor: float = -1.0, parameters: Depth1DParameters | None = None,
-                                subgrid: bool = False) -> dict:
+                                subgrid: bool = False, u_dilation: int = 1) -> dict:
         """The same with the result planes left on `out_device` as CUDA tensors (float32 EPIs): every worker copies its
         rows there with a peer copy (rslf_multi_depth1d_pile_f32_dev)."""
         require_no_subgrid(subgrid, "MultiDevice.depth1d_pile_device_out")
+        require_no_u_dilation(u_dilation, "MultiDevice.depth1d_pile_device_out")
         keep, ptrs, _, V, S, U, C_, stride = host_epis(epis, np.float32, stride=True)
         dev = torch.device("cuda", out_device)
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
@@ -1406,8 +1519,14 @@ class Depth2DComputer:
 
     def __init__(self, epis, dmin: float, dmax: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, verbose: bool = False, ctx: Context | None = None,
-                 subgrid: bool = False, peaks: bool = False, propagation_ratio: float | None = None):
+                 subgrid: bool = False, peaks: bool = False, propagation_ratio: float | None = None,
+                 u_dilation: int = 1, dilation_kind=DILATE_CUBIC):
         self.m_parameters = parameters or Depth1DParameters.get_default()
+        # not in the reference: the EPIs are dilated along u on the device (Volume.dilated_u) and the object behaves bit for
+        # bit as if built from the dilated EPIs with par_slope_factor * u_dilation -- sweep, propagation, consistency, warp,
+        # novel view and the renderers all answer in the dilated frame, U' wide; undilated() brings a plane back
+        self.m_u_dilation, self.m_dilation_kind = _u_dilation(u_dilation, dilation_kind, "Depth2DComputer")
+        require_no_line_confidence_dilated(self.m_parameters, self.m_u_dilation, "Depth2DComputer")
         # not in the reference: ambiguous pixels are withheld from propagation (rslf_sweep_propagation_ratio;
         # get_withheld_sources); reads the peak planes
         self.m_propagation_ratio = _propagation_ratio(propagation_ratio, "Depth2DComputer")
@@ -1430,6 +1549,9 @@ class Depth2DComputer:
             self.m_epis = Volume.from_epis(list(a), epi_scale_factor, ctx)
         else:
             self.m_epis = Volume.from_dense(epis, epi_scale_factor if epi_scale_factor > 0 else 1.0, ctx)
+        if self.m_u_dilation != 1:
+            self.m_epis = self.m_epis.dilated_u(self.m_u_dilation, self.m_dilation_kind)
+            self.m_parameters = _dilated_parameters(self.m_parameters, self.m_u_dilation)
         vol = self.m_epis
         self.m_dim_d, self.m_dmin, self.m_dmax = int(dim_d), float(dmin), float(dmax)
         self.m_accept_all = False
@@ -1450,7 +1572,19 @@ class Depth2DComputer:
         mode = int(self.m_parameters.par_line_confidence_mode)
         if mode not in (LINE_CONF_OFF, LINE_CONF_AS_BUILT, LINE_CONF_GATE):
             raise ValueError("par_line_confidence_mode=%d: 0 (off), 1 (as built) or 2 (gate)" % mode)
+        require_no_line_confidence_dilated(self.m_parameters, self.m_u_dilation, "Depth2DComputer")   # (set after the constructor ran)
         return mode
+
+    def undilated(self, name: str) -> torch.Tensor:
+        """A result plane on the source grid, [S, V, U] (rbar [S, V, U, C]): its columns u * u_dilation.  Names: depth,
+        valid (get_valid_depths_mask_s_v_u), edge_mask, edge_confidence, disp_confidence, rbar, scan_mask.  With
+        u_dilation = 1 the plane itself."""
+        planes = dict(depth=self.m_best_depth_s_v_u, edge_mask=self.m_edge_confidence_mask_s_v_u,
+                      edge_confidence=self.m_edge_confidence_s_v_u, disp_confidence=self.m_disp_confidence_s_v_u,
+                      rbar=self.m_rbar_s_v_u, scan_mask=self.m_scan_mask_s_v_u, valid=None)
+        if name == "valid":
+            planes["valid"] = self.get_valid_depths_mask_s_v_u()
+        return _undilated("Depth2DComputer", planes, name, self.m_epis, ("rbar",))
 
     def run(self, want_stats: bool = True) -> None:
         """dc.hpp:748-805."""
@@ -1675,10 +1809,16 @@ class Depth1DComputer:
     confidence + scan, no median.  Results are [U] CUDA tensors."""
 
     def __init__(self, epi, dmin: float, dmax: float, dim_d: int, s_hat: int = -1, epi_scale_factor: float = -1.0,
-                 parameters: Depth1DParameters | None = None, ctx: Context | None = None, subgrid: bool = False):
+                 parameters: Depth1DParameters | None = None, ctx: Context | None = None, subgrid: bool = False,
+                 u_dilation: int = 1, dilation_kind=DILATE_CUBIC):
         self.m_parameters = parameters or Depth1DParameters.get_default()
         self.m_subgrid = bool(subgrid)   # not in the reference: disparities moved off the hypothesis grid (subgrid_refine)
+        # not in the reference: the EPI dilated along u on the device, as Depth1DComputer_pile does
+        self.m_u_dilation, self.m_dilation_kind = _u_dilation(u_dilation, dilation_kind, "Depth1DComputer")
         self.m_epi = Volume.from_epis([np.asarray(epi)], epi_scale_factor, ctx)
+        if self.m_u_dilation != 1:
+            self.m_epi = self.m_epi.dilated_u(self.m_u_dilation, self.m_dilation_kind)
+            self.m_parameters = _dilated_parameters(self.m_parameters, self.m_u_dilation)
         vol = self.m_epi
         self.m_dim_d, self.m_dmin, self.m_dmax = int(dim_d), float(dmin), float(dmax)
         self.m_s_hat = int(np.floor((0.0 + vol.S) / 2)) if (s_hat < 0 or s_hat > vol.S - 1) else int(s_hat)   # dc.hpp:303-311
@@ -1717,6 +1857,13 @@ class Depth1DComputer:
         out = _coloured_epi_rows(vol.ctx, self.m_best_depth_u, self.m_edge_confidence_mask_u, vol.S, self.m_s_hat, 0, lut_bgr)
         out[:, 0, :] = 0
         return out
+
+    def undilated(self, name: str) -> torch.Tensor:
+        """A result plane on the source grid, [U] (rbar [U, C]).  Names: depth, valid (the edge mask), edge_confidence,
+        disp_confidence, rbar, depth_idx, score."""
+        planes = dict(depth=self.m_best_depth_u, valid=self.m_edge_confidence_mask_u, edge_confidence=self.m_edge_confidence_u,
+                      disp_confidence=self.m_disp_confidence_u, rbar=self.m_rbar_u, depth_idx=self.m_depth_idx_u, score=self.m_score_u)
+        return _undilated("Depth1DComputer", planes, name, self.m_epi, ("rbar",))[0]
 
     def get_scores_u_d(self) -> torch.Tensor:
         """After run(): the EPI's [U, D] score matrix, the reference's buf_scores_u_d (core.hpp:616-625), over the pixels
@@ -2166,7 +2313,8 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                             ctx: Context | None = None, line_mode: int = LINE_CONF_OFF, want_levels: bool = False, keep: bool = False,
                             validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None,
                             uniqueness_ratio: float | None = None, propagation_ratio: float | None = None,
-                            consistency_min_agree: int | None = None, consistency_tol: float | None = None, consistency_radius: int = 0):
+                            consistency_min_agree: int | None = None, consistency_tol: float | None = None, consistency_radius: int = 0,
+                            u_dilation: int = 1):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -2190,7 +2338,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     rslf_f2c_run_host_cs): after a level's sweep, validity rule and uniqueness ratio, a pixel that is still valid becomes invalid
     unless agree >= min(seen, m) among the other views (view_consistency's counts; consistency_radius > 0: only views within
     it), so a coarser level decides it.  consistency_tol=None: one step of the hypothesis grid.
-    KeptFineToCoarse.consistency_gate, .inconsistent(level) and .get_gate_counts(level) read it back."""
+    KeptFineToCoarse.consistency_gate, .inconsistent(level) and .get_gate_counts(level) read it back.
+    u_dilation: refused (require_no_u_dilation): the pyramid has no dilated levels."""
+    require_no_u_dilation(u_dilation, "fine_to_coarse_run_host")
     want_cs = consistency_min_agree is not None and consistency_min_agree is not False and consistency_min_agree != 0
     cs_tol, cs_radius, cs_min_agree = 0.0, 0, 0
     if want_cs:
@@ -2284,8 +2434,9 @@ class FineToCoarse:
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                  ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None,
-                 propagation_ratio=None, consistency_min_agree=None):
+                 propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1):
         require_no_peaks(peaks, "FineToCoarse")   # (the pyramid's levels carry no peak planes)
+        require_no_u_dilation(u_dilation, "FineToCoarse")   # (nor dilated levels)
         require_no_propagation_ratio(propagation_ratio, "FineToCoarse")
         require_no_consistency_gate(consistency_min_agree, "FineToCoarse")
         self.m_parameters = parameters or Depth1DParameters.get_default()

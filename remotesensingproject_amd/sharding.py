@@ -296,13 +296,14 @@ class ShardedDepth2D:
     (tests/test_gpu_sweep2d.py)."""
 
     def __init__(self, vol, shard: Shard, dmin, dmax, dim_d: int, parameters=None, group=None, subgrid: bool = False, peaks=None,
-                 propagation_ratio=None):
+                 propagation_ratio=None, u_dilation: int = 1):
         """dmin / dmax: floats, or [S, rows, U] f32 planes over the volume's rows (a fine-to-coarse level's tightened
         per-pixel ranges, dc.hpp:201-203).  subgrid: refused -- the sub-grid sweep is a one-device mode."""
         from . import depth as rs
         rs.require_no_subgrid(subgrid, "ShardedDepth2D")   # before a device is touched
         rs.require_no_peaks(peaks, "ShardedDepth2D")       # the sweep's peaks: one device too
         rs.require_no_propagation_ratio(propagation_ratio, "ShardedDepth2D")   # ... and the gate that reads them
+        rs.require_no_u_dilation(u_dilation, "ShardedDepth2D")   # the dilation along u: one device, one level
         self.rs, self.vol, self.shard, self.group = rs, vol, shard, group
         self.bounds = (dmin, dmax) if isinstance(dmin, torch.Tensor) else None
         self.p = parameters or rs.Depth1DParameters()
@@ -484,9 +485,10 @@ class ShardedFineToCoarse:
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, rank: int, world: int, epi_scale_factor: float = -1.0,
                  parameters=None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True, ctx=None, group=None,
-                 subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None):
+                 subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1):
         from . import depth as rs
         rs.require_no_peaks(peaks, "ShardedFineToCoarse")
+        rs.require_no_u_dilation(u_dilation, "ShardedFineToCoarse")
         rs.require_no_propagation_ratio(propagation_ratio, "ShardedFineToCoarse")
         rs.require_no_consistency_gate(consistency_min_agree, "ShardedFineToCoarse")
         rs.require_no_subgrid(subgrid, "ShardedFineToCoarse")   # a one-device mode; refused before a device is touched

@@ -1,0 +1,177 @@
+"""The dilation along u (rslf_volume_dilate_u, K16) at the bench shapes, against a device-to-device copy that moves the same
+number of bytes; a c2 sweep with and without the dilation; and the small-slope field's error table on the device.
+
+    python tools/probe_dilate.py [--configs c2,c3,mansion_lr] [--factors 2,4] [--reps 5] [--rounds 3] [--seeds 3] [--tree DIR]
+
+--tree DIR: import the package from another checkout (another build of the library) instead of this one.
+
+K16 reads the source slab once and writes a slab f times as large: (1 + f) x the source's bytes cross the memory system.  The
+yardstick is a copy that moves as many: a buffer of (source + result) / 2 bytes copied once (read once, written once), in the
+same process, alternating with K16 round by round.  The kernel does nothing a copy does not do except T multiply-adds per
+sample, so the ratio says what the staging, the taps and the row ends cost.
+
+rslf_volume_dilate_u allocates its result before it launches, and an event pair around the call would also time that
+allocation.  So each timed call is queued behind a backlog of copies for the host to get ahead of the device: where the first
+event is still pending when the call returns (`clean`), the pair brackets the kernel alone; where it is not, the pair may hold
+part of the allocation, and the check is the same probe under a kernel trace (profiles/r23_dilate.md: within 3 %).  Volumes
+hold uniform noise (the time does not depend on the values); a figure is the median of --reps calls, the summary the median
+over --rounds and the spread.
+
+The sweep: bench.py's c2 field through Depth2DComputer with u_dilation 1 and 2 (cubic): pixels scanned and time per run.
+The table: tests/dilate_ref.py's small-slope field (V=12, S=9, U=96, disparities in [-0.45, 0.45], 241 hypotheses) through
+Depth1DComputer_pile, mean absolute error of depth_raw relative to the undilated run, per kind and factor, over the seeds.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="c2,c3,mansion_lr")
+    ap.add_argument("--factors", default="2,4")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--seeds", type=int, default=3)
+    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--no-table", action="store_true")
+    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    args = ap.parse_args()
+    tree = os.path.abspath(args.tree)
+    sys.path.insert(0, tree)
+    sys.path.insert(0, os.path.join(tree, "tests"))
+
+    import numpy as np
+    import torch
+    from remotesensingproject_amd import depth as rs
+    from remotesensingproject_amd.synth import CONFIGS, make_config
+
+    torch.cuda.set_device(0)
+    ctx = rs.default_context(0)
+    kinds = ((rs.DILATE_LINEAR, "linear"), (rs.DILATE_CUBIC, "cubic"), (rs.DILATE_LANCZOS3, "lanczos3"))
+    factors = [int(f) for f in args.factors.split(",")]
+    out = dict(reps=args.reps, rounds=args.rounds, k16={})
+
+    def pair():
+        return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    for name in [c for c in args.configs.split(",") if c]:
+        cfg = CONFIGS[name]
+        U, V, S, C_ = cfg["U"], cfg["V"], cfg["S"], cfg["C"]
+        src = rs.Volume.from_dense(torch.rand((V, S, U, C_), device="cuda"), 1.0, ctx)
+        src_bytes = src.describe().bytes
+        for f in factors:
+            probe = src.dilated_u(f, rs.DILATE_CUBIC)
+            dst_bytes = probe.describe().bytes
+            probe.close()
+            half = (src_bytes + dst_bytes) // 2 // 4
+            a, b = torch.empty(half, dtype=torch.float32, device="cuda"), torch.empty(half, dtype=torch.float32, device="cuda")
+            a.fill_(1.0)
+
+            def copy_ms() -> float:
+                e0, e1 = pair()
+                e0.record()
+                b.copy_(a)
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1)
+
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            src.dilated_u(f, rs.DILATE_CUBIC).close()          # (also the warm-up; close() waits for the device)
+            host_ms = (time.perf_counter() - t0) * 1e3
+            one_copy = copy_ms()
+            backlog = max(2, int(2.0 * host_ms / max(one_copy, 1e-3)) + 1)
+
+            def k16_ms(kind):
+                """(the kernel's ms, whether the first event was still pending when the call returned)"""
+                for _ in range(backlog):
+                    b.copy_(a)
+                e0, e1 = pair()
+                e0.record()
+                vol = src.dilated_u(f, kind)
+                clean = not e0.query()
+                e1.record()
+                e1.synchronize()
+                ms = e0.elapsed_time(e1)
+                vol.close()
+                return ms, clean
+
+            got = {k: [] for k in ("copy",) + tuple(n for _, n in kinds)}
+            clean_all = True
+            for _ in range(args.rounds):
+                got["copy"].append(statistics.median(copy_ms() for _ in range(args.reps)))
+                for kind, kname in kinds:
+                    runs = [k16_ms(kind) for _ in range(args.reps)]
+                    clean_all = clean_all and all(c for _, c in runs)
+                    got[kname].append(statistics.median(ms for ms, _ in runs))
+            moved = src_bytes + dst_bytes
+            copy = statistics.median(got["copy"])
+            row = dict(U=U, V=V, S=S, C=C_, f=f, source_bytes=src_bytes, result_bytes=dst_bytes, bytes_moved=moved,
+                       host_call_ms=round(host_ms, 3), backlog_copies=backlog, clean=clean_all,
+                       copy=dict(ms=round(copy, 4), spread=[round(min(got["copy"]), 4), round(max(got["copy"]), 4)],
+                                 gbps=round(moved / copy / 1e6, 1)))
+            for _, kname in kinds:
+                ms = statistics.median(got[kname])
+                row[kname] = dict(ms=round(ms, 4), spread=[round(min(got[kname]), 4), round(max(got[kname]), 4)],
+                                  gbps=round(moved / ms / 1e6, 1), ratio_to_copy=round(ms / copy, 3))
+            out["k16"]["%s/f%d" % (name, f)] = row
+            print("# %s f=%d: copy %.3f ms; %s%s" % (name, f, copy, "; ".join("%s %.3f ms (x%.2f)" % (
+                n, row[n]["ms"], row[n]["ratio_to_copy"]) for _, n in kinds), "" if clean_all else "  [not clean: the pair may hold part of the allocation]"),
+                  flush=True)
+            del a, b
+        src.close()
+        torch.cuda.empty_cache()
+
+    if not args.no_sweep:
+        host, _, cfg = make_config("c2")
+        vol = rs.Volume.from_dense(torch.from_numpy(host).cuda(), 1.0, ctx)
+        sweep = {}
+        for f in (1, 2):
+            comp = rs.Depth2DComputer(vol, cfg["dmin"], cfg["dmax"], cfg["D"], u_dilation=f)
+            comp.run()
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(args.reps):
+                e0, e1 = pair()
+                e0.record()
+                comp.run(want_stats=False)
+                e1.record()
+                e1.synchronize()
+                times.append(e0.elapsed_time(e1))
+            comp.run()
+            sweep["f%d" % f] = dict(U=comp.m_epis.U, pixels_scanned=int(comp.stats.pixels_scanned), units=int(comp.stats.units),
+                                    ms=round(statistics.median(times), 3), spread=[round(min(times), 3), round(max(times), 3)])
+        out["sweep_c2"] = sweep
+        print("# c2 sweep:", sweep, flush=True)
+
+    if not args.no_table:
+        import dilate_ref as dr
+        table = {}
+        cases = [(dr.LINEAR, 2), (dr.CUBIC, 2), (dr.CUBIC, 3), (dr.CUBIC, 4), (dr.LANCZOS3, 2), (dr.LANCZOS3, 4)]
+        for seed in range(1, args.seeds + 1):
+            vol, delta = dr.small_slope_field(seed)
+
+            def mae(f, kind):
+                comp = rs.Depth1DComputer_pile(vol, dr.FIELD_DMIN, dr.FIELD_DMAX, dr.FIELD_D, epi_scale_factor=1.0, u_dilation=f,
+                                               dilation_kind=kind)
+                comp.run()
+                r = comp.results()
+                return dr.field_mae(r["depth_raw"], r["edge_mask"], delta, f)
+
+            plain = mae(1, dr.CUBIC)
+            table.setdefault("plain_mae", []).append(round(plain, 6))
+            for kind, f in cases:
+                table.setdefault("%s_x%d" % (dr.NAMES[kind], f), []).append(round(mae(f, kind) / plain, 4))
+        out["mae_ratio"] = table
+        print("# MAE ratio over the plain run, seeds 1..%d: %s" % (args.seeds, table), flush=True)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
