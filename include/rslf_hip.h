@@ -215,6 +215,36 @@ int rslf_planes_undilate_u(rslf_ctx* ctx, const void* d_in, int elem_bytes, size
 int rslf_planes_undilate_u_host(const void* h_in, size_t in_row_stride_bytes, int elem_bytes, size_t rows, int U_dilated, int factor,
                                 void* h_out, size_t out_row_stride_bytes);
 
+/* ---- derivative channels (K17; not in the reference's code: the second lead of its report) ---- */
+/* Every level down the pyramid, the Gaussian and the halving erase fine texture, and the edge confidence of the coarse
+ * levels -- the ones meant to decide what the fine levels could not -- falls under its threshold.  The absolute
+ * derivatives of the image, taken once at the finest level and carried down by the same downsample, survive where the
+ * intensity has gone flat (averaging an absolute value is not linear).  A one-channel field x[v][s][u] becomes three
+ * channels per pixel, (x, fu, fv):
+ *   h  = 0.5f * weight                                    (float, once)
+ *   fu = cap(fabsf(x[v][s][min(u+1, U-1)] - x[v][s][max(u-1, 0)]) * h, hi)
+ *   fv = cap(fabsf(x[min(v+1, V-1)][s][u] - x[max(v-1, 0)][s][u]) * h, hi)
+ * one binary32 subtraction, fabsf, one binary32 multiplication; cap(f, hi) = f > hi ? hi : f.  Channel 0 is the source's
+ * bits; U == 1 gives fu = 0, V == 1 gives fv = 0; the neighbour along v is another EPI, the image's second spatial axis.
+ * Float elements: hi = max(m, 0), m the source's maximum, so the maximum -- and a level's epi_scale_factor -- stays the
+ * intensity's.  Integer elements (RSLF_ELEM_U8 / _U16: the pyramid's raw levels, integer values held as floats): the
+ * product goes through rintf, ties to even, as cv::saturate_cast rounds, and hi is 255 or 65535.
+ *
+ * rslf_volume_derivative_channels: a new volume [V][S][U][3] from a filled one-channel volume of the same context's device
+ * (hi from its max_value); the kernel is enqueued on the context's stream, and the call then waits for the two floats of the
+ * new slab's range, as the uploads do: min_value and max_value are the new slab's own (the maximum is the source's by the
+ * cap).  The new volume is the caller's (rslf_volume_destroy).  A failed call leaves *out NULL and frees what it allocated --
+ * except where *out IS src on entry (the call would overwrite the source's handle): refused, *out untouched.
+ * RSLF_ERR_INVALID_ARG: NULL, a weight that is not finite or is <= 0, a source never filled, a source of another device;
+ * RSLF_ERR_UNSUPPORTED: a source of three channels. */
+int rslf_volume_derivative_channels(rslf_ctx* ctx, const rslf_volume* src, float weight, rslf_volume** out);
+/* The same on device pointers: a dense level d_in_vsu [V][S][U] of element type `elem` (RSLF_ELEM_*; always floats in
+ * memory) becomes d_out_vsu3 [V][S][U][3].  hi: the cap of float elements, not a NaN and >= 0 (the caller's max(m, 0));
+ * ignored for integer elements, whose cap is their type's.  Enqueued, not awaited.  RSLF_ERR_INVALID_ARG: NULL,
+ * d_out_vsu3 == d_in_vsu, an unknown elem, a bad weight or hi, a dimension < 1; RSLF_ERR_UNSUPPORTED: 3 * U or V * S beyond an int. */
+int rslf_derivative_channels_dense(rslf_ctx* ctx, const float* d_in_vsu, int elem, int V, int S, int U, float weight, float hi,
+                                   float* d_out_vsu3);
+
 /* Host EPIs as the reference holds them: h_epis[v] -> S rows of U*C values,
  * row_stride_bytes apart (cv::Mat::step).  u8: x * float(1/255) (dc.hpp:470).
  * f32: x * float(1/double(scale)); scale < 0 => the max over all EPIs
@@ -1069,6 +1099,21 @@ int rslf_f2c_run_host_cs(rslf_ctx* ctx, const void* const* h_epis, int elem, int
                          int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
                          rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio, float propagation_ratio,
                          float consistency_tol, int consistency_radius, int consistency_min_agree);
+/* The pyramid with derivative channels (K17, above): derivative_weight > 0 on a one-channel field (C == 1) runs the raw form
+ * once on the finest level's upload and goes on with C = 3 -- every level's downsample, scale, sweep, bound tightening and
+ * the fusion run as they do for a three-channel field, bit for bit as the same call on the field (x, fu, fv); a kept run
+ * describes itself with C = 3.  0: off, the narrower entry's call.  The two entries are the fullest of their families plus
+ * the weight.  RSLF_ERR_INVALID_ARG: a negative or non-finite derivative_weight; RSLF_ERR_UNSUPPORTED: C == 3 with a weight. */
+int rslf_fine_to_coarse_run_host_dv(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                    float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                    int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid, float derivative_weight);
+int rslf_f2c_run_host_dv(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                         int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                         rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio, float propagation_ratio,
+                         float consistency_tol, int consistency_radius, int consistency_min_agree, float derivative_weight);
 /* The options read back (each pointer nullable): zeros for NULL and for a run made without the gate. */
 int rslf_f2c_run_consistency_gate(const rslf_f2c_run* run, float* tol, int* radius, int* min_agree);
 /* The pixels the gate made invalid on `level`: 0 for a level accepted whole and for every level of a run made without the

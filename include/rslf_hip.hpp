@@ -1235,6 +1235,24 @@ public:
         if (factor != 1)
             throw std::invalid_argument("set_u_dilation: the dilation along u is not built for FineToCoarse (one level: Depth1DComputer_pile, Depth2DComputer)");
     }
+    // Not in the reference's code (its report's second lead), to be called before run(): the derivative channels
+    // (rslf_fine_to_coarse_run_host_dv, rslf_f2c_run_host_dv; rslf_hip.h "derivative channels").  A one-channel field goes down
+    // the pyramid as (x, min(|dx/du| * weight / 2, hi), min(|dx/dv| * weight / 2, hi)), made once on the device from the
+    // finest level, and every level runs as it does for a three-channel field, bit for bit; a kept run is a three-channel
+    // run (its renderers' shadow cut takes the norm of three channels, get_coloured_epi_pyr's volumes hold the features;
+    // without a kept run the shadow cut of get_coloured_depth_maps reads the EPIs as they were given).  0 switches it off.
+    // Any other weight throws on an RGB field (one channel and two features are three) and on a MultiContext (one device).
+    void set_derivative_channels(float weight)
+    {
+        if (weight != 0.f && CHANNELS != 1)
+            throw std::invalid_argument("set_derivative_channels: the derivative channels are built for a one-channel field (FineToCoarse<1>)");
+        if (weight != 0.f && multi_)
+            throw std::invalid_argument("set_derivative_channels: this object was built on a MultiContext: the derivative channels are built for one context");
+        if (!(weight >= 0.f && weight <= 3.402823466e+38f))
+            throw std::invalid_argument("set_derivative_channels: 0 (off) or a finite weight > 0");
+        derivative_weight_ = weight;
+    }
+    float get_derivative_channels() const { return derivative_weight_; }
     // To be called before run(): the run stays on the device (rslf_f2c_run_host) and this object owns it.  get_results()
     // copies the fused planes out, the coloured getters are rendered there from the kept planes -- nothing is uploaded a
     // second time --, get_coloured_depth_pyr works in every line mode, get_coloured_epi_pyr exists, and the per-level
@@ -1466,7 +1484,7 @@ public:
             run_levels(p);
             return;
         }
-        if (multi_) {
+        if (multi_) {   // (set_derivative_channels refused a weight)
             if (type_ == InputType::U16)   // ushort arithmetic through the pyramid
                 check(rslf_multi_fine_to_coarse_run_host_u16(multi_->get(), (const uint16_t* const*)epis_.data(), dim_v_, dim_s_, dim_u_,
                                                              CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_, &p, max_pyr_depth_,
@@ -1482,10 +1500,11 @@ public:
             return;
         }
         // the family's widest entry, which takes any element type: no mode, no levels out
-        check(rslf_fine_to_coarse_run_host_sub(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
-                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
-                                               out_validity_s_v_u_.data(), &n_levels_, &stats, RSLF_LINE_CONF_OFF, nullptr, 0),
-              "rslf_fine_to_coarse_run_host_sub");
+        check(rslf_fine_to_coarse_run_host_dv(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+                                              dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
+                                              out_validity_s_v_u_.data(), &n_levels_, &stats, RSLF_LINE_CONF_OFF, nullptr, 0,
+                                              derivative_weight_),
+              "rslf_fine_to_coarse_run_host_dv");
     }
     void get_results(std::vector<float>& out_map_s_v_u, std::vector<uint8_t>& out_validity_s_v_u) const
     {
@@ -1619,11 +1638,11 @@ private:
         detail::require(peaks_ || propagation_ratio_ == 0.f, "FineToCoarse: the propagation ratio reads the peak planes: call set_peaks(true)");
         gate_held_ = false;
         // the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's (rslf_hip.h)
-        check(rslf_f2c_run_host_cs(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
+        check(rslf_f2c_run_host_dv(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
                                    &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
                                    keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, peaks_ ? 1 : 0, uniqueness_, propagation_ratio_,
-                                   gate_tol_, gate_radius_, gate_min_agree_),
-              "rslf_f2c_run_host_cs");
+                                   gate_tol_, gate_radius_, gate_min_agree_, derivative_weight_),
+              "rslf_f2c_run_host_dv");
         peaks_held_ = peaks_;
         gate_held_ = gate_min_agree_ > 0;
         rslf_f2c_run_desc d;
@@ -1704,10 +1723,10 @@ private:
         lo.h_Cl_svu = hl.data();
         lo.h_Ce_svu = nullptr;
         // the family's widest entry, which takes any element type
-        check(rslf_fine_to_coarse_run_host_sub(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
-                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
-                                               out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo, subgrid_ ? 1 : 0),
-              "rslf_fine_to_coarse_run_host_sub");
+        check(rslf_fine_to_coarse_run_host_dv(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+                                              dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
+                                              out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo, subgrid_ ? 1 : 0, derivative_weight_),
+              "rslf_fine_to_coarse_run_host_dv");
     }
     int elem() const { return type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32; }
 #ifdef RSLFX_HAVE_OPENCV
@@ -1746,6 +1765,7 @@ private:
     int gate_min_agree_ = 0, gate_radius_ = 0;   // set_consistency_gate
     float gate_tol_ = 0.f;
     bool gate_held_ = false;     // the kept run was made with the consistency gate
+    float derivative_weight_ = 0.f;   // set_derivative_channels
     int validity_rule_;
     rslf_f2c_run* run_;          // the kept run, owned
 };

@@ -73,6 +73,8 @@ SYMBOLS = [
     "rslf_novel_view", "rslf_novel_view_host", "rslf_f2c_run_novel_view", "rslf_f2c_run_novel_view_host",
     # the dilation along u and the way back (K16)
     "rslf_dilated_width", "rslf_volume_dilate_u", "rslf_planes_undilate_u", "rslf_planes_undilate_u_host",
+    # the derivative channels: a one-channel field as (x, |dx/du|, |dx/dv|), and the pyramid on it (K17)
+    "rslf_volume_derivative_channels", "rslf_derivative_channels_dense", "rslf_fine_to_coarse_run_host_dv", "rslf_f2c_run_host_dv",
 ]
 
 
@@ -361,6 +363,10 @@ def lib():
     L.rslf_f2c_run_consistency.argtypes = [vp, vp, ci, ci, cf, ci, ci, C.POINTER(RslfViewCounts), vp, vp]
     L.rslf_f2c_run_consistency_host.argtypes = L.rslf_f2c_run_consistency.argtypes
     L.rslf_f2c_run_host_cs.argtypes = L.rslf_f2c_run_host_pr.argtypes + [cf, ci, ci]
+    L.rslf_f2c_run_host_dv.argtypes = L.rslf_f2c_run_host_cs.argtypes + [cf]
+    L.rslf_fine_to_coarse_run_host_dv.argtypes = L.rslf_fine_to_coarse_run_host_sub.argtypes + [cf]
+    L.rslf_volume_derivative_channels.argtypes = [vp, vp, cf, C.POINTER(vp)]
+    L.rslf_derivative_channels_dense.argtypes = [vp, vp, ci, ci, ci, ci, cf, cf, vp]
     L.rslf_f2c_run_consistency_gate.argtypes = [vp, C.POINTER(cf), C.POINTER(ci), C.POINTER(ci)]
     L.rslf_f2c_run_inconsistent.argtypes = [vp, ci, C.POINTER(C.c_ulonglong)]
     L.rslf_f2c_consistency_mask.argtypes = [vp, vp, vp, ci, ci, ci, cf, cf, ci, ci, vp, vp, vp, vp]

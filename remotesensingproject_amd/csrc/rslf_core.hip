@@ -402,6 +402,29 @@ static int minmax_end(rslf_volume* vol)
     return RSLF_OK;
 }
 
+// The range of a volume whose slab a kernel of another unit wrote (K17): that kernel leaves n (min, max) pairs, as K0's
+// rows do, in the buffer range_partials hands out; volume_range_from_partials folds them as the uploads fold theirs, waits
+// for the two floats and marks the volume filled.
+int rslf::range_partials(rslf_ctx* ctx, size_t n, float** out)
+{
+    const int rc = ensure_partial(ctx, n);
+    if (!rc)
+        *out = ctx->scratch.partial.as<float>();
+    return rc;
+}
+
+int rslf::volume_range_from_partials(rslf_volume* vol, int n)
+{
+    rslf_ctx* ctx = vol->ctx;
+    const int rc = minmax_begin(ctx);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(k0_minmax_final, dim3(1), dim3(256), 0, ctx->stream, ctx->scratch.partial.as<float>(), n,
+                       ctx->scratch.minmax.as<float>());
+    HIP_TRY(hipGetLastError());
+    return minmax_end(vol);
+}
+
 // Pack rows [V0, V0+Vn) from a device buffer holding just those rows.
 template <typename SrcT>
 static int pack_chunk(rslf_volume* vol, const SrcT* d_src, int V0, int Vn, bool image_major, float scale)

@@ -2,6 +2,7 @@
 // the pyramid (Gaussian blur + halving), the bound tightening, the fusion (K5) and the native level loop, whose one-context
 // form is here and whose multi-device form is in rslf_multi_sweep.hip.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
+#include "rslf_plan_derivative.hpp"
 #include "rslf_plan_f2c_consistency.hpp"
 #include "rslf_plan_f2c_peaks.hpp"
 
@@ -289,10 +290,19 @@ static int f2c_valid_mask(hipStream_t st, const float* conf, uint8_t* out, size_
 int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& o, const F2cHostOut& out, rslf_stats* stats,
                          F2cKept* keep, const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep)
 {
-    const int V = req.V, S = req.S, U = req.U, C = req.C;
+    const int V = req.V, S = req.S, U = req.U;
     const rslf_params* const p = req.p;
-    if (!ctx || !req.h_epis || V < 1 || S < 1 || U < 1 || (C != 1 && C != 3))
+    if (!ctx || !req.h_epis || V < 1 || S < 1 || U < 1 || (req.C != 1 && req.C != 3))
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
+    // the derivative channels (K17): a one-channel field is (x, |dx/du|, |dx/dv|) from its upload on, and everything below
+    // runs as it does for a three-channel field
+    if (!plan::derivative_option_ok(o.derivative_weight))
+        return fail(RSLF_ERR_INVALID_ARG, "derivative_weight=%g: 0 (off) or a finite weight > 0", (double)o.derivative_weight);
+    const bool derivative = o.derivative_weight > 0.0f;
+    if (derivative && req.C != 1)
+        return fail(RSLF_ERR_UNSUPPORTED, "derivative_weight=%g with C=%d: the derivative channels are built for a one-channel field",
+                    (double)o.derivative_weight, req.C);
+    const int C = derivative ? kDerivativeChannels : req.C;
     if (!keep && (!out.map_svu || !out.valid_svu))   // a kept run holds the fused planes itself
         return fail(RSLF_ERR_INVALID_ARG, "bad arguments");
     if (!plan::f2c_validity_rule_ok(o.validity_rule) || (!keep && o.validity_rule != RSLF_F2C_VALID_COMPAT))
@@ -312,10 +322,25 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions&
     if (out.levels && out.levels->capacity < P)
         return fail(RSLF_ERR_INVALID_ARG, "levels out: capacity %d < pyramid depth %d", out.levels->capacity, P);
     DevBuf raw;   // the raw (un-normalised) values of the level at hand, [V][S][U][C]
-    HIP_TRY(raw.alloc((size_t)V * S * U * C * sizeof(float)));
-    rc = f2c_upload_raw(ctx, req.elem, req.h_epis, V, S, U, C, req.row_stride_bytes, raw.as<float>());
+    HIP_TRY(raw.alloc((size_t)V * S * U * req.C * sizeof(float)));
+    rc = f2c_upload_raw(ctx, req.elem, req.h_epis, V, S, U, req.C, req.row_stride_bytes, raw.as<float>());
     if (rc)
         return rc;
+    if (derivative) {   // once, at the finest level: the features go down with the intensity from here
+        float hi = 0.0f;   // (integer elements: their type's, derivative_channels_raw)
+        if (req.elem == Elem::F32) {
+            rc = rslf_device_max_f32(ctx, raw.as<const float>(), (size_t)V * S * U, &hi);
+            if (rc)
+                return rc;
+            hi = derivative_hi_f32(hi);
+        }
+        DevBuf source;
+        std::swap(raw, source);
+        HIP_TRY(raw.alloc((size_t)V * S * U * C * sizeof(float)));
+        rc = derivative_channels_raw(ctx, source.as<const float>(), req.elem, V, S, U, o.derivative_weight, hi, raw.as<float>());
+        if (rc)
+            return rc;
+    }   // (`source` is freed here, which waits for the device)
 
     // run(): rslf_fine_to_coarse.hpp:171-299, each level built just before its sweep; every level keeps its disparities
     // and validity for the fusion -- and everything else where the caller owns the planes
@@ -335,6 +360,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions&
         F2cLevel lv;
         lv.V = kl.V = dims[l].V;
         lv.U = kl.U = dims[l].U;
+        lv.C = C;
         lv.params = *p;
         lv.params.slope_factor = (float)((0.0 + lv.U) / U);              // f2c.hpp:139
         kl.slope = lv.params.slope_factor;
@@ -512,11 +538,12 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const
     asked.subgrid = o.subgrid;
     if (int rc = check_sweep_modes(asked))
         return rc;
-    const int S = req.S, C = req.C;
+    const int S = req.S;
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
         if (inject_hit(kInjectSweep))   // host side, before the level's sweep is queued
             throw std::runtime_error("injected failure in a fine-to-coarse level (rslf_debug_inject)");
         const size_t n = (size_t)S * lv.V * lv.U;
+        const int C = lv.C;   // (the request's, or 3 with the derivative channels)
         DevBuf Cd, rbar, mask;
         if (!lv.Cd_svu)   // a kept run's C_d is its owner's
             HIP_TRY(Cd.alloc(n * 4));
@@ -627,6 +654,25 @@ extern "C" int rslf_fine_to_coarse_run_host_sub(rslf_ctx* ctx, const void* const
                             accept_all_last_scale};
     F2cOptions options;
     options.line_mode = line_mode, options.subgrid = subgrid;
+    return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
+}
+RSLF_API_CATCH
+
+// ... and with derivative_weight > 0 a one-channel field goes down the pyramid as (x, |dx/du|, |dx/dv|) (K17)
+extern "C" int rslf_fine_to_coarse_run_host_dv(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                               size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                               const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                               float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                               int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid,
+                                               float derivative_weight) RSLF_API_TRY
+{
+    Elem e;
+    if (int rc = elem_of(elem, &e))
+        return rc;
+    const F2cRequest req = {e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions options;
+    options.line_mode = line_mode, options.subgrid = subgrid, options.derivative_weight = derivative_weight;
     return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
 }
 RSLF_API_CATCH

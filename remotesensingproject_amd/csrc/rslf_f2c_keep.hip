@@ -325,7 +325,7 @@ static int f2c_run_host(rslf_ctx* ctx, int elem, F2cRequest req, const F2cOption
     std::unique_ptr<rslf_f2c_run> r(new rslf_f2c_run());   // whatever path leaves this function, a run not handed out is freed
     r->device = ctx->device;
     r->S = req.S;
-    r->C = req.C;
+    r->C = o.derivative_weight > 0.0f ? 3 : req.C;   // (with the derivative channels the run is a three-channel run; the loop refuses C != 1)
     r->elem = elem;
     r->params = *req.p;
     r->options = o;
@@ -414,6 +414,26 @@ extern "C" int rslf_f2c_run_host_cs(rslf_ctx* ctx, const void* const* h_epis, in
     o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
     o.peaks = peaks, o.uniqueness = uniqueness_ratio, o.propagation_ratio = propagation_ratio;
     o.cs_tol = consistency_tol, o.cs_radius = consistency_radius, o.cs_min_agree = consistency_min_agree;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
+}
+RSLF_API_CATCH
+
+// ... and with derivative_weight > 0 a one-channel field goes down the pyramid as (x, |dx/du|, |dx/dv|) (K17): the run is a
+// three-channel run
+extern "C" int rslf_f2c_run_host_dv(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
+                                    int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
+                                    float uniqueness_ratio, float propagation_ratio, float consistency_tol, int consistency_radius,
+                                    int consistency_min_agree, float derivative_weight) RSLF_API_TRY
+{
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
+    o.peaks = peaks, o.uniqueness = uniqueness_ratio, o.propagation_ratio = propagation_ratio;
+    o.cs_tol = consistency_tol, o.cs_radius = consistency_radius, o.cs_min_agree = consistency_min_agree;
+    o.derivative_weight = derivative_weight;
     return f2c_run_host(ctx, elem, req, o, run, stats);
 }
 RSLF_API_CATCH

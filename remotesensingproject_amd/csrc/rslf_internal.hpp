@@ -19,10 +19,11 @@
 //   rslf_warp.hip         the view warp: any view position from a sweep's planes, z-buffered (k14_view_warp.hpp)
 //   rslf_novel.hip        the novel view: the warp's holes filled, the views that see a point blended (k15_novel_view.hpp)
 //   rslf_dilate.hip       the dilation along u: a volume f times as wide by a good kernel, result planes back (k16_dilate.hpp)
+//   rslf_derivative.hip   the derivative channels: a one-channel field as (x, |dx/du|, |dx/dv|), volume and raw level (k17_derivative.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
 //   rslf_plan.hpp         every host-side decision as pure functions (unit-tested on the CPU under ASan / UBSan)
-//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp, rslf_plan_consistency.hpp, rslf_plan_warp.hpp, rslf_plan_dilate.hpp   ... continued, for the units that need them
+//   rslf_plan_peaks.hpp, rslf_plan_render.hpp, rslf_plan_subgrid.hpp, rslf_plan_sweep_gate.hpp, rslf_plan_consistency.hpp, rslf_plan_warp.hpp, rslf_plan_dilate.hpp, rslf_plan_derivative.hpp   ... continued, for the units that need them
 //   rslf_scratch.hpp      GrowBuf, the one owning buffer type (host-only, unit-tested likewise); its allocators are below
 //
 // Two rules of the multi-device paths: they never write into a rslf_volume they did not create (a chunk of another height
@@ -415,6 +416,9 @@ int ensure_plane_scratch(rslf_ctx* ctx, int V, int U);
 int ensure_group_scratch(rslf_ctx* ctx, size_t recs, size_t tiles, bool* tickets_fresh = nullptr);
 int ensure_staging(rslf_ctx* ctx, size_t bytes);
 int helper_scratch(rslf_ctx* ctx, SharedBuf which, size_t bytes, void** out);
+// the range of a volume from n (min, max) pairs a kernel left in the pack kernels' partials (rslf_derivative.hip)
+int range_partials(rslf_ctx* ctx, size_t n, float** out);
+int volume_range_from_partials(rslf_volume* vol, int n);
 // The element type of a host light field (the cv::Mat depths the reference's constructors take, dc.hpp:269-288,
 // :442-475, :671-705): CV_32F, CV_8U, CV_16U.  Chosen once at the C-ABI entry point; everything below it dispatches on it.
 enum class Elem { F32, U8, U16 };
@@ -582,6 +586,8 @@ struct F2cOptions {
     float propagation_ratio = 0.0f;                 // > 0: every level's sweep gated by this ratio (rslf_f2c_run_host_pr; needs peaks)
     float cs_tol = 0.0f;                            // validity by cross-view consistency (rslf_f2c_run_host_cs): with cs_min_agree > 0, after a
     int cs_radius = 0, cs_min_agree = 0;            // level's rule and uniqueness, a valid pixel the other views contradict becomes invalid
+    float derivative_weight = 0.0f;                 // > 0: a one-channel field goes down the pyramid as (x, |dx/du|, |dx/dv|) by this weight (K17,
+                                                    // rslf_*_run_host_dv): three channels from the finest level's upload on
 };
 // The host outputs of a pyramid, each nullable: the fused planes, the depth, every level's planes.
 struct F2cHostOut {
@@ -595,6 +601,7 @@ struct F2cLevel {
     int V = 0, U = 0;
     rslf_params params;                 // slope_factor set (f2c.hpp:139)
     float scale = 1.0f;                 // the level's epi_scale_factor (dc.hpp:671-705)
+    int C = 0;                          // channels of the level: the request's, or 3 with the derivative channels
     const float* raw_vsuc = nullptr;    // [V][S][U][C] raw values of the level
     const float* dmin_svu = nullptr;    // [S][V][U] ranges tightened from the level above; NULL on level 0
     const float* dmax_svu = nullptr;
@@ -637,6 +644,11 @@ int fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& optio
 // The loop on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run.
 int fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& options, const F2cHostOut& out,
                                rslf_stats* stats, F2cKept* keep);
+
+// rslf_derivative.hip
+// The raw form of the derivative channels (K17), enqueued on the context's stream: a dense level d_in [V][S][U] (integer
+// elements: integer values held as floats) becomes d_out [V][S][U][3].  hi: the cap of float elements (derivative_hi_f32).
+int derivative_channels_raw(rslf_ctx* ctx, const float* d_in, Elem e, int V, int S, int U, float weight, float hi, float* d_out);
 
 // rslf_multi.hip
 void multi_free_dev(rslf_multi::Dev& d);

@@ -181,6 +181,28 @@ def _dilated_parameters(parameters: "Depth1DParameters", factor: int) -> "Depth1
     return p
 
 
+def _derivative_weight(derivative_channels, who: str) -> float:
+    """The weight of a derivative_channels argument: None, False or 0 is off (0.0); anything else is a finite weight > 0."""
+    if derivative_channels is None or derivative_channels is False or derivative_channels == 0:
+        return 0.0
+    try:
+        w = float(derivative_channels)
+    except (TypeError, ValueError):
+        w = float("nan")
+    if isinstance(derivative_channels, bool) or not np.isfinite(w) or w <= 0 or w > float(np.finfo(np.float32).max):
+        raise ValueError("%s: derivative_channels %r is not 0 (off) or a finite weight > 0" % (who, derivative_channels))
+    return w
+
+
+def require_no_derivative_channels(derivative_channels, who: str) -> None:
+    """The derivative channels (DESIGN.md 3 "K17") are built for one device: the pyramid of fine_to_coarse_run_host and
+    FineToCoarse, and Volume.with_derivative_channels for the three computers.  A multi-device or sharded form would have to
+    exchange the rows v - 1 and v + 1 of every chunk's ends: they refuse it instead of ignoring it."""
+    if derivative_channels is not None and derivative_channels is not False and derivative_channels != 0:
+        raise ValueError("%s: derivative_channels=%r is not built here (one device: fine_to_coarse_run_host, FineToCoarse; or "
+                         "Volume.with_derivative_channels)" % (who, derivative_channels))
+
+
 class Context:
     """rslf_ctx bound to one GPU; launches go to torch's current stream on it."""
 
@@ -298,6 +320,7 @@ class Volume:
         self.scale_used: float | None = None
         self.u_dilation = 1                    # of a volume dilated_u() made: the factor ...
         self.u_source: Volume | None = None    # ... and the volume it was made from
+        self.derivative_weight = 0.0           # of a volume with_derivative_channels() made: the weight
 
     # -- constructors -----------------------------------------------------
     @staticmethod
@@ -396,6 +419,27 @@ class Volume:
         out.V, out.S, out.U, out.C = self.V, self.S, factor * (self.U - 1) + 1, self.C
         out.scale_used = self.scale_used
         out.u_dilation, out.u_source = factor, self
+        out.derivative_weight = self.derivative_weight
+        return out
+
+    def with_derivative_channels(self, weight: float) -> "Volume":
+        """Not in the reference's code (its report's second lead): a new three-channel Volume (x, fu, fv) from this
+        one-channel one, fu = min(|x[u+1] - x[u-1]| * weight / 2, hi) along u and fv the same along v, neighbours clamped
+        to the field, hi = max(max_value, 0) (rslf_volume_derivative_channels).  Channel 0 holds this volume's bits and the
+        maximum is this volume's.  Any computer takes the result as it takes a three-channel Volume.  The result carries
+        .derivative_weight."""
+        w = _derivative_weight(weight, "Volume.with_derivative_channels")
+        if w == 0.0:
+            raise ValueError("Volume.with_derivative_channels: derivative_channels %r is not a finite weight > 0" % (weight,))
+        self.ctx.use_current_stream()
+        h = C.c_void_p()
+        check(_lib.lib().rslf_volume_derivative_channels(self.ctx._h, self._h, w, C.byref(h)), "rslf_volume_derivative_channels")
+        out = Volume.__new__(Volume)
+        out.ctx, out._h = self.ctx, h
+        out.V, out.S, out.U, out.C = self.V, self.S, self.U, 3
+        out.scale_used = self.scale_used
+        out.u_dilation, out.u_source = self.u_dilation, self.u_source
+        out.derivative_weight = w
         return out
 
     def describe(self) -> RslfVolumeDesc:
@@ -1106,7 +1150,8 @@ class MultiDevice:
 
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
-                       subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1):
+                       subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1,
+                       *, derivative_channels: float = 0.0):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
@@ -1114,6 +1159,7 @@ class MultiDevice:
         require_no_propagation_ratio(propagation_ratio, "MultiDevice.fine_to_coarse")
         require_no_consistency_gate(consistency_min_agree, "MultiDevice.fine_to_coarse")
         require_no_u_dilation(u_dilation, "MultiDevice.fine_to_coarse")
+        require_no_derivative_channels(derivative_channels, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
@@ -1938,6 +1984,38 @@ def f2c_input(epis, ctx: Context) -> tuple[torch.Tensor, np.dtype]:
     return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(ctx.device), field_dtype(a.dtype)
 
 
+def derivative_channels(ctx: Context, raw_vsuc: torch.Tensor, weight: float, dtype=np.float32) -> torch.Tensor:
+    """A dense RAW one-channel level [V,S,U] / [V,S,U,1] (float32 CUDA; f2c_input's output) as the three-channel level
+    [V,S,U,3] of (x, fu, fv) (rslf_derivative_channels_dense).  `dtype` is the light field's element type: float32 -- the
+    features are capped at max(the level's maximum, 0); np.uint8 / np.uint16 -- the values are integer levels, the features
+    are rounded to integers (ties to even) and capped at 255 / 65535."""
+    w = _derivative_weight(weight, "derivative_channels")
+    if w == 0.0:
+        raise ValueError("derivative_channels: derivative_channels %r is not a finite weight > 0" % (weight,))
+    dt = field_dtype(dtype)
+    if not raw_vsuc.is_cuda or raw_vsuc.dtype != torch.float32:
+        raise ValueError("derivative_channels needs a float32 CUDA tensor")
+    if raw_vsuc.dim() == 4 and raw_vsuc.shape[3] == 1:
+        raw_vsuc = raw_vsuc[..., 0]
+    if raw_vsuc.dim() != 3:
+        raise ValueError("derivative_channels: a one-channel level [V,S,U] or [V,S,U,1], not %s" % (tuple(raw_vsuc.shape),))
+    t = raw_vsuc.contiguous()
+    V, S, U = t.shape
+    hi = 0.0
+    ctx.use_current_stream()
+    if dt == np.float32:
+        mx = C.c_float()
+        check(_lib.lib().rslf_device_max_f32(ctx._h, _ptr(t), t.numel(), C.byref(mx)), "rslf_device_max_f32")
+        hi = max(float(mx.value), 0.0)
+    out = torch.empty((V, S, U, 3), dtype=torch.float32, device=t.device)
+    check(_lib.lib().rslf_derivative_channels_dense(ctx._h, _ptr(t), _ELEM[np.dtype(dt)], V, S, U, w, hi, _ptr(out)),
+          "rslf_derivative_channels_dense")
+    return out
+
+
+_derivative_channels_dense = derivative_channels   # (for the callers whose own argument has the name)
+
+
 def f2c_line_mode(parameters: Depth1DParameters, line_confidence_mode: int | None, who: str) -> int:
     """The line mode of a pyramid.  None: no line confidence, and parameters that ask for one are refused (the paths that
     do not carry C_l).  0 / 1 / 2: that mode on every level; parameters.par_line_confidence_mode must be 0 or equal to it."""
@@ -2314,7 +2392,7 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                             validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None,
                             uniqueness_ratio: float | None = None, propagation_ratio: float | None = None,
                             consistency_min_agree: int | None = None, consistency_tol: float | None = None, consistency_radius: int = 0,
-                            u_dilation: int = 1):
+                            u_dilation: int = 1, *, derivative_channels: float = 0.0):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -2339,8 +2417,13 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     unless agree >= min(seen, m) among the other views (view_consistency's counts; consistency_radius > 0: only views within
     it), so a coarser level decides it.  consistency_tol=None: one step of the hypothesis grid.
     KeptFineToCoarse.consistency_gate, .inconsistent(level) and .get_gate_counts(level) read it back.
-    u_dilation: refused (require_no_u_dilation): the pyramid has no dilated levels."""
+    u_dilation: refused (require_no_u_dilation): the pyramid has no dilated levels.
+    derivative_channels (not in the reference's code, its report's second lead; 0 or None: off, today's call; else a finite
+    weight w > 0; one-channel fields only; rslf_fine_to_coarse_run_host_dv, rslf_f2c_run_host_dv): the finest level becomes
+    (x, min(|dx/du| * w / 2, hi), min(|dx/dv| * w / 2, hi)) on the device and the pyramid runs on it as on a three-channel
+    field, bit for bit; a kept run describes itself with C = 3."""
     require_no_u_dilation(u_dilation, "fine_to_coarse_run_host")
+    dv = _derivative_weight(derivative_channels, "fine_to_coarse_run_host")
     want_cs = consistency_min_agree is not None and consistency_min_agree is not False and consistency_min_agree != 0
     cs_tol, cs_radius, cs_min_agree = 0.0, 0, 0
     if want_cs:
@@ -2373,6 +2456,8 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
         raise ValueError("fine_to_coarse_run_host: uniqueness_ratio %r is not in (0, 1]" % (uniqueness_ratio,))
     ctx = ctx or default_context()
     keep_alive, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
+    if dv and C_ != 1:
+        raise ValueError("fine_to_coarse_run_host: derivative_channels=%r needs a one-channel field, not C=%d" % (derivative_channels, C_))
     L = _lib.lib()
     if keep:
         if want_levels:
@@ -2383,8 +2468,11 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                 float(epi_scale_factor), C.byref(p), int(max_pyr_depth), 1 if accept_all_last_scale else 0, int(line_mode),
                 int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
         # the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's
-        check(L.rslf_f2c_run_host_cs(*args, 1 if subgrid else 0, 1 if want_peaks else 0, float(uniqueness_ratio or 0.0), gate,
-                                     cs_tol, cs_radius, cs_min_agree), "rslf_f2c_run_host_cs")
+        more = (1 if subgrid else 0, 1 if want_peaks else 0, float(uniqueness_ratio or 0.0), gate, cs_tol, cs_radius, cs_min_agree)
+        if dv:
+            check(L.rslf_f2c_run_host_dv(*args, *more, dv), "rslf_f2c_run_host_dv")
+        else:
+            check(L.rslf_f2c_run_host_cs(*args, *more), "rslf_f2c_run_host_cs")
         return KeptFineToCoarse(h, ctx, st, (float(d_min), float(d_max), int(dim_d)))
     if validity_rule != F2C_VALID_COMPAT:
         raise ValueError("fine_to_coarse_run_host: validity_rule needs keep=True")
@@ -2409,8 +2497,12 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
             C.byref(nl), C.byref(st), int(line_mode), C.byref(lo) if lo is not None else None)
     ctx.use_current_stream()
     # the family's widest entry, which takes any element type
-    check(L.rslf_fine_to_coarse_run_host_sub(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0),
-          "rslf_fine_to_coarse_run_host_sub")
+    if dv:
+        check(L.rslf_fine_to_coarse_run_host_dv(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0, dv),
+              "rslf_fine_to_coarse_run_host_dv")
+    else:
+        check(L.rslf_fine_to_coarse_run_host_sub(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0),
+              "rslf_fine_to_coarse_run_host_sub")
     out = dict(out_map=out_map, out_valid=out_valid, n_levels=int(nl.value), stats=st)
     if want_levels:
         out["levels"] = levels
@@ -2429,12 +2521,18 @@ class FineToCoarse:
     `line_confidence_mode` (None, 0, 1 or 2) is the -D_USE_LINE_CONFIDENCE_SCORE build of the pyramid: every level's
     computer runs in that mode with a C_l plane of its own, and in mode 2 (without par_use_disp_confidence_score) each
     level's validity -- the next level's bounds and the fusion -- is C_l > par_line_score_threshold (dc.hpp:903-904).
-    None is the default build; parameters whose par_line_confidence_mode is set are then refused."""
+    None is the default build; parameters whose par_line_confidence_mode is set are then refused.
+
+    `derivative_channels` (not in the reference's code, its report's second lead; 0 or None: off; else a finite weight w > 0,
+    one-channel fields only): the raw finest level becomes (x, min(|dx/du| * w / 2, hi), min(|dx/dv| * w / 2, hi)) on the
+    device (derivative_channels(), once, on f2c_input's output) and the loop runs on it as on any three-channel field."""
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                  ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None,
-                 propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1):
+                 propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1, *, derivative_channels: float = 0.0):
+        # not in the reference: a one-channel field goes down the pyramid as (x, |dx/du|, |dx/dv|) by this weight (K17); 0: off
+        self.m_derivative_channels = _derivative_weight(derivative_channels, "FineToCoarse")
         require_no_peaks(peaks, "FineToCoarse")   # (the pyramid's levels carry no peak planes)
         require_no_u_dilation(u_dilation, "FineToCoarse")   # (nor dilated levels)
         require_no_propagation_ratio(propagation_ratio, "FineToCoarse")
@@ -2445,8 +2543,13 @@ class FineToCoarse:
         ctx = ctx or default_context()
         self.m_computers: list[Depth2DComputer] = []
         self.m_parameter_instances: list[Depth1DParameters] = []
-        for _, _, par, scale, raw in f2c_pyramid(*f2c_input(epis, ctx), epi_scale_factor, self.m_parameters, max_pyr_depth, ctx,
-                                                 line_confidence_mode):
+        raw0, dt = f2c_input(epis, ctx)
+        if self.m_derivative_channels:   # once, on the finest level; the features go down with the intensity
+            if raw0.shape[3] != 1:
+                raise ValueError("FineToCoarse: derivative_channels=%r needs a one-channel field, not C=%d"
+                                 % (derivative_channels, raw0.shape[3]))
+            raw0 = _derivative_channels_dense(ctx, raw0, self.m_derivative_channels, dt)
+        for _, _, par, scale, raw in f2c_pyramid(raw0, dt, epi_scale_factor, self.m_parameters, max_pyr_depth, ctx, line_confidence_mode):
             vol = Volume.from_dense(raw, scale, ctx)
             self.m_computers.append(Depth2DComputer(vol, d_min, d_max, dim_d, parameters=par, subgrid=self.m_subgrid))
             self.m_parameter_instances.append(par)

@@ -1,0 +1,46 @@
+"""The derivative channels through the C++11 host wrapper (include/rslf_hip.hpp): tests/cpp/test_host_derivative.cpp, compiled
+with g++ against librslf_hip.so and run once on the GPU.  fine_to_coarse_run_host(..., keep=True, derivative_channels=1.5)
+computes the planes of a three-level pyramid and writes them to a temporary directory; the program runs
+rslfx::FineToCoarse<1> after set_derivative_channels(1.5) -- kept, with its levels out, and plain -- and holds every plane to
+those bytes, and checks the two forms that throw (an RGB field, an object built on a MultiContext)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+V, S, U, D, W = 44, 5, 44, 10, 1.5
+F = np.float32
+
+
+def test_the_cpp_pyramid_with_derivative_channels(tmp_path):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from remotesensingproject_amd import _lib
+    from remotesensingproject_amd import depth as rs
+    from remotesensingproject_amd.synth import make_lightfield
+    _lib.lib()   # the library the package runs (built first if it is missing)
+    so = _lib.library_path()
+    raw = make_lightfield(U, V, S, 1, seed=171, dmin=-1.0, dmax=1.0, band=4)[0][..., 0]
+    assert raw.shape == (V, S, U) and raw.dtype == F
+    raw.tofile(tmp_path / "input.f32")
+    run = rs.fine_to_coarse_run_host([raw[v] for v in range(V)], -1.0, 1.0, D, keep=True, derivative_channels=W)
+    assert run.n_levels == 3 and run.C == 3
+    for l in range(3):
+        for name, ext in (("depth", "f32"), ("valid", "u8"), ("Cd", "f32")):
+            run.plane(l, name).cpu().numpy().tofile(tmp_path / ("%s_%d.%s" % (name, l, ext)))
+    run.plane(0, "fused_map").cpu().numpy().tofile(tmp_path / "fused_map.f32")
+    fused_valid = run.plane(0, "fused_valid").cpu().numpy()
+    assert fused_valid.any()
+    fused_valid.tofile(tmp_path / "fused_valid.u8")
+    exe = str(tmp_path / "test_host_derivative")
+    subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "test_host_derivative.cpp"), "-o", exe,
+                    "-L", os.path.dirname(so), "-lrslf_hip", "-Wl,-rpath," + os.path.dirname(so)], check=True)
+    out = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True)
+    print(out.stdout + out.stderr)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "host derivative: ok" in out.stdout
