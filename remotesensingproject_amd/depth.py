@@ -336,6 +336,7 @@ class Volume:
         dt = field_dtype(e0.dtype)
         arrs, ptrs, stride = host_rows(epis, dt)   # (arrs: alive over the calls below)
         L = _lib.lib()
+        ctx.use_current_stream()
         if dt == np.uint8:
             check(L.rslf_volume_upload_epis_u8(vol._h, ptrs, stride), "rslf_volume_upload_epis_u8")
             vol.scale_used = 255.0
@@ -361,6 +362,7 @@ class Volume:
         dt = field_dtype(i0.dtype)
         arrs, ptrs, stride = host_rows(imgs, dt)   # (arrs: alive over the calls below)
         L = _lib.lib()
+        ctx.use_current_stream()
         plain = not (transpose or rotate_180)
         if dt == np.uint8:
             if plain:
