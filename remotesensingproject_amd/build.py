@@ -19,6 +19,8 @@ OBJ = os.path.join(CSRC, "build")
 SO = os.path.join(CSRC, "librslf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 COMMON = ["rslf_internal.hpp", "rslf_plan.hpp", "rslf_scratch.hpp", "rslf_device.hpp", "k2_taps.hpp", os.path.join(INCLUDE, "rslf_hip.h")]
+# the host frame of the stack operations' four forms (consistency, view warp, novel view) and what it includes
+STACK_OP = ["rslf_stack_op.hpp", "rslf_plan_stage.hpp", "rslf_plan_warp.hpp", "k14_warp_rule.hpp"]
 # translation unit -> the kernel headers it alone includes (device code is per unit; rslf_internal.hpp lists the units)
 UNITS = {
     "rslf_core.hip": ["k0_pack.hpp"],
@@ -40,10 +42,9 @@ UNITS = {
     "rslf_f2c_peaks.hip": ["k11_f2c_peaks.hpp", "k11_f2c_peak_rule.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp"],
     "rslf_render.hip": ["k6_render.hpp", "rslf_plan_render.hpp"],
     "rslf_consistency.hip": ["k12_consistency.hpp", "k12_consistency_rule.hpp", "rslf_plan_consistency.hpp", "k13_f2c_consistency.hpp",
-                             "rslf_plan_f2c_consistency.hpp"],
-    "rslf_warp.hip": ["k14_view_warp.hpp", "k14_warp_rule.hpp", "rslf_plan_warp.hpp", "k12_consistency_rule.hpp"],
-    "rslf_novel.hip": ["k15_novel_view.hpp", "k15_novel_rule.hpp", "rslf_plan_novel.hpp", "k14_warp_rule.hpp", "rslf_plan_warp.hpp",
-                       "k12_consistency_rule.hpp"],
+                             "rslf_plan_f2c_consistency.hpp"] + STACK_OP,
+    "rslf_warp.hip": ["k14_view_warp.hpp", "k12_consistency_rule.hpp"] + STACK_OP,
+    "rslf_novel.hip": ["k15_novel_view.hpp", "k15_novel_rule.hpp", "rslf_plan_novel.hpp", "k12_consistency_rule.hpp"] + STACK_OP,
     "rslf_dilate.hip": ["k16_dilate.hpp", "k16_dilate_rule.hpp", "rslf_plan_dilate.hpp"],
     "rslf_derivative.hip": ["k17_derivative.hpp", "k17_derivative_rule.hpp", "rslf_plan_derivative.hpp"],
     "rslf_multi.hip": [],

@@ -5,6 +5,7 @@
 // calls for a kept run with the gate set.  C-ABI: include/rslf_hip.h.  One device.
 #include "rslf_internal.hpp"
 #include "rslf_plan_f2c_consistency.hpp"
+#include "rslf_stack_op.hpp"
 
 #include "k12_consistency.hpp"
 #include "k13_f2c_consistency.hpp"
@@ -15,29 +16,37 @@ namespace {
 
 const rslf_view_counts kNoCounts = {nullptr, nullptr, nullptr, nullptr};
 
-int count_planes(const rslf_view_counts& c) { return (c.seen != nullptr) + (c.agree != nullptr) + (c.above != nullptr) + (c.below != nullptr); }
+// What a call asks for besides its inputs.
+struct Request {
+    float tol;
+    int radius, min_agree;
+    const rslf_view_counts* counts;   // nullable: none of the four
+    float* fused;
+    uint8_t* valid_out;
+};
 
 // The argument checks every form shares (plan::consistency_args names the fault), then the grid's limits.
-int check_consistency_args(const void* depth, const void* valid, int S, int V, int U, float tol, int min_agree, const rslf_view_counts& c,
-                           const void* fused, const void* valid_out, unsigned* grid)
+int check_consistency_args(const StackIn& in, const Request& r, unsigned* grid)
 {
-    if (!depth)
+    const int S = in.S, V = in.V, U = in.U;
+    if (!in.depth)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    const void* outs[6] = {c.seen, c.agree, c.above, c.below, fused, valid_out};
+    const rslf_view_counts& c = r.counts ? *r.counts : kNoCounts;
+    const void* outs[6] = {c.seen, c.agree, c.above, c.below, r.fused, r.valid_out};
     bool any = false, aliased = false;
     for (const void* o : outs) {
         any = any || o != nullptr;
-        aliased = aliased || (o != nullptr && (o == depth || o == valid));
+        aliased = aliased || (o != nullptr && (o == in.depth || o == in.valid));
     }
-    switch (plan::consistency_args(S, V, U, tol, min_agree, any, aliased)) {
+    switch (plan::consistency_args(S, V, U, r.tol, r.min_agree, any, aliased)) {
     case plan::kConsistencyOk:
         break;
     case plan::kConsistencyBadShape:
         return fail(RSLF_ERR_INVALID_ARG, "S=%d V=%d U=%d: not a stack of planes", S, V, U);
     case plan::kConsistencyBadTol:
-        return fail(RSLF_ERR_INVALID_ARG, "tol=%g: a finite tolerance >= 0", (double)tol);
+        return fail(RSLF_ERR_INVALID_ARG, "tol=%g: a finite tolerance >= 0", (double)r.tol);
     case plan::kConsistencyBadMinAgree:
-        return fail(RSLF_ERR_INVALID_ARG, "min_agree=%d: a count of views >= 0", min_agree);
+        return fail(RSLF_ERR_INVALID_ARG, "min_agree=%d: a count of views >= 0", r.min_agree);
     case plan::kConsistencyNoOutput:
         return fail(RSLF_ERR_INVALID_ARG, "all six output planes are NULL, nothing to compute");
     case plan::kConsistencyAlias:
@@ -50,18 +59,18 @@ int check_consistency_args(const void* depth, const void* valid, int S, int V, i
     return RSLF_OK;
 }
 
-// One launch on the context's stream; arguments checked.
-int launch_consistency(rslf_ctx* ctx, unsigned grid, const float* depth, const uint8_t* valid, int S, int V, int U, float slope, float tol,
-                       int radius, int min_agree, const rslf_view_counts& c, float* fused, uint8_t* valid_out)
+// One launch on the context's stream, writing device planes; arguments checked.
+int launch_consistency(rslf_ctx* ctx, unsigned grid, const StackIn& in, const Request& r, const rslf_view_counts& c, float* fused,
+                       uint8_t* valid_out)
 {
     ConsistencyArgs a = {};
-    a.depth = depth, a.valid = valid;
-    a.S = S, a.V = V, a.U = U, a.nseg = plan::consistency_segments(U);
-    a.slope = slope, a.tol = tol, a.radius = radius, a.min_agree = min_agree;
+    a.depth = in.depth, a.valid = in.valid;
+    a.S = in.S, a.V = in.V, a.U = in.U, a.nseg = plan::consistency_segments(in.U);
+    a.slope = in.slope, a.tol = r.tol, a.radius = r.radius, a.min_agree = r.min_agree;
     a.order = ctx->consistency_order;
     a.seen = c.seen, a.agree = c.agree, a.above = c.above, a.below = c.below;
     a.fused = fused, a.valid_out = valid_out;
-    if (valid)
+    if (in.valid)
         hipLaunchKernelGGL(k12_view_consistency<true>, dim3(grid), dim3(plan::kConsistencyBlock), 0, ctx->stream, a);
     else
         hipLaunchKernelGGL(k12_view_consistency<false>, dim3(grid), dim3(plan::kConsistencyBlock), 0, ctx->stream, a);
@@ -69,41 +78,31 @@ int launch_consistency(rslf_ctx* ctx, unsigned grid, const float* depth, const u
     return RSLF_OK;
 }
 
-// The launch on device inputs with the result planes on the HOST: the planes asked for are staged in the context's shared
-// output buffer -- the 4-byte planes one after the other, the byte plane last --, copied out, and the stream awaited.
-int consistency_to_host(rslf_ctx* ctx, unsigned grid, const float* d_depth, const uint8_t* d_valid, int S, int V, int U, float slope,
-                        float tol, int radius, int min_agree, const rslf_view_counts& h, float* h_fused, uint8_t* h_valid_out)
+// The checks, then the launch.  host_in: the input planes are host memory; host: the result planes are -- in the output stage
+// the 4-byte planes one after the other, the byte plane last, packed.
+int consistency(rslf_ctx* ctx, StackIn in, const Request& r, bool host_in, bool host)
 {
-    hipStream_t st = ctx->stream;
-    const size_t n = (size_t)S * V * U;
-    void* d_stage = nullptr;
-    int rc = helper_scratch(ctx, kSharedStageOut, n * plan::consistency_out_bytes_per_cell(count_planes(h), h_fused != nullptr, h_valid_out != nullptr),
-                            &d_stage);
+    unsigned grid = 0;
+    int rc = check_consistency_args(in, r, &grid);
+    if (!rc)
+        rc = begin_stack(ctx, host);
+    if (!rc && host_in)
+        rc = stage_stack_in(ctx, in.depth, in.valid, in.S, in.V, in.U, &in);
     if (rc)
         return rc;
-    void* const host4[5] = {h.seen, h.agree, h.above, h.below, h_fused};
-    void* dev4[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    char* at = static_cast<char*>(d_stage);
-    for (int i = 0; i < 5; i++)
-        if (host4[i]) {
-            dev4[i] = at;
-            at += n * 4;
-        }
-    uint8_t* const d_valid_out = h_valid_out ? reinterpret_cast<uint8_t*>(at) : nullptr;
-    const rslf_view_counts dc = {static_cast<int32_t*>(dev4[0]), static_cast<int32_t*>(dev4[1]), static_cast<int32_t*>(dev4[2]),
-                                 static_cast<int32_t*>(dev4[3])};
-    rc = launch_consistency(ctx, grid, d_depth, d_valid, S, V, U, slope, tol, radius, min_agree, dc, static_cast<float*>(dev4[4]), d_valid_out);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
+    const rslf_view_counts& c = r.counts ? *r.counts : kNoCounts;
+    if (!host)
+        return launch_consistency(ctx, grid, in, r, c, r.fused, r.valid_out);
+    const size_t n = (size_t)in.S * in.V * in.U;
+    const HostPlane planes[6] = {{c.seen, n * 4}, {c.agree, n * 4}, {c.above, n * 4}, {c.below, n * 4}, {r.fused, n * 4}, {r.valid_out, n}};
+    void* dev[6];
+    rc = stage_out(ctx, planes, 6, 1, dev);
+    if (rc)
         return rc;
-    }
-    for (int i = 0; i < 5; i++)
-        if (host4[i])
-            HIP_TRY(hipMemcpyAsync(host4[i], dev4[i], n * 4, hipMemcpyDeviceToHost, st));
-    if (h_valid_out)
-        HIP_TRY(hipMemcpyAsync(h_valid_out, d_valid_out, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RSLF_OK;
+    const rslf_view_counts dc = {static_cast<int32_t*>(dev[0]), static_cast<int32_t*>(dev[1]), static_cast<int32_t*>(dev[2]),
+                                 static_cast<int32_t*>(dev[3])};
+    rc = launch_consistency(ctx, grid, in, r, dc, static_cast<float*>(dev[4]), static_cast<uint8_t*>(dev[5]));
+    return deliver_out(ctx, rc, planes, 6, dev);
 }
 
 }  // namespace
@@ -114,13 +113,8 @@ extern "C" int rslf_view_consistency(rslf_ctx* ctx, const float* d_depth_svu, co
 {
     if (!ctx)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    const rslf_view_counts& c = d_out ? *d_out : kNoCounts;
-    unsigned grid = 0;
-    int rc = check_consistency_args(d_depth_svu, d_valid_svu, S, V, U, tol, min_agree, c, d_fused_svu, d_valid_out_svu, &grid);
-    if (rc)
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    return launch_consistency(ctx, grid, d_depth_svu, d_valid_svu, S, V, U, slope, tol, radius, min_agree, c, d_fused_svu, d_valid_out_svu);
+    return consistency(ctx, {d_depth_svu, d_valid_svu, S, V, U, slope, nullptr}, {tol, radius, min_agree, d_out, d_fused_svu, d_valid_out_svu},
+                       false, false);
 }
 RSLF_API_CATCH
 
@@ -130,27 +124,8 @@ extern "C" int rslf_view_consistency_host(rslf_ctx* ctx, const float* h_depth_sv
 {
     if (!ctx)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    const rslf_view_counts& c = h_out ? *h_out : kNoCounts;
-    unsigned grid = 0;
-    int rc = check_consistency_args(h_depth_svu, h_valid_svu, S, V, U, tol, min_agree, c, h_fused_svu, h_valid_out_svu, &grid);
-    if (rc)
-        return rc;
-    if (ctx->sweep.open)
-        return fail(RSLF_ERR_INVALID_ARG, "a sweep is open on this context");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t n = (size_t)S * V * U;
-    void *d_depth = nullptr, *d_valid = nullptr;
-    rc = helper_scratch(ctx, kSharedStagePlanes, n * sizeof(float), &d_depth);
-    if (!rc && h_valid_svu)
-        rc = helper_scratch(ctx, kSharedStageMask, n, &d_valid);
-    if (rc)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(d_depth, h_depth_svu, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (h_valid_svu)
-        HIP_TRY(hipMemcpyAsync(d_valid, h_valid_svu, n, hipMemcpyHostToDevice, st));
-    return consistency_to_host(ctx, grid, static_cast<const float*>(d_depth), static_cast<const uint8_t*>(d_valid), S, V, U, slope, tol,
-                               radius, min_agree, c, h_fused_svu, h_valid_out_svu);
+    return consistency(ctx, {h_depth_svu, h_valid_svu, S, V, U, slope, nullptr}, {tol, radius, min_agree, h_out, h_fused_svu, h_valid_out_svu},
+                       true, true);
 }
 RSLF_API_CATCH
 
@@ -195,39 +170,14 @@ extern "C" int rslf_f2c_consistency_mask(rslf_ctx* ctx, const float* d_depth_svu
 RSLF_API_CATCH
 
 // rslf_f2c_run_consistency and its host form: the kept planes are read in place
-static int f2c_run_consistency(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, float tol, int radius, int min_agree,
-                               const rslf_view_counts* out, float* fused_svu, uint8_t* valid_out_svu, bool host)
-{
-    if (!run || !ctx)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->device != run->device)
-        return fail(RSLF_ERR_INVALID_ARG, "the run lives on device %d, the context on device %d", run->device, ctx->device);
-    if (level < 0 || level >= (int)run->kept.levels.size())
-        return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
-    if (fused_result && level != 0)
-        return fail(RSLF_ERR_INVALID_ARG, "the fused planes are at the finest size: ask for them with level 0, not %d", level);
-    const F2cKeptLevel& kl = run->kept.levels[(size_t)level];
-    const float* depth = fused_result ? run->kept.fused_map.as<const float>() : kl.depth.as<const float>();
-    const uint8_t* valid = fused_result ? run->kept.fused_valid.as<const uint8_t>() : kl.valid.as<const uint8_t>();
-    const rslf_view_counts& c = out ? *out : kNoCounts;
-    unsigned grid = 0;
-    int rc = check_consistency_args(depth, valid, run->S, kl.V, kl.U, tol, min_agree, c, fused_svu, valid_out_svu, &grid);
-    if (rc)
-        return rc;
-    if (host && ctx->sweep.open)
-        return fail(RSLF_ERR_INVALID_ARG, "a sweep is open on this context");
-    HIP_TRY(hipSetDevice(ctx->device));
-    // the slope factor the level's sweep propagated with (f2c.hpp:139); the fused planes are level 0's size: its factor
-    if (host)
-        return consistency_to_host(ctx, grid, depth, valid, run->S, kl.V, kl.U, kl.slope, tol, radius, min_agree, c, fused_svu, valid_out_svu);
-    return launch_consistency(ctx, grid, depth, valid, run->S, kl.V, kl.U, kl.slope, tol, radius, min_agree, c, fused_svu, valid_out_svu);
-}
-
 extern "C" int rslf_f2c_run_consistency(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, float tol, int radius,
                                         int min_agree, const rslf_view_counts* d_out, float* d_fused_svu,
                                         uint8_t* d_valid_out_svu) RSLF_API_TRY
 {
-    return f2c_run_consistency(run, ctx, level, fused_result, tol, radius, min_agree, d_out, d_fused_svu, d_valid_out_svu, false);
+    StackIn in;
+    if (int rc = kept_stack(run, ctx, level, fused_result, &in))
+        return rc;
+    return consistency(ctx, in, {tol, radius, min_agree, d_out, d_fused_svu, d_valid_out_svu}, false, false);
 }
 RSLF_API_CATCH
 
@@ -235,6 +185,9 @@ extern "C" int rslf_f2c_run_consistency_host(const rslf_f2c_run* run, rslf_ctx* 
                                              int min_agree, const rslf_view_counts* h_out, float* h_fused_svu,
                                              uint8_t* h_valid_out_svu) RSLF_API_TRY
 {
-    return f2c_run_consistency(run, ctx, level, fused_result, tol, radius, min_agree, h_out, h_fused_svu, h_valid_out_svu, true);
+    StackIn in;
+    if (int rc = kept_stack(run, ctx, level, fused_result, &in))
+        return rc;
+    return consistency(ctx, in, {tol, radius, min_agree, h_out, h_fused_svu, h_valid_out_svu}, false, true);
 }
 RSLF_API_CATCH

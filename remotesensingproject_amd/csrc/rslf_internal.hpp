@@ -18,6 +18,9 @@
 //                         and its gate form for a kept fine-to-coarse run's levels (k13_f2c_consistency.hpp)
 //   rslf_warp.hip         the view warp: any view position from a sweep's planes, z-buffered (k14_view_warp.hpp)
 //   rslf_novel.hip        the novel view: the warp's holes filled, the views that see a point blended (k15_novel_view.hpp)
+//   rslf_stack_op.hpp     the host frame of those three units' four forms each (device planes, host planes, a kept run, a kept run
+//                         with host outputs): a kept run's plane pair, the open-sweep refusal, the staging of host inputs and
+//                         outputs (layout: rslf_plan_stage.hpp), and the checks and launch batches the warp and the novel view share
 //   rslf_dilate.hip       the dilation along u: a volume f times as wide by a good kernel, result planes back (k16_dilate.hpp)
 //   rslf_derivative.hip   the derivative channels: a one-channel field as (x, |dx/du|, |dx/dv|), volume and raw level (k17_derivative.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)

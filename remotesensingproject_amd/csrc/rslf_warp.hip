@@ -1,9 +1,9 @@
 // librslf_hip.so: the view warp (K14, k14_view_warp.hpp) -- rslf_view_warp on planes the caller holds on the device,
 // rslf_view_warp_host, which stages host planes through the context's shared buffers, and rslf_f2c_run_view_warp (with its
-// host-output form), which reads a kept fine-to-coarse run's planes and kept volume in place.  C-ABI: include/rslf_hip.h.
-// One device.
+// host-output form), which reads a kept fine-to-coarse run's planes and kept volume in place.  The four forms' frame and what
+// the warp shares with the novel view: rslf_stack_op.hpp.  C-ABI: include/rslf_hip.h.  One device.
 #include "rslf_internal.hpp"
-#include "rslf_plan_warp.hpp"
+#include "rslf_stack_op.hpp"
 
 #include "k14_view_warp.hpp"
 
@@ -14,70 +14,20 @@ namespace {
 const rslf_view_warp_out kNoPlanes = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 constexpr int kPlanes = 9;
 
-void plane_list(const rslf_view_warp_out& o, const void* (&p)[kPlanes])
-{
-    const void* q[kPlanes] = {o.hit, o.depth, o.src_view, o.src_col, o.count, o.colour, o.err, o.row_err, o.row_hits};
-    for (int i = 0; i < kPlanes; i++)
-        p[i] = q[i];
-}
+// What a call asks for besides its inputs.
+struct Request {
+    const float* targets;
+    const int* exclude;
+    int T, radius, nearer;
+    const rslf_view_warp_out* out;   // nullable: none of the nine
+};
 
-// The argument checks every form shares (plan::warp_args, plan::warp_target_arg and plan::warp_limits name the fault).
-int check_warp_args(const void* depth, const void* valid, int S, int V, int U, const rslf_volume* vol, const float* targets, int T, int nearer,
-                    const rslf_view_warp_out& o)
+int check_warp_args(const StackIn& in, const Request& r)
 {
-    if (!depth)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument: the depth plane");
-    const void* outs[kPlanes];
-    plane_list(o, outs);
-    bool any = false, aliased = false;
-    for (const void* p : outs) {
-        any = any || p != nullptr;
-        aliased = aliased || (p != nullptr && (p == depth || p == valid || (vol && p == (const void*)vol->base)));
-    }
-    const bool needs_volume = o.colour || o.err || o.row_err;
-    switch (plan::warp_args(S, V, U, T, nearer, any, aliased, needs_volume, vol != nullptr, vol ? vol->V : 0, vol ? vol->S : 0, vol ? vol->U : 0)) {
-    case plan::kWarpOk:
-        break;
-    case plan::kWarpBadShape:
-        return fail(RSLF_ERR_INVALID_ARG, "S=%d V=%d U=%d: not a stack of planes", S, V, U);
-    case plan::kWarpBadTargets:
-        return fail(RSLF_ERR_INVALID_ARG, "T=%d: at least one target", T);
-    case plan::kWarpBadNearer:
-        return fail(RSLF_ERR_INVALID_ARG, "nearer=0: +1 (larger disparities are nearer) or -1");
-    case plan::kWarpNoOutput:
-        return fail(RSLF_ERR_INVALID_ARG, "all nine output planes are NULL, nothing to compute");
-    case plan::kWarpAlias:
-        return fail(RSLF_ERR_INVALID_ARG, "an output plane is an input plane");
-    case plan::kWarpNoVolume:
-        return fail(RSLF_ERR_INVALID_ARG, "colour, err and row_err read the light field: volume is NULL");
-    case plan::kWarpVolumeShape:
-        return fail(RSLF_ERR_INVALID_ARG, "volume is V=%d S=%d U=%d, the planes S=%d V=%d U=%d", vol->V, vol->S, vol->U, S, V, U);
-    }
-    switch (plan::warp_limits(S, V, U, T)) {
-    case plan::kWarpFits:
-        break;
-    case plan::kWarpTooWide:
-        return fail(RSLF_ERR_UNSUPPORTED, "rows of U=%d columns: the warp's z-buffer holds %d", U, plan::kWarpMaxU);
-    case plan::kWarpTooManyViews:
-        return fail(RSLF_ERR_UNSUPPORTED, "S=%d views: the warp's keys count %d", S, kWarpMaxViews);
-    case plan::kWarpGridLimit:
-        return fail(RSLF_ERR_UNSUPPORTED, "T=%d V=%d exceed the grid limit of one launch", T, V);
-    }
-    if (!targets)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument: targets");
-    if (needs_volume && !vol->filled)
-        return fail(RSLF_ERR_INVALID_ARG, "volume has not been filled");
-    for (int k = 0; k < T; k++)
-        switch (plan::warp_target_arg(targets[k], S, o.err || o.row_err)) {
-        case plan::kWarpTargetOk:
-            break;
-        case plan::kWarpTargetRange:
-            return fail(RSLF_ERR_INVALID_ARG, "targets[%d]=%g: a finite position within +-65536", k, (double)targets[k]);
-        case plan::kWarpTargetNotAView:
-            return fail(RSLF_ERR_INVALID_ARG, "targets[%d]=%g: err compares with the view that was taken, a view index in [0, %d)", k,
-                        (double)targets[k], S);
-        }
-    return RSLF_OK;
+    const rslf_view_warp_out& o = r.out ? *r.out : kNoPlanes;
+    const void* outs[kPlanes] = {o.hit, o.depth, o.src_view, o.src_col, o.count, o.colour, o.err, o.row_err, o.row_hits};
+    return check_warp_family_args(in, r.targets, r.T, r.nearer, o.colour || o.err || o.row_err, o.err || o.row_err, outs, kPlanes, "nine",
+                                  "the warp's");
 }
 
 template <bool HAS_VALID, bool COUNT>
@@ -92,89 +42,60 @@ int launch_one(hipStream_t st, unsigned grid, size_t lds, const WarpArgs& a)
     return RSLF_OK;
 }
 
-// The launches of a call on the context's stream; arguments checked.  targets / exclude are read before the return.
-int launch_warp(rslf_ctx* ctx, const float* depth, const uint8_t* valid, int S, int V, int U, float slope, const rslf_volume* vol,
-                const float* targets, const int* exclude, int T, int radius, int nearer, const rslf_view_warp_out& o)
+// The launches of a call on the context's stream, writing the device planes o; arguments checked.
+int launch_warp(rslf_ctx* ctx, const StackIn& in, const Request& r, const rslf_view_warp_out& o)
 {
     WarpArgs a = {};
-    a.depth = depth, a.valid = valid;
-    a.S = S, a.V = V, a.U = U;
-    a.slope = slope, a.radius = radius, a.nearer = nearer;
-    if (vol && (o.colour || o.err || o.row_err))
-        a.vol = view_of(vol);
+    a.radius = r.radius, a.nearer = r.nearer;
     a.hit = o.hit, a.out_depth = o.depth, a.src_view = o.src_view, a.src_col = o.src_col, a.count = o.count;
     a.colour = o.colour, a.err = o.err, a.row_err = o.row_err, a.row_hits = o.row_hits;
-    const void* outs[kPlanes];
-    plane_list(o, outs);
-    bool aligned = U % 4 == 0;
-    for (int i = 0; i < 7; i++)   // (the two row planes are written one value at a time)
-        aligned = aligned && (reinterpret_cast<uintptr_t>(outs[i]) & 15u) == 0;
-    a.vec = aligned ? 1 : 0;
-    const size_t lds = plan::warp_lds_bytes(U, o.count != nullptr);
-    for (int l = 0; l < plan::warp_launches(T); l++) {
-        a.k_first = l * plan::kWarpLaunchTargets;
-        a.T = plan::warp_launch_targets(T, l);
-        for (int k = 0; k < a.T; k++) {
-            a.target[k] = targets[a.k_first + k];
-            a.exclude[k] = exclude ? exclude[a.k_first + k] : -1;
-        }
-        const unsigned grid = plan::warp_grid(V, a.T);
-        int rc;
+    const void* outs[kPlanes] = {o.hit, o.depth, o.src_view, o.src_col, o.count, o.colour, o.err, o.row_err, o.row_hits};
+    const size_t lds = plan::warp_lds_bytes(in.U, o.count != nullptr);
+    const bool valid = in.valid != nullptr, count = o.count != nullptr;
+    return launch_warp_family(a, in, o.colour || o.err || o.row_err, r.targets, r.exclude, r.T, outs, 7, [&](unsigned grid, const WarpArgs& w) {
         if (valid)
-            rc = o.count ? launch_one<true, true>(ctx->stream, grid, lds, a) : launch_one<true, false>(ctx->stream, grid, lds, a);
-        else
-            rc = o.count ? launch_one<false, true>(ctx->stream, grid, lds, a) : launch_one<false, false>(ctx->stream, grid, lds, a);
-        if (rc)
-            return rc;
-    }
-    return RSLF_OK;
+            return count ? launch_one<true, true>(ctx->stream, grid, lds, w) : launch_one<true, false>(ctx->stream, grid, lds, w);
+        return count ? launch_one<false, true>(ctx->stream, grid, lds, w) : launch_one<false, false>(ctx->stream, grid, lds, w);
+    });
 }
 
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// The launches on device inputs with the result planes on the HOST: the planes asked for are staged in the context's shared
-// output buffer, each at a 16-byte boundary, copied out, and the stream awaited.
-int warp_to_host(rslf_ctx* ctx, const float* d_depth, const uint8_t* d_valid, int S, int V, int U, float slope, const rslf_volume* vol,
-                 const float* targets, const int* exclude, int T, int radius, int nearer, const rslf_view_warp_out& h)
+// The checks, then the launches.  host_in: the input planes are host memory; host: the result planes are -- each at a 16-byte
+// boundary of the output stage.
+int view_warp(rslf_ctx* ctx, StackIn in, const Request& r, bool host_in, bool host)
 {
-    hipStream_t st = ctx->stream;
-    const size_t n = (size_t)T * V * U, rows = (size_t)T * V, C = vol ? (size_t)vol->C : 0;
-    void* const host[kPlanes] = {h.hit, h.depth, h.src_view, h.src_col, h.count, h.colour, h.err, h.row_err, h.row_hits};
-    const size_t bytes[kPlanes] = {n, n * 4, n * 4, n * 4, n * 4, n * 4 * C, n * 4, rows * 8, rows * 4};
-    size_t total = 0;
-    for (int i = 0; i < kPlanes; i++)
-        total += host[i] ? up16(bytes[i]) : 0;
-    void* d_stage = nullptr;
-    int rc = helper_scratch(ctx, kSharedStageOut, total, &d_stage);
+    int rc = check_warp_args(in, r);
+    if (!rc)
+        rc = check_volume_device(ctx, in.vol);   // (the caller's; a kept run's is on the run's device, which kept_stack checked)
+    if (!rc)
+        rc = begin_stack(ctx, host);
+    if (!rc && host_in)
+        rc = stage_stack_in(ctx, in.depth, in.valid, in.S, in.V, in.U, &in);
     if (rc)
         return rc;
-    void* dev[kPlanes] = {};
-    char* at = static_cast<char*>(d_stage);
-    for (int i = 0; i < kPlanes; i++)
-        if (host[i]) {
-            dev[i] = at;
-            at += up16(bytes[i]);
-        }
+    const rslf_view_warp_out& h = r.out ? *r.out : kNoPlanes;
+    if (!host)
+        return launch_warp(ctx, in, r, h);
+    const size_t n = (size_t)r.T * in.V * in.U, rows = (size_t)r.T * in.V, C = in.vol ? (size_t)in.vol->C : 0;
+    const HostPlane planes[kPlanes] = {{h.hit, n},         {h.depth, n * 4}, {h.src_view, n * 4},  {h.src_col, n * 4}, {h.count, n * 4},
+                                       {h.colour, n * 4 * C}, {h.err, n * 4},   {h.row_err, rows * 8}, {h.row_hits, rows * 4}};
+    void* dev[kPlanes];
+    rc = stage_out(ctx, planes, kPlanes, 16, dev);
+    if (rc)
+        return rc;
     const rslf_view_warp_out d = {static_cast<uint8_t*>(dev[0]), static_cast<float*>(dev[1]),  static_cast<int32_t*>(dev[2]),
                                   static_cast<int32_t*>(dev[3]), static_cast<int32_t*>(dev[4]), static_cast<float*>(dev[5]),
                                   static_cast<float*>(dev[6]),   static_cast<double*>(dev[7]),  static_cast<int32_t*>(dev[8])};
-    rc = launch_warp(ctx, d_depth, d_valid, S, V, U, slope, vol, targets, exclude, T, radius, nearer, d);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    for (int i = 0; i < kPlanes; i++)
-        if (host[i] && bytes[i])
-            HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return RSLF_OK;
+    return deliver_out(ctx, launch_warp(ctx, in, r, d), planes, kPlanes, dev);
 }
 
-int check_volume_device(const rslf_ctx* ctx, const rslf_volume* vol)
+// rslf_f2c_run_view_warp and its host form: the kept planes and the level's kept volume are read in place
+int run_view_warp(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const Request& r, bool host)
 {
-    if (vol && vol->device != ctx->device)
-        return fail(RSLF_ERR_INVALID_ARG, "volume lives on device %d, the context on device %d", vol->device, ctx->device);
-    return RSLF_OK;
+    StackIn in;
+    int rc = kept_stack(run, ctx, level, fused_result, &in);
+    if (!rc)
+        rc = check_kept_volume(in, r.out && (r.out->colour || r.out->err || r.out->row_err));
+    return rc ? rc : view_warp(ctx, in, r, false, host);
 }
 
 }  // namespace
@@ -185,14 +106,7 @@ extern "C" int rslf_view_warp(rslf_ctx* ctx, const float* d_depth_svu, const uin
 {
     if (!ctx)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    const rslf_view_warp_out& o = d_out ? *d_out : kNoPlanes;
-    int rc = check_warp_args(d_depth_svu, d_valid_svu, S, V, U, volume, targets, T, nearer, o);
-    if (!rc)
-        rc = check_volume_device(ctx, volume);
-    if (rc)
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    return launch_warp(ctx, d_depth_svu, d_valid_svu, S, V, U, slope, volume, targets, exclude, T, radius, nearer, o);   // enqueued, not awaited
+    return view_warp(ctx, {d_depth_svu, d_valid_svu, S, V, U, slope, volume}, {targets, exclude, T, radius, nearer, d_out}, false, false);
 }
 RSLF_API_CATCH
 
@@ -202,72 +116,20 @@ extern "C" int rslf_view_warp_host(rslf_ctx* ctx, const float* h_depth_svu, cons
 {
     if (!ctx)
         return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    const rslf_view_warp_out& o = h_out ? *h_out : kNoPlanes;
-    int rc = check_warp_args(h_depth_svu, h_valid_svu, S, V, U, volume, targets, T, nearer, o);
-    if (!rc)
-        rc = check_volume_device(ctx, volume);
-    if (rc)
-        return rc;
-    if (ctx->sweep.open)
-        return fail(RSLF_ERR_INVALID_ARG, "a sweep is open on this context");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t n = (size_t)S * V * U;
-    void *d_depth = nullptr, *d_valid = nullptr;
-    rc = helper_scratch(ctx, kSharedStagePlanes, n * sizeof(float), &d_depth);
-    if (!rc && h_valid_svu)
-        rc = helper_scratch(ctx, kSharedStageMask, n, &d_valid);
-    if (rc)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(d_depth, h_depth_svu, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (h_valid_svu)
-        HIP_TRY(hipMemcpyAsync(d_valid, h_valid_svu, n, hipMemcpyHostToDevice, st));
-    return warp_to_host(ctx, static_cast<const float*>(d_depth), static_cast<const uint8_t*>(d_valid), S, V, U, slope, volume, targets, exclude,
-                        T, radius, nearer, o);
+    return view_warp(ctx, {h_depth_svu, h_valid_svu, S, V, U, slope, volume}, {targets, exclude, T, radius, nearer, h_out}, true, true);
 }
 RSLF_API_CATCH
-
-// rslf_f2c_run_view_warp and its host form: the kept planes and the level's kept volume are read in place
-static int f2c_run_view_warp(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets, const int* exclude,
-                             int T, int radius, int nearer, const rslf_view_warp_out* out, bool host)
-{
-    if (!run || !ctx)
-        return fail(RSLF_ERR_INVALID_ARG, "NULL argument");
-    if (ctx->device != run->device)
-        return fail(RSLF_ERR_INVALID_ARG, "the run lives on device %d, the context on device %d", run->device, ctx->device);
-    if (level < 0 || level >= (int)run->kept.levels.size())
-        return fail(RSLF_ERR_INVALID_ARG, "level %d of %d", level, (int)run->kept.levels.size());
-    if (fused_result && level != 0)
-        return fail(RSLF_ERR_INVALID_ARG, "the fused planes are at the finest size: ask for them with level 0, not %d", level);
-    const F2cKeptLevel& kl = run->kept.levels[(size_t)level];
-    const float* depth = fused_result ? run->kept.fused_map.as<const float>() : kl.depth.as<const float>();
-    const uint8_t* valid = fused_result ? run->kept.fused_valid.as<const uint8_t>() : kl.valid.as<const uint8_t>();
-    const rslf_view_warp_out& o = out ? *out : kNoPlanes;
-    const rslf_volume* vol = run->options.keep_volumes ? kl.vol.get() : nullptr;
-    if (!vol && (o.colour || o.err || o.row_err))
-        return fail(RSLF_ERR_INVALID_ARG, "colour, err and row_err read the level's volume: the run was made without keep_volumes");
-    int rc = check_warp_args(depth, valid, run->S, kl.V, kl.U, vol, targets, T, nearer, o);
-    if (rc)
-        return rc;
-    if (host && ctx->sweep.open)
-        return fail(RSLF_ERR_INVALID_ARG, "a sweep is open on this context");
-    HIP_TRY(hipSetDevice(ctx->device));
-    // the slope factor the level's sweep propagated with (f2c.hpp:139); the fused planes are level 0's size: its factor
-    if (host)
-        return warp_to_host(ctx, depth, valid, run->S, kl.V, kl.U, kl.slope, vol, targets, exclude, T, radius, nearer, o);
-    return launch_warp(ctx, depth, valid, run->S, kl.V, kl.U, kl.slope, vol, targets, exclude, T, radius, nearer, o);
-}
 
 extern "C" int rslf_f2c_run_view_warp(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets,
                                       const int* exclude, int T, int radius, int nearer, const rslf_view_warp_out* d_out) RSLF_API_TRY
 {
-    return f2c_run_view_warp(run, ctx, level, fused_result, targets, exclude, T, radius, nearer, d_out, false);
+    return run_view_warp(run, ctx, level, fused_result, {targets, exclude, T, radius, nearer, d_out}, false);
 }
 RSLF_API_CATCH
 
 extern "C" int rslf_f2c_run_view_warp_host(const rslf_f2c_run* run, rslf_ctx* ctx, int level, int fused_result, const float* targets,
                                            const int* exclude, int T, int radius, int nearer, const rslf_view_warp_out* h_out) RSLF_API_TRY
 {
-    return f2c_run_view_warp(run, ctx, level, fused_result, targets, exclude, T, radius, nearer, h_out, true);
+    return run_view_warp(run, ctx, level, fused_result, {targets, exclude, T, radius, nearer, h_out}, true);
 }
 RSLF_API_CATCH

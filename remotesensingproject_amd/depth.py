@@ -1327,6 +1327,17 @@ def _consistency_args(tol, radius, min_agree, who: str) -> tuple[float, int, int
     return tol, int(radius), int(min_agree)
 
 
+def _stack_tensors(who: str, depth_s_v_u: torch.Tensor, valid_s_v_u: torch.Tensor | None) -> tuple[int, int, int]:
+    """The input planes of a stack operation (view_consistency, view_warp, novel_view), checked -> (S, V, U)."""
+    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
+        raise ValueError("%s: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]" % who)
+    if valid_s_v_u is not None and (valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8
+                                    or not valid_s_v_u.is_cuda or not valid_s_v_u.is_contiguous()):
+        raise ValueError("%s: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape" % who)
+    S, V, U = (int(x) for x in depth_s_v_u.shape)
+    return S, V, U
+
+
 def _consistency_out(shape, device, counts: bool, fused: bool) -> tuple[Consistency, _lib.RslfViewCounts]:
     """The planes a consistency call writes (seen .. below with counts, fused with fused, valid always) and the C struct."""
     new = lambda dtype: torch.empty(shape, dtype=dtype, device=device)
@@ -1342,12 +1353,7 @@ def view_consistency(ctx: Context, depth_s_v_u: torch.Tensor, valid_s_v_u: torch
     par_slope_factor; radius <= 0: every view, else only views within it.  Returns a Consistency of new tensors -- the four
     counts are None with counts=False, fused with fused=False.  Queued on the context's stream, not awaited."""
     tol, radius, min_agree = _consistency_args(tol, radius, min_agree, "view_consistency")
-    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
-        raise ValueError("view_consistency: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]")
-    if valid_s_v_u is not None and (valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8
-                                    or not valid_s_v_u.is_cuda or not valid_s_v_u.is_contiguous()):
-        raise ValueError("view_consistency: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape")
-    S, V, U = (int(x) for x in depth_s_v_u.shape)
+    S, V, U = _stack_tensors("view_consistency", depth_s_v_u, valid_s_v_u)
     out, c_counts = _consistency_out((S, V, U), depth_s_v_u.device, counts, fused)
     ctx.use_current_stream()
     check(_lib.lib().rslf_view_consistency(ctx._h, _ptr(depth_s_v_u), _ptr(valid_s_v_u), S, V, U, float(slope), tol, radius, min_agree,
@@ -1431,15 +1437,10 @@ def view_warp(ctx: Context, depth_s_v_u: torch.Tensor, valid_s_v_u: torch.Tensor
     only views within it.  colour (default: whenever a volume is given) and err need `volume`; err and rows' row_err also need
     every target to be a view index.  Returns a Warp of new tensors.  Queued on the context's stream, not awaited."""
     c_t, c_ex, T, radius, nearer = _warp_args(targets, exclude, radius, nearer, "view_warp")
-    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
-        raise ValueError("view_warp: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]")
-    if valid_s_v_u is not None and (valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8
-                                    or not valid_s_v_u.is_cuda or not valid_s_v_u.is_contiguous()):
-        raise ValueError("view_warp: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape")
+    S, V, U = _stack_tensors("view_warp", depth_s_v_u, valid_s_v_u)
     colour = volume is not None if colour is None else bool(colour)
     if (colour or err) and volume is None:
         raise ValueError("view_warp: colour and err read the light field: pass volume")
-    S, V, U = (int(x) for x in depth_s_v_u.shape)
     out, c_out = _warp_out(T, V, U, volume.C if volume is not None else 0, depth_s_v_u.device, hit, depth, src, count, colour, err, rows)
     ctx.use_current_stream()
     check(_lib.lib().rslf_view_warp(ctx._h, _ptr(depth_s_v_u), _ptr(valid_s_v_u), S, V, U, float(slope),
@@ -1453,13 +1454,16 @@ def no_view_warp(who: str, what: str = "get_warped_views") -> None:
                      "or use Depth2DComputer / fine_to_coarse_run_host(keep=True)" % (who, what))
 
 
-def _view_prediction(w: Warp) -> ViewPrediction:
-    """Per target, from the row sums (waits for the stream)."""
-    row_err, row_hits = w.row_err.cpu().numpy(), w.row_hits.cpu().numpy().astype(np.int64)
-    hits = row_hits.sum(axis=1)
+def _row_sums(row_err: torch.Tensor, row_count: torch.Tensor, plane: torch.Tensor) -> tuple[np.ndarray, np.ndarray]:
+    """Per target, from the row sums [T, V] (waits for the stream) -> (mean_abs_error, coverage of a [T, V, U] plane)."""
+    err, count = row_err.cpu().numpy(), row_count.cpu().numpy().astype(np.int64).sum(axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
-        mae = np.where(hits > 0, row_err.sum(axis=1) / hits, np.nan)
-    return ViewPrediction(w.err, w.hit, mae, hits / float(w.hit.shape[1] * w.hit.shape[2]), w.row_err, w.row_hits)
+        mae = np.where(count > 0, err.sum(axis=1) / count, np.nan)
+    return mae, count / float(plane.shape[1] * plane.shape[2])
+
+
+def _view_prediction(w: Warp) -> ViewPrediction:
+    return ViewPrediction(w.err, w.hit, *_row_sums(w.row_err, w.row_hits, w.hit), w.row_err, w.row_hits)
 
 
 class NovelView(NamedTuple):
@@ -1522,15 +1526,10 @@ def novel_view(ctx: Context, depth_s_v_u: torch.Tensor, valid_s_v_u: torch.Tenso
     volume is given) and err need `volume`; err and rows' row_err also need every target to be a view index.  Returns a
     NovelView of new tensors.  Queued on the context's stream, not awaited."""
     c_t, c_ex, T, params = _novel_args(targets, exclude, radius, nearer, max_gap, sources, tol, "novel_view")
-    if depth_s_v_u.dim() != 3 or depth_s_v_u.dtype != torch.float32 or not depth_s_v_u.is_cuda or not depth_s_v_u.is_contiguous():
-        raise ValueError("novel_view: depth_s_v_u must be a contiguous float32 CUDA tensor [S, V, U]")
-    if valid_s_v_u is not None and (valid_s_v_u.shape != depth_s_v_u.shape or valid_s_v_u.dtype != torch.uint8
-                                    or not valid_s_v_u.is_cuda or not valid_s_v_u.is_contiguous()):
-        raise ValueError("novel_view: valid_s_v_u must be a contiguous uint8 CUDA tensor of depth_s_v_u's shape")
+    S, V, U = _stack_tensors("novel_view", depth_s_v_u, valid_s_v_u)
     colour = volume is not None if colour is None else bool(colour)
     if (colour or err) and volume is None:
         raise ValueError("novel_view: colour and err read the light field: pass volume")
-    S, V, U = (int(x) for x in depth_s_v_u.shape)
     out, c_out = _novel_out(T, V, U, volume.C if volume is not None else 0, depth_s_v_u.device, colour, depth, fill, n_src, err, rows)
     ctx.use_current_stream()
     check(_lib.lib().rslf_novel_view(ctx._h, _ptr(depth_s_v_u), _ptr(valid_s_v_u), S, V, U, float(slope),
@@ -1546,12 +1545,7 @@ def no_novel_view(who: str, what: str = "get_novel_views") -> None:
 
 
 def _novel_view_prediction(w: NovelView) -> NovelViewPrediction:
-    """Per target, from the row sums (waits for the stream)."""
-    row_err, row_cov = w.row_err.cpu().numpy(), w.row_cov.cpu().numpy().astype(np.int64)
-    cov = row_cov.sum(axis=1)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        mae = np.where(cov > 0, row_err.sum(axis=1) / cov, np.nan)
-    return NovelViewPrediction(w.err, w.fill, w.n_src, mae, cov / float(w.fill.shape[1] * w.fill.shape[2]), w.row_err, w.row_cov)
+    return NovelViewPrediction(w.err, w.fill, w.n_src, *_row_sums(w.row_err, w.row_cov, w.fill), w.row_err, w.row_cov)
 
 
 def grid_step(dmin: float, dmax: float, dim_d: int, who: str) -> float:
@@ -2268,28 +2262,33 @@ class KeptFineToCoarse:
         map and its validity (fused_result=True, which needs level 0) or a level's depth / valid planes, with the slope
         factor the level's sweep propagated with.  tol=None: one step of the run's hypothesis grid.  Returns a Consistency
         of new [S, V_p, U_p] tensors; the run's planes are not written."""
-        if not 0 <= level < self.n_levels:
-            raise ValueError("level %d of %d" % (level, self.n_levels))
-        if fused_result and level != 0:
-            raise ValueError("get_consistency: the fused planes are at the finest size: level 0, or fused_result=False")
-        if tol is None:
-            if self.grid is None:
-                raise ValueError("get_consistency: this object does not know the run's hypothesis grid: pass tol")
-            tol = grid_step(*self.grid, "get_consistency")
-        tol, radius, min_agree = _consistency_args(tol, radius, min_agree, "get_consistency")
+        self._kept_pair("get_consistency", level, fused_result)
+        tol, radius, min_agree = _consistency_args(self._grid_tol("get_consistency", tol), radius, min_agree, "get_consistency")
         out, c_counts = _consistency_out((self.S,) + self.dims[level], self.ctx.device, counts, fused)
         self.ctx.use_current_stream()
         check(_lib.lib().rslf_f2c_run_consistency(self._h, self.ctx._h, int(level), 1 if fused_result else 0, tol, radius, min_agree,
                                                   C.byref(c_counts), _ptr(out.fused), _ptr(out.valid)), "rslf_f2c_run_consistency")
         return out
 
-    def _view_warp(self, who: str, targets, exclude, level: int, fused_result: bool, radius: int, nearer: int, **planes) -> Warp:
+    def _kept_pair(self, who: str, level: int, fused_result: bool, needs_volume: bool = False) -> None:
+        """The refusals every getter of a kept plane pair shares: the level, the fused planes' level, the volume not kept."""
         if not 0 <= level < self.n_levels:
             raise ValueError("level %d of %d" % (level, self.n_levels))
         if fused_result and level != 0:
             raise ValueError("%s: the fused planes are at the finest size: level 0, or fused_result=False" % who)
-        if (planes["colour"] or planes["err"]) and not self.keep_volumes:
+        if needs_volume and not self.keep_volumes:
             raise ValueError("%s: colour and err read the level's volume: this run was made without keep_volumes" % who)
+
+    def _grid_tol(self, who: str, tol):
+        """tol, or for None one step of the run's hypothesis grid."""
+        if tol is not None:
+            return tol
+        if self.grid is None:
+            raise ValueError("%s: this object does not know the run's hypothesis grid: pass tol" % who)
+        return grid_step(*self.grid, who)
+
+    def _view_warp(self, who: str, targets, exclude, level: int, fused_result: bool, radius: int, nearer: int, **planes) -> Warp:
+        self._kept_pair(who, level, fused_result, planes["colour"] or planes["err"])
         c_t, c_ex, T, radius, nearer = _warp_args(targets, exclude, radius, nearer, who)
         out, c_out = _warp_out(T, *self.dims[level], self.C, self.ctx.device, **planes)
         self.ctx.use_current_stream()
@@ -2318,17 +2317,8 @@ class KeptFineToCoarse:
 
     def _novel_view(self, who: str, targets, exclude, level: int, fused_result: bool, radius: int, nearer: int, max_gap: int, sources: int,
                     tol, **planes) -> NovelView:
-        if not 0 <= level < self.n_levels:
-            raise ValueError("level %d of %d" % (level, self.n_levels))
-        if fused_result and level != 0:
-            raise ValueError("%s: the fused planes are at the finest size: level 0, or fused_result=False" % who)
-        if (planes["colour"] or planes["err"]) and not self.keep_volumes:
-            raise ValueError("%s: colour and err read the level's volume: this run was made without keep_volumes" % who)
-        if tol is None:
-            if self.grid is None:
-                raise ValueError("%s: this object does not know the run's hypothesis grid: pass tol" % who)
-            tol = grid_step(*self.grid, who)
-        c_t, c_ex, T, params = _novel_args(targets, exclude, radius, nearer, max_gap, sources, tol, who)
+        self._kept_pair(who, level, fused_result, planes["colour"] or planes["err"])
+        c_t, c_ex, T, params = _novel_args(targets, exclude, radius, nearer, max_gap, sources, self._grid_tol(who, tol), who)
         out, c_out = _novel_out(T, *self.dims[level], self.C, self.ctx.device, **planes)
         self.ctx.use_current_stream()
         check(_lib.lib().rslf_f2c_run_novel_view(self._h, self.ctx._h, int(level), 1 if fused_result else 0, c_t, c_ex, T, C.byref(params),
