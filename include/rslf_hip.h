@@ -214,6 +214,25 @@ int rslf_planes_undilate_u(rslf_ctx* ctx, const void* d_in, int elem_bytes, size
  * no device.  Also refuses a stride shorter than its row. */
 int rslf_planes_undilate_u_host(const void* h_in, size_t in_row_stride_bytes, int elem_bytes, size_t rows, int U_dilated, int factor,
                                 void* h_out, size_t out_row_stride_bytes);
+/* K18, what a fine-to-coarse level needs around a sweep in the dilated frame (the level dilation, below).
+ * The per-pixel ranges dmin, dmax [rows][U] in the dilated frame, [rows][U'], dense: column i * factor + p takes
+ * dmin[i] and dmax[i] bit for bit when p == 0, else fminf(dmin[i], dmin[i + 1]) and fmaxf(dmax[i], dmax[i + 1]) -- the
+ * union of the two neighbours' ranges, so no hypothesis either allowed is lost; of two equal values (-0.0f, +0.0f) the left
+ * one's bits, and a NaN loses to a number (csrc/k18_ranges_rule.hpp).  Both planes in one launch, enqueued on the context's
+ * stream, not awaited.  RSLF_ERR_INVALID_ARG: NULL, an output plane that is an input plane or the other output, U < 1, factor
+ * outside 1..8; RSLF_ERR_UNSUPPORTED: U' does not fit a row. */
+int rslf_planes_dilate_ranges_u(rslf_ctx* ctx, const float* d_dmin, const float* d_dmax, size_t rows, int U, int factor,
+                                float* d_dmin_out, float* d_dmax_out);
+/* The same on host pointers, rows `*_row_stride_bytes` apart (0: dense; a multiple of 4): a loop on the calling thread, no
+ * context, no device.  Also refuses a stride shorter than its row. */
+int rslf_planes_dilate_ranges_u_host(const float* h_dmin, const float* h_dmax, size_t in_row_stride_bytes, size_t rows, int U,
+                                     int factor, float* h_dmin_out, float* h_dmax_out, size_t out_row_stride_bytes);
+/* rslf_planes_undilate_u for n_planes planes of the same rows and widths in ONE launch: d_out[k][r][u] =
+ * d_in[k][r][u * factor], plane k of elem_bytes[k] (1 or 4) bytes per element; at most 8 planes of 4-byte and 2 of 1-byte
+ * elements.  d_in, d_out and elem_bytes are HOST arrays, read before the return.  Enqueued, not awaited.  Refusals:
+ * rslf_planes_undilate_u's per plane, more planes than that, an output plane that is any input or another output. */
+int rslf_planes_undilate_many_u(rslf_ctx* ctx, const void* const* d_in, void* const* d_out, const int* elem_bytes, int n_planes,
+                                size_t rows, int U_dilated, int factor);
 
 /* ---- derivative channels (K17; not in the reference's code: the second lead of its report) ---- */
 /* Every level down the pyramid, the Gaussian and the halving erase fine texture, and the edge confidence of the coarse
@@ -1114,6 +1133,32 @@ int rslf_f2c_run_host_dv(rslf_ctx* ctx, const void* const* h_epis, int elem, int
                          int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
                          rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio, float propagation_ratio,
                          float consistency_tol, int consistency_radius, int consistency_min_agree, float derivative_weight);
+/* The level dilation (K18; not in the reference): level_dilation = f in 2..8 runs every level's SWEEP on the level's packed
+ * volume dilated along u (rslf_volume_dilate_u, kind dilation_kind, the clamp range the packed volume's), U' = f (U_l - 1) + 1
+ * wide, with the level's ranges by rslf_planes_dilate_ranges_u and slope_factor = (float)(U_l / U_0) * (float)f, one binary32
+ * product.  The dilation never enters the level chain: the raw levels are uploaded, given derivative channels, normalised
+ * and downsampled as ever.  The level's planes -- depth, C_e, C_d and the four peak planes -- are the columns u * f of the
+ * sweep's, brought back in one launch before anything reads them, so the validity rules, the uniqueness ratio, the
+ * consistency gate, the bound tightening, the fusion, the fused peaks, levels_out and a kept run's planes, volumes
+ * (undilated) and getters all work on the level's own grid at slope U_l / U_0.  stats.pixels_scanned and a level's withheld
+ * count what the sweeps did, in the dilated frame.  level_dilation = 1 is the narrower entry, launch for launch and bit
+ * for bit (the kind is still checked).  The two entries are the fullest of their families plus the two arguments.
+ * RSLF_ERR_INVALID_ARG, before a device is touched: level_dilation outside 1..8, an unknown dilation_kind;
+ * RSLF_ERR_UNSUPPORTED: level_dilation > 1 together with a line-confidence mode (K7 takes no slope factor). */
+int rslf_fine_to_coarse_run_host_dl(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                    float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                    int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid, float derivative_weight,
+                                    int level_dilation, int dilation_kind);
+int rslf_f2c_run_host_dl(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                         int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                         rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio, float propagation_ratio,
+                         float consistency_tol, int consistency_radius, int consistency_min_agree, float derivative_weight,
+                         int level_dilation, int dilation_kind);
+/* The two read back (each pointer nullable): 1 and RSLF_DILATE_CUBIC for NULL and for a run made without the dilation. */
+int rslf_f2c_run_level_dilation(const rslf_f2c_run* run, int* factor, int* kind);
 /* The options read back (each pointer nullable): zeros for NULL and for a run made without the gate. */
 int rslf_f2c_run_consistency_gate(const rslf_f2c_run* run, float* tol, int* radius, int* min_agree);
 /* The pixels the gate made invalid on `level`: 0 for a level accepted whole and for every level of a run made without the

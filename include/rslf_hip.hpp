@@ -1227,14 +1227,34 @@ public:
         detail::require(mode >= RSLF_LINE_CONF_OFF && mode <= RSLF_LINE_CONF_GATE, "line confidence mode: RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE");
         line_mode_ = mode;
     }
-    // The dilation along u (Depth2DComputer::set_u_dilation) is not built for the pyramid -- its levels would need a decision
-    // about uchar arithmetic in dilated levels and about the width the pyramid starts from: any factor but 1 throws.
+    // The dilation along u (Depth2DComputer::set_u_dilation) is not built for the pyramid's LEVELS -- they would need a decision
+    // about uchar arithmetic in dilated levels and about the width the pyramid starts from: any factor but 1 throws.  The
+    // pyramid's form is set_level_dilation below, which dilates each level's sweep alone.
     void set_u_dilation(int factor, int kind = RSLF_DILATE_CUBIC)
     {
         (void)kind;
         if (factor != 1)
             throw std::invalid_argument("set_u_dilation: the dilation along u is not built for FineToCoarse (one level: Depth1DComputer_pile, Depth2DComputer)");
     }
+    // Not in the reference's code (its report's fourth lead), to be called before run(): the level dilation
+    // (rslf_fine_to_coarse_run_host_dl, rslf_f2c_run_host_dl; rslf_hip.h "the level dilation").  Every level's SWEEP runs on the
+    // level's volume dilated along u by `factor` (1..8, kernel `kind`) with the slope factor times the factor, and its planes
+    // come back to the level's own grid before anything reads them: every result of this object keeps its shape, and the
+    // level chain is untouched.  1 switches it off.  Any other factor throws on a MultiContext (one device); a
+    // line-confidence mode together with it is refused by run().
+    void set_level_dilation(int factor, int kind = RSLF_DILATE_CUBIC)
+    {
+        if (factor < 1 || factor > 8)
+            throw std::invalid_argument("set_level_dilation: a factor in 1..8");
+        if (kind != RSLF_DILATE_LINEAR && kind != RSLF_DILATE_CUBIC && kind != RSLF_DILATE_LANCZOS3)
+            throw std::invalid_argument("set_level_dilation: RSLF_DILATE_LINEAR, RSLF_DILATE_CUBIC or RSLF_DILATE_LANCZOS3");
+        if (factor != 1 && multi_)
+            throw std::invalid_argument("set_level_dilation: this object was built on a MultiContext: the level dilation is built for one context");
+        level_dilation_ = factor;
+        level_dilation_kind_ = kind;
+    }
+    int get_level_dilation() const { return level_dilation_; }
+    int get_level_dilation_kind() const { return level_dilation_kind_; }
     // Not in the reference's code (its report's second lead), to be called before run(): the derivative channels
     // (rslf_fine_to_coarse_run_host_dv, rslf_f2c_run_host_dv; rslf_hip.h "derivative channels").  A one-channel field goes down
     // the pyramid as (x, min(|dx/du| * weight / 2, hi), min(|dx/dv| * weight / 2, hi)), made once on the device from the
@@ -1500,11 +1520,11 @@ public:
             return;
         }
         // the family's widest entry, which takes any element type: no mode, no levels out
-        check(rslf_fine_to_coarse_run_host_dv(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+        check(rslf_fine_to_coarse_run_host_dl(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
                                               out_validity_s_v_u_.data(), &n_levels_, &stats, RSLF_LINE_CONF_OFF, nullptr, 0,
-                                              derivative_weight_),
-              "rslf_fine_to_coarse_run_host_dv");
+                                              derivative_weight_, level_dilation_, level_dilation_kind_),
+              "rslf_fine_to_coarse_run_host_dl");
     }
     void get_results(std::vector<float>& out_map_s_v_u, std::vector<uint8_t>& out_validity_s_v_u) const
     {
@@ -1638,11 +1658,11 @@ private:
         detail::require(peaks_ || propagation_ratio_ == 0.f, "FineToCoarse: the propagation ratio reads the peak planes: call set_peaks(true)");
         gate_held_ = false;
         // the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's (rslf_hip.h)
-        check(rslf_f2c_run_host_dv(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
+        check(rslf_f2c_run_host_dl(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
                                    &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
                                    keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, peaks_ ? 1 : 0, uniqueness_, propagation_ratio_,
-                                   gate_tol_, gate_radius_, gate_min_agree_, derivative_weight_),
-              "rslf_f2c_run_host_dv");
+                                   gate_tol_, gate_radius_, gate_min_agree_, derivative_weight_, level_dilation_, level_dilation_kind_),
+              "rslf_f2c_run_host_dl");
         peaks_held_ = peaks_;
         gate_held_ = gate_min_agree_ > 0;
         rslf_f2c_run_desc d;
@@ -1723,10 +1743,11 @@ private:
         lo.h_Cl_svu = hl.data();
         lo.h_Ce_svu = nullptr;
         // the family's widest entry, which takes any element type
-        check(rslf_fine_to_coarse_run_host_dv(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+        check(rslf_fine_to_coarse_run_host_dl(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
-                                              out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo, subgrid_ ? 1 : 0, derivative_weight_),
-              "rslf_fine_to_coarse_run_host_dv");
+                                              out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo, subgrid_ ? 1 : 0, derivative_weight_,
+                                              level_dilation_, level_dilation_kind_),
+              "rslf_fine_to_coarse_run_host_dl");
     }
     int elem() const { return type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32; }
 #ifdef RSLFX_HAVE_OPENCV
@@ -1766,6 +1787,7 @@ private:
     float gate_tol_ = 0.f;
     bool gate_held_ = false;     // the kept run was made with the consistency gate
     float derivative_weight_ = 0.f;   // set_derivative_channels
+    int level_dilation_ = 1, level_dilation_kind_ = RSLF_DILATE_CUBIC;   // set_level_dilation
     int validity_rule_;
     rslf_f2c_run* run_;          // the kept run, owned
 };

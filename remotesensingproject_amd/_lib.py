@@ -75,6 +75,9 @@ SYMBOLS = [
     "rslf_dilated_width", "rslf_volume_dilate_u", "rslf_planes_undilate_u", "rslf_planes_undilate_u_host",
     # the derivative channels: a one-channel field as (x, |dx/du|, |dx/dv|), and the pyramid on it (K17)
     "rslf_volume_derivative_channels", "rslf_derivative_channels_dense", "rslf_fine_to_coarse_run_host_dv", "rslf_f2c_run_host_dv",
+    # the level dilation: every level's sweep of the pyramid on EPIs dilated along u (K18)
+    "rslf_planes_dilate_ranges_u", "rslf_planes_dilate_ranges_u_host", "rslf_planes_undilate_many_u", "rslf_fine_to_coarse_run_host_dl",
+    "rslf_f2c_run_host_dl", "rslf_f2c_run_level_dilation",
 ]
 
 
@@ -365,6 +368,9 @@ def lib():
     L.rslf_f2c_run_host_cs.argtypes = L.rslf_f2c_run_host_pr.argtypes + [cf, ci, ci]
     L.rslf_f2c_run_host_dv.argtypes = L.rslf_f2c_run_host_cs.argtypes + [cf]
     L.rslf_fine_to_coarse_run_host_dv.argtypes = L.rslf_fine_to_coarse_run_host_sub.argtypes + [cf]
+    L.rslf_f2c_run_host_dl.argtypes = L.rslf_f2c_run_host_dv.argtypes + [ci, ci]
+    L.rslf_fine_to_coarse_run_host_dl.argtypes = L.rslf_fine_to_coarse_run_host_dv.argtypes + [ci, ci]
+    L.rslf_f2c_run_level_dilation.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     L.rslf_volume_derivative_channels.argtypes = [vp, vp, cf, C.POINTER(vp)]
     L.rslf_derivative_channels_dense.argtypes = [vp, vp, ci, ci, ci, ci, cf, cf, vp]
     L.rslf_f2c_run_consistency_gate.argtypes = [vp, C.POINTER(cf), C.POINTER(ci), C.POINTER(ci)]
@@ -384,6 +390,9 @@ def lib():
     L.rslf_volume_dilate_u.argtypes = [vp, vp, ci, ci, C.POINTER(vp)]
     L.rslf_planes_undilate_u.argtypes = [vp, vp, ci, C.c_size_t, ci, ci, vp]
     L.rslf_planes_undilate_u_host.argtypes = [vp, C.c_size_t, ci, C.c_size_t, ci, ci, vp, C.c_size_t]
+    L.rslf_planes_dilate_ranges_u.argtypes = [vp, vp, vp, C.c_size_t, ci, ci, vp, vp]
+    L.rslf_planes_dilate_ranges_u_host.argtypes = [vp, vp, C.c_size_t, C.c_size_t, ci, ci, vp, vp, C.c_size_t]
+    L.rslf_planes_undilate_many_u.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), ci, C.c_size_t, ci, ci]
     L.rslf_f2c_run_peaks.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.argtypes = [vp]
     L.rslf_f2c_run_uniqueness.restype = cf

@@ -45,7 +45,8 @@ UNITS = {
                              "rslf_plan_f2c_consistency.hpp"] + STACK_OP,
     "rslf_warp.hip": ["k14_view_warp.hpp", "k12_consistency_rule.hpp"] + STACK_OP,
     "rslf_novel.hip": ["k15_novel_view.hpp", "k15_novel_rule.hpp", "rslf_plan_novel.hpp", "k12_consistency_rule.hpp"] + STACK_OP,
-    "rslf_dilate.hip": ["k16_dilate.hpp", "k16_dilate_rule.hpp", "rslf_plan_dilate.hpp"],
+    "rslf_dilate.hip": ["k16_dilate.hpp", "k16_dilate_rule.hpp", "rslf_plan_dilate.hpp", "k18_level_dilate.hpp", "k18_ranges_rule.hpp",
+                        "rslf_plan_level_dilate.hpp"],
     "rslf_derivative.hip": ["k17_derivative.hpp", "k17_derivative_rule.hpp", "rslf_plan_derivative.hpp"],
     "rslf_multi.hip": [],
     "rslf_multi_sweep.hip": [],

@@ -3,6 +3,7 @@
 // form is here and whose multi-device form is in rslf_multi_sweep.hip.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
 #include "rslf_plan_derivative.hpp"
+#include "rslf_plan_dilate.hpp"
 #include "rslf_plan_f2c_consistency.hpp"
 #include "rslf_plan_f2c_peaks.hpp"
 
@@ -287,6 +288,19 @@ static int f2c_valid_mask(hipStream_t st, const float* conf, uint8_t* out, size_
     return RSLF_OK;
 }
 
+// The level dilation runs the sweeps' frame alone; K7 samples C_e along u + (s_hat - s) * d with no slope factor.
+int rslf::check_level_dilation(const F2cOptions& o)
+{
+    if (!dilate_factor_ok(o.level_dilation))
+        return fail(RSLF_ERR_INVALID_ARG, "level_dilation=%d: an integer in 1..%d", o.level_dilation, kDilateMaxFactor);
+    if (!dilate_kind_ok(o.dilation_kind))
+        return fail(RSLF_ERR_INVALID_ARG, "dilation_kind=%d: RSLF_DILATE_LINEAR, RSLF_DILATE_CUBIC or RSLF_DILATE_LANCZOS3", o.dilation_kind);
+    if (o.level_dilation > 1 && o.line_mode != RSLF_LINE_CONF_OFF)
+        return fail(RSLF_ERR_UNSUPPORTED, "level_dilation=%d together with line confidence mode %d is not built (the line confidence "
+                    "takes no slope factor)", o.level_dilation, o.line_mode);
+    return RSLF_OK;
+}
+
 int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& o, const F2cHostOut& out, rslf_stats* stats,
                          F2cKept* keep, const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep)
 {
@@ -309,6 +323,8 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions&
         return fail(RSLF_ERR_INVALID_ARG, "validity rule %d: RSLF_F2C_VALID_COMPAT or, for a kept run, _REFERENCE", o.validity_rule);
     if (!plan::line_conf_mode_ok(o.line_mode))
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", o.line_mode);
+    if (int rc = check_level_dilation(o))
+        return rc;
     int rc = check_params(p);
     if (rc)
         return rc;
@@ -542,10 +558,15 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const
     auto sweep = [&](const F2cLevel& lv, rslf_stats* level_stats) -> int {
         if (inject_hit(kInjectSweep))   // host side, before the level's sweep is queued
             throw std::runtime_error("injected failure in a fine-to-coarse level (rslf_debug_inject)");
-        const size_t n = (size_t)S * lv.V * lv.U;
+        const int f = o.level_dilation;
+        int Ud = lv.U;   // the width of the sweep's frame: U' = f (U_l - 1) + 1 with the level dilation, else the level's
+        if (f > 1 && plan::dilated_width(lv.U, f, &Ud) != plan::kDilateOk)
+            return fail(RSLF_ERR_UNSUPPORTED, "U=%d dilated by %d does not fit a row", lv.U, f);
+        const size_t rows = (size_t)S * lv.V;
+        const size_t n = rows * Ud;
         const int C = lv.C;   // (the request's, or 3 with the derivative channels)
         DevBuf Cd, rbar, mask;
-        if (!lv.Cd_svu)   // a kept run's C_d is its owner's
+        if (!lv.Cd_svu || f > 1)   // a kept run's C_d is its owner's (on the level's grid)
             HIP_TRY(Cd.alloc(n * 4));
         HIP_TRY(rbar.alloc(n * 4 * C));
         HIP_TRY(mask.alloc(n));
@@ -555,11 +576,67 @@ int rslf::fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const
         vol.reset(made);
         if (!rc)
             rc = rslf_volume_pack_device_f32(vol.get(), lv.raw_vsuc, lv.scale, nullptr);
-        const SweepPlanes planes = {lv.Ce_svu, mask.as<uint8_t>(), lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(),
-                                    nullptr};
         SweepModes modes;
         modes.line_mode = o.line_mode, modes.Cl_svu = lv.Cl_svu, modes.subgrid = o.subgrid;
         modes.peaks = lv.peaks, modes.propagation_ratio = o.propagation_ratio;
+        if (f > 1) {
+            // The level dilation: the sweep alone runs in the dilated frame.  Its volume is the level's packed volume dilated
+            // (K16; the clamp range is the packed volume's), its ranges the level's by the union rule (K18), its slope factor the
+            // level's times f in one binary32 product; the planes the loop reads are the columns u * f of the sweep's.
+            VolumePtr vol_d;
+            rslf_volume* dilated = nullptr;
+            if (!rc)
+                rc = rslf_volume_dilate_u(ctx, vol.get(), f, o.dilation_kind, &dilated);
+            vol_d.reset(dilated);
+            DevBuf Ce_d, depth_d, dmin_d, dmax_d, pk_d[4];
+            HIP_TRY(Ce_d.alloc(n * 4));
+            HIP_TRY(depth_d.alloc(n * 4));
+            if (lv.dmin_svu) {
+                HIP_TRY(dmin_d.alloc(n * 4));
+                HIP_TRY(dmax_d.alloc(n * 4));
+                if (!rc)
+                    rc = rslf_planes_dilate_ranges_u(ctx, lv.dmin_svu, lv.dmax_svu, rows, lv.U, f, dmin_d.as<float>(), dmax_d.as<float>());
+            }
+            rslf_peaks pk_planes = {};
+            if (lv.peaks) {
+                for (DevBuf& b : pk_d)
+                    HIP_TRY(b.alloc(n * 4));
+                pk_planes = rslf_peaks{pk_d[0].as<int32_t>(), pk_d[1].as<float>(), nullptr, pk_d[2].as<int32_t>(), pk_d[3].as<float>()};
+                modes.peaks = &pk_planes;
+            }
+            rslf_params params = lv.params;
+            params.slope_factor = lv.params.slope_factor * (float)f;   // (no contraction: one product, rounded once)
+            const SweepPlanes planes = {Ce_d.as<float>(), mask.as<uint8_t>(), Cd.as<float>(), depth_d.as<float>(), rbar.as<float>(), nullptr};
+            if (!rc)
+                rc = depth2d_run(ctx, vol_d.get(), lv.dmin_svu ? dmin_d.as<const float>() : nullptr, lv.dmin_svu ? dmax_d.as<const float>() : nullptr,
+                                 req.d_min, req.d_max, req.dim_d, &params, planes, level_stats, modes);
+            if (!rc && o.propagation_ratio > 0.0f && lv.withheld)
+                rc = rslf_sweep_withheld(ctx, lv.withheld);
+            // back to the level's grid in one launch: depth, C_e, C_d (a kept run's) and the four peak planes
+            const void* in[8];
+            void* back[8];
+            int bytes[8], np = 0;
+            const auto add = [&](const void* from, void* to) {
+                if (to)
+                    in[np] = from, back[np] = to, bytes[np] = 4, ++np;
+            };
+            add(depth_d.get(), lv.depth_svu);
+            add(Ce_d.get(), lv.Ce_svu);
+            add(Cd.get(), lv.Cd_svu);
+            if (lv.peaks) {
+                add(pk_d[0].get(), lv.peaks->idx);
+                add(pk_d[1].get(), lv.peaks->score);
+                add(pk_d[2].get(), lv.peaks->runner_idx);
+                add(pk_d[3].get(), lv.peaks->runner_score);
+            }
+            if (!rc)
+                rc = rslf_planes_undilate_many_u(ctx, in, back, bytes, np, rows, Ud, f);
+            if (!rc && lv.vol_out)
+                *lv.vol_out = std::move(vol);   // the undilated level; the dilated volume and the sweep's planes are destroyed here
+            return rc;
+        }
+        const SweepPlanes planes = {lv.Ce_svu, mask.as<uint8_t>(), lv.Cd_svu ? lv.Cd_svu : Cd.as<float>(), lv.depth_svu, rbar.as<float>(),
+                                    nullptr};
         if (!rc)
             rc = depth2d_run(ctx, vol.get(), lv.dmin_svu, lv.dmax_svu, req.d_min, req.d_max, req.dim_d, &lv.params, planes, level_stats, modes);
         if (!rc && o.propagation_ratio > 0.0f && lv.withheld)
@@ -673,6 +750,27 @@ extern "C" int rslf_fine_to_coarse_run_host_dv(rslf_ctx* ctx, const void* const*
                             accept_all_last_scale};
     F2cOptions options;
     options.line_mode = line_mode, options.subgrid = subgrid, options.derivative_weight = derivative_weight;
+    return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
+}
+RSLF_API_CATCH
+
+// ... and with level_dilation > 1 every level's sweep runs on the level's volume dilated along u (K16) and its planes come
+// back to the level's own grid (K18); 1: the narrower entry's call
+extern "C" int rslf_fine_to_coarse_run_host_dl(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                               size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                               const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                               float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                               int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid,
+                                               float derivative_weight, int level_dilation, int dilation_kind) RSLF_API_TRY
+{
+    Elem e;
+    if (int rc = elem_of(elem, &e))
+        return rc;
+    const F2cRequest req = {e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions options;
+    options.line_mode = line_mode, options.subgrid = subgrid, options.derivative_weight = derivative_weight;
+    options.level_dilation = level_dilation, options.dilation_kind = dilation_kind;
     return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
 }
 RSLF_API_CATCH

@@ -310,6 +310,8 @@ static int f2c_run_host(rslf_ctx* ctx, int elem, F2cRequest req, const F2cOption
     case plan::kF2cConsistencyBadTol:
         return fail(RSLF_ERR_INVALID_ARG, "consistency_tol=%g: a finite tolerance >= 0", (double)o.cs_tol);
     }
+    if (int rc = check_level_dilation(o))
+        return rc;
     // (the level's sweeps would end a sweep the caller left open; the entries without the gate do what they always did)
     if (o.cs_min_agree > 0 && ctx->sweep.open)
         return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree: a sweep is open on this context");
@@ -435,6 +437,37 @@ extern "C" int rslf_f2c_run_host_dv(rslf_ctx* ctx, const void* const* h_epis, in
     o.cs_tol = consistency_tol, o.cs_radius = consistency_radius, o.cs_min_agree = consistency_min_agree;
     o.derivative_weight = derivative_weight;
     return f2c_run_host(ctx, elem, req, o, run, stats);
+}
+RSLF_API_CATCH
+
+// ... and with level_dilation > 1 every level's sweep in the frame dilated along u, its planes back on the level's grid (K18)
+extern "C" int rslf_f2c_run_host_dl(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
+                                    int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
+                                    float uniqueness_ratio, float propagation_ratio, float consistency_tol, int consistency_radius,
+                                    int consistency_min_agree, float derivative_weight, int level_dilation, int dilation_kind) RSLF_API_TRY
+{
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
+    o.peaks = peaks, o.uniqueness = uniqueness_ratio, o.propagation_ratio = propagation_ratio;
+    o.cs_tol = consistency_tol, o.cs_radius = consistency_radius, o.cs_min_agree = consistency_min_agree;
+    o.derivative_weight = derivative_weight;
+    o.level_dilation = level_dilation, o.dilation_kind = dilation_kind;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
+}
+RSLF_API_CATCH
+
+// the level dilation a run was made with (each pointer nullable): 1 and RSLF_DILATE_CUBIC for NULL and for a run made without it
+extern "C" int rslf_f2c_run_level_dilation(const rslf_f2c_run* run, int* factor, int* kind) RSLF_API_TRY
+{
+    if (factor)
+        *factor = run ? run->options.level_dilation : 1;
+    if (kind)
+        *kind = run ? run->options.dilation_kind : RSLF_DILATE_CUBIC;
+    return RSLF_OK;
 }
 RSLF_API_CATCH
 

@@ -591,6 +591,8 @@ struct F2cOptions {
     int cs_radius = 0, cs_min_agree = 0;            // level's rule and uniqueness, a valid pixel the other views contradict becomes invalid
     float derivative_weight = 0.0f;                 // > 0: a one-channel field goes down the pyramid as (x, |dx/du|, |dx/dv|) by this weight (K17,
                                                     // rslf_*_run_host_dv): three channels from the finest level's upload on
+    int level_dilation = 1;                         // > 1: every level's SWEEP runs on the level's volume dilated along u by this factor (K16) and
+    int dilation_kind = RSLF_DILATE_CUBIC;          // its planes come back to the level's own grid (K18; rslf_*_run_host_dl); the level chain is untouched
 };
 // The host outputs of a pyramid, each nullable: the fused planes, the depth, every level's planes.
 struct F2cHostOut {
@@ -644,6 +646,8 @@ struct F2cKept {
 // NULL.  With every option off, the loop queues what it always did.
 int fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& options, const F2cHostOut& out, rslf_stats* stats,
                    F2cKept* keep, const std::function<int(const F2cLevel& level, rslf_stats* level_stats)>& sweep);
+// What every pyramid entry refuses of the level dilation before a device is touched: the factor, the kind, a line mode with it.
+int check_level_dilation(const F2cOptions& options);
 // The loop on one context: each level a volume of its own, packed from the raw level and swept by depth2d_run.
 int fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions& options, const F2cHostOut& out,
                                rslf_stats* stats, F2cKept* keep);

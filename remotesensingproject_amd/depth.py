@@ -158,8 +158,9 @@ def _u_dilation(u_dilation, dilation_kind, who: str) -> tuple[int, int]:
 
 def require_no_u_dilation(u_dilation, who: str) -> None:
     """The dilation along u (DESIGN.md 3 "K16") is built for one device and one level: Depth1DComputer_pile, Depth1DComputer
-    and Depth2DComputer.  The pyramid needs a decision about uchar arithmetic in dilated levels and about start_dim_u, and
-    every multi-device or sharded form would have to dilate per chunk: they refuse it instead of ignoring it."""
+    and Depth2DComputer.  The pyramid's levels are never dilated -- its form is the level dilation, which dilates each
+    level's sweep alone (level_dilation=, DESIGN.md 3 "K18") -- and every multi-device or sharded form would have to dilate
+    per chunk: they refuse it instead of ignoring it."""
     if u_dilation is not None and u_dilation != 1:
         raise ValueError("%s: u_dilation=%r is not built here (one device, one level: Depth1DComputer_pile, Depth1DComputer, "
                          "Depth2DComputer; or Volume.dilated_u and a slope factor of your own)" % (who, u_dilation))
@@ -179,6 +180,33 @@ def _dilated_parameters(parameters: "Depth1DParameters", factor: int) -> "Depth1
     p = copy.copy(parameters)
     p.par_slope_factor = float(np.float32(parameters.par_slope_factor) * np.float32(factor))
     return p
+
+
+def _level_dilation(level_dilation, level_dilation_kind, who: str) -> tuple[int, int]:
+    """(factor, kind) of the level_dilation / level_dilation_kind arguments of the pyramid forms: an integer in 1..8, a
+    DILATE_*."""
+    f = 1 if level_dilation is None else level_dilation
+    if isinstance(f, (bool, np.bool_)) or not isinstance(f, (int, np.integer)) or not 1 <= int(f) <= DILATE_MAX_FACTOR:
+        raise ValueError("%s: level_dilation %r is not an integer in 1..%d" % (who, level_dilation, DILATE_MAX_FACTOR))
+    if isinstance(level_dilation_kind, (bool, np.bool_)) or level_dilation_kind not in (DILATE_LINEAR, DILATE_CUBIC, DILATE_LANCZOS3):
+        raise ValueError("%s: level_dilation_kind %r is not DILATE_LINEAR, DILATE_CUBIC or DILATE_LANCZOS3" % (who, level_dilation_kind))
+    return int(f), int(level_dilation_kind)
+
+
+def require_no_level_dilation(level_dilation, who: str) -> None:
+    """The level dilation (DESIGN.md 3 "K18") is built for one device: fine_to_coarse_run_host and FineToCoarse.  A
+    multi-device or sharded form would have to dilate every chunk of every level: they refuse it instead of ignoring it."""
+    if level_dilation is not None and level_dilation != 1:
+        raise ValueError("%s: level_dilation=%r is not built here (one device: fine_to_coarse_run_host, FineToCoarse)"
+                         % (who, level_dilation))
+
+
+def require_no_line_confidence_level_dilated(line_mode, level_dilation: int, who: str) -> None:
+    """K7 samples C_e along u + (s_hat - s) * d with no slope factor (core.hpp:1058): in a level's dilated frame it would
+    walk the wrong line."""
+    if level_dilation != 1 and line_mode is not None and int(line_mode) != LINE_CONF_OFF:
+        raise ValueError("%s: line confidence mode %d together with level_dilation=%d is not built (the line confidence takes "
+                         "no slope factor)" % (who, int(line_mode), level_dilation))
 
 
 def _derivative_weight(derivative_channels, who: str) -> float:
@@ -478,6 +506,58 @@ def undilate_u(ctx: Context, planes: torch.Tensor, factor: int) -> torch.Tensor:
     check(_lib.lib().rslf_planes_undilate_u(ctx._h, _ptr(t), t.element_size(), t.numel() // Ud, Ud, factor, _ptr(out)),
           "rslf_planes_undilate_u")
     return out
+
+
+def undilate_many_u(ctx: Context, planes: Sequence[torch.Tensor], factor: int) -> list:
+    """undilate_u for several planes of the same shape in ONE launch (rslf_planes_undilate_many_u): at most 8 float32 /
+    int32 and 2 uint8 CUDA tensors, any leading dimensions, last dimension factor * (U - 1) + 1.  Returns new dense tensors
+    in the planes' order."""
+    factor, _ = _u_dilation(factor, DILATE_CUBIC, "undilate_many_u")
+    planes = list(planes)
+    if not planes:
+        raise ValueError("undilate_many_u: no planes")
+    shape = tuple(planes[0].shape)
+    for t in planes:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.float32, torch.int32):
+            raise ValueError("undilate_many_u needs uint8, float32 or int32 CUDA tensors")
+        if tuple(t.shape) != shape:
+            raise ValueError("undilate_many_u: planes of different shapes, %s and %s" % (shape, tuple(t.shape)))
+    if len(shape) < 1 or shape[-1] < 1 or (shape[-1] - 1) % factor != 0:
+        raise ValueError("undilate_many_u: the last dimension %s is not factor * (U - 1) + 1 for factor=%d"
+                         % (shape[-1] if shape else None, factor))
+    n4, n1 = sum(t.element_size() == 4 for t in planes), sum(t.element_size() == 1 for t in planes)
+    if n4 > 8 or n1 > 2:
+        raise ValueError("undilate_many_u: %d planes of 4-byte and %d of 1-byte elements: at most 8 and 2 in one call" % (n4, n1))
+    src = [t.contiguous() for t in planes]
+    Ud = shape[-1]
+    outs = [torch.empty(shape[:-1] + ((Ud - 1) // factor + 1,), dtype=t.dtype, device=t.device) for t in src]
+    n = len(src)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_planes_undilate_many_u(ctx._h, (C.c_void_p * n)(*[t.data_ptr() for t in src]),
+                                                 (C.c_void_p * n)(*[t.data_ptr() for t in outs]),
+                                                 (C.c_int * n)(*[t.element_size() for t in src]), n, src[0].numel() // Ud, Ud, factor),
+          "rslf_planes_undilate_many_u")
+    return outs
+
+
+def dilate_ranges_u(ctx: Context, dmin: torch.Tensor, dmax: torch.Tensor, factor: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Per-pixel hypothesis ranges [..., U] in the frame dilated along u, [..., factor * (U - 1) + 1], on the device
+    (rslf_planes_dilate_ranges_u, K18): column i * factor takes column i's range bit for bit, the columns between i and
+    i + 1 the union of the two neighbours' ranges.  float32 CUDA tensors of one shape."""
+    factor, _ = _u_dilation(factor, DILATE_CUBIC, "dilate_ranges_u")
+    for t in (dmin, dmax):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise ValueError("dilate_ranges_u needs float32 CUDA tensors")
+    if tuple(dmin.shape) != tuple(dmax.shape) or dmin.dim() < 1 or dmin.shape[-1] < 1:
+        raise ValueError("dilate_ranges_u: dmin %s and dmax %s are not two planes of one shape" % (tuple(dmin.shape), tuple(dmax.shape)))
+    lo, hi = dmin.contiguous(), dmax.contiguous()
+    U = lo.shape[-1]
+    shape = tuple(lo.shape[:-1]) + (factor * (U - 1) + 1,)
+    out_lo, out_hi = torch.empty(shape, dtype=torch.float32, device=lo.device), torch.empty(shape, dtype=torch.float32, device=lo.device)
+    ctx.use_current_stream()
+    check(_lib.lib().rslf_planes_dilate_ranges_u(ctx._h, _ptr(lo), _ptr(hi), lo.numel() // U, U, factor, _ptr(out_lo), _ptr(out_hi)),
+          "rslf_planes_dilate_ranges_u")
+    return out_lo, out_hi
 
 
 def _undilated(who: str, planes: dict, name: str, vol: "Volume", channels_last=()) -> torch.Tensor:
@@ -1153,7 +1233,7 @@ class MultiDevice:
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                        subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1,
-                       *, derivative_channels: float = 0.0):
+                       *, level_dilation: int = 1, derivative_channels: float = 0.0):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
@@ -1162,6 +1242,7 @@ class MultiDevice:
         require_no_consistency_gate(consistency_min_agree, "MultiDevice.fine_to_coarse")
         require_no_u_dilation(u_dilation, "MultiDevice.fine_to_coarse")
         require_no_derivative_channels(derivative_channels, "MultiDevice.fine_to_coarse")
+        require_no_level_dilation(level_dilation, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
         out_valid = np.empty((S, V, U), np.uint8)
@@ -2185,6 +2266,10 @@ class KeptFineToCoarse:
         check(_lib.lib().rslf_f2c_run_consistency_gate(self._h, C.byref(tol), C.byref(radius), C.byref(min_agree)), "rslf_f2c_run_consistency_gate")
         # (tol, radius, min_agree) of the validity by cross-view consistency, None: the run was made without it
         self.consistency_gate = (float(tol.value), int(radius.value), int(min_agree.value)) if min_agree.value else None
+        factor, kind = C.c_int(), C.c_int()
+        check(_lib.lib().rslf_f2c_run_level_dilation(self._h, C.byref(factor), C.byref(kind)), "rslf_f2c_run_level_dilation")
+        # (factor, kind) of the level dilation the sweeps ran with; (1, DILATE_CUBIC): none.  Every plane is on the level's grid
+        self.level_dilation = (int(factor.value), int(kind.value))
 
     def describe(self) -> "_lib.RslfF2cRunDesc":
         d = _lib.RslfF2cRunDesc()
@@ -2384,7 +2469,8 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                             validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None,
                             uniqueness_ratio: float | None = None, propagation_ratio: float | None = None,
                             consistency_min_agree: int | None = None, consistency_tol: float | None = None, consistency_radius: int = 0,
-                            u_dilation: int = 1, *, derivative_channels: float = 0.0):
+                            u_dilation: int = 1, *, level_dilation: int = 1, level_dilation_kind=DILATE_CUBIC,
+                            derivative_channels: float = 0.0):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
     and, with want_levels, `levels`: per level dict(depth, valid, line_confidence, edge_confidence), each [S,V_p,U_p]
@@ -2409,12 +2495,19 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     unless agree >= min(seen, m) among the other views (view_consistency's counts; consistency_radius > 0: only views within
     it), so a coarser level decides it.  consistency_tol=None: one step of the hypothesis grid.
     KeptFineToCoarse.consistency_gate, .inconsistent(level) and .get_gate_counts(level) read it back.
-    u_dilation: refused (require_no_u_dilation): the pyramid has no dilated levels.
+    u_dilation: refused (require_no_u_dilation): the pyramid has no dilated levels; see level_dilation.
     derivative_channels (not in the reference's code, its report's second lead; 0 or None: off, today's call; else a finite
     weight w > 0; one-channel fields only; rslf_fine_to_coarse_run_host_dv, rslf_f2c_run_host_dv): the finest level becomes
     (x, min(|dx/du| * w / 2, hi), min(|dx/dv| * w / 2, hi)) on the device and the pyramid runs on it as on a three-channel
-    field, bit for bit; a kept run describes itself with C = 3."""
+    field, bit for bit; a kept run describes itself with C = 3.
+    level_dilation (not in the reference's code, its report's fourth lead; 1: off, today's call; else an integer factor in
+    2..8, with level_dilation_kind a DILATE_*; rslf_fine_to_coarse_run_host_dl, rslf_f2c_run_host_dl): every level's SWEEP
+    runs on the level's volume dilated along u with slope factor U_l / U_0 * factor, and its planes come back to the level's
+    own grid before anything reads them: every result has the shapes it always had.  The level chain is untouched.  Not
+    together with a line mode.  KeptFineToCoarse.level_dilation reads it back."""
     require_no_u_dilation(u_dilation, "fine_to_coarse_run_host")
+    dl, dl_kind = _level_dilation(level_dilation, level_dilation_kind, "fine_to_coarse_run_host")
+    require_no_line_confidence_level_dilated(line_mode, dl, "fine_to_coarse_run_host")
     dv = _derivative_weight(derivative_channels, "fine_to_coarse_run_host")
     want_cs = consistency_min_agree is not None and consistency_min_agree is not False and consistency_min_agree != 0
     cs_tol, cs_radius, cs_min_agree = 0.0, 0, 0
@@ -2461,7 +2554,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                 int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
         # the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's
         more = (1 if subgrid else 0, 1 if want_peaks else 0, float(uniqueness_ratio or 0.0), gate, cs_tol, cs_radius, cs_min_agree)
-        if dv:
+        if dl != 1:
+            check(L.rslf_f2c_run_host_dl(*args, *more, dv, dl, dl_kind), "rslf_f2c_run_host_dl")
+        elif dv:
             check(L.rslf_f2c_run_host_dv(*args, *more, dv), "rslf_f2c_run_host_dv")
         else:
             check(L.rslf_f2c_run_host_cs(*args, *more), "rslf_f2c_run_host_cs")
@@ -2489,7 +2584,10 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
             C.byref(nl), C.byref(st), int(line_mode), C.byref(lo) if lo is not None else None)
     ctx.use_current_stream()
     # the family's widest entry, which takes any element type
-    if dv:
+    if dl != 1:
+        check(L.rslf_fine_to_coarse_run_host_dl(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0, dv, dl, dl_kind),
+              "rslf_fine_to_coarse_run_host_dl")
+    elif dv:
         check(L.rslf_fine_to_coarse_run_host_dv(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0, dv),
               "rslf_fine_to_coarse_run_host_dv")
     else:
@@ -2517,12 +2615,19 @@ class FineToCoarse:
 
     `derivative_channels` (not in the reference's code, its report's second lead; 0 or None: off; else a finite weight w > 0,
     one-channel fields only): the raw finest level becomes (x, min(|dx/du| * w / 2, hi), min(|dx/dv| * w / 2, hi)) on the
-    device (derivative_channels(), once, on f2c_input's output) and the loop runs on it as on any three-channel field."""
+    device (derivative_channels(), once, on f2c_input's output) and the loop runs on it as on any three-channel field.
+
+    `level_dilation` / `level_dilation_kind` (not in the reference's code, its report's fourth lead; 1: off; else a factor in
+    2..8 and a DILATE_*): run() sweeps every level on its volume dilated along u (Volume.dilated_u) with the slope factor
+    times the factor and the level's ranges by dilate_ranges_u, and writes the columns u * factor of the sweep's planes into
+    the level's computer: the computers and every getter keep answering on the level's own grid.  Not with a line mode."""
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                  ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None,
-                 propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1, *, derivative_channels: float = 0.0):
+                 propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1, *, level_dilation: int = 1,
+                 level_dilation_kind=DILATE_CUBIC, derivative_channels: float = 0.0):
+        self.m_level_dilation, self.m_level_dilation_kind = _level_dilation(level_dilation, level_dilation_kind, "FineToCoarse")
         # not in the reference: a one-channel field goes down the pyramid as (x, |dx/du|, |dx/dv|) by this weight (K17); 0: off
         self.m_derivative_channels = _derivative_weight(derivative_channels, "FineToCoarse")
         require_no_peaks(peaks, "FineToCoarse")   # (the pyramid's levels carry no peak planes)
@@ -2532,6 +2637,8 @@ class FineToCoarse:
         self.m_parameters = parameters or Depth1DParameters.get_default()
         self.m_subgrid = bool(subgrid)   # not in the reference: every level's sweep in the sub-grid mode (Depth2DComputer)
         f2c_line_mode(self.m_parameters, line_confidence_mode, "FineToCoarse")
+        require_no_line_confidence_level_dilated(line_confidence_mode if line_confidence_mode is not None
+                                                 else self.m_parameters.par_line_confidence_mode, self.m_level_dilation, "FineToCoarse")
         ctx = ctx or default_context()
         self.m_computers: list[Depth2DComputer] = []
         self.m_parameter_instances: list[Depth1DParameters] = []
@@ -2552,6 +2659,9 @@ class FineToCoarse:
     def run(self) -> None:
         """f2c.hpp:171-299."""
         for p, comp in enumerate(self.m_computers):
+            if self.m_level_dilation != 1:
+                self._run_level_dilated(p, comp)
+                continue
             if p == 0:
                 comp.run(want_stats=True)
                 continue
@@ -2569,6 +2679,33 @@ class FineToCoarse:
                                               comp.m_best_depth_s_v_u, comp.m_rbar_s_v_u, comp.m_parameters,
                                               scan_mask_s_v_u=comp.m_scan_mask_s_v_u, want_stats=True,
                                               a_line_confidence_s_v_u=comp.m_line_confidence_s_v_u, subgrid=self.m_subgrid)
+
+    def _run_level_dilated(self, p: int, comp: "Depth2DComputer") -> None:
+        """Level p's sweep in the frame dilated along u: a computer of its own on comp's volume (Volume.dilated_u, the slope
+        factor times the factor), the level's ranges by dilate_ranges_u, and the columns u * factor of its planes into comp."""
+        f, vol = self.m_level_dilation, comp.m_epis
+        dil = Depth2DComputer(vol, self._dmin, self._dmax, comp.m_dim_d, parameters=comp.m_parameters, subgrid=self.m_subgrid,
+                              u_dilation=f, dilation_kind=self.m_level_dilation_kind)
+        if p == 0:
+            dil.run(want_stats=True)
+        else:
+            up = self.m_computers[p - 1]
+            dmin, dmax = f2c_ranges(vol.ctx, up.m_best_depth_s_v_u, up.get_valid_depths_mask_s_v_u(), vol.V, vol.U, self._dmin, self._dmax)
+            comp.m_dmin_s_v_u, comp.m_dmax_s_v_u = dmin, dmax
+            dmin_d, dmax_d = dilate_ranges_u(vol.ctx, dmin, dmax, f)
+            for t in (dil.m_edge_confidence_s_v_u, dil.m_disp_confidence_s_v_u, dil.m_best_depth_s_v_u, dil.m_rbar_s_v_u):
+                t.zero_()
+            dil.m_edge_confidence_mask_s_v_u = compute_2D_edge_confidence(dil.m_epis, dil.m_edge_confidence_s_v_u, dil.m_parameters)
+            dil.stats = compute_2D_depth_epi(dil.m_epis, dmin_d, dmax_d, dil.m_dim_d, dil.m_edge_confidence_s_v_u,
+                                             dil.m_edge_confidence_mask_s_v_u, dil.m_disp_confidence_s_v_u, dil.m_best_depth_s_v_u,
+                                             dil.m_rbar_s_v_u, dil.m_parameters, scan_mask_s_v_u=dil.m_scan_mask_s_v_u,
+                                             want_stats=True, subgrid=self.m_subgrid)
+        (comp.m_best_depth_s_v_u, comp.m_edge_confidence_s_v_u, comp.m_disp_confidence_s_v_u, comp.m_edge_confidence_mask_s_v_u,
+         comp.m_scan_mask_s_v_u) = undilate_many_u(vol.ctx, [dil.m_best_depth_s_v_u, dil.m_edge_confidence_s_v_u,
+                                                             dil.m_disp_confidence_s_v_u, dil.m_edge_confidence_mask_s_v_u,
+                                                             dil.m_scan_mask_s_v_u], f)
+        comp.m_rbar_s_v_u = dil.undilated("rbar")
+        comp.stats = dil.stats   # (what the sweep did, in the dilated frame)
 
     def get_results(self):
         """f2c.hpp:302-324 -> (out_map_s_v_u [S,V,U] f32, out_validity_s_v_u [S,V,U] u8) at the finest scale."""
