@@ -264,6 +264,65 @@ int rslf_volume_derivative_channels(rslf_ctx* ctx, const rslf_volume* src, float
 int rslf_derivative_channels_dense(rslf_ctx* ctx, const float* d_in_vsu, int elem, int V, int S, int U, float weight, float hi,
                                    float* d_out_vsu3);
 
+/* ---- per-view equalisation (K19; not in the reference's code: the remedy its report names for global changes of
+ * illumination between frames, "some preprocessing equalization") ---- */
+/* A sample votes for a line only while its radiance lies within kernel_bandwidth of the running mean, so a view whose gain
+ * has drifted stops voting.  The remedy is one (a, b) per view s and channel c, y = a x + b, from one statistic over all
+ * (v, u) of the view.  The rule (csrc/k19_equalize_rule.hpp) is stated so that any correct implementation gives the same bits:
+ *   Statistics, on integers: hi > 0 is the field's cap (a volume: its max_value; integer elements: 255 or 65535; float
+ *   elements of a dense level: the caller's, e.g. rslf_device_max_f32), k = 65535.0f / hi one binary32 division, and
+ *     q(x) = (uint32) min(rintf(fminf(fmaxf(x, 0.f), hi) * k), 65535.f);      a NaN sample is not counted;
+ *   per (s, c) over all v and u < U: n = #counted, s1 = sum q, s2 = sum q^2, three uint64, exact while V * U <= 2^31 - 1.
+ *   Coefficients, on the host in double: m = s1 / n / 65535 * hi, var = max(s2 / n / 65535^2 * hi^2 - m^2, 0), sd = sqrt(var);
+ *   joint (C == 3 only) adds the three channels' n, s1, s2 first and writes the one pair to all three (hue is kept); the
+ *   target (mt, sdt) is view ref_view's (m, sd) or, ref_view == -1, the arithmetic mean of m and of sd over the views with
+ *   n > 0.  RSLF_EQUALIZE_GAIN: a = m > 0 ? mt / m : 1, b = 0.  RSLF_EQUALIZE_AFFINE: a = sd > 0 ? sdt / sd : 1, b = mt - a m.
+ *   a is clamped to [1 / max_gain, max_gain] and b computed after the clamp; a view with n == 0, the reference view itself,
+ *   and every view of a field whose target has no sample get exactly (1, 0); a and b are rounded to float once, at the end.
+ *   Apply: y = x * a + b (one binary32 multiplication, one addition), integer elements then rintf (ties to even), then
+ *   y < 0 ? 0 : (y > hi ? hi : y); a NaN stays that NaN; a pair (1, 0) copies the source's bits. */
+#define RSLF_EQUALIZE_GAIN    1
+#define RSLF_EQUALIZE_AFFINE  2
+/* The statistics of a filled volume of the context's device into h_stats [S][C][3] (n, s1, s2), hi = the volume's max_value
+ * (also left in *hi_used, nullable).  Awaited.  RSLF_ERR_INVALID_ARG: NULL, a volume never filled or of another device;
+ * RSLF_ERR_UNSUPPORTED: V * U beyond 2^31 - 1, a volume whose min_value < 0 (or that holds a NaN) or whose max_value is not
+ * finite and > 0. */
+int rslf_volume_view_stats(rslf_ctx* ctx, const rslf_volume* vol, uint64_t* h_stats, float* hi_used);
+/* The same of a dense level d_in_vsuc [V][S][U][C] of element type `elem` (RSLF_ELEM_*; always floats in memory) into the
+ * DEVICE buffer d_stats [S][C][3] (8-byte aligned), which the call zeroes first.  hi: the cap of float elements, finite and
+ * > 0; ignored for integer elements.  Enqueued on the context's stream, not awaited.  RSLF_ERR_INVALID_ARG: NULL, an unknown
+ * elem, a bad hi, a dimension < 1, C other than 1 or 3; RSLF_ERR_UNSUPPORTED: V * U beyond 2^31 - 1. */
+int rslf_view_stats_dense(rslf_ctx* ctx, const float* d_in_vsuc, int elem, int V, int S, int U, int C, float hi, uint64_t* d_stats);
+/* h_stats [S][C][3] -> h_a_b [S][C][2] by the rule above.  No context and no device: it works on a machine without a GPU.
+ * RSLF_ERR_INVALID_ARG: NULL, S < 1, C other than 1 or 3, a hi that is not finite and > 0, an unknown mode, ref_view outside
+ * [-1, S), a max_gain that is not finite or < 1, joint with C == 1. */
+int rslf_equalize_coefficients(const uint64_t* h_stats, int S, int C, float hi, int mode, int ref_view, int joint, float max_gain,
+                               float* h_a_b);
+/* Statistics, coefficients, apply: a new volume [V][S][U][C] from a filled one of the same context's device.  The call waits
+ * for the S * C * 3 integers between the two kernels and then for the two floats of the new slab's range, as the uploads do;
+ * the pad is written as zeros.  h_a_b [S][C][2] receives the coefficients (nullable).  *out has rslf_volume_dilate_u's
+ * contract: the caller's on success, NULL after a failed call, and a call whose *out IS src on entry is refused, *out
+ * untouched.  RSLF_ERR_INVALID_ARG: NULL, an unknown mode, ref_view outside [-1, S), a max_gain that is not finite or < 1,
+ * joint with C == 1, a source never filled or of another device; RSLF_ERR_UNSUPPORTED as rslf_volume_view_stats. */
+int rslf_volume_equalize_views(rslf_ctx* ctx, const rslf_volume* src, int mode, int ref_view, int joint, float max_gain,
+                               rslf_volume** out, float* h_a_b);
+/* The apply pass alone, with the caller's coefficients h_a_b [S][C][2] (from a masked statistic of their own, say), all
+ * finite; hi is the source's max_value.  Contract and refusals as above. */
+int rslf_volume_apply_view_gains(rslf_ctx* ctx, const rslf_volume* src, const float* h_a_b, rslf_volume** out);
+/* The three steps on a dense level d_inout_vsuc [V][S][U][C], in place, awaited.  hi as rslf_view_stats_dense; h_a_b nullable.
+ * Refusals: rslf_view_stats_dense's and rslf_volume_equalize_views's of the options. */
+int rslf_equalize_views_dense(rslf_ctx* ctx, float* d_inout_vsuc, int elem, int V, int S, int U, int C, float hi, int mode,
+                              int ref_view, int joint, float max_gain, float* h_a_b);
+/* The apply pass alone on a dense level, with the caller's coefficients h_a_b [S][C][2] (a HOST array, all finite, read
+ * before the return): d_out_vsuc = a x + b of d_in_vsuc; d_out_vsuc may be d_in_vsuc.  hi as rslf_view_stats_dense.  Enqueued
+ * on the context's stream, not awaited.  RSLF_ERR_INVALID_ARG: NULL, an unknown elem, a bad hi, a coefficient that is not
+ * finite, a dimension < 1, C other than 1 or 3; RSLF_ERR_UNSUPPORTED: V * U beyond 2^31 - 1. */
+int rslf_apply_view_gains_dense(rslf_ctx* ctx, const float* d_in_vsuc, int elem, int V, int S, int U, int C, float hi,
+                                const float* h_a_b, float* d_out_vsuc);
+/* The joint statistic adds three channels' sums in one uint64, exact while 3 * V * U * 65535^2 < 2^64: every entry that takes
+ * `joint` refuses joint != 0 with V * U beyond 1431699457 as RSLF_ERR_UNSUPPORTED (rslf_equalize_coefficients is not told V
+ * and U: its caller keeps to the cap). */
+
 /* Host EPIs as the reference holds them: h_epis[v] -> S rows of U*C values,
  * row_stride_bytes apart (cv::Mat::step).  u8: x * float(1/255) (dc.hpp:470).
  * f32: x * float(1/double(scale)); scale < 0 => the max over all EPIs
@@ -1159,6 +1218,37 @@ int rslf_f2c_run_host_dl(rslf_ctx* ctx, const void* const* h_epis, int elem, int
                          int level_dilation, int dilation_kind);
 /* The two read back (each pointer nullable): 1 and RSLF_DILATE_CUBIC for NULL and for a run made without the dilation. */
 int rslf_f2c_run_level_dilation(const rslf_f2c_run* run, int* factor, int* kind);
+/* The pyramid on a field equalised per view (K19, above): equalize_mode = RSLF_EQUALIZE_GAIN or _AFFINE runs
+ * rslf_equalize_views_dense once, in place, on the finest level's upload -- hi the element type's 255 or 65535, for float
+ * elements the upload's maximum -- before the derivative channels, so the features are derivatives of the equalised
+ * intensity, and then goes on unchanged: bit for bit the same call on the equalised field.  equalize_ref_view: the view whose
+ * statistics are the target, -1 for the views' mean; equalize_joint: one pair for the three channels (C == 3);
+ * equalize_max_gain: the clamp of the gain.  equalize_mode = 0: off, the narrower entry's call, launch for launch and bit for
+ * bit; no launch, no allocation, and the three other arguments are not looked at.  The two entries are the fullest of their
+ * families plus the four arguments.  RSLF_ERR_INVALID_ARG, before a device is touched: an unknown mode, equalize_ref_view
+ * outside [-1, S), an equalize_max_gain that is not finite or < 1, equalize_joint with C == 1; RSLF_ERR_UNSUPPORTED, before a
+ * device is touched too: V * U beyond 2^31 - 1 (with equalize_joint: beyond 1431699457); after the upload: a float field whose maximum is not finite and > 0.  The multi-device loop refuses the option by name. */
+int rslf_fine_to_coarse_run_host_eq(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                    float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                    int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid, float derivative_weight,
+                                    int level_dilation, int dilation_kind, int equalize_mode, int equalize_ref_view,
+                                    int equalize_joint, float equalize_max_gain);
+int rslf_f2c_run_host_eq(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C, size_t row_stride_bytes,
+                         float d_min, float d_max, int dim_d, float epi_scale_factor, const rslf_params* p, int max_pyr_depth,
+                         int accept_all_last_scale, int line_mode, int validity_rule, int keep_volumes, rslf_f2c_run** run,
+                         rslf_stats* stats, int subgrid, int peaks, float uniqueness_ratio, float propagation_ratio,
+                         float consistency_tol, int consistency_radius, int consistency_min_agree, float derivative_weight,
+                         int level_dilation, int dilation_kind, int equalize_mode, int equalize_ref_view, int equalize_joint,
+                         float equalize_max_gain);
+/* The settings read back (each pointer nullable): mode 0 and view 0 for NULL and for a run made without the equalisation;
+ * h_a_b [S][C][2], C the field's own channel count, receives the coefficients the run applied and is left untouched by a run
+ * made without it. */
+int rslf_f2c_run_equalize(const rslf_f2c_run* run, int* mode, int* ref_view, float* h_a_b);
+/* C of that h_a_b: the channels of the field the run was made from (1 for a run with derivative channels, which describes
+ * itself with C = 3); 0 for NULL and for a run made without the equalisation.  Returns the count, not a status. */
+int rslf_f2c_run_view_gains_channels(const rslf_f2c_run* run);
 /* The options read back (each pointer nullable): zeros for NULL and for a run made without the gate. */
 int rslf_f2c_run_consistency_gate(const rslf_f2c_run* run, float* tol, int* radius, int* min_agree);
 /* The pixels the gate made invalid on `level`: 0 for a level accepted whole and for every level of a run made without the

@@ -1273,6 +1273,49 @@ public:
         derivative_weight_ = weight;
     }
     float get_derivative_channels() const { return derivative_weight_; }
+    // Not in the reference's code (the remedy its report names for global changes of illumination between frames), to be
+    // called before run(): the per-view equalisation (rslf_fine_to_coarse_run_host_eq, rslf_f2c_run_host_eq; rslf_hip.h
+    // "per-view equalisation").  The finest level's upload is equalised on the device, y = a x + b with one (a, b) per view
+    // and channel, before the derivative channels, and the pyramid runs on it bit for bit as on the equalised field.  mode:
+    // RSLF_EQUALIZE_GAIN or RSLF_EQUALIZE_AFFINE, 0 switches it off; ref_view: the view whose statistics are the target,
+    // -1 the views' mean, -2 (the default) the centre view dim_s / 2, where the sweep starts; joint: one pair for the three
+    // channels of an RGB field, -1 (the default) on for FineToCoarse<3>; max_gain: the clamp of the gain.  Any mode but 0
+    // throws on a MultiContext (one device: a view's statistic spans all scanlines).
+    void set_equalize_views(int mode, int ref_view = -2, int joint = -1, float max_gain = 4.f)
+    {
+        if (mode != 0 && mode != RSLF_EQUALIZE_GAIN && mode != RSLF_EQUALIZE_AFFINE)
+            throw std::invalid_argument("set_equalize_views: 0 (off), RSLF_EQUALIZE_GAIN or RSLF_EQUALIZE_AFFINE");
+        if (mode != 0 && multi_)
+            throw std::invalid_argument("set_equalize_views: this object was built on a MultiContext: the per-view equalisation is built for one context");
+        if (ref_view == -2)
+            ref_view = dim_s_ / 2;
+        if (joint < 0)
+            joint = CHANNELS == 3 ? 1 : 0;
+        if (mode != 0) {
+            if (ref_view < -1 || ref_view >= dim_s_)
+                throw std::invalid_argument("set_equalize_views: ref_view is -1 (the views' mean) or a view in [0, dim_s)");
+            if (joint && CHANNELS != 3)
+                throw std::invalid_argument("set_equalize_views: joint is built for a three-channel field (FineToCoarse<3>)");
+            if (!(max_gain >= 1.f && max_gain <= 3.402823466e+38f))
+                throw std::invalid_argument("set_equalize_views: max_gain is a finite gain >= 1");
+        }
+        equalize_mode_ = mode, equalize_ref_view_ = ref_view, equalize_joint_ = joint ? 1 : 0, equalize_max_gain_ = max_gain;
+    }
+    int get_equalize_views() const { return equalize_mode_; }
+    // The coefficients a kept run's equalisation applied, [dim_s][CHANNELS][2] (a, b); empty for a run made without it
+    // and without a kept run (keep_on_device): the host-planes entries hand no coefficients out.
+    std::vector<float> get_view_gains() const
+    {
+        std::vector<float> a_b;
+        int mode = 0;
+        if (run_)
+            check(rslf_f2c_run_equalize(run_, &mode, nullptr, nullptr), "rslf_f2c_run_equalize");
+        if (mode != 0) {
+            a_b.resize((size_t)dim_s_ * CHANNELS * 2);
+            check(rslf_f2c_run_equalize(run_, nullptr, nullptr, a_b.data()), "rslf_f2c_run_equalize");
+        }
+        return a_b;
+    }
     // To be called before run(): the run stays on the device (rslf_f2c_run_host) and this object owns it.  get_results()
     // copies the fused planes out, the coloured getters are rendered there from the kept planes -- nothing is uploaded a
     // second time --, get_coloured_depth_pyr works in every line mode, get_coloured_epi_pyr exists, and the per-level
@@ -1520,11 +1563,12 @@ public:
             return;
         }
         // the family's widest entry, which takes any element type: no mode, no levels out
-        check(rslf_fine_to_coarse_run_host_dl(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+        check(rslf_fine_to_coarse_run_host_eq(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
                                               out_validity_s_v_u_.data(), &n_levels_, &stats, RSLF_LINE_CONF_OFF, nullptr, 0,
-                                              derivative_weight_, level_dilation_, level_dilation_kind_),
-              "rslf_fine_to_coarse_run_host_dl");
+                                              derivative_weight_, level_dilation_, level_dilation_kind_, equalize_mode_, equalize_ref_view_,
+                                              equalize_joint_, equalize_max_gain_),
+              "rslf_fine_to_coarse_run_host_eq");
     }
     void get_results(std::vector<float>& out_map_s_v_u, std::vector<uint8_t>& out_validity_s_v_u) const
     {
@@ -1658,11 +1702,12 @@ private:
         detail::require(peaks_ || propagation_ratio_ == 0.f, "FineToCoarse: the propagation ratio reads the peak planes: call set_peaks(true)");
         gate_held_ = false;
         // the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's (rslf_hip.h)
-        check(rslf_f2c_run_host_dl(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
+        check(rslf_f2c_run_host_eq(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_, dim_d_, scale_,
                                    &p, max_pyr_depth_, accept_all_ ? 1 : 0, line_mode_ < 0 ? RSLF_LINE_CONF_OFF : line_mode_, validity_rule_,
                                    keep_volumes_ ? 1 : 0, &run_, &stats, subgrid_ ? 1 : 0, peaks_ ? 1 : 0, uniqueness_, propagation_ratio_,
-                                   gate_tol_, gate_radius_, gate_min_agree_, derivative_weight_, level_dilation_, level_dilation_kind_),
-              "rslf_f2c_run_host_dl");
+                                   gate_tol_, gate_radius_, gate_min_agree_, derivative_weight_, level_dilation_, level_dilation_kind_,
+                                   equalize_mode_, equalize_ref_view_, equalize_joint_, equalize_max_gain_),
+              "rslf_f2c_run_host_eq");
         peaks_held_ = peaks_;
         gate_held_ = gate_min_agree_ > 0;
         rslf_f2c_run_desc d;
@@ -1743,11 +1788,12 @@ private:
         lo.h_Cl_svu = hl.data();
         lo.h_Ce_svu = nullptr;
         // the family's widest entry, which takes any element type
-        check(rslf_fine_to_coarse_run_host_dl(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
+        check(rslf_fine_to_coarse_run_host_eq(ctx_->get(), epis_.data(), elem(), dim_v_, dim_s_, dim_u_, CHANNELS, stride_, d_min_, d_max_,
                                               dim_d_, scale_, &p, max_pyr_depth_, accept_all_ ? 1 : 0, out_map_s_v_u_.data(),
                                               out_validity_s_v_u_.data(), &n_levels_, &stats, mode, &lo, subgrid_ ? 1 : 0, derivative_weight_,
-                                              level_dilation_, level_dilation_kind_),
-              "rslf_fine_to_coarse_run_host_dl");
+                                              level_dilation_, level_dilation_kind_, equalize_mode_, equalize_ref_view_, equalize_joint_,
+                                              equalize_max_gain_),
+              "rslf_fine_to_coarse_run_host_eq");
     }
     int elem() const { return type_ == InputType::U8 ? RSLF_ELEM_U8 : type_ == InputType::U16 ? RSLF_ELEM_U16 : RSLF_ELEM_F32; }
 #ifdef RSLFX_HAVE_OPENCV
@@ -1788,6 +1834,8 @@ private:
     bool gate_held_ = false;     // the kept run was made with the consistency gate
     float derivative_weight_ = 0.f;   // set_derivative_channels
     int level_dilation_ = 1, level_dilation_kind_ = RSLF_DILATE_CUBIC;   // set_level_dilation
+    int equalize_mode_ = 0, equalize_ref_view_ = 0, equalize_joint_ = 0;  // set_equalize_views
+    float equalize_max_gain_ = 4.f;
     int validity_rule_;
     rslf_f2c_run* run_;          // the kept run, owned
 };

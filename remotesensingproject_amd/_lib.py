@@ -78,6 +78,10 @@ SYMBOLS = [
     # the level dilation: every level's sweep of the pyramid on EPIs dilated along u (K18)
     "rslf_planes_dilate_ranges_u", "rslf_planes_dilate_ranges_u_host", "rslf_planes_undilate_many_u", "rslf_fine_to_coarse_run_host_dl",
     "rslf_f2c_run_host_dl", "rslf_f2c_run_level_dilation",
+    # the per-view equalisation: a view's quantised statistics, (a, b) per view and channel, and the pyramid on it (K19)
+    "rslf_volume_view_stats", "rslf_view_stats_dense", "rslf_equalize_coefficients", "rslf_volume_equalize_views",
+    "rslf_volume_apply_view_gains", "rslf_equalize_views_dense", "rslf_fine_to_coarse_run_host_eq", "rslf_f2c_run_host_eq",
+    "rslf_f2c_run_equalize", "rslf_apply_view_gains_dense", "rslf_f2c_run_view_gains_channels",
 ]
 
 
@@ -371,6 +375,17 @@ def lib():
     L.rslf_f2c_run_host_dl.argtypes = L.rslf_f2c_run_host_dv.argtypes + [ci, ci]
     L.rslf_fine_to_coarse_run_host_dl.argtypes = L.rslf_fine_to_coarse_run_host_dv.argtypes + [ci, ci]
     L.rslf_f2c_run_level_dilation.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+    L.rslf_f2c_run_host_eq.argtypes = L.rslf_f2c_run_host_dl.argtypes + [ci, ci, ci, cf]
+    L.rslf_fine_to_coarse_run_host_eq.argtypes = L.rslf_fine_to_coarse_run_host_dl.argtypes + [ci, ci, ci, cf]
+    L.rslf_f2c_run_equalize.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), vp]
+    L.rslf_f2c_run_view_gains_channels.argtypes = [vp]
+    L.rslf_apply_view_gains_dense.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, vp, vp]
+    L.rslf_volume_view_stats.argtypes = [vp, vp, vp, C.POINTER(cf)]
+    L.rslf_view_stats_dense.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, vp]
+    L.rslf_equalize_coefficients.argtypes = [vp, ci, ci, cf, ci, ci, ci, cf, vp]
+    L.rslf_volume_equalize_views.argtypes = [vp, vp, ci, ci, ci, cf, C.POINTER(vp), vp]
+    L.rslf_volume_apply_view_gains.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.rslf_equalize_views_dense.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, ci, cf, vp]
     L.rslf_volume_derivative_channels.argtypes = [vp, vp, cf, C.POINTER(vp)]
     L.rslf_derivative_channels_dense.argtypes = [vp, vp, ci, ci, ci, ci, cf, cf, vp]
     L.rslf_f2c_run_consistency_gate.argtypes = [vp, C.POINTER(cf), C.POINTER(ci), C.POINTER(ci)]

@@ -36,7 +36,7 @@ UNITS = {
     "rslf_sweep_peaks.hip": ["k2_scan.hpp", "k10_sweep_peaks.hpp", "k10_peak_merge.hpp", "k8_peak_rule.hpp", "rslf_plan_sweep_peaks.hpp",
                              "rslf_plan_peaks.hpp", "rslf_plan_subgrid.hpp"],
     "rslf_f2c.hip": ["k5_f2c.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_f2c_consistency.hpp",
-                     "rslf_plan_consistency.hpp", "k12_consistency_rule.hpp", "rslf_plan_derivative.hpp", "k17_derivative_rule.hpp"],
+                     "rslf_plan_consistency.hpp", "k12_consistency_rule.hpp", "rslf_plan_derivative.hpp", "k17_derivative_rule.hpp", "k19_equalize_rule.hpp"],
     "rslf_f2c_keep.hip": ["rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp", "rslf_plan_sweep_gate.hpp", "k11_f2c_peak_rule.hpp",
                           "rslf_plan_f2c_consistency.hpp", "rslf_plan_consistency.hpp", "k12_consistency_rule.hpp"],
     "rslf_f2c_peaks.hip": ["k11_f2c_peaks.hpp", "k11_f2c_peak_rule.hpp", "rslf_plan_f2c_peaks.hpp", "rslf_plan_peaks.hpp"],
@@ -48,6 +48,7 @@ UNITS = {
     "rslf_dilate.hip": ["k16_dilate.hpp", "k16_dilate_rule.hpp", "rslf_plan_dilate.hpp", "k18_level_dilate.hpp", "k18_ranges_rule.hpp",
                         "rslf_plan_level_dilate.hpp"],
     "rslf_derivative.hip": ["k17_derivative.hpp", "k17_derivative_rule.hpp", "rslf_plan_derivative.hpp"],
+    "rslf_equalize.hip": ["k19_equalize.hpp", "k19_equalize_rule.hpp", "rslf_plan_equalize.hpp"],
     "rslf_multi.hip": [],
     "rslf_multi_sweep.hip": [],
 }

@@ -3,6 +3,7 @@
 // form is here and whose multi-device form is in rslf_multi_sweep.hip.  C-ABI: include/rslf_hip.h.
 #include "rslf_internal.hpp"
 #include "rslf_plan_derivative.hpp"
+#include "k19_equalize_rule.hpp"
 #include "rslf_plan_dilate.hpp"
 #include "rslf_plan_f2c_consistency.hpp"
 #include "rslf_plan_f2c_peaks.hpp"
@@ -325,6 +326,8 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions&
         return fail(RSLF_ERR_INVALID_ARG, "line confidence mode %d: must be RSLF_LINE_CONF_OFF, _AS_BUILT or _GATE", o.line_mode);
     if (int rc = check_level_dilation(o))
         return rc;
+    if (int rc = check_equalize(o, V, S, U, req.C))
+        return rc;
     int rc = check_params(p);
     if (rc)
         return rc;
@@ -342,6 +345,25 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions&
     rc = f2c_upload_raw(ctx, req.elem, req.h_epis, V, S, U, req.C, req.row_stride_bytes, raw.as<float>());
     if (rc)
         return rc;
+    // the per-view equalisation (K19): once, in place, on the finest level's upload; everything below -- the derivative
+    // channels first -- reads the equalised intensity
+    std::vector<float> view_gains;
+    if (o.equalize_mode != 0) {
+        float hi = 0.0f;   // (integer elements: their type's, equalize_views_raw)
+        if (req.elem == Elem::F32) {
+            rc = rslf_device_max_f32(ctx, raw.as<const float>(), (size_t)V * S * U * req.C, &hi);
+            if (rc)
+                return rc;
+            if (!eq_hi_ok(hi))
+                return fail(RSLF_ERR_UNSUPPORTED, "equalize_views=%d on a float field whose maximum is %g: the cap is finite and > 0",
+                            o.equalize_mode, (double)hi);
+        }
+        view_gains.resize((size_t)S * req.C * 2);
+        rc = equalize_views_raw(ctx, raw.as<float>(), req.elem, V, S, U, req.C, hi, o.equalize_mode, o.equalize_ref_view, o.equalize_joint,
+                                o.equalize_max_gain, view_gains.data());
+        if (rc)
+            return rc;
+    }
     if (derivative) {   // once, at the finest level: the features go down with the intensity from here
         float hi = 0.0f;   // (integer elements: their type's, derivative_channels_raw)
         if (req.elem == Elem::F32) {
@@ -363,6 +385,7 @@ int rslf::fine_to_coarse(rslf_ctx* ctx, const F2cRequest& req, const F2cOptions&
     F2cKept own;
     F2cKept& K = keep ? *keep : own;
     K.levels = std::vector<F2cKeptLevel>((size_t)P);
+    K.view_gains = std::move(view_gains);
     int64_t pixels = 0;
     rslf_stats st1;
     memset(&st1, 0, sizeof(st1));
@@ -771,6 +794,29 @@ extern "C" int rslf_fine_to_coarse_run_host_dl(rslf_ctx* ctx, const void* const*
     F2cOptions options;
     options.line_mode = line_mode, options.subgrid = subgrid, options.derivative_weight = derivative_weight;
     options.level_dilation = level_dilation, options.dilation_kind = dilation_kind;
+    return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
+}
+RSLF_API_CATCH
+
+// ... and with equalize_mode != 0 the finest level's upload is equalised per view, in place, before anything reads it (K19)
+extern "C" int rslf_fine_to_coarse_run_host_eq(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                               size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                               const rslf_params* p, int max_pyr_depth, int accept_all_last_scale,
+                                               float* h_out_map_svu, uint8_t* h_out_valid_svu, int* n_levels, rslf_stats* stats,
+                                               int line_mode, const rslf_f2c_levels_out* levels_out, int subgrid,
+                                               float derivative_weight, int level_dilation, int dilation_kind, int equalize_mode,
+                                               int equalize_ref_view, int equalize_joint, float equalize_max_gain) RSLF_API_TRY
+{
+    Elem e;
+    if (int rc = elem_of(elem, &e))
+        return rc;
+    const F2cRequest req = {e, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions options;
+    options.line_mode = line_mode, options.subgrid = subgrid, options.derivative_weight = derivative_weight;
+    options.level_dilation = level_dilation, options.dilation_kind = dilation_kind;
+    options.equalize_mode = equalize_mode, options.equalize_ref_view = equalize_ref_view, options.equalize_joint = equalize_joint;
+    options.equalize_max_gain = equalize_max_gain;
     return fine_to_coarse_one_context(ctx, req, options, {h_out_map_svu, h_out_valid_svu, n_levels, levels_out}, stats, nullptr);
 }
 RSLF_API_CATCH

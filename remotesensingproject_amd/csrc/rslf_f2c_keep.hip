@@ -312,6 +312,8 @@ static int f2c_run_host(rslf_ctx* ctx, int elem, F2cRequest req, const F2cOption
     }
     if (int rc = check_level_dilation(o))
         return rc;
+    if (int rc = check_equalize(o, req.V, req.S, req.U, req.C))
+        return rc;
     // (the level's sweeps would end a sweep the caller left open; the entries without the gate do what they always did)
     if (o.cs_min_agree > 0 && ctx->sweep.open)
         return fail(RSLF_ERR_INVALID_ARG, "consistency_min_agree: a sweep is open on this context");
@@ -457,6 +459,51 @@ extern "C" int rslf_f2c_run_host_dl(rslf_ctx* ctx, const void* const* h_epis, in
     o.derivative_weight = derivative_weight;
     o.level_dilation = level_dilation, o.dilation_kind = dilation_kind;
     return f2c_run_host(ctx, elem, req, o, run, stats);
+}
+RSLF_API_CATCH
+
+// ... and with equalize_mode != 0 the finest level's upload equalised per view before anything reads it (K19)
+extern "C" int rslf_f2c_run_host_eq(rslf_ctx* ctx, const void* const* h_epis, int elem, int V, int S, int U, int C,
+                                    size_t row_stride_bytes, float d_min, float d_max, int dim_d, float epi_scale_factor,
+                                    const rslf_params* p, int max_pyr_depth, int accept_all_last_scale, int line_mode,
+                                    int validity_rule, int keep_volumes, rslf_f2c_run** run, rslf_stats* stats, int subgrid, int peaks,
+                                    float uniqueness_ratio, float propagation_ratio, float consistency_tol, int consistency_radius,
+                                    int consistency_min_agree, float derivative_weight, int level_dilation, int dilation_kind,
+                                    int equalize_mode, int equalize_ref_view, int equalize_joint, float equalize_max_gain) RSLF_API_TRY
+{
+    const F2cRequest req = {Elem::F32, h_epis, V, S, U, C, row_stride_bytes, d_min, d_max, dim_d, epi_scale_factor, p, max_pyr_depth,
+                            accept_all_last_scale};
+    F2cOptions o;
+    o.line_mode = line_mode, o.validity_rule = validity_rule, o.keep_volumes = keep_volumes != 0, o.subgrid = subgrid;
+    o.peaks = peaks, o.uniqueness = uniqueness_ratio, o.propagation_ratio = propagation_ratio;
+    o.cs_tol = consistency_tol, o.cs_radius = consistency_radius, o.cs_min_agree = consistency_min_agree;
+    o.derivative_weight = derivative_weight;
+    o.level_dilation = level_dilation, o.dilation_kind = dilation_kind;
+    o.equalize_mode = equalize_mode, o.equalize_ref_view = equalize_ref_view, o.equalize_joint = equalize_joint;
+    o.equalize_max_gain = equalize_max_gain;
+    return f2c_run_host(ctx, elem, req, o, run, stats);
+}
+RSLF_API_CATCH
+
+// the equalisation a run was made with (each pointer nullable): mode 0, view 0 for NULL and for a run made without it; h_a_b
+// [S][C][2] of the field as uploaded (C the request's: the equalisation comes before the derivative channels) is written
+// only by a run made with it
+extern "C" int rslf_f2c_run_equalize(const rslf_f2c_run* run, int* mode, int* ref_view, float* h_a_b) RSLF_API_TRY
+{
+    if (mode)
+        *mode = run ? run->options.equalize_mode : 0;
+    if (ref_view)
+        *ref_view = run && run->options.equalize_mode ? run->options.equalize_ref_view : 0;
+    if (h_a_b && run && !run->kept.view_gains.empty())
+        memcpy(h_a_b, run->kept.view_gains.data(), run->kept.view_gains.size() * sizeof(float));
+    return RSLF_OK;
+}
+RSLF_API_CATCH
+
+// channels of the coefficients rslf_f2c_run_equalize writes: the field's own, 0 for NULL and for a run made without the equalisation
+extern "C" int rslf_f2c_run_view_gains_channels(const rslf_f2c_run* run) RSLF_API_TRY
+{
+    return run && run->S > 0 ? (int)(run->kept.view_gains.size() / ((size_t)run->S * 2)) : 0;
 }
 RSLF_API_CATCH
 

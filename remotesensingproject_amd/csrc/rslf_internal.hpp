@@ -22,6 +22,7 @@
 //                         with host outputs): a kept run's plane pair, the open-sweep refusal, the staging of host inputs and
 //                         outputs (layout: rslf_plan_stage.hpp), and the checks and launch batches the warp and the novel view share
 //   rslf_dilate.hip       the dilation along u: a volume f times as wide by a good kernel, result planes back (k16_dilate.hpp)
+//   rslf_equalize.hip     the per-view equalisation: a view's quantised statistics, (a, b) per view and channel, y = a x + b (k19_equalize.hpp)
 //   rslf_derivative.hip   the derivative channels: a one-channel field as (x, |dx/du|, |dx/dv|), volume and raw level (k17_derivative.hpp)
 //   rslf_multi.hip        host pointers in / host planes out, pipelined over one or several devices (pile path)
 //   rslf_multi_sweep.hip  the 2-D sweep sharded over several devices, and fine-to-coarse with its levels swept so
@@ -241,6 +242,9 @@ struct Scratch {
     DeviceBuf withheld;     // one u64: sources a gated sweep withheld (rslf_sweep_propagation_ratio zeroes it, the claims count, rslf_sweep_withheld reads)
     DeviceBuf lc_columns;   // float [V][S][U]: K(r - rbar) columns of a sweep with line confidence, kept from visit to visit
     DeviceBuf lc_argmax;    // int32 [V][U]: arg-max indices of the visit's scan, -1 where it accepted nothing
+    // per-view equalisation (K19)
+    DeviceBuf eq_stats;     // u64 [S][C][3]: a view's (n, s1, s2) per channel, zeroed on the context's stream before every count
+    DeviceBuf eq_table;     // float [S][C][2]: the (a, b) the apply kernel reads, copied from rslf_ctx::eq_table_host
     DeviceBuf shared[kSharedBufs];
 
     static constexpr size_t kMaxPartials = 2048;
@@ -344,6 +348,7 @@ struct rslf_ctx {
     int peaks_list = 1;        // 2-D sweep in the peaks mode: sparse visits take k10_peaks_list over the packed list (0: every visit the dense form; A/B and tests)
     int claim_skip = 1;        // 2-D sweep: the claims skip views with nothing left to paint within reach (0: off, A/B and tests)
     int staging_kib = 0;       // chunked host upload: device staging per pass in KiB (0: plan::kStagingBudget; tests of the later passes)
+    std::vector<float> eq_table_host;   // K19: the host copy of scratch.eq_table: outlives the copy that reads it
     int consistency_order = 0; // K12: the grid's order (k12_consistency.hpp, ConsistencyOrder; 0: scanlines dealt to the XCDs; A/B and tests)
 };
 
@@ -593,6 +598,9 @@ struct F2cOptions {
                                                     // rslf_*_run_host_dv): three channels from the finest level's upload on
     int level_dilation = 1;                         // > 1: every level's SWEEP runs on the level's volume dilated along u by this factor (K16) and
     int dilation_kind = RSLF_DILATE_CUBIC;          // its planes come back to the level's own grid (K18; rslf_*_run_host_dl); the level chain is untouched
+    int equalize_mode = 0;                          // RSLF_EQUALIZE_GAIN / _AFFINE: the finest level's upload is equalised per view, in place, before
+    int equalize_ref_view = 0, equalize_joint = 0;  // anything else reads it (K19; rslf_*_run_host_eq): the view whose statistics are the target (-1: the
+    float equalize_max_gain = 4.0f;                 // views' mean), one pair for the three channels, the clamp of the gain
 };
 // The host outputs of a pyramid, each nullable: the fused planes, the depth, every level's planes.
 struct F2cHostOut {
@@ -638,6 +646,7 @@ struct F2cKept {
     std::vector<F2cKeptLevel> levels;   // finest first
     DevBuf fused_map, fused_valid;      // [S][V_0][U_0]
     DevBuf fused_pk_idx, fused_pk_score, fused_pk_runner_idx, fused_pk_runner_score, fused_level;   // [S][V_0][U_0] (k11_fuse_peaks; runs with peaks only)
+    std::vector<float> view_gains;      // [S][C][2]: the (a, b) the equalisation applied to the finest level's upload (K19; empty when off)
 };
 // FineToCoarse constructor + run() + get_results() (rslf_fine_to_coarse.hpp:103-324) from the request's host EPIs into host
 // planes: the pyramid, the bound tightening and the fusion on ctx, every level swept by `sweep`, which reports the level's
@@ -656,6 +665,15 @@ int fine_to_coarse_one_context(rslf_ctx* ctx, const F2cRequest& req, const F2cOp
 // The raw form of the derivative channels (K17), enqueued on the context's stream: a dense level d_in [V][S][U] (integer
 // elements: integer values held as floats) becomes d_out [V][S][U][3].  hi: the cap of float elements (derivative_hi_f32).
 int derivative_channels_raw(rslf_ctx* ctx, const float* d_in, Elem e, int V, int S, int U, float weight, float hi, float* d_out);
+
+// rslf_equalize.hip
+// What every pyramid entry refuses of the equalisation before a device is touched: the mode, the reference view, the gain's
+// clamp, joint with one channel, a field whose V * U the statistic cannot count exactly.  Mode 0 (off) refuses nothing.
+int check_equalize(const F2cOptions& options, int V, int S, int U, int C);
+// The dense form of the per-view equalisation (K19) in place, awaited: statistics, coefficients on the host, apply.  hi: the
+// cap of float elements (> 0); an integer type's own otherwise.  h_a_b [S][C][2] receives the coefficients (nullable).
+int equalize_views_raw(rslf_ctx* ctx, float* d_inout, Elem e, int V, int S, int U, int C, float hi, int mode, int ref_view, int joint,
+                       float max_gain, float* h_a_b);
 
 // rslf_multi.hip
 void multi_free_dev(rslf_multi::Dev& d);

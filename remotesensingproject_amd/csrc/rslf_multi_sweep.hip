@@ -306,6 +306,9 @@ static int multi_fine_to_coarse(rslf_multi* m, const F2cRequest& req, const F2cO
     if (options.derivative_weight != 0.0f)   // before a device is touched
         return fail(RSLF_ERR_INVALID_ARG, "derivative_channels=%g is not built here (the pyramid's derivative channels are built for one device)",
                     (double)options.derivative_weight);
+    if (options.equalize_mode != 0)
+        return fail(RSLF_ERR_INVALID_ARG, "equalize_views=%d is not built here (a view's statistic spans all scanlines: the pyramid's "
+                    "equalisation is built for one device)", options.equalize_mode);
     if (options.level_dilation != 1)
         return fail(RSLF_ERR_INVALID_ARG, "level_dilation=%d is not built here (the pyramid's level dilation is built for one device)",
                     options.level_dilation);

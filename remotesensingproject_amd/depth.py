@@ -231,6 +231,62 @@ def require_no_derivative_channels(derivative_channels, who: str) -> None:
                          "Volume.with_derivative_channels)" % (who, derivative_channels))
 
 
+EQUALIZE_GAIN, EQUALIZE_AFFINE = 1, 2   # RSLF_EQUALIZE_*
+
+
+class ViewStats(NamedTuple):
+    """Volume.view_stats(): per view and channel, [S, C] each -- the samples counted (uint64), and the mean and standard
+    deviation of the quantised samples on the volume's own scale (float64; NaN where n == 0).  `raw` [S, C, 3] holds the
+    integers (n, s1, s2) themselves and `hi` the cap they were quantised with (csrc/k19_equalize_rule.hpp)."""
+    n: np.ndarray
+    mean: np.ndarray
+    std: np.ndarray
+    raw: np.ndarray
+    hi: float
+
+
+def _equalize_mode(equalize_views, who: str) -> int:
+    """The mode of an equalize_views argument: None, False or 0 is off (0); else EQUALIZE_GAIN or EQUALIZE_AFFINE."""
+    if equalize_views is None or equalize_views is False or (not isinstance(equalize_views, str) and equalize_views == 0):
+        return 0
+    if isinstance(equalize_views, (bool, np.bool_)) or equalize_views not in (EQUALIZE_GAIN, EQUALIZE_AFFINE):
+        raise ValueError("%s: equalize_views %r is not None (off), EQUALIZE_GAIN or EQUALIZE_AFFINE" % (who, equalize_views))
+    return int(equalize_views)
+
+
+def _equalize_args(S: int, C_: int, ref_view, joint, max_gain, who: str) -> tuple[int, int, float]:
+    """(ref_view, joint, max_gain) as the library takes them.  ref_view None: the view S // 2, where the sweep starts;
+    "mean": -1, the mean of the views; joint None: on for three channels."""
+    if ref_view is None:
+        ref = S // 2
+    elif isinstance(ref_view, str):
+        if ref_view != "mean":
+            raise ValueError("%s: equalize ref_view %r is not None, \"mean\" or a view in [0, %d)" % (who, ref_view, S))
+        ref = -1
+    else:
+        ref = int(ref_view)
+        if isinstance(ref_view, (bool, np.bool_)) or ref != ref_view or not 0 <= ref < S:
+            raise ValueError("%s: equalize ref_view %r is not None, \"mean\" or a view in [0, %d)" % (who, ref_view, S))
+    j = (C_ == 3) if joint is None else bool(joint)
+    if j and C_ != 3:
+        raise ValueError("%s: equalize joint=%r needs a three-channel field, not C=%d" % (who, joint, C_))
+    try:
+        g = float(max_gain)
+    except (TypeError, ValueError):
+        g = float("nan")
+    if isinstance(max_gain, bool) or not np.isfinite(g) or g < 1.0 or g > float(np.finfo(np.float32).max):
+        raise ValueError("%s: equalize max_gain %r is not a finite gain >= 1" % (who, max_gain))
+    return ref, 1 if j else 0, g
+
+
+def require_no_equalize_views(equalize_views, who: str) -> None:
+    """The per-view equalisation (DESIGN.md 3 "K19") is built for one device: a view's statistic spans all scanlines, so a
+    multi-device or sharded form needs an all-reduce.  They refuse it instead of ignoring it."""
+    if equalize_views is not None and equalize_views is not False and (isinstance(equalize_views, str) or equalize_views != 0):
+        raise ValueError("%s: equalize_views=%r is not built here (one device: fine_to_coarse_run_host, FineToCoarse; or "
+                         "Volume.equalized_views)" % (who, equalize_views))
+
+
 class Context:
     """rslf_ctx bound to one GPU; launches go to torch's current stream on it."""
 
@@ -470,6 +526,78 @@ class Volume:
         out.scale_used = self.scale_used
         out.u_dilation, out.u_source = self.u_dilation, self.u_source
         out.derivative_weight = w
+        return out
+
+    view_gains = None   # of a volume equalized_views() / with_view_gains() made: the [S, C, 2] float32 (a, b) it was made with
+
+    def _require_intensities(self, who: str) -> None:
+        if getattr(self, "derivative_weight", 0.0) > 0:
+            raise ValueError("%s: a volume with derivative channels (derivative_weight=%r) is refused: its feature channels are "
+                             "not intensities; equalise first" % (who, self.derivative_weight))
+
+    def _like(self, h) -> "Volume":
+        """A new Volume of this one's shape around the handle h, with what this one carries."""
+        out = Volume.__new__(Volume)
+        out.ctx, out._h = self.ctx, h
+        out.V, out.S, out.U, out.C = self.V, self.S, self.U, self.C
+        out.scale_used = self.scale_used
+        out.u_dilation, out.u_source = self.u_dilation, self.u_source
+        out.derivative_weight = self.derivative_weight
+        return out
+
+    def view_stats(self) -> ViewStats:
+        """Not in the reference's code: per view and channel, over all (v, u), the count, mean and standard deviation of
+        this volume's samples quantised to 16 bits of [0, max_value] (rslf_volume_view_stats) -- integers, so the same bits
+        on every run.  A non-negative volume with a finite maximum > 0."""
+        self._require_intensities("Volume.view_stats")
+        raw = np.zeros((self.S, self.C, 3), np.uint64)
+        hi = C.c_float()
+        self.ctx.use_current_stream()
+        check(_lib.lib().rslf_volume_view_stats(self.ctx._h, self._h, raw.ctypes.data, C.byref(hi)), "rslf_volume_view_stats")
+        n = raw[..., 0].copy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            dn = n.astype(np.float64)
+            h = float(hi.value)
+            mean = raw[..., 1].astype(np.float64) / dn / 65535.0 * h
+            var = raw[..., 2].astype(np.float64) / dn / (65535.0 * 65535.0) * (h * h) - mean * mean
+            std = np.sqrt(np.maximum(var, 0.0))
+        return ViewStats(n, mean, std, raw, h)
+
+    def equalized_views(self, mode: int = EQUALIZE_AFFINE, ref_view=None, joint=None, max_gain: float = 4.0) -> "Volume":
+        """Not in the reference's code (the remedy its report names for global changes of illumination between frames): a
+        new Volume y = a x + b with one (a, b) per view and channel, so that every view's mean (EQUALIZE_GAIN: b = 0) or mean
+        and standard deviation (EQUALIZE_AFFINE) over all (v, u) meet the reference view's (rslf_volume_equalize_views).
+        ref_view None: the view S // 2, where the sweep starts; "mean": the mean of the views.  joint None: one pair for
+        the three channels of an RGB volume (hue is kept), False: a pair per channel.  The gain is clamped to
+        [1 / max_gain, max_gain].  The result carries .view_gains [S, C, 2] and what this volume carries."""
+        m = _equalize_mode(mode, "Volume.equalized_views")
+        if m == 0:
+            raise ValueError("Volume.equalized_views: equalize_views %r is not EQUALIZE_GAIN or EQUALIZE_AFFINE" % (mode,))
+        self._require_intensities("Volume.equalized_views")
+        ref, j, g = _equalize_args(self.S, self.C, ref_view, joint, max_gain, "Volume.equalized_views")
+        a_b = np.zeros((self.S, self.C, 2), np.float32)
+        self.ctx.use_current_stream()
+        h = C.c_void_p()
+        check(_lib.lib().rslf_volume_equalize_views(self.ctx._h, self._h, m, ref, j, g, C.byref(h), a_b.ctypes.data),
+              "rslf_volume_equalize_views")
+        out = self._like(h)
+        out.view_gains = a_b
+        return out
+
+    def with_view_gains(self, a_b) -> "Volume":
+        """The apply pass alone (rslf_volume_apply_view_gains): a new Volume y = a x + b from the caller's [S, C, 2]
+        coefficients -- a masked statistic of their own, another field's gains.  y is rounded as the rule says and clamped
+        to [0, max_value]; a pair (1, 0) copies the view."""
+        self._require_intensities("Volume.with_view_gains")
+        t = np.ascontiguousarray(a_b, np.float32)
+        if t.shape != (self.S, self.C, 2) or not np.isfinite(t).all():
+            raise ValueError("Volume.with_view_gains: view_gains must be finite and [S, C, 2] = %s, not %s"
+                             % ((self.S, self.C, 2), t.shape))
+        self.ctx.use_current_stream()
+        h = C.c_void_p()
+        check(_lib.lib().rslf_volume_apply_view_gains(self.ctx._h, self._h, t.ctypes.data, C.byref(h)), "rslf_volume_apply_view_gains")
+        out = self._like(h)
+        out.view_gains = t.copy()
         return out
 
     def describe(self) -> RslfVolumeDesc:
@@ -1233,7 +1361,7 @@ class MultiDevice:
     def fine_to_coarse(self, epis: Sequence[np.ndarray], d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                        parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                        subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1,
-                       *, level_dilation: int = 1, derivative_channels: float = 0.0):
+                       *, equalize_views=None, level_dilation: int = 1, derivative_channels: float = 0.0):
         """FineToCoarse (constructor + run + get_results) over this object's devices (rslf_multi_fine_to_coarse_run_host):
         every level's sweep sharded by scanline.  Returns (out_map [S,V,U] f32, out_validity [S,V,U] u8, levels)."""
         require_no_subgrid(subgrid, "MultiDevice.fine_to_coarse")
@@ -1242,6 +1370,7 @@ class MultiDevice:
         require_no_consistency_gate(consistency_min_agree, "MultiDevice.fine_to_coarse")
         require_no_u_dilation(u_dilation, "MultiDevice.fine_to_coarse")
         require_no_derivative_channels(derivative_channels, "MultiDevice.fine_to_coarse")
+        require_no_equalize_views(equalize_views, "MultiDevice.fine_to_coarse")
         require_no_level_dilation(level_dilation, "MultiDevice.fine_to_coarse")
         keep, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
         out_map = np.empty((S, V, U), np.float32)
@@ -2093,6 +2222,45 @@ def derivative_channels(ctx: Context, raw_vsuc: torch.Tensor, weight: float, dty
 _derivative_channels_dense = derivative_channels   # (for the callers whose own argument has the name)
 
 
+def equalize_views(ctx: Context, raw_vsuc: torch.Tensor, mode: int = EQUALIZE_AFFINE, ref_view=None, joint=None,
+                   max_gain: float = 4.0, dtype=np.float32, inplace: bool = False) -> tuple[torch.Tensor, np.ndarray]:
+    """A dense RAW level [V,S,U] / [V,S,U,C] (float32 CUDA; f2c_input's output) equalised per view (rslf_equalize_views_dense;
+    Volume.equalized_views has the rule).  `dtype` is the light field's element type: float32 -- the cap is the level's
+    maximum; np.uint8 / np.uint16 -- the values are integer levels, the result is rounded to integers (ties to even) and
+    capped at 255 / 65535.  inplace: the tensor itself is equalised (it must be contiguous) and returned.  Returns
+    (the level, view_gains [S, C, 2])."""
+    m = _equalize_mode(mode, "equalize_views")
+    if m == 0:
+        raise ValueError("equalize_views: equalize_views %r is not EQUALIZE_GAIN or EQUALIZE_AFFINE" % (mode,))
+    dt = field_dtype(dtype)
+    if not raw_vsuc.is_cuda or raw_vsuc.dtype != torch.float32:
+        raise ValueError("equalize_views needs a float32 CUDA tensor")
+    if raw_vsuc.dim() not in (3, 4) or (raw_vsuc.dim() == 4 and raw_vsuc.shape[3] not in (1, 3)):
+        raise ValueError("equalize_views: a level [V,S,U], [V,S,U,1] or [V,S,U,3], not %s" % (tuple(raw_vsuc.shape),))
+    V, S, U = raw_vsuc.shape[:3]
+    C_ = raw_vsuc.shape[3] if raw_vsuc.dim() == 4 else 1
+    ref, j, g = _equalize_args(S, C_, ref_view, joint, max_gain, "equalize_views")
+    if inplace:
+        if not raw_vsuc.is_contiguous():
+            raise ValueError("equalize_views: inplace needs a contiguous tensor")
+        t = raw_vsuc
+    else:
+        t = raw_vsuc.clone(memory_format=torch.contiguous_format)
+    hi = 0.0
+    ctx.use_current_stream()
+    if dt == np.float32:
+        mx = C.c_float()
+        check(_lib.lib().rslf_device_max_f32(ctx._h, _ptr(t), t.numel(), C.byref(mx)), "rslf_device_max_f32")
+        hi = float(mx.value)
+    a_b = np.zeros((S, C_, 2), np.float32)
+    check(_lib.lib().rslf_equalize_views_dense(ctx._h, _ptr(t), _ELEM[np.dtype(dt)], V, S, U, C_, hi, m, ref, j, g, a_b.ctypes.data),
+          "rslf_equalize_views_dense")
+    return t, a_b
+
+
+_equalize_views_dense = equalize_views   # (for the callers whose own argument has the name)
+
+
 def f2c_line_mode(parameters: Depth1DParameters, line_confidence_mode: int | None, who: str) -> int:
     """The line mode of a pyramid.  None: no line confidence, and parameters that ask for one are refused (the paths that
     do not carry C_l).  0 / 1 / 2: that mode on every level; parameters.par_line_confidence_mode must be 0 or equal to it."""
@@ -2270,6 +2438,24 @@ class KeptFineToCoarse:
         check(_lib.lib().rslf_f2c_run_level_dilation(self._h, C.byref(factor), C.byref(kind)), "rslf_f2c_run_level_dilation")
         # (factor, kind) of the level dilation the sweeps ran with; (1, DILATE_CUBIC): none.  Every plane is on the level's grid
         self.level_dilation = (int(factor.value), int(kind.value))
+        mode, ref = C.c_int(), C.c_int()
+        check(_lib.lib().rslf_f2c_run_equalize(self._h, C.byref(mode), C.byref(ref), None), "rslf_f2c_run_equalize")
+        # the per-view equalisation the finest level's upload went through: (mode, ref_view), None: the run was made without it
+        self.equalize_views = (int(mode.value), int(ref.value)) if mode.value else None
+        self._view_gains = None
+
+    @property
+    def view_gains(self):
+        """The [S, C, 2] float32 (a, b) the run's equalisation applied, C the field's own channel count; None: the run was
+        made without it."""
+        if self.equalize_views is None:
+            return None
+        if self._view_gains is None:
+            C_ = int(_lib.lib().rslf_f2c_run_view_gains_channels(self._h))   # (the run says how many floats it writes)
+            a_b = np.zeros((self.S, C_, 2), np.float32)
+            check(_lib.lib().rslf_f2c_run_equalize(self._h, None, None, a_b.ctypes.data), "rslf_f2c_run_equalize")
+            self._view_gains = a_b
+        return self._view_gains
 
     def describe(self) -> "_lib.RslfF2cRunDesc":
         d = _lib.RslfF2cRunDesc()
@@ -2469,7 +2655,8 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                             validity_rule: int = F2C_VALID_COMPAT, keep_volumes: bool = True, subgrid: bool = False, peaks=None,
                             uniqueness_ratio: float | None = None, propagation_ratio: float | None = None,
                             consistency_min_agree: int | None = None, consistency_tol: float | None = None, consistency_radius: int = 0,
-                            u_dilation: int = 1, *, level_dilation: int = 1, level_dilation_kind=DILATE_CUBIC,
+                            u_dilation: int = 1, *, equalize_views=None, equalize_ref_view=None, equalize_joint=None,
+                            equalize_max_gain: float = 4.0, level_dilation: int = 1, level_dilation_kind=DILATE_CUBIC,
                             derivative_channels: float = 0.0):
     """rslf_fine_to_coarse_run_host_lc / _u16_lc: the whole pyramid inside the library, host EPIs in (a list of V arrays
     [S,U] / [S,U,3]; float32, uint8 or uint16), host planes out.  Returns dict(out_map, out_valid [S,V,U], n_levels, stats)
@@ -2504,8 +2691,14 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     2..8, with level_dilation_kind a DILATE_*; rslf_fine_to_coarse_run_host_dl, rslf_f2c_run_host_dl): every level's SWEEP
     runs on the level's volume dilated along u with slope factor U_l / U_0 * factor, and its planes come back to the level's
     own grid before anything reads them: every result has the shapes it always had.  The level chain is untouched.  Not
-    together with a line mode.  KeptFineToCoarse.level_dilation reads it back."""
+    together with a line mode.  KeptFineToCoarse.level_dilation reads it back.
+    equalize_views (not in the reference's code, the remedy its report names for global changes of illumination; None: off,
+    today's call; else EQUALIZE_GAIN or EQUALIZE_AFFINE; rslf_fine_to_coarse_run_host_eq, rslf_f2c_run_host_eq): the finest
+    level's upload is equalised per view on the device (Volume.equalized_views has the rule and equalize_ref_view,
+    equalize_joint, equalize_max_gain), before the derivative channels, and the pyramid runs on it bit for bit as on the
+    equalised field.  KeptFineToCoarse.equalize_views and .view_gains read it back."""
     require_no_u_dilation(u_dilation, "fine_to_coarse_run_host")
+    eq = _equalize_mode(equalize_views, "fine_to_coarse_run_host")
     dl, dl_kind = _level_dilation(level_dilation, level_dilation_kind, "fine_to_coarse_run_host")
     require_no_line_confidence_level_dilated(line_mode, dl, "fine_to_coarse_run_host")
     dv = _derivative_weight(derivative_channels, "fine_to_coarse_run_host")
@@ -2543,6 +2736,8 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
     keep_alive, ptrs, dt, V, S, U, C_, stride = host_epis(epis, stride=True)
     if dv and C_ != 1:
         raise ValueError("fine_to_coarse_run_host: derivative_channels=%r needs a one-channel field, not C=%d" % (derivative_channels, C_))
+    eq_args = (eq,) + (_equalize_args(S, C_, equalize_ref_view, equalize_joint, equalize_max_gain, "fine_to_coarse_run_host")
+                       if eq else (0, 0, 4.0))
     L = _lib.lib()
     if keep:
         if want_levels:
@@ -2554,7 +2749,9 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
                 int(validity_rule), 1 if keep_volumes else 0, C.byref(h), C.byref(st))
         # the family's widest entry: what is off goes in neutral (0), and the run is the narrower entry's
         more = (1 if subgrid else 0, 1 if want_peaks else 0, float(uniqueness_ratio or 0.0), gate, cs_tol, cs_radius, cs_min_agree)
-        if dl != 1:
+        if eq:
+            check(L.rslf_f2c_run_host_eq(*args, *more, dv, dl, dl_kind, *eq_args), "rslf_f2c_run_host_eq")
+        elif dl != 1:
             check(L.rslf_f2c_run_host_dl(*args, *more, dv, dl, dl_kind), "rslf_f2c_run_host_dl")
         elif dv:
             check(L.rslf_f2c_run_host_dv(*args, *more, dv), "rslf_f2c_run_host_dv")
@@ -2584,7 +2781,10 @@ def fine_to_coarse_run_host(epis, d_min: float, d_max: float, dim_d: int, epi_sc
             C.byref(nl), C.byref(st), int(line_mode), C.byref(lo) if lo is not None else None)
     ctx.use_current_stream()
     # the family's widest entry, which takes any element type
-    if dl != 1:
+    if eq:
+        check(L.rslf_fine_to_coarse_run_host_eq(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0, dv, dl, dl_kind, *eq_args),
+              "rslf_fine_to_coarse_run_host_eq")
+    elif dl != 1:
         check(L.rslf_fine_to_coarse_run_host_dl(ctx._h, ptrs, _ELEM[np.dtype(dt)], *rest, 1 if subgrid else 0, dv, dl, dl_kind),
               "rslf_fine_to_coarse_run_host_dl")
     elif dv:
@@ -2620,14 +2820,23 @@ class FineToCoarse:
     `level_dilation` / `level_dilation_kind` (not in the reference's code, its report's fourth lead; 1: off; else a factor in
     2..8 and a DILATE_*): run() sweeps every level on its volume dilated along u (Volume.dilated_u) with the slope factor
     times the factor and the level's ranges by dilate_ranges_u, and writes the columns u * factor of the sweep's planes into
-    the level's computer: the computers and every getter keep answering on the level's own grid.  Not with a line mode."""
+    the level's computer: the computers and every getter keep answering on the level's own grid.  Not with a line mode.
+
+    `equalize_views` (not in the reference's code, the remedy its report names for global changes of illumination; None:
+    off; else EQUALIZE_GAIN or EQUALIZE_AFFINE, with `equalize_ref_view`, `equalize_joint`, `equalize_max_gain` as
+    Volume.equalized_views takes them): the raw finest level is equalised per view on the device (equalize_views(), once,
+    in place, on f2c_input's output, before the derivative channels); .m_view_gains holds the [S, C, 2] coefficients."""
 
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, epi_scale_factor: float = -1.0,
                  parameters: Depth1DParameters | None = None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True,
                  ctx: Context | None = None, line_confidence_mode: int | None = None, subgrid: bool = False, peaks=None,
-                 propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1, *, level_dilation: int = 1,
+                 propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1, *, equalize_views=None,
+                 equalize_ref_view=None, equalize_joint=None, equalize_max_gain: float = 4.0, level_dilation: int = 1,
                  level_dilation_kind=DILATE_CUBIC, derivative_channels: float = 0.0):
         self.m_level_dilation, self.m_level_dilation_kind = _level_dilation(level_dilation, level_dilation_kind, "FineToCoarse")
+        # not in the reference: the finest level's upload equalised per view (K19); 0: off
+        self.m_equalize_views = _equalize_mode(equalize_views, "FineToCoarse")
+        self.m_view_gains = None
         # not in the reference: a one-channel field goes down the pyramid as (x, |dx/du|, |dx/dv|) by this weight (K17); 0: off
         self.m_derivative_channels = _derivative_weight(derivative_channels, "FineToCoarse")
         require_no_peaks(peaks, "FineToCoarse")   # (the pyramid's levels carry no peak planes)
@@ -2643,6 +2852,9 @@ class FineToCoarse:
         self.m_computers: list[Depth2DComputer] = []
         self.m_parameter_instances: list[Depth1DParameters] = []
         raw0, dt = f2c_input(epis, ctx)
+        if self.m_equalize_views:   # once, in place, on the finest level; everything below reads the equalised intensity
+            raw0, self.m_view_gains = _equalize_views_dense(ctx, raw0, self.m_equalize_views, equalize_ref_view, equalize_joint,
+                                                            equalize_max_gain, dt, inplace=True)
         if self.m_derivative_channels:   # once, on the finest level; the features go down with the intensity
             if raw0.shape[3] != 1:
                 raise ValueError("FineToCoarse: derivative_channels=%r needs a one-channel field, not C=%d"

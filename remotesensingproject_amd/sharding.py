@@ -486,8 +486,9 @@ class ShardedFineToCoarse:
     def __init__(self, epis, d_min: float, d_max: float, dim_d: int, rank: int, world: int, epi_scale_factor: float = -1.0,
                  parameters=None, max_pyr_depth: int = -1, accept_all_last_scale: bool = True, ctx=None, group=None,
                  subgrid: bool = False, peaks=None, propagation_ratio=None, consistency_min_agree=None, u_dilation: int = 1,
-                 *, level_dilation: int = 1, derivative_channels: float = 0.0):
+                 *, equalize_views=None, level_dilation: int = 1, derivative_channels: float = 0.0):
         from . import depth as rs
+        rs.require_no_equalize_views(equalize_views, "ShardedFineToCoarse")   # one device: a view's statistic spans every rank's scanlines
         rs.require_no_peaks(peaks, "ShardedFineToCoarse")
         rs.require_no_level_dilation(level_dilation, "ShardedFineToCoarse")   # one device: every chunk of every level would be dilated
         rs.require_no_u_dilation(u_dilation, "ShardedFineToCoarse")
